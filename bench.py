@@ -1,13 +1,19 @@
 """Headline benchmark: RA-LENet training-step throughput (ECG windows/s) on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W] [--config ralenet|unet|newrale]
+    python bench.py [--gpus N --steps K --warmup W] [--config ralenet|unet|newrale] [--full] [--dump-outputs DIR]
 
 N > 1 runs one process per GPU over RCCL: either the caller starts the ranks (`python -m torch.distributed.run
 --nproc-per-node N ... bench.py --gpus N`: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* come from the environment), or
 bench.py starts them itself when WORLD_SIZE is not set (child processes, never exec; rank 0's JSON line is relayed).
 
 One "step" = zero_grad -> forward -> mse/SNR/RMSE -> backward -> (all-reduce) -> Adam on one batch of synthetic windows
-already resident in HBM.  Prints ONE JSON line (rank 0).  Workloads (`--config`):
+already resident in HBM.  Prints ONE JSON line (rank 0).  A plain run sets up, runs W warm-up steps, times exactly K
+steps and prints the headline.  `--full` adds everything else the line can carry, each measured after the timed region:
+the serialised roofline leg, the strict-fp32 leg, inference, the leads = 2 shape, the conv-stage roofline, the CPU
+baseline, BASELINE config 3's shape at --gpus 8 and the exact U-Net data-parallel mode at N > 1.  `--dump-outputs DIR`
+writes what the last timed step returned (prediction, loss, SNR, RMSE) and the parameters it left as DIR/<name>.npy;
+inputs and initial weights are seeded, so two builds given the same arguments can be compared output for output.
+Workloads (`--config`):
   ralenet (default)  BASELINE config 2 / 3: RA-LENet "full", 1 lead x 512 samples, 2048 windows per GPU
   unet               the conv U-Net of the same path (UNet.py), 2 leads x 512 samples, 2048 windows per GPU
   newrale            BASELINE config 4: 12 leads x 1024 samples through the transfer-learning adapter, 256 windows per GPU
@@ -342,7 +348,7 @@ def launcher_dry_run(a):
         print(json.dumps({"dry_run": True, "n_gpus": world, "local_rank": int(os.environ.get("LOCAL_RANK", "0")),
                           "rank_sum": t.item(), "steps": a.steps, "warmup": a.warmup,
                           "batch_per_gpu": B, "global_batch": G, "config3_leg": config3_batch(a, world), "collective": facts,
-                          "unet_dp": unet_dp_modes(world) if a.config == "unet" else None}))
+                          "unet_dp": unet_dp_modes(world) if a.full and a.config == "unet" else None}))
     if world > 1:
         dist.destroy_process_group()
 
@@ -362,9 +368,9 @@ def batch_plan(a, world):
 
 def config3_batch(a, world):
     """BASELINE config 3 is RA-LENet at global batch 8192 on 8 GPUs (8 x 1024 windows; SURVEY 8d 'C2').  The headline line
-    keeps 2048 windows per GPU at every N (weak scaling, so that the driver's per-N values are comparable); at --gpus 8 the
-    same process ALSO times config 3's own shape and reports it as `config3` - per-GPU batch of that leg, or None."""
-    if a.config == "ralenet" and world == 8 and not a.batch and not a.global_batch and not a.leads and not a.L:
+    keeps 2048 windows per GPU at every N (weak scaling, so that the driver's per-N values are comparable); at --gpus 8 with
+    --full the same process ALSO times config 3's own shape and reports it as `config3` - per-GPU batch of that leg, or None."""
+    if a.full and a.config == "ralenet" and world == 8 and not a.batch and not a.global_batch and not a.leads and not a.L:
         return 1024
     return None
 
@@ -439,14 +445,40 @@ def build_workload(a, dev, rank):
             "L": L, "text": text + " (fwd+mse/SNR/RMSE+bwd+Adam), N(0,1) inputs seed 2023, random-init weights"}
 
 
+DUMP_BYTES = 64 << 20        # --dump-outputs: at most this much in all, split evenly over the arrays
+
+
+def dump_outputs(d, out, model):
+    """Write the tensors the step returned (pred, loss, snr, rmse) and the flat parameters after it as d/<name>.npy, float32
+    (float64 where the path computed float64).  An array over its share of DUMP_BYTES is replaced by a fixed, seeded sample
+    of its flattened elements, in index order."""
+    import numpy as np
+    import torch
+    arrays = {k: v for k, v in out.items() if torch.is_tensor(v)}
+    arrays["params"] = torch.cat([p.detach().reshape(-1) for p in model.parameters()])
+    os.makedirs(d, exist_ok=True)
+    for k, t in arrays.items():
+        v = t.detach().cpu().numpy()
+        v = v.astype(np.float64 if v.dtype == np.float64 else np.float32)
+        cap = DUMP_BYTES // len(arrays) // v.itemsize
+        if v.size > cap:
+            v = v.reshape(-1)[np.sort(np.random.default_rng(0).choice(v.size, cap, replace=False))]
+        np.save(os.path.join(d, k + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--min-seconds", type=float, default=2.0,
-                    help="the timed region repeats the --steps block until it lasts at least this long (whole blocks; "
-                         "`steps` in the line = steps actually timed, `steps_requested` = --steps; 0 = exactly --steps)")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="repeat the --steps block until the timed region lasts at least this long (whole blocks; "
+                         "`steps` in the line = steps actually timed, `steps_requested` = --steps; default 0 = exactly --steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline (roofline, fp32, inference, leads = 2, conv stages, CPU "
+                         "baseline, config 3, U-Net exact DP mode); the --no-* options below trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step and the parameters after it as DIR/<name>.npy (rank 0)")
     ap.add_argument("--config", default="ralenet", choices=("ralenet", "unet", "newrale"))
     ap.add_argument("--batch", type=int, default=0, help="windows per GPU (default: the config's stated batch)")
     ap.add_argument("--global-batch", type=int, default=0,
@@ -455,10 +487,11 @@ def main():
     ap.add_argument("--L", type=int, default=0)
     ap.add_argument("--variant", default="full")
     ap.add_argument("--kind", default="attn_bwd", help="kernel kind timed for the roofline object")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline and the other N = 1 extras")
-    ap.add_argument("--no-infer", action="store_true", help="skip the inference-forward leg")
-    ap.add_argument("--no-fp32", action="store_true", help="skip the strict-fp32 leg (profile collection: one arithmetic per trace)")
-    ap.add_argument("--kinds", action="store_true", help="print a per-kernel-kind time table to stderr (3 steps each)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline and the other N = 1 extras")
+    ap.add_argument("--no-infer", action="store_true", help="--full: skip the inference-forward leg")
+    ap.add_argument("--no-fp32", action="store_true", help="--full: skip the strict-fp32 leg (profile collection: one arithmetic per trace)")
+    ap.add_argument("--kinds", action="store_true", help="run the serialised roofline leg and print a per-kernel-kind time table "
+                                                         "to stderr (3 steps each)")
     ap.add_argument("--opt", action="append", default=[], help="library switch key=value (ral_global_option; diagnostics only, repeatable)")
     ap.add_argument("--dry-run-launcher", action="store_true", help="CPU/gloo rendezvous only: tests the process launcher")
     # test hooks (tests/test_gpu_dp_procs.py, tests/test_bench_cpu.py): never part of a measurement
@@ -517,9 +550,9 @@ def main():
         step()
     sync()
     lib = _lib.lib()
-    # A timed region of --steps steps is 0.26 s at the default 20: too short for anything sampling the GPU from outside (the
-    # driver's 5 s SMI samples never land in it).  One untimed calibration block of --steps steps sizes the region: it repeats
-    # the block until >= --min-seconds, with no synchronisation between blocks; every rank uses the slowest rank's estimate.
+    # --min-seconds S (off by default: the region is exactly --steps steps): one untimed calibration block of --steps steps
+    # sizes the region for something sampling the GPU from outside (5 s SMI samples never land in a 0.26 s region); it
+    # repeats the block until >= S, with no synchronisation between blocks; every rank uses the slowest rank's estimate.
     steps_req, blocks = a.steps, 1
     if a.min_seconds > 0 and a.steps > 0:
         t0 = time.perf_counter()
@@ -543,12 +576,15 @@ def main():
     median_ms = per_step[len(per_step) // 2] if per_step else None
     n_timed, a.steps = a.steps, steps_req          # (the legs below size themselves from --steps)
     blocks_calibrated = a.min_seconds > 0 and steps_req > 0
+    if a.dump_outputs and rank == 0:               # before any later leg moves the parameters or reuses the buffers
+        dump_outputs(a.dump_outputs, out, model)
 
-    # roofline leg: the same step with the kernels serialised (one lane, no side stream), so that the hipEvent
-    # pair around each launch of the selected kernel measures that kernel alone, not its share of a busy GPU
+    # roofline leg (--full, --kinds): the same step with the kernels serialised (one lane, no side stream), so that the
+    # hipEvent pair around each launch of the selected kernel measures that kernel alone, not its share of a busy GPU
     rl_steps = max(3, a.steps // 4)
     ms, cnt = C.c_double(), C.c_int64()
-    if inner is not None:
+    roofline_leg = inner is not None and (a.full or a.kinds)
+    if roofline_leg:
         h = inner.eng.h
         _lib.check(lib.ral_set_option(h, b"lanes", 1))
         _lib.check(lib.ral_set_option(h, b"side_stream", 0))
@@ -602,7 +638,7 @@ def main():
     # strict-fp32 leg: the same step with every product on the fp32 MFMA (f16_split = 0: no fp16-pair operand anywhere),
     # timed right after the headline region on the same box, so that the line carries both arithmetics
     fp32_leg = None
-    if inner is not None and not a.no_fp32:
+    if a.full and inner is not None and not a.no_fp32:
         h = inner.eng.h
         _lib.check(lib.ral_set_option(h, b"f16_split", 0))
         n32 = max(5, min(10, a.steps))
@@ -623,7 +659,7 @@ def main():
         step(); sync()
 
     infer = infer_graph = None
-    if not a.no_infer and a.config != "newrale":
+    if a.full and not a.no_infer and a.config != "newrale":
         # BASELINE config 5's kernel path: eval-mode forward (BatchNorm running statistics), eager and hipGraph-captured
         from ecg_denoise_amd.infer import GraphedForward
         model.eval()
@@ -653,7 +689,7 @@ def main():
 
     # BASELINE config 3's own shape (global batch 8192 = 8 x 1024) next to the weak-scaling headline, in the same job
     config3 = None
-    b3 = config3_batch(a, world) or (a.test_config3_batch if world > 1 else 0)
+    b3 = config3_batch(a, world) or (a.test_config3_batch if a.full and world > 1 else 0)
     if b3:
         a.batch_override = b3
         W3 = build_workload(a, dev, rank)
@@ -675,7 +711,7 @@ def main():
 
     # U-Net at N > 1: the exact mode (global-batch statistics, 21 collectives per step) next to the per-rank headline
     unet_dp = None
-    if a.config == "unet" and world > 1:
+    if a.full and a.config == "unet" and world > 1:
         unet_dp = unet_dp_modes(world)
         unet_dp["per_rank_bn"].update({"value": round(B * world * n_timed / dt, 1), "unit": "windows/s", "ms_per_step": round(dt / n_timed * 1e3, 3),
                                        "collectives_counted": trainer.collectives_last_step})
@@ -721,9 +757,9 @@ def main():
             res["config3"] = config3
         if unet_dp is not None:
             res["unet_dp"] = unet_dp
-        if inner is not None:
+        if roofline_leg:
             res["roofline"] = roofline_object(a.kind, a.config, Lk, Bk, ms.value, int(cnt.value), rl_steps, attn_ms, n_timed, dt)
-        else:
+        elif inner is None:
             # U-Net: every kernel of the step is an HBM-bound conv stage; stage-granular bytes of SURVEY 8d per window
             # (forward with batch statistics 147 KB + backward 200 KB at 2 leads x 512 samples) over the whole step
             by = 347e3 * (W["leads"] * L) / 1024.0
@@ -736,7 +772,7 @@ def main():
         if infer is not None:
             res["infer_windows_per_s"] = round(infer, 1)
             res["infer_hipgraph_windows_per_s"] = round(infer_graph, 1)
-        if world == 1 and not a.no_cpu and a.config == "ralenet":
+        if a.full and world == 1 and not a.no_cpu and a.config == "ralenet":
             # the reference-parity shape next to the single-lead headline ("also report leads = 2")
             try:
                 del model, trainer, W

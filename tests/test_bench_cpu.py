@@ -33,7 +33,7 @@ def test_self_launch_two_ranks_relays_rank0_line():
 
 def test_global_batch_is_split_over_the_ranks_and_config3_runs_at_eight():
     """`--global-batch G`: G / N windows per GPU (strong scaling); BASELINE config 3 (8192 = 8 x 1024) is a second leg of the
-    default --gpus 8 run, next to the 2048-per-GPU weak-scaling headline"""
+    --gpus 8 --full run, next to the 2048-per-GPU weak-scaling headline (a plain run times the headline only)"""
     r = _run(["--gpus", "2", "--global-batch", "8192", "--dry-run-launcher"])
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -41,6 +41,9 @@ def test_global_batch_is_split_over_the_ranks_and_config3_runs_at_eight():
     r = _run(["--gpus", "2", "--global-batch", "8191", "--dry-run-launcher"])
     assert r.returncode != 0
     r = _run(["--gpus", "8", "--dry-run-launcher"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])["config3_leg"] is None
+    r = _run(["--gpus", "8", "--full", "--dry-run-launcher"])
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert (d["n_gpus"], d["batch_per_gpu"], d["global_batch"], d["config3_leg"]) == (8, 2048, 16384, 1024)
@@ -71,9 +74,9 @@ def test_no_launch_when_the_ranks_were_started_for_us():
 
 
 def test_unet_line_names_both_data_parallel_modes():
-    """`--config unet --gpus N`: per-rank BatchNorm statistics (1 collective per step) are the throughput headline, the exact
-    mode (21 collectives) is timed next to it, and the measured deviation of the headline mode is quoted in the line"""
-    r = _run(["--gpus", "2", "--config", "unet", "--dry-run-launcher"])
+    """`--config unet --gpus N --full`: per-rank BatchNorm statistics (1 collective per step) are the throughput headline, the
+    exact mode (21 collectives) is timed next to it, and the measured deviation of the headline mode is quoted in the line"""
+    r = _run(["--gpus", "2", "--config", "unet", "--full", "--dry-run-launcher"])
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])["unet_dp"]
     assert d["headline_mode"] == "per_rank_bn"
@@ -102,3 +105,31 @@ def test_roofline_object_carries_the_pipe_and_busy_fractions():
     blk = r["attn_block"]
     want = (bench.kind_work("attn_fwd", 512, 2048) + bench.kind_work("attn_bwd", 512, 2048)) / ((1.746 + 3.357) * 1e-3) / 1e12 / 157.3
     assert abs(r["attn_block_frac"] - want) < 1e-3 and blk["fwd_frac"] < blk["bwd_frac"]
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path, monkeypatch):
+    """`--dump-outputs DIR`: every tensor the step returned plus the flat parameters as DIR/<name>.npy, float64 kept, the rest
+    float32; an array over its share of the budget becomes the same seeded sample of its elements on every run"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1 << 20)
+
+    class Model:
+        def parameters(self):
+            return [torch.ones(3, 4), torch.full((5,), 2.0)]
+    out = {"loss": torch.tensor([0.25], dtype=torch.float64), "pred": torch.arange(1 << 20, dtype=torch.float32).reshape(256, 1, -1),
+           "snr": torch.arange(8, dtype=torch.float16), "loss_is_global": True}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), out, Model())
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["loss.npy", "params.npy", "pred.npy", "snr.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= (1 << 20) + 4 * 128
+    get = lambda d, k: np.load(tmp_path / d / (k + ".npy"))
+    assert get("a", "loss").dtype == np.float64 and get("a", "loss").tolist() == [0.25]
+    assert get("a", "snr").dtype == np.float32 and get("a", "snr").tolist() == list(range(8))
+    np.testing.assert_array_equal(get("a", "params"), [1.0] * 12 + [2.0] * 5)
+    p = get("a", "pred")
+    assert p.dtype == np.float32 and p.size == (1 << 20) // 4 // 4 and np.all(np.diff(p) > 0)   # sampled, in index order
+    np.testing.assert_array_equal(p, get("b", "pred"))

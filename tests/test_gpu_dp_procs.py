@@ -110,7 +110,7 @@ def test_bench_global_batch_two_ranks_on_one_gpu():
 
 def _bench(extra):
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--no-cpu", "--test-backend", "gloo", "--test-share-gpu"] + extra, capture_output=True, text=True,
+                        "--full", "--no-cpu", "--test-backend", "gloo", "--test-share-gpu"] + extra, capture_output=True, text=True,
                        timeout=900)
     assert p.returncode == 0, p.stdout + p.stderr
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

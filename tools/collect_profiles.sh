@@ -33,9 +33,9 @@ RAL_TOOL_OPTIONS=attn_f16=0 python3 tools/attn_bench.py > $O/attn_bench_fp32.log
 python3 tools/diag/step_timeline_events.py $O/step_timeline_events.txt > /dev/null 2>&1
 RAL_LANES=1 RAL_NO_SIDE_STREAM=1 python3 tools/diag/step_timeline_events.py $O/step_timeline_events_serial.txt > /dev/null 2>&1
 [ -x tools/diag/valu_probe ] && ./tools/diag/valu_probe > $O/valu_probe.log 2>&1
-python3 bench.py --steps 50 --warmup 5 --kinds > $O/bench.json 2> $O/bench_kinds.log
-python3 bench.py --config newrale --no-cpu > $O/bench_newrale.json 2> $O/bench_newrale.err
-python3 bench.py --config unet --no-cpu > $O/bench_unet.json 2> $O/bench_unet.err
+python3 bench.py --full --min-seconds 2 --steps 50 --warmup 5 --kinds > $O/bench.json 2> $O/bench_kinds.log
+python3 bench.py --full --min-seconds 2 --config newrale --no-cpu > $O/bench_newrale.json 2> $O/bench_newrale.err
+python3 bench.py --full --min-seconds 2 --config unet --no-cpu > $O/bench_unet.json 2> $O/bench_unet.err
 python3 tools/config_bench.py > $O/config_bench.log 2>&1
 python3 tools/baselines_bench.py > $O/baselines_bench.log 2>&1
 # U-Net TRAIN step: kernel trace (timeline of one step) and statistics
