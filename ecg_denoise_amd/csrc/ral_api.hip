@@ -1520,6 +1520,28 @@ int ral_stream_stitch(const float* y, const float* stats, int64_t R, int64_t T, 
   return 0;
 }
 
+int ral_newrale_stream_front(const float* rec, int64_t R, int64_t T, int L, int hop, int64_t w0, int nw,
+                             const float* adapter_params, float* inner_x, float* stats, ral_stream s) {
+  if (!rec || !adapter_params || !inner_x || !stats) return fail("newrale_stream_front: null pointer");
+  if (launch_newrale_front(rec, (long long)R, (long long)T, L, hop, (long long)w0, nw, adapter_params, inner_x, stats, (hipStream_t)s))
+    return fail("newrale_stream_front: need R >= 1, T >= L, L a multiple of 16 in [16, 1024], 1 <= hop <= L with L - hop even, "
+                "a window range inside the records (R=%lld T=%lld L=%d hop=%d w0=%lld nw=%d)", (long long)R, (long long)T, L, hop,
+                (long long)w0, nw);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int ral_newrale_stream_back(const float* inner_y, const float* stats, const float* adapter_params, int64_t R, int64_t T, int L,
+                            int hop, int64_t w0, int nw, float* out, ral_stream s) {
+  if (!inner_y || !stats || !adapter_params || !out) return fail("newrale_stream_back: null pointer");
+  if (launch_newrale_back(inner_y, stats, adapter_params, (long long)R, (long long)T, L, hop, (long long)w0, nw, out, (hipStream_t)s))
+    return fail("newrale_stream_back: need R >= 1, T >= L, L a multiple of 16 in [16, 1024], 1 <= hop <= L with L - hop even, "
+                "a window range inside the records (R=%lld T=%lld L=%d hop=%d w0=%lld nw=%d)", (long long)R, (long long)T, L, hop,
+                (long long)w0, nw);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 int ral_wavelet_denoise(const float* x, float* y, int64_t rows, int L, float threshold, ral_stream s) {
   if (!x || !y) return fail("wavelet_denoise: null pointer");
   if (!(threshold >= 0.f)) return fail("wavelet_denoise: the threshold factor must be non-negative (got %g)", (double)threshold);

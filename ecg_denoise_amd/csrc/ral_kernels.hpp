@@ -74,6 +74,11 @@ int launch_stream_windows(const float* rec, long long R, long long T, int leads,
                           float* win, float* stats, hipStream_t s);
 int launch_stream_stitch(const float* y, const float* stats, long long R, long long T, int leads, int L, int hop, float* out,
                          hipStream_t s);
+// the 12-lead adapter around the inner model of a streamed record group (ral_newrale_stream_front / _back); -1: bad arguments
+int launch_newrale_front(const float* rec, long long R, long long T, int L, int hop, long long w0, int nw, const float* prm,
+                         float* inner, float* stats, hipStream_t s);
+int launch_newrale_back(const float* iy, const float* stats, const float* prm, long long R, long long T, int L, int hop,
+                        long long w0, int nw, float* out, hipStream_t s);
 int launch_conv13_fwd(const float* x, const float* w, const float* b, float* y, int B, int cin, int cout, int L,
                       int lrelu, hipStream_t s);
 int launch_conv13_bwd(const float* x, const float* y, const float* dy, const float* w, float* gw, float* gb,

@@ -590,6 +590,33 @@ RAL_DEV void stream_geom(long long T, int L, int hop, int& n_reg, int& n) {
   n = n_reg + (((T - L) % hop) != 0 ? 1 : 0);
 }
 
+// The stitch rule: which window keeps which samples of its record.  h = (L - hop) / 2; window 0 keeps [0, hop + h), window k
+// [k hop + h, (k + 1) hop + h), the last window [last_begin, T) (a single window keeps the whole record).  The kept ranges are
+// disjoint and cover [0, T): k_stream_stitch maps a sample to its window (stream_owner), k_newrale_back a window to its samples
+// (stream_kept).
+struct StreamKeep {
+  int n_reg, n, h;
+  long long last_begin;   // first sample the last window keeps
+};
+RAL_DEV StreamKeep stream_keep(long long T, int L, int hop) {
+  StreamKeep s;
+  stream_geom(T, L, hop, s.n_reg, s.n);
+  s.h = (L - hop) >> 1;
+  s.last_begin = s.n > 1 ? (long long)(s.n - 2) * hop + L - s.h : 0;
+  return s;
+}
+RAL_DEV long long stream_start(const StreamKeep& s, int k, long long T, int L, int hop) {   // first sample of window k
+  return k < s.n_reg ? (long long)k * hop : T - L;
+}
+RAL_DEV int stream_owner(const StreamKeep& s, long long t, int hop) {
+  if (s.n == 1 || t >= s.last_begin) return s.n - 1;
+  return t < s.h ? 0 : (int)((t - s.h) / hop);
+}
+RAL_DEV void stream_kept(const StreamKeep& s, int k, long long T, int hop, long long& b, long long& e) {
+  b = k == 0 ? 0 : (k == s.n - 1 ? s.last_begin : (long long)k * hop + s.h);
+  e = k == s.n - 1 ? T : (long long)(k + 1) * hop + s.h;
+}
+
 __global__ __launch_bounds__(64) void k_stream_windows(const float* __restrict__ rec, long long T, int leads, int L, int hop,
                                                        long long w0, float* __restrict__ win, float* __restrict__ stats) {
   int n_reg, n;
@@ -615,19 +642,15 @@ __global__ __launch_bounds__(64) void k_stream_windows(const float* __restrict__
 
 __global__ __launch_bounds__(256) void k_stream_stitch(const float* __restrict__ y, const float* __restrict__ stats, long long R,
                                                        long long T, int leads, int L, int hop, float* __restrict__ out) {
-  int n_reg, n;
-  stream_geom(T, L, hop, n_reg, n);
-  const int h = (L - hop) >> 1;
-  const long long last_begin = n > 1 ? (long long)(n - 2) * hop + L - h : 0;   // first sample the last window keeps
+  const StreamKeep sk = stream_keep(T, L, hop);
   const long long total = R * leads * T;
   for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
     const long long rc = e / T, t = e - rc * T;
     const long long r = rc / leads;
     const int c = (int)(rc - r * leads);
-    int k; long long off;
-    if (n == 1 || t >= last_begin) { k = n - 1; off = t - (k < n_reg ? (long long)k * hop : T - L); }
-    else { k = t < h ? 0 : (int)((t - h) / hop); off = t - (long long)k * hop; }
-    const long long gw = r * n + k;
+    const int k = stream_owner(sk, t, hop);
+    const long long off = t - stream_start(sk, k, T, L, hop);
+    const long long gw = r * sk.n + k;
     const float mean = stats[(gw * leads + c) * 2], sd = stats[(gw * leads + c) * 2 + 1];
     out[e] = fmaf(y[(gw * leads + c) * L + off], sd, mean);
   }
@@ -648,5 +671,194 @@ int launch_stream_stitch(const float* y, const float* stats, long long R, long l
   const long long total = R * leads * T;
   const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
   k_stream_stitch<<<grid, 256, 0, s>>>(y, stats, R, T, leads, L, hop, out);
+  return 0;
+}
+
+// =================================================================================
+// Record streaming through the 12-lead adapter (NewRALE, reference model/ralenet_12leads.py:698-709): the steps around the
+// inner RA-LENet as two kernels.  k_newrale_front: window gather + per-lead z-score (k_stream_windows' arithmetic) + conv1
+// (12 -> 6) + conv2 (6 -> 2) -> the inner model's input (nw, 2, L).  k_newrale_back: conv3 (2 -> 6) + conv4 (6 -> 12) +
+// de-normalisation, written straight into the record for the samples the window keeps (k_stream_stitch's rule).
+// One workgroup per window, the whole window staged in LDS with a 6-sample zero halo on each row (the Conv1d padding of
+// every adapter conv): at L = 1024 the front kernel holds 12 + 6 rows of 1036 floats (75 KB, two workgroups per CU), the
+// back kernel 2 + 6 rows (33 KB).  Every thread computes 4 consecutive samples of every output channel from a 16-sample
+// register window per input row; the weights are wave-uniform loads from the parameter buffer.  The sums run in
+// k_conv13_fwd's order (bias, then input channel, then tap), so the results equal the unfused launches.
+// =================================================================================
+#define NR_LEADS 12
+#define NR_MID 6
+#define NR_PT 4   // consecutive output samples per thread
+// offsets in the adapter's flat parameter buffer (NewRALE.SHAPES, every tensor padded to a multiple of 4 floats)
+#define NR_C1W 0
+#define NR_C1B 936
+#define NR_C2W 944
+#define NR_C2B 1100
+#define NR_C3W 1104
+#define NR_C3B 1260
+#define NR_C4W 1268
+#define NR_C4B 2204
+
+// acc[co][p] = b[co] + sum_ci sum_k w[(co CIN + ci) 13 + k] * xs[ci LP + l0 + p + k]: output samples l0 .. l0 + 3 of a
+// Conv1d(CIN, COUT, k13, p6) whose input rows (stride LP) carry a 6-sample halo in front (l0 % 4 == 0, LP % 4 == 0)
+template <int CIN, int COUT>
+RAL_DEV void conv13_tile(const float* __restrict__ xs, int LP, int l0, const float* __restrict__ w, const float* __restrict__ b,
+                         float (&acc)[COUT][NR_PT]) {
+#pragma unroll
+  for (int co = 0; co < COUT; ++co)
+#pragma unroll
+    for (int p = 0; p < NR_PT; ++p) acc[co][p] = b[co];
+  for (int ci = 0; ci < CIN; ++ci) {
+    float xr[NR_PT + 12];
+    const float4* xv = reinterpret_cast<const float4*>(xs + ci * LP + l0);
+#pragma unroll
+    for (int j = 0; j < (NR_PT + 12) / 4; ++j) {
+      const float4 v = xv[j];
+      xr[4 * j] = v.x; xr[4 * j + 1] = v.y; xr[4 * j + 2] = v.z; xr[4 * j + 3] = v.w;
+    }
+#pragma unroll
+    for (int co = 0; co < COUT; ++co)
+#pragma unroll
+      for (int k = 0; k < K13; ++k) {
+        const float wk = w[(co * CIN + ci) * K13 + k];
+#pragma unroll
+        for (int p = 0; p < NR_PT; ++p) acc[co][p] = fmaf(wk, xr[p + k], acc[co][p]);
+      }
+  }
+}
+
+RAL_DEV float lrelu001(float v) { return v > 0.f ? v : 0.01f * v; }
+
+// zero the halo columns [0, 6) and [L + 6, L + 12) of `rows` rows of stride L + 12 (the window loops write the interiors only)
+RAL_DEV void zero_halos(float* xs, int rows, int L) {
+  for (int i = threadIdx.x; i < rows * 12; i += blockDim.x) {
+    const int row = i / 12, j = i - row * 12;
+    xs[row * (L + 12) + (j < 6 ? j : L + j)] = 0.f;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_newrale_front(const float* __restrict__ rec, long long T, int L, int hop, long long w0,
+                                                       int nw, const float* __restrict__ prm, float* __restrict__ inner,
+                                                       float* __restrict__ stats) {
+  extern __shared__ float4 smem4[];
+  const int LP = L + 12;
+  float* xs = reinterpret_cast<float*>(smem4);   // 12 x LP: the window, z-scored in place
+  float* a1 = xs + NR_LEADS * LP;                // 6 x LP: conv1's output
+  zero_halos(xs, NR_LEADS + NR_MID, L);
+  const StreamKeep sk = stream_keep(T, L, hop);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int i = blockIdx.x; i < nw; i += gridDim.x) {
+    const long long gw = w0 + i, r = gw / sk.n;
+    const int k = (int)(gw - r * sk.n);
+    const float* src = rec + r * NR_LEADS * T + stream_start(sk, k, T, L, hop);
+    __syncthreads();   // (the previous window's readers are done; the halos are written)
+    for (int e = threadIdx.x; e < NR_LEADS * L; e += blockDim.x) {
+      const int c = e / L, l = e - c * L;
+      xs[c * LP + 6 + l] = src[c * T + l];
+    }
+    __syncthreads();
+    // z-score, one wave per lead: k_stream_windows' sums in its order (population std, floor 1e-6)
+    for (int c = wave; c < NR_LEADS; c += blockDim.x >> 6) {
+      float* row = xs + c * LP + 6;
+      float sum = 0.f;
+      for (int l = lane; l < L; l += 64) sum += row[l];
+      const float mean = group_sum<64>(sum) / (float)L;
+      float ss = 0.f;
+      for (int l = lane; l < L; l += 64) { const float d = row[l] - mean; ss = fmaf(d, d, ss); }
+      const float sd = fmaxf(sqrtf(group_sum<64>(ss) / (float)L), 1e-6f);
+      const float inv = 1.0f / sd;
+      for (int l = lane; l < L; l += 64) row[l] = (row[l] - mean) * inv;
+      if (lane == 0) { stats[(gw * NR_LEADS + c) * 2] = mean; stats[(gw * NR_LEADS + c) * 2 + 1] = sd; }
+    }
+    __syncthreads();
+    for (int l0 = NR_PT * threadIdx.x; l0 < L; l0 += NR_PT * blockDim.x) {   // conv1 + LeakyReLU -> a1
+      float acc[NR_MID][NR_PT];
+      conv13_tile<NR_LEADS, NR_MID>(xs, LP, l0, prm + NR_C1W, prm + NR_C1B, acc);
+#pragma unroll
+      for (int co = 0; co < NR_MID; ++co)
+#pragma unroll
+        for (int p = 0; p < NR_PT; ++p) a1[co * LP + 6 + l0 + p] = lrelu001(acc[co][p]);
+    }
+    __syncthreads();
+    for (int l0 = NR_PT * threadIdx.x; l0 < L; l0 += NR_PT * blockDim.x) {   // conv2 + LeakyReLU -> inner (nw, 2, L)
+      float acc[2][NR_PT];
+      conv13_tile<NR_MID, 2>(a1, LP, l0, prm + NR_C2W, prm + NR_C2B, acc);
+#pragma unroll
+      for (int co = 0; co < 2; ++co)
+        *reinterpret_cast<float4*>(inner + ((size_t)i * 2 + co) * L + l0) =
+            make_float4(lrelu001(acc[co][0]), lrelu001(acc[co][1]), lrelu001(acc[co][2]), lrelu001(acc[co][3]));
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_newrale_back(const float* __restrict__ iy, const float* __restrict__ stats,
+                                                      const float* __restrict__ prm, long long T, int L, int hop, long long w0,
+                                                      int nw, float* __restrict__ out) {
+  extern __shared__ float4 smem4[];
+  const int LP = L + 12;
+  float* ys = reinterpret_cast<float*>(smem4);   // 2 x LP: the inner model's output
+  float* a3 = ys + 2 * LP;                       // 6 x LP: conv3's output
+  zero_halos(ys, 2 + NR_MID, L);
+  const StreamKeep sk = stream_keep(T, L, hop);
+  for (int i = blockIdx.x; i < nw; i += gridDim.x) {
+    const long long gw = w0 + i, r = gw / sk.n;
+    const int k = (int)(gw - r * sk.n);
+    const long long start = stream_start(sk, k, T, L, hop);
+    long long kb, ke;
+    stream_kept(sk, k, T, hop, kb, ke);
+    const int ob = (int)(kb - start), oe = (int)(ke - start);   // kept samples [ob, oe) of the window
+    __syncthreads();
+    for (int e = threadIdx.x; e < 2 * L; e += blockDim.x) {
+      const int c = e / L, l = e - c * L;
+      ys[c * LP + 6 + l] = iy[(size_t)i * 2 * L + e];
+    }
+    __syncthreads();
+    for (int l0 = NR_PT * threadIdx.x; l0 < L; l0 += NR_PT * blockDim.x) {   // conv3 + LeakyReLU -> a3
+      float acc[NR_MID][NR_PT];
+      conv13_tile<2, NR_MID>(ys, LP, l0, prm + NR_C3W, prm + NR_C3B, acc);
+#pragma unroll
+      for (int co = 0; co < NR_MID; ++co)
+#pragma unroll
+        for (int p = 0; p < NR_PT; ++p) a3[co * LP + 6 + l0 + p] = lrelu001(acc[co][p]);
+    }
+    __syncthreads();
+    // conv4 on the 4-sample tiles that hold kept samples; de-normalise; write the kept ones into the record
+    float* dst = out + r * NR_LEADS * T + start;
+    for (int l0 = (ob & ~(NR_PT - 1)) + NR_PT * threadIdx.x; l0 < oe; l0 += NR_PT * blockDim.x) {
+      float acc[NR_LEADS][NR_PT];
+      conv13_tile<NR_MID, NR_LEADS>(a3, LP, l0, prm + NR_C4W, prm + NR_C4B, acc);
+#pragma unroll
+      for (int c = 0; c < NR_LEADS; ++c) {
+        const float mean = stats[(gw * NR_LEADS + c) * 2], sd = stats[(gw * NR_LEADS + c) * 2 + 1];
+#pragma unroll
+        for (int p = 0; p < NR_PT; ++p) {
+          const int l = l0 + p;
+          if (l >= ob && l < oe) dst[c * T + l] = fmaf(acc[c][p], sd, mean);
+        }
+      }
+    }
+  }
+}
+
+static bool newrale_stream_args_ok(long long R, long long T, int L, int hop, long long w0, int nw) {
+  if (R < 1 || L < 16 || L % 16 != 0 || L > 1024 || T < L || hop < 1 || hop > L || ((L - hop) & 1) || nw < 1 || w0 < 0) return false;
+  const long long n_reg = (T - L) / hop + 1, n = n_reg + (((T - L) % hop) != 0 ? 1 : 0);
+  return n <= 0x7fffffffLL && w0 + nw <= R * n;
+}
+
+int launch_newrale_front(const float* rec, long long R, long long T, int L, int hop, long long w0, int nw, const float* prm,
+                         float* inner, float* stats, hipStream_t s) {
+  if (!newrale_stream_args_ok(R, T, L, hop, w0, nw)) return -1;
+  const size_t lds = (size_t)(NR_LEADS + NR_MID) * (L + 12) * sizeof(float);
+  RAL_SET_LDS(k_newrale_front, lds);
+  k_newrale_front<<<nw < 2048 ? nw : 2048, 256, lds, s>>>(rec, T, L, hop, w0, nw, prm, inner, stats);
+  return 0;
+}
+
+int launch_newrale_back(const float* iy, const float* stats, const float* prm, long long R, long long T, int L, int hop,
+                        long long w0, int nw, float* out, hipStream_t s) {
+  if (!newrale_stream_args_ok(R, T, L, hop, w0, nw)) return -1;
+  const size_t lds = (size_t)(2 + NR_MID) * (L + 12) * sizeof(float);
+  RAL_SET_LDS(k_newrale_back, lds);
+  k_newrale_back<<<nw < 2048 ? nw : 2048, 256, lds, s>>>(iy, stats, prm, T, L, hop, w0, nw, out);
   return 0;
 }

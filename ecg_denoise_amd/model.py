@@ -147,6 +147,7 @@ class _ModuleBase(_AutogradMixin):
     VARIANT = None
 
     def __init__(self, variant, leads=2, L=512, max_batch=32, train=True, device="cuda:0", seed=None, autograd=False):
+        self.param_gen = 0     # host-side parameter generation: bumped whenever the parameters may have changed
         self.eng = _Engine(variant, leads, L, max_batch, train, device)
         self.training = bool(train)
         self.step_count = 0
@@ -159,14 +160,19 @@ class _ModuleBase(_AutogradMixin):
     def train(self, mode=True):
         if mode and not self.eng.trainable:
             raise _lib.RalError("model was created with train=False")
+        flip = self.training != bool(mode)
         self.training = bool(mode)
-        self._params_changed()
+        self._params_changed(bump=flip)
         return self
 
-    def _params_changed(self):
+    def _params_changed(self, bump=True):
         """tell the library whether the parameters stand still (eval mode: the weight planes of one forward serve the next) - and, by
         telling it again, that they may have been rewritten (load_state_dict, reset_parameters).  Parameters edited in place in eval
-        mode through `parameters()` / `eng.params` need this call too."""
+        mode through `parameters()` / `eng.params` need this call too.  Bumps `param_gen`, which captured plans of the 12-lead
+        streaming path (infer.py) compare against theirs; train() / eval() bump it only when the mode flips, so that putting an
+        eval-mode model into eval mode again (as every capture does) leaves the other plans of the model valid."""
+        if bump:
+            self.param_gen += 1
         if self.eng.variant in ("nra", "full", "mlp") and getattr(self.eng, "h", None):
             _lib.check(_lib.lib().ral_set_option(self.eng.h, b"static_params", 0 if self.training else 1))
 
@@ -391,6 +397,7 @@ class _ModuleBase(_AutogradMixin):
     def step(self, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0):
         """torch.optim.Adam(lr=1e-3) of denoise_train.py:24 as one fused flat kernel."""
         self.step_count += 1
+        self.param_gen += 1
         _lib.check(_lib.lib().ral_adam_step(self.eng.h, lr, betas[0], betas[1], eps, self.step_count, grad_scale,
                                             _stream()))
 
@@ -502,6 +509,7 @@ class NewRALE(_AutogradMixin):
         z = lambda: torch.zeros(cur, dtype=torch.float32, device=self.device)
         self.params, self.grads, self.adam_m, self.adam_v = z(), z(), z(), z()
         self.training, self.step_count = True, 0
+        self.param_gen = 0     # of the adapter parameters (the inner model keeps its own): see generation()
         rng = np.random.default_rng(seed)
         fan = None
         for k, shp in self.SHAPES.items():
@@ -516,6 +524,10 @@ class NewRALE(_AutogradMixin):
 
     def train(self, mode=True):
         self.training = bool(mode); self.rale.train(mode); return self
+
+    def generation(self):
+        """(adapter, inner model) parameter generations: a plan captured under another pair may hold stale weights"""
+        return self.param_gen, self.rale.param_gen
 
     def eval(self):
         return self.train(False)
@@ -553,6 +565,7 @@ class NewRALE(_AutogradMixin):
                 self._view(self.params, k).copy_(torch.as_tensor(sd[k]).to(self.device, torch.float32))
             elif strict:
                 raise _lib.RalError(f"missing {k}")
+        self.param_gen += 1
         inner = OrderedDict((k[5:], v) for k, v in sd.items() if k.startswith("rale."))
         if inner:
             self.rale.load_state_dict(inner, strict)
@@ -642,6 +655,7 @@ class NewRALE(_AutogradMixin):
 
     def step(self, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0):
         self.step_count += 1
+        self.param_gen += 1
         _lib.check(_lib.lib().ral_adam_flat(_ptr(self.params), _ptr(self.grads), _ptr(self.adam_m), _ptr(self.adam_v),
                                             self.params.numel(), lr, betas[0], betas[1], eps, self.step_count, grad_scale,
                                             _stream()))
