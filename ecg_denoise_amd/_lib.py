@@ -81,6 +81,10 @@ _SIGS = {
     "ral_prep_windows": (C.c_int, [_VP, _VP, C.c_int64, C.c_int, C.c_int, C.c_double, _VP, _VP, _VP, _VP]),
     "ral_stream_windows": (C.c_int, [_VP, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, _VP, _VP, _VP]),
     "ral_stream_stitch": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, _VP, _VP]),
+    "ral_live_windows": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int,
+                                   C.c_int64, C.c_int64, C.c_int, _VP, _VP, _VP]),
+    "ral_live_emit": (C.c_int, [_VP, _VP, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int,
+                                C.c_int64, C.c_int, _VP, _VP, _VP, _VP]),
     "ral_newrale_stream_front": (C.c_int, [_VP, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int, _VP, _VP, _VP,
                                            _VP]),
     "ral_newrale_stream_back": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int, _VP,

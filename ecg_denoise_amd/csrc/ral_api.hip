@@ -1520,6 +1520,34 @@ int ral_stream_stitch(const float* y, const float* stats, int64_t R, int64_t T, 
   return 0;
 }
 
+int ral_live_windows(const float* hist, const float* x, float* hist_out, int64_t S, int leads, int L, int hop, int C, int64_t base,
+                     int64_t k0, int nw, int64_t T, int64_t w0, int nb, float* win, float* stats, ral_stream s) {
+  if (!hist || !x || !win || !stats) return fail("live_windows: null pointer");
+  if (launch_live_windows(hist, x, hist_out, (long long)S, leads, L, hop, C, (long long)base, (long long)k0, nw, (long long)T,
+                          (long long)w0, nb, win, stats, (hipStream_t)s))
+    return fail("live_windows: need S >= 1, leads >= 1, L a multiple of 64 and <= 2048, 1 <= hop <= L with L - hop even, C >= 0, "
+                "T < 0 or T >= L, windows k0 .. k0 + nw - 1 of the stream inside samples [base, base + L + C), a window range "
+                "inside the S * nw windows, and nb >= 1 or a history to write (S=%lld leads=%d L=%d hop=%d C=%d base=%lld k0=%lld "
+                "nw=%d T=%lld w0=%lld nb=%d)", (long long)S, leads, L, hop, C, (long long)base, (long long)k0, nw, (long long)T,
+                (long long)w0, nb);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int ral_live_emit(const float* y, const float* stats, int64_t S, int leads, int L, int hop, int64_t k0, int nw, int64_t T,
+                  int64_t w0, int nb, int64_t lo, int m, float* out, float* last_y, float* last_stats, ral_stream s) {
+  if (!y || !stats || !out) return fail("live_emit: null pointer");
+  if (launch_live_emit(y, stats, (long long)S, leads, L, hop, (long long)k0, nw, (long long)T, (long long)w0, nb, (long long)lo, m,
+                       out, last_y, last_stats, (hipStream_t)s))
+    return fail("live_emit: need S >= 1, leads >= 1, L a multiple of 64 and <= 2048, 1 <= hop <= L with L - hop even, "
+                "T < 0 or T >= L with windows k0 .. k0 + nw - 1 in the stream, a window range of nb >= 1 windows inside the "
+                "S * nw, lo >= 0, m >= 0, and last_y and last_stats both given or both null (S=%lld leads=%d L=%d hop=%d "
+                "k0=%lld nw=%d T=%lld w0=%lld nb=%d lo=%lld m=%d)", (long long)S, leads, L, hop, (long long)k0, nw, (long long)T,
+                (long long)w0, nb, (long long)lo, m);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 int ral_newrale_stream_front(const float* rec, int64_t R, int64_t T, int L, int hop, int64_t w0, int nw,
                              const float* adapter_params, float* inner_x, float* stats, ral_stream s) {
   if (!rec || !adapter_params || !inner_x || !stats) return fail("newrale_stream_front: null pointer");

@@ -74,6 +74,12 @@ int launch_stream_windows(const float* rec, long long R, long long T, int leads,
                           float* win, float* stats, hipStream_t s);
 int launch_stream_stitch(const float* y, const float* stats, long long R, long long T, int leads, int L, int hop, float* out,
                          hipStream_t s);
+// live streams (ral_live_windows / ral_live_emit); -1: bad arguments
+int launch_live_windows(const float* hist, const float* x, float* hist_out, long long S, int leads, int L, int hop, int C,
+                        long long base, long long k0, int nw, long long T, long long w0, int nb, float* win, float* stats,
+                        hipStream_t s);
+int launch_live_emit(const float* y, const float* stats, long long S, int leads, int L, int hop, long long k0, int nw, long long T,
+                     long long w0, int nb, long long lo, int m, float* out, float* last_y, float* last_stats, hipStream_t s);
 // the 12-lead adapter around the inner model of a streamed record group (ral_newrale_stream_front / _back); -1: bad arguments
 int launch_newrale_front(const float* rec, long long R, long long T, int L, int hop, long long w0, int nw, const float* prm,
                          float* inner, float* stats, hipStream_t s);

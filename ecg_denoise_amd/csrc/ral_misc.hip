@@ -592,8 +592,8 @@ RAL_DEV void stream_geom(long long T, int L, int hop, int& n_reg, int& n) {
 
 // The stitch rule: which window keeps which samples of its record.  h = (L - hop) / 2; window 0 keeps [0, hop + h), window k
 // [k hop + h, (k + 1) hop + h), the last window [last_begin, T) (a single window keeps the whole record).  The kept ranges are
-// disjoint and cover [0, T): k_stream_stitch maps a sample to its window (stream_owner), k_newrale_back a window to its samples
-// (stream_kept).
+// disjoint and cover [0, T): k_stream_stitch maps a sample to its window (stream_owner), k_newrale_back and k_live_emit a window
+// to its samples (stream_kept).
 struct StreamKeep {
   int n_reg, n, h;
   long long last_begin;   // first sample the last window keeps
@@ -603,6 +603,15 @@ RAL_DEV StreamKeep stream_keep(long long T, int L, int hop) {
   stream_geom(T, L, hop, s.n_reg, s.n);
   s.h = (L - hop) >> 1;
   s.last_begin = s.n > 1 ? (long long)(s.n - 2) * hop + L - s.h : 0;
+  return s;
+}
+// A live stream whose end T is not known yet: every window is regular and none is the last (n = n_reg = INT_MAX), so
+// stream_start and stream_kept answer for window k < INT_MAX - 1 without reading T.
+RAL_DEV StreamKeep stream_keep_open(int L, int hop) {
+  StreamKeep s;
+  s.n_reg = s.n = 0x7fffffff;
+  s.h = (L - hop) >> 1;
+  s.last_begin = 0;
   return s;
 }
 RAL_DEV long long stream_start(const StreamKeep& s, int k, long long T, int L, int hop) {   // first sample of window k
@@ -617,6 +626,22 @@ RAL_DEV void stream_kept(const StreamKeep& s, int k, long long T, int hop, long 
   e = k == s.n - 1 ? T : (long long)(k + 1) * hop + s.h;
 }
 
+// The z-score of one lead of one window by one wave (lane = threadIdx.x & 63), src(l) its samples l in [0, L): mean, population
+// std with a floor of 1e-6 (as np_norm; constant leads stay finite), dst[l] = (src(l) - mean) / std.  src may read dst.  Every
+// window gather (k_stream_windows, k_live_windows, k_newrale_front) runs these sums, so they all produce the same bits.
+template <class Src>
+RAL_DEV void zscore_wave(const Src& src, float* dst, int L, float& mean, float& sd) {
+  const int lane = threadIdx.x & 63;
+  float sum = 0.f;
+  for (int l = lane; l < L; l += 64) sum += src(l);
+  mean = group_sum<64>(sum) / (float)L;
+  float ss = 0.f;
+  for (int l = lane; l < L; l += 64) { const float d = src(l) - mean; ss = fmaf(d, d, ss); }   // (second pass: L1 hits)
+  sd = fmaxf(sqrtf(group_sum<64>(ss) / (float)L), 1e-6f);
+  const float inv = 1.0f / sd;
+  for (int l = lane; l < L; l += 64) dst[l] = (src(l) - mean) * inv;
+}
+
 __global__ __launch_bounds__(64) void k_stream_windows(const float* __restrict__ rec, long long T, int leads, int L, int hop,
                                                        long long w0, float* __restrict__ win, float* __restrict__ stats) {
   int n_reg, n;
@@ -627,17 +652,9 @@ __global__ __launch_bounds__(64) void k_stream_windows(const float* __restrict__
   const int k = (int)(gw - r * n);
   const long long start = k < n_reg ? (long long)k * hop : T - L;
   const float* src = rec + (r * leads + c) * T + start;
-  const int lane = threadIdx.x;
-  float sum = 0.f;
-  for (int l = lane; l < L; l += 64) sum += src[l];
-  const float mean = group_sum<64>(sum) / (float)L;
-  float ss = 0.f;
-  for (int l = lane; l < L; l += 64) { const float d = src[l] - mean; ss = fmaf(d, d, ss); }   // (second pass: L1 hits)
-  const float sd = fmaxf(sqrtf(group_sum<64>(ss) / (float)L), 1e-6f);   // population std, as np_norm; constant leads stay finite
-  const float inv = 1.0f / sd;
-  float* dst = win + ((size_t)i * leads + c) * L;
-  for (int l = lane; l < L; l += 64) dst[l] = (src[l] - mean) * inv;
-  if (lane == 0) { stats[(gw * leads + c) * 2] = mean; stats[(gw * leads + c) * 2 + 1] = sd; }
+  float mean, sd;
+  zscore_wave([=](int l) { return src[l]; }, win + ((size_t)i * leads + c) * L, L, mean, sd);
+  if (threadIdx.x == 0) { stats[(gw * leads + c) * 2] = mean; stats[(gw * leads + c) * 2 + 1] = sd; }
 }
 
 __global__ __launch_bounds__(256) void k_stream_stitch(const float* __restrict__ y, const float* __restrict__ stats, long long R,
@@ -671,6 +688,113 @@ int launch_stream_stitch(const float* y, const float* stats, long long R, long l
   const long long total = R * leads * T;
   const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
   k_stream_stitch<<<grid, 256, 0, s>>>(y, stats, R, T, leads, L, hop, out);
+  return 0;
+}
+
+// =================================================================================
+// Live streams (LiveDenoiser, infer.py): S streams advance in lockstep by a chunk of C samples.  A stream keeps the last L
+// samples it has received, `hist` (S, leads, L); with the chunk `x` (S, leads, C) they form V = hist ++ x, samples
+// [base, base + L + C) of the stream (base = samples received before the chunk - L; positions below 0 are never read).  The
+// windows are those of the offline path (stream_keep: T >= 0, the stream ends at T; stream_keep_open: T < 0, the end is not
+// known), numbered as there: the windows k0 .. k0 + nw - 1 of every stream, all inside V, are window gw = s nw + j of a call.
+// k_live_windows gathers them straight from hist and x and z-scores them (zscore_wave); its workgroups past the windows
+// write the last L samples of V to hist_out (another buffer than hist: no workgroup reads what another one writes).
+// k_live_emit de-normalises the model output and writes the samples [lo, lo + m) of the stream that the windows keep
+// (stream_kept) into out (S, leads, m).  Both take absolute positions; with T < 0 and k0 > 0 their results depend only on
+// positions relative to base, so a captured push serves every later push that advances by a multiple of hop.
+// =================================================================================
+__global__ __launch_bounds__(64) void k_live_windows(const float* __restrict__ hist, const float* __restrict__ x,
+                                                     float* __restrict__ hist_out, int leads, int L, int hop, int C,
+                                                     long long base, int k0, int nw, long long T, long long w0, int nb,
+                                                     float* __restrict__ win, float* __restrict__ stats) {
+  const int nwl = nb * leads;
+  if ((int)blockIdx.x >= nwl) {   // the history of one (stream, lead): V[C, C + L)
+    const size_t sc = blockIdx.x - nwl;
+    const float* hr = hist + sc * L;
+    const float* xr = x + sc * C;
+    float* dst = hist_out + sc * L;
+    for (int l = threadIdx.x; l < L; l += 64) dst[l] = C + l < L ? hr[C + l] : xr[C + l - L];
+    return;
+  }
+  const StreamKeep sk = T < 0 ? stream_keep_open(L, hop) : stream_keep(T, L, hop);
+  const int i = blockIdx.x / leads, c = blockIdx.x - i * leads;   // window of this launch, lead
+  const long long gw = w0 + i;
+  const long long s = gw / nw;
+  const int j = (int)(gw - s * nw);
+  const int o = (int)(stream_start(sk, k0 + j, T, L, hop) - base);   // the window is V[o, o + L)
+  const float* hr = hist + (s * leads + c) * L;
+  const float* xr = x + (s * leads + c) * C - L;
+  float mean, sd;
+  zscore_wave([=](int l) { const int v = o + l; return v < L ? hr[v] : xr[v]; }, win + ((size_t)i * leads + c) * L, L, mean, sd);
+  if (threadIdx.x == 0) { stats[(gw * leads + c) * 2] = mean; stats[(gw * leads + c) * 2 + 1] = sd; }
+}
+
+// y (nb, leads, L): the model output for windows [w0, w0 + nb) of the call; last_y / last_stats (optional): window j = nw - 1
+// of every stream is also kept whole, (S, leads, L) and (S, leads, 2), for a later call with T known.
+__global__ __launch_bounds__(64) void k_live_emit(const float* __restrict__ y, const float* __restrict__ stats, int leads, int L,
+                                                  int hop, int k0, int nw, long long T, long long w0, long long lo, int m,
+                                                  float* __restrict__ out, float* __restrict__ last_y,
+                                                  float* __restrict__ last_stats) {
+  const StreamKeep sk = T < 0 ? stream_keep_open(L, hop) : stream_keep(T, L, hop);
+  const int i = blockIdx.x / leads, c = blockIdx.x - i * leads;
+  const long long gw = w0 + i;
+  const long long s = gw / nw;
+  const int j = (int)(gw - s * nw), k = k0 + j;
+  const long long start = stream_start(sk, k, T, L, hop);
+  long long b, e;
+  stream_kept(sk, k, T, hop, b, e);
+  b = b > lo ? b : lo;                   // (the kept range lies inside the window: stream_kept; clipped to it all the same)
+  b = b > start ? b : start;
+  e = e < lo + m ? e : lo + m;
+  e = e < start + L ? e : start + L;
+  const float mean = stats[(gw * leads + c) * 2], sd = stats[(gw * leads + c) * 2 + 1];
+  const float* yr = y + ((size_t)i * leads + c) * L;
+  float* dst = out + (s * leads + c) * m - lo;
+  for (long long t = b + threadIdx.x; t < e; t += 64) dst[t] = fmaf(yr[t - start], sd, mean);
+  if (last_y && j == nw - 1) {
+    float* ly = last_y + (s * leads + c) * L;
+    for (int l = threadIdx.x; l < L; l += 64) ly[l] = yr[l];
+    if (threadIdx.x == 0) { last_stats[(s * leads + c) * 2] = mean; last_stats[(s * leads + c) * 2 + 1] = sd; }
+  }
+}
+
+// The host side of the same geometry (stream_geom / stream_start), for argument checks: window k of a stream ending at T (T < 0:
+// open) starts at *start; false if there is no window k.
+static bool live_window_start(long long T, int L, int hop, long long k, long long& start) {
+  if (T < 0) { start = k * hop; return k < 0x7ffffffeLL; }
+  const long long n_reg = (T - L) / hop + 1, n = n_reg + (((T - L) % hop) != 0 ? 1 : 0);
+  start = k < n_reg ? k * hop : T - L;
+  return k < n && n < 0x7fffffffLL;
+}
+
+static bool live_geom_ok(long long S, int leads, int L, int hop, long long k0, int nw, long long T, long long w0, int nb) {
+  if (S < 1 || leads < 1 || L < 64 || L % 64 != 0 || L > 2048 || hop < 1 || hop > L || ((L - hop) & 1)) return false;
+  if (nw < 0 || k0 < 0 || nb < 0 || w0 < 0 || (T >= 0 && T < L) || w0 + nb > S * nw) return false;
+  long long st;
+  return nw == 0 || live_window_start(T, L, hop, k0 + nw - 1, st);
+}
+
+int launch_live_windows(const float* hist, const float* x, float* hist_out, long long S, int leads, int L, int hop, int C,
+                        long long base, long long k0, int nw, long long T, long long w0, int nb, float* win, float* stats,
+                        hipStream_t s) {
+  if (!live_geom_ok(S, leads, L, hop, k0, nw, T, w0, nb) || C < 0 || (nb == 0 && !hist_out)) return -1;
+  if (nw > 0) {   // every window inside V: the first one starts at or after base, the last one ends at or before base + L + C
+    long long first, last;
+    live_window_start(T, L, hop, k0, first);
+    live_window_start(T, L, hop, k0 + nw - 1, last);
+    if (first < base || last + L > base + L + C) return -1;
+  }
+  const long long grid = (long long)nb * leads + (hist_out ? S * leads : 0);
+  if (grid > 0x7fffffffLL) return -1;
+  k_live_windows<<<(int)grid, 64, 0, s>>>(hist, x, hist_out, leads, L, hop, C, base, (int)k0, nw, T, w0, nb, win, stats);
+  return 0;
+}
+
+int launch_live_emit(const float* y, const float* stats, long long S, int leads, int L, int hop, long long k0, int nw, long long T,
+                     long long w0, int nb, long long lo, int m, float* out, float* last_y, float* last_stats, hipStream_t s) {
+  if (!live_geom_ok(S, leads, L, hop, k0, nw, T, w0, nb) || nb < 1 || lo < 0 || m < 0 || (!last_y != !last_stats)) return -1;
+  if ((long long)nb * leads > 0x7fffffffLL) return -1;
+  k_live_emit<<<nb * leads, 64, 0, s>>>(y, stats, leads, L, hop, (int)k0, nw, T, w0, lo, m, out, last_y, last_stats);
   return 0;
 }
 
@@ -756,17 +880,11 @@ __global__ __launch_bounds__(256) void k_newrale_front(const float* __restrict__
       xs[c * LP + 6 + l] = src[c * T + l];
     }
     __syncthreads();
-    // z-score, one wave per lead: k_stream_windows' sums in its order (population std, floor 1e-6)
+    // z-score, one wave per lead (zscore_wave: k_stream_windows' bits)
     for (int c = wave; c < NR_LEADS; c += blockDim.x >> 6) {
       float* row = xs + c * LP + 6;
-      float sum = 0.f;
-      for (int l = lane; l < L; l += 64) sum += row[l];
-      const float mean = group_sum<64>(sum) / (float)L;
-      float ss = 0.f;
-      for (int l = lane; l < L; l += 64) { const float d = row[l] - mean; ss = fmaf(d, d, ss); }
-      const float sd = fmaxf(sqrtf(group_sum<64>(ss) / (float)L), 1e-6f);
-      const float inv = 1.0f / sd;
-      for (int l = lane; l < L; l += 64) row[l] = (row[l] - mean) * inv;
+      float mean, sd;
+      zscore_wave([=](int l) { return row[l]; }, row, L, mean, sd);
       if (lane == 0) { stats[(gw * NR_LEADS + c) * 2] = mean; stats[(gw * NR_LEADS + c) * 2 + 1] = sd; }
     }
     __syncthreads();

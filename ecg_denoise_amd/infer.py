@@ -10,7 +10,10 @@ de-normalised and stitched back (overlapping regions keep the centre of each win
 A 12-lead `NewRALE` streams the same way around its inner 2-lead RA-LENet: the adapter convolutions run fused with the
 windowing (`ral_newrale_stream_front`) and with the stitching (`ral_newrale_stream_back`).  Its captured plans remember the
 model's parameter generation and are captured again once the weights change (the inner eval-mode forward leaves the
-preparation of its weight planes out of a capture)."""
+preparation of its weight planes out of a capture).
+
+`LiveDenoiser` denoises S streams that arrive chunk by chunk; what it returns, concatenated, is what `StreamingDenoiser`
+returns for the complete records."""
 import torch
 
 from . import _lib
@@ -170,3 +173,164 @@ class StreamingDenoiser:
             self._run(p)
         out = p["out"][0] if single else p["out"]
         return out.clone() if copy else out
+
+
+def live_frontier(n, L, hop):
+    """F(n): after n samples of a stream, samples [0, F(n)) are final for every length T >= n the stream may end at.  Each is
+    kept by a regular window that is complete at n (window k keeps [k hop + h, (k + 1) hop + h), window 0 from 0; h =
+    (L - hop) / 2), and neither a later window nor the right-aligned last one of any T >= n claims it.  0 before the first
+    window is complete."""
+    if n < L:
+        return 0
+    return ((n - L) // hop + 1) * hop + (L - hop) // 2
+
+
+def live_latency(L, hop):
+    """D = n - F(n) for every n >= L on the hop grid: the constant lag of a live stream fed in chunks of a multiple of hop"""
+    return (-L) % hop + (L - hop) // 2
+
+
+class LiveDenoiser:
+    """S streams denoised while they arrive, in lockstep chunks of C samples (C a positive multiple of hop = L - overlap).
+
+    `push(x)` takes the next chunk of every stream, x (S, leads, C), and returns the samples that have become final, (S, leads,
+    m) on the device: nothing before L samples have arrived, samples [0, F(n)) when the first window completes
+    (`live_frontier`), then C per push, `latency` samples behind the newest one.  `flush(x=None)` takes an optional last chunk of
+    any length r >= 0, returns the rest of every stream and resets the object.  Concatenated per stream, everything `push` and
+    `flush` returned equals `StreamingDenoiser(model, overlap=overlap).denoise(record)`: the same windows, per-window z-score,
+    stitch rule and right-aligned last window.
+
+    Per push `ral_live_windows` gathers every stream's new windows straight from its last L samples (kept on the device, two
+    buffers used in turn: a push reads one and writes the other) and the chunk, the model runs them in batches of at most
+    max_batch windows, and `ral_live_emit` writes the samples they keep.  Once the lag is constant (the first L samples have
+    arrived) a push replays one of two captured hipGraphs, by push parity; they are captured again when the model's parameter
+    generation moves (the eval-mode capture leaves out the preparation of the weight planes).  Earlier pushes and `flush` run
+    eagerly.  Accepts the 1- and 2-lead models of `StreamingDenoiser` (RALENet, UNet, ACDAE, DANet); puts the model in eval mode."""
+
+    def __init__(self, model, streams, chunk, overlap=0, use_graph=True):
+        if isinstance(model, NewRALE):
+            raise _lib.RalError("LiveDenoiser does not take a NewRALE: live 12-lead streams are not supported "
+                                "(StreamingDenoiser denoises complete 12-lead records)")
+        e = model.eng
+        self.model, self.eng, self.L, self.leads = model, e, e.L, e.leads
+        if overlap < 0 or overlap >= self.L or overlap % 2:
+            raise _lib.RalError("overlap must be an even number of samples in [0, L)")
+        self.overlap, self.hop = overlap, self.L - overlap
+        if streams < 1:
+            raise _lib.RalError("streams must be >= 1")
+        if chunk < 1 or chunk % self.hop:
+            raise _lib.RalError(f"chunk must be a positive multiple of hop = L - overlap = {self.hop} (got {chunk})")
+        self.S, self.C, self.use_graph = int(streams), int(chunk), use_graph
+        nw = self.C // self.hop                      # windows per stream and push, at most (every push once the lag is constant)
+        dev = e.device
+        z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
+        self.hist = [z(self.S, self.leads, self.L), z(self.S, self.leads, self.L)]    # push parity p reads hist[p], writes hist[1 - p]
+        self.x = z(self.S, self.leads, self.C)
+        self.win = z(min(e.max_batch, self.S * nw), self.leads, self.L)      # one batch of windows
+        self.y = torch.zeros_like(self.win)
+        self.stats = z(self.S * nw * self.leads * 2)
+        self.out = z(self.S, self.leads, self.C)
+        self.last_y, self.last_stats = z(self.S, self.leads, self.L), z(self.S * self.leads * 2)   # the last regular window
+        self.graphs, self.gen = [None, None], None
+        self.latency = live_latency(self.L, self.hop)
+        model.eval()
+        self.reset()
+
+    def reset(self):
+        """drop every stream's state; the next push starts new streams (the captured graphs stay valid)"""
+        self.samples_in, self.parity = 0, 0
+
+    def _n_reg(self, n):
+        return (n - self.L) // self.hop + 1 if n >= self.L else 0
+
+    def _run(self, x, C, k0, nw, T, lo, m, out, keep, stats):
+        """enqueue one call on the current stream (captured or eager): the windows k0 .. k0 + nw - 1 of every stream from the
+        history and x (C samples), the model, the kept samples in [lo, lo + m) -> out; a push (keep) also writes the next
+        history and keeps the last window.  stats: (mean, std) of the S * nw windows"""
+        lib, e, S, n = _lib.lib(), self.eng, self.S, self.samples_in
+        h_in, h_out = self.hist[self.parity], (self.hist[1 - self.parity] if keep else None)
+        base, batch = n - self.L, self.win.shape[0]
+        for w0 in range(0, max(S * nw, 1), batch):
+            nb = min(batch, S * nw - w0)
+            if nb == 0 and h_out is None:
+                break
+            _lib.check(lib.ral_live_windows(_ptr(h_in), _ptr(x), _ptr(h_out if w0 == 0 else None), S, self.leads, self.L,
+                                            self.hop, C, base, k0, nw, T, w0, nb, _ptr(self.win), _ptr(stats), _stream()))
+            if nb == 0:
+                break
+            _lib.check(lib.ral_forward(e.h, _ptr(self.win), _ptr(self.y), nb, 0, _stream()))
+            _lib.check(lib.ral_live_emit(_ptr(self.y), _ptr(stats), S, self.leads, self.L, self.hop, k0, nw, T, w0, nb, lo,
+                                         m, _ptr(out), _ptr(self.last_y if keep else None),
+                                         _ptr(self.last_stats if keep else None), _stream()))
+
+    def _chunk(self, x, what):
+        x = torch.as_tensor(x, dtype=torch.float32)
+        if x.dim() != 3 or x.shape[0] != self.S or x.shape[1] != self.leads:
+            raise _lib.RalError(f"{what}: expected a chunk of shape ({self.S}, {self.leads}, samples), got {tuple(x.shape)}")
+        return x
+
+    def _capture(self, args):
+        dev = self.eng.device
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):          # warm-up outside capture (lazy LDS-size attributes, lane streams)
+            self._run(*args)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._run(*args)
+        return g
+
+    @torch.no_grad()
+    def push(self, x, copy=True):
+        """x (S, leads, C), host or device -> the samples of every stream that became final, (S, leads, m) on the device.  The
+        result is a fresh tensor; `copy=False` returns a view of a buffer that the next push may overwrite."""
+        x = self._chunk(x, "push")
+        if x.shape[2] != self.C:
+            raise _lib.RalError(f"push: every chunk has C = {self.C} samples (got {x.shape[2]}); flush takes a shorter last one")
+        n0, n1 = self.samples_in, self.samples_in + self.C
+        k0 = self._n_reg(n0)
+        nw = self._n_reg(n1) - k0
+        lo = live_frontier(n0, self.L, self.hop)
+        m = live_frontier(n1, self.L, self.hop) - lo
+        self.x.copy_(x, non_blocking=True)
+        if n0 >= self.L and self.use_graph:
+            # steady state: nw = C / hop, m = C, k0 > 0; the arguments of the capturing push serve every later push of the
+            # same parity (the open-stream rule depends only on positions relative to the history)
+            if self.gen != self.model.param_gen:
+                self.graphs, self.gen = [None, None], self.model.param_gen
+            if self.graphs[self.parity] is None:
+                self.graphs[self.parity] = self._capture((self.x, self.C, k0, nw, -1, lo, m, self.out, True, self.stats))
+            self.graphs[self.parity].replay()
+            out = self.out
+        else:
+            out = self.out if m == self.C else torch.empty(self.S, self.leads, m, device=self.eng.device)
+            self._run(self.x, self.C, k0, nw, -1, lo, m, out, True, self.stats)
+        self.samples_in, self.parity = n1, 1 - self.parity
+        return out.clone() if copy and out is self.out else out
+
+    @torch.no_grad()
+    def flush(self, x=None):
+        """the optional last chunk x (S, leads, r), any r >= 0 -> the rest of every stream, (S, leads, T - F(n)) for a stream of
+        T = n + r samples; the object is reset afterwards"""
+        r = 0 if x is None else self._chunk(x, "flush").shape[2]
+        n, T = self.samples_in, self.samples_in + r
+        if T < self.L:
+            raise _lib.RalError(f"flush: a stream shorter than one window ({T} < {self.L} samples)")
+        xd = torch.zeros(self.S, self.leads, max(r, 1), device=self.eng.device)
+        if r:
+            xd.copy_(x)
+        k0 = self._n_reg(n)
+        nw = (T - self.L) // self.hop + 1 + (1 if (T - self.L) % self.hop else 0) - k0
+        lo = live_frontier(n, self.L, self.hop)
+        out = torch.empty(self.S, self.leads, T - lo, device=self.eng.device)
+        if nw:   # (a long last chunk may hold more windows than a push: stats of their own)
+            stats = self.stats if self.stats.numel() >= self.S * nw * self.leads * 2 else \
+                torch.empty(self.S * nw * self.leads * 2, device=self.eng.device)
+            self._run(xd, r, k0, nw, T, lo, T - lo, out, False, stats)
+        if n >= self.L and T > lo:    # the last regular window of the pushes: it keeps [lo, T) if it is the stream's last one
+            _lib.check(_lib.lib().ral_live_emit(_ptr(self.last_y), _ptr(self.last_stats), self.S, self.leads, self.L, self.hop,
+                                                k0 - 1, 1, T, 0, self.S, lo, T - lo, _ptr(out), None, None, _stream()))
+        self.reset()
+        return out
