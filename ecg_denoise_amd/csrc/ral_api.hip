@@ -30,40 +30,30 @@ static int fail(const char* fmt, ...) {
 extern "C" const char* ral_last_error(void) { return g_err; }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Switches.  Every tuning / experiment switch of the library has a compile-time default and a name in the list below.  The
-// product build reads NO environment variable for them: the only way to change one is ral_global_option() (C ABI; process-
-// wide, to be called before the first use - most are read once), which the tests use to pick kernels.  The library reads
+// Switches.  A switch stays only while a test, a bench.py leg or a committed tool sets it to pick a kernel or a schedule;
+// every other tuning choice is a named constant next to its launcher.  Each switch has a compile-time default and a name in
+// the list below.  The product build reads NO environment variable for them: the only way to change one is
+// ral_global_option() (C ABI; process-wide, to be called before the first use - most are read once).  The library reads
 // exactly two environment variables, both validated: RAL_LANES (1 .. 4 micro-batch chains) and RAL_NO_SIDE_STREAM (0 / 1).
 // A diagnostic build (-DRAL_DIAG) additionally takes RAL_<NAME> from the environment for every switch (tools/diag/*.sh).
 static const char* const KNOB_NAMES[] = {
-  "ACDAE_DW_MFMA", "ACDAE_ENC_MFMA", "ATTNB_NT0", "ATTNF_NT0", "ATTNW_WAVES",
-  "ATTN_BWD_LDS", "ATTN_BWD_M", "ATTN_BWD_MH", "ATTN_BWD_V_HI", "ATTN_BWD_V_LO", "ATTN_BWD_W", "ATTN_F16", "ATTN_FWD_H",
-  "ATTN_FWD_LDS", "ATTN_FWD_V_HI", "ATTN_FWD_V_LO", "ATTN_FWD_W", "ATTN_QT1", "ATTN_QT4", "ATTN_SPLIT", "BUCKET_WAIT", "DANET_GRID_A",
-  "DANET_GRID_B", "DANET_GRID_D", "DANET_GRID_F", "DANET_GRID_W", "DIAG_SKIP_WIDE_DW", "DW_F16", "DW_KSPLIT_128", "DW_KSPLIT_16",
-  "DW_KSPLIT_32", "DW_KSPLIT_64", "DW_KSPLIT_8", "DW_LDS", "DW_PRIO", "DW_SETS", "F16_SPLIT", "FUSE_DW", "GRID_ATTNB", 
-  "GRID_ATTNW", "GRID_FWD", "GRID_MLPB", "GRID_MLPBW", "GRID_MLPS", "GRID_MLPW", "GRID_QKVB", "GRID_QKVW", "GRID_RESB", "LOSS_GRID",
-  "MLP_BWD_W", "MLP_BWD_W_F16", "MLP_F16", "MLP_FWD_W", "MLP_HLDS", "MLP_HTHREADS", "MLPB_HTHREADS", "MLP_LDS", "MLP_TOK", "PREP_OVERLAP", "QKVB_F16", "QKVB_FDW", "QKVB_SEG", "TABRED_SIDE", "QKV_WS", "UNET_BWD_GRID",
-  "UNET_BWD_WP", "UNET_DEBUG", "UNET_EVAL_GRID", "UNET_FOLD", "UNET_FUSED", "UNET_FWD_GRID", "UNET_NREP", "UNET_WG_PER_CU"};
+  "ATTN_BWD_M", "ATTN_BWD_MH", "ATTN_BWD_W", "ATTN_F16", "ATTN_FWD_H", "ATTN_FWD_W", "DW_SETS", "F16_SPLIT", "FUSE_DW",
+  "MLP_BWD_W", "MLP_BWD_W_F16", "MLP_FWD_W", "TABRED_SIDE", "UNET_EVAL_GRID", "UNET_FUSED"};
 static std::mutex g_knob_mu;
 static std::map<std::string, long long>& knob_table() { static std::map<std::string, long long> t; return t; }
-static std::map<std::string, int>& knob_read() { static std::map<std::string, int> t; return t; }   // switches a consumer has read already
-// grid caps, thread counts and split counts: 0 would be a launch with no workgroup (a launch error), not "automatic"
-static const char* const KNOB_MIN1[] = {
-  "DANET_GRID_A", "DANET_GRID_B", "DANET_GRID_D", "DANET_GRID_F", "DANET_GRID_W", "GRID_FWD", "GRID_ATTNB", "GRID_MLPB", "GRID_MLPS",
-  "GRID_QKVB", "GRID_RESB", "LOSS_GRID", "UNET_FWD_GRID", "UNET_EVAL_GRID", "UNET_BWD_GRID", "UNET_BWD_WP", "UNET_NREP", "DW_SETS",
-  "DW_KSPLIT_8", "DW_KSPLIT_16", "DW_KSPLIT_32", "DW_KSPLIT_64", "DW_KSPLIT_128"};
+static std::map<std::string, long long>& knob_read() { static std::map<std::string, long long> t; return t; }   // value each switch was read at
+// grid caps and set counts: 0 would be a launch with no workgroup (a launch error), not "automatic"
+static const char* const KNOB_MIN1[] = {"DW_SETS", "UNET_EVAL_GRID"};
 long long ral_knob(const char* name, long long dflt) {
-  {
-    std::lock_guard<std::mutex> lk(g_knob_mu);
-    knob_read()[name] = 1;
-    auto it = knob_table().find(name);
-    if (it != knob_table().end()) return it->second;
-  }
+  long long v = dflt;
+  std::lock_guard<std::mutex> lk(g_knob_mu);
+  auto it = knob_table().find(name);
+  if (it != knob_table().end()) v = it->second;
 #ifdef RAL_DIAG
-  const std::string e = std::string("RAL_") + name;
-  if (const char* v = getenv(e.c_str())) return atoll(v);
+  else if (const char* e = getenv((std::string("RAL_") + name).c_str())) v = atoll(e);
 #endif
-  return dflt;
+  knob_read()[name] = v;
+  return v;
 }
 // a validated integer environment variable (the product build has two): out-of-range or non-numeric text keeps the default
 int ral_env_int(const char* name, int dflt, int lo, int hi) {
@@ -112,14 +102,12 @@ extern "C" int ral_global_option(const char* key, long long value) {
   if (!known) return fail("unknown switch %s", key);
   if (value < 0) return fail("switch %s: negative value %lld", key, value);
   for (const char* n : KNOB_MIN1)
-    if (k == n && value < 1) return fail("switch %s: value %lld out of range (a grid / thread / split count: >= 1)", key, value);
-  if (k == "MLP_HTHREADS" && value != 256 && value != 512 && value != 1024) return fail("switch %s: 256, 512 or 1024 threads (got %lld)", key, value);
-  if (k == "MLPB_HTHREADS" && value != 256 && value != 512) return fail("switch %s: 256 or 512 threads (got %lld)", key, value);
+    if (k == n && value < 1) return fail("switch %s: value %lld out of range (a grid / set count: >= 1)", key, value);
   std::lock_guard<std::mutex> lk(g_knob_mu);
   // most consumers read a switch once and keep it: a change after that first read would be ignored silently, so it is refused
-  // (the same value again is fine: tests and tools set their switches at start-up, possibly more than once)
-  auto cur = knob_table().find(k);
-  if (knob_read().count(k) && !(cur != knob_table().end() && cur->second == value))
+  // (the value in force, default included, is fine: tests and tools set their switches at start-up, possibly more than once)
+  auto rd = knob_read().find(k);
+  if (rd != knob_read().end() && rd->second != value)
     return fail("switch %s was already read by the library (switches are latched at first use): set it before the first model is created", key);
   knob_table()[k] = value;
   return 0;
@@ -495,36 +483,29 @@ static size_t plan_workspace(const ral_config& c, RalModel* m /* may be null: si
   return cur;
 }
 
-static size_t env_size(const char* name, size_t dflt) { return (size_t)ral_knob(name + 4, (long long)dflt); }   // (name = "RAL_<KNOB>")
+// LDS budgets of a workgroup (bytes; fewer bytes = smaller head groups / more hidden chunks but more co-resident workgroups per CU)
+static constexpr size_t ATTN_FWD_LDS = 72 * 1024, ATTN_BWD_LDS = 78 * 1024, MLP_LDS = 78000;
 
 // head-group size of the attention kernels: the largest power-of-two fraction of the heads whose tiles fit the LDS budget
 static int attn_head_group(int N, int H, int Len, bool bwd) {
-  const size_t budget = bwd ? env_size("RAL_ATTN_BWD_LDS", 78 * 1024) : env_size("RAL_ATTN_FWD_LDS", 72 * 1024);
+  const size_t budget = bwd ? ATTN_BWD_LDS : ATTN_FWD_LDS;
   int hg = H;
   while (hg > 1 && (bwd ? attn_bwd_lds(N, hg, Len) : attn_fwd_lds(N, hg, Len)) > budget) hg /= 2;
   return hg;
 }
 
 static void choose_tiling(RalModel* m) {
-  // tuning knobs (bytes of LDS a workgroup may take; fewer bytes = more hidden chunks / smaller head
-  // groups but more co-resident workgroups per CU).  Environment overrides are for experiments only.
-  const size_t budget = env_size("RAL_MLP_LDS", 78000);
   // split-K workgroups of a fully sliced weight-gradient product per channel width {8,16,32,64,128} (products with
   // fewer slices get more, up to RAL_DW_MINWG workgroups per launch - see ral_dw.hip for why that is 192)
   static const int KS_DEFAULT[5] = {128, 128, 128, 64, 32};
   for (int l = 0; l < 5; ++l) m->dw_ksplit[l] = KS_DEFAULT[l];
-  {   // DW_KSPLIT_<width>: split-K workgroups of one channel width
-    static const char* const KSN[5] = {"DW_KSPLIT_8", "DW_KSPLIT_16", "DW_KSPLIT_32", "DW_KSPLIT_64", "DW_KSPLIT_128"};
-    for (int l = 0; l < 5; ++l) { const int v = (int)ral_knob(KSN[l], m->dw_ksplit[l]); if (v > 0) m->dw_ksplit[l] = v; }
-  }
-  set_dw_lds_budget(env_size("RAL_DW_LDS", 76 * 1024));
   for (int l = 0; l < 5; ++l) {
     const int C = CH[l], N = m->Lp >> l, H = C / 4;
     int n = 1;
-    while (n < 4 && mlp_fwd_lds(C, N, n) > budget) n *= 2;
+    while (n < 4 && mlp_fwd_lds(C, N, n) > MLP_LDS) n *= 2;
     m->nch_f[l] = n;
     n = 1;
-    while (n < 4 && mlp_bwd_lds(C, N, n) > budget) n *= 2;
+    while (n < 4 && mlp_bwd_lds(C, N, n) > MLP_LDS) n *= 2;
     m->nch_b[l] = n;
     const int Len = l < 4 ? RWLEN[l] : 0;
     m->hg_f[l] = attn_head_group(N, H, Len, false);
@@ -654,8 +635,7 @@ static int fwd_begin(RalModel* m, const float* x, int B, int training, hipStream
   m->skip_prep = !training && m->static_params && m->planes_valid;
   if (training) m->planes_valid = false;                         // (an optimiser step will follow)
   else if (m->static_params) m->planes_valid = true;             // (what this forward prepares stays)
-  static const bool prep_on = ral_knob("PREP_OVERLAP", 1) != 0;
-  if (!m->skip_prep && prep_on && m->side_stream && m->ev_prep_go) {
+  if (!m->skip_prep && m->side_stream && m->ev_prep_go) {
     hipStream_t ps = lanes_of(m)->l[0].s2;
     HIP_OK(hipEventRecord(m->ev_prep_go, s));            // (the parameters are final: everything queued on s so far has run)
     HIP_OK(hipStreamWaitEvent(ps, m->ev_prep_go, 0));
@@ -783,9 +763,8 @@ static void run_block_bwd(RalModel* m, int bi, const float* dy, const float* ext
     launch_attn_bwd(qkv, o, dohm, lse, table, gtable, dqkv, scratch, (size_t)B * (E1 / 2 + 2048), N, H, m->hg_b[l], Len, B,
                     (m->f16_split > 0 && m->attn_f16) ? 1 : 0, s, NE);
     attn_tab_defer_to(nullptr); }
-  bool fused_qkv_dw;
   { ProfScope p(m, K_QKV_BWD, s);
-    fused_qkv_dw = launch_qkv_bwd(C, dqkv, xin, m->pe[l], dx1, woff(extra, w0, E1), w, wt, m->paramsT, splitb ? m->whT : nullptr, gmax, g, woff(dx, w0, E1), N, B, m->want_dw, s); }
+    launch_qkv_bwd(C, dqkv, xin, m->pe[l], dx1, woff(extra, w0, E1), w, wt, m->paramsT, splitb ? m->whT : nullptr, gmax, g, woff(dx, w0, E1), N, B, s); }
   if (!m->want_dw) return;
   if (side) {
     EV(hipEventRecord(ln.ev_ready[k], s));
@@ -793,11 +772,7 @@ static void run_block_bwd(RalModel* m, int bi, const float* dy, const float* ext
   }
   if (tabred.ntab > 0) launch_attn_tpart_reduce(tabred.tpart, tabred.gtable, tabred.ntab, tabred.nrow, sd);
   { ProfScope p(m, K_DW, sd);
-#ifdef RAL_DIAG   // diagnostic builds only (make VARIANT=diag EXTRA=-DRAL_DIAG; WRONG gradients): what the weight-gradient kernels of the levels C >= RAL_DIAG_SKIP_WIDE_DW cost the step
-    static const int skipw = (int)ral_knob("DIAG_SKIP_WIDE_DW", 0);
-    if (!(skipw && C >= skipw))
-#endif
-    launch_block_dw(C, dyw, upre, w.le ? a2c0 : nullptr, dupre, x1, dx1, o, dqkv, xin, m->pe[l], w, g, N, B, m->dw_ksplit[l], fused_mlp_dw, gmax, sd, fused_qkv_dw); }
+    launch_block_dw(C, dyw, upre, w.le ? a2c0 : nullptr, dupre, x1, dx1, o, dqkv, xin, m->pe[l], w, g, N, B, m->dw_ksplit[l], fused_mlp_dw, gmax, sd); }
   if (side) { EV(hipEventRecord(ln.ev_done[k], sd)); ln.dw_pending[k] = true; }
 }
 
@@ -1060,21 +1035,14 @@ int ral_create(const ral_config* cfg, ral_handle** out) {
     LaneSet* LS = new LaneSet();
     m->lanes = LS;
     m->n_lanes = ral_env_int("RAL_LANES", 2, 1, MAX_LANES);        // one of the TWO environment variables the library reads
-    // the weight-gradient streams are off the critical path: lowest priority, so that their workgroups fill the
-    // gaps the main chain leaves instead of competing with it (RAL_DW_PRIO=0 keeps the default priority)
-    int prio_least = 0, prio_greatest = 0;
-    (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-    const int pmode = (int)env_size("RAL_DW_PRIO", 0);   // 0 default, 1 lowest, 2 highest
-    const bool low = pmode != 0;
-    // a failed creation would leave a null stream (= the legacy default stream: the fork/join ordering would silently
+    // (the weight-gradient streams s2 run at the default priority, like the chains.)  A failed creation would leave a null stream (= the legacy default stream: the fork/join ordering would silently
     // change), so the first error fails the whole ral_create
     hipError_t first = hipSuccess;
     auto ok = [&](hipError_t r) { if (r != hipSuccess && first == hipSuccess) first = r; };
     for (int i = 0; i < MAX_LANES; ++i) {
       Lane& ln = LS->l[i];
       if (i > 0) ok(hipStreamCreateWithFlags(&LS->own[i], hipStreamNonBlocking));
-      if (low) ok(hipStreamCreateWithPriority(&ln.s2, hipStreamNonBlocking, pmode == 2 ? prio_greatest : prio_least));
-      else ok(hipStreamCreateWithFlags(&ln.s2, hipStreamNonBlocking));
+      ok(hipStreamCreateWithFlags(&ln.s2, hipStreamNonBlocking));
       for (int k = 0; k < MAX_SETS; ++k) {
         ok(hipEventCreateWithFlags(&ln.ev_ready[k], hipEventDisableTiming));
         ok(hipEventCreateWithFlags(&ln.ev_done[k], hipEventDisableTiming));
@@ -1323,14 +1291,9 @@ int ral_grad_bucket_wait(ral_handle* h, int k, ral_stream s) {
   if (k == 1) {
     if (m->dec_lanes <= 0) return fail("bucket 1 is available after ral_backward_begin");
     LaneSet* LS = lanes_of(m);
-#ifdef RAL_DIAG   // diagnostic builds only (dropping a wait is a data race): 1 chains only, 2 side streams only, 0 none
-    static const int dbg = (int)ral_knob("BUCKET_WAIT", 3);
-#else
-    constexpr int dbg = 3;
-#endif
     for (int i = 0; i < m->dec_lanes; ++i) {
-      if (dbg & 1) HIP_OK(hipStreamWaitEvent((hipStream_t)s, LS->l[i].ev_dec_main, 0));
-      if (m->dec_side && (dbg & 2)) HIP_OK(hipStreamWaitEvent((hipStream_t)s, LS->l[i].ev_dec_side, 0));
+      HIP_OK(hipStreamWaitEvent((hipStream_t)s, LS->l[i].ev_dec_main, 0));
+      if (m->dec_side) HIP_OK(hipStreamWaitEvent((hipStream_t)s, LS->l[i].ev_dec_side, 0));
     }
     return 0;
   }

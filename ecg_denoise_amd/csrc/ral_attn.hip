@@ -418,12 +418,10 @@ int attnw_grid_max(int N, int H, int B) {
   return g < 1024 ? g : 1024;
 }
 // the grid of a launch: a whole number of resident rounds (workgroups per CU x 256 CUs) - 1024 workgroups on 768 slots
-// would run a second round one third full (RAL_GRID_ATTNW overrides)
+// would run a second round one third full
 template <class K>
 static int attnw_grid(K kernel, size_t lds, int N, int H, int B) {
-  static const int genv = (int)ral_knob("GRID_ATTNW", 0);
   const int gmax = attnw_grid_max(N, H, B);
-  if (genv > 0) return genv < gmax ? genv : gmax;
   const int occ = ral_occupancy(reinterpret_cast<const void*>(kernel), 256, lds, 3);
   const int slots = ral_num_cus() * (occ > 4 ? 4 : occ);
   return slots < gmax ? slots : gmax;
@@ -703,18 +701,15 @@ void launch_attn_bwd_w(const float* qkv, const float* o_hm, const float* do_hm, 
   const int hw = N >= 64 ? 1 : 64 / N, T = hw * N;
   const int ntask = B * H / hw;
   const int ntab = table ? (2 * Len - 1) * H : 0;
-  // waves per workgroup (RAL_ATTNW_WAVES).  Measured at batch 2048, us per launch with 4 / 3 / 2 / 1 waves: N = 128: 236 / 274 /
+  // waves per workgroup.  Measured at batch 2048, us per launch with 4 / 3 / 2 / 1 waves: N = 128: 236 / 274 /
   // 245 / 283 (four-wave workgroups of 61 KB leave a CU two of them, five two-wave ones fit - and are no faster), N = 64:
   // 131 / 135 / 142 / 173, N = 32: 82 / 80 / 83 / 99
-  static const int wv_env = (int)ral_knob("ATTNW_WAVES", 0);
-  const int nwv = wv_env ? wv_env : 4;
+  const int nwv = 4;
   (void)f16;
   const size_t lds = ((size_t)nwv * T * 18 + 2 * ntab) * sizeof(float);
   int grid = 0;
   auto grid_of = [&](auto kern) {
-    static const int genv = (int)ral_knob("GRID_ATTNW", 0);
     const int gmax = attnw_grid_max(N, H, B);          // (the scratch is sized for one workgroup per four tasks)
-    if (genv > 0) return genv < gmax ? genv : gmax;
     const int occ = ral_occupancy(reinterpret_cast<const void*>(kern), 64 * nwv, lds, 3);
     const int slots = ral_num_cus() * (occ > 8 ? 8 : occ);
     const int need = (ntask + nwv - 1) / nwv;

@@ -1162,20 +1162,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_vkv(const float* __restrict__ 
 // B1: QKV projection + LN1 backward:  dh = dqkv Wqkv;  dx = dx1 + sqrt(C) * LN1bwd(dh)
 //   grads: bqkv, ln1 w/b.   `extra` (optional) is added to dx (skip-connection gradient).
 // =================================================================================
-// FDW (narrow levels, C <= 32): the weight gradient of the projection, dWqkv[m][c] = sum_t dqkv[t][m] LN1(x)[t][c], and its bias
-// gradient are formed HERE - both operands pass through this kernel anyway (dqkv sits in the LDS, the LayerNorm output is one
-// FMA away from the row the LayerNorm backward holds), so the separate token-contraction launch of ral_dw.hip, which read dqkv
-// (3E) and x (E) again from HBM and re-computed the LayerNorm, disappears for these blocks.  Every wave owns NJ (tile, token
-// range) jobs for the whole kernel - fp32 MFMA tiles with the token as the contraction index, accumulators in registers over
-// all the windows of the (persistent) workgroup -; the partials of the token ranges meet in the LDS at the end and leave as
-// one pass of coalesced atomics.
-template <int C> struct QkvDwShape {
-  static constexpr int TM = (3 * C + 15) / 16, TN = (C + 15) / 16, TILES = TM * TN;
-  static constexpr int KS = C == 32 ? 2 : 8;                        // token ranges per tile
-  static constexpr int NJ = TILES * KS / 8;                          // jobs per wave (8 waves)
-  static_assert(TILES * KS % 8 == 0, "whole jobs per wave");
-};
-template <int C, bool FDW = false>
+template <int C>
 // (dqkv, x, dx1 and extra are deliberately NOT __restrict__: see k_dw - loads the compiler can prove invariant are sunk
 // across the compiler barrier of the prefetch, next to their uses, which puts the HBM round trip back in front of them)
 #ifndef RAL_QKVB_MINB
@@ -1189,21 +1176,13 @@ __global__ __launch_bounds__(512, RAL_QKVB_MINB) void k_qkv_bwd(const float* dqk
   constexpr int LD = LDof<C>::v, LPR = C / 4;
   float* DQ = reinterpret_cast<float*>(smem4);  // HM, N x 3C
   float* Dh = DQ + N * 3 * C;                   // N x LD
-  float* Hl = Dh + N * LD;                      // FDW: N x LD, LN1 output (the B operand of the weight-gradient tiles)
-  float* red = Hl + (FDW ? N * LD : 0);         // 2C
+  float* red = Dh + N * LD;                     // 2C
   const int RPP = blockDim.x / LPR;
   const int cq = (threadIdx.x % LPR) * 4;
   const float sqrtC = sqrtf((float)C);
   const float4 gam1 = *reinterpret_cast<const float4*>(w.ln1w + cq);
-  float4 bet1 = make_float4(0.f, 0.f, 0.f, 0.f);
-  if constexpr (FDW) bet1 = *reinterpret_cast<const float4*>(w.ln1b + cq);
   float4 dgam = make_float4(0.f, 0.f, 0.f, 0.f), dbet = make_float4(0.f, 0.f, 0.f, 0.f);
   const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6, lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
-  using DWS = QkvDwShape<C>;
-  f32x4 accw[FDW ? DWS::NJ : 1];
-  float bsw[FDW ? DWS::NJ : 1];
-#pragma unroll
-  for (int j = 0; j < (FDW ? DWS::NJ : 1); ++j) { accw[j] = f32x4{0.f, 0.f, 0.f, 0.f}; bsw[j] = 0.f; }
   // One workgroup per CU is resident next to the weight-gradient kernels, so nothing else hides this kernel's HBM round
   // trips: the next window's operands are requested under the current window's LayerNorm phase.  NQ float4 of dqkv and
   // NR rows of x / dx1 / extra per thread are kept in flight (the BASELINE shapes have N C = 4096: NQ = 6, NR = 2 cover
@@ -1244,7 +1223,6 @@ __global__ __launch_bounds__(512, RAL_QKVB_MINB) void k_qkv_bwd(const float* dqk
     out = f4add(out, d1);
     if (extra) out = f4add(out, e);
     *reinterpret_cast<float4*>(dx + wo + (size_t)row * C + cq) = out;
-    if constexpr (FDW) *reinterpret_cast<float4*>(Hl + row * LD + cq) = f4add(f4mul(xh, gam1), bet1);
     dgam = f4add(dgam, f4mul(dh, xh));
     dbet = f4add(dbet, dh);
   };
@@ -1324,40 +1302,6 @@ __global__ __launch_bounds__(512, RAL_QKVB_MINB) void k_qkv_bwd(const float* dqk
       ln_row(wo, row, *reinterpret_cast<const float4*>(x + o), *reinterpret_cast<const float4*>(pe + row * C + cq),
              *reinterpret_cast<const float4*>(dx1 + o), *reinterpret_cast<const float4*>(ex + o));
     }
-    if constexpr (FDW) {
-      if (gr.wqkv) {   // (frozen weights, ral_backward_input: no weight gradients)
-        lds_barrier();   // the window's LayerNorm output is in Hl; dqkv still in DQ (the next window's prefetch stays in flight)
-        const int tlen = N / DWS::KS;
-        // the jobs of a wave advance together, 16 tokens at a time: the operand reads of all of them are issued before the
-        // first product, and consecutive MFMAs go to different accumulators
-        const float* Ap[DWS::NJ]; const float* Bp[DWS::NJ];
-#pragma unroll
-        for (int j = 0; j < DWS::NJ; ++j) {
-          const int job = wave + 8 * j, tile = job % DWS::TILES, kpart = job / DWS::TILES;
-          const int mi = tile / DWS::TN, nj = tile % DWS::TN;
-          int am = mi * 16 + r, bc = nj * 16 + r;                 // operand columns of this lane, clamped into the matrix
-          am = am < 3 * C ? am : 3 * C - 1;
-          bc = bc < C ? bc : C - 1;
-          Ap[j] = DQ + ((am >> 2) * N + kpart * tlen + 4 * g) * 4 + (am & 3);   // dqkv[t][am] at + 4 t (head-major quads)
-          Bp[j] = Hl + (kpart * tlen + 4 * g) * LD + bc;                        // LN1(x)[t][bc] at + t LD
-        }
-        for (int t0 = 0; t0 < tlen; t0 += 16) {
-          float av[DWS::NJ][4], bv[DWS::NJ][4];
-#pragma unroll
-          for (int j = 0; j < DWS::NJ; ++j)
-#pragma unroll
-            for (int s_ = 0; s_ < 4; ++s_) { av[j][s_] = Ap[j][4 * (t0 + s_)]; bv[j][s_] = Bp[j][(t0 + s_) * LD]; }
-#pragma unroll
-          for (int s_ = 0; s_ < 4; ++s_)
-#pragma unroll
-            for (int j = 0; j < DWS::NJ; ++j) {
-              accw[j] = mfma4(av[j][s_], bv[j][s_], accw[j]);
-              bsw[j] += av[j][s_];
-            }
-        }
-        lds_barrier();   // DQ may take the next window now
-      }
-    }
     if (more) {
       if (pfq) {
 #pragma unroll
@@ -1381,31 +1325,6 @@ __global__ __launch_bounds__(512, RAL_QKVB_MINB) void k_qkv_bwd(const float* dqk
     atomicAdd(gr.ln1w + threadIdx.x, (float)redd[threadIdx.x]);
     atomicAdd(gr.ln1b + threadIdx.x, (float)redd[C + threadIdx.x]);
 #endif
-  }
-  if constexpr (FDW) {
-    if (!gr.wqkv) return;
-    // ---- flush dWqkv / dbqkv: the token-range partials meet in an LDS image of the matrix (3C x C floats + 3C, behind the small
-    // sums above), then consecutive threads add consecutive floats (global float atomics run at full rate for 256 contiguous bytes)
-    float* img = reinterpret_cast<float*>(smem4) + 4 * C + 8;   // (past the 2C doubles of redd)
-    __syncthreads();
-    for (int i = threadIdx.x; i < 3 * C * C + 3 * C; i += blockDim.x) img[i] = 0.f;
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < DWS::NJ; ++j) {
-      const int job = wave + 8 * j, tile = job % DWS::TILES;
-      const int mi = tile / DWS::TN, nj = tile % DWS::TN;
-      const int col = nj * 16 + r;
-#pragma unroll
-      for (int q_ = 0; q_ < 4; ++q_) {
-        const int row = mi * 16 + 4 * g + q_;
-        if (row < 3 * C && col < C) atomicAdd(img + row * C + col, accw[j][q_]);
-      }
-      const float bs = rows_sum(bsw[j]);         // column sums of dqkv over this job's tokens: lane (r, *) holds row mi * 16 + r
-      if (nj == 0 && g == 0 && mi * 16 + r < 3 * C) atomicAdd(img + 3 * C * C + mi * 16 + r, bs);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 3 * C * C; i += blockDim.x) atomicAdd(gr.wqkv + i, img[i]);
-    for (int i = threadIdx.x; i < 3 * C; i += blockDim.x) atomicAdd(gr.bqkv + i, img[3 * C * C + i]);
   }
 }
 
@@ -1941,8 +1860,7 @@ __global__ void k_conv1_bwd_dx(const float* __restrict__ dz, const float* __rest
 // box, ms per step): k_qkv_bwd at 128: 17.22, 160: 17.13, 192: 17.12, 224: 17.84 (1024 windows over 224 workgroups leave
 // a ragged last round), 256: 17.29 - the CUs it leaves free go to the weight-gradient kernels running beside it; then
 // k_mlp_bwd_s at 256: 17.11, 320: 17.08, 384: 16.99, 448: 17.02, 512: 17.04.
-// (RAL_GRID_QKVB / RESB / MLPB / MLPS / ATTNB override.)
-static inline int env_grid(const char* name, int dflt) { return (int)ral_knob(name + 4, dflt); }   // (name = "RAL_<KNOB>")
+static constexpr int GRID_QKVB = 192, GRID_RESB = 256, GRID_MLPB = 512, GRID_MLPS = 384, GRID_ATTNB = 8192;
 static inline int cap(int items, int gmax) { return items < gmax ? items : gmax; }
 static inline int ew_grid(size_t n, int per = 256) {
   size_t g = (n + per - 1) / per;
@@ -1989,53 +1907,42 @@ static bool launch_mlp_bwd_s(const float* dx2, const float* x1, const BlockP& w,
   // no longer negligible on the critical stream, so the gain flattens)
   int tw; size_t lds;
   if (!mlp_bwd_s_applies<C>(N, &tw, &lds)) return false;
-  static const int gs = env_grid("RAL_GRID_MLPS", 384);
-  const int grid = cap(B, gs);
+  const int grid = cap(B, GRID_MLPS);
 #define GO(t) { RAL_SET_LDS((k_mlp_bwd_s<C, t>), lds); k_mlp_bwd_s<C, t><<<grid, 512, lds, s>>>(dx2, x1, w, wt, gr, dx1, do_hm, N, B, want_dw ? 1 : 0, NE); return true; }
   switch (tw) { case 1: GO(1) case 2: GO(2) case 4: GO(4) case 8: GO(8) default: return false; }
 #undef GO
 }
 
-// wide levels on split fp16 operands (RAL_MLP_F16=0: the fp32-MFMA kernel everywhere): the hidden-chunk count that gives
-// the fc2^T phase exactly one 32 x 32 unit per wave and fits the LDS budget, or 0
+// wide levels on split fp16 operands: the hidden-chunk count that gives the fc2^T phase exactly one 32 x 32 unit per wave and
+// fits the LDS budget, or 0
 size_t mlp_bwd_h_lds(int C, int N, int nch, bool small = false) {   // small: the four-wave form (no separate dg tile)
   const int HC = 4 * C / nch;
   return (size_t)2 * N * ldb_of(C) * 2 + (small ? 0 : (size_t)N * ld_of(C) * 4) + (size_t)N * (HC + 8) * 4 + ((size_t)2 * (N + 2) + 5 * N + 2 * C + 4) * 4;
 }
-// Threads of a k_mlp_bwd_h workgroup (MLPB_HTHREADS).  256 (default): four waves, 37-39 KB of LDS, 150 registers per lane, three
-// workgroups per CU; 512: eight waves, 75-78 KB, 128 registers (28-68 bytes of scratch), two per CU.  Measured at batch 2048: the
-// four-wave form is the SLOWER kernel on an empty GPU (`mlp_bwd` 2.66 -> 2.76 ms per step serialised) and the faster training step
-// (12.98 -> 12.88 ms, 13.57 -> 13.42 on a slower box; interleaved A/B, three rounds each).  What it changes beside the other lane's
-// kernels and the 76 KB weight-gradient workgroups: half the LDS and half the waves per workgroup, no spills, and no dg
-// read-modify-write through LDS per hidden chunk (k_qkv_bwd_h with half the LDS and waves alone - QKVB_SEG - did not move the step).
-static int mlp_bwd_h_threads() {
-  static const int t = (int)ral_knob("MLPB_HTHREADS", 256);
-  return t == 512 ? 512 : 256;
-}
+// Threads of a k_mlp_bwd_h workgroup: 256 (nch > 0): four waves, 37-39 KB of LDS, 150 registers per lane, three workgroups per
+// CU; 512 (nch < 0): eight waves, 75-78 KB, 128 registers (28-68 bytes of scratch), two per CU - the shapes the four-wave form does
+// not cover.  Measured at batch 2048 on the shapes both take: the four-wave form is the SLOWER kernel on an empty GPU (`mlp_bwd`
+// 2.66 -> 2.76 ms per step serialised) and the faster training step (12.98 -> 12.88 ms, 13.57 -> 13.42 on a slower box;
+// interleaved A/B, three rounds each).  What it changes beside the other lane's kernels and the 76 KB weight-gradient
+// workgroups: half the LDS and half the waves per workgroup, no spills, and no dg read-modify-write through LDS per hidden chunk
+// (k_qkv_bwd_h with half the LDS and waves alone - half-window work items - did not move the step).
 int mlp_bwd_h_nch(int C, int N) {
-  static const bool on = (ral_knob("MLP_F16", 1) != 0);
-  if (!on || (C != 32 && C != 64 && C != 128) || N % 32 != 0) return 0;
-  const int nwaves = mlp_bwd_h_threads() / 64;
-  if (nwaves == 4) {   // N C = 4096: one 32 x 32 unit of dg per wave; HC + 8 >= C + 4: the dg tile fits the chunk's bytes
-    for (int nch = 1; nch <= 4; nch *= 2)
-      if (N * C == 4096 && 4 * C / nch >= C && (4 * C / nch / 32) * (N / 32) == 4 && mlp_bwd_h_lds(C, N, nch, true) <= 54400) return nch;
-  } else
+  if ((C != 32 && C != 64 && C != 128) || N % 32 != 0) return 0;
+  // four waves: N C = 4096, one 32 x 32 unit of dg per wave; HC + 8 >= C + 4: the dg tile fits the chunk's bytes
   for (int nch = 1; nch <= 4; nch *= 2)
-    if ((4 * C / nch / 32) * (N / 32) == 8 && mlp_bwd_h_lds(C, N, nch) <= 79872) return nch;
-  if (nwaves != 8)   // (a shape the small workgroups do not cover keeps the eight-wave form)
-    for (int nch = 1; nch <= 4; nch *= 2)
-      if ((4 * C / nch / 32) * (N / 32) == 8 && mlp_bwd_h_lds(C, N, nch) <= 79872) return -nch;
+    if (N * C == 4096 && 4 * C / nch >= C && (4 * C / nch / 32) * (N / 32) == 4 && mlp_bwd_h_lds(C, N, nch, true) <= 54400) return nch;
+  for (int nch = 1; nch <= 4; nch *= 2)   // eight waves
+    if ((4 * C / nch / 32) * (N / 32) == 8 && mlp_bwd_h_lds(C, N, nch) <= 79872) return -nch;
   return 0;
 }
 template <int C>
 static void launch_mlp_bwd_hc(int nch, const float* dx2, const float* x1, const float* upre, const BlockP& w, const BlockP& wt,
                               const float* ptbase, const void* wtt, const BlockP& gr, float* dupre, float* dx1, float* do_hm,
                               float* a2c0, unsigned* gmax, int N, int B, hipStream_t s) {
-  const bool small = nch > 0 && mlp_bwd_h_threads() == 256;
+  const bool small = nch > 0;
   if (nch < 0) nch = -nch;
   const size_t lds = mlp_bwd_h_lds(C, N, nch, small);
-  static const int gm = env_grid("RAL_GRID_MLPB", 512);
-  const int grid = cap(B, small ? gm * 3 / 2 : gm);
+  const int grid = cap(B, small ? GRID_MLPB * 3 / 2 : GRID_MLPB);
   const _Float16* wp = reinterpret_cast<const _Float16*>(wtt);
   if (small) {
     if (nch == 2) { RAL_SET_LDS((k_mlp_bwd_h<C, 2, 256>), lds); k_mlp_bwd_h<C, 2, 256><<<grid, 256, lds, s>>>(dx2, x1, upre, w, wt, ptbase, wp, gr, dupre, dx1, do_hm, a2c0, gmax, N, B); }
@@ -2055,8 +1962,7 @@ static bool launch_mlp_bwd_c(int nch, const float* dx2, const float* x1, const f
     if (launch_mlp_bwd_s<C>(dx2, x1, w, wt, gr, dx1, do_hm, N, B, want_dw, s, NE)) return true;
   }
   const size_t lds = mlp_bwd_lds(C, N, nch);
-  static const int gm = env_grid("RAL_GRID_MLPB", 512);
-  const int grid = cap(B, gm);
+  const int grid = cap(B, GRID_MLPB);
   if (nch == 1) { RAL_SET_LDS((k_mlp_bwd<C, 1>), lds); k_mlp_bwd<C, 1><<<grid, 512, lds, s>>>(dx2, x1, upre, w, wt, gr, dupre, dx1, do_hm, a2c0, N, B, NE); }
   else if (nch == 2) { RAL_SET_LDS((k_mlp_bwd<C, 2>), lds); k_mlp_bwd<C, 2><<<grid, 512, lds, s>>>(dx2, x1, upre, w, wt, gr, dupre, dx1, do_hm, a2c0, N, B, NE); }
   else { RAL_SET_LDS((k_mlp_bwd<C, 4>), lds); k_mlp_bwd<C, 4><<<grid, 512, lds, s>>>(dx2, x1, upre, w, wt, gr, dupre, dx1, do_hm, a2c0, N, B, NE); }
@@ -2099,14 +2005,9 @@ size_t attn_bwd_lds(int N, int HG, int Len) {
 // kernel vs scalar path).  Without an R-wave table: N = 512: 790 / 853, 256: 446 / 464, 128: 285 / 265, 64: 208 / 155;
 // with one (the in-window keys cost two lane gathers each, plus the partial-sum pass): 128: 285 / 293, 64: 208 / 192, and
 // inside the training step (bench.py --kinds) the N = 64 case with a table came out 2 % slower than the MFMA-tile kernel.
-// So: N <= 128 without a table, never with one.  The switches ATTN_BWD_V_LO / _HI force a range for both cases (0 / 0 = never).
+// So: N <= 128 without a table, never with one.
 bool attn_bwd_uses_stat2(int N, int Len, bool table) {
-  static int lo = -1, hi = -1;
-  static const bool init = [] { lo = (int)ral_knob("ATTN_BWD_V_LO", -1); hi = (int)ral_knob("ATTN_BWD_V_HI", -1); return true; }();
-  (void)init;
-  if (N < 64 || N % 4 != 0 || (table && 2 * Len - 1 > 64)) return false;
-  if (lo >= 0) return N >= lo && N <= hi;
-  return !table && N <= 128;
+  return !table && N >= 64 && N <= 128 && N % 4 == 0;
 }
 
 size_t attn_bwd_scratch_floats(int N, int H, int Len, bool table, int B) {
@@ -2162,31 +2063,24 @@ void launch_attn_bwd(const float* qkv, const float* o_hm, const float* do_hm, co
     }
     return;
   }
-  static const int split_env = (int)ral_knob("ATTN_SPLIT", 2);   // see launch_attn_fwd
-  int split = split_env;
-  while (split > 1 && (HG % split != 0 || N % 32 != 0)) split /= 2;
-  if (split > 1) {
-    const int hg = HG / split;
+  if (HG % ATTN_SPLIT == 0 && N % 32 == 0) {   // workgroup split (ral_kernels.hpp)
+    const int hg = HG / ATTN_SPLIT;
     const size_t l2 = attn_bwd_lds(N, hg, Len);
     const int it2 = B * (H / hg);
-    static const bool nt_off = (ral_knob("ATTNB_NT0", 0) != 0);   // experiment knob: run-time window length everywhere
-    const int grid2 = cap(it2, env_grid("RAL_GRID_ATTNB", 8192));
+    const int grid2 = cap(it2, GRID_ATTNB);
 #define NTCASE(n, tab) { RAL_SET_LDS((k_attn_bwd<2, n, tab>), l2); \
-      k_attn_bwd<2, n, tab><<<grid2, 512 / split, l2, s>>>(qkv, o_hm, do_hm, lse, table, gtable, dqkv, N, H, hg, Len, B); return; }
-    if (!nt_off) {
-      if (N == 32 && !table) NTCASE(32, false)
-      if (N == 64 && table) NTCASE(64, true)
-    }
+      k_attn_bwd<2, n, tab><<<grid2, 512 / ATTN_SPLIT, l2, s>>>(qkv, o_hm, do_hm, lse, table, gtable, dqkv, N, H, hg, Len, B); return; }
+    if (N == 32 && !table) NTCASE(32, false)
+    if (N == 64 && table) NTCASE(64, true)
 #undef NTCASE
     RAL_SET_LDS((k_attn_bwd<2>), l2);
-    k_attn_bwd<2><<<grid2, 512 / split, l2, s>>>(qkv, o_hm, do_hm, lse, table, gtable, dqkv, N, H, hg, Len, B);
+    k_attn_bwd<2><<<grid2, 512 / ATTN_SPLIT, l2, s>>>(qkv, o_hm, do_hm, lse, table, gtable, dqkv, N, H, hg, Len, B);
     return;
   }
   const size_t lds = attn_bwd_lds(N, HG, Len);
   const int items = B * (H / HG);
   const int grid = items < 4096 ? items : 4096;
-  static const bool force1 = (ral_knob("ATTN_QT1", 0) != 0);   // experiment knob
-  if (N % 32 == 0 && !force1) {
+  if (N % 32 == 0) {
     RAL_SET_LDS((k_attn_bwd<2>), lds);
     k_attn_bwd<2><<<grid, 512, lds, s>>>(qkv, o_hm, do_hm, lse, table, gtable, dqkv, N, H, HG, Len, B);
   } else {
@@ -2196,72 +2090,36 @@ void launch_attn_bwd(const float* qkv, const float* o_hm, const float* do_hm, co
 }
 
 size_t qkv_bwd_lds(int C, int N) { return ((size_t)N * 3 * C + (size_t)N * ld_of(C) + 5 * C + 8) * sizeof(float); }
-// QKVB_FDW = 1: the narrow levels form the projection's weight gradient inside k_qkv_bwd instead of the separate launch of
-// ral_dw.hip.  Built in round 6 for its HBM bytes (-4E per narrow block: 0.5 GB of the step's 33 GB) and measured: the
-// weight-gradient kind 2.91 -> 2.51 ms per step serialised, k_qkv_bwd 1.10 -> 1.35 ms - and the STEP 0.06 ms slower (12.90 ->
-// 12.96 ms, same box, three interleaved rounds): the separate launch runs on the side stream and is bound by HBM, which the
-// chain kernels beside it leave idle; inside k_qkv_bwd the same product is fp32-MFMA tiles fed by 4-byte LDS reads on the
-// critical path.  Default OFF; the switch and tests/test_gpu_configs.py keep it alive.
-bool qkv_bwd_fuses_dw(int C, int N) {
-  static const bool on = (ral_knob("QKVB_FDW", 0) != 0);
-  if (!on || C > 32) return false;
-  const int ks = C == 32 ? 2 : 8;
-  if (qkv_bwd_lds(C, N) + (size_t)N * ld_of(C) * sizeof(float) > 156 * 1024) return false;   // (C = 8 at 1024 tokens: the LayerNorm-output tile does not fit)
-  return N % (16 * ks) == 0;
-}
-
 bool qkv_bwd_uses_f16(int C, int N) {
-  static const bool on = (ral_knob("QKVB_F16", 1) != 0);
-  return on && (C == 32 || C == 64 || C == 128) && N % 32 == 0 && N * 3 * C / 4 <= 6 * 512;
+  return (C == 32 || C == 64 || C == 128) && N % 32 == 0 && N * 3 * C / 4 <= 6 * 512;
 }
-bool launch_qkv_bwd(int C, const float* dqkv, const float* x, const float* pe, const float* dx1, const float* extra,
+void launch_qkv_bwd(int C, const float* dqkv, const float* x, const float* pe, const float* dx1, const float* extra,
                     const BlockP& w, const BlockP& wt, const float* ptbase, const void* wtt, unsigned* gmax, const BlockP& gr, float* dx, int N, int B,
-                    bool want_dw, hipStream_t s) {
-  static const int gq = env_grid("RAL_GRID_QKVB", 192);
-  const int grid = cap(B, gq);
+                    hipStream_t s) {
+  const int grid = cap(B, GRID_QKVB);
   if (wtt && qkv_bwd_uses_f16(C, N)) {
-    // QKVB_SEG = 2: a work item is HALF a window (four-wave workgroups, half the LDS) where half a window still is a whole number of
-    // 32-token product units and one prefetch round of 256 threads (N C = 4096, N >= 64).  Measured: `qkv_bwd` 1.105 -> 1.075 ms per
-    // step serialised, the step unchanged (13.03 / 13.02 ms, and flat over grids of 128 .. 256 workgroups): default off.
-    static const int seg = (int)ral_knob("QKVB_SEG", 1);
-    const int NS = (seg == 2 && N * C == 4096 && N % 64 == 0) ? 2 : 1, NT = N / NS, nth = 512 / NS;
-    const size_t ldsh = (size_t)2 * NT * ldb_of(3 * C) * 2 + ((size_t)NT * ld_of(C) + 2 * C + 2 * NT) * 4;
+    // a work item is a whole window (NS = 1).  Half-window items (NS = 2: four-wave workgroups, half the LDS) measured `qkv_bwd`
+    // 1.105 -> 1.075 ms per step serialised and the step unchanged.
+    const size_t ldsh = (size_t)2 * N * ldb_of(3 * C) * 2 + ((size_t)N * ld_of(C) + 2 * C + 2 * N) * 4;
     const _Float16* wp = reinterpret_cast<const _Float16*>(wtt);
-    const int gridh = NS == 1 ? grid : (cap(B * NS, gq * NS) / NS) * NS;
-    if (C == 32) { RAL_SET_LDS((k_qkv_bwd_h<32>), ldsh); k_qkv_bwd_h<32><<<gridh, nth, ldsh, s>>>(dqkv, x, pe, dx1, extra, w, wt, ptbase, wp, gr, dx, gmax, N, B, NS); }
-    else if (C == 64) { RAL_SET_LDS((k_qkv_bwd_h<64>), ldsh); k_qkv_bwd_h<64><<<gridh, nth, ldsh, s>>>(dqkv, x, pe, dx1, extra, w, wt, ptbase, wp, gr, dx, gmax, N, B, NS); }
-    else { RAL_SET_LDS((k_qkv_bwd_h<128>), ldsh); k_qkv_bwd_h<128><<<gridh, nth, ldsh, s>>>(dqkv, x, pe, dx1, extra, w, wt, ptbase, wp, gr, dx, gmax, N, B, NS); }
-    return false;
+    if (C == 32) { RAL_SET_LDS((k_qkv_bwd_h<32>), ldsh); k_qkv_bwd_h<32><<<grid, 512, ldsh, s>>>(dqkv, x, pe, dx1, extra, w, wt, ptbase, wp, gr, dx, gmax, N, B, 1); }
+    else if (C == 64) { RAL_SET_LDS((k_qkv_bwd_h<64>), ldsh); k_qkv_bwd_h<64><<<grid, 512, ldsh, s>>>(dqkv, x, pe, dx1, extra, w, wt, ptbase, wp, gr, dx, gmax, N, B, 1); }
+    else { RAL_SET_LDS((k_qkv_bwd_h<128>), ldsh); k_qkv_bwd_h<128><<<grid, 512, ldsh, s>>>(dqkv, x, pe, dx1, extra, w, wt, ptbase, wp, gr, dx, gmax, N, B, 1); }
+    return;
   }
   const size_t lds = qkv_bwd_lds(C, N);
-  if (qkv_bwd_fuses_dw(C, N)) {   // narrow levels: weight gradient of the projection inside the kernel
-    size_t ldsf = lds + (size_t)N * ld_of(C) * sizeof(float);
-    const size_t img = ((size_t)4 * C + 8 + 3 * C * C + 3 * C) * sizeof(float);
-    if (ldsf < img) ldsf = img;
-    BlockP g2 = gr;
-    if (!want_dw) g2.wqkv = nullptr;   // (frozen weights: the kernel skips the tiles)
-    switch (C) {
-#define CASE(c) case c: RAL_SET_LDS((k_qkv_bwd<c, true>), ldsf); \
-      k_qkv_bwd<c, true><<<grid, 512, ldsf, s>>>(dqkv, x, pe, dx1, extra, w, wt, g2, dx, N, B); break;
-      CASE(8) CASE(16) CASE(32)
-#undef CASE
-    }
-    return true;
-  }
   switch (C) {
 #define CASE(c) case c: RAL_SET_LDS((k_qkv_bwd<c>), lds); \
     k_qkv_bwd<c><<<grid, 512, lds, s>>>(dqkv, x, pe, dx1, extra, w, wt, gr, dx, N, B); break;
     CASE(8) CASE(16) CASE(32) CASE(64) CASE(128)
 #undef CASE
   }
-  return false;
 }
 
 void launch_resample_bwd(int D, bool sep, const float* dy, const float* x, const float* wred, const float* lnw,
                          float* g_lnw, float* g_lnb, float* dx, int T, int Tv, int B, hipStream_t s) {
   const size_t lds = ((size_t)2 * T * ld_of(D) + 2 * D + 4) * sizeof(float);
-  static const int gr = env_grid("RAL_GRID_RESB", 256);
-  const int grid = cap(B, gr);
+  const int grid = cap(B, GRID_RESB);
 #define CASE(d) case d: if (sep) { RAL_SET_LDS((k_resample_bwd<d, true>), lds); k_resample_bwd<d, true><<<grid, 256, lds, s>>>(dy, x, wred, lnw, g_lnw, g_lnb, dx, T, Tv, B); } \
                         else { RAL_SET_LDS((k_resample_bwd<d, false>), lds); k_resample_bwd<d, false><<<grid, 256, lds, s>>>(dy, x, wred, lnw, g_lnw, g_lnb, dx, T, Tv, B); } break;
   switch (D) { CASE(8) CASE(16) CASE(32) CASE(64) CASE(128) }

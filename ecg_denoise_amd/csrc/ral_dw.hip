@@ -44,7 +44,7 @@ constexpr int dw_tile_floats(int w, bool hm, int tc) { return hm ? (w / 4) * (tc
 #define RAL_DW_MINWG 192
 #endif
 // (LDS of a workgroup's two staging buffers; smaller chunks co-reside more easily with the chain kernels' workgroups but
-// were measured slower on the step: RAL_DW_LDS = 40 000: 17.74 ms, 24 000: 18.01 ms against 17.04 at the full 76 KB)
+// were measured slower on the step: a budget of 40 000 bytes: 17.74 ms, 24 000: 18.01 ms against 17.04 at the full 76 KB)
 #ifndef RAL_DW_LDS_BYTES
 #define RAL_DW_LDS_BYTES (76 * 1024)
 #endif
@@ -506,9 +506,6 @@ __global__ __launch_bounds__(512, RAL_DW_WPE) void k_dw(const float* Y, const fl
 }
 
 // ---------------------------------------------------------------------------------
-static size_t g_dw_budget = RAL_DW_LDS_BYTES;
-void set_dw_lds_budget(size_t bytes) { g_dw_budget = bytes < (size_t)RAL_DW_LDS_BYTES ? bytes : (size_t)RAL_DW_LDS_BYTES; }
-
 template <int M, int NC, int MS, int NS, int LAYY, int XF>
 static void launch_dw_t(const float* Y, const float* X, const float* pe, const float* lnw, const float* lnb,
                         const float* a2c0, float* dW, float* dB, int N, int B, int ksplit, hipStream_t s,
@@ -528,8 +525,8 @@ static void launch_dw_t(const float* Y, const float* X, const float* pe, const f
     if (ymax) {   // split operands (token chunks of at least one 32-token MFMA step)
       int TC = dw_tcmax(MS, NS, yhm, xhm, XF == XF_LNPE);
       auto bytesh = [&](int tc) { return (size_t)2 * tc * (MS + 8 + NS + 8) * sizeof(float); };
-      while (TC > 32 && (N % TC != 0 || bytesh(TC) > g_dw_budget)) TC /= 2;
-      if (TC >= 32 && N % TC == 0 && bytesh(TC) <= g_dw_budget + 4096) {
+      while (TC > 32 && (N % TC != 0 || bytesh(TC) > RAL_DW_LDS_BYTES)) TC /= 2;
+      if (TC >= 32 && N % TC == 0 && bytesh(TC) <= RAL_DW_LDS_BYTES + 4096) {
         const size_t lds = bytesh(TC) > fold ? bytesh(TC) : fold;
         RAL_SET_LDS((k_dw<M, NC, MS, NS, LAYY, XF, true>), lds);
         k_dw<M, NC, MS, NS, LAYY, XF, true><<<grid, 512, lds, s>>>(Y, X, pe, lnw, lnb, a2c0, dW, dB, ymax, xscale, N, TC, B, NV);
@@ -540,7 +537,7 @@ static void launch_dw_t(const float* Y, const float* X, const float* pe, const f
   // largest power-of-two token chunk dividing N within the compile-time staging bound and the LDS budget
   int TC = dw_tcmax(MS, NS, yhm, xhm, XF == XF_LNPE);
   auto bytes = [&](int tc) { return (size_t)2 * (dw_tile_floats(MS, yhm, tc) + dw_tile_floats(NS, xhm, tc)) * sizeof(float); };
-  while (TC > 16 && (N % TC != 0 || bytes(TC) > g_dw_budget)) TC /= 2;
+  while (TC > 16 && (N % TC != 0 || bytes(TC) > RAL_DW_LDS_BYTES)) TC /= 2;
   const size_t lds = bytes(TC) > fold ? bytes(TC) : fold;
   RAL_SET_LDS((k_dw<M, NC, MS, NS, LAYY, XF>), lds);
   k_dw<M, NC, MS, NS, LAYY, XF><<<grid, 512, lds, s>>>(Y, X, pe, lnw, lnb, a2c0, dW, dB, nullptr, nullptr, N, TC, B, NV);
@@ -554,23 +551,21 @@ template <int W> struct SliceOf { static constexpr int v = W > RAL_DW_SLICE ? ((
 template <int C>
 static void launch_block_dw_c(const float* dx2, const float* upre, const float* a2c0, const float* dupre, const float* x1,
                               const float* dx1, const float* o_hm, const float* dqkv, const float* x, const float* pe,
-                              const BlockP& w, const BlockP& gr, int N, int B, int ks, bool skip_mlp, const unsigned* gmax, hipStream_t s, bool skip_qkv) {
-  static const bool h_on = (ral_knob("DW_F16", 1) != 0);
-  const unsigned* gm = (h_on && C >= 32) ? gmax : nullptr;
+                              const BlockP& w, const BlockP& gr, int N, int B, int ks, bool skip_mlp, const unsigned* gmax, hipStream_t s) {
+  const unsigned* gm = C >= 32 ? gmax : nullptr;
   if (!skip_mlp) {
   launch_dw_t<C, 4 * C, C, SliceOf<4 * C>::v, LAY_TOK, XF_A2>(dx2, upre, nullptr, nullptr, nullptr, a2c0, gr.w2, gr.b2, N, B, ks, s, gm ? gm + 0 : nullptr, w.asc ? w.asc + ASC_HID : nullptr);
   launch_dw_t<4 * C, C, SliceOf<4 * C>::v, C, LAY_TOK, XF_LN>(dupre, x1, nullptr, w.ln2w, w.ln2b, nullptr, gr.w1, gr.b1, N, B, ks, s, gm ? gm + 1 : nullptr, w.asc ? w.asc + ASC_LN2 : nullptr);
   }
   launch_dw_t<C, C, SliceOf<C>::v, C, LAY_TOK, XF_HM>(dx1, o_hm, nullptr, nullptr, nullptr, nullptr, gr.wp, gr.bp, N, B, ks, s, gm ? gm + 2 : nullptr, w.asc ? w.asc + ASC_O : nullptr);
-  if (!skip_qkv)
   launch_dw_t<3 * C, C, SliceOf<3 * C>::v, C, LAY_HM, XF_LNPE>(dqkv, x, pe, w.ln1w, w.ln1b, nullptr, gr.wqkv, gr.bqkv, N, B, ks, s, gm ? gm + 3 : nullptr, w.asc ? w.asc + ASC_LN1 : nullptr);
 }
 
 void launch_block_dw(int C, const float* dx2, const float* upre, const float* a2c0, const float* dupre, const float* x1,
                      const float* dx1, const float* o_hm, const float* dqkv, const float* x, const float* pe,
-                     const BlockP& w, const BlockP& gr, int N, int B, int ksplit, bool skip_mlp, const unsigned* gmax, hipStream_t s, bool skip_qkv) {
+                     const BlockP& w, const BlockP& gr, int N, int B, int ksplit, bool skip_mlp, const unsigned* gmax, hipStream_t s) {
   switch (C) {
-#define CASE(c) case c: launch_block_dw_c<c>(dx2, upre, a2c0, dupre, x1, dx1, o_hm, dqkv, x, pe, w, gr, N, B, ksplit, skip_mlp, gmax, s, skip_qkv); break;
+#define CASE(c) case c: launch_block_dw_c<c>(dx2, upre, a2c0, dupre, x1, dx1, o_hm, dqkv, x, pe, w, gr, N, B, ksplit, skip_mlp, gmax, s); break;
     CASE(8) CASE(16) CASE(32) CASE(64) CASE(128)
 #undef CASE
   }

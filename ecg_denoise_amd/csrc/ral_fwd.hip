@@ -415,7 +415,7 @@ RAL_DEV void put_pair_planes(float* X, int t, float4 x) {
 // slots, ral_api.hip): keys past NE are masked out of the softmax (s = -inf), the R-wave window is centred in the NE tokens;
 // the padding queries are computed like any other (their rows are never used)
 template <int QT, int NT = 0, bool TAB = true, bool F16 = false, bool RAG = false>
-__global__ __launch_bounds__(512, (QT >= 4 ? 3 : 4)) void k_attn_fwd(const float* __restrict__ qkv, float* __restrict__ o_hm,
+__global__ __launch_bounds__(512, 4) void k_attn_fwd(const float* __restrict__ qkv, float* __restrict__ o_hm,
                                                   float* __restrict__ lse, const float* __restrict__ table,
                                                   int N_rt, int H, int HG, int Len, int B, int NE_rt = 0) {
   extern __shared__ float4 smem4[];
@@ -1010,10 +1010,8 @@ __global__ void k_add(const float* __restrict__ a, const float* __restrict__ b, 
 // =================================================================================
 // host launchers
 // =================================================================================
-static inline int grid_for(int items) {
-  static const int gmax = (int)ral_knob("GRID_FWD", 4096);
-  return items < gmax ? items : gmax;
-}
+static constexpr int GRID_FWD = 4096;   // workgroup cap of the persistent forward kernels
+static inline int grid_for(int items) { return items < GRID_FWD ? items : GRID_FWD; }
 
 // widths whose projection has a split-operand kernel (the caller passes the tiled weight planes to choose it)
 bool qkv_fwd_uses_f16(int C) { return C == 32 || C == 64 || C == 128; }
@@ -1029,16 +1027,14 @@ void launch_qkv_fwd(int C, const float* x, const float* pe, const BlockP& w, con
       kern<<<(int)(ngroups < wgs ? ngroups : wgs), 256, ldsb, s>>>(x, pe, w, wtp, qkv, N, B);
     };
     // weight-stationary kernel: one workgroup per CU (C = 128) / two (C = 64), token groups of 64 = whole windows
-    static const bool ws = (ral_knob("QKV_WS", 1) != 0);
     auto gows = [&](auto kern, int C_, int per_cu) {
       const size_t ldsb = (size_t)2 * 2 * 64 * ldb_of(C_) * 2;
       RAL_SET_LDS(kern, ldsb);
       const long ngroups = ((long)B * N + 63) / 64;
-      static const int gq = (int)ral_knob("GRID_QKVW", 0);
-      const int wgs = gq > 0 ? gq : 256 * per_cu;
+      const int wgs = 256 * per_cu;
       kern<<<(int)(ngroups < wgs ? ngroups : wgs), 6 * C_, ldsb, s>>>(x, pe, w, wtp, qkv, N, B);
     };
-    if (ws && 64 % N == 0) {
+    if (64 % N == 0) {
       if (C == 64) { gows(k_qkv_fwd_ws<64, 64>, 64, 2); return; }
       if (C == 128) { gows(k_qkv_fwd_ws<128, 64>, 128, 1); return; }
     }
@@ -1067,54 +1063,39 @@ void launch_attn_fwd(const float* qkv, float* o_hm, float* lse, const float* tab
     return;
   }
   if (attn_fwd_w_takes(N, H, Len, table != nullptr)) { launch_attn_fwd_w(qkv, o_hm, lse, table, N, H, Len, B, f16, s); return; }
-  // Window lengths [lo, hi] that take the query-per-lane kernel on the scalar path.  Measured at batch 2048
+  // Window lengths [64, 256] take the query-per-lane kernel on the scalar path.  Measured at batch 2048
   // (tools/attn_bench.py, us per launch, MFMA-tile kernel vs scalar path): N = 512: 322 / 333, 256: 184 / 172,
-  // 128: 122 / 90, 64: 91 / 51.  The switches ATTN_FWD_V_LO / _HI override (0 / 0 = never).
-  static int vlo = 64, vhi = 256;
-  static const bool vinit = [] { vlo = (int)ral_knob("ATTN_FWD_V_LO", vlo); vhi = (int)ral_knob("ATTN_FWD_V_HI", vhi); return true; }();
-  (void)vinit;
+  // 128: 122 / 90, 64: 91 / 51.
   // with the S tile on the f16 matrix cores the tile kernel takes the long windows from the scalar path again
   // (RAL_ATTN_FWD_H = smallest such N, 0 = never)
   static const int hlo = (int)ral_knob("ATTN_FWD_H", 256);
   const bool tile16 = f16 && hlo > 0 && N >= hlo && N % 32 == 0;
-  if (!tile16 && N >= vlo && N <= vhi && N >= 64 && N % 4 == 0 && (!table || 2 * Len - 1 <= 64)) {
+  if (!tile16 && N >= 64 && N <= 256 && N % 4 == 0 && (!table || 2 * Len - 1 <= 64)) {
     const int ntask = B * H * ((N + 63) / 64);
     if (table) k_attn_fwd_v<true><<<(ntask + 3) / 4, 256, 0, s>>>(qkv, o_hm, lse, table, N, H, Len, ntask);
     else k_attn_fwd_v<false><<<(ntask + 3) / 4, 256, 0, s>>>(qkv, o_hm, lse, table, N, H, 0, ntask);
     return;
   }
-  // Workgroup split: 1 / SPLIT of the head group per item and 512 / SPLIT threads, so that 2 * SPLIT workgroups share
-  // a CU and one's staging latency and barrier waits hide behind the others' tiles (same waves per CU, same LDS).
-  // Measured at batch 2048 (fwd + bwd attention, ms per step): split 1: 7.76, split 2: 7.53 (RAL_ATTN_SPLIT).
-  static const int split_env = (int)ral_knob("ATTN_SPLIT", 2);
-  int split = split_env;
-  while (split > 1 && (HG % split != 0 || N % 32 != 0)) split /= 2;
-  if (split > 1) {
-    const int hg = HG / split;
+  if (HG % ATTN_SPLIT == 0 && N % 32 == 0) {   // workgroup split (ral_kernels.hpp)
+    const int hg = HG / ATTN_SPLIT;
     const size_t l2 = attn_fwd_lds(N, hg, Len);
-    static const bool nt_off = (ral_knob("ATTNF_NT0", 0) != 0);   // experiment knob: run-time window length everywhere
-    if (N == 32 && !table && !nt_off) {
+    if (N == 32 && !table) {
       RAL_SET_LDS((k_attn_fwd<2, 32, false>), l2);
-      k_attn_fwd<2, 32, false><<<grid_for(B * (H / hg)), 512 / split, l2, s>>>(qkv, o_hm, lse, table, N, H, hg, Len, B);
+      k_attn_fwd<2, 32, false><<<grid_for(B * (H / hg)), 512 / ATTN_SPLIT, l2, s>>>(qkv, o_hm, lse, table, N, H, hg, Len, B);
       return;
     }
     if (tile16) {
       RAL_SET_LDS((k_attn_fwd<2, 0, true, true>), l2);
-      k_attn_fwd<2, 0, true, true><<<grid_for(B * (H / hg)), 512 / split, l2, s>>>(qkv, o_hm, lse, table, N, H, hg, Len, B);
+      k_attn_fwd<2, 0, true, true><<<grid_for(B * (H / hg)), 512 / ATTN_SPLIT, l2, s>>>(qkv, o_hm, lse, table, N, H, hg, Len, B);
       return;
     }
     RAL_SET_LDS((k_attn_fwd<2>), l2);
-    k_attn_fwd<2><<<grid_for(B * (H / hg)), 512 / split, l2, s>>>(qkv, o_hm, lse, table, N, H, hg, Len, B);
+    k_attn_fwd<2><<<grid_for(B * (H / hg)), 512 / ATTN_SPLIT, l2, s>>>(qkv, o_hm, lse, table, N, H, hg, Len, B);
     return;
   }
   const size_t lds = attn_fwd_lds(N, HG, Len);
   const int items = B * (H / HG);
-  static const bool force1 = (ral_knob("ATTN_QT1", 0) != 0);   // experiment knobs
-  static const bool force4 = (ral_knob("ATTN_QT4", 0) != 0);
-  if (N % 64 == 0 && force4) {
-    RAL_SET_LDS((k_attn_fwd<4>), lds);
-    k_attn_fwd<4><<<grid_for(items), 512, lds, s>>>(qkv, o_hm, lse, table, N, H, HG, Len, B);
-  } else if (N % 32 == 0 && !force1) {
+  if (N % 32 == 0) {
     RAL_SET_LDS((k_attn_fwd<2>), lds);
     k_attn_fwd<2><<<grid_for(items), 512, lds, s>>>(qkv, o_hm, lse, table, N, H, HG, Len, B);
   } else {
@@ -1136,37 +1117,29 @@ static void launch_mlp_fwd_c(int nch, const float* x, const float* o, const Bloc
   else { RAL_SET_LDS((k_mlp_fwd<C, 4>), lds); k_mlp_fwd<C, 4><<<grid_for(B), 512, lds, s>>>(x, o, w, x1, upre, x2, N, B, NE, addend, sum_out); }
 }
 
-// wide levels on split fp16 operands (RAL_MLP_F16=0: the fp32-MFMA kernel everywhere)
-bool mlp_fwd_uses_f16(int C, int N) {
-  static const bool on = (ral_knob("MLP_F16", 1) != 0);
-  return on && (C == 32 || C == 64 || C == 128) && N % 32 == 0;
-}
+// wide levels on split fp16 operands
+bool mlp_fwd_uses_f16(int C, int N) { return (C == 32 || C == 64 || C == 128) && N % 32 == 0; }
 size_t mlp_fwd_h_lds(int C, int T, int nch) {   // T = tokens of a work item
   return (size_t)T * ld_of(C) * 4 + (size_t)2 * T * ldb_of(C) * 2 + (size_t)2 * T * ldb_of(4 * C / nch) * 2 + (T / 16 * 2 + T + 4) * 4;
 }
-// windows per work item and hidden chunks of the split-operand kernel: the most tokens (up to RAL_MLP_TOK, a power-of-two
-// number of windows dividing the batch) whose tiles fit RAL_MLP_HLDS bytes with at most four hidden chunks
-static void mlp_fwd_h_plan(int C, int N, int B, int nth_ /* threads of the workgroup that will run it */, int* wpi_out, int* nch_out) {
-  static const int tokmax = (int)ral_knob("MLP_TOK", 0);   // default: one window per item (64 / 128 tokens measured slower: mlp_fwd 1.87 / 1.93 against 1.76 ms per step - one workgroup per CU)
-  static const size_t budget = (size_t)ral_knob("MLP_HLDS", 150 * 1024);
-  int wpi = 1;
-  while (wpi * 2 * N <= tokmax && B % (wpi * 2) == 0 && mlp_fwd_h_lds(C, wpi * 2 * N, 4) <= budget) wpi *= 2;
+// hidden chunks of the split-operand kernel: the fewest whose tiles fit the workgroup's LDS budget.  A work item is one window
+// (wpi = 1: items of 64 / 128 tokens measured slower, mlp_fwd 1.87 / 1.93 against 1.76 ms per step - one workgroup per CU).
+// (four-wave workgroups: three per CU.  The hardware admits one workgroup fewer than 160 KB / LDS suggests once the last one
+// would end within a granule of the top: 53 000 bytes run three per CU, 54 576 two - tools/diag/occ_probe.hip, census - while
+// hipOccupancyMaxActiveBlocksPerMultiprocessor still answers three.)
+static int mlp_fwd_h_nch(int C, int N, int nth /* threads of the workgroup that will run it */) {
+  const size_t budget = nth == 256 ? 53000 : 78000;
   int nch = 1;
-  // (four-wave workgroups: three per CU.  The hardware admits one workgroup fewer than 160 KB / LDS suggests once the last one
-  // would end within a granule of the top: 53 000 bytes run three per CU, 54 576 two - tools/diag/occ_probe.hip, census - while
-  // hipOccupancyMaxActiveBlocksPerMultiprocessor still answers three.)
-  const size_t b1 = wpi == 1 ? (nth_ == 256 ? 53000 : 78000) : budget;
-  while (nch < (nth_ == 256 ? 8 : 4) && mlp_fwd_h_lds(C, wpi * N, nch) > b1) nch *= 2;
-  *wpi_out = wpi; *nch_out = nch;
+  while (nch < (nth == 256 ? 8 : 4) && mlp_fwd_h_lds(C, N, nch) > budget) nch *= 2;
+  return nch;
 }
 template <int C, int NTH>
 static void launch_mlp_fwd_hc(const float* x, const float* o, const BlockP& w, const float* pbase, const void* wh,
                               float* x1, float* upre, float* x2, int N, int B, hipStream_t s, const float* addend, float* sum_out) {
-  int wpi, nch;
-  mlp_fwd_h_plan(C, N, B, NTH, &wpi, &nch);
-  const size_t lds = mlp_fwd_h_lds(C, wpi * N, nch);
+  const int nch = mlp_fwd_h_nch(C, N, NTH), wpi = 1;
+  const size_t lds = mlp_fwd_h_lds(C, N, nch);
   const _Float16* whp = reinterpret_cast<const _Float16*>(wh);
-  const int grid = grid_for(B / wpi);
+  const int grid = grid_for(B);
   if (nch == 1) { RAL_SET_LDS((k_mlp_fwd_h<C, 1, NTH>), lds); k_mlp_fwd_h<C, 1, NTH><<<grid, NTH, lds, s>>>(x, o, w, pbase, whp, x1, upre, x2, N, B, wpi, addend, sum_out); }
   else if (nch == 2) { RAL_SET_LDS((k_mlp_fwd_h<C, 2, NTH>), lds); k_mlp_fwd_h<C, 2, NTH><<<grid, NTH, lds, s>>>(x, o, w, pbase, whp, x1, upre, x2, N, B, wpi, addend, sum_out); }
   else if (nch == 4 || NTH != 256) { RAL_SET_LDS((k_mlp_fwd_h<C, 4, NTH>), lds); k_mlp_fwd_h<C, 4, NTH><<<grid, NTH, lds, s>>>(x, o, w, pbase, whp, x1, upre, x2, N, B, wpi, addend, sum_out); }
@@ -1178,16 +1151,13 @@ void launch_mlp_fwd(int C, int nch, const float* x, const float* o, const BlockP
   if (NE <= 0 || NE > N) NE = N;
   const bool padded = NE < N;   // padded windows: the generic kernel (its local-enhancement conv knows where the window ends)
   if (!padded && wh && mlp_fwd_uses_f16(C, N)) {
-    // threads of a k_mlp_fwd_h workgroup: 256 (default; four waves, four or eight hidden chunks, <= 53 000 bytes of LDS, three workgroups per CU, every
-    // K-chunk's weight fragments of a proj / fc1 unit requested together: 135-163 registers), 512 (two per CU at 128 registers) or
-    // 1024.  Measured: `mlp_fwd` 1.620 / 1.625 ms per step serialised for 512 / 256, the step 12.69 -> 12.67 ms (three interleaved
-    // rounds, each in favour), inference 557.6 k -> 562.3 k windows/s
-    static const int nth = (int)ral_knob("MLP_HTHREADS", 256);
+    // threads of a k_mlp_fwd_h workgroup at C = 64, 128: 256 (four waves, four or eight hidden chunks, <= 53 000 bytes of LDS, three
+    // workgroups per CU, every K-chunk's weight fragments of a proj / fc1 unit requested together: 135-163 registers).  Measured
+    // 256 / 512 threads (512: two per CU at 128 registers): `mlp_fwd` 1.625 / 1.620 ms per step serialised, the step 12.67 / 12.69
+    // ms (three interleaved rounds, each in favour of 256), inference 562.3 k / 557.6 k windows/s.  C = 32 runs 512.
     if (C == 32) launch_mlp_fwd_hc<32, 512>(x, o, w, pbase, wh, x1, upre, x2, N, B, s, addend, sum_out);
-    else if (nth == 256 && C == 64) launch_mlp_fwd_hc<64, 256>(x, o, w, pbase, wh, x1, upre, x2, N, B, s, addend, sum_out);
-    else if (nth == 256) launch_mlp_fwd_hc<128, 256>(x, o, w, pbase, wh, x1, upre, x2, N, B, s, addend, sum_out);
-    else if (C == 64) { if (nth == 1024) launch_mlp_fwd_hc<64, 1024>(x, o, w, pbase, wh, x1, upre, x2, N, B, s, addend, sum_out); else launch_mlp_fwd_hc<64, 512>(x, o, w, pbase, wh, x1, upre, x2, N, B, s, addend, sum_out); }
-    else { if (nth == 1024) launch_mlp_fwd_hc<128, 1024>(x, o, w, pbase, wh, x1, upre, x2, N, B, s, addend, sum_out); else launch_mlp_fwd_hc<128, 512>(x, o, w, pbase, wh, x1, upre, x2, N, B, s, addend, sum_out); }
+    else if (C == 64) launch_mlp_fwd_hc<64, 256>(x, o, w, pbase, wh, x1, upre, x2, N, B, s, addend, sum_out);
+    else launch_mlp_fwd_hc<128, 256>(x, o, w, pbase, wh, x1, upre, x2, N, B, s, addend, sum_out);
     return;
   }
   if (!padded && !sum_out)

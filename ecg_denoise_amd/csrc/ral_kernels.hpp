@@ -26,6 +26,11 @@ void launch_tile_planes(const float* params, void* wt, const void* desc, int nde
 void launch_act_scales(const float* params, const void* desc, float* asc, int nblk, hipStream_t s);
 void launch_qkv_fwd(int C, const float* x, const float* pe, const BlockP& w, const void* wt /* of Wqkv */, float* qkv, int N, int B, hipStream_t s);
 size_t attn_fwd_lds(int N, int HG, int Len);
+// Workgroup split of the attention tile kernels (forward and backward): 1 / ATTN_SPLIT of the head group per item and
+// 512 / ATTN_SPLIT threads, so that 2 * ATTN_SPLIT workgroups share a CU and one's staging latency and barrier waits hide behind
+// the others' tiles (same waves per CU, same LDS).  Measured at batch 2048 (fwd + bwd attention, ms per step): split 1: 7.76,
+// split 2: 7.53.  Head groups or windows it does not divide (HG % 2, N % 32) run unsplit.
+constexpr int ATTN_SPLIT = 2;
 // NE: existing tokens of the N slots (0 or N: all; fewer: padded windows, the generic kernel masks the keys past NE)
 void launch_attn_fwd(const float* qkv, float* o_hm, float* lse, const float* table, int N, int H, int HG, int Len,
                      int B, int f16, hipStream_t s, int NE = 0);
@@ -139,12 +144,9 @@ size_t attn_bwd_mh_scratch_floats(int N, int H, int Len, bool table, int B);
 void launch_attn_bwd_mh(const float* qkv, const float* o_hm, const float* do_hm, const float* lse, const float* table,
                         float* gtable, float* dqkv, float* tpart, int N, int H, int Len, int B, hipStream_t s);
 size_t qkv_bwd_lds(int C, int N);
-// returns true when the projection's weight / bias gradients were produced here (narrow levels: qkv_bwd_fuses_dw): the caller
-// then skips that product in launch_block_dw
-bool qkv_bwd_fuses_dw(int C, int N);
-bool launch_qkv_bwd(int C, const float* dqkv, const float* x, const float* pe, const float* dx1, const float* extra,
+void launch_qkv_bwd(int C, const float* dqkv, const float* x, const float* pe, const float* dx1, const float* extra,
                     const BlockP& w, const BlockP& wt, const float* ptbase, const void* wtt /* as launch_mlp_bwd */, unsigned* gmax,
-                    const BlockP& gr, float* dx, int N, int B, bool want_dw, hipStream_t s);
+                    const BlockP& gr, float* dx, int N, int B, hipStream_t s);
 void launch_resample_bwd(int D, bool sep, const float* dy, const float* x, const float* wred, const float* lnw,
                          float* g_lnw, float* g_lnb, float* dx, int T, int Tv, int B, hipStream_t s);
 void launch_final_bwd(int leads, const float* dy, const float* u0, const float* x0, const float* w, float* gw,
@@ -158,9 +160,7 @@ void launch_conv1_bwd_dx(int leads, const float* dz, const float* w, float* dx, 
 // ---- weight gradients (ral_dw.hip)
 void launch_block_dw(int C, const float* dx2, const float* upre, const float* a2c0, const float* dupre, const float* x1,
                      const float* dx1, const float* o_hm, const float* dqkv, const float* x, const float* pe,
-                     const BlockP& w, const BlockP& gr, int N, int B, int ksplit, bool skip_mlp, const unsigned* gmax /* 4 maxima of the split data-gradient kernels, or nullptr */, hipStream_t s,
-                     bool skip_qkv = false /* the projection's weight gradient was formed inside k_qkv_bwd */);
-void set_dw_lds_budget(size_t bytes);
+                     const BlockP& w, const BlockP& gr, int N, int B, int ksplit, bool skip_mlp, const unsigned* gmax /* 4 maxima of the split data-gradient kernels, or nullptr */, hipStream_t s);
 void launch_resample_dw(int D, bool sep, const float* dy, const float* x, const float* lnw, const float* lnb,
                         float* dW, int T, int Tv, int B, int ksplit, hipStream_t s);
 

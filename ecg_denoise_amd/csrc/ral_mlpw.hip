@@ -458,11 +458,10 @@ template <int C>
 static void go_mlp_fwd_w(const float* x, const float* o, const BlockP& w, float* x1, float* x2, int N, int B, hipStream_t s) {
   const size_t lds = (size_t)MlpwShape<C>::TOTAL * sizeof(float);
   RAL_SET_LDS((k_mlp_fwd_w<C>), lds);
-  static const int genv = (int)ral_knob("GRID_MLPW", 0);
   static int occ = 0;
   if (!occ && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_mlp_fwd_w<C>, 256, lds) != hipSuccess || occ < 1)) occ = 3;
   const int nwg = (B * (N / (16 * MlpwShape<C>::S)) + 3) / 4;
-  int grid = genv > 0 ? genv : ral_num_cus() * (occ > 4 ? 4 : occ);
+  int grid = ral_num_cus() * (occ > 4 ? 4 : occ);
   if (grid > nwg) grid = nwg;
   k_mlp_fwd_w<C><<<grid, 256, lds, s>>>(x, o, w, x1, x2, N, B);
 }
@@ -470,11 +469,10 @@ template <int C>
 static void go_mlp_fwd_wh(const float* x, const float* o, const BlockP& w, float* x1, float* x2, int N, int B, hipStream_t s) {
   const size_t lds = MlpwhShape<C>::BYTES;
   RAL_SET_LDS((k_mlp_fwd_wh<C>), lds);
-  static const int genv = (int)ral_knob("GRID_MLPW", 0);
   static int occ = 0;
   if (!occ && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_mlp_fwd_wh<C>, 256, lds) != hipSuccess || occ < 1)) occ = 3;
   const int nwg = (B * (N / (16 * MlpwhShape<C>::S)) + 3) / 4;
-  int grid = genv > 0 ? genv : ral_num_cus() * (occ > 4 ? 4 : occ);
+  int grid = ral_num_cus() * (occ > 4 ? 4 : occ);
   if (grid > nwg) grid = nwg;
   k_mlp_fwd_wh<C><<<grid, 256, lds, s>>>(x, o, w, x1, x2, N, B);
 }
@@ -1294,13 +1292,12 @@ int mlp_bwd_w_kind(int C, int N, bool f16_ok) {
 template <int C>
 static void go_mlp_bwd_w(const float* dx2, const float* x1, const BlockP& w, const BlockP& gr, float* dx1, float* do_hm, int N, int B,
                          bool want_dw, hipStream_t s) {
-  static const int genv = (int)ral_knob("GRID_MLPBW", 0);
   const int nwg = (B * (N / 16) + 3) / 4;
   const size_t lds = (size_t)MlpbwShape<C>::TOTAL * sizeof(float);
   RAL_SET_LDS((k_mlp_bwd_w<C>), lds);
   static int occ = 0;
   if (!occ && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_mlp_bwd_w<C>, 256, lds) != hipSuccess || occ < 1)) occ = 3;
-  int grid = genv > 0 ? genv : ral_num_cus() * (occ > 3 ? 3 : occ);
+  int grid = ral_num_cus() * (occ > 3 ? 3 : occ);
   if (grid > nwg) grid = nwg;
   k_mlp_bwd_w<C><<<grid, 256, lds, s>>>(dx2, x1, w, gr, dx1, do_hm, N, B, want_dw ? 1 : 0);
 }
@@ -1308,11 +1305,10 @@ template <bool H16>
 static void go_mlp_bwd_w2(const float* dx2, const float* x1, const BlockP& w, const BlockP& gr, float* dx1, float* do_hm, int N, int B,
                           bool want_dw, hipStream_t s) {
   using SH = Mlpbw2Shape<32>;
-  static const int genv = (int)ral_knob("GRID_MLPBW", 0);
   const int nwg = (B * (N / 16) + SH::NP - 1) / SH::NP;
   const size_t lds = (size_t)(H16 ? Mlpbw2hShape<32>::TOTAL : SH::TOTAL) * sizeof(float);
   RAL_SET_LDS((k_mlp_bwd_w2<32, H16>), lds);
-  int grid = genv > 0 ? genv : ral_num_cus() * (4 / SH::NP);      // (eight waves per CU: 232 registers)
+  int grid = ral_num_cus() * (4 / SH::NP);      // (eight waves per CU: 232 registers)
   if (grid > nwg) grid = nwg;
   k_mlp_bwd_w2<32, H16><<<grid, 128 * SH::NP, lds, s>>>(dx2, x1, w, gr, dx1, do_hm, N, B, want_dw ? 1 : 0);
 }

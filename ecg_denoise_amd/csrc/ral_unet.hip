@@ -1845,7 +1845,7 @@ UNetModel* unet_create(const ral_config* c, char* err, size_t cap) {
   if (c->train) {
     // the specialised backward kernels (all of them apply when every level's length is a multiple of 4) leave their
     // weight-gradient partials in scratch rows; otherwise some stage runs the generic kernel and everything stays atomic
-    m->fold = c->L % 64 == 0 && (ral_knob("UNET_FOLD", 1) != 0);
+    m->fold = c->L % 64 == 0;
     std::vector<int> cols;
     const int ch[5] = {c->leads, 4, 8, 16, 32};
     const int Cs[11] = {4, 8, 16, 32, 32, 32, 32, 16, 8, 4, ch[0]};
@@ -2017,7 +2017,7 @@ int unet_forward_stage(UNetModel* m, const float* x, int B, int training, int si
       else (void)hipMemsetAsync(P.bn_sums, 0, 1280 * sizeof(double), s);
     }
   } else if (x != m->last_x || B != m->last_B) { snprintf(err, cap, "U-Net stages must follow stage 0 of the same batch"); return -1; }
-  static const int fgmax = (int)ral_knob("UNET_FWD_GRID", 512);   // (train forward at batch 2048: 0.31 / 0.27 / 0.29 / 0.41 ms with 256 / 512 / 1024 / 2048 workgroups)
+  constexpr int fgmax = 512;   // (train forward at batch 2048: 0.31 / 0.27 / 0.29 / 0.41 ms with 256 / 512 / 1024 / 2048 workgroups)
   static const int egmax = (int)ral_knob("UNET_EVAL_GRID", 512);   // (stage-by-stage eval forward at batch 2048: 173 / 158 / 177 us with 256 / 512 / 1024 workgroups)
   const int gcap = training ? fgmax : egmax;
   const int grid = B < gcap ? B : gcap;
@@ -2085,8 +2085,6 @@ static int unet_forward_fused(UNetModel* m, const float* x, float* y, int B, hip
     const hipError_t e = P.cfg.leads == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_unet_infer<1>, 256, lds)
                                            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_unet_infer<2>, 256, lds);
     if (e != hipSuccess || per_cu < 1) per_cu = 1;
-    if (ral_knob("UNET_DEBUG", 0)) fprintf(stderr, "k_unet_infer: lds %zu B, occupancy query -> %d workgroups per CU (rc %d), %d CUs\n", lds, per_cu, (int)e, ncu);
-    { const int v = (int)ral_knob("UNET_WG_PER_CU", 0); if (v > 0) per_cu = v; }
     m->infer_grid = per_cu * ncu;
   }
   const int grid = B < m->infer_grid ? B : m->infer_grid;
@@ -2096,14 +2094,9 @@ static int unet_forward_fused(UNetModel* m, const float* x, float* y, int B, hip
   return 0;
 }
 
-static int unet_nrep() {
-  static const int n = [] { int k = (int)ral_knob("UNET_NREP", UNET_MAXREP); return k < 1 ? 1 : (k > UNET_MAXREP ? UNET_MAXREP : k); }();
-  return n;
-}
-
 int unet_forward(UNetModel* m, const float* x, float* y, int B, int training, hipStream_t s, char* err, size_t cap) {
   if (!training && unet_infer_fused_applies(m)) return unet_forward_fused(m, x, y, B, s, err, cap);
-  m->nrep_f = (training && m->pub.cfg.train) ? unet_nrep() : 1;
+  m->nrep_f = (training && m->pub.cfg.train) ? UNET_MAXREP : 1;
   for (int si = 0; si < 11; ++si)
     if (unet_forward_stage(m, x, B, training, si, B, s, err, cap)) { m->nrep_f = 1; return -1; }
   const int rc = unet_forward_finish(m, y, B, training, B, s, err, cap);
@@ -2166,7 +2159,7 @@ int unet_forward_loss(UNetModel* m, const float* x, const float* target, float* 
   UNetPublic& P = m->pub;
   if (!P.cfg.train || !P.grads || !P.bn_sums) { snprintf(err, cap, "forward + loss needs train=1, grads and bn_sums bound"); return -1; }
   if (!target || !y || !dy) { snprintf(err, cap, "forward + loss: null pointer"); return -1; }
-  m->nrep_f = unet_nrep();
+  m->nrep_f = UNET_MAXREP;
   for (int si = 0; si < 11; ++si)
     if (unet_forward_stage(m, x, B, 1, si, B, s, err, cap)) { m->nrep_f = 1; return -1; }
   Src o = make_src(m, 10, ACT_NONE, true, false, 0);
@@ -2178,10 +2171,10 @@ int unet_forward_loss(UNetModel* m, const float* x, const float* target, float* 
     u.l[k++] = BnUpd{m->nrep_f > 1 ? unet_rep(m, 0, bi) : P.bn_sums + 128 * bi, P.bn_sums + 128 * bi, P.state + m->lay.run[bi],
                      m->C[zi], (double)B * m->Ln[zi], m->nrep_f};
   }
-  m->nrep_b = unet_nrep();
+  m->nrep_b = UNET_MAXREP;
   unet_zero_bwd_records(m, s);
   const int C = m->C[10], L = m->Ln[10], n = C * L;
-  static const int gmax = [] { const int v = (int)ral_knob("LOSS_GRID", 256); return v < 1 ? 1 : v; }();
+  constexpr int gmax = 256;   // (as k_loss_w's grid, ral_misc.hip)
   const int g = (B + UOL_WAVES - 1) / UOL_WAVES;
   k_unet_out_loss<<<g < gmax ? g : gmax, 64 * UOL_WAVES, 0, s>>>(o, y, target, dy, snr, rmse, loss_sum, C, L, B, (double)B * L,
                                                                (float)(2.0 / ((double)B * n)), fin, fin_scale, fin3, u,
@@ -2227,9 +2220,8 @@ int unet_backward_stage(UNetModel* m, int B, int si, int64_t gwin, hipStream_t s
   if (si < 0 || si > 10) { snprintf(err, cap, "U-Net stage %d outside [0, 10]", si); return -1; }
   // every workgroup ends with ~2 000 global atomics (its share of dW, db and the BatchNorm-backward sums): the chip retires
   // ~75 of them per ns, so 1024 workgroups spend 30 us per launch on them alone.  Measured train step at batch 2048 with
-  // 1024 / 512 / 384 workgroups: 1.23 / 1.08 / 1.12 ms (RAL_UNET_BWD_GRID)
-  static const int gmax0 = (int)ral_knob("UNET_BWD_GRID", 512);
-  static const int wp = (int)ral_knob("UNET_BWD_WP", 2);
+  // 1024 / 512 / 384 workgroups: 1.23 / 1.08 / 1.12 ms
+  constexpr int gmax0 = 512, wp = 2;   // (wp: at most two windows per pass of the specialised kernels, launch_bwd_t)
   const int gmax = (m->fold && gmax0 > m->part_rows_max) ? m->part_rows_max : gmax0;
   const int grid = B < gmax ? B : gmax;
   if (m->last_dy == nullptr) { snprintf(err, cap, "U-Net backward stages must follow ral_unet_backward_start"); return -1; }
@@ -2241,7 +2233,7 @@ int unet_backward_stage(UNetModel* m, int B, int si, int64_t gwin, hipStream_t s
   const size_t lds = bwd_lds(st);
   static size_t cur = 0;
   if (lds > cur) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_unet_bwd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); cur = lds; }
-  if (!launch_unet_bwd_fast(st, si, P.cfg.leads, B, grid, wp < 1 ? 1 : wp, s)) k_unet_bwd<<<grid, 256, lds, s>>>(st, B);
+  if (!launch_unet_bwd_fast(st, si, P.cfg.leads, B, grid, wp, s)) k_unet_bwd<<<grid, 256, lds, s>>>(st, B);
   if (hipGetLastError() != hipSuccess) { snprintf(err, cap, "U-Net backward launch failed"); return -1; }
   return 0;
 }
@@ -2270,7 +2262,7 @@ int unet_backward_finish(UNetModel* m, int B, int64_t gwin, hipStream_t s, char*
 
 int unet_backward(UNetModel* m, const float* dy, float* dx, int B, hipStream_t s, char* err, size_t cap) {
   if (dx) { snprintf(err, cap, "U-Net input gradient is not provided"); return -1; }
-  m->nrep_b = unet_nrep();
+  m->nrep_b = UNET_MAXREP;
   if (unet_backward_start(m, dy, B, B, s, err, cap)) { m->nrep_b = 1; return -1; }
   for (int si = 10; si >= 0; --si)
     if (unet_backward_stage(m, B, si, B, s, err, cap)) { m->nrep_b = 1; return -1; }

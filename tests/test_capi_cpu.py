@@ -117,21 +117,26 @@ def test_product_path_has_no_cpu_fallback():
             assert "oracle" not in open(os.path.join(pkg, f)).read().replace("no CPU fallback", ""), f
 
 
-def test_global_option_validates_its_key_and_value():
-    """`ral_global_option` is the only way to change a library switch (no environment variable does): unknown names and negative
-    values are rejected with a message, known names are case-insensitive and accept an optional RAL_ prefix"""
+def test_global_option_validates_key_and_value_and_refuses_retired_switches():
+    """`ral_global_option` is the only way to change a library switch (no environment variable does): unknown names - retired
+    switches among them - and negative values are rejected with a message, known names are case-insensitive and accept an
+    optional RAL_ prefix"""
     L = _lib.lib()
     assert L.ral_global_option(b"attn_f16", 1) == 0
     assert L.ral_global_option(b"RAL_ATTN_F16", 1) == 0
-    assert L.ral_global_option(b"Grid_QkvB", 192) == 0
+    assert L.ral_global_option(b"Unet_Eval_Grid", 512) == 0
     assert L.ral_global_option(b"no_such_switch", 1) != 0 and b"unknown switch" in L.ral_last_error()
+    assert L.ral_global_option(b"mlp_hthreads", 256) != 0 and b"unknown switch" in L.ral_last_error()   # retired: a constant now
     assert L.ral_global_option(b"attn_f16", -1) != 0 and b"negative" in L.ral_last_error()
     assert L.ral_global_option(None, 1) != 0
-    # grid / thread / split counts: 0 would be a launch without a workgroup
-    for k in (b"unet_fwd_grid", b"grid_fwd", b"danet_grid_a", b"dw_ksplit_64", b"grid_qkvb"):
+    # grid / set counts: 0 would be a launch without a workgroup
+    for k in (b"unet_eval_grid", b"dw_sets"):
         assert L.ral_global_option(k, 0) != 0 and b"out of range" in L.ral_last_error(), k
-    assert L.ral_global_option(b"mlp_hthreads", 384) != 0
-    assert L.ral_global_option(b"grid_attnw", 0) == 0          # 0 = automatic for this one
+    # the others take 0 (attn_fwd_h = 0: never); a refusal here can only be the latch, which is checked after the range
+    first = L.ral_global_option(b"attn_fwd_h", 0)
+    assert first == 0 or b"already read" in L.ral_last_error()
+    if first == 0:
+        assert L.ral_global_option(b"attn_fwd_h", 256) == 0   # (back to the default before anything reads it)
 
 
 def test_global_option_after_the_first_read_is_refused_not_ignored():
@@ -145,6 +150,21 @@ def test_global_option_after_the_first_read_is_refused_not_ignored():
     if first == 0:
         assert L.ral_global_option(b"dw_sets", 6) == 0
     assert L.ral_global_option(b"dw_sets", 4) != 0 and b"already read" in L.ral_last_error()
+
+
+def test_global_option_accepts_the_default_after_the_first_read():
+    """a switch the library has read without it ever being set latches its default: setting that same value is accepted,
+    any other is refused (a fresh process, so that nothing has set DW_SETS before)"""
+    import subprocess
+    import sys
+    code = ("import ctypes as C, sys\n"
+            "from ecg_denoise_amd import _lib\n"
+            "L = _lib.lib()\n"
+            "assert L.ral_workspace_bytes(C.byref(_lib.make_config('full', 2, 512, 8, 1))) > 0   # reads DW_SETS: 6\n"
+            "assert L.ral_global_option(b'dw_sets', 6) == 0, L.ral_last_error()\n"
+            "assert L.ral_global_option(b'dw_sets', 4) != 0 and b'already read' in L.ral_last_error()\n")
+    p = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
 
 
 def test_library_reads_only_the_two_documented_environment_variables():
