@@ -89,6 +89,10 @@ _SIGS = {
                                            _VP]),
     "ral_newrale_stream_back": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int, _VP,
                                           _VP]),
+    "ral_newrale_live_front": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int,
+                                         C.c_int64, C.c_int64, C.c_int, _VP, _VP, _VP, _VP]),
+    "ral_newrale_live_back": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int64,
+                                        C.c_int, C.c_int64, C.c_int, _VP, _VP, _VP, _VP]),
     "ral_attention_forward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
     "ral_attention_backward_scratch_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "ral_attention_backward": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, C.c_int, C.c_int, C.c_int,

@@ -1533,6 +1533,36 @@ int ral_newrale_stream_back(const float* inner_y, const float* stats, const floa
   return 0;
 }
 
+int ral_newrale_live_front(const float* hist, const float* x, float* hist_out, int64_t S, int L, int hop, int C, int64_t base,
+                           int64_t k0, int nw, int64_t T, int64_t w0, int nb, const float* adapter_params, float* inner_x,
+                           float* stats, ral_stream s) {
+  if (!hist || !x || !adapter_params || !inner_x || !stats) return fail("newrale_live_front: null pointer");
+  if (launch_newrale_live_front(hist, x, hist_out, (long long)S, L, hop, C, (long long)base, (long long)k0, nw, (long long)T,
+                                (long long)w0, nb, adapter_params, inner_x, stats, (hipStream_t)s))
+    return fail("newrale_live_front: need S >= 1, L a multiple of 16 in [16, 1024], 1 <= hop <= L with L - hop even, C >= 0, "
+                "T < 0 or T >= L, windows k0 .. k0 + nw - 1 of the stream inside samples [base, base + L + C), a window range "
+                "inside the S * nw windows, and nb >= 1 or a history to write (another buffer than hist) (S=%lld L=%d hop=%d "
+                "C=%d base=%lld k0=%lld nw=%d T=%lld w0=%lld nb=%d)", (long long)S, L, hop, C, (long long)base, (long long)k0,
+                nw, (long long)T, (long long)w0, nb);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int ral_newrale_live_back(const float* inner_y, const float* stats, const float* adapter_params, int64_t S, int L, int hop,
+                          int64_t k0, int nw, int64_t T, int64_t w0, int nb, int64_t lo, int m, float* out, float* last_y,
+                          float* last_stats, ral_stream s) {
+  if (!inner_y || !stats || !adapter_params || !out) return fail("newrale_live_back: null pointer");
+  if (launch_newrale_live_back(inner_y, stats, adapter_params, (long long)S, L, hop, (long long)k0, nw, (long long)T,
+                               (long long)w0, nb, (long long)lo, m, out, last_y, last_stats, (hipStream_t)s))
+    return fail("newrale_live_back: need S >= 1, L a multiple of 16 in [16, 1024], 1 <= hop <= L with L - hop even, "
+                "T < 0 or T >= L with windows k0 .. k0 + nw - 1 in the stream, a window range of nb >= 1 windows inside the "
+                "S * nw, lo >= 0, m >= 0, and last_y and last_stats both given or both null (S=%lld L=%d hop=%d k0=%lld nw=%d "
+                "T=%lld w0=%lld nb=%d lo=%lld m=%d)", (long long)S, L, hop, (long long)k0, nw, (long long)T, (long long)w0, nb,
+                (long long)lo, m);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 int ral_wavelet_denoise(const float* x, float* y, int64_t rows, int L, float threshold, ral_stream s) {
   if (!x || !y) return fail("wavelet_denoise: null pointer");
   if (!(threshold >= 0.f)) return fail("wavelet_denoise: the threshold factor must be non-negative (got %g)", (double)threshold);

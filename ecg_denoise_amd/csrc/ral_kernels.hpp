@@ -90,6 +90,13 @@ int launch_newrale_front(const float* rec, long long R, long long T, int L, int 
                          float* inner, float* stats, hipStream_t s);
 int launch_newrale_back(const float* iy, const float* stats, const float* prm, long long R, long long T, int L, int hop,
                         long long w0, int nw, float* out, hipStream_t s);
+// the same kernels on live 12-lead streams (ral_newrale_live_front / _back; the geometry of launch_live_*); -1: bad arguments
+int launch_newrale_live_front(const float* hist, const float* x, float* hist_out, long long S, int L, int hop, int C,
+                              long long base, long long k0, int nw, long long T, long long w0, int nb, const float* prm,
+                              float* inner, float* stats, hipStream_t s);
+int launch_newrale_live_back(const float* iy, const float* stats, const float* prm, long long S, int L, int hop, long long k0,
+                             int nw, long long T, long long w0, int nb, long long lo, int m, float* out, float* last_y,
+                             float* last_stats, hipStream_t s);
 int launch_conv13_fwd(const float* x, const float* w, const float* b, float* y, int B, int cin, int cout, int L,
                       int lrelu, hipStream_t s);
 int launch_conv13_bwd(const float* x, const float* y, const float* dy, const float* w, float* gw, float* gb,

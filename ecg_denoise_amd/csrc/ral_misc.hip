@@ -767,23 +767,29 @@ static bool live_window_start(long long T, int L, int hop, long long k, long lon
   return k < n && n < 0x7fffffffLL;
 }
 
-static bool live_geom_ok(long long S, int leads, int L, int hop, long long k0, int nw, long long T, long long w0, int nb) {
-  if (S < 1 || leads < 1 || L < 64 || L % 64 != 0 || L > 2048 || hop < 1 || hop > L || ((L - hop) & 1)) return false;
+// lmul / lmax: the window lengths of the caller's kernels (L a multiple of lmul in [lmul, lmax])
+static bool live_geom_ok(long long S, int leads, int L, int hop, long long k0, int nw, long long T, long long w0, int nb,
+                         int lmul = 64, int lmax = 2048) {
+  if (S < 1 || leads < 1 || L < lmul || L % lmul != 0 || L > lmax || hop < 1 || hop > L || ((L - hop) & 1)) return false;
   if (nw < 0 || k0 < 0 || nb < 0 || w0 < 0 || (T >= 0 && T < L) || w0 + nb > S * nw) return false;
   long long st;
   return nw == 0 || live_window_start(T, L, hop, k0 + nw - 1, st);
+}
+
+// every window k0 .. k0 + nw - 1 inside V: the first one starts at or after base, the last one ends at or before base + L + C
+static bool live_windows_in_v(int L, int hop, int C, long long base, long long k0, int nw, long long T) {
+  if (nw == 0) return true;
+  long long first, last;
+  live_window_start(T, L, hop, k0, first);
+  live_window_start(T, L, hop, k0 + nw - 1, last);
+  return first >= base && last + L <= base + L + C;
 }
 
 int launch_live_windows(const float* hist, const float* x, float* hist_out, long long S, int leads, int L, int hop, int C,
                         long long base, long long k0, int nw, long long T, long long w0, int nb, float* win, float* stats,
                         hipStream_t s) {
   if (!live_geom_ok(S, leads, L, hop, k0, nw, T, w0, nb) || C < 0 || (nb == 0 && !hist_out)) return -1;
-  if (nw > 0) {   // every window inside V: the first one starts at or after base, the last one ends at or before base + L + C
-    long long first, last;
-    live_window_start(T, L, hop, k0, first);
-    live_window_start(T, L, hop, k0 + nw - 1, last);
-    if (first < base || last + L > base + L + C) return -1;
-  }
+  if (!live_windows_in_v(L, hop, C, base, k0, nw, T)) return -1;
   const long long grid = (long long)nb * leads + (hist_out ? S * leads : 0);
   if (grid > 0x7fffffffLL) return -1;
   k_live_windows<<<(int)grid, 64, 0, s>>>(hist, x, hist_out, leads, L, hop, C, base, (int)k0, nw, T, w0, nb, win, stats);
@@ -860,24 +866,150 @@ RAL_DEV void zero_halos(float* xs, int rows, int L) {
   }
 }
 
-__global__ __launch_bounds__(256) void k_newrale_front(const float* __restrict__ rec, long long T, int L, int hop, long long w0,
-                                                       int nw, const float* __restrict__ prm, float* __restrict__ inner,
-                                                       float* __restrict__ stats) {
+// The record kernels and the live ones are ONE body each, templated on where a window comes from (k_newrale_front) and where
+// its kept samples go (k_newrale_back): the live bits equal the record bits by construction.
+// Window sources: window(sk, i, src) returns the number gw of window i of the launch (its stats slot) and sets the reader
+// src(c, l) of its sample l of lead c; write_history is what the workgroups past the windows do (live calls only).
+struct NrRecordWindows {   // windows [w0, w0 + nw) of a record group (R, 12, T), numbered as in k_stream_windows
+  const float* rec;
+  long long T, w0;
+  int L, hop;
+  struct Reader {
+    const float* p;
+    long long T;
+    RAL_DEV float operator()(int c, int l) const { return p[c * T + l]; }
+  };
+  RAL_DEV StreamKeep keep() const { return stream_keep(T, L, hop); }
+  RAL_DEV long long window(const StreamKeep& sk, int i, Reader& src) const {
+    const long long gw = w0 + i, r = gw / sk.n;
+    const int k = (int)(gw - r * sk.n);
+    src.p = rec + r * NR_LEADS * T + stream_start(sk, k, T, L, hop);
+    src.T = T;
+    return gw;
+  }
+  RAL_DEV void write_history(int, int) const {}
+};
+
+struct NrLiveWindows {     // a live call (k_live_windows' geometry, 12 leads): window gw = s nw + j is window k0 + j of stream s
+  const float* hist;       // (S, 12, L)
+  const float* x;          // (S, 12, C)
+  float* hist_out;         // (S, 12, L) or null
+  long long S, base, T, w0;
+  int L, hop, C, k0, nw;
+  struct Reader {          // the window is V[o, o + L) of V = hist ++ x
+    const float* hr;
+    const float* xr;
+    int o, L, C;
+    RAL_DEV float operator()(int c, int l) const { const int v = o + l; return v < L ? hr[c * L + v] : xr[c * C + v]; }
+  };
+  RAL_DEV StreamKeep keep() const { return T < 0 ? stream_keep_open(L, hop) : stream_keep(T, L, hop); }
+  RAL_DEV long long window(const StreamKeep& sk, int i, Reader& src) const {
+    const long long gw = w0 + i, s = gw / nw;
+    const int j = (int)(gw - s * nw);
+    src.o = (int)(stream_start(sk, k0 + j, T, L, hop) - base);
+    src.hr = hist + s * NR_LEADS * L;
+    src.xr = x + s * NR_LEADS * C - L;
+    src.L = L;
+    src.C = C;
+    return gw;
+  }
+  // workgroup g of ng writes V[C, C + L) of the (stream, lead) rows g, g + ng, ... into hist_out (another buffer than hist)
+  RAL_DEV void write_history(int g, int ng) const {
+    for (long long r = g; r < S * NR_LEADS; r += ng) {
+      const float* hr = hist + r * L;
+      const float* xr = x + r * C;
+      float* dst = hist_out + r * L;
+      for (int l = threadIdx.x; l < L; l += blockDim.x) dst[l] = C + l < L ? hr[C + l] : xr[C + l - L];
+    }
+  }
+};
+
+// Where the kept samples of a window of k_newrale_back go: window(sk, i) -> its number gw, the samples [ob, oe) of the window
+// it keeps, and the element out[dst + c * stride + l] that takes its sample l of lead c; ly: where the inner output of the
+// window is kept whole (live calls, the last window of every stream), or null.
+struct NrKept {
+  long long gw, dst, stride;
+  int ob, oe;
+  float* ly;
+};
+
+struct NrRecordKeep {      // into the record group (R, 12, T): k_stream_stitch's rule
+  float* out;
+  long long T, w0;
+  int L, hop;
+  RAL_DEV StreamKeep keep() const { return stream_keep(T, L, hop); }
+  RAL_DEV NrKept window(const StreamKeep& sk, int i) const {
+    NrKept kp;
+    kp.gw = w0 + i;
+    const long long r = kp.gw / sk.n;
+    const int k = (int)(kp.gw - r * sk.n);
+    const long long start = stream_start(sk, k, T, L, hop);
+    long long kb, ke;
+    stream_kept(sk, k, T, hop, kb, ke);
+    kp.ob = (int)(kb - start);
+    kp.oe = (int)(ke - start);
+    kp.dst = r * NR_LEADS * T + start;
+    kp.stride = T;
+    kp.ly = nullptr;
+    return kp;
+  }
+  RAL_DEV void keep_stats(const NrKept&, const float*) const {}
+};
+
+struct NrLiveKeep {        // into a live call's out (S, 12, m): the samples in [lo, lo + m), sample t at t - lo (k_live_emit)
+  float* out;
+  float* last_y;           // (S, 2, L) or null
+  float* last_stats;       // (S, 12, 2) or null (with last_y)
+  long long T, w0, lo;
+  int L, hop, k0, nw, m;
+  RAL_DEV StreamKeep keep() const { return T < 0 ? stream_keep_open(L, hop) : stream_keep(T, L, hop); }
+  RAL_DEV NrKept window(const StreamKeep& sk, int i) const {
+    NrKept kp;
+    kp.gw = w0 + i;
+    const long long s = kp.gw / nw;
+    const int j = (int)(kp.gw - s * nw), k = k0 + j;
+    const long long start = stream_start(sk, k, T, L, hop);
+    long long b, e;
+    stream_kept(sk, k, T, hop, b, e);
+    b = b > lo ? b : lo;                 // (clipped to the window as in k_live_emit)
+    b = b > start ? b : start;
+    e = e < lo + m ? e : lo + m;
+    e = e < start + L ? e : start + L;
+    kp.ob = (int)(b - start);
+    kp.oe = e > b ? (int)(e - start) : kp.ob;
+    kp.dst = s * NR_LEADS * m + start - lo;   // (negative for start < lo: only l >= ob, t >= lo, is written)
+    kp.stride = m;
+    kp.ly = last_y && j == nw - 1 ? last_y + s * 2 * L : nullptr;
+    return kp;
+  }
+  RAL_DEV void keep_stats(const NrKept& kp, const float* stats) const {   // (mean, std) of the 12 leads of a kept window
+    if (kp.ly && threadIdx.x < 2 * NR_LEADS)
+      last_stats[(kp.gw / nw) * 2 * NR_LEADS + threadIdx.x] = stats[kp.gw * 2 * NR_LEADS + threadIdx.x];
+  }
+};
+
+// nwg workgroups take the windows [0, nw) of the launch in turn; workgroups nwg .. gridDim.x - 1 write the history
+template <class Win>
+__global__ __launch_bounds__(256) void k_newrale_front(Win win, int nw, int nwg, const float* __restrict__ prm,
+                                                       float* __restrict__ inner, float* __restrict__ stats) {
+  if ((int)blockIdx.x >= nwg) {
+    win.write_history((int)blockIdx.x - nwg, (int)gridDim.x - nwg);
+    return;
+  }
   extern __shared__ float4 smem4[];
-  const int LP = L + 12;
+  const int L = win.L, LP = L + 12;
   float* xs = reinterpret_cast<float*>(smem4);   // 12 x LP: the window, z-scored in place
   float* a1 = xs + NR_LEADS * LP;                // 6 x LP: conv1's output
   zero_halos(xs, NR_LEADS + NR_MID, L);
-  const StreamKeep sk = stream_keep(T, L, hop);
+  const StreamKeep sk = win.keep();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int i = blockIdx.x; i < nw; i += gridDim.x) {
-    const long long gw = w0 + i, r = gw / sk.n;
-    const int k = (int)(gw - r * sk.n);
-    const float* src = rec + r * NR_LEADS * T + stream_start(sk, k, T, L, hop);
+  for (int i = blockIdx.x; i < nw; i += nwg) {
+    typename Win::Reader src;
+    const long long gw = win.window(sk, i, src);
     __syncthreads();   // (the previous window's readers are done; the halos are written)
     for (int e = threadIdx.x; e < NR_LEADS * L; e += blockDim.x) {
       const int c = e / L, l = e - c * L;
-      xs[c * LP + 6 + l] = src[c * T + l];
+      xs[c * LP + 6 + l] = src(c, l);
     }
     __syncthreads();
     // z-score, one wave per lead (zscore_wave: k_stream_windows' bits)
@@ -908,27 +1040,26 @@ __global__ __launch_bounds__(256) void k_newrale_front(const float* __restrict__
   }
 }
 
-__global__ __launch_bounds__(256) void k_newrale_back(const float* __restrict__ iy, const float* __restrict__ stats,
-                                                      const float* __restrict__ prm, long long T, int L, int hop, long long w0,
-                                                      int nw, float* __restrict__ out) {
+template <class Dst>
+__global__ __launch_bounds__(256) void k_newrale_back(Dst dst, int nw, const float* __restrict__ iy,
+                                                      const float* __restrict__ stats, const float* __restrict__ prm) {
   extern __shared__ float4 smem4[];
-  const int LP = L + 12;
+  const int L = dst.L, LP = L + 12;
   float* ys = reinterpret_cast<float*>(smem4);   // 2 x LP: the inner model's output
   float* a3 = ys + 2 * LP;                       // 6 x LP: conv3's output
   zero_halos(ys, 2 + NR_MID, L);
-  const StreamKeep sk = stream_keep(T, L, hop);
+  const StreamKeep sk = dst.keep();
   for (int i = blockIdx.x; i < nw; i += gridDim.x) {
-    const long long gw = w0 + i, r = gw / sk.n;
-    const int k = (int)(gw - r * sk.n);
-    const long long start = stream_start(sk, k, T, L, hop);
-    long long kb, ke;
-    stream_kept(sk, k, T, hop, kb, ke);
-    const int ob = (int)(kb - start), oe = (int)(ke - start);   // kept samples [ob, oe) of the window
+    const NrKept kp = dst.window(sk, i);
+    const long long gw = kp.gw;
     __syncthreads();
     for (int e = threadIdx.x; e < 2 * L; e += blockDim.x) {
       const int c = e / L, l = e - c * L;
-      ys[c * LP + 6 + l] = iy[(size_t)i * 2 * L + e];
+      const float v = iy[(size_t)i * 2 * L + e];
+      ys[c * LP + 6 + l] = v;
+      if (kp.ly) kp.ly[e] = v;
     }
+    dst.keep_stats(kp, stats);
     __syncthreads();
     for (int l0 = NR_PT * threadIdx.x; l0 < L; l0 += NR_PT * blockDim.x) {   // conv3 + LeakyReLU -> a3
       float acc[NR_MID][NR_PT];
@@ -939,9 +1070,8 @@ __global__ __launch_bounds__(256) void k_newrale_back(const float* __restrict__ 
         for (int p = 0; p < NR_PT; ++p) a3[co * LP + 6 + l0 + p] = lrelu001(acc[co][p]);
     }
     __syncthreads();
-    // conv4 on the 4-sample tiles that hold kept samples; de-normalise; write the kept ones into the record
-    float* dst = out + r * NR_LEADS * T + start;
-    for (int l0 = (ob & ~(NR_PT - 1)) + NR_PT * threadIdx.x; l0 < oe; l0 += NR_PT * blockDim.x) {
+    // conv4 on the 4-sample tiles that hold kept samples; de-normalise; write the kept ones
+    for (int l0 = (kp.ob & ~(NR_PT - 1)) + NR_PT * threadIdx.x; l0 < kp.oe; l0 += NR_PT * blockDim.x) {
       float acc[NR_LEADS][NR_PT];
       conv13_tile<NR_MID, NR_LEADS>(a3, LP, l0, prm + NR_C4W, prm + NR_C4B, acc);
 #pragma unroll
@@ -950,12 +1080,16 @@ __global__ __launch_bounds__(256) void k_newrale_back(const float* __restrict__ 
 #pragma unroll
         for (int p = 0; p < NR_PT; ++p) {
           const int l = l0 + p;
-          if (l >= ob && l < oe) dst[c * T + l] = fmaf(acc[c][p], sd, mean);
+          if (l >= kp.ob && l < kp.oe) dst.out[kp.dst + c * kp.stride + l] = fmaf(acc[c][p], sd, mean);
         }
       }
     }
   }
 }
+
+static constexpr int NR_GRID = 2048;   // workgroup cap of the windows of one launch (grid-stride beyond)
+static size_t newrale_front_lds(int L) { return (size_t)(NR_LEADS + NR_MID) * (L + 12) * sizeof(float); }
+static size_t newrale_back_lds(int L) { return (size_t)(2 + NR_MID) * (L + 12) * sizeof(float); }
 
 static bool newrale_stream_args_ok(long long R, long long T, int L, int hop, long long w0, int nw) {
   if (R < 1 || L < 16 || L % 16 != 0 || L > 1024 || T < L || hop < 1 || hop > L || ((L - hop) & 1) || nw < 1 || w0 < 0) return false;
@@ -966,17 +1100,48 @@ static bool newrale_stream_args_ok(long long R, long long T, int L, int hop, lon
 int launch_newrale_front(const float* rec, long long R, long long T, int L, int hop, long long w0, int nw, const float* prm,
                          float* inner, float* stats, hipStream_t s) {
   if (!newrale_stream_args_ok(R, T, L, hop, w0, nw)) return -1;
-  const size_t lds = (size_t)(NR_LEADS + NR_MID) * (L + 12) * sizeof(float);
-  RAL_SET_LDS(k_newrale_front, lds);
-  k_newrale_front<<<nw < 2048 ? nw : 2048, 256, lds, s>>>(rec, T, L, hop, w0, nw, prm, inner, stats);
+  const size_t lds = newrale_front_lds(L);
+  RAL_SET_LDS(k_newrale_front<NrRecordWindows>, lds);
+  const int grid = nw < NR_GRID ? nw : NR_GRID;
+  k_newrale_front<<<grid, 256, lds, s>>>(NrRecordWindows{rec, T, w0, L, hop}, nw, grid, prm, inner, stats);
   return 0;
 }
 
 int launch_newrale_back(const float* iy, const float* stats, const float* prm, long long R, long long T, int L, int hop,
                         long long w0, int nw, float* out, hipStream_t s) {
   if (!newrale_stream_args_ok(R, T, L, hop, w0, nw)) return -1;
-  const size_t lds = (size_t)(2 + NR_MID) * (L + 12) * sizeof(float);
-  RAL_SET_LDS(k_newrale_back, lds);
-  k_newrale_back<<<nw < 2048 ? nw : 2048, 256, lds, s>>>(iy, stats, prm, T, L, hop, w0, nw, out);
+  const size_t lds = newrale_back_lds(L);
+  RAL_SET_LDS(k_newrale_back<NrRecordKeep>, lds);
+  k_newrale_back<<<nw < NR_GRID ? nw : NR_GRID, 256, lds, s>>>(NrRecordKeep{out, T, w0, L, hop}, nw, iy, stats, prm);
+  return 0;
+}
+
+// Live 12-lead streams (NewRALELiveDenoiser): the record kernels' bodies on k_live_windows' / k_live_emit's geometry.  L as for
+// the record kernels (a multiple of 16 in [16, 1024]).
+int launch_newrale_live_front(const float* hist, const float* x, float* hist_out, long long S, int L, int hop, int C,
+                              long long base, long long k0, int nw, long long T, long long w0, int nb, const float* prm,
+                              float* inner, float* stats, hipStream_t s) {
+  if (!live_geom_ok(S, NR_LEADS, L, hop, k0, nw, T, w0, nb, 16, 1024) || C < 0 || (nb == 0 && !hist_out) || hist_out == hist)
+    return -1;
+  if (!live_windows_in_v(L, hop, C, base, k0, nw, T)) return -1;
+  const long long rows = S * NR_LEADS;
+  const int nwg = nb < NR_GRID ? nb : NR_GRID;
+  const int nhg = hist_out ? (int)(rows < NR_GRID ? rows : NR_GRID) : 0;    // history workgroups, rows in turn
+  const size_t lds = newrale_front_lds(L);
+  RAL_SET_LDS(k_newrale_front<NrLiveWindows>, lds);
+  k_newrale_front<<<nwg + nhg, 256, lds, s>>>(NrLiveWindows{hist, x, hist_out, S, base, T, w0, L, hop, C, (int)k0, nw}, nb, nwg,
+                                              prm, inner, stats);
+  return 0;
+}
+
+int launch_newrale_live_back(const float* iy, const float* stats, const float* prm, long long S, int L, int hop, long long k0,
+                             int nw, long long T, long long w0, int nb, long long lo, int m, float* out, float* last_y,
+                             float* last_stats, hipStream_t s) {
+  if (!live_geom_ok(S, NR_LEADS, L, hop, k0, nw, T, w0, nb, 16, 1024) || nb < 1 || lo < 0 || m < 0 || (!last_y != !last_stats))
+    return -1;
+  const size_t lds = newrale_back_lds(L);
+  RAL_SET_LDS(k_newrale_back<NrLiveKeep>, lds);
+  k_newrale_back<<<nb < NR_GRID ? nb : NR_GRID, 256, lds, s>>>(NrLiveKeep{out, last_y, last_stats, T, w0, lo, L, hop, (int)k0, nw, m},
+                                                               nb, iy, stats, prm);
   return 0;
 }

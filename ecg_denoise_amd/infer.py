@@ -12,8 +12,8 @@ windowing (`ral_newrale_stream_front`) and with the stitching (`ral_newrale_stre
 model's parameter generation and are captured again once the weights change (the inner eval-mode forward leaves the
 preparation of its weight planes out of a capture).
 
-`LiveDenoiser` denoises S streams that arrive chunk by chunk; what it returns, concatenated, is what `StreamingDenoiser`
-returns for the complete records."""
+`LiveDenoiser` denoises S streams that arrive chunk by chunk, `NewRALELiveDenoiser` S 12-lead streams through a `NewRALE`;
+what they return, concatenated, is what `StreamingDenoiser` returns for the complete records."""
 import torch
 
 from . import _lib
@@ -190,29 +190,15 @@ def live_latency(L, hop):
     return (-L) % hop + (L - hop) // 2
 
 
-class LiveDenoiser:
-    """S streams denoised while they arrive, in lockstep chunks of C samples (C a positive multiple of hop = L - overlap).
+class _LiveBase:
+    """What the live denoisers share: the stream geometry, the frontier bookkeeping of `push` / `flush`, the two hipGraphs of
+    the steady state (one per push parity) and their capture.  A subclass allocates its buffers and supplies `_run` (one call:
+    the windows of every stream, the model, the kept samples) and `_emit_last` (at `flush`, the samples the last regular window
+    of the pushes keeps)."""
 
-    `push(x)` takes the next chunk of every stream, x (S, leads, C), and returns the samples that have become final, (S, leads,
-    m) on the device: nothing before L samples have arrived, samples [0, F(n)) when the first window completes
-    (`live_frontier`), then C per push, `latency` samples behind the newest one.  `flush(x=None)` takes an optional last chunk of
-    any length r >= 0, returns the rest of every stream and resets the object.  Concatenated per stream, everything `push` and
-    `flush` returned equals `StreamingDenoiser(model, overlap=overlap).denoise(record)`: the same windows, per-window z-score,
-    stitch rule and right-aligned last window.
-
-    Per push `ral_live_windows` gathers every stream's new windows straight from its last L samples (kept on the device, two
-    buffers used in turn: a push reads one and writes the other) and the chunk, the model runs them in batches of at most
-    max_batch windows, and `ral_live_emit` writes the samples they keep.  Once the lag is constant (the first L samples have
-    arrived) a push replays one of two captured hipGraphs, by push parity; they are captured again when the model's parameter
-    generation moves (the eval-mode capture leaves out the preparation of the weight planes).  Earlier pushes and `flush` run
-    eagerly.  Accepts the 1- and 2-lead models of `StreamingDenoiser` (RALENet, UNet, ACDAE, DANet); puts the model in eval mode."""
-
-    def __init__(self, model, streams, chunk, overlap=0, use_graph=True):
-        if isinstance(model, NewRALE):
-            raise _lib.RalError("LiveDenoiser does not take a NewRALE: live 12-lead streams are not supported "
-                                "(StreamingDenoiser denoises complete 12-lead records)")
-        e = model.eng
-        self.model, self.eng, self.L, self.leads = model, e, e.L, e.leads
+    def _setup(self, model, eng, leads, streams, chunk, overlap, use_graph):
+        """validate and set the geometry -> windows per stream and push, at most (every push once the lag is constant)"""
+        self.model, self.eng, self.L, self.leads = model, eng, eng.L, leads
         if overlap < 0 or overlap >= self.L or overlap % 2:
             raise _lib.RalError("overlap must be an even number of samples in [0, L)")
         self.overlap, self.hop = overlap, self.L - overlap
@@ -221,20 +207,9 @@ class LiveDenoiser:
         if chunk < 1 or chunk % self.hop:
             raise _lib.RalError(f"chunk must be a positive multiple of hop = L - overlap = {self.hop} (got {chunk})")
         self.S, self.C, self.use_graph = int(streams), int(chunk), use_graph
-        nw = self.C // self.hop                      # windows per stream and push, at most (every push once the lag is constant)
-        dev = e.device
-        z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
-        self.hist = [z(self.S, self.leads, self.L), z(self.S, self.leads, self.L)]    # push parity p reads hist[p], writes hist[1 - p]
-        self.x = z(self.S, self.leads, self.C)
-        self.win = z(min(e.max_batch, self.S * nw), self.leads, self.L)      # one batch of windows
-        self.y = torch.zeros_like(self.win)
-        self.stats = z(self.S * nw * self.leads * 2)
-        self.out = z(self.S, self.leads, self.C)
-        self.last_y, self.last_stats = z(self.S, self.leads, self.L), z(self.S * self.leads * 2)   # the last regular window
         self.graphs, self.gen = [None, None], None
         self.latency = live_latency(self.L, self.hop)
-        model.eval()
-        self.reset()
+        return self.C // self.hop
 
     def reset(self):
         """drop every stream's state; the next push starts new streams (the captured graphs stay valid)"""
@@ -243,25 +218,12 @@ class LiveDenoiser:
     def _n_reg(self, n):
         return (n - self.L) // self.hop + 1 if n >= self.L else 0
 
-    def _run(self, x, C, k0, nw, T, lo, m, out, keep, stats):
-        """enqueue one call on the current stream (captured or eager): the windows k0 .. k0 + nw - 1 of every stream from the
-        history and x (C samples), the model, the kept samples in [lo, lo + m) -> out; a push (keep) also writes the next
-        history and keeps the last window.  stats: (mean, std) of the S * nw windows"""
-        lib, e, S, n = _lib.lib(), self.eng, self.S, self.samples_in
-        h_in, h_out = self.hist[self.parity], (self.hist[1 - self.parity] if keep else None)
-        base, batch = n - self.L, self.win.shape[0]
-        for w0 in range(0, max(S * nw, 1), batch):
-            nb = min(batch, S * nw - w0)
-            if nb == 0 and h_out is None:
-                break
-            _lib.check(lib.ral_live_windows(_ptr(h_in), _ptr(x), _ptr(h_out if w0 == 0 else None), S, self.leads, self.L,
-                                            self.hop, C, base, k0, nw, T, w0, nb, _ptr(self.win), _ptr(stats), _stream()))
-            if nb == 0:
-                break
-            _lib.check(lib.ral_forward(e.h, _ptr(self.win), _ptr(self.y), nb, 0, _stream()))
-            _lib.check(lib.ral_live_emit(_ptr(self.y), _ptr(stats), S, self.leads, self.L, self.hop, k0, nw, T, w0, nb, lo,
-                                         m, _ptr(out), _ptr(self.last_y if keep else None),
-                                         _ptr(self.last_stats if keep else None), _stream()))
+    def _generation(self):
+        """the parameter generation the captured graphs are valid for"""
+        return self.model.param_gen
+
+    def _ready(self, what):
+        """raise if the model cannot run a live call now"""
 
     def _chunk(self, x, what):
         x = torch.as_tensor(x, dtype=torch.float32)
@@ -286,6 +248,7 @@ class LiveDenoiser:
     def push(self, x, copy=True):
         """x (S, leads, C), host or device -> the samples of every stream that became final, (S, leads, m) on the device.  The
         result is a fresh tensor; `copy=False` returns a view of a buffer that the next push may overwrite."""
+        self._ready("push")
         x = self._chunk(x, "push")
         if x.shape[2] != self.C:
             raise _lib.RalError(f"push: every chunk has C = {self.C} samples (got {x.shape[2]}); flush takes a shorter last one")
@@ -298,8 +261,9 @@ class LiveDenoiser:
         if n0 >= self.L and self.use_graph:
             # steady state: nw = C / hop, m = C, k0 > 0; the arguments of the capturing push serve every later push of the
             # same parity (the open-stream rule depends only on positions relative to the history)
-            if self.gen != self.model.param_gen:
-                self.graphs, self.gen = [None, None], self.model.param_gen
+            gen = self._generation()
+            if self.gen != gen:
+                self.graphs, self.gen = [None, None], gen
             if self.graphs[self.parity] is None:
                 self.graphs[self.parity] = self._capture((self.x, self.C, k0, nw, -1, lo, m, self.out, True, self.stats))
             self.graphs[self.parity].replay()
@@ -314,6 +278,7 @@ class LiveDenoiser:
     def flush(self, x=None):
         """the optional last chunk x (S, leads, r), any r >= 0 -> the rest of every stream, (S, leads, T - F(n)) for a stream of
         T = n + r samples; the object is reset afterwards"""
+        self._ready("flush")
         r = 0 if x is None else self._chunk(x, "flush").shape[2]
         n, T = self.samples_in, self.samples_in + r
         if T < self.L:
@@ -330,7 +295,129 @@ class LiveDenoiser:
                 torch.empty(self.S * nw * self.leads * 2, device=self.eng.device)
             self._run(xd, r, k0, nw, T, lo, T - lo, out, False, stats)
         if n >= self.L and T > lo:    # the last regular window of the pushes: it keeps [lo, T) if it is the stream's last one
-            _lib.check(_lib.lib().ral_live_emit(_ptr(self.last_y), _ptr(self.last_stats), self.S, self.leads, self.L, self.hop,
-                                                k0 - 1, 1, T, 0, self.S, lo, T - lo, _ptr(out), None, None, _stream()))
+            self._emit_last(k0 - 1, T, lo, out)
         self.reset()
         return out
+
+
+class LiveDenoiser(_LiveBase):
+    """S streams denoised while they arrive, in lockstep chunks of C samples (C a positive multiple of hop = L - overlap).
+
+    `push(x)` takes the next chunk of every stream, x (S, leads, C), and returns the samples that have become final, (S, leads,
+    m) on the device: nothing before L samples have arrived, samples [0, F(n)) when the first window completes
+    (`live_frontier`), then C per push, `latency` samples behind the newest one.  `flush(x=None)` takes an optional last chunk of
+    any length r >= 0, returns the rest of every stream and resets the object.  Concatenated per stream, everything `push` and
+    `flush` returned equals `StreamingDenoiser(model, overlap=overlap).denoise(record)`: the same windows, per-window z-score,
+    stitch rule and right-aligned last window.
+
+    Per push `ral_live_windows` gathers every stream's new windows straight from its last L samples (kept on the device, two
+    buffers used in turn: a push reads one and writes the other) and the chunk, the model runs them in batches of at most
+    max_batch windows, and `ral_live_emit` writes the samples they keep.  Once the lag is constant (the first L samples have
+    arrived) a push replays one of two captured hipGraphs, by push parity; they are captured again when the model's parameter
+    generation moves (the eval-mode capture leaves out the preparation of the weight planes).  Earlier pushes and `flush` run
+    eagerly.  Accepts the 1- and 2-lead models of `StreamingDenoiser` (RALENet, UNet, ACDAE, DANet); puts the model in eval mode.
+    A 12-lead `NewRALE` streams through `NewRALELiveDenoiser`."""
+
+    def __init__(self, model, streams, chunk, overlap=0, use_graph=True):
+        if isinstance(model, NewRALE):
+            raise _lib.RalError("LiveDenoiser does not take a NewRALE: live 12-lead streams run through NewRALELiveDenoiser")
+        e = model.eng
+        nw = self._setup(model, e, e.leads, streams, chunk, overlap, use_graph)
+        dev = e.device
+        z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
+        self.hist = [z(self.S, self.leads, self.L), z(self.S, self.leads, self.L)]    # push parity p reads hist[p], writes hist[1 - p]
+        self.x = z(self.S, self.leads, self.C)
+        self.win = z(min(e.max_batch, self.S * nw), self.leads, self.L)      # one batch of windows
+        self.y = torch.zeros_like(self.win)
+        self.stats = z(self.S * nw * self.leads * 2)
+        self.out = z(self.S, self.leads, self.C)
+        self.last_y, self.last_stats = z(self.S, self.leads, self.L), z(self.S * self.leads * 2)   # the last regular window
+        model.eval()
+        self.reset()
+
+    def _run(self, x, C, k0, nw, T, lo, m, out, keep, stats):
+        """enqueue one call on the current stream (captured or eager): the windows k0 .. k0 + nw - 1 of every stream from the
+        history and x (C samples), the model, the kept samples in [lo, lo + m) -> out; a push (keep) also writes the next
+        history and keeps the last window.  stats: (mean, std) of the S * nw windows"""
+        lib, e, S, n = _lib.lib(), self.eng, self.S, self.samples_in
+        h_in, h_out = self.hist[self.parity], (self.hist[1 - self.parity] if keep else None)
+        base, batch = n - self.L, self.win.shape[0]
+        for w0 in range(0, max(S * nw, 1), batch):
+            nb = min(batch, S * nw - w0)
+            if nb == 0 and h_out is None:
+                break
+            _lib.check(lib.ral_live_windows(_ptr(h_in), _ptr(x), _ptr(h_out if w0 == 0 else None), S, self.leads, self.L,
+                                            self.hop, C, base, k0, nw, T, w0, nb, _ptr(self.win), _ptr(stats), _stream()))
+            if nb == 0:
+                break
+            _lib.check(lib.ral_forward(e.h, _ptr(self.win), _ptr(self.y), nb, 0, _stream()))
+            _lib.check(lib.ral_live_emit(_ptr(self.y), _ptr(stats), S, self.leads, self.L, self.hop, k0, nw, T, w0, nb, lo,
+                                         m, _ptr(out), _ptr(self.last_y if keep else None),
+                                         _ptr(self.last_stats if keep else None), _stream()))
+
+    def _emit_last(self, k, T, lo, out):
+        _lib.check(_lib.lib().ral_live_emit(_ptr(self.last_y), _ptr(self.last_stats), self.S, self.leads, self.L, self.hop,
+                                            k, 1, T, 0, self.S, lo, T - lo, _ptr(out), None, None, _stream()))
+
+
+class NewRALELiveDenoiser(_LiveBase):
+    """`LiveDenoiser` for a 12-lead `NewRALE`: S streams of 12 leads denoised while they arrive, in lockstep chunks of C samples
+    (a positive multiple of hop = L - overlap; L from the inner model).  The same surface and contract: `push(x)` with x
+    (S, 12, C), `flush(x=None)`, `reset()`, `latency`; concatenated per stream, what they return equals
+    `StreamingDenoiser(model, overlap=overlap).denoise(record)`.
+
+    Per batch of at most max_batch windows (of the inner engine) `ral_newrale_live_front` gathers every stream's new windows
+    from its history and the chunk, z-scores them per lead and applies conv1 and conv2 (its first launch of a push also writes
+    the next history), the inner model runs its eval-mode forward, and `ral_newrale_live_back` applies conv3 and conv4,
+    de-normalises and writes the kept samples.  The steady-state graphs are captured again when `model.generation()` (adapter,
+    inner model) moves.  `push` and `flush` refuse a model in training mode (the inner BatchNorm would use batch statistics);
+    the constructor puts the model in eval mode."""
+
+    def __init__(self, model, streams, chunk, overlap=0, use_graph=True):
+        if not isinstance(model, NewRALE):
+            raise _lib.RalError(f"NewRALELiveDenoiser takes a NewRALE (got {type(model).__name__}; LiveDenoiser takes the "
+                                "1- and 2-lead models)")
+        e = model.rale.eng
+        nw = self._setup(model, e, 12, streams, chunk, overlap, use_graph)
+        dev = e.device
+        z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
+        self.hist = [z(self.S, 12, self.L), z(self.S, 12, self.L)]    # push parity p reads hist[p], writes hist[1 - p]
+        self.x = z(self.S, 12, self.C)
+        self.win = z(min(e.max_batch, self.S * nw), 2, self.L)      # the inner model's input and output for one batch
+        self.y = torch.zeros_like(self.win)
+        self.stats = z(self.S * nw * 12 * 2)
+        self.out = z(self.S, 12, self.C)
+        self.last_y, self.last_stats = z(self.S, 2, self.L), z(self.S * 12 * 2)   # the last regular window (inner output)
+        model.eval()
+        self.reset()
+
+    def _generation(self):
+        return self.model.generation()
+
+    def _ready(self, what):
+        if self.model.training:
+            raise _lib.RalError(f"NewRALELiveDenoiser.{what} runs the eval-mode forward: call model.eval() first")
+
+    def _run(self, x, C, k0, nw, T, lo, m, out, keep, stats):
+        """as LiveDenoiser._run, through the adapter kernels around the inner model"""
+        lib, h, S, n = _lib.lib(), self.eng.h, self.S, self.samples_in
+        prm = _ptr(self.model.params)
+        h_in, h_out = self.hist[self.parity], (self.hist[1 - self.parity] if keep else None)
+        base, batch = n - self.L, self.win.shape[0]
+        for w0 in range(0, max(S * nw, 1), batch):
+            nb = min(batch, S * nw - w0)
+            if nb == 0 and h_out is None:
+                break
+            _lib.check(lib.ral_newrale_live_front(_ptr(h_in), _ptr(x), _ptr(h_out if w0 == 0 else None), S, self.L, self.hop, C,
+                                                  base, k0, nw, T, w0, nb, prm, _ptr(self.win), _ptr(stats), _stream()))
+            if nb == 0:
+                break
+            _lib.check(lib.ral_forward(h, _ptr(self.win), _ptr(self.y), nb, 0, _stream()))
+            _lib.check(lib.ral_newrale_live_back(_ptr(self.y), _ptr(stats), prm, S, self.L, self.hop, k0, nw, T, w0, nb, lo, m,
+                                                 _ptr(out), _ptr(self.last_y if keep else None),
+                                                 _ptr(self.last_stats if keep else None), _stream()))
+
+    def _emit_last(self, k, T, lo, out):
+        _lib.check(_lib.lib().ral_newrale_live_back(_ptr(self.last_y), _ptr(self.last_stats), _ptr(self.model.params), self.S,
+                                                    self.L, self.hop, k, 1, T, 0, self.S, lo, T - lo, _ptr(out), None, None,
+                                                    _stream()))
