@@ -7,6 +7,8 @@ import ctypes as C
 import os
 import subprocess
 
+import numpy as np
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RAL_LIB_PATH") or os.path.join(HERE, "libralenet.so")   # override: diagnostic builds only
 CSRC = os.path.join(HERE, "csrc")
@@ -22,6 +24,13 @@ class RalConfig(C.Structure):
 
 class RalError(RuntimeError):
     pass
+
+
+# ral_pool_row (include/ralenet.h): one row of a stream pool's per-call table, as a numpy record
+POOL_ROW = np.dtype([("n0", "<i8"), ("T", "<i8"), ("k0", "<i8"), ("lo", "<i8"), ("x_off", "<i8"), ("out_off", "<i8"),
+                     ("w_off", "<i8"), ("slot", "<i4"), ("c", "<i4"), ("nw", "<i4"), ("m", "<i4"), ("turn", "<i4"),
+                     ("flags", "<i4")])
+POOL_KEEP = 1
 
 
 def build(jobs=8, verbose=False):
@@ -93,6 +102,14 @@ _SIGS = {
                                          C.c_int64, C.c_int64, C.c_int, _VP, _VP, _VP, _VP]),
     "ral_newrale_live_back": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int64,
                                         C.c_int, C.c_int64, C.c_int, _VP, _VP, _VP, _VP]),
+    "ral_pool_windows": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int, _VP, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.c_int64, C.c_int, _VP, _VP, _VP]),
+    "ral_pool_emit": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int,
+                                C.c_int, _VP, C.c_int64, _VP, _VP, _VP]),
+    "ral_newrale_pool_front": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int, _VP, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                         C.c_int64, C.c_int, _VP, _VP, _VP, _VP]),
+    "ral_newrale_pool_back": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, _VP, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64,
+                                        C.c_int, C.c_int, _VP, C.c_int64, _VP, _VP, _VP]),
     "ral_attention_forward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
     "ral_attention_backward_scratch_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "ral_attention_backward": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, C.c_int, C.c_int, C.c_int,

@@ -1563,6 +1563,74 @@ int ral_newrale_live_back(const float* inner_y, const float* stats, const float*
   return 0;
 }
 
+// a refused pool call: the one rule that is broken and, if it is a row's, which row
+static int pool_fail(const char* name, const char* why, int bad, int rows, long long cap, int L, int hop, long long total,
+                     long long w0, int nb) {
+  char row[32] = "";
+  if (bad >= 0) snprintf(row, sizeof(row), " in row %d", bad);
+  return fail("%s: need %s%s (rows=%d capacity=%lld L=%d hop=%d packed=%lld w0=%lld nb=%d)", name, why, row, rows, cap, L, hop,
+              total, w0, nb);
+}
+
+int ral_pool_windows(float* hist, const float* x, int64_t x_total, const ral_pool_row* table, int rows, ral_pool_row* table_dev,
+                     int upload, int64_t capacity, int leads, int L, int hop, int write_hist, int64_t w0, int nb, float* win,
+                     float* stats, ral_stream s) {
+  if (!hist || !x || !table || !table_dev || !win || !stats) return fail("pool_windows: null pointer");
+  const char* why = nullptr;
+  int bad = -1;
+  const int rc = launch_pool_windows(hist, x, (long long)x_total, table, rows, table_dev, upload, (long long)capacity, leads, L, hop,
+                                     write_hist, (long long)w0, nb, win, stats, (hipStream_t)s, &why, &bad);
+  if (rc == -1) return pool_fail("pool_windows", why, bad, rows, (long long)capacity, L, hop, (long long)x_total, (long long)w0, nb);
+  if (rc) return fail("pool_windows: copying the table to the device failed");
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int ral_pool_emit(const float* y, const float* stats, const ral_pool_row* table, int rows, ral_pool_row* table_dev, int upload,
+                  int64_t capacity, int leads, int L, int hop, int64_t w0, int nb, int from_last, float* out, int64_t out_total,
+                  float* last_y, float* last_stats, ral_stream s) {
+  if (!y || !stats || !table || !table_dev || !out) return fail("pool_emit: null pointer");
+  const char* why = nullptr;
+  int bad = -1;
+  const int rc = launch_pool_emit(y, stats, table, rows, table_dev, upload, (long long)capacity, leads, L, hop, (long long)w0, nb,
+                                  from_last, out, (long long)out_total, last_y, last_stats, (hipStream_t)s, &why, &bad);
+  if (rc == -1) return pool_fail("pool_emit", why, bad, rows, (long long)capacity, L, hop, (long long)out_total, (long long)w0, nb);
+  if (rc) return fail("pool_emit: copying the table to the device failed");
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int ral_newrale_pool_front(float* hist, const float* x, int64_t x_total, const ral_pool_row* table, int rows,
+                           ral_pool_row* table_dev, int upload, int64_t capacity, int L, int hop, int write_hist, int64_t w0,
+                           int nb, const float* adapter_params, float* inner_x, float* stats, ral_stream s) {
+  if (!hist || !x || !table || !table_dev || !adapter_params || !inner_x || !stats) return fail("newrale_pool_front: null pointer");
+  const char* why = nullptr;
+  int bad = -1;
+  const int rc = launch_newrale_pool_front(hist, x, (long long)x_total, table, rows, table_dev, upload, (long long)capacity, L, hop,
+                                           write_hist, (long long)w0, nb, adapter_params, inner_x, stats, (hipStream_t)s, &why, &bad);
+  if (rc == -1)
+    return pool_fail("newrale_pool_front", why, bad, rows, (long long)capacity, L, hop, (long long)x_total, (long long)w0, nb);
+  if (rc) return fail("newrale_pool_front: copying the table to the device failed");
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int ral_newrale_pool_back(const float* inner_y, const float* stats, const float* adapter_params, const ral_pool_row* table,
+                          int rows, ral_pool_row* table_dev, int upload, int64_t capacity, int L, int hop, int64_t w0, int nb,
+                          int from_last, float* out, int64_t out_total, float* last_y, float* last_stats, ral_stream s) {
+  if (!inner_y || !stats || !adapter_params || !table || !table_dev || !out) return fail("newrale_pool_back: null pointer");
+  const char* why = nullptr;
+  int bad = -1;
+  const int rc = launch_newrale_pool_back(inner_y, stats, adapter_params, table, rows, table_dev, upload, (long long)capacity, L,
+                                          hop, (long long)w0, nb, from_last, out, (long long)out_total, last_y, last_stats,
+                                          (hipStream_t)s, &why, &bad);
+  if (rc == -1)
+    return pool_fail("newrale_pool_back", why, bad, rows, (long long)capacity, L, hop, (long long)out_total, (long long)w0, nb);
+  if (rc) return fail("newrale_pool_back: copying the table to the device failed");
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 int ral_wavelet_denoise(const float* x, float* y, int64_t rows, int L, float threshold, ral_stream s) {
   if (!x || !y) return fail("wavelet_denoise: null pointer");
   if (!(threshold >= 0.f)) return fail("wavelet_denoise: the threshold factor must be non-negative (got %g)", (double)threshold);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include "ral_device.hpp"
+#include "../../include/ralenet.h"   // ral_pool_row
 
 // gfx950 has 160 KB of LDS per CU; dynamic LDS above 64 KB must be opted into per kernel.
 #define RAL_SET_LDS(kernel, bytes)                                                                     \
@@ -97,6 +98,21 @@ int launch_newrale_live_front(const float* hist, const float* x, float* hist_out
 int launch_newrale_live_back(const float* iy, const float* stats, const float* prm, long long S, int L, int hop, long long k0,
                              int nw, long long T, long long w0, int nb, long long lo, int m, float* out, float* last_y,
                              float* last_stats, hipStream_t s);
+// the stream pool (ral_pool_windows / ral_pool_emit, ral_newrale_pool_front / _back): the host table is checked, then copied to
+// tab_dev on s (upload != 0), then the kernel is launched; -1: bad arguments (*why: the rule that is broken, *bad: the row that breaks it or -1), -2: the copy failed
+int launch_pool_windows(float* hist, const float* x, long long x_total, const ral_pool_row* tab, int rows, ral_pool_row* tab_dev,
+                        int upload, long long cap, int leads, int L, int hop, int write_hist, long long w0, int nb, float* win,
+                        float* stats, hipStream_t s, const char** why, int* bad);
+int launch_pool_emit(const float* y, const float* stats, const ral_pool_row* tab, int rows, ral_pool_row* tab_dev, int upload,
+                     long long cap, int leads, int L, int hop, long long w0, int nb, int from_last, float* out,
+                     long long out_total, float* last_y, float* last_stats, hipStream_t s, const char** why, int* bad);
+int launch_newrale_pool_front(float* hist, const float* x, long long x_total, const ral_pool_row* tab, int rows,
+                              ral_pool_row* tab_dev, int upload, long long cap, int L, int hop, int write_hist, long long w0,
+                              int nb, const float* prm, float* inner, float* stats, hipStream_t s, const char** why, int* bad);
+int launch_newrale_pool_back(const float* iy, const float* stats, const float* prm, const ral_pool_row* tab, int rows,
+                             ral_pool_row* tab_dev, int upload, long long cap, int L, int hop, long long w0, int nb, int from_last,
+                             float* out, long long out_total, float* last_y, float* last_stats, hipStream_t s, const char** why,
+                             int* bad);
 int launch_conv13_fwd(const float* x, const float* w, const float* b, float* y, int B, int cin, int cout, int L,
                       int lrelu, hipStream_t s);
 int launch_conv13_bwd(const float* x, const float* y, const float* dy, const float* w, float* gw, float* gb,

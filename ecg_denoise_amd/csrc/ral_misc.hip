@@ -3,6 +3,8 @@
 //
 // Reference behaviour: model/raletransformer.py:568-572, 636, 676-678;
 // local_utils/evaluate.py:10-51; denoise_train.py:24,53 (Adam lr 1e-3, mse mean).
+#include <vector>
+
 #include "ral_device.hpp"
 #include "ral_kernels.hpp"
 
@@ -925,10 +927,12 @@ struct NrLiveWindows {     // a live call (k_live_windows' geometry, 12 leads): 
 };
 
 // Where the kept samples of a window of k_newrale_back go: window(sk, i) -> its number gw, the samples [ob, oe) of the window
-// it keeps, and the element out[dst + c * stride + l] that takes its sample l of lead c; ly: where the inner output of the
-// window is kept whole (live calls, the last window of every stream), or null.
+// it keeps, and the element out[dst + c * stride + l] that takes its sample l of lead c; src: where its inner output is read
+// (window i of the launch at i * 2 L, a pool's kept window at its slot); ly: where the inner output of the window is kept
+// whole (live calls, the last window of every stream), or null.
 struct NrKept {
   long long gw, dst, stride;
+  long long src;           // the window's inner output is iy[src, src + 2 L)
   int ob, oe;
   float* ly;
 };
@@ -950,6 +954,7 @@ struct NrRecordKeep {      // into the record group (R, 12, T): k_stream_stitch'
     kp.oe = (int)(ke - start);
     kp.dst = r * NR_LEADS * T + start;
     kp.stride = T;
+    kp.src = (long long)i * 2 * L;
     kp.ly = nullptr;
     return kp;
   }
@@ -979,6 +984,7 @@ struct NrLiveKeep {        // into a live call's out (S, 12, m): the samples in 
     kp.oe = e > b ? (int)(e - start) : kp.ob;
     kp.dst = s * NR_LEADS * m + start - lo;   // (negative for start < lo: only l >= ob, t >= lo, is written)
     kp.stride = m;
+    kp.src = (long long)i * 2 * L;
     kp.ly = last_y && j == nw - 1 ? last_y + s * 2 * L : nullptr;
     return kp;
   }
@@ -1055,7 +1061,7 @@ __global__ __launch_bounds__(256) void k_newrale_back(Dst dst, int nw, const flo
     __syncthreads();
     for (int e = threadIdx.x; e < 2 * L; e += blockDim.x) {
       const int c = e / L, l = e - c * L;
-      const float v = iy[(size_t)i * 2 * L + e];
+      const float v = iy[kp.src + e];
       ys[c * LP + 6 + l] = v;
       if (kp.ly) kp.ly[e] = v;
     }
@@ -1142,6 +1148,310 @@ int launch_newrale_live_back(const float* iy, const float* stats, const float* p
   const size_t lds = newrale_back_lds(L);
   RAL_SET_LDS(k_newrale_back<NrLiveKeep>, lds);
   k_newrale_back<<<nb < NR_GRID ? nb : NR_GRID, 256, lds, s>>>(NrLiveKeep{out, last_y, last_stats, T, w0, lo, L, hop, (int)k0, nw, m},
+                                                               nb, iy, stats, prm);
+  return 0;
+}
+
+// =================================================================================
+// Stream pool (LivePool / NewRALELivePool, infer.py): the live kernels with every per-call scalar replaced by a row of a table,
+// ral_pool_row (include/ralenet.h), one row per stream the call names.  A slot of the pool keeps its last L samples in one of
+// two history planes, hist (2, capacity, leads, L): a row reads plane `turn` of its slot, and the history workgroups of the
+// call's first gather launch write the other plane for the rows that stay open (RAL_POOL_KEEP) - no workgroup reads what
+// another one writes, and the slots of a call are distinct.  V of a row is its history ++ its chunk, samples
+// [n0 - L, n0 + c) of the stream; positions below sample 0 are never read and are written as zeros.  Window gw of the call is
+// window k0 + (gw - w_off) of the row found by pool_find_row (the rows' w_off are the prefix sums of their nw).  The window
+// arithmetic is that of the live kernels: zscore_wave, stream_keep / stream_keep_open, stream_start, stream_kept.
+// =================================================================================
+typedef ral_pool_row PoolRow;
+
+// the row that holds window gw of the call: the last one with w_off <= gw (rows without windows share the w_off of the next
+// row with some, or the total behind the last one, so they are never the answer for gw below the total)
+RAL_DEV int pool_find_row(const PoolRow* __restrict__ tab, int rows, long long gw) {
+  int a = 0, b = rows - 1;
+  while (a < b) {
+    const int mid = (a + b + 1) >> 1;
+    if (tab[mid].w_off <= gw) a = mid; else b = mid - 1;
+  }
+  return a;
+}
+
+// What a workgroup derives from its row is the same in every lane.  Passing it through readfirstlane keeps it in scalar
+// registers: observed with -Rpass-analysis=kernel-resource-usage for gfx950, k_newrale_back<NrPoolKeep> needs 135 VGPRs
+// without these calls and 110 with them.
+RAL_DEV int pool_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+RAL_DEV long long pool_uniform(long long v) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long long)v);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)v >> 32));
+  return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+RAL_DEV StreamKeep pool_keep(const PoolRow& t, int L, int hop) { return t.T < 0 ? stream_keep_open(L, hop) : stream_keep(t.T, L, hop); }
+
+// the samples [b, e) of the stream that window k of row t (starting at `start`) gives to this call: what the window keeps
+// (stream_kept), inside [lo, lo + m) and inside the window, as k_live_emit clips them
+RAL_DEV void pool_kept(const StreamKeep& sk, const PoolRow& t, int k, long long start, int L, int hop, long long& b, long long& e) {
+  stream_kept(sk, k, t.T, hop, b, e);
+  b = b > t.lo ? b : t.lo;
+  b = b > start ? b : start;
+  e = e < t.lo + t.m ? e : t.lo + t.m;
+  e = e < start + L ? e : start + L;
+}
+
+// the next history of (row, lead): V[c, c + L), the last L samples the stream has received after this call
+RAL_DEV void pool_write_history(const PoolRow& t, int c, int leads, int L, size_t plane, float* hist, const float* __restrict__ x) {
+  const float* hr = hist + (size_t)t.turn * plane + ((size_t)t.slot * leads + c) * L;
+  const float* xr = x + t.x_off * leads + (long long)c * t.c - L;
+  float* dst = hist + (size_t)(1 - t.turn) * plane + ((size_t)t.slot * leads + c) * L;
+  const long long first = t.n0 + t.c - L;       // the stream position of dst[0]
+  for (int l = threadIdx.x; l < L; l += blockDim.x) {
+    const int v = t.c + l;
+    dst[l] = first + l < 0 ? 0.f : (v < L ? hr[v] : xr[v]);
+  }
+}
+
+__global__ __launch_bounds__(64) void k_pool_windows(float* hist, const float* __restrict__ x, const PoolRow* __restrict__ tab,
+                                                     int rows, long long cap, int leads, int L, int hop, long long w0, int nb,
+                                                     float* __restrict__ win, float* __restrict__ stats) {
+  const int nwl = nb * leads;
+  const size_t plane = (size_t)cap * leads * L;
+  if ((int)blockIdx.x >= nwl) {   // the history of one (row, lead)
+    const int rc = blockIdx.x - nwl, r = rc / leads;
+    const PoolRow t = tab[r];
+    if (t.flags & RAL_POOL_KEEP) pool_write_history(t, rc - r * leads, leads, L, plane, hist, x);
+    return;
+  }
+  const int i = blockIdx.x / leads, c = blockIdx.x - i * leads;   // window of this launch, lead
+  const long long gw = w0 + i;
+  const PoolRow t = tab[pool_find_row(tab, rows, gw)];
+  const StreamKeep sk = pool_keep(t, L, hop);
+  const int j = (int)(gw - t.w_off);
+  const int o = (int)(stream_start(sk, (int)t.k0 + j, t.T, L, hop) - (t.n0 - L));   // the window is V[o, o + L)
+  const float* hr = hist + (size_t)t.turn * plane + ((size_t)t.slot * leads + c) * L;
+  const float* xr = x + t.x_off * leads + (long long)c * t.c - L;
+  float mean, sd;
+  zscore_wave([=](int l) { const int v = o + l; return v < L ? hr[v] : xr[v]; }, win + ((size_t)i * leads + c) * L, L, mean, sd);
+  if (threadIdx.x == 0) { stats[(gw * leads + c) * 2] = mean; stats[(gw * leads + c) * 2 + 1] = sd; }
+}
+
+// y (nb, leads, L) and stats: the model output and (mean, std) of windows [w0, w0 + nb) of the call.  from_last: window gw is
+// the one window of row gw, and y / stats are the kept windows of the slots, (capacity, leads, L) and (capacity, leads, 2).
+__global__ __launch_bounds__(64) void k_pool_emit(const float* __restrict__ y, const float* __restrict__ stats,
+                                                  const PoolRow* __restrict__ tab, int rows, int leads, int L, int hop,
+                                                  long long w0, int from_last, float* __restrict__ out,
+                                                  float* __restrict__ last_y, float* __restrict__ last_stats) {
+  const int i = blockIdx.x / leads, c = blockIdx.x - i * leads;
+  const long long gw = w0 + i;
+  const PoolRow t = tab[from_last ? (int)gw : pool_find_row(tab, rows, gw)];
+  const StreamKeep sk = pool_keep(t, L, hop);
+  const int j = from_last ? 0 : (int)(gw - t.w_off), k = (int)t.k0 + j;
+  const long long start = stream_start(sk, k, t.T, L, hop);
+  long long b, e;
+  pool_kept(sk, t, k, start, L, hop, b, e);
+  const long long sw = from_last ? (long long)t.slot : gw;            // the window's place in stats
+  const float mean = stats[(sw * leads + c) * 2], sd = stats[(sw * leads + c) * 2 + 1];
+  const float* yr = y + ((size_t)(from_last ? t.slot : i) * leads + c) * L;
+  float* dst = out + t.out_off * leads + (long long)c * t.m - t.lo;
+  for (long long p = b + threadIdx.x; p < e; p += 64) dst[p] = fmaf(yr[p - start], sd, mean);
+  if (last_y && (t.flags & RAL_POOL_KEEP) && j == t.nw - 1) {
+    float* ly = last_y + ((size_t)t.slot * leads + c) * L;
+    for (int l = threadIdx.x; l < L; l += 64) ly[l] = yr[l];
+    if (threadIdx.x == 0) { last_stats[((size_t)t.slot * leads + c) * 2] = mean; last_stats[((size_t)t.slot * leads + c) * 2 + 1] = sd; }
+  }
+}
+
+// The table is checked here, on the host, before anything reaches the device: a wrong row would send a kernel out of bounds.
+// -> null if the table is sound, else the rule that is broken, with *bad the row that breaks it (-1: the geometry).
+// x_total / out_total: samples per lead in the packed chunk / output buffer (ignored when negative: the emit / gather does not
+// touch that buffer).  from_last: the table of an emit of kept windows (one window per row, the last regular one before n0).
+// walk = false (a launch that reuses the device copy of a table checked at its upload): the geometry only.
+static const char* pool_table_fault(const PoolRow* tab, int rows, long long cap, int leads, int L, int hop, int lmul, int lmax,
+                                    long long x_total, long long out_total, bool from_last, bool walk, int* bad) {
+  *bad = -1;
+  if (rows < 1) return "rows >= 1";
+  if (cap < 1) return "capacity >= 1";
+  if (leads < 1) return "leads >= 1";
+  if (L < lmul || L % lmul != 0 || L > lmax) return lmul == 64 ? "L a multiple of 64 and <= 2048" : "L a multiple of 16 in [16, 1024]";
+  if (hop < 1 || hop > L || ((L - hop) & 1)) return "1 <= hop <= L with L - hop even";
+  if (!walk) return nullptr;
+  std::vector<bool> seen((size_t)cap, false);
+  long long w_sum = 0;
+  for (int r = 0; r < rows; ++r) {
+    const PoolRow& t = tab[r];
+    *bad = r;
+    if (t.slot < 0 || t.slot >= cap) return "0 <= slot < capacity";
+    if (seen[(size_t)t.slot]) return "every slot at most once";
+    seen[(size_t)t.slot] = true;
+    if (t.n0 < 0 || t.c < 0 || t.c > 0x3fffffff || t.nw < 0 || t.m < 0 || t.k0 < 0 || t.lo < 0)
+      return "n0, c, nw, m, k0, lo >= 0 and c < 2^30";
+    if (t.turn != 0 && t.turn != 1) return "turn 0 or 1";
+    if (t.flags & ~(RAL_POOL_KEEP)) return "flags RAL_POOL_KEEP or 0";
+    if (t.T >= 0 ? (t.T < L || t.T != t.n0 + t.c || (t.flags & RAL_POOL_KEEP)) : (t.T != -1 || !(t.flags & RAL_POOL_KEEP) || t.c < 1))
+      return "T = n0 + c >= L without RAL_POOL_KEEP, or T = -1 with RAL_POOL_KEEP and c >= 1";
+    if (t.w_off != w_sum) return "w_off the prefix sum of nw";
+    w_sum += t.nw;
+    if (x_total >= 0 && (t.x_off < 0 || t.x_off + t.c > x_total)) return "the chunk inside the packed chunks";
+    if (out_total >= 0 && (t.out_off < 0 || t.out_off + t.m > out_total)) return "the emitted samples inside the packed output";
+    if (t.lo + t.m > t.n0 + t.c) return "lo + m <= n0 + c (nothing emitted that was not received)";
+    if (from_last) {   // the last regular window complete at n0: it ends at or before n0, the next one would not
+      long long st;
+      if (t.T < 0 || t.nw != 1 || t.n0 < L || !live_window_start(t.T, L, hop, t.k0, st) || t.k0 * hop + L > t.n0 ||
+          (t.k0 + 1) * hop + L <= t.n0)
+        return "from_last rows with T known, nw = 1, n0 >= L and k0 the last regular window complete at n0";
+    } else if (t.nw > 0) {
+      long long first, last;
+      if (!live_window_start(t.T, L, hop, t.k0, first) || !live_window_start(t.T, L, hop, t.k0 + t.nw - 1, last))
+        return "windows k0 .. k0 + nw - 1 in the stream";
+      if (first < t.n0 - L || first < 0) return "the first window at or after the history, max(n0 - L, 0)";
+      if (last + L > t.n0 + t.c) return "the last window inside the received samples, n0 + c";
+      if (t.lo < first || t.lo + t.m > last + L) return "[lo, lo + m) inside the windows";
+    }
+  }
+  *bad = -1;
+  return w_sum <= 0x7fffffffLL ? nullptr : "at most 2^31 - 1 windows";
+}
+
+static long long pool_windows_total(const PoolRow* tab, int rows) { return tab[rows - 1].w_off + tab[rows - 1].nw; }
+
+// the checks of a gather / an emit launch: the table (walked when it is uploaded), then the launch's own arguments
+static const char* pool_gather_fault(const PoolRow* tab, int rows, long long cap, int leads, int L, int hop, int lmul, int lmax,
+                                     long long x_total, int upload, int write_hist, long long w0, int nb, int* bad) {
+  *bad = -1;
+  if (x_total < 0) return "x_total >= 0";
+  if (const char* why = pool_table_fault(tab, rows, cap, leads, L, hop, lmul, lmax, x_total, -1, false, upload != 0, bad)) return why;
+  if (w0 < 0 || nb < 0 || w0 + nb > pool_windows_total(tab, rows)) return "a window range inside the call's windows";
+  if (nb == 0 && !write_hist) return "nb >= 1 or write_hist";
+  if ((long long)nb * leads + (write_hist ? (long long)rows * leads : 0) > 0x7fffffffLL) return "at most 2^31 - 1 workgroups";
+  return nullptr;
+}
+
+static const char* pool_emit_fault(const PoolRow* tab, int rows, long long cap, int leads, int L, int hop, int lmul, int lmax,
+                                   long long out_total, int upload, long long w0, int nb, int from_last, const float* last_y,
+                                   const float* last_stats, int* bad) {
+  *bad = -1;
+  if (out_total < 0) return "out_total >= 0";
+  if (const char* why = pool_table_fault(tab, rows, cap, leads, L, hop, lmul, lmax, -1, out_total, from_last != 0, upload != 0, bad))
+    return why;
+  if (w0 < 0 || nb < 1 || w0 + nb > pool_windows_total(tab, rows)) return "a window range of nb >= 1 windows inside the call's";
+  if (!last_y != !last_stats) return "last_y and last_stats both given or both null";
+  if (from_last && last_y) return "last_y and last_stats null with from_last";
+  if ((long long)nb * leads > 0x7fffffffLL) return "at most 2^31 - 1 workgroups";
+  return nullptr;
+}
+
+static int pool_upload(const PoolRow* tab, int rows, PoolRow* tab_dev, hipStream_t s) {
+  return hipMemcpyAsync(tab_dev, tab, (size_t)rows * sizeof(PoolRow), hipMemcpyHostToDevice, s) == hipSuccess ? 0 : -2;
+}
+
+int launch_pool_windows(float* hist, const float* x, long long x_total, const ral_pool_row* tab, int rows, ral_pool_row* tab_dev,
+                        int upload, long long cap, int leads, int L, int hop, int write_hist, long long w0, int nb, float* win,
+                        float* stats, hipStream_t s, const char** why, int* bad) {
+  if ((*why = pool_gather_fault(tab, rows, cap, leads, L, hop, 64, 2048, x_total, upload, write_hist, w0, nb, bad))) return -1;
+  const long long grid = (long long)nb * leads + (write_hist ? (long long)rows * leads : 0);
+  if (upload && pool_upload(tab, rows, tab_dev, s)) return -2;
+  k_pool_windows<<<(int)grid, 64, 0, s>>>(hist, x, tab_dev, rows, cap, leads, L, hop, w0, nb, win, stats);
+  return 0;
+}
+
+int launch_pool_emit(const float* y, const float* stats, const ral_pool_row* tab, int rows, ral_pool_row* tab_dev, int upload,
+                     long long cap, int leads, int L, int hop, long long w0, int nb, int from_last, float* out,
+                     long long out_total, float* last_y, float* last_stats, hipStream_t s, const char** why, int* bad) {
+  if ((*why = pool_emit_fault(tab, rows, cap, leads, L, hop, 64, 2048, out_total, upload, w0, nb, from_last, last_y, last_stats, bad)))
+    return -1;
+  if (upload && pool_upload(tab, rows, tab_dev, s)) return -2;
+  k_pool_emit<<<nb * leads, 64, 0, s>>>(y, stats, tab_dev, rows, leads, L, hop, w0, from_last, out, last_y, last_stats);
+  return 0;
+}
+
+// 12-lead pool streams (NewRALELivePool): the bodies of k_newrale_front / k_newrale_back on the pool's table.  The stream
+// geometry differs from row to row, so keep() is a placeholder and window() works out the row's own.
+struct NrPoolWindows {
+  float* hist;             // (2, capacity, 12, L)
+  const float* x;          // the packed chunks
+  const PoolRow* tab;
+  long long cap, w0;
+  int rows, L, hop;
+  typedef NrLiveWindows::Reader Reader;
+  RAL_DEV StreamKeep keep() const { return stream_keep_open(L, hop); }
+  RAL_DEV long long window(const StreamKeep&, int i, Reader& src) const {
+    const long long gw = w0 + i;
+    const PoolRow t = tab[pool_find_row(tab, rows, gw)];
+    const StreamKeep sk = pool_keep(t, L, hop);
+    const int j = (int)(gw - t.w_off);
+    src.o = pool_uniform((int)(stream_start(sk, (int)t.k0 + j, t.T, L, hop) - (t.n0 - L)));
+    src.hr = hist + pool_uniform((long long)(((size_t)t.turn * cap + t.slot) * NR_LEADS * L));
+    src.xr = x + pool_uniform((long long)(t.x_off * NR_LEADS - L));
+    src.L = L;
+    src.C = pool_uniform(t.c);
+    return gw;
+  }
+  // workgroup g of ng writes the next history of the (row, lead) pairs g, g + ng, ... of the rows that stay open
+  RAL_DEV void write_history(int g, int ng) const {
+    for (int rc = g; rc < rows * NR_LEADS; rc += ng) {
+      const int r = rc / NR_LEADS;
+      const PoolRow t = tab[r];
+      if (t.flags & RAL_POOL_KEEP) pool_write_history(t, rc - r * NR_LEADS, NR_LEADS, L, (size_t)cap * NR_LEADS * L, hist, x);
+    }
+  }
+};
+
+struct NrPoolKeep {        // into the packed output of a pool call: row t's samples [lo, lo + m) as (12, m) at out_off * 12
+  float* out;
+  float* last_y;           // (capacity, 2, L) or null
+  float* last_stats;       // (capacity, 12, 2) or null (with last_y)
+  const PoolRow* tab;
+  long long w0;
+  int rows, L, hop, from_last;
+  RAL_DEV StreamKeep keep() const { return stream_keep_open(L, hop); }
+  RAL_DEV NrKept window(const StreamKeep&, int i) const {
+    NrKept kp;
+    const long long g = w0 + i;
+    const PoolRow t = tab[from_last ? (int)g : pool_find_row(tab, rows, g)];
+    const StreamKeep sk = pool_keep(t, L, hop);
+    const int j = from_last ? 0 : (int)(g - t.w_off), k = (int)t.k0 + j;
+    const long long start = stream_start(sk, k, t.T, L, hop);
+    long long b, e;
+    pool_kept(sk, t, k, start, L, hop, b, e);
+    kp.gw = pool_uniform(from_last ? (long long)t.slot : g);    // (from_last: stats are the slots' kept ones)
+    kp.ob = pool_uniform((int)(b - start));
+    kp.oe = e > b ? pool_uniform((int)(e - start)) : kp.ob;
+    kp.dst = pool_uniform((long long)(t.out_off * NR_LEADS + start - t.lo));
+    kp.stride = pool_uniform(t.m);
+    kp.src = pool_uniform((from_last ? (long long)t.slot : (long long)i) * 2 * L);
+    const long long keep_at = last_y && (t.flags & RAL_POOL_KEEP) && j == t.nw - 1 ? (long long)t.slot * 2 * L : -1;
+    kp.ly = pool_uniform(keep_at) >= 0 ? last_y + pool_uniform(keep_at) : nullptr;
+    return kp;
+  }
+  RAL_DEV void keep_stats(const NrKept& kp, const float* stats) const {
+    if (kp.ly && threadIdx.x < 2 * NR_LEADS)
+      last_stats[((kp.ly - last_y) / (2 * L)) * 2 * NR_LEADS + threadIdx.x] = stats[kp.gw * 2 * NR_LEADS + threadIdx.x];
+  }
+};
+
+int launch_newrale_pool_front(float* hist, const float* x, long long x_total, const ral_pool_row* tab, int rows,
+                              ral_pool_row* tab_dev, int upload, long long cap, int L, int hop, int write_hist, long long w0,
+                              int nb, const float* prm, float* inner, float* stats, hipStream_t s, const char** why, int* bad) {
+  if ((*why = pool_gather_fault(tab, rows, cap, NR_LEADS, L, hop, 16, 1024, x_total, upload, write_hist, w0, nb, bad))) return -1;
+  if (upload && pool_upload(tab, rows, tab_dev, s)) return -2;
+  const long long hrows = (long long)rows * NR_LEADS;
+  const int nwg = nb < NR_GRID ? nb : NR_GRID;
+  const int nhg = write_hist ? (int)(hrows < NR_GRID ? hrows : NR_GRID) : 0;
+  const size_t lds = newrale_front_lds(L);
+  RAL_SET_LDS(k_newrale_front<NrPoolWindows>, lds);
+  k_newrale_front<<<nwg + nhg, 256, lds, s>>>(NrPoolWindows{hist, x, tab_dev, cap, w0, rows, L, hop}, nb, nwg, prm, inner, stats);
+  return 0;
+}
+
+int launch_newrale_pool_back(const float* iy, const float* stats, const float* prm, const ral_pool_row* tab, int rows,
+                             ral_pool_row* tab_dev, int upload, long long cap, int L, int hop, long long w0, int nb, int from_last,
+                             float* out, long long out_total, float* last_y, float* last_stats, hipStream_t s, const char** why,
+                             int* bad) {
+  if ((*why = pool_emit_fault(tab, rows, cap, NR_LEADS, L, hop, 16, 1024, out_total, upload, w0, nb, from_last, last_y, last_stats,
+                              bad)))
+    return -1;
+  if (upload && pool_upload(tab, rows, tab_dev, s)) return -2;
+  const size_t lds = newrale_back_lds(L);
+  RAL_SET_LDS(k_newrale_back<NrPoolKeep>, lds);
+  k_newrale_back<<<nb < NR_GRID ? nb : NR_GRID, 256, lds, s>>>(NrPoolKeep{out, last_y, last_stats, tab_dev, w0, rows, L, hop, from_last},
                                                                nb, iy, stats, prm);
   return 0;
 }

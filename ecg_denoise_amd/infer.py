@@ -13,7 +13,9 @@ model's parameter generation and are captured again once the weights change (the
 preparation of its weight planes out of a capture).
 
 `LiveDenoiser` denoises S streams that arrive chunk by chunk, `NewRALELiveDenoiser` S 12-lead streams through a `NewRALE`;
-what they return, concatenated, is what `StreamingDenoiser` returns for the complete records."""
+what they return, concatenated, is what `StreamingDenoiser` returns for the complete records.  `LivePool` and
+`NewRALELivePool` do the same for streams that start, stop and arrive independently of each other."""
+import numpy as np
 import torch
 
 from . import _lib
@@ -421,3 +423,257 @@ class NewRALELiveDenoiser(_LiveBase):
         _lib.check(_lib.lib().ral_newrale_live_back(_ptr(self.last_y), _ptr(self.last_stats), _ptr(self.model.params), self.S,
                                                     self.L, self.hop, k, 1, T, 0, self.S, lo, T - lo, _ptr(out), None, None,
                                                     _stream()))
+
+
+def pool_plan(n0, c, closing, L, hop):
+    """What one call does for a stream that had received n0 samples and now gets c more (closing: the stream ends with them, and
+    n0 + c >= L) -> (first window k0, window count nw, lo, m, T): the call runs windows k0 .. k0 + nw - 1 of the stream, emits
+    samples [lo, lo + m), and T is the stream's length (-1 while it stays open).  An open stream runs the regular windows that
+    became complete and emits up to `live_frontier(n0 + c)`; a closing one runs all remaining windows (the right-aligned last
+    one among them) and emits up to its end.  A pure function of its arguments, elementwise over integers or integer arrays."""
+    n0, c = np.asarray(n0, dtype=np.int64), np.asarray(c, dtype=np.int64)
+    closing = np.asarray(closing, dtype=bool)
+    n1, h = n0 + c, (L - hop) // 2
+    n_reg = lambda n: np.where(n >= L, (n - L) // hop + 1, 0)
+    front = lambda n: np.where(n >= L, n_reg(n) * hop + h, 0)
+    k0, lo = n_reg(n0), front(n0)
+    n_all = n_reg(n1) + ((n1 - L) % hop != 0)           # every window of a stream of n1 samples
+    nw = np.where(closing, n_all, n_reg(n1)) - k0
+    m = np.where(closing, n1, front(n1)) - lo
+    return k0, nw, lo, m, np.where(closing, n1, -1)
+
+
+class PoolState:
+    """The host side of a stream pool, without a device: which slots hold an open stream, how many samples each has received and
+    which of its two history buffers is current.  `plan` checks the arguments of a call and builds its tables (`_lib.POOL_ROW`)
+    without changing anything; `commit` applies a planned call."""
+
+    def __init__(self, capacity, leads, L, overlap, name="LivePool", grid=(64, 2048)):
+        if L < grid[0] or L % grid[0] or L > grid[1]:      # the window lengths of the pool's gather / emit kernels
+            raise _lib.RalError(f"{name}: L must be a multiple of {grid[0]} up to {grid[1]} (got {L})")
+        if overlap < 0 or overlap >= L or overlap % 2:
+            raise _lib.RalError("overlap must be an even number of samples in [0, L)")
+        if capacity < 1:
+            raise _lib.RalError("capacity must be >= 1")
+        self.capacity, self.leads, self.L, self.hop, self.name = int(capacity), int(leads), int(L), int(L - overlap), name
+        self.n = np.zeros(self.capacity, dtype=np.int64)
+        self.turn = np.zeros(self.capacity, dtype=np.int32)
+        self.is_open = np.zeros(self.capacity, dtype=bool)
+        self.free = list(range(self.capacity - 1, -1, -1))      # (slot 0 first)
+
+    def open(self):
+        if not self.free:
+            raise _lib.RalError(f"{self.name}.open: all {self.capacity} slots hold an open stream")
+        sid = self.free.pop()
+        self.n[sid], self.is_open[sid] = 0, True
+        return sid
+
+    def plan(self, shapes, close=()):
+        """shapes {sid: shape of its chunk}, close: the sids that end with this call -> (sids in row order, table, table of the
+        kept last windows to emit); raises RalError for a bad argument"""
+        name = self.name
+        sids = list(shapes)
+        closing = []
+        for sid in close:
+            if sid not in shapes and sid not in closing:
+                closing.append(sid)
+        sids += closing
+        if not sids:
+            raise _lib.RalError(f"{name}.push: nothing to do (no chunk and no stream to close)")
+        for sid in sids:
+            if not isinstance(sid, (int, np.integer)) or isinstance(sid, bool) or not 0 <= sid < self.capacity \
+                    or not self.is_open[sid]:
+                raise _lib.RalError(f"{name}.push: {sid!r} is not an open stream")
+        lens = np.zeros(len(sids), dtype=np.int64)
+        for r, (sid, shape) in enumerate(shapes.items()):
+            if len(shape) != 2 or shape[0] != self.leads:
+                raise _lib.RalError(f"{name}.push: stream {sid}: expected a chunk of shape ({self.leads}, samples), got "
+                                    f"{tuple(shape)}")
+            lens[r] = shape[1]
+        slot = np.asarray(sids, dtype=np.int64)
+        ends = np.zeros(len(sids), dtype=bool)
+        ends[np.isin(slot, np.asarray(list(close), dtype=np.int64))] = True
+        if np.any((lens == 0) & ~ends):
+            sid = sids[int(np.argmax((lens == 0) & ~ends))]
+            raise _lib.RalError(f"{name}.push: stream {sid}: an empty chunk (only a closing stream may come without samples)")
+        if np.any(lens > 0x3fffffff):
+            raise _lib.RalError(f"{name}.push: a chunk of more than 2^30 - 1 samples")
+        n0 = self.n[slot]
+        short = ends & (n0 + lens < self.L)
+        if np.any(short):
+            r = int(np.argmax(short))
+            raise _lib.RalError(f"{name}.push: stream {sids[r]} would end shorter than one window ({int(n0[r] + lens[r])} < "
+                                f"{self.L} samples)")
+        k0, nw, lo, m, T = pool_plan(n0, lens, ends, self.L, self.hop)
+        tab = np.zeros(len(sids), dtype=_lib.POOL_ROW)
+        tab["n0"], tab["T"], tab["k0"], tab["lo"], tab["slot"], tab["c"], tab["nw"], tab["m"] = n0, T, k0, lo, slot, lens, nw, m
+        tab["x_off"], tab["out_off"], tab["w_off"] = np.cumsum(lens) - lens, np.cumsum(m) - m, np.cumsum(nw) - nw
+        tab["turn"], tab["flags"] = self.turn[slot], np.where(ends, 0, _lib.POOL_KEEP)
+        # a closing stream without a further window: its last regular window so far turns out to be its last one and keeps
+        # [lo, T) (with further windows that one stays regular and has given everything it keeps)
+        last = tab[ends & (n0 >= self.L) & (nw == 0) & (T > lo)].copy()
+        last["k0"] -= 1
+        last["nw"], last["w_off"] = 1, np.arange(len(last))
+        return sids, tab, last
+
+    def commit(self, tab):
+        slot, keep = tab["slot"], (tab["flags"] & _lib.POOL_KEEP) != 0
+        self.n[slot] = tab["n0"] + tab["c"]
+        self.turn[slot[keep]] ^= 1
+        for sid in slot[~keep]:
+            self.is_open[sid] = False
+            self.free.append(int(sid))
+
+
+class _PoolBase:
+    """What the stream pools share: the slots and their state (`PoolState`), the packing of a call's chunks, the batches of at
+    most max_batch windows, the packed result.  A subclass supplies the model check, `_gather` and `_emit`."""
+
+    def _setup(self, model, eng, leads, inner_leads, capacity, overlap, grid):
+        self.model, self.eng, self.leads = model, eng, leads
+        self.state = PoolState(capacity, leads, eng.L, overlap, type(self).__name__, grid)
+        self.capacity, self.L, self.hop, self.overlap = self.state.capacity, eng.L, self.state.hop, overlap
+        dev = eng.device
+        z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
+        self.hist = z(2, self.capacity, leads, self.L)        # a slot reads plane turn[slot] and writes the other
+        self.last_y, self.last_stats = z(self.capacity, inner_leads, self.L), z(self.capacity, leads, 2)
+        self.inner_leads = inner_leads
+        self.win = self.y = self.stats = None                  # one batch of windows, the call's statistics: grown on demand
+        self.windows_run = 0                                   # windows the pool has run so far
+        model.eval()
+
+    open_streams = property(lambda self: tuple(int(s) for s in np.flatnonzero(self.state.is_open)))
+
+    def open(self):
+        """-> the sid of a new stream (a free slot); RalError when `capacity` streams are open"""
+        return self.state.open()
+
+    def samples_in(self, sid):
+        if not (isinstance(sid, (int, np.integer)) and 0 <= sid < self.capacity and self.state.is_open[sid]):
+            raise _lib.RalError(f"{type(self).__name__}.samples_in: {sid!r} is not an open stream")
+        return int(self.state.n[sid])
+
+    def _ready(self, what):
+        """raise if the model cannot run a call now"""
+
+    def close(self, sid, x=None):
+        """end one stream, with an optional last chunk -> the rest of it, (leads, T - F(n))"""
+        return self.push({} if x is None else {sid: x}, close=(sid,))[sid]
+
+    @torch.no_grad()
+    def push(self, chunks, close=()):
+        """chunks {sid: (leads, c) samples, host or device}, close: the sids that end with this call (with or without a chunk) ->
+        {sid: the samples that became final, (leads, m) on the device} for every sid named.  Every argument is checked before any
+        device work; a call that raises has changed nothing."""
+        self._ready("push")
+        dev = self.eng.device
+        xs = {sid: x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, dtype=np.float32))
+              for sid, x in chunks.items()}
+        sids, tab, last = self.state.plan({sid: tuple(x.shape) for sid, x in xs.items()}, tuple(close))
+        lib, leads, R = _lib.lib(), self.leads, len(tab)
+        x_total, out_total = int(tab["c"].sum()), int(tab["m"].sum())
+        total = int(tab["w_off"][-1] + tab["nw"][-1])
+        # the chunks, packed: row r's (leads, c) at x_off * leads
+        xp = torch.empty(max(x_total, 1) * leads, dtype=torch.float32, device=dev)
+        flat = [x.reshape(-1) for x in xs.values() if x.numel()]
+        if flat:
+            if all(not f.is_cuda for f in flat) or all(f.is_cuda and f.dtype == torch.float32 for f in flat):
+                xp[:x_total * leads].copy_(flat[0] if len(flat) == 1 else torch.cat(flat), non_blocking=True)
+            else:
+                o = 0
+                for f in flat:
+                    xp[o:o + f.numel()].copy_(f, non_blocking=True)
+                    o += f.numel()
+        out = torch.empty(max(out_total, 1) * leads, dtype=torch.float32, device=dev)
+        batch = min(self.eng.max_batch, max(total, 1))
+        if self.win is None or self.win.shape[0] < batch:
+            self.win = torch.zeros(batch, self.inner_leads, self.L, dtype=torch.float32, device=dev)
+            self.y = torch.zeros_like(self.win)
+        if self.stats is None or self.stats.numel() < total * leads * 2:
+            self.stats = torch.zeros(max(total, 1) * leads * 2, dtype=torch.float32, device=dev)
+        tab_dev = torch.empty(R * tab.itemsize, dtype=torch.uint8, device=dev)
+        geom = (self.capacity, leads, self.L, self.hop)
+        keep_any, first = bool((tab["flags"] & _lib.POOL_KEEP).any()), True
+        for w0 in range(0, max(total, 1), self.win.shape[0]):
+            nb = min(self.win.shape[0], total - w0)
+            write_hist = first and keep_any          # the call's first gather also writes the next histories
+            if nb == 0 and not write_hist:
+                break
+            self._gather(lib, xp, x_total, tab, tab_dev, first, geom, write_hist, w0, nb)
+            first = False
+            if nb == 0:
+                break
+            _lib.check(lib.ral_forward(self.eng.h, _ptr(self.win), _ptr(self.y), nb, 0, _stream()))
+            self._emit(lib, self.y, self.stats, tab, tab_dev, False, geom, w0, nb, False, out, out_total, True)
+        if len(last):
+            last_dev = torch.empty(len(last) * last.itemsize, dtype=torch.uint8, device=dev)
+            self._emit(lib, self.last_y, self.last_stats, last, last_dev, True, geom, 0, len(last), True, out, out_total, False)
+        self.state.commit(tab)
+        self.windows_run += total
+        parts = out[:out_total * leads].split([int(v) * leads for v in tab["m"]])
+        return {sid: p.view(leads, -1) for sid, p in zip(sids, parts)}
+
+
+class LivePool(_PoolBase):
+    """A pool of up to `capacity` independent live streams: each is opened and closed on its own and gets chunks of any length,
+    whenever they come.  `open()` returns a stream id; `push(chunks, close=())` takes {sid: (leads, c)} for any subset of the
+    open streams, ends the streams listed in `close`, and returns {sid: (leads, m)} on the device, the samples of each named
+    stream that became final: after n samples a stream has been given exactly [0, live_frontier(n, L, hop)), and closing it
+    returns the rest.  Concatenated per stream from `open` to `close`, the results equal
+    `StreamingDenoiser(model, overlap=overlap).denoise(record)` on the complete record bit for bit, whatever the chunking, the
+    other streams of the pool, the slot and the batching.  `close(sid, x=None)` ends one stream.
+
+    Per call the host plans one table row per named stream (`pool_plan`), `ral_pool_windows` gathers every window that became
+    complete from the slots' last L samples and the packed chunks (its first launch also writes the next history of the rows
+    that stay open, into the slot's other buffer), the model runs them in batches of at most max_batch windows in eval mode,
+    and `ral_pool_emit` writes the samples they keep into one packed result.  No hipGraph: the geometry differs from call to
+    call, so every call runs the ordinary eval forward and weight changes take effect at once.  Accepts the 1- and 2-lead
+    models of `LiveDenoiser` (RALENet, UNet, ACDAE, DANet); puts the model in eval mode.  A `NewRALE` runs through
+    `NewRALELivePool`."""
+
+    def __init__(self, model, capacity, overlap=0):
+        if isinstance(model, NewRALE):
+            raise _lib.RalError("LivePool does not take a NewRALE: pools of 12-lead streams run through NewRALELivePool")
+        self._setup(model, model.eng, model.eng.leads, model.eng.leads, capacity, overlap, (64, 2048))
+
+    def _gather(self, lib, xp, x_total, tab, tab_dev, upload, geom, write_hist, w0, nb):
+        cap, leads, L, hop = geom
+        _lib.check(lib.ral_pool_windows(_ptr(self.hist), _ptr(xp), x_total, tab.ctypes.data, len(tab), _ptr(tab_dev), int(upload),
+                                        cap, leads, L, hop, int(write_hist), w0, nb, _ptr(self.win), _ptr(self.stats), _stream()))
+
+    def _emit(self, lib, y, stats, tab, tab_dev, upload, geom, w0, nb, from_last, out, out_total, keep):
+        cap, leads, L, hop = geom
+        _lib.check(lib.ral_pool_emit(_ptr(y), _ptr(stats), tab.ctypes.data, len(tab), _ptr(tab_dev), int(upload), cap, leads, L,
+                                     hop, w0, nb, int(from_last), _ptr(out), out_total, _ptr(self.last_y if keep else None),
+                                     _ptr(self.last_stats if keep else None), _stream()))
+
+
+class NewRALELivePool(_PoolBase):
+    """`LivePool` for a 12-lead `NewRALE`: the same surface and contract with chunks of shape (12, c).  Per batch
+    `ral_newrale_pool_front` gathers the windows, z-scores every lead and applies conv1 and conv2, the inner model runs its
+    eval-mode forward, and `ral_newrale_pool_back` applies conv3 and conv4, de-normalises and writes the kept samples; the kept
+    last window of a slot is the inner output.  `push` and `close` refuse a model in training mode; the constructor puts the
+    model in eval mode."""
+
+    def __init__(self, model, capacity, overlap=0):
+        if not isinstance(model, NewRALE):
+            raise _lib.RalError(f"NewRALELivePool takes a NewRALE (got {type(model).__name__}; LivePool takes the 1- and 2-lead "
+                                "models)")
+        self._setup(model, model.rale.eng, 12, 2, capacity, overlap, (16, 1024))
+
+    def _ready(self, what):
+        if self.model.training:
+            raise _lib.RalError(f"NewRALELivePool.{what} runs the eval-mode forward: call model.eval() first")
+
+    def _gather(self, lib, xp, x_total, tab, tab_dev, upload, geom, write_hist, w0, nb):
+        cap, _, L, hop = geom
+        _lib.check(lib.ral_newrale_pool_front(_ptr(self.hist), _ptr(xp), x_total, tab.ctypes.data, len(tab), _ptr(tab_dev),
+                                              int(upload), cap, L, hop, int(write_hist), w0, nb, _ptr(self.model.params),
+                                              _ptr(self.win), _ptr(self.stats), _stream()))
+
+    def _emit(self, lib, y, stats, tab, tab_dev, upload, geom, w0, nb, from_last, out, out_total, keep):
+        cap, _, L, hop = geom
+        _lib.check(lib.ral_newrale_pool_back(_ptr(y), _ptr(stats), _ptr(self.model.params), tab.ctypes.data, len(tab),
+                                             _ptr(tab_dev), int(upload), cap, L, hop, w0, nb, int(from_last), _ptr(out), out_total,
+                                             _ptr(self.last_y if keep else None), _ptr(self.last_stats if keep else None),
+                                             _stream()))
