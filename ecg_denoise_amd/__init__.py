@@ -32,3 +32,4 @@ def hw_queues_set_too_late():
 
 from .model import ACDAE, DANet, NewRALE, RALENet, UNet, ralenet  # noqa: F401
 from .infer import LiveDenoiser, LivePool, NewRALELiveDenoiser, NewRALELivePool  # noqa: F401
+from .evaluate import RecordScores, mix_records, score_records  # noqa: F401

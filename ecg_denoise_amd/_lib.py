@@ -110,6 +110,10 @@ _SIGS = {
                                          C.c_int64, C.c_int, _VP, _VP, _VP, _VP]),
     "ral_newrale_pool_back": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, _VP, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64,
                                         C.c_int, C.c_int, _VP, C.c_int64, _VP, _VP, _VP]),
+    "ral_mix_records_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int, C.c_int64]),
+    "ral_mix_records": (C.c_int, [_VP, _VP, C.c_int64, C.c_int, C.c_int64, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "ral_score_records_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int, C.c_int64, C.c_int64]),
+    "ral_score_records": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int, C.c_int64, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP]),
     "ral_attention_forward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
     "ral_attention_backward_scratch_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "ral_attention_backward": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, C.c_int, C.c_int, C.c_int,

@@ -1631,6 +1631,49 @@ int ral_newrale_pool_back(const float* inner_y, const float* stats, const float*
   return 0;
 }
 
+int64_t ral_mix_records_scratch_bytes(int64_t R, int leads, int64_t T) {
+  const long long n = mix_records_scratch_bytes((long long)R, leads, (long long)T);
+  if (n < 0) return fail("mix_records_scratch_bytes: need R >= 1, 1 <= leads <= 16, T >= 1 (R=%lld leads=%d T=%lld)", (long long)R, leads, (long long)T);
+  return n;
+}
+
+int ral_mix_records(const float* rec, const float* noise, int64_t R, int leads, int64_t T, int64_t Tn, const int64_t* offsets,
+                    const double* snr_db, void* scratch, float* noisy, float* clean, ral_stream s) {
+  if (!rec || !noise || !offsets || !snr_db || !scratch || !noisy || !clean) return fail("mix_records: need no null pointer");
+  const char* why = nullptr;
+  long long bad = -1;
+  const int rc = launch_mix_records(rec, noise, (long long)R, leads, (long long)T, (long long)Tn, offsets, snr_db, scratch, noisy,
+                                    clean, (hipStream_t)s, &why, &bad);
+  if (rc == -1) {
+    char at[96] = "";
+    if (bad >= 0) snprintf(at, sizeof(at), " in record %lld (offset=%lld snr_db=%g)", bad, (long long)offsets[bad], snr_db[bad]);
+    return fail("mix_records: need %s%s (R=%lld leads=%d T=%lld Tn=%lld)", why, at, (long long)R, leads, (long long)T, (long long)Tn);
+  }
+  if (rc) return fail("mix_records: copying offsets / snr_db to the device failed");
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int64_t ral_score_records_scratch_bytes(int64_t R, int leads, int64_t T, int64_t W) {
+  const long long n = score_records_scratch_bytes((long long)R, leads, (long long)T, (long long)W);
+  if (n < 0)
+    return fail("score_records_scratch_bytes: need R >= 1, 1 <= leads <= 16, T >= 1, 1 <= W <= T (R=%lld leads=%d T=%lld W=%lld)",
+                (long long)R, leads, (long long)T, (long long)W);
+  return n;
+}
+
+int ral_score_records(const float* clean, const float* out, const float* noisy, int64_t R, int leads, int64_t T, int64_t W,
+                      void* scratch, double* per_lead, double* per_record, double* per_window, double* window_mean, ral_stream s) {
+  if (!clean || !out || !scratch || !per_lead || !per_record || !per_window || !window_mean)
+    return fail("score_records: need no null pointer (only noisy may be null)");
+  const char* why = nullptr;
+  if (launch_score_records(clean, out, noisy, (long long)R, leads, (long long)T, (long long)W, scratch, per_lead, per_record,
+                           per_window, window_mean, (hipStream_t)s, &why))
+    return fail("score_records: need %s (R=%lld leads=%d T=%lld W=%lld)", why, (long long)R, leads, (long long)T, (long long)W);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 int ral_wavelet_denoise(const float* x, float* y, int64_t rows, int L, float threshold, ral_stream s) {
   if (!x || !y) return fail("wavelet_denoise: null pointer");
   if (!(threshold >= 0.f)) return fail("wavelet_denoise: the threshold factor must be non-negative (got %g)", (double)threshold);

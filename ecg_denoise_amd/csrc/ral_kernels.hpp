@@ -113,6 +113,17 @@ int launch_newrale_pool_back(const float* iy, const float* stats, const float* p
                              ral_pool_row* tab_dev, int upload, long long cap, int L, int hop, long long w0, int nb, int from_last,
                              float* out, long long out_total, float* last_y, float* last_stats, hipStream_t s, const char** why,
                              int* bad);
+// noise-stress evaluation of record groups (ral_eval.hip; ral_mix_records / ral_score_records): the arguments are checked, then
+// (mix) the host arrays copied into the scratch on s, then the kernels launched; -1: bad arguments (*why: the rule that is
+// broken, *bad: the record that breaks it or -1), -2: the copy failed.  *_scratch_bytes: -1 for a shape the call would refuse
+long long mix_records_scratch_bytes(long long R, int leads, long long T);
+int launch_mix_records(const float* rec, const float* noise, long long R, int leads, long long T, long long Tn,
+                       const int64_t* offsets, const double* snr_db, void* scratch, float* noisy, float* clean, hipStream_t s,
+                       const char** why, long long* bad);
+long long score_records_scratch_bytes(long long R, int leads, long long T, long long W);
+int launch_score_records(const float* clean, const float* out, const float* noisy, long long R, int leads, long long T, long long W,
+                         void* scratch, double* per_lead, double* per_record, double* per_window, double* window_mean,
+                         hipStream_t s, const char** why);
 int launch_conv13_fwd(const float* x, const float* w, const float* b, float* y, int B, int cin, int cout, int L,
                       int lrelu, hipStream_t s);
 int launch_conv13_bwd(const float* x, const float* y, const float* dy, const float* w, float* gw, float* gb,

@@ -176,6 +176,19 @@ class StreamingDenoiser:
         out = p["out"][0] if single else p["out"]
         return out.clone() if copy else out
 
+    def evaluate(self, records, noise, snr_db, offsets=None, rng=None, window=None):
+        """Noise-stress evaluation of a record group on the device: clean `records` (R, leads, T) and one noise record
+        `noise` (leads, Tn), device tensors -> `evaluate.RecordScores`.  `mix_records` z-scores every record and adds its noise
+        segment at `snr_db` dB (a scalar or one value per record: a whole intensity sweep in one call), the noisy records are
+        streamed through `denoise`, and `score_records` gives SNR in / out and RMSE in / out per lead, per record, per tile of
+        `window` samples (default L) and as tile means.  The plans and graphs of `denoise` are used as they are."""
+        from .evaluate import mix_records, score_records
+        if not torch.is_tensor(records) or records.dim() != 3 or records.shape[1] != self.leads:
+            raise _lib.RalError(f"evaluate: expected a device tensor of records of shape (R, {self.leads}, T)")
+        noisy, clean = mix_records(records, noise, snr_db, offsets, rng)
+        out = self.denoise(noisy, copy=False)
+        return score_records(clean, out, noisy, self.L if window is None else window)
+
 
 def live_frontier(n, L, hop):
     """F(n): after n samples of a stream, samples [0, F(n)) are final for every length T >= n the stream may end at.  Each is

@@ -75,6 +75,25 @@ def noise(rng, kind, shape):
     raise ValueError(kind)
 
 
+def make_records(R, leads, T, seed=2023, block=4096):
+    """-> R synthetic clean records, float32 (R, leads, T), of any length T >= 1 (amplitudes in mV, not z-scored).  A record up
+    to `block` samples is one `_beats` strip; a longer one is a sequence of independent strips of `block` samples (each with its
+    own heart rate; the rhythm restarts at a strip boundary), so the cost grows with T and not with T^2."""
+    rng = np.random.default_rng(seed)
+    nb = -(-int(T) // block)
+    if nb <= 1:
+        x = _beats(rng, R, int(T), leads)
+    else:
+        x = _beats(rng, R * nb, block, leads).reshape(R, nb, leads, block).transpose(0, 2, 1, 3).reshape(R, leads, nb * block)
+    return np.ascontiguousarray(x[..., :T], dtype=np.float32)
+
+
+def make_noise_record(kind, leads, Tn, seed=2023):
+    """-> one synthetic noise record, float32 (leads, Tn), of kind bw / ma / em / emb (`noise`): the stand-in for an NSTDB
+    record that `mix_records` cuts its segments from."""
+    return np.ascontiguousarray(noise(np.random.default_rng(seed), kind, (1, leads, int(Tn)))[0], dtype=np.float32)
+
+
 def make_dataset(n=10000, leads=2, L=256, noise_name="emb", snr_db=0.0, seed=2023):
     """-> (noisy, clean) float32 arrays of shape (n, leads, L); the on-disk counterpart is
     data/dict_data/{m4,m2,0,p2,p4}/{bw,ma,em,emb}.npy + data/dict_data/ecg.npy (data_utils.py:92-117)."""

@@ -1,0 +1,179 @@
+"""Noise-stress evaluation of streamed denoising on synthetic records: the reference's experiment grid (run.sh: models x
+{bw, ma, em, emb} x {-4, -2, 0, 2, 4 dB}, one `snr:..., rmse:...` line each) on long records through `StreamingDenoiser`.
+
+For every noise kind ONE `StreamingDenoiser.evaluate` call covers the whole intensity sweep: the records of the group are split
+over the five intensities through per-record SNRs (`--records` per intensity, so 5 x `--records` records of `--T` samples per
+call).  Per (kind, intensity) the tool prints the reference-format line (`RecordScores.output_line`) of the model and of the
+classical baseline - `wavelet_denoise` on the same noisy records, cut into rows of `--wavelet-L` samples, scored through
+`score_records` with the same tile length - and at the end one JSON object: per cell SNR in / out / improvement and RMSE (mean
+over the tiles of L samples, the reference's protocol, and over whole records), for both.
+
+The JSON also carries device-event timings (`--time-shapes`, default "64x2x650000,16x12x650000": records x leads x samples; 2 leads
+run `--model`, 12 leads a NewRALE around RALENet("full", L = 256)): after a warm-up call of the same shape, `mix`, `denoise` and
+`score` on their own, and `evaluate` against `denoise` alone on the same noisy records, the two alternating in one process
+(`--reps` pairs, medians).  `overhead_share` = (evaluate - denoise) / evaluate; GB/s are algorithmic (bytes from the shapes: mix
+24 B, score 12 B per sample and lead).  Without `--ckpt` the model has its seeded initial weights: the timings and the plumbing
+are meaningful, the dB are not those of a trained model.  Needs a HIP device: there is no fallback.
+
+    python tools/stress_eval.py [--model full|nra|mlp|unet|acdae|danet|newrale] [--ckpt state_dict.pth] [--L 512]
+                                [--records 4] [--T 65000] [--overlap 0] [--batch 4096] [--time-shapes ...] [--reps 5]
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from ecg_denoise_amd import ACDAE, DANet, NewRALE, RALENet, UNet, mix_records, score_records, synth, wavelet_denoise  # noqa: E402
+from ecg_denoise_amd.data import NOISE_TYPES, TRUE_NOISE  # noqa: E402
+from ecg_denoise_amd.infer import StreamingDenoiser  # noqa: E402
+
+DEV = "cuda:0"
+
+
+def make_model(name, L, batch, ckpt=None):
+    kw = dict(L=L, max_batch=batch, train=False, device=DEV)
+    if name in ("full", "nra", "mlp"):
+        m = RALENet(name, leads=2, seed=777, **kw)
+    elif name == "unet":
+        m = UNet(leads=2, seed=777, **kw)
+    elif name == "acdae":
+        m = ACDAE(seed=777, **kw)
+    elif name == "danet":
+        m = DANet(seed=777, **kw)
+    elif name == "newrale":
+        m = NewRALE(RALENet("full", leads=2, seed=777, **kw), seed=778)
+    else:
+        raise SystemExit(f"stress_eval: unknown model {name}")
+    if ckpt:
+        m.load_state_dict(torch.load(ckpt, map_location="cpu"))
+    return m.eval()
+
+
+def _records(R, leads, T, seed, distinct=4):
+    """R records on the device; at most `distinct` different ones are synthesised, the others repeat them (the timing legs
+    need the shape, not the variety)"""
+    base = torch.tensor(synth.make_records(min(R, distinct), leads, T, seed=seed), device=DEV)
+    return base.repeat(-(-R // base.shape[0]), 1, 1)[:R].contiguous()
+
+
+def _row(sc):
+    """all-tiles means (reference protocol) and the mean of the per-record values, as plain floats"""
+    s = sc.summary()
+    rec = sc.per_record.mean(0).tolist()
+    s.update(record_snr_in_db=rec[0], record_snr_out_db=rec[1], record_rmse_out=rec[3])
+    return s
+
+
+def _subset(sc, idx, window):
+    """the scores of the records idx of a group as a RecordScores of their own (the all-tiles row formed again)"""
+    from ecg_denoise_amd.evaluate import RecordScores
+    pw = sc.per_window[idx]
+    wm = torch.cat([sc.window_mean[idx], pw.reshape(-1, 4).mean(0, keepdim=True)])
+    return RecordScores(sc.per_lead[idx], sc.per_record[idx], pw, wm, window)
+
+
+def grid(args, model, name):
+    sd = StreamingDenoiser(model, batch=args.batch, overlap=args.overlap, use_graph=True)
+    leads, n_int = sd.leads, len(TRUE_NOISE)
+    R = args.records * n_int
+    rec = _records(R, leads, args.T, seed=2023, distinct=R)
+    snrs = [float(TRUE_NOISE[r // args.records]) for r in range(R)]
+    Lw = args.wavelet_L
+    cells, lines = [], []
+    import random
+    for kind in NOISE_TYPES:
+        noise = torch.tensor(synth.make_noise_record(kind, leads, args.T + 4096, seed=7), device=DEV)
+        rng = random.Random(2023)
+        offsets = [rng.randint(0, 4096 - 1) for _ in range(R)]
+        sc = sd.evaluate(rec, noise, snrs, offsets=offsets)
+        noisy, clean = mix_records(rec, noise, snrs, offsets=offsets)
+        nrow = args.T // Lw * Lw                      # the baseline takes rows of an even length <= 8192
+        wav = wavelet_denoise(noisy[..., :nrow].reshape(R, leads, nrow // Lw, Lw).reshape(-1, Lw)).reshape(R, leads, nrow)
+        sw = score_records(clean[..., :nrow].contiguous(), wav, noisy[..., :nrow].contiguous(), window=sd.L)
+        for i, snr in enumerate(TRUE_NOISE):
+            idx = torch.arange(i * args.records, (i + 1) * args.records, device=DEV)
+            a, b = _subset(sc, idx, sd.L), _subset(sw, idx, sd.L)
+            lines.append(a.output_line(name, 0, kind, snr))
+            lines.append(b.output_line("wavelet", 0, kind, snr))
+            cells.append({"noise": kind, "intensity": snr, "model": _row(a), "wavelet": _row(b)})
+    return cells, lines
+
+
+def _median_ms(fn, reps):
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b))
+    return float(np.median(ts)), ts
+
+
+def timing(args, R, leads, T, model, name):
+    sd = StreamingDenoiser(model, batch=args.batch, overlap=args.overlap, use_graph=True)
+    rec = _records(R, leads, T, seed=5, distinct=1 if leads > 2 else 4)
+    noise = torch.tensor(synth.make_noise_record("ma", leads, T + 4096, seed=9), device=DEV)
+    snrs = [float(TRUE_NOISE[r % len(TRUE_NOISE)]) for r in range(R)]
+    offsets = [(r * 997) % 4096 for r in range(R)]
+    noisy, clean = mix_records(rec, noise, snrs, offsets=offsets)
+    out = sd.denoise(noisy)                                   # warm-up: plan + graph of this shape
+    score_records(clean, out, noisy, window=sd.L)
+    sd.evaluate(rec, noise, snrs, offsets=offsets)
+    torch.cuda.synchronize()
+    leg = {"model": name, "records": R, "leads": leads, "T": T, "L": sd.L, "overlap": args.overlap,
+           "windows": R * sd.windows_per_record(T)}
+    leg["mix_ms"], _ = _median_ms(lambda: mix_records(rec, noise, snrs, offsets=offsets), args.reps)
+    leg["score_ms"], _ = _median_ms(lambda: score_records(clean, out, noisy, window=sd.L), args.reps)
+    ev, dn = [], []
+    for _ in range(args.reps):                                # alternating, one process
+        dn.append(_median_ms(lambda: sd.denoise(noisy, copy=False), 1)[0])
+        ev.append(_median_ms(lambda: sd.evaluate(rec, noise, snrs, offsets=offsets), 1)[0])
+    leg["denoise_ms"], leg["evaluate_ms"] = float(np.median(dn)), float(np.median(ev))
+    leg["denoise_ms_all"], leg["evaluate_ms_all"] = dn, ev
+    leg["overhead_share"] = (leg["evaluate_ms"] - leg["denoise_ms"]) / leg["evaluate_ms"]
+    elems = R * leads * T
+    leg["mix_GBps"] = 24 * elems / leg["mix_ms"] / 1e6        # rec + noise read twice, noisy + clean written
+    leg["score_GBps"] = 12 * elems / leg["score_ms"] / 1e6    # clean, out, noisy read once
+    leg["us_per_window"] = {k: 1e3 * leg[k + "_ms"] / leg["windows"] for k in ("mix", "score", "denoise", "evaluate")}
+    return leg
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="full")
+    ap.add_argument("--ckpt", default=None)
+    ap.add_argument("--L", type=int, default=512)
+    ap.add_argument("--records", type=int, default=4, help="records per intensity in the grid")
+    ap.add_argument("--T", type=int, default=65000)
+    ap.add_argument("--overlap", type=int, default=0)
+    ap.add_argument("--batch", type=int, default=4096)
+    ap.add_argument("--wavelet-L", type=int, default=1024)
+    ap.add_argument("--time-shapes", default="64x2x650000,16x12x650000")
+    ap.add_argument("--reps", type=int, default=5)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("stress_eval: needs a HIP device")
+    res = {"tool": "stress_eval", "model": args.model, "ckpt": args.ckpt, "trained": bool(args.ckpt), "L": args.L,
+           "records_per_intensity": args.records, "T": args.T, "overlap": args.overlap, "grid": [], "timing": []}
+    model = make_model(args.model, args.L, args.batch, args.ckpt)
+    res["grid"], lines = grid(args, model, args.model)
+    sys.stdout.write("".join(lines))
+    for shape in [s for s in args.time_shapes.split(",") if s]:
+        R, leads, T = (int(v) for v in shape.split("x"))
+        own = StreamingDenoiser(model).leads == leads
+        m = model if own else make_model("newrale" if leads == 12 else "full", 256 if leads == 12 else args.L, args.batch)
+        res["timing"].append(timing(args, R, leads, T, m, args.model if own else ("newrale" if leads == 12 else "full")))
+        torch.cuda.empty_cache()
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
