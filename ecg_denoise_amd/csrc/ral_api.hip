@@ -37,7 +37,7 @@ extern "C" const char* ral_last_error(void) { return g_err; }
 // exactly two environment variables, both validated: RAL_LANES (1 .. 4 micro-batch chains) and RAL_NO_SIDE_STREAM (0 / 1).
 // A diagnostic build (-DRAL_DIAG) additionally takes RAL_<NAME> from the environment for every switch (tools/diag/*.sh).
 static const char* const KNOB_NAMES[] = {
-  "ATTN_BWD_M", "ATTN_BWD_MH", "ATTN_BWD_W", "ATTN_F16", "ATTN_FWD_H", "ATTN_FWD_W", "DW_SETS", "F16_SPLIT", "FUSE_DW",
+  "ATTN_BWD_M", "ATTN_BWD_MH", "ATTN_BWD_W", "ATTN_F16", "ATTN_FWD_H", "ATTN_FWD_T32", "ATTN_FWD_W", "DW_SETS", "F16_SPLIT", "FUSE_DW",
   "MLP_BWD_W", "MLP_BWD_W_F16", "MLP_FWD_W", "TABRED_SIDE", "UNET_EVAL_GRID", "UNET_FUSED"};
 static std::mutex g_knob_mu;
 static std::map<std::string, long long>& knob_table() { static std::map<std::string, long long> t; return t; }

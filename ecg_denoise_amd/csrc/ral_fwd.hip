@@ -411,6 +411,57 @@ RAL_DEV void put_pair_planes(float* X, int t, float4 x) {
   *reinterpret_cast<fh16x4*>(X + 4 * t) = fh16x4{s0.a, s1.a, s2.a, s3.a};
   *reinterpret_cast<fh16x4*>(X + 4 * t + 2) = fh16x4{s0.b, s1.b, s2.b, s3.b};
 }
+// Staging of one (window, head group) item, shared by k_attn_fwd and k_attn_fwd_t32: q log2 e, k, v as fp32 quads, |q|, the
+// per-head maxima and the table times log2 e into LDS; F16: q and k then split in place into fp16-pair planes.  Ends on a barrier.
+// tid: threadIdx.x
+template <bool F16>
+RAL_DEV void attn_fwd_stage(const float* __restrict__ base, const float* __restrict__ table, float* Qs, float* Ks, float* Vs,
+                            float* Mq, int* Kmax, float* tab, float* Bmax, int* Qmax, int N, int H, int HG, int h0, int Len, int tid) {
+  if (tid < HG) { Kmax[tid] = 0; Qmax[tid] = 0; if (table) Bmax[tid] = 0.f; }
+  __syncthreads();
+  {   // one staging pass with the q, k and v loads of two indices in flight together
+    const float4* gq = reinterpret_cast<const float4*>(base + (size_t)h0 * N * 4);
+    const float4* gk = reinterpret_cast<const float4*>(base + (size_t)(H + h0) * N * 4);
+    const float4* gv = reinterpret_cast<const float4*>(base + (size_t)(2 * H + h0) * N * 4);
+    const int n4 = HG * N, bd = blockDim.x;
+    int i = tid;
+    for (; i + bd < n4; i += 2 * bd) {
+      float4 q0 = gq[i], q1 = gq[i + bd];
+      const float4 k0 = gk[i], k1 = gk[i + bd], v0 = gv[i], v1 = gv[i + bd];
+      q0 = f4scale(q0, RAL_LOG2E); q1 = f4scale(q1, RAL_LOG2E);
+      reinterpret_cast<float4*>(Qs)[i] = q0; reinterpret_cast<float4*>(Qs)[i + bd] = q1;
+      reinterpret_cast<float4*>(Ks)[i] = k0; reinterpret_cast<float4*>(Ks)[i + bd] = k1;
+      if constexpr (F16) { atomicMax(Qmax + i / N, __float_as_int(f4dot(q0, q0))); atomicMax(Qmax + (i + bd) / N, __float_as_int(f4dot(q1, q1))); }
+      reinterpret_cast<float4*>(Vs)[i] = v0; reinterpret_cast<float4*>(Vs)[i + bd] = v1;
+      Mq[i] = sqrtf(f4dot(q0, q0)); Mq[i + bd] = sqrtf(f4dot(q1, q1));
+      atomicMax(Kmax + i / N, __float_as_int(f4dot(k0, k0)));   // non-negative floats order like ints
+      atomicMax(Kmax + (i + bd) / N, __float_as_int(f4dot(k1, k1)));
+    }
+    for (; i < n4; i += bd) {
+      const float4 q0 = f4scale(gq[i], RAL_LOG2E), k0 = gk[i], v0 = gv[i];
+      reinterpret_cast<float4*>(Qs)[i] = q0; reinterpret_cast<float4*>(Ks)[i] = k0; reinterpret_cast<float4*>(Vs)[i] = v0;
+      if constexpr (F16) atomicMax(Qmax + i / N, __float_as_int(f4dot(q0, q0)));
+      Mq[i] = sqrtf(f4dot(q0, q0));
+      atomicMax(Kmax + i / N, __float_as_int(f4dot(k0, k0)));
+    }
+  }
+  if (table)
+    for (int i = tid; i < (2 * Len - 1) * HG; i += blockDim.x) {
+      const float t = table[(i / HG) * H + h0 + (i % HG)] * RAL_LOG2E;
+      tab[i] = t;
+      if (t > 0.f) atomicMax(reinterpret_cast<int*>(Bmax) + i % HG, __float_as_int(t));
+    }
+  __syncthreads();
+  if constexpr (F16) {   // second pass: q and k of a head balanced by one power of two (pair_balance) and split IN PLACE
+    for (int i = tid; i < HG * N; i += blockDim.x) {
+      float cq, ck;
+      pair_balance(sqrtf(__int_as_float(Qmax[i / N])), sqrtf(__int_as_float(Kmax[i / N])), cq, ck);
+      const float4 q = reinterpret_cast<const float4*>(Qs)[i], k = reinterpret_cast<const float4*>(Ks)[i];
+      put_pair_planes(Qs, i, f4scale(q, cq)); put_pair_planes(Ks, i, f4scale(k, ck));
+    }
+    __syncthreads();
+  }
+}
 // RAG: only the first NE of the window's N token slots exist (a window length that is not a multiple of 256 runs on padded
 // slots, ral_api.hip): keys past NE are masked out of the softmax (s = -inf), the R-wave window is centred in the NE tokens;
 // the padding queries are computed like any other (their rows are never used)
@@ -438,50 +489,7 @@ __global__ __launch_bounds__(512, 4) void k_attn_fwd(const float* __restrict__ q
   for (int item = blockIdx.x; item < B * ngrp; item += gridDim.x) {
     const int win = item / ngrp, h0 = (item - win * ngrp) * HG;
     const float* base = qkv + (size_t)win * 3 * H * N * 4;
-    if ((int)threadIdx.x < HG) { Kmax[threadIdx.x] = 0; Qmax[threadIdx.x] = 0; if (table) Bmax[threadIdx.x] = 0.f; }
-    __syncthreads();
-    {   // one staging pass with the q, k and v loads of two indices in flight together
-      const float4* gq = reinterpret_cast<const float4*>(base + (size_t)h0 * N * 4);
-      const float4* gk = reinterpret_cast<const float4*>(base + (size_t)(H + h0) * N * 4);
-      const float4* gv = reinterpret_cast<const float4*>(base + (size_t)(2 * H + h0) * N * 4);
-      const int n4 = HG * N, bd = blockDim.x;
-      int i = threadIdx.x;
-      for (; i + bd < n4; i += 2 * bd) {
-        float4 q0 = gq[i], q1 = gq[i + bd];
-        const float4 k0 = gk[i], k1 = gk[i + bd], v0 = gv[i], v1 = gv[i + bd];
-        q0 = f4scale(q0, RAL_LOG2E); q1 = f4scale(q1, RAL_LOG2E);
-        reinterpret_cast<float4*>(Qs)[i] = q0; reinterpret_cast<float4*>(Qs)[i + bd] = q1;
-        reinterpret_cast<float4*>(Ks)[i] = k0; reinterpret_cast<float4*>(Ks)[i + bd] = k1;
-        if constexpr (F16) { atomicMax(Qmax + i / N, __float_as_int(f4dot(q0, q0))); atomicMax(Qmax + (i + bd) / N, __float_as_int(f4dot(q1, q1))); }
-        reinterpret_cast<float4*>(Vs)[i] = v0; reinterpret_cast<float4*>(Vs)[i + bd] = v1;
-        Mq[i] = sqrtf(f4dot(q0, q0)); Mq[i + bd] = sqrtf(f4dot(q1, q1));
-        atomicMax(Kmax + i / N, __float_as_int(f4dot(k0, k0)));   // non-negative floats order like ints
-        atomicMax(Kmax + (i + bd) / N, __float_as_int(f4dot(k1, k1)));
-      }
-      for (; i < n4; i += bd) {
-        const float4 q0 = f4scale(gq[i], RAL_LOG2E), k0 = gk[i], v0 = gv[i];
-        reinterpret_cast<float4*>(Qs)[i] = q0; reinterpret_cast<float4*>(Ks)[i] = k0; reinterpret_cast<float4*>(Vs)[i] = v0;
-        if constexpr (F16) atomicMax(Qmax + i / N, __float_as_int(f4dot(q0, q0)));
-        Mq[i] = sqrtf(f4dot(q0, q0));
-        atomicMax(Kmax + i / N, __float_as_int(f4dot(k0, k0)));
-      }
-    }
-    if (table)
-      for (int i = threadIdx.x; i < (2 * Len - 1) * HG; i += blockDim.x) {
-        const float t = table[(i / HG) * H + h0 + (i % HG)] * RAL_LOG2E;
-        tab[i] = t;
-        if (t > 0.f) atomicMax(reinterpret_cast<int*>(Bmax) + i % HG, __float_as_int(t));
-      }
-    __syncthreads();
-    if constexpr (F16) {   // second pass: q and k of a head balanced by one power of two (pair_balance) and split IN PLACE
-      for (int i = threadIdx.x; i < HG * N; i += blockDim.x) {
-        float cq, ck;
-        pair_balance(sqrtf(__int_as_float(Qmax[i / N])), sqrtf(__int_as_float(Kmax[i / N])), cq, ck);
-        const float4 q = reinterpret_cast<const float4*>(Qs)[i], k = reinterpret_cast<const float4*>(Ks)[i];
-        put_pair_planes(Qs, i, f4scale(q, cq)); put_pair_planes(Ks, i, f4scale(k, ck));
-      }
-      __syncthreads();
-    }
+    attn_fwd_stage<F16>(base, table, Qs, Ks, Vs, Mq, Kmax, tab, Bmax, Qmax, N, H, HG, h0, Len, threadIdx.x);
     const int qblocks = N / (16 * QT);
     for (int task = wave; task < HG * qblocks; task += nw) {
       const int hl = task / qblocks, q0 = (task - hl * qblocks) * 16 * QT;
@@ -607,6 +615,183 @@ __global__ __launch_bounds__(512, 4) void k_attn_fwd(const float* __restrict__ q
           if (g == 0) {
             const int q = q0 + 16 * qt + r;
             const size_t hq = ((size_t)win * H + h0 + hl) * N + q;
+            *reinterpret_cast<float4*>(o_hm + hq * 4) = f4scale(o, 1.0f / l);
+            if (lse) lse[hq] = (mg + __builtin_amdgcn_logf(l)) * RAL_LN2;
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// =================================================================================
+// K2t: the same attention with the score as 32-key x 32-query blocks, one v_mfma_f32_32x32x16_f16 per block where
+// k_attn_fwd<., ., ., true> issues four 16x16x16 ones: a quarter of the matrix instructions, of the waits for their results
+// and of the A-operand reads per score (profiles/attn_fwd_t32_probe.txt, attn_fwd_t32_levels.txt).  Staging, LDS image and
+// the Cauchy-Schwarz shift are k_attn_fwd's (F16).  Lane l = (r = l & 31, h = l >> 5):
+//   A (key on the row)      plane h of key kt + r, twice: {a, a}            K axis 8h + j = (plane h of k) x
+//   B (query on the column) both planes of query q0 + r (one 16-byte read)               (plane j >> 2 of q), dim j & 3
+// so the K axis carries the four piece pairs of the 16x16 tile's lane groups, term for term (lane map checked with exact
+// integer data: tools/diag/mfma32_map_probe.hip).  The accumulator holds query r and the 16 keys kt + 8i + 4h + j (register
+// 4i + j): a lane owns one query, the softmax state is lane-private, and the two halves of a query (l ^ 32) are added once
+// per task.  QB query blocks of a wave share the A operand and the V rows (QB = 2: half a V row read per score, as k_attn_fwd).
+// The R-wave table enters a biased block through the C operand (-m + bias), so every block is consumed by the same code.
+// Needs N % (32 QB) == 0 and no padded windows (launch_attn_fwd).
+// <2, true> and <2, false>: 128 VGPRs, no scratch, four waves per SIMD; LDS as k_attn_fwd (attn_fwd_lds: 26.7 KB per head at N = 512)
+// =================================================================================
+typedef _Float16 fh16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+template <int QB, bool TAB>
+__global__ __launch_bounds__(512, 4) void k_attn_fwd_t32(const float* __restrict__ qkv, float* __restrict__ o_hm,
+                                                      float* __restrict__ lse, const float* __restrict__ table,
+                                                      int N, int H, int HG, int Len, int B) {
+  extern __shared__ float4 smem4[];
+  if constexpr (!TAB) { table = nullptr; Len = 0; }
+  float* Qs = reinterpret_cast<float*>(smem4);
+  float* Ks = Qs + HG * N * 4;
+  float* Vs = Ks + HG * N * 4;
+  float* Mq = Vs + HG * N * 4;
+  int* Kmax = reinterpret_cast<int*>(Mq + HG * N);
+  float* tab = reinterpret_cast<float*>(Kmax + HG + 4);
+  float* Bmax = tab + (table ? (2 * Len - 1) * HG : 0);
+  int* Qmax = reinterpret_cast<int*>(Bmax + HG);
+  const int ngrp = H / HG;
+  const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;   // (task indices on the scalar side)
+  const int off = (N - Len) >> 1;
+  const int kb0 = table ? (off & ~31) : N, kb1 = table ? ((off + Len + 31) & ~31) : N;  // biased key blocks
+  for (int item = blockIdx.x; item < B * ngrp; item += gridDim.x) {
+    const int win = item / ngrp, h0 = (item - win * ngrp) * HG;
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));   // the staging addresses are recomputed per item, not kept in registers across the task loop
+    attn_fwd_stage<true>(qkv + (size_t)win * 3 * H * N * 4, table, Qs, Ks, Vs, Mq, Kmax, tab, Bmax, Qmax, N, H, HG, h0, Len, tid);
+    const int qblocks = N / (32 * QB);
+    for (int task = wave; task < HG * qblocks; task += nw) {
+      const int hl = task / qblocks, q0 = (task - hl * qblocks) * 32 * QB;
+      const float* Kh = Ks + hl * N * 4;
+      const float4* Vh = reinterpret_cast<const float4*>(Vs + hl * N * 4);
+      const float kmx = sqrtf(__int_as_float(Kmax[hl])) * 1.0000002f;
+      float mq[QB];
+      fh16x8 qh[QB];
+      f32x2 l2[QB], o01[QB], o23[QB];
+      auto a_frag = [&](int kt) -> fh16x4 { return *reinterpret_cast<const fh16x4*>(Kh + 4 * (kt + r) + 2 * h); };
+      auto sc_block = [&](fh16x4 a, int qb, f32x16 c) -> f32x16 {
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(fh16x8{a[0], a[1], a[2], a[3], a[0], a[1], a[2], a[3]}, qh[qb], c, 0, 0, 0);
+      };
+      auto splat16 = [](float v) -> f32x16 { return f32x16{v, v, v, v, v, v, v, v, v, v, v, v, v, v, v, v}; };
+#pragma unroll
+      for (int qb = 0; qb < QB; ++qb) {
+        const int q = q0 + 32 * qb + r;
+        qh[qb] = *reinterpret_cast<const fh16x8*>(Qs + (hl * N + q) * 4);
+        mq[qb] = Mq[hl * N + q] * kmx + (table ? Bmax[hl] : 0.f);
+        l2[qb] = f32x2{0.f, 0.f}; o01[qb] = f32x2{0.f, 0.f}; o23[qb] = f32x2{0.f, 0.f};
+      }
+      // two consecutive keys (accumulator registers e, e + 1) of one query block against their V rows
+      auto pair = [&](int qb, const f32x16& s, int e, const float4 (&v2)[2]) {
+        const f32x2 p = f32x2{__builtin_amdgcn_exp2f(s[e]), __builtin_amdgcn_exp2f(s[e + 1])};
+        l2[qb] += p;
+        o01[qb] = pk_fma(splat2(p[0]), f32x2{v2[0].x, v2[0].y}, o01[qb]);
+        o23[qb] = pk_fma(splat2(p[0]), f32x2{v2[0].z, v2[0].w}, o23[qb]);
+        // (odd key: the high half of p for both lanes through op_sel - the compiler copies it to a low half first)
+        asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "+v"(o01[qb]) : "v"(p), "v"(f32x2{v2[1].x, v2[1].y}));
+        asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "+v"(o23[qb]) : "v"(p), "v"(f32x2{v2[1].z, v2[1].w}));
+      };
+      // One block: the A fragment was requested by the block before, the V rows of a key pair (they serve every query
+      // block) are requested a pair ahead, the first pair before the matrix instructions issue.
+      auto v_pair = [&](int kt, int e, float4 (&v2)[2]) {
+        v2[0] = Vh[kt + 8 * (e >> 2) + 4 * h + (e & 3)]; v2[1] = Vh[kt + 8 * (e >> 2) + 4 * h + (e & 3) + 1];
+      };
+      fh16x4 an = a_frag(0);
+      auto block = [&](int kt, auto biased) {
+        const fh16x4 a = an;
+        float4 va[2], vb[2];
+        v_pair(kt, 0, va);
+        an = a_frag(kt + 32 < N ? kt + 32 : 0);
+        f32x16 s[QB];
+#pragma unroll
+        for (int qb = 0; qb < QB; ++qb) {
+          f32x16 c = splat16(-mq[qb]);
+          if constexpr (decltype(biased)::value) {   // the table entries ride in on the C operand
+            int qi = q0 + 32 * qb + r - off, kb = kt + 4 * h - off;
+            asm volatile("" : "+v"(qi), "+v"(kb));   // (indices computed here, not 32 of them kept across the sweep)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+              const int ki = kb + 8 * (e >> 2) + (e & 3);
+              const bool in = (unsigned)qi < (unsigned)Len && (unsigned)ki < (unsigned)Len;   // (no branch: entry 0 where outside)
+              c[e] += in ? tab[in ? (qi - ki + Len - 1) * HG + hl : 0] : 0.f;
+            }
+          }
+          s[qb] = sc_block(a, qb, c);   // s - m, log2 units
+        }
+#pragma unroll
+        for (int e = 0; e < 16; e += 4) {
+          __builtin_amdgcn_sched_barrier(0);   // (the scheduler would fetch all 16 V rows first: 64 registers)
+          v_pair(kt, e + 2, vb);
+#pragma unroll
+          for (int qb = 0; qb < QB; ++qb) pair(qb, s[qb], e, va);
+          __builtin_amdgcn_sched_barrier(0);
+          if (e + 4 < 16) v_pair(kt, e + 4, va);
+#pragma unroll
+          for (int qb = 0; qb < QB; ++qb) pair(qb, s[qb], e + 2, vb);
+        }
+      };
+      // only query blocks that touch the centred R-wave window take the biased key blocks
+      const bool qbias = table && (q0 < off + Len) && (q0 + 32 * QB > off);
+      const int e0 = qbias ? kb0 : N, e1 = qbias ? kb1 : N;
+      for (int kt = 0; kt < e0; kt += 32) block(kt, std::false_type{});
+      if constexpr (TAB) for (int kt = e0; kt < e1; kt += 32) block(kt, std::true_type{});
+      for (int kt = e1; kt < N; kt += 32) block(kt, std::false_type{});
+      bool redo = false;
+#pragma unroll
+      for (int qb = 0; qb < QB; ++qb) {
+        const float lv = swap32_add(l2[qb][0] + l2[qb][1]);
+        const float4 ov = make_float4(swap32_add(o01[qb][0]), swap32_add(o01[qb][1]), swap32_add(o23[qb][0]), swap32_add(o23[qb][1]));
+        redo = redo || !(lv > 1e-30f);
+        if (h == 0) {
+          const size_t hq = ((size_t)win * H + h0 + hl) * N + q0 + 32 * qb + r;
+          *reinterpret_cast<float4*>(o_hm + hq * 4) = f4scale(ov, 1.0f / lv);
+          if (lse) lse[hq] = (mq[qb] + __builtin_amdgcn_logf(lv)) * RAL_LN2;   // natural-log units
+        }
+      }
+      if (__any(redo)) {   // exact running-max recurrence, a query block at a time (never taken on real data)
+#pragma unroll
+        for (int qb = 0; qb < QB; ++qb) {
+          float mx = -INFINITY, l = 0.f;
+          float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+          for (int kt = 0; kt < N; kt += 32) {
+            f32x16 s = sc_block(a_frag(kt), qb, splat16(0.f));
+            if constexpr (TAB) {
+              int qi = q0 + 32 * qb + r - off, kb = kt + 4 * h - off;
+              asm volatile("" : "+v"(qi), "+v"(kb));
+#pragma unroll
+              for (int e = 0; e < 16; ++e) {
+                const int ki = kb + 8 * (e >> 2) + (e & 3);
+                if (qi >= 0 && qi < Len && ki >= 0 && ki < Len) s[e] += tab[(qi - ki + Len - 1) * HG + hl];
+              }
+            }
+            float mn = mx;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) mn = fmaxf(mn, s[e]);
+            const float corr = __builtin_amdgcn_exp2f(mx - mn);
+            mx = mn;
+            l *= corr; o = f4scale(o, corr);
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+              const float p = __builtin_amdgcn_exp2f(s[e] - mn);
+              const float4 v = Vh[kt + 8 * (e >> 2) + 4 * h + (e & 3)];
+              l += p;
+              o.x = fmaf(p, v.x, o.x); o.y = fmaf(p, v.y, o.y); o.z = fmaf(p, v.z, o.z); o.w = fmaf(p, v.w, o.w);
+            }
+          }
+          const float mg = fmaxf(mx, __shfl_xor(mx, 32));
+          const float sc = __builtin_amdgcn_exp2f(mx - mg);
+          l *= sc; o = f4scale(o, sc);
+          l = swap32_add(l);
+          o = make_float4(swap32_add(o.x), swap32_add(o.y), swap32_add(o.z), swap32_add(o.w));
+          if (h == 0) {
+            const size_t hq = ((size_t)win * H + h0 + hl) * N + q0 + 32 * qb + r;
             *reinterpret_cast<float4*>(o_hm + hq * 4) = f4scale(o, 1.0f / l);
             if (lse) lse[hq] = (mg + __builtin_amdgcn_logf(l)) * RAL_LN2;
           }
@@ -1070,6 +1255,23 @@ void launch_attn_fwd(const float* qkv, float* o_hm, float* lse, const float* tab
   // (RAL_ATTN_FWD_H = smallest such N, 0 = never)
   static const int hlo = (int)ral_knob("ATTN_FWD_H", 256);
   const bool tile16 = f16 && hlo > 0 && N >= hlo && N % 32 == 0;
+  // 32x32 score blocks (k_attn_fwd_t32) from RAL_ATTN_FWD_T32 up (smallest such N, 0 = never).  Measured at batch 2048
+  // (tools/attn_bench.py, us per launch, three interleaved rounds, the kernel the level had before vs k_attn_fwd_t32):
+  // N = 512: 274 / 253, 278 / 252, 277 / 252, 256: 162 / 150, 161 / 151, 165 / 148, 128: 91 / 107, 91 / 106, 91 / 106,
+  // 64: 53 / 80, 54 / 80, 53 / 80 (profiles/attn_fwd_t32_levels.txt): the scalar path keeps N = 128 and 64
+  static const int tlo = (int)ral_knob("ATTN_FWD_T32", 256);
+  if (f16 && tlo > 0 && N >= tlo && N % 64 == 0) {
+    const int hg = HG % ATTN_SPLIT == 0 ? HG / ATTN_SPLIT : HG, thr = hg == HG ? 512 : 512 / ATTN_SPLIT;
+    const size_t l2 = attn_fwd_lds(N, hg, Len);
+    if (table) {
+      RAL_SET_LDS((k_attn_fwd_t32<2, true>), l2);
+      k_attn_fwd_t32<2, true><<<grid_for(B * (H / hg)), thr, l2, s>>>(qkv, o_hm, lse, table, N, H, hg, Len, B);
+    } else {
+      RAL_SET_LDS((k_attn_fwd_t32<2, false>), l2);
+      k_attn_fwd_t32<2, false><<<grid_for(B * (H / hg)), thr, l2, s>>>(qkv, o_hm, lse, table, N, H, hg, Len, B);
+    }
+    return;
+  }
   if (!tile16 && N >= 64 && N <= 256 && N % 4 == 0 && (!table || 2 * Len - 1 <= 64)) {
     const int ntask = B * H * ((N + 63) / 64);
     if (table) k_attn_fwd_v<true><<<(ntask + 3) / 4, 256, 0, s>>>(qkv, o_hm, lse, table, N, H, Len, ntask);

@@ -11,6 +11,7 @@
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 template <int KIND>
 __global__ void k_probe(float* out, long long* cyc, float seed, int iters) {
@@ -21,6 +22,9 @@ __global__ void k_probe(float* out, long long* cyc, float seed, int iters) {
   const float m = 1.0000001f, c = 1e-7f;
   const f32x2 m2 = {m, m}, c2 = {c, c};
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  f32x16 big[4];   // 32x32 accumulators (KIND 27 - 28)
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 16; ++j) big[i][j] = KIND >= 27 && KIND <= 28 ? seed * (float)j : 0.f;
   __syncthreads();
   const long long t0 = __builtin_amdgcn_s_memtime();
   const long long r0 = __builtin_amdgcn_s_memrealtime();
@@ -209,6 +213,34 @@ __global__ void k_probe(float* out, long long* cyc, float seed, int iters) {
         for (int i = 0; i < 8; ++i) asm volatile("v_pk_fma_f32 %0, %1, %2, %0" : "+v"(p[2 + (i & 3)]) : "v"(m2), "v"(c2));
       }
       acc += ac2;
+    } else if (KIND == 27) {   // 16 bare f16 MFMAs 32x32x16 (4 accumulators of 16 registers)
+      typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+      h8 a8;
+      for (int i = 0; i < 8; ++i) a8[i] = (_Float16)a[i];
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %1, %0" : "+v"(big[i]) : "v"(a8));
+    } else if (KIND == 28 || KIND == 29) {   // forward mix of 16 tiles: 28 = one 32x32x16 f16 MFMA per four tiles, 29 = one 16x16x16 f16 MFMA per tile
+      typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+      typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+      h4 a4; h8 a8;
+      for (int i = 0; i < 4; ++i) a4[i] = (_Float16)a[i];
+      for (int i = 0; i < 8; ++i) a8[i] = (_Float16)a[i];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        if (KIND == 28) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %1, %0" : "+v"(big[b & 1]) : "v"(a8));
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          if (KIND == 29) asm volatile("v_mfma_f32_16x16x16_f16 %0, %1, %1, %0" : "+v"(acc) : "v"(a4));
+#pragma unroll
+          for (int i = 0; i < 4; ++i) asm volatile("v_exp_f32 %0, %0" : "+v"(a[4 + i]));
+#pragma unroll
+          for (int i = 0; i < 2; ++i) asm volatile("v_pk_add_f32 %0, %0, %1" : "+v"(p[i]) : "v"(c2));
+#pragma unroll
+          for (int i = 0; i < 8; ++i) asm volatile("v_pk_fma_f32 %0, %1, %2, %0" : "+v"(p[2 + (i & 3)]) : "v"(m2), "v"(c2));
+        }
+      }
     } else if (KIND == 8) {   // 16 bare mfma 16x16x4 f32 (4 accumulators)
       f32x4 ac[4] = {acc, acc, acc, acc};
 #pragma unroll
@@ -223,6 +255,9 @@ __global__ void k_probe(float* out, long long* cyc, float seed, int iters) {
   float s = 0.f;
   for (int i = 0; i < 16; ++i) s += a[i];
   for (int i = 0; i < 8; ++i) s += p[i][0] + p[i][1];
+  if (KIND >= 27 && KIND <= 28)
+    for (int i = 0; i < 4; ++i)
+      for (int j = 0; j < 16; ++j) s += big[i][j];
   out[blockIdx.x * blockDim.x + threadIdx.x] = s + acc[0] + acc[1] + acc[2] + acc[3];
   const long long r1 = __builtin_amdgcn_s_memrealtime();
   if (threadIdx.x == 0) { cyc[blockIdx.x] = t1 - t0; cyc[256 + blockIdx.x] = r1 - r0; }
@@ -268,6 +303,7 @@ int main() {
   run<20>("v_mfma_f32_16x16x32_bf16, asm-forced (per mfma)", 16);
   run<21>("v_mfma_f32_16x16x16_f16 (per mfma)", 16);
   run<22>("v_mfma_f32_16x16x32_f16 (per mfma)", 16);
+  run<27>("v_mfma_f32_32x32x16_f16 (per mfma)", 16);
   run<26>("bwd tile A, no mfma (4exp 4mul 8pkfma)", 4);
   run<23>("bwd tile A + 2 fp32 mfma 16x16x4", 4);
   run<24>("bwd tile A + 2 f16 mfma 16x16x16", 4);
@@ -284,6 +320,8 @@ int main() {
   run<10>("fwd tile packed + 1 bf16 mfma", 4);
   run<11>("fwd tile packed + 2 bf16 mfma", 4);
   run<4>("fwd tile packed (per tile: 4exp 2pkadd 8pkfma 1mfma)", 4);
+  run<29>("fwd tile packed + 1 f16 mfma 16x16x16 (per tile)", 16);
+  run<28>("fwd block 32x32 (per 16x16 tile: 4exp 2pkadd 8pkfma, 1/4 mfma 32x32x16)", 16);
   run<5>("fwd tile scalar (per tile: 4exp 4add 16fma 1mfma)", 4);
   return 0;
 }
