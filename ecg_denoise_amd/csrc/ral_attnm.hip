@@ -16,7 +16,8 @@
 //     is a transposing LDS read, ds_read_b64_tr_b16, of the SAME token-major planes the S / dP tiles read by rows, masked
 //     into its half of K);
 //   * only dS crosses lanes, once: its two pieces go through a 16 x 16 LDS tile of the wave ([key][query] rows of 40 bytes,
-//     written as they stand, read back with the transposing read) and meet k^T in a third K = 32 instruction (dQ^T);
+//     written as they stand, read back with the transposing read) and meet k^T in a third K = 32 instruction per tile
+//     (dQ^T; issued for two key tiles at a time, K = [keys of one tile | keys of the next]: dq_tiles2);
 //   * per tile: 5 matrix instructions (~90 cycles of the matrix pipe) beside 4 exponentials + 14 conversions (~70 issue
 //     cycles): the two pipes are balanced, where the two-sweep form left the matrix pipe idle.
 // Range.  p is evaluated as 2^8 p (the shift sits in the C operand of the S tile, next to -lse) so that probabilities down to
@@ -43,6 +44,7 @@ typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef s16x4 __attribute__((address_space(3))) * lds_s16x4;
+typedef u32x2 __attribute__((address_space(3))) * lds_u32x2;
 
 // fp16 pairs, two elements per register (element 0 in the low half): h1 = fp16(x), h2 = fp16(x - h1).
 // h1 is formed by plain casts (the compiler emits v_cvt_pk_f16_f32 and keeps the wait states a consumer of a transcendental /
@@ -58,6 +60,8 @@ RAL_DEV unsigned pair_lo2(float x0, float y0, float x1, float y1, unsigned h1) {
   asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(h2) : "v"(x1), "v"(y1), "v"(h1));
   return h2;
 }
+// (h1 = fp16(fma(x, y, 0)) - which the compiler turns into v_fma_mixlo/hi_f16 with a zero addend, one rounding, no v_mul_f32 +
+// v_cvt_pk_f16_f32 - is 8 instructions fewer per four tiles and measured 2.5 % SLOWER at N = 512: DESIGN_HISTORY.md)
 RAL_DEV void pair_prod2(float x0, float y0, float x1, float y1, unsigned& h1, unsigned& h2) {
   h1 = pair_hi2(x0 * y0, x1 * y1);
   h2 = pair_lo2(x0, y0, x1, y1, h1);
@@ -128,6 +132,93 @@ RAL_DEV float f4amax(float4 v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fma
 #define RAL_ATTNM_WPE 4
 #endif
 
+// ---- the tile body both kernels share -------------------------------------------------------------------------------
+constexpr int ATTNM_BUF = 160;       // floats of one dS piece tile: 16 key rows of 40 bytes
+
+// 2^8 p of a tile the R-wave table window meets: the bias joins the score in front of the exponential, and p dP of the
+// entries inside the window goes to the table gradient (doubles in the LDS).  ki / qi: this lane's key / first query
+// relative to the window's first token.
+RAL_DEV void tile_exp_table(const f32x4& s, const f32x4& dp, float (&p)[4], const float* tab, double* dtab, int ki, int qi,
+                            int Len, int H, int head, float sc_tab) {
+  const bool kok = (unsigned)ki < (unsigned)Len;
+  const int rel0 = qi - ki + Len - 1;
+  int e[4]; bool in[4]; float b[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    in[j] = kok && (unsigned)(qi + j) < (unsigned)Len;
+    e[j] = min(max(rel0 + j, 0), 2 * Len - 2) * H + head;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) b[j] = tab[e[j]];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) p[j] = __builtin_amdgcn_exp2f(s[j] + (in[j] ? b[j] : 0.f));
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (in[j]) atomicAdd(dtab + e[j], (double)(p[j] * dp[j] * sc_tab));
+}
+RAL_DEV void tile_exp(const f32x4& s, float (&p)[4]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) p[j] = __builtin_amdgcn_exp2f(s[j]);
+}
+// One 16 x 16 score tile, key on the lane: S and dP from the row / column operands, `expo(s, dp, p)` for 2^8 p (tile_exp, or
+// the table path where the window meets the tile), P and dS as fp16 pairs, both pieces against a8 into dV^T / dK^T of the
+// key tile, and the dS pieces into the wave's LDS tile at bw ([key r][queries 4g .. 4g+3]) for the dQ product.
+template <bool SU, typename EXPO>
+RAL_DEV void bwd_tile(u32x2 Aq, u32x2 Ad, u32x2 Bk, u32x2 Bv, f32x4 cl, f32x4 cdl, float su, const u32x4& a8, f32x4& acc,
+                      lds_u32x2 bw, EXPO&& expo) {
+  f32x4 s = mm16(Aq, Bk, cl);                // (cq ck) (S - lse + 8), log2 units   [query 4g+j][key r]
+  const f32x4 dp = mm16(Ad, Bv, cdl);        // (dP - delta) cd cv
+  if constexpr (SU) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s[j] *= su;
+  }
+  float p[4];
+  expo(s, dp, p);
+  unsigned ph1[2], ph2[2], sh1[2], sh2[2];
+  pair_of2(p[0], p[1], ph1[0], ph2[0]); pair_of2(p[2], p[3], ph1[1], ph2[1]);
+  pair_prod2(p[0], dp[0], p[1], dp[1], sh1[0], sh2[0]); pair_prod2(p[2], dp[2], p[3], dp[3], sh1[1], sh2[1]);
+  pair_settle(ph2[0], ph2[1], sh2[0], sh2[1]);
+  acc = mm32(a8, u32x4{ph1[0], ph1[1], sh1[0], sh1[1]}, acc);
+  acc = mm32(a8, u32x4{ph2[0], ph2[1], sh2[0], sh2[1]}, acc);
+  RAL_XB_FENCE();
+  bw[0] = u32x2{sh1[0], sh1[1]};
+  bw[ATTNM_BUF / 2] = u32x2{sh2[0], sh2[1]};
+  RAL_XB_FENCE();
+}
+// this lane's slot of the wave's dS piece tiles as an LDS address in a register of its own (opaque to the compiler, which
+// otherwise rebuilds it from a shared base with a v_add_u32 in front of every write: the offset is beyond ds_write2's reach).
+// OWN = false leaves it to the compiler: the KT = 8 instances of k_attn_bwd_mh have no register to give - with it they
+// reload a spilled operand inside the sweep.
+template <bool OWN = true>
+RAL_DEV lds_u32x2 xb_slot(float* p) {
+  lds_u32x2 a = (lds_u32x2)(p);
+  if constexpr (OWN) asm volatile("" : "+v"(a));
+  return a;
+}
+// dQ^T += k^T planes x dS^T of the key tiles kp, kp + 1 (kp even: their pieces lie in the two parities of the wave's LDS
+// tiles at xb, this lane's row / column already in it).  The K = 32 contraction runs over [keys of tile kp | keys of tile
+// kp + 1], first pieces then second pieces: each k^T read fills its own half of the A operand, where one tile per
+// instruction ([first | second piece] against [k^T | k^T]) needed the half copied with two v_mov_b32 per tile.
+// ka / kb: the transposing-read addresses of the two tiles' k planes (rows 8-15 of the result: v planes, unused).
+RAL_DEV void dq_tiles2(f32x4& dq, const float* xb, const float* ka, const float* kb) {
+  const u32x2 b1a = tr_read(xb), b2a = tr_read(xb + ATTNM_BUF);
+  const u32x2 b1b = tr_read(xb + 2 * ATTNM_BUF), b2b = tr_read(xb + 3 * ATTNM_BUF);
+  const u32x2 xa = tr_read(ka), xc = tr_read(kb);
+  const u32x4 a = {xa[0], xa[1], xc[0], xc[1]};
+  dq = mm32(a, u32x4{b1a[0], b1a[1], b1b[0], b1b[1]}, dq);
+  dq = mm32(a, u32x4{b2a[0], b2a[1], b2b[0], b2b[1]}, dq);
+}
+
+// A operand of the dV^T / dK^T product from the transposing read xt of [dO planes | q planes]: rows 0-7 (lanes r < 8) keep it
+// in the P half of K, rows 8-15 in the dS half, zeros elsewhere.  mlo / mhi: all ones / zero on lanes r < 8 and the reverse
+// (row_masks) - four VOP2 v_and_b32 where a select on the lane condition is four VOP3 v_cndmask_b32.
+RAL_DEV void row_masks(int r, unsigned& mlo, unsigned& mhi) {
+  mlo = r < 8 ? ~0u : 0u; mhi = ~mlo;
+  asm volatile("" : "+v"(mlo), "+v"(mhi));   // (opaque: the compiler would turn x & mask back into the select)
+}
+RAL_DEV u32x4 a8_of(u32x2 xt, unsigned mlo, unsigned mhi) {
+  return u32x4{xt[0] & mlo, xt[1] & mlo, xt[0] & mhi, xt[1] & mhi};
+}
 // One wave per head (two heads at N = 32), N = 32, 64, 128: operands in a private LDS slice, no workgroup barrier in the task loop.  Loop order: query tile outside (dQ^T of the tile in one
 // accumulator), key tiles inside (dV^T / dK^T of every key tile of the head in KT accumulators, statically indexed).
 template <int NT, bool TAB>
@@ -138,7 +229,7 @@ __global__ __launch_bounds__(256, RAL_ATTNM_WPE) void k_attn_bwd_m(const float* 
   constexpr int HW = NT >= 64 ? 1 : 64 / NT;   // heads per task
   constexpr int T = HW * NT, TPL = T / 64;     // tokens per task, tokens per lane
   constexpr int KT = NT / 16;                  // key (query) tiles per head
-  constexpr int BUF = 160;                     // floats of one dS piece tile: 16 key rows of 40 bytes
+  constexpr int BUF = ATTNM_BUF;
   constexpr int PPAD = 32;                     // floats between plane images: the transposing reads take k with v (dO with q) chunks in one
                                                // instruction, and images a multiple of 64 dwords apart would put them on the same banks
   constexpr int WSZ = T * 18 + 4 * PPAD + 4 * BUF;   // floats of LDS per wave
@@ -226,7 +317,8 @@ __global__ __launch_bounds__(256, RAL_ATTNM_WPE) void k_attn_bwd_m(const float* 
   };
   // lane roles of the transposing reads: row tq of the block, column quad tp
   const int tq = r >> 2, tp = r & 3;
-  const bool lowrows = r < 8;
+  unsigned mlo, mhi;
+  row_masks(r, mlo, mhi);
   while (task < ntask) {
     // (the operands of a task are requested and deposited at the top of its trip: requesting the NEXT task's under the
     // current one's tiles - 21 registers held across the sweep - measured 116 against 110 us per launch at N = 64)
@@ -241,9 +333,17 @@ __global__ __launch_bounds__(256, RAL_ATTNM_WPE) void k_attn_bwd_m(const float* 
       f32x4 acc[KT];
 #pragma unroll
       for (int kt = 0; kt < KT; ++kt) acc[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-      for (int qt = 0; qt < KT; ++qt) {
-        const int q0 = qt * 16;
+      // query tiles [qa, qb) are the ones the table window can meet (meets(q0, 16)); the others run the tile body without the
+      // per-tile test, through one loop - the tiles in front of the window, then those behind it - and the window's own come
+      // last (dV^T / dK^T sum over the query tiles in that order)
+      int qa = 0, qb = 0;
+      if constexpr (TAB) {
+        if (off < SH) qb = NT;
+        else { qa = (off - SH) & ~15; qb = min(NT, (off + Len - SH + 15) & ~15); }
+      }
+      const lds_u32x2 bw0 = xb_slot(Xb + r * 10 + 2 * g);
+      // one query tile against every key tile of the head
+      auto qtile = [&](int q0, auto tabbed) {
         const int qr = (q0 + SH + r) & MSK;          // this lane's query as a row of the S tile / a column of dQ^T
         const int q4 = (q0 + SH + 4 * g) & MSK;      // first of the four queries of this lane group
         const u32x2 Aq = *reinterpret_cast<const u32x2*>(Qh + 4 * qr + 2 * (g >> 1));
@@ -253,16 +353,12 @@ __global__ __launch_bounds__(256, RAL_ATTNM_WPE) void k_attn_bwd_m(const float* 
         const f32x4 cl = {l4.x, l4.y, l4.z, l4.w}, cdl = {d4.x, d4.y, d4.z, d4.w};
         // A operand of the dV^T / dK^T product: rows 0-7 = dO planes^T in the P half of K, rows 8-15 = q planes^T in the dS half
         const u32x2 xt = tr_read((tp < 2 ? Dh : Qh) + 4 * (q4 + tq) + 2 * (tp & 1));
-        const u32x4 a8 = lowrows ? u32x4{xt[0], xt[1], 0u, 0u} : u32x4{0u, 0u, xt[0], xt[1]};
-        const bool qin = meets(q0, 16);
+        const u32x4 a8 = a8_of(xt, mlo, mhi);
         f32x4 dq = {0.f, 0.f, 0.f, 0.f};
-        auto dq_step = [&](int kp) {   // dQ^T += k^T planes x dS^T of key tile kp (its pieces were written a tile ago)
-          const float* bp = Xb + (kp & 1) * 2 * BUF + (4 * g + tq) * 10 + 2 * tp;
-          const u32x2 b1 = tr_read(bp), b2 = tr_read(bp + BUF);
-          const int k4 = (kp * 16 + SH + 4 * g) & MSK;
-          const u32x2 kx = tr_read((tp < 2 ? Kh : Vh) + 4 * (k4 + tq) + 2 * (tp & 1));   // (rows 8-15: v planes, results unused)
-          dq = mm32(u32x4{kx[0], kx[1], kx[0], kx[1]}, u32x4{b1[0], b1[1], b2[0], b2[1]}, dq);
+        auto kplane = [&](int kp) -> const float* {   // transposing-read address of the k planes of key tile kp
+          return (tp < 2 ? Kh : Vh) + 4 * (((kp * 16 + SH + 4 * g) & MSK) + tq) + 2 * (tp & 1);
         };
+        const float* xb = Xb + (4 * g + tq) * 10 + 2 * tp;
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt) {
           const int k0 = kt * 16;
@@ -270,53 +366,15 @@ __global__ __launch_bounds__(256, RAL_ATTNM_WPE) void k_attn_bwd_m(const float* 
           // (keeping these operands of all key tiles of a short head in registers measured the same: 111 against 109 us at N = 64)
           const u32x2 Bk = *reinterpret_cast<const u32x2*>(Kh + 4 * kr + 2 * (g & 1));
           const u32x2 Bv = *reinterpret_cast<const u32x2*>(Vh + 4 * kr + 2 * (g & 1));
-          f32x4 s = mm16(Aq, Bk, cl);                // (cq ck) (S - lse + 8), log2 units   [query 4g+j][key r]
-          const f32x4 dp = mm16(Ad, Bv, cdl);        // (dP - delta) cd cv
-          if constexpr (decltype(su_on)::value) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) s[j] *= su;
-          }
-          float p[4];
-          unsigned ph1[2], ph2[2], sh1[2], sh2[2];
-          if (TAB && qin && meets(k0, 16)) {
-            const int ki = kr - off;
-            const bool kok = (unsigned)ki < (unsigned)Len;
-            const int rel0 = (q4 - off) - ki + Len - 1;
-            int e[4]; bool in[4]; float b[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              in[j] = kok && (unsigned)(q4 + j - off) < (unsigned)Len;
-              e[j] = min(max(rel0 + j, 0), 2 * Len - 2) * H + head;
+          auto expo = [&](const f32x4& s, const f32x4& dp, float (&p)[4]) {
+            if constexpr (decltype(tabbed)::value) {
+              if (meets(k0, 16)) { tile_exp_table(s, dp, p, tab, dtab, kr - off, q4 - off, Len, H, head, sc_tab); return; }
             }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) b[j] = tab[e[j]];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) p[j] = __builtin_amdgcn_exp2f(s[j] + (in[j] ? b[j] : 0.f));
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-              if (in[j]) atomicAdd(dtab + e[j], (double)(p[j] * dp[j] * sc_tab));
-          } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) p[j] = __builtin_amdgcn_exp2f(s[j]);
-          }
-          pair_of2(p[0], p[1], ph1[0], ph2[0]); pair_of2(p[2], p[3], ph1[1], ph2[1]);
-          pair_prod2(p[0], dp[0], p[1], dp[1], sh1[0], sh2[0]); pair_prod2(p[2], dp[2], p[3], dp[3], sh1[1], sh2[1]);
-          pair_settle(ph2[0], ph2[1], sh2[0], sh2[1]);
-          acc[kt] = mm32(a8, u32x4{ph1[0], ph1[1], sh1[0], sh1[1]}, acc[kt]);
-          acc[kt] = mm32(a8, u32x4{ph2[0], ph2[1], sh2[0], sh2[1]}, acc[kt]);
-          // dS pieces of the tile, [key r][queries 4g .. 4g+3]
-          float* bw = Xb + (kt & 1) * 2 * BUF + r * 10 + 2 * g;
-          *reinterpret_cast<u32x2*>(bw) = u32x2{sh1[0], sh1[1]};
-          *reinterpret_cast<u32x2*>(bw + BUF) = u32x2{sh2[0], sh2[1]};
-          RAL_XB_FENCE();
-          if (kt > 0) dq_step(kt - 1);
+            tile_exp(s, p);
+          };
+          bwd_tile<decltype(su_on)::value>(Aq, Ad, Bk, Bv, cl, cdl, su, a8, acc[kt], bw0 + (kt & 1) * BUF, expo);
+          if (kt & 1) dq_tiles2(dq, xb, kplane(kt - 1), kplane(kt));
         }
-// (fence + keep-alive below: without them hipcc interleaves the reads of this last step with the last tile and re-uses the
-        // registers of a8 for them; that build returned dV of the last key tile off by 2-16 %, deterministically, although its
-        // instruction stream reads correct and tools/diag/mfma_war_probe*.hip / lds_order_probe.hip find no hazard in the
-        // hardware - unexplained; every shape is checked against fp64 in tests/test_gpu_attention.py)
-        asm volatile("" ::: "memory");
-        dq_step(KT - 1);
         // dQ[query r][d]: rows d (h1 planes of k) + rows 4 + d (h2 planes) of the accumulator = lane groups 0 and 1
         {
           float v[4];
@@ -324,8 +382,18 @@ __global__ __launch_bounds__(256, RAL_ATTNM_WPE) void k_attn_bwd_m(const float* 
           for (int j = 0; j < 4; ++j) v[j] = swap16_add(dq[j]) * sc_dq;
           if (g == 0) *reinterpret_cast<float4*>(dbase + ((size_t)head * NT + qr) * 4) = make_float4(v[0], v[1], v[2], v[3]);
         }
+        // (keep-alive of a8, with the fence in front of every dQ step: without them hipcc interleaves the reads of the last
+        // step with the last tile and re-uses the registers of a8 for them; that build returned dV of the last key tile off by
+        // 2-16 %, deterministically, although its instruction stream reads correct and tools/diag/mfma_war_probe*.hip /
+        // lds_order_probe.hip find no hazard in the hardware - unexplained; every shape is checked against fp64 in
+        // tests/test_gpu_attention.py, every tile in tests/test_gpu_attention_bwd_tiles.py)
         asm volatile("" :: "v"(a8));
-      }
+      };
+      const int nplain = NT - (qb - qa);
+#pragma unroll 1
+      for (int i = 0; i < nplain; i += 16) qtile(i < qa ? i : i + (qb - qa), std::false_type{});
+#pragma unroll 1
+      for (int q0 = qa; q0 < qb; q0 += 16) qtile(q0, std::true_type{});
       // dV (rows 0-7: lane groups 0, 1) and dK (rows 8-15: lane groups 2, 3) of every key tile
 #pragma unroll
       for (int kt = 0; kt < KT; ++kt) {
@@ -363,16 +431,17 @@ __global__ __launch_bounds__(512, 4) void k_attn_bwd_mh(const float* __restrict_
                                                         const float* __restrict__ do_hm, const float* __restrict__ lse,
                                                         const float* __restrict__ table, float* __restrict__ tpart,
                                                         float* __restrict__ dqkv, int N, int H, int HG, int Len_rt, int B) {
-  constexpr int BUF = 160;
+  constexpr int BUF = ATTNM_BUF;
   extern __shared__ float4 smem4[];
   float* sm = reinterpret_cast<float*>(smem4);
-  const int T = HG * N;
+  constexpr int T = 128 * KT;                             // = HG N: eight waves of KT key tiles (attn_bwd_mh_takes)
   constexpr int PPAD = 32;                                // (see k_attn_bwd_m)
+  constexpr int PLANE = 4 * T + PPAD;                        // floats from one plane image to the next
   float* Qp = sm;
-  float* Kp = Qp + 4 * T + PPAD;
-  float* Vp = Kp + 4 * T + PPAD;
-  float* Dp = Vp + 4 * T + PPAD;
-  float* Ls = Dp + 4 * T + PPAD;
+  float* Kp = Qp + PLANE;
+  float* Vp = Kp + PLANE;
+  float* Dp = Vp + PLANE;
+  float* Ls = Dp + PLANE;
   float* Dl = Ls + T;
   // dQ image, (T, 4) DOUBLES in units of 1 / sc_dq: on gfx950 ds_add_f64 takes 8 LDS cycles per wave-instruction, ds_add_f32
   // 192 (three per lane; tools/diag/lds_cost_probe.hip) - with fp32 adds this image was 48 of the 74 LDS cycles of a tile
@@ -393,7 +462,8 @@ __global__ __launch_bounds__(512, 4) void k_attn_bwd_mh(const float* __restrict_
   const int hl = wave / wph, ks = (wave - hl * wph) * KT * 16;   // this wave's head of the group and first key
   const int tb = hl * N;
   const int tq = r >> 2, tp = r & 3;
-  const bool lowrows = r < 8;
+  unsigned mlo, mhi;
+  row_masks(r, mlo, mhi);
   auto meets = [&](int x0, int w) -> bool { return TAB && x0 < off + Len && x0 + w > off; };
   for (int item = blockIdx.x; item < B * ngrp; item += gridDim.x) {
     const int win = item / ngrp, h0 = (item - win * ngrp) * HG;
@@ -483,80 +553,64 @@ __global__ __launch_bounds__(512, 4) void k_attn_bwd_mh(const float* __restrict_
         acc[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
         kin[kt] = meets(k0, 16);
       }
-#pragma unroll 1
-      for (int q0 = 0; q0 < N; q0 += 16) {
-        const int qr = q0 + r, q4 = q0 + 4 * g;
-        const u32x2 Aq = *reinterpret_cast<const u32x2*>(Qh + 4 * qr + 2 * (g >> 1));
-        const u32x2 Ad = *reinterpret_cast<const u32x2*>(Dh + 4 * qr + 2 * (g >> 1));
-        const float4 l4 = *reinterpret_cast<const float4*>(Ls + tb + q4);
-        const float4 d4 = *reinterpret_cast<const float4*>(Dl + tb + q4);
+      // query tiles [qa, qb): the ones the table window can meet, if it meets this wave's keys at all; the others run the
+      // tile body without the per-tile test (one loop: the tiles in front of the window, then those behind it; the window's
+      // own come last, and dV^T / dK^T sum over the query tiles in that order)
+      int qa = 0, qb = 0;
+      if constexpr (TAB) {
+        bool anyk = false;
+#pragma unroll
+        for (int kt = 0; kt < KT; ++kt) anyk = anyk || kin[kt];
+        if (anyk) { qa = off & ~15; qb = min(N, (off + Len + 15) & ~15); }
+      }
+      // lane parts of the addresses of a query tile: one wave-uniform offset per trip is added to each
+      const float* arow = Qh + 4 * r + 2 * (g >> 1);                                  // q row; the dO row lies Dh - Qh behind it
+      const float* lrow = Ls + tb + 4 * g;                                            // -lse of the lane group's queries; -delta: + T
+      const float* xrow = (tp < 2 ? Dh : Qh) + 4 * (4 * g + tq) + 2 * (tp & 1);       // transposing read of dO / q planes
+      double* dqrow = dQb + 4 * (tb + r) + g;
+      const float* xb = Xb + (4 * g + tq) * 10 + 2 * tp;
+      const float* krow = (tp < 2 ? Kh : Vh) + 4 * (ks + 4 * g + tq) + 2 * (tp & 1);  // transposing read of k planes (rows 8-15: v planes, unused)
+      const lds_u32x2 bw0 = xb_slot<(KT <= 4)>(Xb + r * 10 + 2 * g);
+      // one query tile against the wave's key tiles
+      auto qtile = [&](int q0, auto tabbed) {
+        const u32x2 Aq = *reinterpret_cast<const u32x2*>(arow + 4 * q0);
+        const u32x2 Ad = *reinterpret_cast<const u32x2*>(arow + 4 * q0 + 3 * PLANE);
+        const float4 l4 = *reinterpret_cast<const float4*>(lrow + q0);
+        const float4 d4 = *reinterpret_cast<const float4*>(lrow + q0 + T);
         const f32x4 cl = {l4.x, l4.y, l4.z, l4.w}, cdl = {d4.x, d4.y, d4.z, d4.w};
-        const u32x2 xt = tr_read((tp < 2 ? Dh : Qh) + 4 * (q4 + tq) + 2 * (tp & 1));
-        const u32x4 a8 = lowrows ? u32x4{xt[0], xt[1], 0u, 0u} : u32x4{0u, 0u, xt[0], xt[1]};
-        const bool qin = meets(q0, 16);
+        const u32x2 xt = tr_read(xrow + 4 * q0);
+        const u32x4 a8 = a8_of(xt, mlo, mhi);
         f32x4 dq = {0.f, 0.f, 0.f, 0.f};
-        auto dq_step = [&](int kp) {
-          const float* bp = Xb + (kp & 1) * 2 * BUF + (4 * g + tq) * 10 + 2 * tp;
-          const u32x2 b1 = tr_read(bp), b2 = tr_read(bp + BUF);
-          // (k planes^T of the wave's four key tiles read again per query tile: kept in registers they are 8 more and the kernel
-          // spills at the 128 of four waves per SIMD - 569 against 550 us at N = 512, same box; rows 8-15: v planes, unused)
-          const u32x2 kx = tr_read((tp < 2 ? Kh : Vh) + 4 * (ks + 16 * kp + 4 * g + tq) + 2 * (tp & 1));
-          dq = mm32(u32x4{kx[0], kx[1], kx[0], kx[1]}, u32x4{b1[0], b1[1], b2[0], b2[1]}, dq);
-        };
+        // (k planes^T of the wave's four key tiles read again per query tile: kept in registers they are 8 more and the kernel
+        // spills at the 128 of four waves per SIMD - 569 against 550 us at N = 512, same box)
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt) {
-          const int k0 = ks + 16 * kt;
-          f32x4 s = mm16(Aq, Bk[kt], cl);           // (Bk / Bv read per tile instead of kept: 546 against 531 us at N = 512, same box)
-          const f32x4 dp = mm16(Ad, Bv[kt], cdl);
-          if constexpr (decltype(su_on)::value) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) s[j] *= su;
-          }
-          float p[4];
-          unsigned ph1[2], ph2[2], sh1[2], sh2[2];
-          if (TAB && qin && kin[kt]) {
-            const int ki = k0 + r - off;
-            const bool kok = (unsigned)ki < (unsigned)Len;
-            const int rel0 = (q4 - off) - ki + Len - 1;
-            int e[4]; bool in[4]; float b[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              in[j] = kok && (unsigned)(q4 + j - off) < (unsigned)Len;
-              e[j] = min(max(rel0 + j, 0), 2 * Len - 2) * H + head;
+          auto expo = [&](const f32x4& s, const f32x4& dp, float (&p)[4]) {
+            if constexpr (decltype(tabbed)::value) {
+              if (kin[kt]) {
+                tile_exp_table(s, dp, p, tab, dtab, ks + 16 * kt + r - off, q0 + 4 * g - off, Len, H, head, sc_tab);
+                return;
+              }
             }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) b[j] = tab[e[j]];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) p[j] = __builtin_amdgcn_exp2f(s[j] + (in[j] ? b[j] : 0.f));
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-              if (in[j]) atomicAdd(dtab + e[j], (double)(p[j] * dp[j] * sc_tab));
-          } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) p[j] = __builtin_amdgcn_exp2f(s[j]);
-          }
-          pair_of2(p[0], p[1], ph1[0], ph2[0]); pair_of2(p[2], p[3], ph1[1], ph2[1]);
-          pair_prod2(p[0], dp[0], p[1], dp[1], sh1[0], sh2[0]); pair_prod2(p[2], dp[2], p[3], dp[3], sh1[1], sh2[1]);
-          pair_settle(ph2[0], ph2[1], sh2[0], sh2[1]);
-          acc[kt] = mm32(a8, u32x4{ph1[0], ph1[1], sh1[0], sh1[1]}, acc[kt]);
-          acc[kt] = mm32(a8, u32x4{ph2[0], ph2[1], sh2[0], sh2[1]}, acc[kt]);
-          RAL_XB_FENCE();
-          float* bw = Xb + (kt & 1) * 2 * BUF + r * 10 + 2 * g;
-          *reinterpret_cast<u32x2*>(bw) = u32x2{sh1[0], sh1[1]};
-          *reinterpret_cast<u32x2*>(bw + BUF) = u32x2{sh2[0], sh2[1]};
-          RAL_XB_FENCE();
-          if (kt > 0) dq_step(kt - 1);
+            tile_exp(s, p);
+          };
+          // (Bk / Bv read per tile instead of kept: 546 against 531 us at N = 512, same box)
+          bwd_tile<decltype(su_on)::value>(Aq, Ad, Bk[kt], Bv[kt], cl, cdl, su, a8, acc[kt], bw0 + (kt & 1) * BUF, expo);
+          if (kt & 1) dq_tiles2(dq, xb, krow + 64 * (kt - 1), krow + 64 * kt);
         }
-        asm volatile("" ::: "memory");   // (see k_attn_bwd_m)
-        dq_step(KT - 1);
         // lane (r, g) <- dQ^T rows g (h1 planes of k) and 4 + g (h2 planes) of query r; one add into the image
         {
           float v[4] = {dq[0], dq[1], dq[2], dq[3]};
           rows_transpose4(v);
-          atomicAdd(dQb + 4 * (tb + q0 + r) + g, (double)(v[0] + v[1]));
+          atomicAdd(dqrow + 4 * q0, (double)(v[0] + v[1]));
         }
-        asm volatile("" :: "v"(a8));
-      }
+        asm volatile("" :: "v"(a8));     // (see k_attn_bwd_m)
+      };
+      const int nplain = N - (qb - qa);
+#pragma unroll 1
+      for (int i = 0; i < nplain; i += 16) qtile(i < qa ? i : i + (qb - qa), std::false_type{});
+#pragma unroll 1
+      for (int q0 = qa; q0 < qb; q0 += 16) qtile(q0, std::true_type{});
       // dV (lane groups 0, 1) and dK (lane groups 2, 3) of the wave's key tiles
 #pragma unroll
       for (int kt = 0; kt < KT; ++kt) {
@@ -618,7 +672,7 @@ bool attn_bwd_mh_takes(int N, int H, int Len, bool table) {
   const int kt = attnmh_kt(N), wph = N / (16 * kt);
   if (N % (16 * kt) != 0 || (wph != 1 && wph != 2 && wph != 4 && wph != 8)) return false;
   const int hg = attnmh_hg(N, H);
-  if (H % hg != 0) return false;
+  if (H % hg != 0 || hg * N != 128 * kt) return false;   // (the kernel's T: eight waves of kt key tiles)
   if (table && (2 * Len - 1) * H > 2048) return false;
   return attn_bwd_mh_lds(N, H, hg, Len) <= 150 * 1024;
 }
