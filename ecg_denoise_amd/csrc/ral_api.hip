@@ -376,7 +376,7 @@ struct RalModel {
   void* tdesc = nullptr; int tn = 0, ttotal = 0;
   const float* last_x = nullptr;
   int last_B = 0;
-  int nch_f[5], nch_b[5], hg_f[5], hg_b[5];
+  int nch_f[5], nch_b[5];
   int dw_ksplit[5] = {256, 256, 256, 256, 256};
   // optional in-library kernel timing (bench.py roofline leg): hipEvent pairs around the
   // launches of ONE selected kernel kind, on the stream the kernels run on
@@ -414,6 +414,11 @@ struct ProfScope {
     m->prof_used++;
   }
 };
+
+// Attention backward scratch of the workspace, floats per window (E1 = 8 Lp floats per window and tensor): the (H, N, 2) =
+// E1 / 2 floats the scalar-path sweeps hand over, or rows of table-gradient partials (2048 floats cover the scalar-path tail at
+// H <= 16 and one row of any table the model has).  ral_create checks it against the plans (check_attn_scratch).
+static constexpr size_t attn_scratch_per_window(size_t E1) { return E1 / 2 + 2048; }
 
 struct ral_handle {
   int kind;  // 0 ralenet, 1 unet, 2 acdae, 3 danet
@@ -468,9 +473,7 @@ static size_t plan_workspace(const ral_config& c, RalModel* m /* may be null: si
       M.dx1[k] = take(("dx1_" + std::to_string(k)).c_str(), E); M.dohm[k] = take(("do_" + std::to_string(k)).c_str(), E);
       M.dqkv[k] = take(("dqkv_" + std::to_string(k)).c_str(), 3 * E); M.dupre[k] = take(("dupre_" + std::to_string(k)).c_str(), 4 * E);
       M.a2c0[k] = take(("a2c0_" + std::to_string(k)).c_str(), E / 8);
-      // attention backward scratch: (B, H, N, 2) = E / 2 floats from sweep Q to sweep KV, then (B, 2, H, 64) table-gradient
-      // partials (H <= 16 on the levels that have a table: at most 2048 floats per window)
-      M.astat[k] = take(("astat_" + std::to_string(k)).c_str(), E / 2 + (size_t)B * 2048);
+      M.astat[k] = take(("astat_" + std::to_string(k)).c_str(), B * attn_scratch_per_window((size_t)8 * Lp));
     }
     M.dz0 = take("dz0", E);
     Layout L_; build_layout(c, L_);
@@ -483,15 +486,24 @@ static size_t plan_workspace(const ral_config& c, RalModel* m /* may be null: si
   return cur;
 }
 
-// LDS budgets of a workgroup (bytes; fewer bytes = smaller head groups / more hidden chunks but more co-resident workgroups per CU)
-static constexpr size_t ATTN_FWD_LDS = 72 * 1024, ATTN_BWD_LDS = 78 * 1024, MLP_LDS = 78000;
+// LDS budget of an MLP workgroup (bytes; fewer bytes = more hidden chunks but more co-resident workgroups per CU)
+static constexpr size_t MLP_LDS = 78000;
 
-// head-group size of the attention kernels: the largest power-of-two fraction of the heads whose tiles fit the LDS budget
-static int attn_head_group(int N, int H, int Len, bool bwd) {
-  const size_t budget = bwd ? ATTN_BWD_LDS : ATTN_FWD_LDS;
-  int hg = H;
-  while (hg > 1 && (bwd ? attn_bwd_lds(N, hg, Len) : attn_fwd_lds(N, hg, Len)) > budget) hg /= 2;
-  return hg;
+// The attention backward of every level must find its scratch in the workspace for any lane batch: a plan's need is at most
+// B times its need at B = 1 (linear, or min(ceil(B c), ATTN_ROWS_MAX) rows), so one window's share has to cover B = 1.
+static int check_attn_scratch(const RalModel* m) {
+  for (int l = 0; l < 5; ++l) {
+    const int N = m->Lp >> l, H = CH[l] / 4, NE = m->L >> l;
+    for (int tab = 0; tab < 2; ++tab)
+      for (int f16 = 0; f16 < 2; ++f16) {
+        const int Len = tab && l < 4 && m->lay.rwave ? RWLEN[l] : 0;
+        const AttnPlan p = attn_bwd_plan(N, H, Len, f16, NE, 1);
+        if (p.scratch_floats > attn_scratch_per_window(m->E1))
+          return fail("attention backward at N=%d H=%d Len=%d f16=%d (%s) needs %zu floats of scratch per window, the workspace has %zu",
+                      N, H, Len, f16, p.name, p.scratch_floats, attn_scratch_per_window(m->E1));
+      }
+  }
+  return 0;
 }
 
 static void choose_tiling(RalModel* m) {
@@ -500,16 +512,13 @@ static void choose_tiling(RalModel* m) {
   static const int KS_DEFAULT[5] = {128, 128, 128, 64, 32};
   for (int l = 0; l < 5; ++l) m->dw_ksplit[l] = KS_DEFAULT[l];
   for (int l = 0; l < 5; ++l) {
-    const int C = CH[l], N = m->Lp >> l, H = C / 4;
+    const int C = CH[l], N = m->Lp >> l;
     int n = 1;
     while (n < 4 && mlp_fwd_lds(C, N, n) > MLP_LDS) n *= 2;
     m->nch_f[l] = n;
     n = 1;
     while (n < 4 && mlp_bwd_lds(C, N, n) > MLP_LDS) n *= 2;
     m->nch_b[l] = n;
-    const int Len = l < 4 ? RWLEN[l] : 0;
-    m->hg_f[l] = attn_head_group(N, H, Len, false);
-    m->hg_b[l] = attn_head_group(N, H, Len, true);
   }
 }
 
@@ -570,8 +579,8 @@ static void run_block_fwd(RalModel* m, int bi, const float* in, bool training, c
   { ProfScope p(m, K_QKV_FWD, s); launch_qkv_fwd(C, x, m->pe[l], w, split ? m->wh + 2 * m->lay.blk[bi].wqkv : nullptr, qkv, N, B, s); }
   const int NE = m->L >> l;   // existing tokens of the N slots (NE < N: a window length that is not a multiple of 256)
   { ProfScope p(m, K_ATTN_FWD, s);
-    launch_attn_fwd(qkv, o, training ? woff(a.lse, w0, E1 / 4) : nullptr, table, N, H, m->hg_f[l], Len, B,
-                    (m->f16_split > 0 && m->attn_f16) ? 1 : 0, s, NE); }
+    launch_attn_fwd(attn_fwd_plan(N, H, Len, (m->f16_split > 0 && m->attn_f16) ? 1 : 0, NE), qkv, o,
+                    training ? woff(a.lse, w0, E1 / 4) : nullptr, table, N, H, Len, B, s, NE); }
   { ProfScope p(m, K_MLP_FWD, s);
     launch_mlp_fwd(C, m->nch_f[l], x, o, w, m->params, split ? m->wh : nullptr, training ? woff(a.x1, w0, E1) : nullptr,
                    (training && !mlp_bwd_is_fused(C, N)) ? woff(a.upre, w0, 4 * E1) : nullptr,
@@ -717,7 +726,8 @@ static int fwd_end(RalModel* m, float* y, int B, int64_t global_windows, int tra
 // backward
 // ---------------------------------------------------------------------------------
 // one block: dy (grad of block output) -> dx (grad of block input) [+ extra]; all pointers are window-0 bases
-static void run_block_bwd(RalModel* m, int bi, const float* dy, const float* extra, float* dx, Lane& ln) {
+// (non-zero: the attention backward found the workspace scratch smaller than its plan needs - its gradients were not computed)
+static int run_block_bwd(RalModel* m, int bi, const float* dy, const float* extra, float* dx, Lane& ln) {
   const int si = bi / 2, l = STAGES[si].level, C = CH[l], N = m->Lp >> l, H = C / 4;
   const size_t E1 = m->E1;
   BlockP w = block_ptrs(m->lay.blk[bi], m->params);
@@ -756,30 +766,30 @@ static void run_block_bwd(RalModel* m, int bi, const float* dy, const float* ext
   // the rows up runs with the block's weight-gradient kernels (side stream), not on the chain: nothing on the chain reads it
   AttnTabReduce tabred{nullptr, nullptr, 0, 0};
   static const bool tab_side = ral_knob("TABRED_SIDE", 1) != 0;
+  int short_scratch;
   { ProfScope p(m, K_ATTN_BWD, s);
-    if (side && tab_side) attn_tab_defer_to(&tabred);
-    // (each lane's scratch: its share of the stat2 region followed by its share of the partials region)
-    float* scratch = m->astat[k] + (size_t)w0 * (E1 / 2 + 2048);
-    launch_attn_bwd(qkv, o, dohm, lse, table, gtable, dqkv, scratch, (size_t)B * (E1 / 2 + 2048), N, H, m->hg_b[l], Len, B,
-                    (m->f16_split > 0 && m->attn_f16) ? 1 : 0, s, NE);
-    attn_tab_defer_to(nullptr); }
+    const size_t per_window = attn_scratch_per_window(E1);   // (each lane's scratch: its windows' share)
+    short_scratch = launch_attn_bwd(attn_bwd_plan(N, H, Len, (m->f16_split > 0 && m->attn_f16) ? 1 : 0, NE, B), qkv, o, dohm, lse, table,
+                                    gtable, dqkv, m->astat[k] + (size_t)w0 * per_window, (size_t)B * per_window, N, H, Len, B, s, NE,
+                                    side && tab_side ? &tabred : nullptr); }
   { ProfScope p(m, K_QKV_BWD, s);
     launch_qkv_bwd(C, dqkv, xin, m->pe[l], dx1, woff(extra, w0, E1), w, wt, m->paramsT, splitb ? m->whT : nullptr, gmax, g, woff(dx, w0, E1), N, B, s); }
-  if (!m->want_dw) return;
+  if (!m->want_dw) return short_scratch;
   if (side) {
     EV(hipEventRecord(ln.ev_ready[k], s));
     EV(hipStreamWaitEvent(sd, ln.ev_ready[k], 0));
   }
-  if (tabred.ntab > 0) launch_attn_tpart_reduce(tabred.tpart, tabred.gtable, tabred.ntab, tabred.nrow, sd);
+  if (tabred.ntab > 0) launch_attn_tpart_reduce(tabred, sd);
   { ProfScope p(m, K_DW, sd);
     launch_block_dw(C, dyw, upre, w.le ? a2c0 : nullptr, dupre, x1, dx1, o, dqkv, xin, m->pe[l], w, g, N, B, m->dw_ksplit[l], fused_mlp_dw, gmax, sd); }
   if (side) { EV(hipEventRecord(ln.ev_done[k], sd)); ln.dw_pending[k] = true; }
+  return short_scratch;
 }
 
 // stage: grad of stage output `dy` -> grad of stage input written to `dx` (+extra). Uses `tmp` between blocks.
-static void run_stage_bwd(RalModel* m, int si, const float* dy, const float* extra, float* tmp, float* dx, Lane& ln) {
-  run_block_bwd(m, si * 2 + 1, dy, nullptr, tmp, ln);
-  run_block_bwd(m, si * 2, tmp, extra, dx, ln);
+static int run_stage_bwd(RalModel* m, int si, const float* dy, const float* extra, float* tmp, float* dx, Lane& ln) {
+  const int rc = run_block_bwd(m, si * 2 + 1, dy, nullptr, tmp, ln);
+  return run_block_bwd(m, si * 2, tmp, extra, dx, ln) | rc;
 }
 
 static void run_res_bwd(RalModel* m, int ri, const float* dy, const float* in, float* dx, Lane& ln) {
@@ -836,29 +846,30 @@ static int bwd_begin(RalModel* m, const float* dy, int B, hipStream_t s) {
       EV(hipStreamWaitEvent(LS->l[k].s2, LS->l[k].ev_fork, 0));
     }
 #define EACH_LANE(stmt) for (int k_ = 0; k_ < nl; ++k_) { Lane& ln = LS->l[k_]; stmt; }
+  int short_scratch = 0;
   // decoder: ps_k <- stage <- (u = ps(.) + p)
   EACH_LANE(run_res_bwd(m, 7, m->du0, m->act[17].out, gy[17], ln))
-  EACH_LANE(run_stage_bwd(m, 8, gy[17], nullptr, gy[16], gin[8], ln))          // g u1
+  EACH_LANE(short_scratch |= run_stage_bwd(m, 8, gy[17], nullptr, gy[16], gin[8], ln))          // g u1
   EACH_LANE(run_res_bwd(m, 6, gin[8], m->act[15].out, gy[15], ln))
-  EACH_LANE(run_stage_bwd(m, 7, gy[15], nullptr, gy[14], gin[7], ln))          // g u2
+  EACH_LANE(short_scratch |= run_stage_bwd(m, 7, gy[15], nullptr, gy[14], gin[7], ln))          // g u2
   EACH_LANE(run_res_bwd(m, 5, gin[7], m->act[13].out, gy[13], ln))
-  EACH_LANE(run_stage_bwd(m, 6, gy[13], nullptr, gy[12], gin[6], ln))          // g u3
+  EACH_LANE(short_scratch |= run_stage_bwd(m, 6, gy[13], nullptr, gy[12], gin[6], ln))          // g u3
   EACH_LANE(run_res_bwd(m, 4, gin[6], m->act[11].out, gy[11], ln))
-  EACH_LANE(run_stage_bwd(m, 5, gy[11], nullptr, gy[10], gin[5], ln))          // g x_mid
+  EACH_LANE(short_scratch |= run_stage_bwd(m, 5, gy[11], nullptr, gy[10], gin[5], ln))          // g x_mid
   // the decoder's parameters (utransformer4 .. transconv: the upper half of the flat gradient buffer) have their
   // final gradients once every lane's chain and weight-gradient stream pass this point: gradient bucket 1
   EACH_LANE(EV(hipEventRecord(ln.ev_dec_main, ln.s)); if (side) EV(hipEventRecord(ln.ev_dec_side, ln.s2));)
   m->dec_lanes = nl; m->dec_side = side;
-  EACH_LANE(run_stage_bwd(m, 4, gin[5], gin[5], gy[8], gin[4], ln))            // g p4 = transformer^T(g x_mid) + g x_mid
+  EACH_LANE(short_scratch |= run_stage_bwd(m, 4, gin[5], gin[5], gy[8], gin[4], ln))            // g p4 = transformer^T(g x_mid) + g x_mid
   // encoder: pm_k <- stage, skip gradients added by the first block of each stage
   EACH_LANE(run_res_bwd(m, 3, gin[4], m->act[7].out, gy[7], ln))
-  EACH_LANE(run_stage_bwd(m, 3, gy[7], gin[6], gy[6], gin[3], ln))             // g p3 (+ g u3)
+  EACH_LANE(short_scratch |= run_stage_bwd(m, 3, gy[7], gin[6], gy[6], gin[3], ln))             // g p3 (+ g u3)
   EACH_LANE(run_res_bwd(m, 2, gin[3], m->act[5].out, gy[5], ln))
-  EACH_LANE(run_stage_bwd(m, 2, gy[5], gin[7], gy[4], gin[2], ln))             // g p2 (+ g u2)
+  EACH_LANE(short_scratch |= run_stage_bwd(m, 2, gy[5], gin[7], gy[4], gin[2], ln))             // g p2 (+ g u2)
   EACH_LANE(run_res_bwd(m, 1, gin[2], m->act[3].out, gy[3], ln))
-  EACH_LANE(run_stage_bwd(m, 1, gy[3], gin[8], gy[2], gin[1], ln))             // g p1 (+ g u1)
+  EACH_LANE(short_scratch |= run_stage_bwd(m, 1, gy[3], gin[8], gy[2], gin[1], ln))             // g p1 (+ g u1)
   EACH_LANE(run_res_bwd(m, 0, gin[1], m->act[1].out, gy[1], ln))
-  EACH_LANE(run_stage_bwd(m, 0, gy[1], m->du0, gy[0], gin[0], ln))             // g x0 (+ d u0)
+  EACH_LANE(short_scratch |= run_stage_bwd(m, 0, gy[1], m->du0, gy[0], gin[0], ln))             // g x0 (+ d u0)
 #undef EACH_LANE
   if (side)   // join the side streams into their lanes, then the lanes into s
     for (int k = 0; k < nl; ++k) {
@@ -868,6 +879,7 @@ static int bwd_begin(RalModel* m, const float* dy, int B, hipStream_t s) {
   join_lanes(m, s);
   launch_bn8_bwd_stats(gin[0], m->a0, m->ss, m->bn_sums + 32, (size_t)B * m->Lp, s);
   HIP_OK(hipGetLastError());
+  if (short_scratch) return fail("attention backward: the workspace scratch is smaller than a plan needs (ral_create checks it: the ATTN_* switches changed since?)");
   return sched_check();
 }
 
@@ -1021,6 +1033,7 @@ int ral_create(const ral_config* cfg, ral_handle** out) {
   m->Lp = (cfg->L + 255) / 256 * 256;
   m->E1 = 8 * m->Lp;
   build_layout(*cfg, m->lay);
+  if (cfg->train && check_attn_scratch(m)) { destroy_model(m); delete h; return -1; }
   m->slab_bytes = plan_workspace(*cfg, nullptr, nullptr);
   hipError_t e = hipMalloc(reinterpret_cast<void**>(&m->slab), m->slab_bytes);
   if (e != hipSuccess) {
@@ -1694,30 +1707,47 @@ static int check_attn_args(int N, int H, int Len, int B) {
 int ral_attention_forward(const float* qkv, float* o, float* lse, const float* table, int N, int H, int Len, int B,
                           ral_stream s) {
   if (!qkv || !o) return fail("attention: null pointer");
-  if (check_attn_args(N, H, table ? Len : 0, B)) return -1;
-  launch_attn_fwd(qkv, o, lse, table, N, H, attn_head_group(N, H, table ? Len : 0, false), table ? Len : 0, B, attn_f16_default(), (hipStream_t)s);
+  if (!table || Len == 0) { table = nullptr; Len = 0; }
+  if (check_attn_args(N, H, Len, B)) return -1;
+  launch_attn_fwd(attn_fwd_plan(N, H, Len, attn_f16_default(), 0), qkv, o, lse, table, N, H, Len, B, (hipStream_t)s);
   HIP_OK(hipGetLastError());
   return 0;
 }
 
+int ral_attention_plan(int backward, int N, int H, int Len, int has_table, int f16, int NE, int B, char* kernel_name, int name_cap,
+                       int32_t* hg, int32_t* threads, int64_t* lds_bytes, int64_t* scratch_floats) {
+  if (!has_table) Len = 0;
+  if (check_attn_args(N, H, Len, B)) return -1;
+  if (NE < 0 || NE > N) return fail("attention: NE=%d existing tokens of N=%d slots", NE, N);
+  if (f16 < 0) f16 = attn_f16_default();
+  const AttnPlan p = backward ? attn_bwd_plan(N, H, Len, f16, NE, B) : attn_fwd_plan(N, H, Len, f16, NE);
+  if (kernel_name && name_cap > 0) snprintf(kernel_name, (size_t)name_cap, "%s", p.name);
+  if (hg) *hg = p.hg;
+  if (threads) *threads = p.threads;
+  if (lds_bytes) *lds_bytes = (int64_t)p.lds;
+  if (scratch_floats) *scratch_floats = (int64_t)p.scratch_floats;
+  return 0;
+}
+
 int64_t ral_attention_backward_scratch_floats(int N, int H, int Len, int has_table, int B) {
-  if (check_attn_args(N, H, has_table ? Len : 0, B)) return -1;
-  return (int64_t)attn_bwd_scratch_floats(N, H, has_table ? Len : 0, has_table != 0, B);
+  if (!has_table) Len = 0;
+  if (check_attn_args(N, H, Len, B)) return -1;
+  return (int64_t)attn_bwd_plan(N, H, Len, attn_f16_default(), 0, B).scratch_floats;
 }
 
 int ral_attention_backward(const float* qkv, const float* o, const float* d_o, const float* lse, const float* table,
                            float* gtable, float* dqkv, float* scratch, int64_t scratch_floats, int N, int H, int Len,
                            int B, ral_stream s) {
   if (!qkv || !o || !d_o || !lse || !dqkv || (table && !gtable)) return fail("attention: null pointer");
-  if (check_attn_args(N, H, table ? Len : 0, B)) return -1;
-  // scratch of the two-sweep scalar-path kernels ((B, H, N, 2) floats + table-gradient partials): owned by the caller,
-  // so the entry point holds no state, never allocates and can be captured into a hipGraph
-  const int64_t need = ral_attention_backward_scratch_floats(N, H, Len, table != nullptr, B);
-  if (need > 0 && (!scratch || scratch_floats < need))
+  if (!table || Len == 0) { table = nullptr; Len = 0; }
+  if (check_attn_args(N, H, Len, B)) return -1;
+  // scratch of the kernels that hand partial results from one launch to the next: owned by the caller, so the entry point
+  // holds no state, never allocates and can be captured into a hipGraph
+  const AttnPlan p = attn_bwd_plan(N, H, Len, attn_f16_default(), 0, B);
+  if (launch_attn_bwd(p, qkv, o, d_o, lse, table, gtable, dqkv, scratch, scratch && scratch_floats > 0 ? (size_t)scratch_floats : 0, N, H, Len, B,
+                      (hipStream_t)s))
     return fail("attention backward: this shape needs %lld floats of scratch (ral_attention_backward_scratch_floats), got %lld",
-                (long long)need, (long long)(scratch ? scratch_floats : 0));
-  launch_attn_bwd(qkv, o, d_o, lse, table, gtable, dqkv, need > 0 ? scratch : nullptr, need > 0 ? (size_t)scratch_floats : 0, N, H,
-                  attn_head_group(N, H, table ? Len : 0, true), table ? Len : 0, B, attn_f16_default(), (hipStream_t)s);
+                (long long)p.scratch_floats, (long long)(scratch ? scratch_floats : 0));
   HIP_OK(hipGetLastError());
   return 0;
 }

@@ -50,23 +50,15 @@ RAL_DEV float quad_rows_sum(float x, float y, float z, float w) {
 
 RAL_DEV float f4absmax(float4 v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))); }
 
-// F16: the S and dP tiles on the f16 matrix cores.  A 16 x 16 tile of q k^T at head_dim 4 is a K = 4 product; with both
-// operands as fp16 PAIRS (x = h1 + h2, unscaled residual) the four piece products of the four dims are exactly one
-// v_mfma_f32_16x16x16_f16: lane group g' carries piece pair (g' >> 1, g' & 1) over the four dims, i.e. the A operand of a
-// lane is plane (g >> 1) of its row's token and the B operand plane (g & 1) of its column's token - one 8-byte LDS read
-// each, no packing instruction.  Beside the tile's vector work such an MFMA costs 10.6 cycles per SIMD slot against 41.7
-// for v_mfma_f32_16x16x4_f32 (tools/diag/valu_probe.hip, kinds 23-26: 164.5 -> 102.2 cycles per sweep-A tile).
-// Range: dO and v are multiplied by one power of two per task first (largest magnitude into [2^13, 2^14): dP is linear in
-// both, the factor leaves with the results), q and k are not (S goes through the exponential); their pieces carry an
-// ABSOLUTE error of 2^-25 below |x| = 2^-2, which is what matters for a score, and 2^-23 relative above.
-template <int NT, bool TAB, bool F16, int QT>
+template <int NT, bool TAB>
 __global__ __launch_bounds__(256, RAL_ATTNW_WPE) void k_attn_bwd_w(const float* qkv, const float* o_hm, const float* do_hm,
                                                                    const float* lse, const float* __restrict__ table,
                                                                    float* __restrict__ tpart, float* dqkv, int H, int Len_rt,
                                                                    int ntask) {
   constexpr int HW = NT >= 64 ? 1 : 64 / NT;   // heads per task
   constexpr int T = HW * NT, TPL = T / 64;     // tokens per task, tokens per lane
-  constexpr int WSZ = T * (F16 ? 30 : 18);     // floats of LDS per wave
+  constexpr int WSZ = T * 18;                  // floats of LDS per wave
+  constexpr int QT = 2;                        // 16-token tiles per query (key) block
   constexpr int NB = NT / (16 * QT);           // query (key) blocks per head
   static_assert(NT % (16 * QT) == 0 && T % 64 == 0, "window length");
   constexpr int NBU = NB <= 2 ? NB : 1;        // unrolled blocks (a static store count for the wait, see the task loop)
@@ -79,18 +71,13 @@ __global__ __launch_bounds__(256, RAL_ATTNW_WPE) void k_attn_bwd_w(const float* 
   float* sm = reinterpret_cast<float*>(smem4);
   const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  // fp32 tiles (quads per token): Q32 = q log2 e, K32, D32 = dO (and V32 without F16); pair planes (F16): Qp, Kp, Vp, Dp,
-  // plane p of a tile at + p * 2 T floats, the four halves of token t at float index 2 t
+  // fp32 tiles (quads per token): Q32 = q log2 e, K32, D32 = dO, V32
   float* Q32 = sm + wave * WSZ;
   float* K32 = Q32 + 4 * T;
   float* D32 = K32 + 4 * T;
-  float* V32 = D32 + 4 * T;              // !F16 only
-  float* Qp = D32 + 4 * T;               // F16 only (same place as V32)
-  float* Kp = Qp + 4 * T;
-  float* Vp = Kp + 4 * T;
-  float* Dp = Vp + 4 * T;
-  float* Ls = F16 ? Dp + 4 * T : V32 + 4 * T;   // -lse * log2(e)   (negated: C operands of the S / dP tiles)
-  float* Dl = Ls + T;                           // -rowsum(dO * O) (F16: times the task's scale)
+  float* V32 = D32 + 4 * T;
+  float* Ls = V32 + 4 * T;               // -lse * log2(e)   (negated: C operands of the S / dP tiles)
+  float* Dl = Ls + T;                    // -rowsum(dO * O)
   const int Len = TAB ? Len_rt : 0;
   const int ntab = TAB ? (2 * Len - 1) * H : 0;
   const int nwv = blockDim.x >> 6;   // waves per workgroup (the launcher sizes it so that the wave slices fill the LDS)
@@ -110,7 +97,6 @@ __global__ __launch_bounds__(256, RAL_ATTNW_WPE) void k_attn_bwd_w(const float* 
   const int xe1 = !TAB ? NT : (off < SH ? NT : ((off + Len - SH + 15) & ~15));
   const int stride = gridDim.x * nwv;
   int task = blockIdx.x * nwv + wave;
-  float inv = 1.f;               // F16: 1 / (scale of dO x scale of v) of the task in the LDS
 
   // operands of one task in flight (PREF: one token per lane): q, k, v, dO, O quads and lse
   float4 pq, pk, pv, pd, po;
@@ -126,44 +112,20 @@ __global__ __launch_bounds__(256, RAL_ATTNW_WPE) void k_attn_bwd_w(const float* 
     go = reinterpret_cast<const float4*>(o_hm) + hq;
     gl = lse + hq;
   };
-  auto put = [&](int t, float4 q, float4 k, float4 v, float4 d, float4 o, float l, float cd, float cv, float cq, float ck) {
-    const float4 ql = f4scale(q, RAL_LOG2E);
-    reinterpret_cast<float4*>(Q32)[t] = ql;
+  auto put = [&](int t, float4 q, float4 k, float4 v, float4 d, float4 o, float l) {
+    reinterpret_cast<float4*>(Q32)[t] = f4scale(q, RAL_LOG2E);
     reinterpret_cast<float4*>(K32)[t] = k;
     reinterpret_cast<float4*>(D32)[t] = d;
     Ls[t] = -l * RAL_LOG2E;
-    if constexpr (F16) {
-      auto planes = [&](float* X, float4 x) {
-        const H2x4 s2 = split4(x);
-        *reinterpret_cast<h16x4*>(X + 2 * t) = s2.a;
-        *reinterpret_cast<h16x4*>(X + 2 * T + 2 * t) = s2.b;
-      };
-      planes(Qp, f4scale(ql, cq)); planes(Kp, f4scale(k, ck)); planes(Vp, f4scale(v, cv)); planes(Dp, f4scale(d, cd));
-      Dl[t] = -f4dot(d, o) * (cd * cv);
-    } else {
-      reinterpret_cast<float4*>(V32)[t] = v;
-      Dl[t] = -f4dot(d, o);
-    }
-  };
-  // the task's powers of two for dO and v (largest magnitude into [2^13, 2^14)); returns 1 / their product
-  auto scales = [&](float md, float mv, float& cd, float& cv) -> float {
-    const unsigned bd = __float_as_uint(group_max<64>(md)), bv = __float_as_uint(group_max<64>(mv));
-    cd = h2_row_scale(bd); cv = h2_row_scale(bv);
-    return h2_row_unscale(bd) * h2_row_unscale(bv);
+    reinterpret_cast<float4*>(V32)[t] = v;
+    Dl[t] = -f4dot(d, o);
   };
   auto request = [&](int tk) {
     const float4 *gq, *gk, *gv, *gd, *go; const float* gl;
     task_ptrs(tk, gq, gk, gv, gd, go, gl);
     pq = gq[lane]; pk = gk[lane]; pv = gv[lane]; pd = gd[lane]; po = go[lane]; pl = gl[lane];
   };
-  auto deposit = [&]() {
-    float cd = 1.f, cv = 1.f, cq = 1.f, ck = 1.f;
-    if constexpr (F16) {
-      inv = scales(f4absmax(pd), f4absmax(pv), cd, cv);
-      pair_balance(group_max<64>(f4absmax(pq)) * RAL_LOG2E, group_max<64>(f4absmax(pk)), cq, ck);
-    }
-    put(lane, pq, pk, pv, pd, po, pl, cd, cv, cq, ck);
-  };
+  auto deposit = [&]() { put(lane, pq, pk, pv, pd, po, pl); };
   auto stage = [&](int tk) {   // request + deposit in one go (all loads of the task in flight together)
     const float4 *gq, *gk, *gv, *gd, *go; const float* gl;
     task_ptrs(tk, gq, gk, gv, gd, go, gl);
@@ -173,23 +135,9 @@ __global__ __launch_bounds__(256, RAL_ATTNW_WPE) void k_attn_bwd_w(const float* 
       const int t = lane + 64 * u;
       q[u] = gq[t]; k[u] = gk[t]; v[u] = gv[t]; d[u] = gd[t]; o[u] = go[t]; l[u] = gl[t];
     }
-    float cd = 1.f, cv = 1.f, cq = 1.f, ck = 1.f;
-    if constexpr (F16) {
-      float md = 0.f, mv = 0.f, mq = 0.f, mk = 0.f;
 #pragma unroll
-      for (int u = 0; u < TPL; ++u) {
-        md = fmaxf(md, f4absmax(d[u])); mv = fmaxf(mv, f4absmax(v[u])); mq = fmaxf(mq, f4absmax(q[u])); mk = fmaxf(mk, f4absmax(k[u]));
-      }
-      inv = scales(md, mv, cd, cv);
-      pair_balance(group_max<64>(mq) * RAL_LOG2E, group_max<64>(mk), cq, ck);
-    }
-#pragma unroll
-    for (int u = 0; u < TPL; ++u) put(lane + 64 * u, q[u], k[u], v[u], d[u], o[u], l[u], cd, cv, cq, ck);
+    for (int u = 0; u < TPL; ++u) put(lane + 64 * u, q[u], k[u], v[u], d[u], o[u], l[u]);
   };
-  // MFMA operands of the token on this lane's row (A) / column (B) of a tile
-  auto opA = [&](const float* X, int tok) -> h16x4 { return *reinterpret_cast<const h16x4*>(X + (g >> 1) * 2 * T + 2 * tok); };
-  auto opB = [&](const float* X, int tok) -> h16x4 { return *reinterpret_cast<const h16x4*>(X + (g & 1) * 2 * T + 2 * tok); };
-  auto mm = [&](h16x4 a, h16x4 b, f32x4 c) -> f32x4 { return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0); };
   // Order inside a trip: request the next task's operands, sweep (and store) the current one, THEN wait for the request
   // and move it into the LDS.  With the wait at the top of the next trip (across the back edge) the compiler could not
   // count the stores issued since and waited for them too - a store round trip exposed per task; here the loads, the
@@ -205,7 +153,6 @@ __global__ __launch_bounds__(256, RAL_ATTNW_WPE) void k_attn_bwd_w(const float* 
     else stage(task);
     const int hh = task * HW, win = hh / H, h0 = hh - win * H;
     float* dbase = dqkv + (size_t)win * 3 * H * NT * 4;
-    const float oscale = F16 ? inv : 1.f;
 #pragma unroll
     for (int hl = 0; hl < HW; ++hl) {
       const int head = h0 + hl, tb = hl * NT;   // tb: first token of the head in the task's tiles
@@ -216,7 +163,6 @@ __global__ __launch_bounds__(256, RAL_ATTNW_WPE) void k_attn_bwd_w(const float* 
         const int q0 = qb * 16 * QT;
         const float4* K4 = reinterpret_cast<const float4*>(K32) + tb;
         float qf[QT], df[QT];
-        h16x4 qh[QT], dh[QT];
         f32x4 lq[QT], dl[QT];
         f32x2 dq01[QT], dq23[QT];
         bool qin[QT];
@@ -225,8 +171,7 @@ __global__ __launch_bounds__(256, RAL_ATTNW_WPE) void k_attn_bwd_w(const float* 
         for (int qt = 0; qt < QT; ++qt) {
           const int q = (q0 + 16 * qt + SH + r) & MSK;
           qtok[qt] = q;
-          if constexpr (F16) { qh[qt] = opB(Qp, tb + q); dh[qt] = opB(Dp, tb + q); }
-          else { qf[qt] = Q32[(tb + q) * 4 + g]; df[qt] = D32[(tb + q) * 4 + g]; }
+          qf[qt] = Q32[(tb + q) * 4 + g]; df[qt] = D32[(tb + q) * 4 + g];
           const float l = Lh[q], d = Eh[q];
           lq[qt] = f32x4{l, l, l, l}; dl[qt] = f32x4{d, d, d, d};
           dq01[qt] = f32x2{0.f, 0.f}; dq23[qt] = f32x2{0.f, 0.f};
@@ -234,17 +179,13 @@ __global__ __launch_bounds__(256, RAL_ATTNW_WPE) void k_attn_bwd_w(const float* 
         }
         auto tileA = [&](int kt, auto biased) {
           const int kr = tb + ((kt + SH + r) & MSK), k4i = (kt + SH + 4 * g) & MSK;
-          float kf, vf; h16x4 kh, vh;
-          if constexpr (F16) { kh = opA(Kp, kr); vh = opA(Vp, kr); }
-          else { kf = K32[kr * 4 + g]; vf = V32[kr * 4 + g]; }
+          const float kf = K32[kr * 4 + g], vf = V32[kr * 4 + g];
           float4 k4[4];
 #pragma unroll
           for (int j = 0; j < 4; ++j) k4[j] = K4[k4i + j];
 #pragma unroll
           for (int qt = 0; qt < QT; ++qt) {
-            f32x4 s, dp;
-            if constexpr (F16) { s = mm(kh, qh[qt], lq[qt]); dp = mm(vh, dh[qt], dl[qt]); }
-            else { s = mfma4(kf, qf[qt], lq[qt]); dp = mfma4(vf, df[qt], dl[qt]); }   // s - lse, dP - delta   [key 4g+j][query r]
+            const f32x4 s = mfma4(kf, qf[qt], lq[qt]), dp = mfma4(vf, df[qt], dl[qt]);   // s - lse, dP - delta   [key 4g+j][query r]
             float ds[4];
             if (decltype(biased)::value && qin[qt]) {
               // (the four table reads are unconditional - clamped index - and issued together: one LDS round trip per tile)
@@ -263,7 +204,7 @@ __global__ __launch_bounds__(256, RAL_ATTNW_WPE) void k_attn_bwd_w(const float* 
               for (int j = 0; j < 4; ++j) ds[j] = __builtin_amdgcn_exp2f(s[j] + (in[j] ? b[j] : 0.f)) * dp[j];
 #pragma unroll
               for (int j = 0; j < 4; ++j)
-                if (in[j]) atomicAdd(dtab + e[j], ds[j] * oscale);
+                if (in[j]) atomicAdd(dtab + e[j], ds[j]);
             } else {
 #pragma unroll
               for (int j = 0; j < 4; ++j) ds[j] = __builtin_amdgcn_exp2f(s[j]) * dp[j];
@@ -290,7 +231,7 @@ __global__ __launch_bounds__(256, RAL_ATTNW_WPE) void k_attn_bwd_w(const float* 
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
           const float v = quad_rows_sum(dq01[qt][0], dq01[qt][1], dq23[qt][0], dq23[qt][1]);
-          dbase[((size_t)head * NT + qtok[qt]) * 4 + g] = (0.5f * oscale) * v;   // q = 0.5 (h Wq^T + b)
+          dbase[((size_t)head * NT + qtok[qt]) * 4 + g] = 0.5f * v;   // q = 0.5 (h Wq^T + b)
         }
       }
       // ---------------- sweep B: dK, dV (key block on the lanes, loop over query tiles) ----------------
@@ -300,7 +241,6 @@ __global__ __launch_bounds__(256, RAL_ATTNW_WPE) void k_attn_bwd_w(const float* 
         const float4* Q4 = reinterpret_cast<const float4*>(Q32) + tb;
         const float4* D4 = reinterpret_cast<const float4*>(D32) + tb;
         float kf[QT], vf[QT];
-        h16x4 kh[QT], vh[QT];
         f32x2 dk01[QT], dk23[QT], dv01[QT], dv23[QT];
         bool kin[QT];
         int ktok[QT];
@@ -308,16 +248,13 @@ __global__ __launch_bounds__(256, RAL_ATTNW_WPE) void k_attn_bwd_w(const float* 
         for (int t = 0; t < QT; ++t) {
           const int k = (k0 + 16 * t + SH + r) & MSK;
           ktok[t] = k;
-          if constexpr (F16) { kh[t] = opB(Kp, tb + k); vh[t] = opB(Vp, tb + k); }
-          else { kf[t] = K32[(tb + k) * 4 + g]; vf[t] = V32[(tb + k) * 4 + g]; }
+          kf[t] = K32[(tb + k) * 4 + g]; vf[t] = V32[(tb + k) * 4 + g];
           dk01[t] = f32x2{0.f, 0.f}; dk23[t] = f32x2{0.f, 0.f}; dv01[t] = f32x2{0.f, 0.f}; dv23[t] = f32x2{0.f, 0.f};
           kin[t] = meets(k0 + 16 * t, 16);
         }
         auto tileB = [&](int qt, auto biased) {
           const int qr = tb + ((qt + SH + r) & MSK), q4i = (qt + SH + 4 * g) & MSK;
-          float qa, da; h16x4 qah, dah;
-          if constexpr (F16) { qah = opA(Qp, qr); dah = opA(Dp, qr); }
-          else { qa = Q32[qr * 4 + g]; da = D32[qr * 4 + g]; }
+          const float qa = Q32[qr * 4 + g], da = D32[qr * 4 + g];
           const float4 l4 = *reinterpret_cast<const float4*>(Lh + q4i);
           const float4 d4 = *reinterpret_cast<const float4*>(Eh + q4i);
           float4 q4[4], o4[4];
@@ -325,9 +262,8 @@ __global__ __launch_bounds__(256, RAL_ATTNW_WPE) void k_attn_bwd_w(const float* 
           for (int j = 0; j < 4; ++j) { q4[j] = Q4[q4i + j]; o4[j] = D4[q4i + j]; }
 #pragma unroll
           for (int t = 0; t < QT; ++t) {
-            f32x4 s, dp;
-            if constexpr (F16) { s = mm(qah, kh[t], f32x4{l4.x, l4.y, l4.z, l4.w}); dp = mm(dah, vh[t], f32x4{d4.x, d4.y, d4.z, d4.w}); }
-            else { s = mfma4(qa, kf[t], f32x4{l4.x, l4.y, l4.z, l4.w}); dp = mfma4(da, vf[t], f32x4{d4.x, d4.y, d4.z, d4.w}); }   // [query 4g+j][key r]
+            f32x4 s = mfma4(qa, kf[t], f32x4{l4.x, l4.y, l4.z, l4.w});                      // [query 4g+j][key r]
+            const f32x4 dp = mfma4(da, vf[t], f32x4{d4.x, d4.y, d4.z, d4.w});
             if (decltype(biased)::value && kin[t]) {
               const int ki = ktok[t] - off;
               const bool kok = (unsigned)ki < (unsigned)Len;
@@ -364,7 +300,7 @@ __global__ __launch_bounds__(256, RAL_ATTNW_WPE) void k_attn_bwd_w(const float* 
           const float vk = quad_rows_sum(dk01[t][0], dk01[t][1], dk23[t][0], dk23[t][1]);
           const float vv = quad_rows_sum(dv01[t][0], dv01[t][1], dv23[t][0], dv23[t][1]);
           const size_t kk = ((size_t)head * NT + ktok[t]) * 4 + g;
-          dbase[(size_t)H * NT * 4 + kk] = vk * (RAL_LN2 * oscale);      // Q32 carried log2(e)
+          dbase[(size_t)H * NT * 4 + kk] = vk * RAL_LN2;      // Q32 carried log2(e)
           dbase[(size_t)2 * H * NT * 4 + kk] = vv;
         }
       }
@@ -392,50 +328,17 @@ __global__ __launch_bounds__(256) void k_attn_tpart_reduce(const float* __restri
   if (lane == 0) atomicAdd(gtable + i, t);
 }
 
-// A caller that wants the reduction somewhere else than behind the attention kernel on the chain stream (ral_api.hip runs it on
-// the block's weight-gradient stream: nothing on the chain reads the table gradient) sets this slot around launch_attn_bwd; the
-// reduction is then recorded instead of launched.
-thread_local AttnTabReduce* g_attn_tab_defer = nullptr;
-void attn_tab_defer_to(AttnTabReduce* slot) { g_attn_tab_defer = slot; if (slot) slot->ntab = 0; }
-void launch_attn_tpart_reduce(const float* tpart, float* gtable, int ntab, int nrow, hipStream_t s) {
-  if (g_attn_tab_defer) { *g_attn_tab_defer = AttnTabReduce{tpart, gtable, ntab, nrow}; return; }
-  k_attn_tpart_reduce<<<(ntab + 3) / 4, 256, 0, s>>>(tpart, gtable, ntab, nrow);
+void launch_attn_tpart_reduce(const AttnTabReduce& r, hipStream_t s) {
+  k_attn_tpart_reduce<<<(r.ntab + 3) / 4, 256, 0, s>>>(r.tpart, r.gtable, r.ntab, r.nrow);
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-int attn_f16_default() {
-  static const int m = (int)ral_knob("ATTN_F16", 1);
-  return m;
-}
-static int attnw_mode() {   // RAL_ATTN_BWD_W=0: never (the workgroup kernels of ral_bwd.hip take every shape)
-  static const int m = (int)ral_knob("ATTN_BWD_W", 1);
-  return m;
-}
-// upper bound of the grid (what the scratch is sized for): one workgroup per four tasks, at most 1024
-int attnw_grid_max(int N, int H, int B) {
-  const int hw = N >= 64 ? 1 : 64 / N;
-  const int ntask = B * H / hw, g = (ntask + 3) / 4;
-  return g < 1024 ? g : 1024;
-}
-// the grid of a launch: a whole number of resident rounds (workgroups per CU x 256 CUs) - 1024 workgroups on 768 slots
-// would run a second round one third full
-template <class K>
-static int attnw_grid(K kernel, size_t lds, int N, int H, int B) {
-  const int gmax = attnw_grid_max(N, H, B);
-  const int occ = ral_occupancy(reinterpret_cast<const void*>(kernel), 256, lds, 3);
-  const int slots = ral_num_cus() * (occ > 4 ? 4 : occ);
-  return slots < gmax ? slots : gmax;
-}
-bool attn_bwd_w_takes(int N, int H, int Len, bool table) {
-  if (!attnw_mode()) return false;
-  if (N != 32 && N != 64 && N != 128) return false;
-  if (N == 32 && (H & 1)) return false;
-  if (table && (2 * Len - 1) * H > 2048) return false;
-  return true;
-}
-size_t attn_bwd_w_scratch_floats(int N, int H, int Len, bool table, int B) {
-  if (!table || !attn_bwd_w_takes(N, H, Len, table)) return 0;
-  return (size_t)attnw_grid_max(N, H, B) * (size_t)((2 * Len - 1) * H);
+// the grid of a launch: a whole number of resident rounds (workgroups per CU x CUs; 1024 workgroups on 768 slots would run
+// a second round one third full), at most one workgroup per four tasks and at most max_rows
+int attn_wave_grid(const void* kernel, size_t lds, int ntask, int occ_cap, int max_rows) {
+  const int occ = ral_occupancy(kernel, 256, lds, 3);
+  const int slots = ral_num_cus() * (occ > occ_cap ? occ_cap : occ), need = (ntask + 3) / 4;
+  const int g = slots < need ? slots : need;
+  return g < max_rows ? g : max_rows;
 }
 // =====================================================================================================================
 // Attention FORWARD (softmax(q k^T + bias) v, raletransformer.py:299-316 / transformer.py:302-310) in the same two forms:
@@ -670,61 +573,38 @@ __global__ __launch_bounds__(256, (NT == 64 ? 3 : 4)) void k_attn_fwd_w(const fl
   }
 }
 
-bool attn_fwd_w_takes(int N, int H, int Len, bool table) {
-  static const int on = (int)ral_knob("ATTN_FWD_W", 1);
-  // measured at batch 2048 (us per launch, this kernel with f16 tiles / the kernels of ral_fwd.hip): N = 32: 39 / 45,
-  // 64 (table): 64 / 54, 128 (table): 90 / 91 - the scalar-path forward keeps N = 64 and 128 (RAL_ATTN_FWD_W=2: all three)
-  if (!on || (N != 32 && N != 64 && N != 128) || (on < 2 && N != 32)) return false;
-  if (N == 32 && (H & 1)) return false;
-  if (table && (2 * Len - 1) * H > 2048) return false;
-  return true;
-}
-void launch_attn_fwd_w(const float* qkv, float* o_hm, float* lse, const float* table, int N, int H, int Len, int B, int f16,
+void launch_attn_fwd_w(const AttnPlan& p, const float* qkv, float* o_hm, float* lse, const float* table, int N, int H, int Len, int B,
                        hipStream_t s) {
-  const int hw = N >= 64 ? 1 : 64 / N, T = hw * N;
-  const int ntask = B * H / hw;
-  const int ntab = table ? (2 * Len - 1) * H : 0;
-  const size_t lds = ((size_t)4 * T * 13 + ntab + (table ? H : 0)) * sizeof(float);
-  int grid = 0;
-#define GO(n, tab, h) { RAL_SET_LDS((k_attn_fwd_w<n, tab, h>), lds); grid = attnw_grid(k_attn_fwd_w<n, tab, h>, lds, N, H, B); \
-    k_attn_fwd_w<n, tab, h><<<grid, 256, lds, s>>>(qkv, o_hm, lse, table, H, Len, ntask); }
-#define GOH(n, tab) { if (f16) GO(n, tab, true) else GO(n, tab, false) }
-  if (N == 32) { if (table) GOH(32, true) else GOH(32, false) }
-  else if (N == 64) { if (table) GOH(64, true) else GOH(64, false) }
-  else { if (table) GOH(128, true) else GOH(128, false) }
-#undef GOH
+  using K = AttnKernel;
+  const int ntask = B * H / p.hg;
+#define GO(e, n, tab, h) case K::e: { RAL_SET_LDS((k_attn_fwd_w<n, tab, h>), p.lds); \
+    const int grid = attn_wave_grid(reinterpret_cast<const void*>(k_attn_fwd_w<n, tab, h>), p.lds, ntask, 4, ATTN_ROWS_MAX); \
+    k_attn_fwd_w<n, tab, h><<<grid, 256, p.lds, s>>>(qkv, o_hm, lse, table, H, Len, ntask); } break;
+#define GON(n) GO(FWD_W##n, n, false, false) GO(FWD_W##n##_F16, n, false, true) GO(FWD_W##n##_TAB, n, true, false) GO(FWD_W##n##_TAB_F16, n, true, true)
+  switch (p.kernel) {
+    GON(32) GON(64) GON(128)
+    default: break;   // (launch_attn_fwd sends no other plan here)
+  }
+#undef GON
 #undef GO
 }
 
-void launch_attn_bwd_w(const float* qkv, const float* o_hm, const float* do_hm, const float* lse, const float* table,
-                       float* gtable, float* dqkv, float* tpart, int N, int H, int Len, int B, int f16, hipStream_t s) {
-  const int hw = N >= 64 ? 1 : 64 / N, T = hw * N;
-  const int ntask = B * H / hw;
-  const int ntab = table ? (2 * Len - 1) * H : 0;
-  // waves per workgroup.  Measured at batch 2048, us per launch with 4 / 3 / 2 / 1 waves: N = 128: 236 / 274 /
-  // 245 / 283 (four-wave workgroups of 61 KB leave a CU two of them, five two-wave ones fit - and are no faster), N = 64:
-  // 131 / 135 / 142 / 173, N = 32: 82 / 80 / 83 / 99
-  const int nwv = 4;
-  (void)f16;
-  const size_t lds = ((size_t)nwv * T * 18 + 2 * ntab) * sizeof(float);
+// Waves per workgroup: four (ral_attn_plan.hip sizes the LDS for them).  Measured at batch 2048, us per launch with 4 / 3 / 2 /
+// 1 waves: N = 128: 236 / 274 / 245 / 283 (four-wave workgroups of 61 KB leave a CU two of them, five two-wave ones fit -
+// and are no faster), N = 64: 131 / 135 / 142 / 173, N = 32: 82 / 80 / 83 / 99.  Returns its grid = the rows of tpart it wrote.
+int launch_attn_bwd_w(const AttnPlan& p, const float* qkv, const float* o_hm, const float* do_hm, const float* lse, const float* table,
+                      float* dqkv, float* tpart, int N, int H, int Len, int B, hipStream_t s) {
+  using K = AttnKernel;
+  const int ntask = B * H / p.hg;
   int grid = 0;
-  auto grid_of = [&](auto kern) {
-    const int gmax = attnw_grid_max(N, H, B);          // (the scratch is sized for one workgroup per four tasks)
-    const int occ = ral_occupancy(reinterpret_cast<const void*>(kern), 64 * nwv, lds, 3);
-    const int slots = ral_num_cus() * (occ > 8 ? 8 : occ);
-    const int need = (ntask + nwv - 1) / nwv;
-    int g = slots < need ? slots : need;
-    return g < gmax ? g : gmax;
-  };
-#define GO(n, tab, h, qt) { RAL_SET_LDS((k_attn_bwd_w<n, tab, h, qt>), lds); grid = grid_of(k_attn_bwd_w<n, tab, h, qt>); \
-    k_attn_bwd_w<n, tab, h, qt><<<grid, 64 * nwv, lds, s>>>(qkv, o_hm, do_hm, lse, table, tpart, dqkv, H, Len, ntask); }
-#define GOH(n, tab) { GO(n, tab, false, 2) }   // (the f16 tiles of this form went with round 5: k_attn_bwd_m, ral_attnm.hip)
-  if (N == 32) { if (table) GOH(32, true) else GOH(32, false) }
-  else if (N == 64) {
-    if (table) GOH(64, true) else GOH(64, false)
+#define GO(e, n, tab) case K::e: { RAL_SET_LDS((k_attn_bwd_w<n, tab>), p.lds); \
+    grid = attn_wave_grid(reinterpret_cast<const void*>(k_attn_bwd_w<n, tab>), p.lds, ntask, 8, p.rows); \
+    k_attn_bwd_w<n, tab><<<grid, p.threads, p.lds, s>>>(qkv, o_hm, do_hm, lse, table, tpart, dqkv, H, Len, ntask); } break;
+  switch (p.kernel) {
+    GO(BWD_W32, 32, false) GO(BWD_W32_TAB, 32, true) GO(BWD_W64, 64, false) GO(BWD_W64_TAB, 64, true)
+    GO(BWD_W128, 128, false) GO(BWD_W128_TAB, 128, true)
+    default: break;
   }
-  else { if (table) GOH(128, true) else GOH(128, false) }
-#undef GOH
 #undef GO
-  if (table) launch_attn_tpart_reduce(tpart, gtable, ntab, grid, s);
+  return grid;
 }

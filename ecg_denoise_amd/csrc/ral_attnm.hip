@@ -434,7 +434,7 @@ __global__ __launch_bounds__(512, 4) void k_attn_bwd_mh(const float* __restrict_
   constexpr int BUF = ATTNM_BUF;
   extern __shared__ float4 smem4[];
   float* sm = reinterpret_cast<float*>(smem4);
-  constexpr int T = 128 * KT;                             // = HG N: eight waves of KT key tiles (attn_bwd_mh_takes)
+  constexpr int T = 128 * KT;                             // = HG N: eight waves of KT key tiles (mh_takes, ral_attn_plan.hip)
   constexpr int PPAD = 32;                                // (see k_attn_bwd_m)
   constexpr int PLANE = 4 * T + PPAD;                        // floats from one plane image to the next
   float* Qp = sm;
@@ -642,82 +642,35 @@ __global__ __launch_bounds__(512, 4) void k_attn_bwd_mh(const float* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-static int attnm_mode() {   // RAL_ATTN_BWD_M=0: never
-  static const int m = (int)ral_knob("ATTN_BWD_M", 1);
-  return m;
-}
-bool attn_bwd_m_takes(int N, int H, int Len, bool table) {
-  if (!attnm_mode()) return false;
-  if (N != 32 && N != 64 && N != 128) return false;
-  if (N == 32 && (H & 1)) return false;
-  if (table && (2 * Len - 1) * H > 2048) return false;
-  return true;
-}
-size_t attn_bwd_m_scratch_floats(int N, int H, int Len, bool table, int B) {
-  if (!table || !attn_bwd_m_takes(N, H, Len, table)) return 0;
-  return (size_t)attnw_grid_max(N, H, B) * (size_t)((2 * Len - 1) * H);
-}
-// ---- long windows
-static int attnmh_kt(int N) { return N >= 1024 ? 8 : 4; }
-size_t attn_bwd_mh_lds(int N, int H, int hg, int Len) {
-  return ((size_t)26 * hg * N + 4 * 32 + 4 * hg + 8 * 4 * 160 + (Len > 0 ? (size_t)3 * (2 * Len - 1) * H + 2 : 0) + 4) * sizeof(float);
-}
-static int attnmh_hg(int N, int H) {   // heads per item: eight waves of KT key tiles each
-  const int wph = N / (16 * attnmh_kt(N));
-  return wph >= 8 ? 1 : 8 / wph;
-}
-bool attn_bwd_mh_takes(int N, int H, int Len, bool table) {
-  static const int on = (int)ral_knob("ATTN_BWD_MH", 1);
-  if (!on || N < 256) return false;
-  const int kt = attnmh_kt(N), wph = N / (16 * kt);
-  if (N % (16 * kt) != 0 || (wph != 1 && wph != 2 && wph != 4 && wph != 8)) return false;
-  const int hg = attnmh_hg(N, H);
-  if (H % hg != 0 || hg * N != 128 * kt) return false;   // (the kernel's T: eight waves of kt key tiles)
-  if (table && (2 * Len - 1) * H > 2048) return false;
-  return attn_bwd_mh_lds(N, H, hg, Len) <= 150 * 1024;
-}
-static int attnmh_grid(int N, int H, int B) {
-  const int items = B * (H / attnmh_hg(N, H));
-  return items < 1024 ? items : 1024;
-}
-size_t attn_bwd_mh_scratch_floats(int N, int H, int Len, bool table, int B) {
-  if (!table || !attn_bwd_mh_takes(N, H, Len, table)) return 0;
-  return (size_t)attnmh_grid(N, H, B) * (size_t)((2 * Len - 1) * H);
-}
-void launch_attn_bwd_mh(const float* qkv, const float* o_hm, const float* do_hm, const float* lse, const float* table,
-                        float* gtable, float* dqkv, float* tpart, int N, int H, int Len, int B, hipStream_t s) {
-  const int hg = attnmh_hg(N, H), grid = attnmh_grid(N, H, B), kt = attnmh_kt(N);
-  const size_t lds = attn_bwd_mh_lds(N, H, hg, Len);
-  const int ntab = table ? (2 * Len - 1) * H : 0;
-#define GO(k, tab) { RAL_SET_LDS((k_attn_bwd_mh<k, tab>), lds); \
-    k_attn_bwd_mh<k, tab><<<grid, 512, lds, s>>>(qkv, o_hm, do_hm, lse, table, tpart, dqkv, N, H, hg, table ? Len : 0, B); }
-  if (kt == 4) { if (table) GO(4, true) else GO(4, false) }
-  else { if (table) GO(8, true) else GO(8, false) }
+// Both return their grid = the rows of tpart they wrote (ral_attn_plan.hip: heads per item, LDS, the rows the scratch holds).
+int launch_attn_bwd_mh(const AttnPlan& p, const float* qkv, const float* o_hm, const float* do_hm, const float* lse, const float* table,
+                       float* dqkv, float* tpart, int N, int H, int Len, int B, hipStream_t s) {
+  using K = AttnKernel;
+  const int grid = p.rows;   // one workgroup per (window, head group) item, persistent beyond ATTN_ROWS_MAX
+#define GO(e, k, tab) case K::e: { RAL_SET_LDS((k_attn_bwd_mh<k, tab>), p.lds); \
+    k_attn_bwd_mh<k, tab><<<grid, 512, p.lds, s>>>(qkv, o_hm, do_hm, lse, table, tpart, dqkv, N, H, p.hg, Len, B); } break;
+  switch (p.kernel) {
+    GO(BWD_MH4, 4, false) GO(BWD_MH4_TAB, 4, true) GO(BWD_MH8, 8, false) GO(BWD_MH8_TAB, 8, true)
+    default: return 0;
+  }
 #undef GO
-  if (table) launch_attn_tpart_reduce(tpart, gtable, ntab, grid, s);
+  return grid;
 }
 
-void launch_attn_bwd_m(const float* qkv, const float* o_hm, const float* do_hm, const float* lse, const float* table,
-                       float* gtable, float* dqkv, float* tpart, int N, int H, int Len, int B, hipStream_t s) {
-  const int hw = N >= 64 ? 1 : 64 / N, T = hw * N;
-  const int ntask = B * H / hw;
-  const int ntab = table ? (2 * Len - 1) * H : 0;
-  const int nwv = 4;   // (two-wave workgroups: 198 / 125 against 176 / 111 us at N = 128 / 64)
-  const size_t lds = ((size_t)nwv * (T * 18 + 4 * 32 + 4 * 160) + 3 * ntab + 2) * sizeof(float);
+// (four waves per workgroup; two-wave workgroups: 198 / 125 against 176 / 111 us at N = 128 / 64)
+int launch_attn_bwd_m(const AttnPlan& p, const float* qkv, const float* o_hm, const float* do_hm, const float* lse, const float* table,
+                      float* dqkv, float* tpart, int N, int H, int Len, int B, hipStream_t s) {
+  using K = AttnKernel;
+  const int ntask = B * H / p.hg;
   int grid = 0;
-  auto grid_of = [&](auto kern) {
-    const int gmax = attnw_grid_max(N, H, B);          // (the scratch is sized for one workgroup per four tasks)
-    const int occ = ral_occupancy(reinterpret_cast<const void*>(kern), 64 * nwv, lds, 3);
-    const int slots = ral_num_cus() * (occ > 8 ? 8 : occ);
-    const int need = (ntask + nwv - 1) / nwv;
-    int g = slots < need ? slots : need;
-    return g < gmax ? g : gmax;
-  };
-#define GO(n, tab) { RAL_SET_LDS((k_attn_bwd_m<n, tab>), lds); grid = grid_of(k_attn_bwd_m<n, tab>); \
-    k_attn_bwd_m<n, tab><<<grid, 64 * nwv, lds, s>>>(qkv, o_hm, do_hm, lse, table, tpart, dqkv, H, Len, ntask); }
-  if (N == 32) { if (table) GO(32, true) else GO(32, false) }
-  else if (N == 64) { if (table) GO(64, true) else GO(64, false) }
-  else { if (table) GO(128, true) else GO(128, false) }
+#define GO(e, n, tab) case K::e: { RAL_SET_LDS((k_attn_bwd_m<n, tab>), p.lds); \
+    grid = attn_wave_grid(reinterpret_cast<const void*>(k_attn_bwd_m<n, tab>), p.lds, ntask, 8, p.rows); \
+    k_attn_bwd_m<n, tab><<<grid, p.threads, p.lds, s>>>(qkv, o_hm, do_hm, lse, table, tpart, dqkv, H, Len, ntask); } break;
+  switch (p.kernel) {
+    GO(BWD_M32, 32, false) GO(BWD_M32_TAB, 32, true) GO(BWD_M64, 64, false) GO(BWD_M64_TAB, 64, true)
+    GO(BWD_M128, 128, false) GO(BWD_M128_TAB, 128, true)
+    default: break;
+  }
 #undef GO
-  if (table) launch_attn_tpart_reduce(tpart, gtable, ntab, grid, s);
+  return grid;
 }

@@ -403,7 +403,7 @@ RAL_STAMPS_DEFINE(ral_debug_stamps_fwd)
 // set-up and loop control weigh as much as the tiles - see k_attn_bwd)
 // F16: the S tile on the f16 matrix cores - q log2 e and k staged as token-interleaved fp16-pair planes ([h1 x 4 | h2 x 4],
 // 16 bytes per token as the fp32 quad they replace), one v_mfma_f32_16x16x16_f16 per tile (lane group g' = piece pair
-// (g' >> 1, g' & 1) over the four dims; see k_attn_bwd_w in ral_attn.hip), 10.6 instead of 41.7 cycles beside the tile's
+// (g' >> 1, g' & 1) over the four dims; as k_attn_fwd_w in ral_attn.hip), 10.6 instead of 41.7 cycles beside the tile's
 // vector work (tools/diag/valu_probe.hip)
 typedef _Float16 fh16x4 __attribute__((ext_vector_type(4)));
 RAL_DEV void put_pair_planes(float* X, int t, float4 x) {
@@ -638,7 +638,7 @@ __global__ __launch_bounds__(512, 4) void k_attn_fwd(const float* __restrict__ q
 // per task.  QB query blocks of a wave share the A operand and the V rows (QB = 2: half a V row read per score, as k_attn_fwd).
 // The R-wave table enters a biased block through the C operand (-m + bias), so every block is consumed by the same code.
 // Needs N % (32 QB) == 0 and no padded windows (launch_attn_fwd).
-// <2, true> and <2, false>: 128 VGPRs, no scratch, four waves per SIMD; LDS as k_attn_fwd (attn_fwd_lds: 26.7 KB per head at N = 512)
+// <2, true> and <2, false>: 128 VGPRs, no scratch, four waves per SIMD; LDS as k_attn_fwd (tile_fwd_lds, ral_attn_plan.hip: 26.7 KB per head at N = 512)
 // =================================================================================
 typedef _Float16 fh16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -1235,75 +1235,28 @@ void launch_qkv_fwd(int C, const float* x, const float* pe, const BlockP& w, con
   }
 }
 
-size_t attn_fwd_lds(int N, int HG, int Len) {
-  return ((size_t)3 * HG * N * 4 + (size_t)HG * N + 3 * HG + 8 + (Len > 0 ? (size_t)(2 * Len - 1) * HG : 0)) * sizeof(float);
-}
-
-void launch_attn_fwd(const float* qkv, float* o_hm, float* lse, const float* table, int N, int H, int HG, int Len,
-                     int B, int f16, hipStream_t s, int NE) {
-  if (NE > 0 && NE < N) {   // padded windows (NE of the N token slots exist): the generic tile kernel with its key mask
-    const size_t lds = attn_fwd_lds(N, HG, Len);
-    RAL_SET_LDS((k_attn_fwd<1, 0, true, false, true>), lds);
-    k_attn_fwd<1, 0, true, false, true><<<grid_for(B * (H / HG)), 512, lds, s>>>(qkv, o_hm, lse, table, N, H, HG, Len, B, NE);
-    return;
+void launch_attn_fwd(const AttnPlan& p, const float* qkv, float* o_hm, float* lse, const float* table, int N, int H, int Len,
+                     int B, hipStream_t s, int NE) {
+  using K = AttnKernel;
+  const int hg = p.hg, grid = grid_for(B * (H / hg));
+#define TILE(kern) { RAL_SET_LDS((kern), p.lds); kern<<<grid, p.threads, p.lds, s>>>(qkv, o_hm, lse, table, N, H, hg, Len, B); } break;
+  const int ntask = B * H * ((N + 63) / 64);   // of the scalar-path kernel: a wave per 64 queries of a head
+  switch (p.kernel) {
+    case K::FWD_RAG:
+      RAL_SET_LDS((k_attn_fwd<1, 0, true, false, true>), p.lds);
+      k_attn_fwd<1, 0, true, false, true><<<grid, p.threads, p.lds, s>>>(qkv, o_hm, lse, table, N, H, hg, Len, B, NE);
+      break;
+    case K::FWD_G1: TILE((k_attn_fwd<1>))
+    case K::FWD_G2: TILE((k_attn_fwd<2>))
+    case K::FWD_G2_F16: TILE((k_attn_fwd<2, 0, true, true>))
+    case K::FWD_G2_N32: TILE((k_attn_fwd<2, 32, false>))
+    case K::FWD_T32: TILE((k_attn_fwd_t32<2, false>))
+    case K::FWD_T32_TAB: TILE((k_attn_fwd_t32<2, true>))
+    case K::FWD_V: k_attn_fwd_v<false><<<(ntask + 3) / 4, 256, 0, s>>>(qkv, o_hm, lse, table, N, H, 0, ntask); break;
+    case K::FWD_V_TAB: k_attn_fwd_v<true><<<(ntask + 3) / 4, 256, 0, s>>>(qkv, o_hm, lse, table, N, H, Len, ntask); break;
+    default: launch_attn_fwd_w(p, qkv, o_hm, lse, table, N, H, Len, B, s);
   }
-  if (attn_fwd_w_takes(N, H, Len, table != nullptr)) { launch_attn_fwd_w(qkv, o_hm, lse, table, N, H, Len, B, f16, s); return; }
-  // Window lengths [64, 256] take the query-per-lane kernel on the scalar path.  Measured at batch 2048
-  // (tools/attn_bench.py, us per launch, MFMA-tile kernel vs scalar path): N = 512: 322 / 333, 256: 184 / 172,
-  // 128: 122 / 90, 64: 91 / 51.
-  // with the S tile on the f16 matrix cores the tile kernel takes the long windows from the scalar path again
-  // (RAL_ATTN_FWD_H = smallest such N, 0 = never)
-  static const int hlo = (int)ral_knob("ATTN_FWD_H", 256);
-  const bool tile16 = f16 && hlo > 0 && N >= hlo && N % 32 == 0;
-  // 32x32 score blocks (k_attn_fwd_t32) from RAL_ATTN_FWD_T32 up (smallest such N, 0 = never).  Measured at batch 2048
-  // (tools/attn_bench.py, us per launch, three interleaved rounds, the kernel the level had before vs k_attn_fwd_t32):
-  // N = 512: 274 / 253, 278 / 252, 277 / 252, 256: 162 / 150, 161 / 151, 165 / 148, 128: 91 / 107, 91 / 106, 91 / 106,
-  // 64: 53 / 80, 54 / 80, 53 / 80 (profiles/attn_fwd_t32_levels.txt): the scalar path keeps N = 128 and 64
-  static const int tlo = (int)ral_knob("ATTN_FWD_T32", 256);
-  if (f16 && tlo > 0 && N >= tlo && N % 64 == 0) {
-    const int hg = HG % ATTN_SPLIT == 0 ? HG / ATTN_SPLIT : HG, thr = hg == HG ? 512 : 512 / ATTN_SPLIT;
-    const size_t l2 = attn_fwd_lds(N, hg, Len);
-    if (table) {
-      RAL_SET_LDS((k_attn_fwd_t32<2, true>), l2);
-      k_attn_fwd_t32<2, true><<<grid_for(B * (H / hg)), thr, l2, s>>>(qkv, o_hm, lse, table, N, H, hg, Len, B);
-    } else {
-      RAL_SET_LDS((k_attn_fwd_t32<2, false>), l2);
-      k_attn_fwd_t32<2, false><<<grid_for(B * (H / hg)), thr, l2, s>>>(qkv, o_hm, lse, table, N, H, hg, Len, B);
-    }
-    return;
-  }
-  if (!tile16 && N >= 64 && N <= 256 && N % 4 == 0 && (!table || 2 * Len - 1 <= 64)) {
-    const int ntask = B * H * ((N + 63) / 64);
-    if (table) k_attn_fwd_v<true><<<(ntask + 3) / 4, 256, 0, s>>>(qkv, o_hm, lse, table, N, H, Len, ntask);
-    else k_attn_fwd_v<false><<<(ntask + 3) / 4, 256, 0, s>>>(qkv, o_hm, lse, table, N, H, 0, ntask);
-    return;
-  }
-  if (HG % ATTN_SPLIT == 0 && N % 32 == 0) {   // workgroup split (ral_kernels.hpp)
-    const int hg = HG / ATTN_SPLIT;
-    const size_t l2 = attn_fwd_lds(N, hg, Len);
-    if (N == 32 && !table) {
-      RAL_SET_LDS((k_attn_fwd<2, 32, false>), l2);
-      k_attn_fwd<2, 32, false><<<grid_for(B * (H / hg)), 512 / ATTN_SPLIT, l2, s>>>(qkv, o_hm, lse, table, N, H, hg, Len, B);
-      return;
-    }
-    if (tile16) {
-      RAL_SET_LDS((k_attn_fwd<2, 0, true, true>), l2);
-      k_attn_fwd<2, 0, true, true><<<grid_for(B * (H / hg)), 512 / ATTN_SPLIT, l2, s>>>(qkv, o_hm, lse, table, N, H, hg, Len, B);
-      return;
-    }
-    RAL_SET_LDS((k_attn_fwd<2>), l2);
-    k_attn_fwd<2><<<grid_for(B * (H / hg)), 512 / ATTN_SPLIT, l2, s>>>(qkv, o_hm, lse, table, N, H, hg, Len, B);
-    return;
-  }
-  const size_t lds = attn_fwd_lds(N, HG, Len);
-  const int items = B * (H / HG);
-  if (N % 32 == 0) {
-    RAL_SET_LDS((k_attn_fwd<2>), lds);
-    k_attn_fwd<2><<<grid_for(items), 512, lds, s>>>(qkv, o_hm, lse, table, N, H, HG, Len, B);
-  } else {
-    RAL_SET_LDS((k_attn_fwd<1>), lds);
-    k_attn_fwd<1><<<grid_for(items), 512, lds, s>>>(qkv, o_hm, lse, table, N, H, HG, Len, B);
-  }
+#undef TILE
 }
 
 size_t mlp_fwd_lds(int C, int N, int nch) {

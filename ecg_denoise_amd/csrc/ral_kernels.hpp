@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include "ral_device.hpp"
+#include "ral_attn_plan.hpp"
 #include "../../include/ralenet.h"   // ral_pool_row
 
 // gfx950 has 160 KB of LDS per CU; dynamic LDS above 64 KB must be opted into per kernel.
@@ -26,15 +27,6 @@ void launch_tile_planes(const float* params, void* wt, const void* desc, int nde
 // the activation scales of the nblk transformer blocks (ASC_N floats each; desc: 12 ints per block - see k_act_scales)
 void launch_act_scales(const float* params, const void* desc, float* asc, int nblk, hipStream_t s);
 void launch_qkv_fwd(int C, const float* x, const float* pe, const BlockP& w, const void* wt /* of Wqkv */, float* qkv, int N, int B, hipStream_t s);
-size_t attn_fwd_lds(int N, int HG, int Len);
-// Workgroup split of the attention tile kernels (forward and backward): 1 / ATTN_SPLIT of the head group per item and
-// 512 / ATTN_SPLIT threads, so that 2 * ATTN_SPLIT workgroups share a CU and one's staging latency and barrier waits hide behind
-// the others' tiles (same waves per CU, same LDS).  Measured at batch 2048 (fwd + bwd attention, ms per step): split 1: 7.76,
-// split 2: 7.53.  Head groups or windows it does not divide (HG % 2, N % 32) run unsplit.
-constexpr int ATTN_SPLIT = 2;
-// NE: existing tokens of the N slots (0 or N: all; fewer: padded windows, the generic kernel masks the keys past NE)
-void launch_attn_fwd(const float* qkv, float* o_hm, float* lse, const float* table, int N, int H, int HG, int Len,
-                     int B, int f16, hipStream_t s, int NE = 0);
 size_t mlp_fwd_lds(int C, int N, int nch);
 // pbase / wt: the parameter buffer and the tiled-plane buffer; the levels where mlp_fwd_uses_f16(C, N) run their Linear
 // layers on the planes (wt == nullptr: fp32 MFMA everywhere)
@@ -143,40 +135,28 @@ bool qkv_bwd_uses_f16(int C, int N);
 bool launch_mlp_bwd(int C, int nch, const float* dx2, const float* x1, const float* upre, const BlockP& w,
                     const BlockP& wt, const float* ptbase, const void* wtt, unsigned* gmax, const BlockP& gr, float* dupre, float* dx1, float* do_hm,
                     float* a2c0, int N, int B, bool want_dw, hipStream_t s, int f16_narrow = 0, int NE = 0 /* existing tokens; see launch_attn_fwd */);
-size_t attn_bwd_lds(int N, int HG, int Len);
-bool attn_bwd_uses_stat2(int N, int Len, bool table);   // does launch_attn_bwd need its (B, H, N, 2) scratch for this shape?
-// scratch / scratch_floats: caller-owned; attn_bwd_scratch_floats() says how much the kernels chosen for a shape need
-size_t attn_bwd_scratch_floats(int N, int H, int Len, bool table, int B);
-void launch_attn_bwd(const float* qkv, const float* o_hm, const float* do_hm, const float* lse, const float* table,
-                     float* gtable, float* dqkv, float* scratch, size_t scratch_floats, int N, int H, int HG, int Len, int B,
-                     int f16, hipStream_t s, int NE = 0);
-// f16: S and dP tiles as fp16-pair products on the f16 matrix cores (0: exact fp32 MFMA).  attn_f16_default(): 1 unless
-// RAL_ATTN_F16=0 (what the handle-free operator entry points use; a model handle follows its f16_split option)
-int attn_f16_default();
-// wave-autonomous kernels of the short windows (ral_attn.hip)
-bool attn_fwd_w_takes(int N, int H, int Len, bool table);
-void launch_attn_fwd_w(const float* qkv, float* o_hm, float* lse, const float* table, int N, int H, int Len, int B, int f16,
-                       hipStream_t s);
-bool attn_bwd_w_takes(int N, int H, int Len, bool table);
-size_t attn_bwd_w_scratch_floats(int N, int H, int Len, bool table, int B);
-void launch_attn_bwd_w(const float* qkv, const float* o_hm, const float* do_hm, const float* lse, const float* table,
-                       float* gtable, float* dqkv, float* tpart, int N, int H, int Len, int B, int f16, hipStream_t s);
-int attnw_grid_max(int N, int H, int B);   // upper bound of the wave-autonomous kernels' grids (what their scratch is sized for)
-void launch_attn_tpart_reduce(const float* tpart, float* gtable, int ntab, int nrow, hipStream_t s);
-// deferred form: while a slot is set (attn_tab_defer_to(&slot) ... attn_tab_defer_to(nullptr)), launch_attn_tpart_reduce records
-// its arguments there (ntab > 0) instead of launching; the caller launches it later with launch_attn_tpart_reduce on the stream of
-// its choice (after un-setting the slot)
+// ---- attention: ral_attn_plan.hpp chooses the kernel, these execute the plan (each family's launch code sits with its kernel:
+// ral_fwd.hip, ral_bwd.hip, ral_attn.hip (_w), ral_attnm.hip (_m, _mh))
+void launch_attn_fwd(const AttnPlan& p, const float* qkv, float* o_hm, float* lse, const float* table, int N, int H, int Len,
+                     int B, hipStream_t s, int NE = 0);
+void launch_attn_fwd_w(const AttnPlan& p, const float* qkv, float* o_hm, float* lse, const float* table, int N, int H, int Len, int B, hipStream_t s);
+// the reduction of a plan's table partials: recorded into *defer for the caller to launch on the stream of its choice, or
+// (defer == nullptr) launched on s behind the kernel
 struct AttnTabReduce { const float* tpart; float* gtable; int ntab, nrow; };
-void attn_tab_defer_to(AttnTabReduce* slot);
-// one sweep, every contraction on the f16 matrix cores (ral_attnm.hip; only with f16 != 0)
-bool attn_bwd_m_takes(int N, int H, int Len, bool table);
-size_t attn_bwd_m_scratch_floats(int N, int H, int Len, bool table, int B);
-void launch_attn_bwd_m(const float* qkv, const float* o_hm, const float* do_hm, const float* lse, const float* table,
-                       float* gtable, float* dqkv, float* tpart, int N, int H, int Len, int B, hipStream_t s);
-bool attn_bwd_mh_takes(int N, int H, int Len, bool table);   // its workgroup form for N >= 256
-size_t attn_bwd_mh_scratch_floats(int N, int H, int Len, bool table, int B);
-void launch_attn_bwd_mh(const float* qkv, const float* o_hm, const float* do_hm, const float* lse, const float* table,
-                        float* gtable, float* dqkv, float* tpart, int N, int H, int Len, int B, hipStream_t s);
+void launch_attn_tpart_reduce(const AttnTabReduce& r, hipStream_t s);
+// scratch: caller-owned, at least p.scratch_floats floats; non-zero return (nothing launched): it is smaller
+int launch_attn_bwd(const AttnPlan& p, const float* qkv, const float* o_hm, const float* do_hm, const float* lse, const float* table,
+                    float* gtable, float* dqkv, float* scratch, size_t scratch_floats, int N, int H, int Len, int B, hipStream_t s,
+                    int NE = 0, AttnTabReduce* defer = nullptr);
+// (_w, _m, _mh: tpart = the scratch; they return the rows of partials they wrote = their grid)
+int launch_attn_bwd_w(const AttnPlan& p, const float* qkv, const float* o_hm, const float* do_hm, const float* lse, const float* table,
+                      float* dqkv, float* tpart, int N, int H, int Len, int B, hipStream_t s);
+int launch_attn_bwd_m(const AttnPlan& p, const float* qkv, const float* o_hm, const float* do_hm, const float* lse, const float* table,
+                      float* dqkv, float* tpart, int N, int H, int Len, int B, hipStream_t s);
+int launch_attn_bwd_mh(const AttnPlan& p, const float* qkv, const float* o_hm, const float* do_hm, const float* lse, const float* table,
+                       float* dqkv, float* tpart, int N, int H, int Len, int B, hipStream_t s);
+// grid of a persistent wave-per-head kernel (256 threads, four tasks per workgroup): whole resident rounds, at most max_rows
+int attn_wave_grid(const void* kernel, size_t lds, int ntask, int occ_cap, int max_rows);
 size_t qkv_bwd_lds(int C, int N);
 void launch_qkv_bwd(int C, const float* dqkv, const float* x, const float* pe, const float* dx1, const float* extra,
                     const BlockP& w, const BlockP& wt, const float* ptbase, const void* wtt /* as launch_mlp_bwd */, unsigned* gmax,

@@ -2,12 +2,15 @@
 torch autograd restatement of `softmax(q k^T + R-wave bias) v` (raletransformer.py:299-316; bias table :534-558), one case
 per kernel the launchers can pick (default switches; `test_every_kernel_choice_of_the_launchers` re-runs the file with the
 others):
-  * N = 512 / 256, with and without a table: k_attn_bwd_mh (workgroup per head group, ONE sweep, every contraction on the
-    f16 matrix cores), forward k_attn_fwd<2, 0, true, true> (f16 S tile)
-  * N = 128 / 64 / 32, with and without a table: k_attn_bwd_m (one wave per head, rotated tiles with a table), forward
-    k_attn_fwd_v (N = 64, 128) and k_attn_fwd_w (N = 32)
-  * N = 48 (L = 768 windows) and N = 1024: the generic kernels of ral_bwd.hip / ral_fwd.hip (QT = 1; one head per item)
+  * N = 1024 / 512 / 256, with and without a table: k_attn_bwd_mh<8, .> / <4, .> (workgroup per head group, ONE sweep, every
+    contraction on the f16 matrix cores), forward k_attn_fwd_t32<2, .> (32x32 score blocks on the f16 matrix cores)
+  * N = 128 / 64 / 32, with and without a table: k_attn_bwd_m<N, .> (one wave per head, rotated tiles with a table), forward
+    k_attn_fwd_v<.> (N = 64, 128) and k_attn_fwd_w<32, ., true> (N = 32)
+  * N = 288 (a multiple of 32 but not of 64): forward k_attn_fwd<2, 0, true, true, false> (f16 S tile), backward the tile
+    kernel k_attn_bwd<2, 0, true, false>
+  * N = 48 (L = 768 windows): the generic kernels k_attn_fwd<1, 0, true, false, false> / k_attn_bwd<1, 0, true, false>
   * a table as wide as the window (N = 32, Len = 8 ... N = 64, Len = 32): every tile takes the table path
+tests/test_attention_plan_cpu.py asserts these names, and those under each option string below, for every case of this file.
 Batches that are not a multiple of anything (5, 3) and B = 700 (persistent workgroups take several items)."""
 import ctypes as C
 
@@ -82,6 +85,7 @@ def _case(N, H, Len, B, seed, scales=(1.0, 1.0, 1.0, 1.0)):
     (128, 8, 0, 3), (64, 16, 0, 5),                                                      # the same lengths without a table
     (48, 8, 8, 3), (1024, 2, 64, 1),                                                     # L = 768 and L = 1024 top levels
     (256, 4, 0, 3), (512, 2, 0, 2), (32, 8, 8, 5), (64, 2, 32, 3), (32, 2, 24, 3),                       # long windows without a table; a table as wide as the short window's tiles
+    (288, 2, 0, 3), (1024, 1, 0, 3),                                                     # the two kernels no other case reaches: k_attn_fwd<2, 0, true, true>, k_attn_bwd_mh<8, false>
 ])
 def test_attention_operator_against_fp64(N, H, Len, B):
     errs = _case(N, H, Len, B, seed=N + Len)

@@ -10,7 +10,7 @@ import collections, csv, json, sys
 KIND_OF = {"k_qkv_fwd": "qkv_fwd", "k_attn_fwd": "attn_fwd", "k_mlp_fwd": "mlp_fwd", "k_resample_fwd": "resample_fwd",
            "k_resample_bwd": "resample_bwd", "k_dw": "dw", "k_mlp_bwd": "mlp_bwd", "k_mlp_bwd_s": "mlp_bwd",
            "k_attn_bwd": "attn_bwd", "k_qkv_bwd": "qkv_bwd", "k_attn_fwd_v": "attn_fwd", "k_attn_bwd_vq": "attn_bwd",
-           "k_attn_bwd_vkv": "attn_bwd", "k_attn_table_reduce": "attn_bwd",
+           "k_attn_bwd_vkv": "attn_bwd",
            "k_attn_bwd_w": "attn_bwd", "k_attn_bwd_h": "attn_bwd", "k_attn_bwd_m": "attn_bwd", "k_attn_bwd_mh": "attn_bwd", "k_attn_fwd_w": "attn_fwd",   # (k_attn_tpart_reduce: 0.1 MB
            # behind 14 of the 18 attention launches - not a launch of its own in the per-launch average)
            "k_mlp_fwd_w": "mlp_fwd", "k_mlp_fwd_wh": "mlp_fwd", "k_mlp_fwd_h": "mlp_fwd", "k_mlp_bwd_h": "mlp_bwd", "k_mlp_bwd_w": "mlp_bwd", "k_mlp_bwd_w2": "mlp_bwd",
