@@ -31,6 +31,9 @@ POOL_ROW = np.dtype([("n0", "<i8"), ("T", "<i8"), ("k0", "<i8"), ("lo", "<i8"), 
                      ("w_off", "<i8"), ("slot", "<i4"), ("c", "<i4"), ("nw", "<i4"), ("m", "<i4"), ("turn", "<i4"),
                      ("flags", "<i4")])
 POOL_KEEP = 1
+# ral_rate_row: one row of a rate-conversion pool's per-call table
+RATE_ROW = np.dtype([("n0", "<i8"), ("T", "<i8"), ("m0", "<i8"), ("x_off", "<i8"), ("out_off", "<i8"), ("slot", "<i4"),
+                     ("c", "<i4"), ("m", "<i4"), ("turn", "<i4"), ("flags", "<i4"), ("pad_", "<i4")])
 
 
 def build(jobs=8, verbose=False):
@@ -114,6 +117,9 @@ _SIGS = {
     "ral_mix_records": (C.c_int, [_VP, _VP, C.c_int64, C.c_int, C.c_int64, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP]),
     "ral_score_records_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int, C.c_int64, C.c_int64]),
     "ral_score_records": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int, C.c_int64, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "ral_rate_records": (C.c_int, [_VP, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, _VP, C.c_int, _VP, C.c_int64, _VP]),
+    "ral_rate_pool": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int, _VP, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _VP,
+                                C.c_int, C.c_int, _VP, C.c_int64, _VP]),
     "ral_attention_forward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
     "ral_attention_backward_scratch_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "ral_attention_plan": (C.c_int, [C.c_int] * 8 + [C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),

@@ -1687,6 +1687,37 @@ int ral_score_records(const float* clean, const float* out, const float* noisy, 
   return 0;
 }
 
+int ral_rate_records(const float* x, int64_t R, int leads, int64_t T, int up, int down, const float* bank, int ntaps, float* y,
+                     int64_t T_out, ral_stream s) {
+  if (!x || !bank || !y) return fail("rate_records: null pointer");
+  const char* why = nullptr;
+  if (launch_rate_records(x, (long long)R, leads, (long long)T, up, down, bank, ntaps, y, (long long)T_out, (hipStream_t)s, &why))
+    return fail("rate_records: need %s (R=%lld leads=%d T=%lld up=%d down=%d ntaps=%d T_out=%lld)", why, (long long)R, leads,
+                (long long)T, up, down, ntaps, (long long)T_out);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int ral_rate_pool(float* hist, const float* x, int64_t x_total, const ral_rate_row* table, int rows, ral_rate_row* table_dev,
+                  int upload, int64_t capacity, int leads, int up, int down, const float* bank, int ntaps, int hist_len, float* out,
+                  int64_t out_total, ral_stream s) {
+  if (!hist || !x || !table || !table_dev || !bank || !out) return fail("rate_pool: null pointer");
+  const char* why = nullptr;
+  int bad = -1;
+  const int rc = launch_rate_pool(hist, x, (long long)x_total, table, rows, table_dev, upload, (long long)capacity, leads, up, down,
+                                  bank, ntaps, hist_len, out, (long long)out_total, (hipStream_t)s, &why, &bad);
+  if (rc == -1) {
+    char row[32] = "";
+    if (bad >= 0) snprintf(row, sizeof(row), " in row %d", bad);
+    return fail("rate_pool: need %s%s (rows=%d capacity=%lld leads=%d up=%d down=%d ntaps=%d hist_len=%d x_total=%lld "
+                "out_total=%lld)", why, row, rows, (long long)capacity, leads, up, down, ntaps, hist_len, (long long)x_total,
+                (long long)out_total);
+  }
+  if (rc) return fail("rate_pool: copying the table to the device failed");
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 int ral_wavelet_denoise(const float* x, float* y, int64_t rows, int L, float threshold, ral_stream s) {
   if (!x || !y) return fail("wavelet_denoise: null pointer");
   if (!(threshold >= 0.f)) return fail("wavelet_denoise: the threshold factor must be non-negative (got %g)", (double)threshold);

@@ -116,6 +116,14 @@ long long score_records_scratch_bytes(long long R, int leads, long long T, long 
 int launch_score_records(const float* clean, const float* out, const float* noisy, long long R, int leads, long long T, long long W,
                          void* scratch, double* per_lead, double* per_record, double* per_window, double* window_mean,
                          hipStream_t s, const char** why);
+// sample-rate conversion (ral_rate.hip; ral_rate_records / ral_rate_pool): the arguments (and, with upload != 0, the host table)
+// are checked, the table copied to tab_dev on s, the kernel launched; -1: bad arguments (*why: the rule that is broken, *bad:
+// the row that breaks it or -1), -2: the copy failed
+int launch_rate_records(const float* x, long long R, int leads, long long T, int up, int down, const float* bank, int ntaps,
+                        float* y, long long T_out, hipStream_t s, const char** why);
+int launch_rate_pool(float* hist, const float* x, long long x_total, const ral_rate_row* tab, int rows, ral_rate_row* tab_dev,
+                     int upload, long long cap, int leads, int up, int down, const float* bank, int ntaps, int hist_len,
+                     float* out, long long out_total, hipStream_t s, const char** why, int* bad);
 int launch_conv13_fwd(const float* x, const float* w, const float* b, float* y, int B, int cin, int cout, int L,
                       int lrelu, hipStream_t s);
 int launch_conv13_bwd(const float* x, const float* y, const float* dy, const float* w, float* gw, float* gb,
