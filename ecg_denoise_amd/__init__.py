@@ -35,3 +35,5 @@ from .infer import LiveDenoiser, LivePool, NewRALELiveDenoiser, NewRALELivePool 
 from .evaluate import RecordScores, mix_records, score_records  # noqa: F401
 from .rate import (RateLivePool, RateStreamingDenoiser, Resampler, ResamplerPool, rate_bank, rate_frontier,  # noqa: F401
                    rate_latency, rate_length, rate_ratio)
+from .beats import (BeatDetector, BeatPool, Beats, BeatScores, beat_bank, beat_frontier, beat_geometry, beat_latency,  # noqa: F401
+                    evaluate_beats, match_beats)

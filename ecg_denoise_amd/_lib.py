@@ -26,6 +26,12 @@ class RalError(RuntimeError):
     pass
 
 
+class BeatGeom(C.Structure):
+    """ral_beat_geom: the detector's lengths in samples and its two thresholds"""
+    _fields_ = [("half", C.c_int32), ("wi", C.c_int32), ("wt", C.c_int32), ("rf", C.c_int32), ("rw", C.c_int32),
+                ("alpha", C.c_float), ("floor", C.c_float), ("pad_", C.c_int32)]
+
+
 # ral_pool_row (include/ralenet.h): one row of a stream pool's per-call table, as a numpy record
 POOL_ROW = np.dtype([("n0", "<i8"), ("T", "<i8"), ("k0", "<i8"), ("lo", "<i8"), ("x_off", "<i8"), ("out_off", "<i8"),
                      ("w_off", "<i8"), ("slot", "<i4"), ("c", "<i4"), ("nw", "<i4"), ("m", "<i4"), ("turn", "<i4"),
@@ -34,6 +40,9 @@ POOL_KEEP = 1
 # ral_rate_row: one row of a rate-conversion pool's per-call table
 RATE_ROW = np.dtype([("n0", "<i8"), ("T", "<i8"), ("m0", "<i8"), ("x_off", "<i8"), ("out_off", "<i8"), ("slot", "<i4"),
                      ("c", "<i4"), ("m", "<i4"), ("turn", "<i4"), ("flags", "<i4"), ("pad_", "<i4")])
+# ral_beat_row: one row of a beat-detection pool's per-call table
+BEAT_ROW = np.dtype([("n0", "<i8"), ("T", "<i8"), ("d0", "<i8"), ("x_off", "<i8"), ("out_off", "<i8"), ("slot", "<i4"),
+                     ("c", "<i4"), ("d", "<i4"), ("cap", "<i4"), ("turn", "<i4"), ("flags", "<i4")])
 
 
 def build(jobs=8, verbose=False):
@@ -120,6 +129,12 @@ _SIGS = {
     "ral_rate_records": (C.c_int, [_VP, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, _VP, C.c_int, _VP, C.c_int64, _VP]),
     "ral_rate_pool": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int, _VP, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _VP,
                                 C.c_int, C.c_int, _VP, C.c_int64, _VP]),
+    "ral_beat_records_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int, C.c_int64, C.POINTER(BeatGeom)]),
+    "ral_beat_records": (C.c_int, [_VP, C.c_int64, C.c_int, C.c_int64, C.POINTER(BeatGeom), _VP, C.c_int, _VP, C.c_int64, _VP,
+                                   C.c_int64, _VP, _VP]),
+    "ral_beat_pool": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int, _VP, C.c_int, C.c_int64, C.c_int, C.POINTER(BeatGeom), _VP,
+                                C.c_int, C.c_int, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP]),
+    "ral_beat_match": (C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int64, C.c_int64, _VP, _VP]),
     "ral_attention_forward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
     "ral_attention_backward_scratch_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "ral_attention_plan": (C.c_int, [C.c_int] * 8 + [C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),

@@ -1718,6 +1718,71 @@ int ral_rate_pool(float* hist, const float* x, int64_t x_total, const ral_rate_r
   return 0;
 }
 
+static void beat_geom_text(const ral_beat_geom* g, char* buf, size_t n) {
+  if (g) snprintf(buf, n, "half=%d Wi=%d Wt=%d Rf=%d Rw=%d alpha=%g floor=%g", g->half, g->wi, g->wt, g->rf, g->rw, g->alpha, g->floor);
+  else snprintf(buf, n, "no geometry");
+}
+
+int64_t ral_beat_records_scratch_bytes(int64_t R, int leads, int64_t T, const ral_beat_geom* geom) {
+  const char* why = nullptr;
+  const long long n = beat_records_scratch_bytes((long long)R, leads, (long long)T, geom, &why);
+  if (n < 0) {
+    char gt[160];
+    beat_geom_text(geom, gt, sizeof(gt));
+    return fail("beat_records_scratch_bytes: need %s (R=%lld leads=%d T=%lld %s)", why, (long long)R, leads, (long long)T, gt);
+  }
+  return n;
+}
+
+int ral_beat_records(const float* x, int64_t R, int leads, int64_t T, const ral_beat_geom* geom, const float* bank, int ntaps,
+                     void* scratch, int64_t scratch_bytes, int32_t* peaks, int64_t cap, int32_t* count, ral_stream s) {
+  if (!x || !geom || !bank || !scratch || !peaks || !count) return fail("beat_records: null pointer");
+  const char* why = nullptr;
+  if (launch_beat_records(x, (long long)R, leads, (long long)T, geom, bank, ntaps, scratch, (long long)scratch_bytes, peaks,
+                          (long long)cap, count, (hipStream_t)s, &why)) {
+    char gt[160];
+    beat_geom_text(geom, gt, sizeof(gt));
+    return fail("beat_records: need %s (R=%lld leads=%d T=%lld ntaps=%d cap=%lld scratch_bytes=%lld %s)", why, (long long)R, leads,
+                (long long)T, ntaps, (long long)cap, (long long)scratch_bytes, gt);
+  }
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int ral_beat_pool(float* hist, const float* x, int64_t x_total, const ral_beat_row* table, int rows, ral_beat_row* table_dev,
+                  int upload, int64_t capacity, int leads, const ral_beat_geom* geom, const float* bank, int ntaps, int hist_len,
+                  void* scratch, int64_t scratch_bytes, int64_t* peaks, int64_t peaks_total, int32_t* count, ral_stream s) {
+  if (!hist || !x || !table || !table_dev || !geom || !bank || !scratch || !peaks || !count) return fail("beat_pool: null pointer");
+  const char* why = nullptr;
+  int bad = -1;
+  const int rc = launch_beat_pool(hist, x, (long long)x_total, table, rows, table_dev, upload, (long long)capacity, leads, geom, bank,
+                                  ntaps, hist_len, scratch, (long long)scratch_bytes, (long long*)peaks, (long long)peaks_total, count,
+                                  (hipStream_t)s, &why, &bad);
+  if (rc == -1) {
+    char row[32] = "", gt[160];
+    if (bad >= 0) snprintf(row, sizeof(row), " in row %d", bad);
+    beat_geom_text(geom, gt, sizeof(gt));
+    return fail("beat_pool: need %s%s (rows=%d capacity=%lld leads=%d ntaps=%d hist_len=%d x_total=%lld peaks_total=%lld "
+                "scratch_bytes=%lld %s)", why, row, rows, (long long)capacity, leads, ntaps, hist_len, (long long)x_total,
+                (long long)peaks_total, (long long)scratch_bytes, gt);
+  }
+  if (rc) return fail("beat_pool: copying the table to the device failed");
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int ral_beat_match(const int32_t* ref, const int32_t* ref_count, int64_t ref_cap, const int32_t* det, const int32_t* det_count,
+                   int64_t det_cap, int64_t R, int64_t tol, int64_t* out, ral_stream s) {
+  if (!ref || !ref_count || !det || !det_count || !out) return fail("beat_match: null pointer");
+  const char* why = nullptr;
+  if (launch_beat_match(ref, ref_count, (long long)ref_cap, det, det_count, (long long)det_cap, (long long)R, (long long)tol,
+                        (long long*)out, (hipStream_t)s, &why))
+    return fail("beat_match: need %s (R=%lld ref_cap=%lld det_cap=%lld tol=%lld)", why, (long long)R, (long long)ref_cap,
+                (long long)det_cap, (long long)tol);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 int ral_wavelet_denoise(const float* x, float* y, int64_t rows, int L, float threshold, ral_stream s) {
   if (!x || !y) return fail("wavelet_denoise: null pointer");
   if (!(threshold >= 0.f)) return fail("wavelet_denoise: the threshold factor must be non-negative (got %g)", (double)threshold);

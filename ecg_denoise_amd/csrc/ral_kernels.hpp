@@ -124,6 +124,19 @@ int launch_rate_records(const float* x, long long R, int leads, long long T, int
 int launch_rate_pool(float* hist, const float* x, long long x_total, const ral_rate_row* tab, int rows, ral_rate_row* tab_dev,
                      int upload, long long cap, int leads, int up, int down, const float* bank, int ntaps, int hist_len,
                      float* out, long long out_total, hipStream_t s, const char** why, int* bad);
+// beat detection (ral_beats.hip; ral_beat_records / ral_beat_pool / ral_beat_match): the arguments (and, with upload != 0, the host
+// table) are checked, the table copied to tab_dev on s, the kernels launched; -1: bad arguments (*why: the rule that is broken,
+// *bad: the row that breaks it or -1), -2: the copy failed.  beat_records_scratch_bytes: -1 for a shape the call would refuse
+long long beat_records_scratch_bytes(long long R, int leads, long long T, const ral_beat_geom* geom, const char** why);
+int launch_beat_records(const float* x, long long R, int leads, long long T, const ral_beat_geom* geom, const float* bank, int ntaps,
+                        void* scratch, long long scratch_bytes, int* peaks, long long cap, int* count, hipStream_t s,
+                        const char** why);
+int launch_beat_pool(float* hist, const float* x, long long x_total, const ral_beat_row* tab, int rows, ral_beat_row* tab_dev,
+                     int upload, long long cap, int leads, const ral_beat_geom* geom, const float* bank, int ntaps, int hist_len,
+                     void* scratch, long long scratch_bytes, long long* peaks, long long peaks_total, int* count, hipStream_t s,
+                     const char** why, int* bad);
+int launch_beat_match(const int* ref, const int* nref, long long ref_cap, const int* det, const int* ndet, long long det_cap,
+                      long long R, long long tol, long long* out, hipStream_t s, const char** why);
 int launch_conv13_fwd(const float* x, const float* w, const float* b, float* y, int B, int cin, int cout, int L,
                       int lrelu, hipStream_t s);
 int launch_conv13_bwd(const float* x, const float* y, const float* dy, const float* w, float* gw, float* gb,

@@ -16,10 +16,12 @@ _WAVES = np.array([
 ])
 
 
-def _beats(rng, n, L, leads):
+def _beats(rng, n, L, leads, truth=None):
+    """`truth`: a list that receives, per strip, the R-peak sample indices that fall inside it (no draw depends on it)"""
     t = np.arange(L) / FS
     x = np.zeros((n, leads, L))
     for i in range(n):
+        at = []
         rr = 60.0 / rng.uniform(50, 110)
         r0 = (L / 2 + rng.uniform(-L / 16, L / 16)) / FS
         k0 = int(np.floor((0 - r0) / rr)) - 1
@@ -27,9 +29,12 @@ def _beats(rng, n, L, leads):
         amp = rng.uniform(0.8, 1.2)
         for k in range(k0, k1 + 1):
             rk = r0 + k * rr * (1 + (0 if k == 0 else rng.normal(0, 0.03)))
+            at.append(int(np.floor(rk * FS + 0.5)))
             for ld in range(leads):
                 for (off, wid, a) in _WAVES[ld % 2]:
                     x[i, ld] += amp * a * np.exp(-0.5 * ((t - rk - off * np.sqrt(rr / 0.8)) / wid) ** 2)
+        if truth is not None:
+            truth.append(sorted(p for p in at if 0 <= p < L))
     return x
 
 
@@ -86,6 +91,27 @@ def make_records(R, leads, T, seed=2023, block=4096):
     else:
         x = _beats(rng, R * nb, block, leads).reshape(R, nb, leads, block).transpose(0, 2, 1, 3).reshape(R, leads, nb * block)
     return np.ascontiguousarray(x[..., :T], dtype=np.float32)
+
+
+def make_records_with_beats(R, leads, T, seed=2023, block=4096):
+    """-> (records, beats): `make_records(R, leads, T, seed, block)` bit for bit (the same draws in the same order) and, per
+    record, the ascending sample indices of its R peaks (the centre of the R wave's Gaussian, rounded to a sample; the R wave
+    peaks there in every lead).  Two properties of the truth list that a scorer must know: beats can fall closer together than a
+    detector's refractory period - beat k sits at r0 + k rr (1 + jitter_k) with an independent 3 % jitter of the whole offset
+    k rr, so far from the strip's centre two neighbours can nearly coincide (seed 2023 at T = 4096 has a pair 33 samples apart),
+    and a beat whose centre lies just outside a strip still leaves part of its waves inside without being listed; and the
+    rhythm restarts at every strip boundary (a record longer than `block` is a sequence of independent strips), so the interval
+    across a boundary is arbitrary."""
+    rng = np.random.default_rng(seed)
+    nb = -(-int(T) // block)
+    truth = []
+    if nb <= 1:
+        x = _beats(rng, R, int(T), leads, truth)
+        beats = truth
+    else:
+        x = _beats(rng, R * nb, block, leads, truth).reshape(R, nb, leads, block).transpose(0, 2, 1, 3).reshape(R, leads, nb * block)
+        beats = [[b * block + p for b in range(nb) for p in truth[r * nb + b] if b * block + p < T] for r in range(R)]
+    return np.ascontiguousarray(x[..., :T], dtype=np.float32), beats
 
 
 def make_noise_record(kind, leads, Tn, seed=2023):

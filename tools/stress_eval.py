@@ -15,8 +15,13 @@ run `--model`, 12 leads a NewRALE around RALENet("full", L = 256)): after a warm
 24 B, score 12 B per sample and lead).  Without `--ckpt` the model has its seeded initial weights: the timings and the plumbing
 are meaningful, the dB are not those of a trained model.  Needs a HIP device: there is no fallback.
 
+`--beats` adds what the protocol was built to ask - does denoising give back the beats the noise destroyed: per cell one more
+line and a "beats" entry in the JSON with sensitivity (Se), positive predictivity (+P) and F1 of `BeatDetector` on the noisy and
+on the denoised records against its detections on the clean ones (`evaluate_beats`, 150 ms).  Without the flag the output is
+what it was.
+
     python tools/stress_eval.py [--model full|nra|mlp|unet|acdae|danet|newrale] [--ckpt state_dict.pth] [--L 512]
-                                [--records 4] [--T 65000] [--overlap 0] [--batch 4096] [--time-shapes ...] [--reps 5]
+                                [--records 4] [--T 65000] [--overlap 0] [--batch 4096] [--time-shapes ...] [--reps 5] [--beats]
 """
 import argparse
 import json
@@ -29,7 +34,8 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from ecg_denoise_amd import ACDAE, DANet, NewRALE, RALENet, UNet, mix_records, score_records, synth, wavelet_denoise  # noqa: E402
+from ecg_denoise_amd import (ACDAE, DANet, NewRALE, RALENet, UNet, evaluate_beats, mix_records, score_records, synth,  # noqa: E402
+                             wavelet_denoise)
 from ecg_denoise_amd.data import NOISE_TYPES, TRUE_NOISE  # noqa: E402
 from ecg_denoise_amd.infer import StreamingDenoiser  # noqa: E402
 
@@ -96,12 +102,18 @@ def grid(args, model, name):
         nrow = args.T // Lw * Lw                      # the baseline takes rows of an even length <= 8192
         wav = wavelet_denoise(noisy[..., :nrow].reshape(R, leads, nrow // Lw, Lw).reshape(-1, Lw)).reshape(R, leads, nrow)
         sw = score_records(clean[..., :nrow].contiguous(), wav, noisy[..., :nrow].contiguous(), window=sd.L)
+        ev = evaluate_beats(sd, rec, noise, snrs, offsets=offsets) if args.beats else None
         for i, snr in enumerate(TRUE_NOISE):
             idx = torch.arange(i * args.records, (i + 1) * args.records, device=DEV)
             a, b = _subset(sc, idx, sd.L), _subset(sw, idx, sd.L)
             lines.append(a.output_line(name, 0, kind, snr))
             lines.append(b.output_line("wavelet", 0, kind, snr))
             cells.append({"noise": kind, "intensity": snr, "model": _row(a), "wavelet": _row(b)})
+            if ev is not None:
+                bn, bd = (type(v)(v.counts[idx], v.tol).pooled for v in (ev.noisy, ev.denoised))
+                cells[-1]["beats"] = {"noisy": bn, "denoised": bd}
+                col = lambda d: f"Se {d['sensitivity']:.4f} +P {d['ppv']:.4f} F1 {d['f1']:.4f} (tp {d['tp']} fp {d['fp']} fn {d['fn']})"
+                lines.append(f"{name}_0_{kind}_intensity{snr}:beats: noisy {col(bn)}, denoised {col(bd)}\n")
     return cells, lines
 
 
@@ -158,6 +170,7 @@ def main():
     ap.add_argument("--wavelet-L", type=int, default=1024)
     ap.add_argument("--time-shapes", default="64x2x650000,16x12x650000")
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--beats", action="store_true", help="add Se / +P / F1 of beat detection, noisy and denoised")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("stress_eval: needs a HIP device")
