@@ -37,3 +37,4 @@ from .rate import (RateLivePool, RateStreamingDenoiser, Resampler, ResamplerPool
                    rate_latency, rate_length, rate_ratio)
 from .beats import (BeatDetector, BeatPool, Beats, BeatScores, beat_bank, beat_frontier, beat_geometry, beat_latency,  # noqa: F401
                     evaluate_beats, match_beats)
+from .rhythm import (BeatClasses, BeatClassifier, BeatClassPool, evaluate_rhythm, rhythm_check, rhythm_geometry)  # noqa: F401

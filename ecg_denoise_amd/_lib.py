@@ -32,6 +32,11 @@ class BeatGeom(C.Structure):
                 ("alpha", C.c_float), ("floor", C.c_float), ("pad_", C.c_int32)]
 
 
+class RhythmGeom(C.Structure):
+    """ral_rhythm_geom: the classifier's two lengths in samples and its two thresholds"""
+    _fields_ = [("wb", C.c_int32), ("sa", C.c_int32), ("c0", C.c_float), ("r0", C.c_float)]
+
+
 # ral_pool_row (include/ralenet.h): one row of a stream pool's per-call table, as a numpy record
 POOL_ROW = np.dtype([("n0", "<i8"), ("T", "<i8"), ("k0", "<i8"), ("lo", "<i8"), ("x_off", "<i8"), ("out_off", "<i8"),
                      ("w_off", "<i8"), ("slot", "<i4"), ("c", "<i4"), ("nw", "<i4"), ("m", "<i4"), ("turn", "<i4"),
@@ -44,6 +49,10 @@ RATE_ROW = np.dtype([("n0", "<i8"), ("T", "<i8"), ("m0", "<i8"), ("x_off", "<i8"
 BEAT_ROW = np.dtype([("n0", "<i8"), ("T", "<i8"), ("d0", "<i8"), ("x_off", "<i8"), ("out_off", "<i8"), ("slot", "<i4"),
                      ("c", "<i4"), ("d", "<i4"), ("cap", "<i4"), ("turn", "<i4"), ("flags", "<i4")])
 
+# ral_rhythm_row: one row of a beat-class pool's per-call table
+RHYTHM_ROW = np.dtype([("n0", "<i8"), ("T", "<i8"), ("x_off", "<i8"), ("new_off", "<i8"), ("out_off", "<i8"), ("nb", "<i8"),
+                       ("e0", "<i8"), ("slot", "<i4"), ("c", "<i4"), ("m", "<i4"), ("ne", "<i4"), ("turn", "<i4"), ("flags", "<i4")])
+RHYTHM_K, RHYTHM_MIN_REF = 8, 3
 
 def build(jobs=8, verbose=False):
     """Compile every HIP source for gfx950 into ecg_denoise_amd/libralenet.so (in-tree)."""
@@ -135,6 +144,11 @@ _SIGS = {
     "ral_beat_pool": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int, _VP, C.c_int, C.c_int64, C.c_int, C.POINTER(BeatGeom), _VP,
                                 C.c_int, C.c_int, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP]),
     "ral_beat_match": (C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int64, C.c_int64, _VP, _VP]),
+    "ral_rhythm_pool_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int, C.POINTER(RhythmGeom)]),
+    "ral_rhythm_records": (C.c_int, [_VP, C.c_int64, C.c_int, C.c_int64, C.POINTER(RhythmGeom), _VP, _VP, C.c_int64, _VP, _VP, _VP,
+                                     _VP]),
+    "ral_rhythm_pool": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int, _VP, C.c_int, C.c_int64, C.c_int, C.POINTER(RhythmGeom),
+                                  C.c_int, _VP, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
     "ral_attention_forward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
     "ral_attention_backward_scratch_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "ral_attention_plan": (C.c_int, [C.c_int] * 8 + [C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),

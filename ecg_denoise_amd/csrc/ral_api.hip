@@ -1783,6 +1783,64 @@ int ral_beat_match(const int32_t* ref, const int32_t* ref_count, int64_t ref_cap
   return 0;
 }
 
+static void rhythm_geom_text(const ral_rhythm_geom* g, char* buf, size_t n) {
+  if (g) snprintf(buf, n, "Wb=%d Sa=%d c0=%g r0=%g", g->wb, g->sa, g->c0, g->r0);
+  else snprintf(buf, n, "no geometry");
+}
+
+int64_t ral_rhythm_pool_scratch_bytes(int64_t beats, int leads, const ral_rhythm_geom* geom) {
+  const char* why = nullptr;
+  const long long n = rhythm_pool_scratch_bytes((long long)beats, leads, geom, &why);
+  if (n < 0) {
+    char gt[96];
+    rhythm_geom_text(geom, gt, sizeof(gt));
+    return fail("rhythm_pool_scratch_bytes: need %s (beats=%lld leads=%d %s)", why, (long long)beats, leads, gt);
+  }
+  return n;
+}
+
+int ral_rhythm_records(const float* x, int64_t R, int leads, int64_t T, const ral_rhythm_geom* geom, const int32_t* peaks,
+                       const int32_t* count, int64_t cap, int32_t* label, float* corr, float* rr_ratio, ral_stream s) {
+  if (!x || !geom || !peaks || !count || !label || !corr || !rr_ratio) return fail("rhythm_records: null pointer");
+  const char* why = nullptr;
+  if (launch_rhythm_records(x, (long long)R, leads, (long long)T, geom, peaks, count, (long long)cap, label, corr, rr_ratio,
+                            (hipStream_t)s, &why)) {
+    char gt[96];
+    rhythm_geom_text(geom, gt, sizeof(gt));
+    return fail("rhythm_records: need %s (R=%lld leads=%d T=%lld cap=%lld %s)", why, (long long)R, leads, (long long)T,
+                (long long)cap, gt);
+  }
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int ral_rhythm_pool(const float* hist, const float* x, int64_t x_total, const ral_rhythm_row* table, int rows,
+                    ral_rhythm_row* table_dev, int upload, int64_t capacity, int leads, const ral_rhythm_geom* geom, int hist_len,
+                    float* ring, int64_t* ring_pos, const int64_t* new_pos, int64_t new_total, void* scratch,
+                    int64_t scratch_bytes, int64_t* out_pos, int32_t* label, float* corr, float* rr_ratio, int64_t out_total,
+                    ral_stream s) {
+  if (!hist || !x || !table || !table_dev || !geom || !ring || !ring_pos || !new_pos || !scratch || !out_pos || !label || !corr ||
+      !rr_ratio)
+    return fail("rhythm_pool: null pointer");
+  const char* why = nullptr;
+  int bad = -1;
+  const int rc = launch_rhythm_pool(hist, x, (long long)x_total, table, rows, table_dev, upload, (long long)capacity, leads, geom,
+                                    hist_len, ring, (long long*)ring_pos, (const long long*)new_pos, (long long)new_total, scratch,
+                                    (long long)scratch_bytes, (long long*)out_pos, label, corr, rr_ratio, (long long)out_total,
+                                    (hipStream_t)s, &why, &bad);
+  if (rc == -1) {
+    char row[32] = "", gt[96];
+    if (bad >= 0) snprintf(row, sizeof(row), " in row %d", bad);
+    rhythm_geom_text(geom, gt, sizeof(gt));
+    return fail("rhythm_pool: need %s%s (rows=%d capacity=%lld leads=%d hist_len=%d x_total=%lld new_total=%lld out_total=%lld "
+                "scratch_bytes=%lld %s)", why, row, rows, (long long)capacity, leads, hist_len, (long long)x_total,
+                (long long)new_total, (long long)out_total, (long long)scratch_bytes, gt);
+  }
+  if (rc) return fail("rhythm_pool: copying the table to the device failed");
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 int ral_wavelet_denoise(const float* x, float* y, int64_t rows, int L, float threshold, ral_stream s) {
   if (!x || !y) return fail("wavelet_denoise: null pointer");
   if (!(threshold >= 0.f)) return fail("wavelet_denoise: the threshold factor must be non-negative (got %g)", (double)threshold);

@@ -137,6 +137,15 @@ int launch_beat_pool(float* hist, const float* x, long long x_total, const ral_b
                      const char** why, int* bad);
 int launch_beat_match(const int* ref, const int* nref, long long ref_cap, const int* det, const int* ndet, long long det_cap,
                       long long R, long long tol, long long* out, hipStream_t s, const char** why);
+// beat classes (ral_rhythm.hip; ral_rhythm_records / ral_rhythm_pool): the same conventions as beat detection above
+long long rhythm_pool_scratch_bytes(long long beats, int leads, const ral_rhythm_geom* geom, const char** why);
+int launch_rhythm_records(const float* x, long long R, int leads, long long T, const ral_rhythm_geom* geom, const int* peaks,
+                          const int* count, long long cap, int* label, float* corr, float* rr, hipStream_t s, const char** why);
+int launch_rhythm_pool(const float* hist, const float* x, long long x_total, const ral_rhythm_row* tab, int rows,
+                       ral_rhythm_row* tab_dev, int upload, long long cap, int leads, const ral_rhythm_geom* geom, int hist_len,
+                       float* ring, long long* ring_pos, const long long* new_pos, long long new_total, void* scratch,
+                       long long scratch_bytes, long long* out_pos, int* label, float* corr, float* rr, long long out_total,
+                       hipStream_t s, const char** why, int* bad);
 int launch_conv13_fwd(const float* x, const float* w, const float* b, float* y, int B, int cin, int cout, int L,
                       int lrelu, hipStream_t s);
 int launch_conv13_bwd(const float* x, const float* y, const float* dy, const float* w, float* gw, float* gb,

@@ -114,6 +114,67 @@ def make_records_with_beats(R, leads, T, seed=2023, block=4096):
     return np.ascontiguousarray(x[..., :T], dtype=np.float32), beats
 
 
+# a ventricular ectopic: no P wave, a wide QRS (Gaussian widths 0.022 - 0.036 s against the normal 0.010 - 0.014 s), the R wave of
+# the odd lead upside down, a discordant T (opposite to the R of its lead); same columns as _WAVES.  The deep S keeps enough of
+# the complex inside 8 - 24 Hz for `BeatDetector` to find it
+_V_WAVES = np.array([
+    [(-0.050, 0.022, -0.15), (0.0, 0.022, 1.30), (0.058, 0.026, -0.75), (0.30, 0.060, -0.35)],
+    [(-0.050, 0.024, 0.10), (0.0, 0.024, -1.00), (0.062, 0.028, 0.55), (0.30, 0.065, 0.30)],
+])
+
+
+def make_records_with_rhythm(R, leads, T, seed=2023, p_v=0.12, p_s=0.0):
+    """-> (records, beats, labels): R synthetic clean records, float32 (R, leads, T), at 360 Hz with ectopic beats, per record
+    the ascending sample indices of its R peaks and per beat its label, 0 normal (N), 1 ventricular (V), 2 premature with a
+    normal shape (S).  Draws of its own (`make_records` and `make_records_with_beats` keep theirs).  A record is one strip:
+    heart rate 50 - 110 bpm, amplitude 0.8 - 1.2 and the waves of `_beats` (`_WAVES`, P and T offsets scaled with the
+    square root of the interval), every sinus interval rr (1 + a 3 % jitter).  A beat becomes V with probability `p_v`,
+    otherwise S with probability `p_s` - never the first beat of the list and never directly after a V or an S.  Such a beat
+    comes early, at 0.55 - 0.75 of the running interval after the beat before it, and is followed by a compensatory pause: the
+    sinus beat it pre-empts is dropped and the one after that comes on time.  A V beat has the waves of `_V_WAVES`, an S beat
+    the normal ones.  A wave is added within 8 of its widths (beyond them it is below 2e-14 of its height), so the cost grows
+    with T."""
+    rng = np.random.default_rng(seed)
+    T = int(T)
+    x = np.zeros((R, leads, T))
+    t = np.arange(T) / FS
+    beats, labels = [], []
+    for i in range(R):
+        rr = 60.0 / rng.uniform(50, 110)
+        amp = rng.uniform(0.8, 1.2)
+        stretch = np.sqrt(rr / 0.8)
+        at, lab = [], []
+        prev, was_early = -rng.uniform(1.0, 2.0) * rr, True       # (a sinus beat before the record: its T wave may reach in)
+        events = [(prev, 0)]
+        while prev < T / FS + rr:
+            gap = rr * (1 + rng.normal(0, 0.03))
+            u, kind = rng.uniform(0.55, 0.75), rng.uniform()
+            early = bool(at) and not was_early and kind < p_v + p_s
+            if early:
+                events.append((prev + u * gap, 1 if kind < p_v else 2))
+                gap *= 2                                           # the pre-empted sinus beat is dropped
+                if 0 <= int(np.floor(events[-1][0] * FS + 0.5)) < T:
+                    at.append(int(np.floor(events[-1][0] * FS + 0.5)))
+                    lab.append(events[-1][1])
+            prev += gap
+            events.append((prev, 0))
+            was_early = early
+            p = int(np.floor(prev * FS + 0.5))
+            if 0 <= p < T:
+                at.append(p)
+                lab.append(0)
+        for rk, kind in events:
+            for ld in range(leads):
+                for (off, wid, a) in (_V_WAVES if kind == 1 else _WAVES)[ld % 2]:
+                    c = rk + off * stretch
+                    lo, hi = max(0, int((c - 8 * wid) * FS)), min(T, int((c + 8 * wid) * FS) + 2)
+                    if lo < hi:
+                        x[i, ld, lo:hi] += amp * a * np.exp(-0.5 * ((t[lo:hi] - c) / wid) ** 2)
+        beats.append(at)
+        labels.append(lab)
+    return x.astype(np.float32), beats, labels
+
+
 def make_noise_record(kind, leads, Tn, seed=2023):
     """-> one synthetic noise record, float32 (leads, Tn), of kind bw / ma / em / emb (`noise`): the stand-in for an NSTDB
     record that `mix_records` cuts its segments from."""

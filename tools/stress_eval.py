@@ -20,8 +20,15 @@ line and a "beats" entry in the JSON with sensitivity (Se), positive predictivit
 on the denoised records against its detections on the clean ones (`evaluate_beats`, 150 ms).  Without the flag the output is
 what it was.
 
+`--classes` asks the reference's own downstream question (test_cls.py) of the deterministic beat classifier: per cell one more
+line and a "classes" entry in the JSON with the N / V / S / unclassified counts of `BeatClassifier` on the clean, the noisy and
+the denoised records at the clean records' detections, and accuracy, precision and F1 of the noisy and of the denoised V
+decisions against the clean ones (`evaluate_rhythm`; NaN where a ratio has no denominator).  Without the flag the output is
+what it was.
+
     python tools/stress_eval.py [--model full|nra|mlp|unet|acdae|danet|newrale] [--ckpt state_dict.pth] [--L 512]
                                 [--records 4] [--T 65000] [--overlap 0] [--batch 4096] [--time-shapes ...] [--reps 5] [--beats]
+                                [--classes]
 """
 import argparse
 import json
@@ -34,8 +41,8 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from ecg_denoise_amd import (ACDAE, DANet, NewRALE, RALENet, UNet, evaluate_beats, mix_records, score_records, synth,  # noqa: E402
-                             wavelet_denoise)
+from ecg_denoise_amd import (ACDAE, DANet, NewRALE, RALENet, UNet, evaluate_beats, evaluate_rhythm, mix_records,  # noqa: E402
+                             score_records, synth, wavelet_denoise)
 from ecg_denoise_amd.data import NOISE_TYPES, TRUE_NOISE  # noqa: E402
 from ecg_denoise_amd.infer import StreamingDenoiser  # noqa: E402
 
@@ -84,6 +91,21 @@ def _subset(sc, idx, window):
     return RecordScores(sc.per_lead[idx], sc.per_record[idx], pw, wm, window)
 
 
+def _classes_cell(ev, idx):
+    """the records idx of an `evaluate_rhythm` result -> counts per class and the three scores, noisy and denoised"""
+    from ecg_denoise_amd.rhythm import _score
+    rows = torch.zeros(ev.mask.shape[0], dtype=torch.bool, device=ev.mask.device)
+    rows[idx] = True
+    mask = ev.mask & rows[:, None]
+    truth = (ev.clean.label[mask] == 1).long()
+    out = {k: dict(zip(("N", "V", "S", "unclassified"), c.counts()[idx].sum(0).tolist()))
+           for k, c in (("clean", ev.clean), ("noisy", ev.noisy), ("denoised", ev.denoised))}
+    out["scored_beats"] = int(mask.sum())
+    out["noisy"].update(_score(ev.noisy.logits(mask)[0], truth))
+    out["denoised"].update(_score(ev.denoised.logits(mask)[0], truth))
+    return out
+
+
 def grid(args, model, name):
     sd = StreamingDenoiser(model, batch=args.batch, overlap=args.overlap, use_graph=True)
     leads, n_int = sd.leads, len(TRUE_NOISE)
@@ -103,6 +125,7 @@ def grid(args, model, name):
         wav = wavelet_denoise(noisy[..., :nrow].reshape(R, leads, nrow // Lw, Lw).reshape(-1, Lw)).reshape(R, leads, nrow)
         sw = score_records(clean[..., :nrow].contiguous(), wav, noisy[..., :nrow].contiguous(), window=sd.L)
         ev = evaluate_beats(sd, rec, noise, snrs, offsets=offsets) if args.beats else None
+        evc = evaluate_rhythm(sd, rec, noise, snrs, offsets=offsets) if args.classes else None
         for i, snr in enumerate(TRUE_NOISE):
             idx = torch.arange(i * args.records, (i + 1) * args.records, device=DEV)
             a, b = _subset(sc, idx, sd.L), _subset(sw, idx, sd.L)
@@ -114,6 +137,13 @@ def grid(args, model, name):
                 cells[-1]["beats"] = {"noisy": bn, "denoised": bd}
                 col = lambda d: f"Se {d['sensitivity']:.4f} +P {d['ppv']:.4f} F1 {d['f1']:.4f} (tp {d['tp']} fp {d['fp']} fn {d['fn']})"
                 lines.append(f"{name}_0_{kind}_intensity{snr}:beats: noisy {col(bn)}, denoised {col(bd)}\n")
+            if evc is not None:
+                cc = _classes_cell(evc, idx)
+                cells[-1]["classes"] = cc
+                col = lambda d: (f"acc {d['acc']:.4f} precision {d['precision']:.4f} F1 {d['f1']:.4f} "
+                                 f"(N {d['N']} V {d['V']} S {d['S']} unclassified {d['unclassified']})")
+                lines.append(f"{name}_0_{kind}_intensity{snr}:classes: clean V {cc['clean']['V']} of {cc['scored_beats']} scored, "
+                             f"noisy {col(cc['noisy'])}, denoised {col(cc['denoised'])}\n")
     return cells, lines
 
 
@@ -171,6 +201,7 @@ def main():
     ap.add_argument("--time-shapes", default="64x2x650000,16x12x650000")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--beats", action="store_true", help="add Se / +P / F1 of beat detection, noisy and denoised")
+    ap.add_argument("--classes", action="store_true", help="add beat classes (N / V / S) and acc / precision / F1, noisy and denoised")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("stress_eval: needs a HIP device")
