@@ -41,7 +41,8 @@ import torch
 
 from . import _lib
 from .model import _ptr, _stream
-from .rate import _as_chunks, _rate
+from .pools import SlotState, StreamSurface, as_chunks, pack_chunks
+from .rate import _rate
 
 MODEL_RATE = 360
 AAMI_TOL_S = 0.15        # ANSI/AAMI EC57: a detection within 150 ms of a reference beat matches it
@@ -186,68 +187,28 @@ class BeatDetector:
         return Beats(peaks, count, self.fs)
 
 
-class BeatPoolState:
-    """The host side of a `BeatPool`, without a device: which slots hold an open stream, how many samples each has received and
-    which of its two history planes is current.  `plan` checks the arguments of a call and builds its table (`_lib.BEAT_ROW`)
-    without changing anything; `commit` applies a planned call.  After n samples the decisions [0, frontier(n)) of a stream
-    have been made; closing it at T makes the rest, up to T."""
+class BeatPoolState(SlotState):
+    """The host side of a `BeatPool`, without a device: the slots (`SlotState`) and the detector's geometry.  `plan` checks the
+    arguments of a call and builds its table (`_lib.BEAT_ROW`) without changing anything; `commit` applies a planned call.
+    After n samples the decisions [0, frontier(n)) of a stream have been made; closing it at T makes the rest, up to T."""
 
     def __init__(self, leads, capacity, fs=MODEL_RATE, name="BeatPool"):
         self.geometry = beat_check(fs, leads)
-        if isinstance(capacity, bool) or not isinstance(capacity, numbers.Integral) or capacity < 1:
-            raise _lib.RalError(f"{name}: capacity must be >= 1")
-        self.fs, self.leads, self.capacity, self.name = fs, int(leads), int(capacity), name
-        self.lag = _lag(self.geometry)
+        super().__init__(capacity, leads, name)
+        self.fs, self.lag = fs, _lag(self.geometry)
         self.hist_len = 2 * self.lag
-        self.n = np.zeros(self.capacity, dtype=np.int64)
-        self.turn = np.zeros(self.capacity, dtype=np.int32)
-        self.is_open = np.zeros(self.capacity, dtype=bool)
-        self.free = list(range(self.capacity - 1, -1, -1))      # (slot 0 first)
 
     def frontier(self, n):
         return max(0, int(n) - self.lag)
 
-    def open(self):
-        if not self.free:
-            raise _lib.RalError(f"{self.name}.open: all {self.capacity} slots hold an open stream")
-        sid = self.free.pop()
-        self.n[sid], self.is_open[sid] = 0, True
-        return sid
-
-    def _is_open(self, sid):
-        return isinstance(sid, (int, np.integer)) and not isinstance(sid, bool) and 0 <= sid < self.capacity \
-            and bool(self.is_open[sid])
-
     def plan(self, shapes, close=()):
         """shapes {sid: shape of its chunk, (leads, c) with c >= 0}, close: the sids that end with this call -> (sids in row
         order, table); raises RalError for a bad argument"""
-        name = self.name
-        sids = list(shapes)
-        for sid in close:
-            if sid not in sids:
-                sids.append(sid)
-        if not sids:
-            raise _lib.RalError(f"{name}.push: nothing to do (no chunk and no stream to close)")
-        for sid in sids:
-            if not self._is_open(sid):
-                raise _lib.RalError(f"{name}.push: {sid!r} is not an open stream")
-        if len(sids) > 65535:
-            raise _lib.RalError(f"{name}.push: more than 65535 streams in one call")
-        lens = np.zeros(len(sids), dtype=np.int64)
-        for r, (sid, shape) in enumerate(shapes.items()):
-            if len(shape) != 2 or shape[0] != self.leads:
-                raise _lib.RalError(f"{name}.push: stream {sid}: expected a chunk of shape ({self.leads}, samples), got "
-                                    f"{tuple(shape)}")
-            lens[r] = shape[1]
-        if np.any(lens > 0x3fffffff):
-            raise _lib.RalError(f"{name}.push: a chunk of more than 2^30 - 1 samples")
-        slot = np.asarray(sids, dtype=np.int64)
-        ends = np.isin(slot, np.asarray(list(close), dtype=np.int64))
-        n0 = self.n[slot]
+        sids, slot, lens, ends, n0 = self.named(shapes, close, 65535, "65535 streams")
         n1 = n0 + lens
         if np.any(ends & (n1 < 1)):
             r = int(np.argmax(ends & (n1 < 1)))
-            raise _lib.RalError(f"{name}.push: stream {sids[r]} would end without a single sample")
+            raise _lib.RalError(f"{self.name}.push: stream {sids[r]} would end without a single sample")
         d0 = np.maximum(0, n0 - self.lag)
         d = np.where(ends, n1, np.maximum(0, n1 - self.lag)) - d0
         cap = np.where(d > 0, d // (self.geometry["Rf"] + 1) + 1, 0)
@@ -264,16 +225,10 @@ class BeatPoolState:
         s = np.where(tab["d"] > 0, np.minimum(tab["n0"] + tab["c"], d1 + w) - np.maximum(0, d0 - w), 0)
         return max(1, int(s.max()))
 
-    def commit(self, tab):
-        slot, keep = tab["slot"], (tab["flags"] & _lib.POOL_KEEP) != 0
-        self.n[slot] = tab["n0"] + tab["c"]
-        self.turn[slot[keep]] ^= 1
-        for sid in slot[~keep]:
-            self.is_open[sid] = False
-            self.free.append(int(sid))
+    commit = SlotState.commit_rows
 
 
-class BeatPool:
+class BeatPool(StreamSurface):
     """R peaks of up to `capacity` independent live streams of `leads` leads at rate `fs`, chunk by chunk (`ral_beat_pool`).
     `open()` returns a stream id; `push(chunks, close=())` takes {sid: (leads, c)} (c >= 0, host or device) for any subset of the
     open streams, ends the streams listed in `close`, and returns {sid: int64 device tensor} for every sid named: the peaks of
@@ -294,40 +249,25 @@ class BeatPool:
         self.det.on_device()
         self.hist = torch.zeros(2, self.capacity, self.leads, self.hist_len, dtype=torch.float32, device=self.device)
 
-    open_streams = property(lambda self: tuple(int(s) for s in np.flatnonzero(self.state.is_open)))
-
-    def open(self):
-        """-> the sid of a new stream (a free slot); RalError when `capacity` streams are open"""
-        return self.state.open()
-
-    def samples_in(self, sid):
-        if not self.state._is_open(sid):
-            raise _lib.RalError(f"{type(self).__name__}.samples_in: {sid!r} is not an open stream")
-        return int(self.state.n[sid])
-
     def plan(self, shapes, close=()):
         return self.state.plan(shapes, close)
 
-    def close(self, sid, x=None):
-        """end one stream, with an optional last chunk -> its remaining peaks"""
-        return self.push({} if x is None else {sid: x}, close=(sid,))[sid]
-
     @torch.no_grad()
     def push(self, chunks, close=()):
-        xs = _as_chunks(chunks)
+        xs = as_chunks(chunks)
         sids, tab = self.state.plan({sid: tuple(x.shape) for sid, x in xs.items()}, tuple(close))
+        xp, x_total, _ = pack_chunks(xs, self.leads, self.device)
+        return self.run(xp, x_total, sids, tab)
+
+    def run(self, xp, x_total, sids, tab):
+        """carry out a planned call: xp, x_total the chunks as `pack_chunks` packs them, sids and tab as planned ->
+        {sid: peaks}; commits the plan"""
         dev, leads, d, lib = self.device, self.leads, self.det, _lib.lib()
-        x_total, peaks_total = int(tab["c"].sum()), int(tab["cap"].sum())
+        peaks_total = int(tab["cap"].sum())
         nbytes = lib.ral_beat_records_scratch_bytes(len(tab), leads, self.state.span(tab), d.geom)
         if nbytes < 0:
             raise _lib.RalError(lib.ral_last_error().decode())
         with torch.cuda.device(dev):
-            xp = torch.empty(max(x_total, 1) * leads, dtype=torch.float32, device=dev)
-            o = 0
-            for x in xs.values():                       # row r's (leads, c) at x_off * leads
-                if x.numel():
-                    xp[o:o + x.numel()].copy_(x.reshape(-1), non_blocking=True)
-                    o += x.numel()
             scratch = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=dev)
             peaks = torch.empty(max(peaks_total, 1), dtype=torch.int64, device=dev)
             count = torch.empty(len(tab), dtype=torch.int32, device=dev)

@@ -20,6 +20,7 @@ import torch
 
 from . import _lib
 from .model import NewRALE, _ptr, _stream
+from .pools import SlotState, StreamSurface, as_chunks, pack_chunks
 
 
 class GraphedForward:
@@ -456,62 +457,26 @@ def pool_plan(n0, c, closing, L, hop):
     return k0, nw, lo, m, np.where(closing, n1, -1)
 
 
-class PoolState:
-    """The host side of a stream pool, without a device: which slots hold an open stream, how many samples each has received and
-    which of its two history buffers is current.  `plan` checks the arguments of a call and builds its tables (`_lib.POOL_ROW`)
-    without changing anything; `commit` applies a planned call."""
+class PoolState(SlotState):
+    """The host side of a stream pool, without a device: the slots (`SlotState`) and the window geometry.  `plan` checks the
+    arguments of a call and builds its tables (`_lib.POOL_ROW`) without changing anything; `commit` applies a planned call."""
 
     def __init__(self, capacity, leads, L, overlap, name="LivePool", grid=(64, 2048)):
         if L < grid[0] or L % grid[0] or L > grid[1]:      # the window lengths of the pool's gather / emit kernels
             raise _lib.RalError(f"{name}: L must be a multiple of {grid[0]} up to {grid[1]} (got {L})")
         if overlap < 0 or overlap >= L or overlap % 2:
             raise _lib.RalError("overlap must be an even number of samples in [0, L)")
-        if capacity < 1:
-            raise _lib.RalError("capacity must be >= 1")
-        self.capacity, self.leads, self.L, self.hop, self.name = int(capacity), int(leads), int(L), int(L - overlap), name
-        self.n = np.zeros(self.capacity, dtype=np.int64)
-        self.turn = np.zeros(self.capacity, dtype=np.int32)
-        self.is_open = np.zeros(self.capacity, dtype=bool)
-        self.free = list(range(self.capacity - 1, -1, -1))      # (slot 0 first)
-
-    def open(self):
-        if not self.free:
-            raise _lib.RalError(f"{self.name}.open: all {self.capacity} slots hold an open stream")
-        sid = self.free.pop()
-        self.n[sid], self.is_open[sid] = 0, True
-        return sid
+        super().__init__(capacity, leads, name)
+        self.L, self.hop = int(L), int(L - overlap)
 
     def plan(self, shapes, close=()):
         """shapes {sid: shape of its chunk}, close: the sids that end with this call -> (sids in row order, table, table of the
         kept last windows to emit); raises RalError for a bad argument"""
         name = self.name
-        sids = list(shapes)
-        closing = []
-        for sid in close:
-            if sid not in shapes and sid not in closing:
-                closing.append(sid)
-        sids += closing
-        if not sids:
-            raise _lib.RalError(f"{name}.push: nothing to do (no chunk and no stream to close)")
-        for sid in sids:
-            if not isinstance(sid, (int, np.integer)) or isinstance(sid, bool) or not 0 <= sid < self.capacity \
-                    or not self.is_open[sid]:
-                raise _lib.RalError(f"{name}.push: {sid!r} is not an open stream")
-        lens = np.zeros(len(sids), dtype=np.int64)
-        for r, (sid, shape) in enumerate(shapes.items()):
-            if len(shape) != 2 or shape[0] != self.leads:
-                raise _lib.RalError(f"{name}.push: stream {sid}: expected a chunk of shape ({self.leads}, samples), got "
-                                    f"{tuple(shape)}")
-            lens[r] = shape[1]
-        slot = np.asarray(sids, dtype=np.int64)
-        ends = np.zeros(len(sids), dtype=bool)
-        ends[np.isin(slot, np.asarray(list(close), dtype=np.int64))] = True
+        sids, slot, lens, ends, n0 = self.named(shapes, close)
         if np.any((lens == 0) & ~ends):
             sid = sids[int(np.argmax((lens == 0) & ~ends))]
             raise _lib.RalError(f"{name}.push: stream {sid}: an empty chunk (only a closing stream may come without samples)")
-        if np.any(lens > 0x3fffffff):
-            raise _lib.RalError(f"{name}.push: a chunk of more than 2^30 - 1 samples")
-        n0 = self.n[slot]
         short = ends & (n0 + lens < self.L)
         if np.any(short):
             r = int(np.argmax(short))
@@ -529,18 +494,13 @@ class PoolState:
         last["nw"], last["w_off"] = 1, np.arange(len(last))
         return sids, tab, last
 
-    def commit(self, tab):
-        slot, keep = tab["slot"], (tab["flags"] & _lib.POOL_KEEP) != 0
-        self.n[slot] = tab["n0"] + tab["c"]
-        self.turn[slot[keep]] ^= 1
-        for sid in slot[~keep]:
-            self.is_open[sid] = False
-            self.free.append(int(sid))
+    commit = SlotState.commit_rows
 
 
-class _PoolBase:
-    """What the stream pools share: the slots and their state (`PoolState`), the packing of a call's chunks, the batches of at
-    most max_batch windows, the packed result.  A subclass supplies the model check, `_gather` and `_emit`."""
+class _PoolBase(StreamSurface):
+    """What the window pools share: the slots and their state (`PoolState`), the batches of at most max_batch windows, the packed
+    result; `close(sid, x=None)` returns the rest of a stream, (leads, T - F(n)).  A subclass supplies the model check, `_gather`
+    and `_emit`."""
 
     def _setup(self, model, eng, leads, inner_leads, capacity, overlap, grid):
         self.model, self.eng, self.leads = model, eng, leads
@@ -555,23 +515,8 @@ class _PoolBase:
         self.windows_run = 0                                   # windows the pool has run so far
         model.eval()
 
-    open_streams = property(lambda self: tuple(int(s) for s in np.flatnonzero(self.state.is_open)))
-
-    def open(self):
-        """-> the sid of a new stream (a free slot); RalError when `capacity` streams are open"""
-        return self.state.open()
-
-    def samples_in(self, sid):
-        if not (isinstance(sid, (int, np.integer)) and 0 <= sid < self.capacity and self.state.is_open[sid]):
-            raise _lib.RalError(f"{type(self).__name__}.samples_in: {sid!r} is not an open stream")
-        return int(self.state.n[sid])
-
     def _ready(self, what):
         """raise if the model cannot run a call now"""
-
-    def close(self, sid, x=None):
-        """end one stream, with an optional last chunk -> the rest of it, (leads, T - F(n))"""
-        return self.push({} if x is None else {sid: x}, close=(sid,))[sid]
 
     @torch.no_grad()
     def push(self, chunks, close=()):
@@ -580,23 +525,11 @@ class _PoolBase:
         device work; a call that raises has changed nothing."""
         self._ready("push")
         dev = self.eng.device
-        xs = {sid: x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, dtype=np.float32))
-              for sid, x in chunks.items()}
+        xs = as_chunks(chunks)
         sids, tab, last = self.state.plan({sid: tuple(x.shape) for sid, x in xs.items()}, tuple(close))
         lib, leads, R = _lib.lib(), self.leads, len(tab)
-        x_total, out_total = int(tab["c"].sum()), int(tab["m"].sum())
-        total = int(tab["w_off"][-1] + tab["nw"][-1])
-        # the chunks, packed: row r's (leads, c) at x_off * leads
-        xp = torch.empty(max(x_total, 1) * leads, dtype=torch.float32, device=dev)
-        flat = [x.reshape(-1) for x in xs.values() if x.numel()]
-        if flat:
-            if all(not f.is_cuda for f in flat) or all(f.is_cuda and f.dtype == torch.float32 for f in flat):
-                xp[:x_total * leads].copy_(flat[0] if len(flat) == 1 else torch.cat(flat), non_blocking=True)
-            else:
-                o = 0
-                for f in flat:
-                    xp[o:o + f.numel()].copy_(f, non_blocking=True)
-                    o += f.numel()
+        out_total, total = int(tab["m"].sum()), int(tab["w_off"][-1] + tab["nw"][-1])
+        xp, x_total, _ = pack_chunks(xs, leads, dev)
         out = torch.empty(max(out_total, 1) * leads, dtype=torch.float32, device=dev)
         batch = min(self.eng.max_batch, max(total, 1))
         if self.win is None or self.win.shape[0] < batch:

@@ -33,6 +33,7 @@ import torch
 from . import _lib
 from .infer import LivePool, NewRALELivePool, StreamingDenoiser
 from .model import NewRALE, _ptr, _stream
+from .pools import SlotState, StreamSurface, as_chunks, pack_chunks
 
 MODEL_RATE = 360
 
@@ -155,11 +156,10 @@ class Resampler:
         return y
 
 
-class RatePoolState:
-    """The host side of a `ResamplerPool`, without a device: which slots hold an open stream, how many samples each has received
-    and which of its two history planes is current.  `plan` checks the arguments of a call and builds its table
-    (`_lib.RATE_ROW`) without changing anything; `commit` applies a planned call.  After n samples a stream has been given
-    `frontier(n)` outputs; closing it at T gives the rest, up to `length(T)`."""
+class RatePoolState(SlotState):
+    """The host side of a `ResamplerPool`, without a device: the slots (`SlotState`) and the conversion.  `plan` checks the
+    arguments of a call and builds its table (`_lib.RATE_ROW`) without changing anything; `commit` applies a planned call.
+    After n samples a stream has been given `frontier(n)` outputs; closing it at T gives the rest, up to `length(T)`."""
 
     def __init__(self, up, down, leads, capacity, name="ResamplerPool"):
         self.up, self.down = _pair(up, down)
@@ -168,14 +168,8 @@ class RatePoolState:
             rate_check(self.up, self.down)
         if not isinstance(leads, numbers.Integral) or leads < 1:
             raise _lib.RalError(f"{name}: leads must be >= 1")
-        if not isinstance(capacity, numbers.Integral) or capacity < 1:
-            raise _lib.RalError(f"{name}: capacity must be >= 1")
-        self.leads, self.capacity, self.name = int(leads), int(capacity), name
+        super().__init__(capacity, leads, name)
         self.hist_len = rate_taps_per_output(self.up, self.down)      # 2 half / up + 1
-        self.n = np.zeros(self.capacity, dtype=np.int64)
-        self.turn = np.zeros(self.capacity, dtype=np.int32)
-        self.is_open = np.zeros(self.capacity, dtype=bool)
-        self.free = list(range(self.capacity - 1, -1, -1))      # (slot 0 first)
 
     def frontier(self, n):
         return int(n) if self.identity else rate_frontier(n, self.up, self.down)
@@ -183,47 +177,14 @@ class RatePoolState:
     def length(self, T):
         return int(T) if self.identity else rate_length(T, self.up, self.down)
 
-    def open(self):
-        if not self.free:
-            raise _lib.RalError(f"{self.name}.open: all {self.capacity} slots hold an open stream")
-        sid = self.free.pop()
-        self.n[sid], self.is_open[sid] = 0, True
-        return sid
-
-    def _is_open(self, sid):
-        return isinstance(sid, (int, np.integer)) and not isinstance(sid, bool) and 0 <= sid < self.capacity \
-            and bool(self.is_open[sid])
-
     def plan(self, shapes, close=()):
         """shapes {sid: shape of its chunk, (leads, c) with c >= 0}, close: the sids that end with this call -> (sids in row
         order, table); raises RalError for a bad argument"""
-        name = self.name
-        sids = list(shapes)
-        for sid in close:
-            if sid not in sids:
-                sids.append(sid)
-        if not sids:
-            raise _lib.RalError(f"{name}.push: nothing to do (no chunk and no stream to close)")
-        for sid in sids:
-            if not self._is_open(sid):
-                raise _lib.RalError(f"{name}.push: {sid!r} is not an open stream")
-        if len(sids) * self.leads > 65535:
-            raise _lib.RalError(f"{name}.push: more than 65535 (stream, lead) pairs in one call")
-        lens = np.zeros(len(sids), dtype=np.int64)
-        for r, (sid, shape) in enumerate(shapes.items()):
-            if len(shape) != 2 or shape[0] != self.leads:
-                raise _lib.RalError(f"{name}.push: stream {sid}: expected a chunk of shape ({self.leads}, samples), got "
-                                    f"{tuple(shape)}")
-            lens[r] = shape[1]
-        if np.any(lens > 0x3fffffff):
-            raise _lib.RalError(f"{name}.push: a chunk of more than 2^30 - 1 samples")
-        slot = np.asarray(sids, dtype=np.int64)
-        ends = np.isin(slot, np.asarray(list(close), dtype=np.int64))
-        n0 = self.n[slot]
+        sids, slot, lens, ends, n0 = self.named(shapes, close, 65535 // self.leads, "65535 (stream, lead) pairs")
         n1 = n0 + lens
         if np.any(ends & (n1 < 1)):
             r = int(np.argmax(ends & (n1 < 1)))
-            raise _lib.RalError(f"{name}.push: stream {sids[r]} would end without a single sample")
+            raise _lib.RalError(f"{self.name}.push: stream {sids[r]} would end without a single sample")
         m0 = np.asarray([self.frontier(v) for v in n0], dtype=np.int64)
         m1 = np.asarray([self.length(v) if e else self.frontier(v) for v, e in zip(n1, ends)], dtype=np.int64)
         tab = np.zeros(len(sids), dtype=_lib.RATE_ROW)
@@ -233,21 +194,10 @@ class RatePoolState:
         return sids, tab
 
     def commit(self, tab):
-        slot, keep = tab["slot"], (tab["flags"] & _lib.POOL_KEEP) != 0
-        self.n[slot] = tab["n0"] + tab["c"]
-        if not self.identity:
-            self.turn[slot[keep]] ^= 1
-        for sid in slot[~keep]:
-            self.is_open[sid] = False
-            self.free.append(int(sid))
+        self.commit_rows(tab, flip=not self.identity)      # the identity keeps no history: its planes never take turns
 
 
-def _as_chunks(chunks):
-    return {sid: x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, dtype=np.float32))
-            for sid, x in chunks.items()}
-
-
-class ResamplerPool:
+class ResamplerPool(StreamSurface):
     """Up to `capacity` independent streams of `leads` leads from `fs_in` to `fs_out`, chunk by chunk (`ral_rate_pool`).
     `open()` returns a stream id; `push(chunks, close=())` takes {sid: (leads, c)} (c >= 0, host or device) for any subset of the
     open streams, ends the streams listed in `close`, and returns {sid: (leads, m)} on the device: after n samples a stream has
@@ -269,30 +219,15 @@ class ResamplerPool:
             self.bank = torch.from_numpy(rate_bank(up, down).astype(np.float32)).to(self.device)
             self.hist = torch.zeros(2, self.capacity, self.leads, self.hist_len, dtype=torch.float32, device=self.device)
 
-    open_streams = property(lambda self: tuple(int(s) for s in np.flatnonzero(self.state.is_open)))
-
-    def open(self):
-        """-> the sid of a new stream (a free slot); RalError when `capacity` streams are open"""
-        return self.state.open()
-
-    def samples_in(self, sid):
-        if not self.state._is_open(sid):
-            raise _lib.RalError(f"{type(self).__name__}.samples_in: {sid!r} is not an open stream")
-        return int(self.state.n[sid])
-
     def plan(self, shapes, close=()):
         return self.state.plan(shapes, close)
 
     def commit(self, tab):
         self.state.commit(tab)
 
-    def close(self, sid, x=None):
-        """end one stream, with an optional last chunk -> the rest of it"""
-        return self.push({} if x is None else {sid: x}, close=(sid,))[sid]
-
     @torch.no_grad()
     def push(self, chunks, close=()):
-        xs = _as_chunks(chunks)
+        xs = as_chunks(chunks)
         sids, tab = self.state.plan({sid: tuple(x.shape) for sid, x in xs.items()}, tuple(close))
         return self.run(xs, sids, tab)
 
@@ -303,17 +238,9 @@ class ResamplerPool:
             self.state.commit(tab)
             empty = torch.empty(leads, 0, dtype=torch.float32, device=dev)
             return {sid: xs[sid].to(device=dev, dtype=torch.float32) if sid in xs else empty for sid in sids}
-        x_total, out_total = int(tab["c"].sum()), int(tab["m"].sum())
+        out_total = int(tab["m"].sum())
         with torch.cuda.device(dev):
-            xp = torch.empty(max(x_total, 1) * leads, dtype=torch.float32, device=dev)
-            flat = [x.reshape(-1) for x in xs.values() if x.numel()]      # row r's (leads, c) at x_off * leads
-            if flat and (all(not f.is_cuda for f in flat) or all(f.is_cuda and f.dtype == torch.float32 for f in flat)):
-                xp[:x_total * leads].copy_(flat[0] if len(flat) == 1 else torch.cat(flat), non_blocking=True)
-            else:
-                o = 0
-                for f in flat:
-                    xp[o:o + f.numel()].copy_(f, non_blocking=True)
-                    o += f.numel()
+            xp, x_total, _ = pack_chunks(xs, leads, dev)
             out = torch.empty(max(out_total, 1) * leads, dtype=torch.float32, device=dev)
             tab_dev = torch.empty(len(tab) * tab.itemsize, dtype=torch.uint8, device=dev)
             _lib.check(_lib.lib().ral_rate_pool(_ptr(self.hist), _ptr(xp), x_total, tab.ctypes.data, len(tab), _ptr(tab_dev), 1,
@@ -370,7 +297,7 @@ class RateStreamingDenoiser:
         return score_records(clean, self.denoise(noisy), noisy, self.window if window is None else window)
 
 
-class RateLivePool:
+class RateLivePool(StreamSurface):
     """`LivePool` for streams sampled at `fs`: the same surface (`open`, `push`, `close`, `samples_in`, `open_streams`) with
     chunks at `fs` in and samples at `fs` out.  Three pools in a chain: `ResamplerPool` (fs -> fs_model), `LivePool` or
     `NewRALELivePool` by the model's type, `ResamplerPool` (fs_model -> fs).  Concatenated per stream from `open` to `close`, the
@@ -401,17 +328,13 @@ class RateLivePool:
     def samples_in(self, sid):
         return self.front.samples_in(sid)
 
-    def close(self, sid, x=None):
-        """end one stream, with an optional last chunk -> the rest of it"""
-        return self.push({} if x is None else {sid: x}, close=(sid,))[sid]
-
     @torch.no_grad()
     def push(self, chunks, close=()):
         """chunks {sid: (leads, c) samples at fs, host or device}, close: the sids that end with this call -> {sid: the samples
         at fs that became final, (leads, m) on the device} for every sid named"""
         name = type(self).__name__
         self.inner._ready("push")
-        xs = _as_chunks(chunks)
+        xs = as_chunks(chunks)
         close = tuple(close)
         for sid, x in xs.items():
             if x.dim() == 2 and x.shape[1] == 0 and sid not in close:

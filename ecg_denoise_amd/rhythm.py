@@ -43,7 +43,8 @@ import torch
 from . import _lib, scoring
 from .beats import MODEL_RATE, BeatDetector, BeatPool, BeatPoolState, Beats, _lag, _round
 from .model import _ptr, _stream
-from .rate import _as_chunks, _rate
+from .pools import StreamSurface, as_chunks, pack_chunks
+from .rate import _rate
 
 K, MIN_REF = _lib.RHYTHM_K, _lib.RHYTHM_MIN_REF
 # the LDS budget of ral_rhythm.hip (rhythm_geom there): per lead a wave stages the windows of K neighbours, the template, the
@@ -218,7 +219,7 @@ class RhythmPoolState:
         self.done[slot] = np.where(tab["ne"] > 0, tab["e0"] + tab["ne"], tab["e0"])
 
 
-class BeatClassPool:
+class BeatClassPool(StreamSurface):
     """Beat classes of up to `capacity` independent live streams of `leads` leads at rate `fs`, chunk by chunk: it owns a
     `BeatPool` (`beats`) and classifies what that detects (`ral_rhythm_pool`).  `open()` returns a stream id;
     `push(chunks, close=())` takes {sid: (leads, c)} (c >= 0, host or device) for any subset of the open streams, ends the streams
@@ -244,10 +245,6 @@ class BeatClassPool:
 
     open_streams = property(lambda self: self.beats.open_streams)
 
-    def open(self):
-        """-> the sid of a new stream (a free slot); RalError when `capacity` streams are open"""
-        return self.state.open()
-
     def samples_in(self, sid):
         return self.beats.samples_in(sid)
 
@@ -256,26 +253,15 @@ class BeatClassPool:
         self.beats.samples_in(sid)
         return int(self.state.nb[sid])
 
-    def close(self, sid, x=None):
-        """end one stream, with an optional last chunk -> its remaining beats"""
-        return self.push({} if x is None else {sid: x}, close=(sid,))[sid]
-
     @torch.no_grad()
     def push(self, chunks, close=()):
         close = tuple(close)
-        xs = _as_chunks(chunks)
+        xs = as_chunks(chunks)
         sids, btab = self.state.plan({sid: tuple(x.shape) for sid, x in xs.items()}, close)      # (raises before anything changes)
         dev, leads, lib = self.device, self.leads, _lib.lib()
-        x_total = int(btab["c"].sum())
         with torch.cuda.device(dev):
-            xp = torch.empty(max(x_total, 1) * leads, dtype=torch.float32, device=dev)
-            packed, o = {}, 0
-            for sid, x in xs.items():                   # row r's (leads, c) at x_off * leads; the detector gets these views
-                n = x.numel()
-                xp[o:o + n].copy_(x.reshape(-1), non_blocking=True)
-                packed[sid] = xp[o:o + n].view(leads, x.shape[1])
-                o += n
-            new = self.beats.push(packed, close=close)
+            xp, x_total, _ = pack_chunks(xs, leads, dev)
+            new = self.beats.run(xp, x_total, sids, btab)      # the detector and the classifier read the same buffer
             tab = self.state.table(btab, [new[sid].numel() for sid in sids])
             new_total, out_total = int(tab["m"].sum()), int(tab["ne"].sum())
             new_pos = torch.cat([new[sid] for sid in sids]) if new_total else torch.zeros(1, dtype=torch.int64, device=dev)
