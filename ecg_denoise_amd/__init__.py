@@ -3,7 +3,7 @@
 Python here is host glue only: device memory and streams come from PyTorch-ROCm, all
 arithmetic runs in hand-written HIP kernels behind the C ABI of include/ralenet.h."""
 from ._lib import RalError, build  # noqa: F401
-from .baselines import wavelet_denoise  # noqa: F401
+from .baselines import ClassicalDenoiser, fft_denoise, wavelet_denoise  # noqa: F401
 import os as _os
 
 # The step uses four HIP streams of its own (two micro-batch chains and their weight-gradient side streams); a data-parallel

@@ -158,6 +158,8 @@ _SIGS = {
     "ral_set_option": (C.c_int, [_VP, C.c_char_p, C.c_int]),
     "ral_global_option": (C.c_int, [C.c_char_p, C.c_longlong]),
     "ral_wavelet_denoise": (C.c_int, [_VP, _VP, C.c_int64, C.c_int, C.c_float, _VP]),
+    "ral_fft_denoise_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
+    "ral_fft_denoise": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int, C.c_int, C.c_float, _VP, _VP]),
     "ral_profile_select": (C.c_int, [_VP, C.c_char_p]),
     "ral_profile_read": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "ral_profile_timeline": (C.c_int, [_VP, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int64)]),

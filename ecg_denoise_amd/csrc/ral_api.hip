@@ -1850,6 +1850,36 @@ int ral_wavelet_denoise(const float* x, float* y, int64_t rows, int L, float thr
   return 0;
 }
 
+static int fft_denoise_counts(const char* who, int64_t groups, int rows_per_group, int L) {
+  if (groups < 0 || rows_per_group < 1)
+    return fail("%s: need groups >= 0 and rows_per_group >= 1 (groups=%lld rows_per_group=%d)", who, (long long)groups, rows_per_group);
+  if (groups > 0x7fffffffLL / rows_per_group)
+    return fail("%s: need groups * rows_per_group < 2^31 (groups=%lld rows_per_group=%d)", who, (long long)groups, rows_per_group);
+  if (fft_denoise_scratch_bytes(0, 1, L) < 0) return fail("%s: L=%d is not supported: need %s", who, L, fft_denoise_rule());
+  return 0;
+}
+
+int64_t ral_fft_denoise_scratch_bytes(int64_t groups, int rows_per_group, int L) {
+  if (fft_denoise_counts("fft_denoise_scratch_bytes", groups, rows_per_group, L)) return -1;
+  return (int64_t)fft_denoise_scratch_bytes((long long)groups, rows_per_group, L);
+}
+
+int ral_fft_denoise(const float* x, float* y, int32_t* kept, int64_t groups, int rows_per_group, int L, float threshold,
+                    void* scratch, ral_stream s) {
+  if (!x || !y) return fail("fft_denoise: null pointer (x=%p y=%p)", (const void*)x, (void*)y);
+  if (fft_denoise_counts("fft_denoise", groups, rows_per_group, L)) return -1;
+  if (!(threshold >= 0.f)) return fail("fft_denoise: the threshold factor must be non-negative (got %g)", (double)threshold);
+  const long long need = fft_denoise_scratch_bytes((long long)groups, rows_per_group, L);
+  if (need > 0 && !scratch)
+    return fail("fft_denoise: null scratch, %lld bytes are needed (groups=%lld rows_per_group=%d L=%d)", need, (long long)groups,
+                rows_per_group, L);
+  const int rc = launch_fft_denoise(x, y, kept, (long long)groups, rows_per_group, L, threshold, scratch, (hipStream_t)s);
+  if (rc == -2) return fail("fft_denoise: %s", hipGetErrorString(hipGetLastError()));
+  if (rc) return fail("fft_denoise: refused (groups=%lld rows_per_group=%d L=%d)", (long long)groups, rows_per_group, L);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 static int check_attn_args(int N, int H, int Len, int B) {
   if (N < 16 || N % 16 != 0 || N > 1024) return fail("attention: N must be a multiple of 16 in [16, 1024] (got %d)", N);
   if (H < 1 || (H & (H - 1)) != 0 || H > 32) return fail("attention: H must be a power of two <= 32 (got %d)", H);

@@ -210,3 +210,9 @@ void launch_resample_dw(int D, bool sep, const float* dy, const float* x, const 
 
 // db8 wavelet-threshold baseline (ral_wavelet.hip); non-zero = rejected arguments
 int launch_wavelet_denoise(const float* x, float* y, long long rows, int L, float threshold, hipStream_t s);
+// FFT-threshold baseline (ral_fft.hip).  scratch bytes: 0 = one launch, -1 = refused length or counts; launch: -1 = refused
+// arguments (fft_denoise_rule names the lengths), -2 = a HIP error
+const char* fft_denoise_rule();
+long long fft_denoise_scratch_bytes(long long groups, int rows_per_group, int L);
+int launch_fft_denoise(const float* x, float* y, int32_t* kept, long long groups, int rows_per_group, int L, float threshold,
+                       void* scratch, hipStream_t s);

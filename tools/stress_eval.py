@@ -26,9 +26,14 @@ the denoised records at the clean records' detections, and accuracy, precision a
 decisions against the clean ones (`evaluate_rhythm`; NaN where a ratio has no denominator).  Without the flag the output is
 what it was.
 
+`--fft` adds the reference's other classical baseline, the model "fft" of test_cls.py: `fft_denoise` on the same noisy records
+through `ClassicalDenoiser("fft", --fft-L)` (windows of `--fft-L` samples, default 1000 as in test_cls.py:246; the leads of a
+window share one cutoff), scored like the wavelet row: per cell one more reference-format line and an "fft" entry in the JSON.
+Without the flag the output is what it was.
+
     python tools/stress_eval.py [--model full|nra|mlp|unet|acdae|danet|newrale] [--ckpt state_dict.pth] [--L 512]
                                 [--records 4] [--T 65000] [--overlap 0] [--batch 4096] [--time-shapes ...] [--reps 5] [--beats]
-                                [--classes]
+                                [--classes] [--fft] [--fft-L 1000]
 """
 import argparse
 import json
@@ -41,7 +46,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from ecg_denoise_amd import (ACDAE, DANet, NewRALE, RALENet, UNet, evaluate_beats, evaluate_rhythm, mix_records,  # noqa: E402
+from ecg_denoise_amd import (ACDAE, ClassicalDenoiser, DANet, NewRALE, RALENet, UNet, evaluate_beats, evaluate_rhythm, mix_records,  # noqa: E402
                              score_records, synth, wavelet_denoise)
 from ecg_denoise_amd.data import NOISE_TYPES, TRUE_NOISE  # noqa: E402
 from ecg_denoise_amd.infer import StreamingDenoiser  # noqa: E402
@@ -124,6 +129,7 @@ def grid(args, model, name):
         nrow = args.T // Lw * Lw                      # the baseline takes rows of an even length <= 8192
         wav = wavelet_denoise(noisy[..., :nrow].reshape(R, leads, nrow // Lw, Lw).reshape(-1, Lw)).reshape(R, leads, nrow)
         sw = score_records(clean[..., :nrow].contiguous(), wav, noisy[..., :nrow].contiguous(), window=sd.L)
+        sf = score_records(clean, ClassicalDenoiser("fft", args.fft_L, device=DEV).denoise(noisy), noisy, window=sd.L) if args.fft else None
         ev = evaluate_beats(sd, rec, noise, snrs, offsets=offsets) if args.beats else None
         evc = evaluate_rhythm(sd, rec, noise, snrs, offsets=offsets) if args.classes else None
         for i, snr in enumerate(TRUE_NOISE):
@@ -132,6 +138,10 @@ def grid(args, model, name):
             lines.append(a.output_line(name, 0, kind, snr))
             lines.append(b.output_line("wavelet", 0, kind, snr))
             cells.append({"noise": kind, "intensity": snr, "model": _row(a), "wavelet": _row(b)})
+            if sf is not None:
+                f = _subset(sf, idx, sd.L)
+                lines.append(f.output_line("fft", 0, kind, snr))
+                cells[-1]["fft"] = _row(f)
             if ev is not None:
                 bn, bd = (type(v)(v.counts[idx], v.tol).pooled for v in (ev.noisy, ev.denoised))
                 cells[-1]["beats"] = {"noisy": bn, "denoised": bd}
@@ -202,6 +212,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--beats", action="store_true", help="add Se / +P / F1 of beat detection, noisy and denoised")
     ap.add_argument("--classes", action="store_true", help="add beat classes (N / V / S) and acc / precision / F1, noisy and denoised")
+    ap.add_argument("--fft", action="store_true", help="add the FFT-threshold baseline (the model 'fft') beside the wavelet one")
+    ap.add_argument("--fft-L", type=int, default=1000)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("stress_eval: needs a HIP device")
