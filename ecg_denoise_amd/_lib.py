@@ -37,6 +37,12 @@ class RhythmGeom(C.Structure):
     _fields_ = [("wb", C.c_int32), ("sa", C.c_int32), ("c0", C.c_float), ("r0", C.c_float)]
 
 
+class HrvGeom(C.Structure):
+    """ral_hrv_geom: the HRV window's lengths in samples, its bin count, min_nn and the rate"""
+    _fields_ = [("W", C.c_int32), ("lo_n", C.c_int32), ("hi_n", C.c_int32), ("t50", C.c_int32), ("F", C.c_int32),
+                ("min_nn", C.c_int32), ("fs", C.c_double)]
+
+
 # ral_pool_row (include/ralenet.h): one row of a stream pool's per-call table, as a numpy record
 POOL_ROW = np.dtype([("n0", "<i8"), ("T", "<i8"), ("k0", "<i8"), ("lo", "<i8"), ("x_off", "<i8"), ("out_off", "<i8"),
                      ("w_off", "<i8"), ("slot", "<i4"), ("c", "<i4"), ("nw", "<i4"), ("m", "<i4"), ("turn", "<i4"),
@@ -53,6 +59,8 @@ BEAT_ROW = np.dtype([("n0", "<i8"), ("T", "<i8"), ("d0", "<i8"), ("x_off", "<i8"
 RHYTHM_ROW = np.dtype([("n0", "<i8"), ("T", "<i8"), ("x_off", "<i8"), ("new_off", "<i8"), ("out_off", "<i8"), ("nb", "<i8"),
                        ("e0", "<i8"), ("slot", "<i4"), ("c", "<i4"), ("m", "<i4"), ("ne", "<i4"), ("turn", "<i4"), ("flags", "<i4")])
 RHYTHM_K, RHYTHM_MIN_REF = 8, 3
+# ral_hrv_row: one window of one record
+HRV_ROW = np.dtype([("w0", "<i8"), ("w1", "<i8"), ("rec", "<i4"), ("pad_", "<i4")])
 
 def build(jobs=8, verbose=False):
     """Compile every HIP source for gfx950 into ecg_denoise_amd/libralenet.so (in-tree)."""
@@ -149,6 +157,8 @@ _SIGS = {
                                      _VP]),
     "ral_rhythm_pool": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int, _VP, C.c_int, C.c_int64, C.c_int, C.POINTER(RhythmGeom),
                                   C.c_int, _VP, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
+    "ral_hrv_windows": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int64, _VP, C.c_int, C.POINTER(HrvGeom), _VP, _VP,
+                                  _VP, _VP, _VP]),
     "ral_attention_forward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
     "ral_attention_backward_scratch_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "ral_attention_plan": (C.c_int, [C.c_int] * 8 + [C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),

@@ -1841,6 +1841,27 @@ int ral_rhythm_pool(const float* hist, const float* x, int64_t x_total, const ra
   return 0;
 }
 
+int ral_hrv_windows(const int32_t* pos, const int32_t* label_or_null, const int32_t* count, int64_t R, int64_t cap,
+                    const ral_hrv_row* table, int64_t rows, ral_hrv_row* table_dev, int upload, const ral_hrv_geom* geom,
+                    const int32_t* band, int32_t* counts, float* stats, float* psd_or_null, ral_stream s) {
+  if (!pos || !count || !table_dev || (upload && !table) || !geom || !band || !counts || !stats)
+    return fail("hrv_windows: null pointer");
+  const char* why = nullptr;
+  long long bad = -1;
+  const int rc = launch_hrv_windows(pos, label_or_null, count, (long long)R, (long long)cap, table, (long long)rows, table_dev,
+                                    upload, geom, band, counts, stats, psd_or_null, (hipStream_t)s, &why, &bad);
+  if (rc == -1) {
+    char row[40] = "";
+    if (bad >= 0) snprintf(row, sizeof(row), " in row %lld", bad);
+    return fail("hrv_windows: need %s%s (R=%lld cap=%lld rows=%lld W=%d lo_n=%d hi_n=%d t50=%d F=%d min_nn=%d fs=%g)", why, row,
+                (long long)R, (long long)cap, (long long)rows, geom->W, geom->lo_n, geom->hi_n, geom->t50, geom->F, geom->min_nn,
+                geom->fs);
+  }
+  if (rc) return fail("hrv_windows: copying the table to the device failed");
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 int ral_wavelet_denoise(const float* x, float* y, int64_t rows, int L, float threshold, ral_stream s) {
   if (!x || !y) return fail("wavelet_denoise: null pointer");
   if (!(threshold >= 0.f)) return fail("wavelet_denoise: the threshold factor must be non-negative (got %g)", (double)threshold);

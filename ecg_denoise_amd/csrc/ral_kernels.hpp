@@ -137,7 +137,12 @@ int launch_beat_pool(float* hist, const float* x, long long x_total, const ral_b
                      const char** why, int* bad);
 int launch_beat_match(const int* ref, const int* nref, long long ref_cap, const int* det, const int* ndet, long long det_cap,
                       long long R, long long tol, long long* out, hipStream_t s, const char** why);
-// beat classes (ral_rhythm.hip; ral_rhythm_records / ral_rhythm_pool): the same conventions as beat detection above
+// heart-rate variability (ral_hrv.hip; ral_hrv_windows): -1 with *why (and *bad, the table row, or -1) for a refusal, -2 when the
+// table's copy failed
+int launch_hrv_windows(const int* pos, const int* label, const int* count, long long R, long long cap, const ral_hrv_row* tab,
+                       long long rows, ral_hrv_row* tab_dev, int upload, const ral_hrv_geom* geom, const int* band, int* counts,
+                       float* stats, float* psd, hipStream_t s, const char** why, long long* bad);
+// beat classes (ral_rhythm.hip;ral_rhythm_records / ral_rhythm_pool): the same conventions as beat detection above
 long long rhythm_pool_scratch_bytes(long long beats, int leads, const ral_rhythm_geom* geom, const char** why);
 int launch_rhythm_records(const float* x, long long R, int leads, long long T, const ral_rhythm_geom* geom, const int* peaks,
                           const int* count, long long cap, int* label, float* corr, float* rr, hipStream_t s, const char** why);

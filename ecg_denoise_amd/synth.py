@@ -175,6 +175,44 @@ def make_records_with_rhythm(R, leads, T, seed=2023, p_v=0.12, p_s=0.0):
     return x.astype(np.float32), beats, labels
 
 
+def make_beats_with_hrv(R, T, fs=360, seed=2023, lf=0.04, hf=0.02, p_v=0.0, p_s=0.0, bpm=(55.0, 95.0)):
+    """-> (beats, labels): per record the strictly ascending sample indices in [0, T) of the beats of a rhythm with a known
+    variability, at rate `fs`, and per beat its label, 0 normal (N), 1 ventricular (V), 2 premature with a normal shape (S).  No
+    signal is generated.  Draws of its own (the other generators keep theirs).  Per record a mean heart rate from `bpm` (beats
+    per minute, uniform) gives rr0, and a sinus beat at time t is followed by the next after
+    rr0 + lf sin(2 pi 0.1 t + a) + hf sin(2 pi 0.25 t + b) seconds (a, b uniform phases): `lf` and `hf` are the amplitudes, in
+    seconds, of the modulation at 0.1 Hz (the LF band) and at 0.25 Hz (the HF band), so the NN series carries about lf^2 / 2 and
+    hf^2 / 2 of power there.  A beat becomes V with probability `p_v`, otherwise S with probability `p_s` - never the first beat
+    and never directly after a V or an S; it comes at 0.55 - 0.75 of the interval and the sinus beat it pre-empts is dropped (a
+    compensatory pause), as in `make_records_with_rhythm`."""
+    rng = np.random.default_rng(seed)
+    T, fs = int(T), float(fs)
+    beats, labels = [], []
+    for _ in range(R):
+        rr0 = 60.0 / rng.uniform(*bpm)
+        a, b = rng.uniform(0, 2 * np.pi, 2)
+        t, at, lab, was_early = rng.uniform(0, rr0), [], [], True
+        while t * fs < T:
+            p = int(np.floor(t * fs + 0.5))
+            if p < T and (not at or p > at[-1]):
+                at.append(p)
+                lab.append(0)
+            gap = rr0 + lf * np.sin(2 * np.pi * 0.1 * t + a) + hf * np.sin(2 * np.pi * 0.25 * t + b)
+            u, kind = rng.uniform(0.55, 0.75), rng.uniform()
+            early = len(at) > 0 and not was_early and kind < p_v + p_s
+            if early:
+                pe = int(np.floor((t + u * gap) * fs + 0.5))
+                if at[-1] < pe < T:
+                    at.append(pe)
+                    lab.append(1 if kind < p_v else 2)
+                gap *= 2
+            was_early = early
+            t += gap
+        beats.append(at)
+        labels.append(lab)
+    return beats, labels
+
+
 def make_noise_record(kind, leads, Tn, seed=2023):
     """-> one synthetic noise record, float32 (leads, Tn), of kind bw / ma / em / emb (`noise`): the stand-in for an NSTDB
     record that `mix_records` cuts its segments from."""

@@ -1,0 +1,353 @@
+"""HRV on the device: `HrvAnalyzer.analyse` against the numpy oracle (tests/hrv_util.py, which states the tolerances), `HrvPool`
+against the three-call composition on the complete record bit for bit, `evaluate_hrv` against its explicit composition, and
+the refusals of the C entry point.  Every comparison prints its worst spectral error as a fraction of its bound."""
+import ctypes
+import functools
+from fractions import Fraction
+
+import numpy as np
+import pytest
+import torch
+
+import hrv_util as U
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+SHORT = dict(win_s=30, hop_s=10, min_nn=8)
+_MODELS = {}
+
+
+def _geometry(fs, **kw):
+    from ecg_denoise_amd import hrv_geometry
+    return hrv_geometry(fs, **kw)
+
+
+@functools.lru_cache(maxsize=None)
+def _short(fs):
+    """-> (T, beats, labels) of 4 lists of 120 s at rate fs with V and S beats"""
+    from ecg_denoise_amd import synth
+    T = int(120 * fs)
+    beats, labels = synth.make_beats_with_hrv(4, T, fs=float(fs), seed=21, p_v=0.06, p_s=0.06)
+    assert all(1 in l and 2 in l for l in labels)
+    return T, beats, labels
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int32) if t.dtype == torch.float32 else t
+
+
+def _same_bits(a, b):
+    ok = torch.equal(a.counts, b.counts) and torch.equal(_bits(a.stats), _bits(b.stats)) and np.array_equal(a.index, b.index)
+    return ok and ((a.psd is None and b.psd is None) or torch.equal(_bits(a.psd), _bits(b.psd)))
+
+
+def _check(h, beats, labels, T, g, what):
+    """every window of an `HrvWindows` over whole records against the oracle -> (windows, windows with a spectrum)"""
+    assert h.counts.dtype == torch.int32 and h.stats.dtype == torch.float32 and h.counts.is_cuda and h.stats.is_cuda
+    assert tuple(h.counts.shape) == (len(h), 4) and tuple(h.stats.shape) == (len(h), 10) and tuple(h.index.shape) == (len(h), 2)
+    assert h.psd is None or (tuple(h.psd.shape) == (len(h), g["F"]) and h.psd.dtype == torch.float32)
+    counts, stats = h.counts.cpu().numpy(), h.stats.cpu().numpy()
+    psd = None if h.psd is None else h.psd.cpu().numpy()
+    at, worst, spectra = 0, 0.0, 0
+    for r in range(len(beats)):
+        for w, o in enumerate(U.oracle_record(beats[r], None if labels is None else labels[r], T, g)):
+            assert h.index[at].tolist() == [r, w]
+            worst = max(worst, U.compare(counts[at], stats[at], None if psd is None else psd[at], o, g))
+            spectra += o["m"] >= g["min_nn"]
+            at += 1
+    assert at == len(h)
+    print(f"\n[hrv] {what}: {at} windows, {spectra} with a spectrum, worst spectral error {worst:.4f} of its bound")
+    return at, spectra
+
+
+def _analyse(fs, beats, T, classes=None, psd=False, **kw):
+    from ecg_denoise_amd import HrvAnalyzer
+    return HrvAnalyzer(fs, device=DEV, **kw).analyse(beats, T, classes, psd)
+
+
+# ------------------------------------------------------------------------------------------------ 1. against the oracle
+@pytest.mark.parametrize("fs", [360, 500, Fraction(725, 2)])
+def test_short_windows_equal_the_oracle(fs):
+    """4 lists of 120 s with V and S beats, windows of 30 s every 10 s, min_nn = 8: with labels and without, with psd and without"""
+    T, beats, labels = _short(fs)
+    g = _geometry(fs, **SHORT)
+    for lab in (labels, None):
+        h = _analyse(fs, beats, T, lab, psd=True, **SHORT)
+        n, spectra = _check(h, beats, lab, T, g, f"short windows at {fs} Hz, {'labels' if lab else 'no labels'}")
+        assert n == 40 and spectra == 40
+        h0 = _analyse(fs, beats, T, lab, psd=False, **SHORT)
+        assert h0.psd is None and torch.equal(h0.counts, h.counts) and torch.equal(_bits(h0.stats), _bits(h.stats))
+    with_lab, without = _analyse(fs, beats, T, labels, **SHORT), _analyse(fs, beats, T, None, **SHORT)
+    assert bool((with_lab.n_nn <= without.n_nn).all()) and bool((with_lab.n_nn < without.n_nn).any())      # V and S beats cost intervals
+    assert torch.equal(with_lab.counts[:, 0], without.counts[:, 0])
+    row = with_lab.tolist()[3]
+    assert row["record"] == 0 and row["window"] == 3 and row["n_nn"] == int(with_lab.n_nn[3]) and row["hr"] == float(with_lab.hr[3])
+    assert torch.equal(with_lab.lf_hf, with_lab.stats[:, 9]) and torch.equal(with_lab.sdnn, with_lab.stats[:, 2])
+
+
+# ------------------------------------------------------------------------------------------------ 2. the long window
+def test_the_long_window():
+    """one list of 1 200 s at 1 024 Hz at about 170 beats per minute in one window: W = 1 228 800, F = 480 (two rounds of the
+    strided frequency loop), m about 3 400 of max_m = 3 989, products (k + 1) q up to 5.9e8"""
+    from ecg_denoise_amd import synth
+    fs, T = 1024, 1024 * 1200
+    beats, labels = synth.make_beats_with_hrv(1, T, fs=fs, seed=3, lf=0.01, hf=0.005, bpm=(168.0, 172.0))
+    g = _geometry(fs, win_s=1200)
+    assert (g["W"], g["F"], g["max_m"]) == (1228800, 480, 3989)
+    h = _analyse(fs, beats, T, labels, psd=True, win_s=1200)
+    n, spectra = _check(h, beats, labels, T, g, "the long window")
+    assert n == 1 and spectra == 1 and 3300 <= int(h.n_nn[0]) <= 3500 and int(h.counts[0, 0]) == len(beats[0])
+
+
+# ------------------------------------------------------------------------------------------------ 3. edges
+def test_edges():
+    fs, g = 360, _geometry(360, **SHORT)
+    W, H, lo, hi, t50 = g["W"], g["H"], g["lo_n"], g["hi_n"], g["t50"]
+    assert (W, H, lo, hi, t50) == (10800, 3600, 108, 720, 18)
+    T = W                                      # one window: every list with a spectrum spreads over it (the condition of the bound)
+
+    def chain(start, steps):
+        return [int(v) for v in start + np.concatenate([[0], np.cumsum(steps)])]
+
+    lists = [[], [100], [100, 400], [100, 400, 700],
+             chain(50, [300] * 30),                                             # 4: all beats V
+             chain(10, [lo - 1, lo, hi, hi + 1, lo, hi, lo - 1, hi + 1, 300]),  # 5: just inside and just outside [lo_n, hi_n]
+             chain(200, [290 + 3 * (i % 5) for i in range(30)]),                # 6: m = min_nn - 1 (see the labels)
+             chain(200, [290 + 3 * (i % 5) for i in range(30)]),                # 7: m = min_nn
+             chain(100, [300] * 30),                                            # 8: equal intervals
+             chain(0, [299, 310] * 17 + [T - 1 - 17 * 609]),                    # 9: beats at 0 and at T - 1
+             chain(77, [300, 300 + t50, 300, 300 + t50 + 1, 300, 300 - t50, 300 - t50 - 1] * 4)]      # 10: |D| = t50 and t50 + 1
+    labels = [[0] * len(p) for p in lists]
+    labels[4] = [1] * len(lists[4])
+    for r, keep in ((6, (1, 5, 8, 12, 17, 20, 25)), (7, (1, 5, 8, 12, 17, 20, 25, 29))):      # only these intervals lie between two N
+        labels[r] = [0 if i in keep or i + 1 in keep else 1 for i in range(31)]                # beats: scattered over the window
+    assert lists[9][-1] == T - 1 and all(p[-1] < T for p in lists if p)
+    h = _analyse(fs, lists, T, labels, psd=True, **SHORT)
+    n, spectra = _check(h, lists, labels, T, g, "edges")
+    nw = 1
+    assert n == nw * len(lists) and spectra == 4             # the lists 7 to 10
+    c, s = h.counts.cpu().numpy().reshape(len(lists), nw, 4), h.stats.cpu().numpy().reshape(len(lists), nw, 10)
+    assert c[0].tolist() == [[0] * 4] * nw and np.isnan(s[0]).all()
+    assert c[1, 0].tolist() == [1, 0, 0, 0] and np.isnan(s[1]).all()
+    assert c[2, 0].tolist() == [2, 1, 0, 0] and np.isfinite(s[2, 0, :2]).all() and np.isnan(s[2, 0, 2:]).all()
+    assert s[2, 0, 0] == np.float32(300 / 360) and s[2, 0, 1] == np.float32(72.0)
+    assert c[3, 0].tolist() == [3, 2, 1, 0] and s[3, 0, 2] == 0.0 and s[3, 0, 3] == 0.0 and np.isnan(s[3, 0, 5:]).all()
+    assert c[4, 0].tolist() == [31, 0, 0, 0] and np.isnan(s[4]).all()
+    assert c[5, 0].tolist() == [10, 5, 2, 2]                  # lo, hi | lo, hi | 300: the four outside ones break the chain
+    assert c[6, 0].tolist() == [31, 7, 0, 0] and np.isnan(s[6, 0, 3:]).all() and np.isfinite(s[6, 0, :3]).all()
+    assert c[7, 0].tolist() == [31, 8, 0, 0] and np.isfinite(s[7, 0, :3]).all() and np.isfinite(s[7, 0, 5:9]).all()
+    assert c[8, 0].tolist() == [31, 30, 29, 0] and s[8, 0, 2] == 0.0 and s[8, 0, 3] == 0.0 and s[8, 0, 4] == 0.0
+    assert s[8, 0, 5:9].tolist() == [0.0] * 4 and np.isnan(s[8, 0, 9]) and float(h.psd[8 * nw].abs().max()) == 0.0
+    assert c[9, 0].tolist() == [36, 35, 34, 1]                # the beats at 0 and at T - 1 both count
+    d = np.diff(lists[10])
+    dd = np.diff(d[:np.searchsorted(lists[10], W) - 1])
+    assert c[10, 0, 3] == int((np.abs(dd) > t50).sum()) and int((np.abs(dd) == t50).sum()) >= 4 and int((np.abs(dd) == t50 + 1).sum()) >= 4
+    # a record shorter than the window: one window [0, T), W still the frequency base
+    short = [p for p in lists[7]]
+    Ts = short[-1] + 1
+    hs = _analyse(fs, [short], Ts, [labels[7]], psd=True, **SHORT)
+    _check(hs, [short], [labels[7]], Ts, g, "T < W")
+    assert len(hs) == 1 and Ts < W and torch.equal(_bits(hs.stats[0]), _bits(h.stats[7 * nw]))
+    # a Beats whose cap is wider than any count
+    from ecg_denoise_amd import Beats
+    cap = max(len(p) for p in lists)
+    pad = torch.full((len(lists), cap + 29), -1, dtype=torch.int32, device=DEV)
+    for r, p in enumerate(lists):
+        pad[r, :len(p)] = torch.tensor(p, dtype=torch.int32)
+    count = torch.tensor([len(p) for p in lists], dtype=torch.int32, device=DEV)
+    h2 = _analyse(fs, Beats(pad, count), T, labels, psd=True, **SHORT)
+    assert _same_bits(h, h2)
+
+
+# ------------------------------------------------------------------------------------------------ 4. batch invariance
+def test_a_record_alone_gives_the_bits_of_its_rows_in_the_batch():
+    T, beats, labels = _short(360)
+    h = _analyse(360, beats, T, labels, psd=True, **SHORT)
+    assert _same_bits(h, _analyse(360, beats, T, labels, psd=True, **SHORT))
+    nw = len(h) // 4
+    for r in (0, 3):
+        one = _analyse(360, [beats[r]], T, [labels[r]], psd=True, **SHORT)
+        assert torch.equal(one.counts, h.counts[r * nw:(r + 1) * nw]) and torch.equal(_bits(one.stats), _bits(h.stats[r * nw:(r + 1) * nw]))
+        assert torch.equal(_bits(one.psd), _bits(h.psd[r * nw:(r + 1) * nw]))
+
+
+# ------------------------------------------------------------------------------------------------ 5. end to end on records
+CHAIN = dict(win_s=20, hop_s=5, min_nn=8)
+
+
+@functools.lru_cache(maxsize=None)
+def _chain():
+    """make_records_with_rhythm(2, 2, 21600) through detector, classifier and analyzer -> (records on the device, Beats,
+    BeatClasses, HrvWindows)"""
+    from ecg_denoise_amd import BeatClassifier, BeatDetector, HrvAnalyzer, synth
+    x, _, _ = synth.make_records_with_rhythm(2, 2, 21600, seed=31, p_v=0.08, p_s=0.05)
+    xd = torch.from_numpy(x).to(DEV)
+    beats = BeatDetector(device=DEV).detect(xd)
+    classes = BeatClassifier(device=DEV).classify(xd, beats)
+    return xd, beats, classes, HrvAnalyzer(device=DEV, **CHAIN).analyse(beats, 21600, classes)
+
+
+def test_the_three_call_chain_equals_the_oracle_at_the_detectors_lists():
+    xd, beats, classes, h = _chain()
+    lists, labels = beats.tolist(), [c[0] for c in classes.tolist()]
+    assert min(len(p) for p in lists) >= 40 and any(l != 0 for row in labels for l in row)
+    n, spectra = _check(h, lists, labels, 21600, _geometry(360, **CHAIN), "detector, classifier, analyzer")
+    assert n == 2 * ((21600 - 7200) // 1800 + 1) and spectra >= n // 2
+
+
+# ------------------------------------------------------------------------------------------------ 6. the pool
+def _pool_run(seed, disturb=False):
+    """both records of `_chain` through an HrvPool in seeded random chunks, the second stream opened later and closed earlier
+    or later than the first -> per stream (HrvWindows list, pushes with no window)"""
+    from ecg_denoise_amd import HrvPool, RalError
+    xd = _chain()[0]
+    rng = np.random.default_rng(seed)
+    pool = HrvPool(2, capacity=3, device=DEV, **CHAIN)
+    sid, at, got, empty = {}, {}, {0: [], 1: []}, {0: 0, 1: 0}
+    call = 0
+    while len(sid) < 2 or pool.open_streams:
+        for i in (0, 1):
+            if i not in sid and call >= 3 * i:
+                sid[i], at[i] = pool.open(), 0
+        if disturb:
+            free = [s for s in range(3) if s not in pool.open_streams][0]
+            some = pool.open_streams[0] if pool.open_streams else free
+            for chunks, close in (({free: xd[0][:, :10]}, ()), ({some: xd[0][:1, :10]}, ()), ({}, (free,)), ({}, ())):
+                with pytest.raises(RalError):
+                    pool.push(chunks, close=close)
+        chunks, close = {}, []
+        for i in sid:
+            if sid[i] not in pool.open_streams or at[i] is None or rng.random() < 0.25:
+                continue
+            c = min(21600 - at[i], int(rng.integers(1, 6001)))
+            chunks[sid[i]] = xd[i][:, at[i]:at[i] + c]
+            at[i] += c
+            if at[i] == 21600:
+                close.append(sid[i])
+        call += 1
+        if not chunks:
+            continue
+        res = pool.push(chunks, close=close)
+        assert set(res) == set(chunks)
+        for i in sid:
+            if sid[i] in res:
+                got[i].append(res[sid[i]])
+                empty[i] += len(res[sid[i]]) == 0
+                assert all(ix[0] == sid[i] for ix in res[sid[i]].index.tolist())
+                if sid[i] in close:
+                    at[i] = None
+    return got, empty
+
+
+@pytest.mark.parametrize("seed,disturb", [(5, False), (6, True)])
+def test_pool_equals_the_three_call_chain_bit_for_bit(seed, disturb):
+    """two seeded random chunkings; in the second, raising calls (a slot with no open stream, a wrong lead count, nothing to
+    do) come before every push and leave the results unchanged"""
+    _, _, _, want = _chain()
+    nw = len(want) // 2
+    got, empty = _pool_run(seed, disturb)
+    for i in (0, 1):
+        counts = torch.cat([h.counts for h in got[i]])
+        stats = torch.cat([h.stats for h in got[i]])
+        assert [ix[1] for h in got[i] for ix in h.index.tolist()] == list(range(nw))
+        assert torch.equal(counts, want.counts[i * nw:(i + 1) * nw])
+        assert torch.equal(_bits(stats), _bits(want.stats[i * nw:(i + 1) * nw]))
+        assert empty[i] >= 1 and all(h.psd is None and tuple(h.stats.shape) == (len(h), 10) for h in got[i])
+
+
+# ------------------------------------------------------------------------------------------------ 7. evaluate_hrv
+def _evaluate(dn, rec, noise, ana, cls):
+    """evaluate_hrv against its explicit composition -> the HrvEvaluation"""
+    from ecg_denoise_amd import BeatDetector, evaluate_hrv, mix_records
+    ev = evaluate_hrv(dn, rec, noise, 6.0, offsets=[5, 200], analyzer=ana, classifier=cls)
+    noisy, clean = mix_records(rec, noise, 6.0, offsets=[5, 200])
+    det = BeatDetector(device=DEV)
+    hs = []
+    for x in (clean, noisy, dn.denoise(noisy)):
+        b = det.detect(x)
+        hs.append(ana.analyse(b, 21600, cls.classify(x, b)))
+    for what, mine, theirs in zip(("clean", "noisy", "denoised"), (ev.clean, ev.noisy, ev.denoised), hs):
+        print(f"\n[hrv] evaluate_hrv c0={cls.c0} {what}: beats {theirs.counts[:, 0].tolist()} n_nn {theirs.n_nn.tolist()}")
+        assert _same_bits(mine, theirs)
+    print(f"[hrv] evaluate_hrv c0={cls.c0} errors {ev.errors} windows {ev.windows}")
+    assert set(ev.errors) == {"noisy", "denoised"} and set(ev.windows) == {"hr", "sdnn", "rmssd", "log_lf_hf"}
+    for name in ev.windows:
+        c, a, b = ((torch.log(h.lf_hf.double()) if name == "log_lf_hf" else getattr(h, name).double()).cpu().numpy() for h in hs)
+        ok = np.isfinite(c) & np.isfinite(a) & np.isfinite(b)
+        assert ev.windows[name] == int(ok.sum()) <= len(hs[0])
+        for key, v in (("noisy", a), ("denoised", b)):
+            e = ev.errors[key][name]
+            if ev.windows[name]:
+                assert np.isfinite(e) and e >= 0 and abs(e - np.abs(v[ok] - c[ok]).mean()) <= 1e-12 * max(1.0, e)
+            else:
+                assert np.isnan(e)
+    assert ev.windows["log_lf_hf"] <= ev.windows["sdnn"] <= ev.windows["hr"] and ev.windows["rmssd"] <= ev.windows["sdnn"]
+    return ev
+
+
+def test_evaluate_hrv_is_the_explicit_composition():
+    """with a freshly initialised RALENet("full", leads=2, L=64) and emb noise at 6 dB: the plumbing, not an improvement (an
+    untrained model promises none).  Such a model's output is not an ECG.  With the default classifier (c0 = 0.7) nearly every
+    beat of the denoised records is called V - seen on an MI355X: 19 - 28 beats but at most ONE NN interval in each of the 18
+    windows, so heart rate is compared on 10 windows and SDNN, RMSSD and log(LF/HF) on none (their errors are NaN by definition) -
+    and that run is held to the composition and to consistent counts.  All eight errors are required to be finite with a
+    classifier, handed to `evaluate_hrv` explicitly, that excludes no beat by shape or prematurity (c0 = -1, r0 = 0): then the
+    intervals alone decide and every window of the three records has a spectrum."""
+    from ecg_denoise_amd import BeatClassifier, HrvAnalyzer, RALENet, synth
+    from ecg_denoise_amd.infer import StreamingDenoiser
+    if "full" not in _MODELS:
+        _MODELS["full"] = RALENet("full", leads=2, L=64, max_batch=16, train=False, device=DEV, seed=11).eval()
+    dn = StreamingDenoiser(_MODELS["full"], use_graph=False)
+    rec = _chain()[0]
+    noise = torch.from_numpy(synth.make_noise_record("emb", 2, 21600 + 500, seed=3)).to(DEV)
+    ana = HrvAnalyzer(device=DEV, **CHAIN)
+    ev = _evaluate(dn, rec, noise, ana, BeatClassifier(device=DEV))
+    assert ev.windows["hr"] >= 1
+    ev = _evaluate(dn, rec, noise, ana, BeatClassifier(c0=-1.0, r0=0.0, device=DEV))
+    assert all(ev.windows[name] >= 1 for name in ev.windows)
+    assert all(np.isfinite(e) for side in ev.errors.values() for e in side.values())
+
+
+# ------------------------------------------------------------------------------------------------ 8. the C entry point
+def test_the_c_entry_point_refuses_by_name():
+    from ecg_denoise_amd import _lib
+    lib = _lib.lib()
+    g = _geometry(360, **SHORT)
+    pos = torch.tensor([[100, 400, 700, -1]], dtype=torch.int32, device=DEV)
+    count = torch.tensor([3], dtype=torch.int32, device=DEV)
+    band = torch.from_numpy(g["band"]).to(DEV)
+    counts = torch.full((2, 4), -7, dtype=torch.int32, device=DEV)
+    stats = torch.full((2, 10), -7.0, dtype=torch.float32, device=DEV)
+    tab_dev = torch.zeros(2 * _lib.HRV_ROW.itemsize, dtype=torch.uint8, device=DEV)
+
+    def call(geom, rows, R=1, cap=4):
+        tab = np.zeros(len(rows), dtype=_lib.HRV_ROW)
+        for i, (rec, w0, w1) in enumerate(rows):
+            tab[i] = (w0, w1, rec, 0)
+        rc = lib.ral_hrv_windows(pos.data_ptr(), None, count.data_ptr(), R, cap, tab.ctypes.data, len(rows), tab_dev.data_ptr(), 1,
+                                 ctypes.byref(geom), band.data_ptr(), counts.data_ptr(), stats.data_ptr(), None, None)
+        torch.cuda.synchronize()
+        return rc, lib.ral_last_error().decode()
+
+    def geom(**kw):
+        v = dict(W=g["W"], lo_n=g["lo_n"], hi_n=g["hi_n"], t50=g["t50"], F=g["F"], min_nn=g["min_nn"], fs=360.0)
+        v.update(kw)
+        return _lib.HrvGeom(v["W"], v["lo_n"], v["hi_n"], v["t50"], v["F"], v["min_nn"], v["fs"])
+
+    ok = [(0, 0, 10800)]
+    for kw, rule in ((dict(W=1), "2 <= W < 2^31"), (dict(lo_n=0), "1 <= lo_n <= hi_n"), (dict(lo_n=721), "1 <= lo_n <= hi_n"),
+                     (dict(F=0), "1 <= F <= 4096"), (dict(F=4097), "1 <= F <= 4096"), (dict(W=2 ** 30, F=2, lo_n=2 ** 19, hi_n=2 ** 20), "F * W < 2^31"),
+                     (dict(lo_n=2, hi_n=5), "max_m = (W - 1) // lo_n <= 4096"), (dict(min_nn=1), "2 <= min_nn"),
+                     (dict(fs=0.0), "a finite fs > 0")):
+        rc, msg = call(geom(**kw), ok)
+        assert rc != 0 and msg.startswith("hrv_windows: need " + rule), msg
+    for rows, rule in (([(1, 0, 10800)], "0 <= rec < R in row 0"), ([(0, 0, 10800), (-1, 0, 10)], "0 <= rec < R in row 1"),
+                       ([(0, 0, 10801)], "0 <= w0 < w1 <= w0 + W in row 0"), ([(0, 5, 5)], "0 <= w0 < w1 <= w0 + W in row 0"),
+                       ([(0, 0, 10), (0, -1, 10)], "0 <= w0 < w1 <= w0 + W in row 1")):
+        rc, msg = call(geom(), rows)
+        assert rc != 0 and msg.startswith("hrv_windows: need " + rule), msg
+    rc, msg = call(geom(), ok, R=0)
+    assert rc != 0 and "1 <= R" in msg
+    assert bool((counts == -7).all()) and bool((stats == -7.0).all())          # nothing was launched
+    rc, msg = call(geom(), ok)
+    assert rc == 0 and counts[0].tolist() == [3, 2, 1, 0] and bool((counts[1] == -7).all())

@@ -31,9 +31,14 @@ through `ClassicalDenoiser("fft", --fft-L)` (windows of `--fft-L` samples, defau
 window share one cutoff), scored like the wavelet row: per cell one more reference-format line and an "fft" entry in the JSON.
 Without the flag the output is what it was.
 
+`--hrv` asks the third question, are the rhythm statistics back: per cell one more line and an "hrv" entry in the JSON with the
+mean absolute error of heart rate, SDNN, RMSSD and log(LF/HF) of the noisy and of the denoised records against the clean ones,
+each record detected, classified and analysed on its own (`evaluate_hrv`; windows of `--hrv-win` seconds every `--hrv-hop`
+seconds; NaN where no window has all three values).  Without the flag the output is what it was.
+
     python tools/stress_eval.py [--model full|nra|mlp|unet|acdae|danet|newrale] [--ckpt state_dict.pth] [--L 512]
                                 [--records 4] [--T 65000] [--overlap 0] [--batch 4096] [--time-shapes ...] [--reps 5] [--beats]
-                                [--classes] [--fft] [--fft-L 1000]
+                                [--classes] [--fft] [--fft-L 1000] [--hrv] [--hrv-win 60] [--hrv-hop 30]
 """
 import argparse
 import json
@@ -46,8 +51,8 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from ecg_denoise_amd import (ACDAE, ClassicalDenoiser, DANet, NewRALE, RALENet, UNet, evaluate_beats, evaluate_rhythm, mix_records,  # noqa: E402
-                             score_records, synth, wavelet_denoise)
+from ecg_denoise_amd import (ACDAE, ClassicalDenoiser, DANet, NewRALE, RALENet, UNet, evaluate_beats, evaluate_hrv, evaluate_rhythm,  # noqa: E402
+                             mix_records, score_records, synth, wavelet_denoise)
 from ecg_denoise_amd.data import NOISE_TYPES, TRUE_NOISE  # noqa: E402
 from ecg_denoise_amd.infer import StreamingDenoiser  # noqa: E402
 
@@ -111,6 +116,20 @@ def _classes_cell(ev, idx):
     return out
 
 
+def _hrv_cell(ev, idx):
+    """the records idx of an `evaluate_hrv` result -> per metric the windows compared and the two mean absolute errors"""
+    from ecg_denoise_amd.hrv import METRICS, _metric
+    rows = torch.from_numpy(np.isin(ev.clean.index[:, 0], idx.cpu().numpy())).to(ev.clean.stats.device)
+    out = {"windows": {}, "noisy": {}, "denoised": {}}
+    for m in METRICS:
+        c, a, b = (_metric(h, m) for h in (ev.clean, ev.noisy, ev.denoised))
+        ok = rows & torch.isfinite(c) & torch.isfinite(a) & torch.isfinite(b)
+        out["windows"][m] = int(ok.sum())
+        for key, v in (("noisy", a), ("denoised", b)):
+            out[key][m] = float((v[ok] - c[ok]).abs().mean()) if out["windows"][m] else float("nan")
+    return out
+
+
 def grid(args, model, name):
     sd = StreamingDenoiser(model, batch=args.batch, overlap=args.overlap, use_graph=True)
     leads, n_int = sd.leads, len(TRUE_NOISE)
@@ -132,6 +151,11 @@ def grid(args, model, name):
         sf = score_records(clean, ClassicalDenoiser("fft", args.fft_L, device=DEV).denoise(noisy), noisy, window=sd.L) if args.fft else None
         ev = evaluate_beats(sd, rec, noise, snrs, offsets=offsets) if args.beats else None
         evc = evaluate_rhythm(sd, rec, noise, snrs, offsets=offsets) if args.classes else None
+        evh = None
+        if args.hrv:
+            from ecg_denoise_amd import HrvAnalyzer
+            evh = evaluate_hrv(sd, rec, noise, snrs, offsets=offsets,
+                               analyzer=HrvAnalyzer(win_s=args.hrv_win, hop_s=args.hrv_hop, device=DEV))
         for i, snr in enumerate(TRUE_NOISE):
             idx = torch.arange(i * args.records, (i + 1) * args.records, device=DEV)
             a, b = _subset(sc, idx, sd.L), _subset(sw, idx, sd.L)
@@ -154,6 +178,13 @@ def grid(args, model, name):
                                  f"(N {d['N']} V {d['V']} S {d['S']} unclassified {d['unclassified']})")
                 lines.append(f"{name}_0_{kind}_intensity{snr}:classes: clean V {cc['clean']['V']} of {cc['scored_beats']} scored, "
                              f"noisy {col(cc['noisy'])}, denoised {col(cc['denoised'])}\n")
+            if evh is not None:
+                hc = _hrv_cell(evh, idx)
+                cells[-1]["hrv"] = hc
+                col = lambda d: (f"hr {d['hr']:.3f} bpm sdnn {1e3 * d['sdnn']:.2f} ms rmssd {1e3 * d['rmssd']:.2f} ms "
+                                 f"log(lf/hf) {d['log_lf_hf']:.3f}")
+                lines.append(f"{name}_0_{kind}_intensity{snr}:hrv: mean absolute error over {hc['windows']['hr']} windows, "
+                             f"noisy {col(hc['noisy'])}, denoised {col(hc['denoised'])}\n")
     return cells, lines
 
 
@@ -214,6 +245,9 @@ def main():
     ap.add_argument("--classes", action="store_true", help="add beat classes (N / V / S) and acc / precision / F1, noisy and denoised")
     ap.add_argument("--fft", action="store_true", help="add the FFT-threshold baseline (the model 'fft') beside the wavelet one")
     ap.add_argument("--fft-L", type=int, default=1000)
+    ap.add_argument("--hrv", action="store_true", help="add the errors of heart rate, SDNN, RMSSD and log(LF/HF), noisy and denoised")
+    ap.add_argument("--hrv-win", type=int, default=60)
+    ap.add_argument("--hrv-hop", type=int, default=30)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("stress_eval: needs a HIP device")
