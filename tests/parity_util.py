@@ -63,6 +63,24 @@ def make_case(variant, leads, L, B, seed=1234, dtype=torch.float64):
     return p32, x, tgt
 
 
+def compare_grads(ng, p, grads):
+    """relative L2 error per parameter gradient: the library's `named_grads()` against the oracle's `grads` (in the order of `p`)"""
+    gerr = OrderedDict()
+    for (k, _), g in zip(p.items(), grads):
+        g = torch.zeros_like(p[k]) if g is None else g
+        gn = g.norm().item()
+        mine = ng[k].cpu().numpy()
+        if k.endswith("to_kv.bias"):
+            # key-bias gradient is identically zero (softmax shift invariance): compare the value half,
+            # and bound the key half by rounding noise
+            C = mine.size // 2
+            gerr["grad:" + k + "[v]"] = rel(mine[C:], g.numpy()[C:])
+            gerr["gradabs:" + k + "[k]"] = float(np.abs(mine[:C]).max())
+        else:
+            gerr["grad:" + k] = rel(mine, g.numpy()) if gn > 1e-12 else float(np.abs(mine).max())
+    return gerr
+
+
 def run_parity(variant, leads, L, B, device="cuda:0", trace=True, seed=1234):
     """-> dict of relative errors (HIP fp32 vs fp64 oracle)."""
     from ecg_denoise_amd import RALENet
@@ -92,19 +110,53 @@ def run_parity(variant, leads, L, B, device="cuda:0", trace=True, seed=1234):
     if trace:
         for k, v in tr.items():
             res["act:" + k] = rel(model.debug_tensor(k).cpu().numpy()[:v.numel()], v.detach().numpy())
-    ng = model.named_grads()
-    gerr = OrderedDict()
-    for (k, _), g in zip(p.items(), grads):
-        g = torch.zeros_like(p[k]) if g is None else g
-        gn = g.norm().item()
-        mine = ng[k].cpu().numpy()
-        if k.endswith("to_kv.bias"):
-            # key-bias gradient is identically zero (softmax shift invariance): compare the value half,
-            # and bound the key half by rounding noise
-            C = mine.size // 2
-            gerr["grad:" + k + "[v]"] = rel(mine[C:], g.numpy()[C:])
-            gerr["gradabs:" + k + "[k]"] = float(np.abs(mine[:C]).max())
-        else:
-            gerr["grad:" + k] = rel(mine, g.numpy()) if gn > 1e-12 else float(np.abs(mine).max())
-    res.update(gerr)
+    res.update(compare_grads(model.named_grads(), p, grads))
     return res, model, (p32, x, tgt)
+
+
+def oracle_windows(p32, x, tgt, idx, variant="full"):
+    """fp64 oracle of a whole-batch train step whose output gradient is zero outside the windows `idx` (dy[idx] = d mse / d y
+    of the whole batch): the BatchNorm statistics come from the WHOLE batch (the stem conv of every window is cheap on the CPU),
+    the transformer stack runs on the picked windows only, and the BatchNorm backward - the one place where the other
+    windows see the gradient - is reproduced by hand.  -> (pred of the windows `idx`, {parameter name: gradient})."""
+    import torch.nn.functional as F
+    from test_dp_gloo import _rest_of_network
+    B, L = x.shape[0], x.shape[2]
+    n = x.shape[1] * L
+    sl = idx if isinstance(idx, slice) else torch.as_tensor(list(idx), dtype=torch.long)
+    p = OrderedDict((k, v.double().requires_grad_(True)) for k, v in p32.items())
+    a0 = F.leaky_relu(F.conv1d(x.double(), p["conv1.0.weight"], p["conv1.0.bias"], padding=1), 0.2)   # (B, 8, L)
+    cnt = B * L
+    mean = a0.detach().sum((0, 2)) / cnt
+    var = (a0.detach() ** 2).sum((0, 2)) / cnt - mean ** 2
+    rstd = 1.0 / torch.sqrt(var + 1e-5)
+    xhat = (a0.detach() - mean[None, :, None]) * rstd[None, :, None]
+    x0 = (xhat[sl] * p["conv1.2.weight"].detach()[None, :, None] + p["conv1.2.bias"].detach()[None, :, None]).requires_grad_(True)
+    pred = _rest_of_network(p, x0, variant)
+    loss = ((pred - tgt[sl].double()) ** 2).sum() / (B * n)
+    names = [k for k in p if not k.startswith("conv1.")]
+    gs = torch.autograd.grad(loss, [x0] + [p[k] for k in names], allow_unused=True)
+    gx0 = torch.zeros_like(a0.detach()); gx0[sl] = gs[0]
+    s1, s2 = gx0.sum((0, 2)) / cnt, (gx0 * xhat).sum((0, 2)) / cnt
+    da = p["conv1.2.weight"].detach()[None, :, None] * rstd[None, :, None] * (gx0 - s1[None, :, None] - xhat * s2[None, :, None])
+    gw, gb = torch.autograd.grad(a0, [p["conv1.0.weight"], p["conv1.0.bias"]], da)
+    want = {k: (g if g is not None else torch.zeros_like(p[k])) for k, g in zip(names, gs[1:])}
+    want["conv1.0.weight"], want["conv1.0.bias"] = gw, gb
+    want["conv1.2.weight"], want["conv1.2.bias"] = (gx0 * xhat).sum((0, 2)), gx0.sum((0, 2))
+    return pred.detach(), want
+
+
+def window_grad_errors(named_grads, want):
+    """relative L2 error of every parameter gradient of the library against `want` (oracle_windows)"""
+    err = OrderedDict()
+    for k, g in want.items():
+        mine = named_grads[k].cpu().numpy()
+        if k.endswith("to_kv.bias"):
+            C_ = mine.size // 2          # the key half is identically zero (softmax shift invariance): the value half
+            e = rel(mine[C_:], g.numpy()[C_:])
+        elif k == "conv1.0.bias":
+            continue          # exactly zero through a BatchNorm: rounding noise on both sides
+        else:
+            e = rel(mine, g.numpy()) if g.norm().item() > 1e-14 else 0.0
+        err[k] = e
+    return err
