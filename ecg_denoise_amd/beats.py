@@ -204,18 +204,14 @@ class BeatPoolState(SlotState):
     def plan(self, shapes, close=()):
         """shapes {sid: shape of its chunk, (leads, c) with c >= 0}, close: the sids that end with this call -> (sids in row
         order, table); raises RalError for a bad argument"""
-        sids, slot, lens, ends, n0 = self.named(shapes, close, 65535, "65535 streams")
+        named = self.named(shapes, close, 65535, "65535 streams")
+        sids, _, lens, ends, n0 = named
+        tab = self.rows(_lib.BEAT_ROW, named, need_sample=True)
         n1 = n0 + lens
-        if np.any(ends & (n1 < 1)):
-            r = int(np.argmax(ends & (n1 < 1)))
-            raise _lib.RalError(f"{self.name}.push: stream {sids[r]} would end without a single sample")
         d0 = np.maximum(0, n0 - self.lag)
         d = np.where(ends, n1, np.maximum(0, n1 - self.lag)) - d0
         cap = np.where(d > 0, d // (self.geometry["Rf"] + 1) + 1, 0)
-        tab = np.zeros(len(sids), dtype=_lib.BEAT_ROW)
-        tab["n0"], tab["T"], tab["d0"], tab["slot"], tab["c"], tab["d"], tab["cap"] = n0, np.where(ends, n1, -1), d0, slot, lens, d, cap
-        tab["x_off"], tab["out_off"] = np.cumsum(lens) - lens, np.cumsum(cap) - cap
-        tab["turn"], tab["flags"] = self.turn[slot], np.where(ends, 0, _lib.POOL_KEEP)
+        tab["d0"], tab["d"], tab["cap"], tab["out_off"] = d0, d, cap, np.cumsum(cap) - cap
         return sids, tab
 
     def span(self, tab):

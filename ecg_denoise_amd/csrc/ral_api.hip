@@ -1576,14 +1576,24 @@ int ral_newrale_live_back(const float* inner_y, const float* stats, const float*
   return 0;
 }
 
-// a refused pool call: the one rule that is broken and, if it is a row's, which row
-static int pool_fail(const char* name, const char* why, int bad, int rows, long long cap, int L, int hop, long long total,
-                     long long w0, int nb) {
-  char row[32] = "";
-  if (bad >= 0) snprintf(row, sizeof(row), " in row %d", bad);
-  return fail("%s: need %s%s (rows=%d capacity=%lld L=%d hop=%d packed=%lld w0=%lld nb=%d)", name, why, row, rows, cap, L, hop,
-              total, w0, nb);
+// How an entry point that takes a table ends.  rc = 0: launched; what the launches left behind is the result.  rc = -1,
+// refused: the one rule that is broken and, if it is a row's, which row, then the call's arguments as args_fmt words them.
+// Any other rc: the table did not reach the device.
+static int table_done(const char* name, int rc, const char* why, long long bad, const char* args_fmt, ...) {
+  if (rc == 0) {
+    HIP_OK(hipGetLastError());
+    return 0;
+  }
+  if (rc != -1) return fail("%s: copying the table to the device failed", name);
+  char row[40] = "", args[sizeof(g_err)];
+  if (bad >= 0) snprintf(row, sizeof(row), " in row %lld", bad);
+  va_list ap;
+  va_start(ap, args_fmt);
+  vsnprintf(args, sizeof(args), args_fmt, ap);
+  va_end(ap);
+  return fail("%s: need %s%s (%s)", name, why, row, args);
 }
+static const char POOL_ARGS[] = "rows=%d capacity=%lld L=%d hop=%d packed=%lld w0=%lld nb=%d";
 
 int ral_pool_windows(float* hist, const float* x, int64_t x_total, const ral_pool_row* table, int rows, ral_pool_row* table_dev,
                      int upload, int64_t capacity, int leads, int L, int hop, int write_hist, int64_t w0, int nb, float* win,
@@ -1593,10 +1603,8 @@ int ral_pool_windows(float* hist, const float* x, int64_t x_total, const ral_poo
   int bad = -1;
   const int rc = launch_pool_windows(hist, x, (long long)x_total, table, rows, table_dev, upload, (long long)capacity, leads, L, hop,
                                      write_hist, (long long)w0, nb, win, stats, (hipStream_t)s, &why, &bad);
-  if (rc == -1) return pool_fail("pool_windows", why, bad, rows, (long long)capacity, L, hop, (long long)x_total, (long long)w0, nb);
-  if (rc) return fail("pool_windows: copying the table to the device failed");
-  HIP_OK(hipGetLastError());
-  return 0;
+  return table_done("pool_windows", rc, why, bad, POOL_ARGS, rows, (long long)capacity, L, hop, (long long)x_total, (long long)w0,
+                    nb);
 }
 
 int ral_pool_emit(const float* y, const float* stats, const ral_pool_row* table, int rows, ral_pool_row* table_dev, int upload,
@@ -1607,10 +1615,8 @@ int ral_pool_emit(const float* y, const float* stats, const ral_pool_row* table,
   int bad = -1;
   const int rc = launch_pool_emit(y, stats, table, rows, table_dev, upload, (long long)capacity, leads, L, hop, (long long)w0, nb,
                                   from_last, out, (long long)out_total, last_y, last_stats, (hipStream_t)s, &why, &bad);
-  if (rc == -1) return pool_fail("pool_emit", why, bad, rows, (long long)capacity, L, hop, (long long)out_total, (long long)w0, nb);
-  if (rc) return fail("pool_emit: copying the table to the device failed");
-  HIP_OK(hipGetLastError());
-  return 0;
+  return table_done("pool_emit", rc, why, bad, POOL_ARGS, rows, (long long)capacity, L, hop, (long long)out_total, (long long)w0,
+                    nb);
 }
 
 int ral_newrale_pool_front(float* hist, const float* x, int64_t x_total, const ral_pool_row* table, int rows,
@@ -1621,11 +1627,8 @@ int ral_newrale_pool_front(float* hist, const float* x, int64_t x_total, const r
   int bad = -1;
   const int rc = launch_newrale_pool_front(hist, x, (long long)x_total, table, rows, table_dev, upload, (long long)capacity, L, hop,
                                            write_hist, (long long)w0, nb, adapter_params, inner_x, stats, (hipStream_t)s, &why, &bad);
-  if (rc == -1)
-    return pool_fail("newrale_pool_front", why, bad, rows, (long long)capacity, L, hop, (long long)x_total, (long long)w0, nb);
-  if (rc) return fail("newrale_pool_front: copying the table to the device failed");
-  HIP_OK(hipGetLastError());
-  return 0;
+  return table_done("newrale_pool_front", rc, why, bad, POOL_ARGS, rows, (long long)capacity, L, hop, (long long)x_total,
+                    (long long)w0, nb);
 }
 
 int ral_newrale_pool_back(const float* inner_y, const float* stats, const float* adapter_params, const ral_pool_row* table,
@@ -1637,11 +1640,8 @@ int ral_newrale_pool_back(const float* inner_y, const float* stats, const float*
   const int rc = launch_newrale_pool_back(inner_y, stats, adapter_params, table, rows, table_dev, upload, (long long)capacity, L,
                                           hop, (long long)w0, nb, from_last, out, (long long)out_total, last_y, last_stats,
                                           (hipStream_t)s, &why, &bad);
-  if (rc == -1)
-    return pool_fail("newrale_pool_back", why, bad, rows, (long long)capacity, L, hop, (long long)out_total, (long long)w0, nb);
-  if (rc) return fail("newrale_pool_back: copying the table to the device failed");
-  HIP_OK(hipGetLastError());
-  return 0;
+  return table_done("newrale_pool_back", rc, why, bad, POOL_ARGS, rows, (long long)capacity, L, hop, (long long)out_total,
+                    (long long)w0, nb);
 }
 
 int64_t ral_mix_records_scratch_bytes(int64_t R, int leads, int64_t T) {
@@ -1706,16 +1706,9 @@ int ral_rate_pool(float* hist, const float* x, int64_t x_total, const ral_rate_r
   int bad = -1;
   const int rc = launch_rate_pool(hist, x, (long long)x_total, table, rows, table_dev, upload, (long long)capacity, leads, up, down,
                                   bank, ntaps, hist_len, out, (long long)out_total, (hipStream_t)s, &why, &bad);
-  if (rc == -1) {
-    char row[32] = "";
-    if (bad >= 0) snprintf(row, sizeof(row), " in row %d", bad);
-    return fail("rate_pool: need %s%s (rows=%d capacity=%lld leads=%d up=%d down=%d ntaps=%d hist_len=%d x_total=%lld "
-                "out_total=%lld)", why, row, rows, (long long)capacity, leads, up, down, ntaps, hist_len, (long long)x_total,
-                (long long)out_total);
-  }
-  if (rc) return fail("rate_pool: copying the table to the device failed");
-  HIP_OK(hipGetLastError());
-  return 0;
+  return table_done("rate_pool", rc, why, bad, "rows=%d capacity=%lld leads=%d up=%d down=%d ntaps=%d hist_len=%d x_total=%lld "
+                    "out_total=%lld", rows, (long long)capacity, leads, up, down, ntaps, hist_len, (long long)x_total,
+                    (long long)out_total);
 }
 
 static void beat_geom_text(const ral_beat_geom* g, char* buf, size_t n) {
@@ -1758,17 +1751,11 @@ int ral_beat_pool(float* hist, const float* x, int64_t x_total, const ral_beat_r
   const int rc = launch_beat_pool(hist, x, (long long)x_total, table, rows, table_dev, upload, (long long)capacity, leads, geom, bank,
                                   ntaps, hist_len, scratch, (long long)scratch_bytes, (long long*)peaks, (long long)peaks_total, count,
                                   (hipStream_t)s, &why, &bad);
-  if (rc == -1) {
-    char row[32] = "", gt[160];
-    if (bad >= 0) snprintf(row, sizeof(row), " in row %d", bad);
-    beat_geom_text(geom, gt, sizeof(gt));
-    return fail("beat_pool: need %s%s (rows=%d capacity=%lld leads=%d ntaps=%d hist_len=%d x_total=%lld peaks_total=%lld "
-                "scratch_bytes=%lld %s)", why, row, rows, (long long)capacity, leads, ntaps, hist_len, (long long)x_total,
-                (long long)peaks_total, (long long)scratch_bytes, gt);
-  }
-  if (rc) return fail("beat_pool: copying the table to the device failed");
-  HIP_OK(hipGetLastError());
-  return 0;
+  char gt[160] = "";
+  if (rc) beat_geom_text(geom, gt, sizeof(gt));
+  return table_done("beat_pool", rc, why, bad, "rows=%d capacity=%lld leads=%d ntaps=%d hist_len=%d x_total=%lld "
+                    "peaks_total=%lld scratch_bytes=%lld %s", rows, (long long)capacity, leads, ntaps, hist_len, (long long)x_total,
+                    (long long)peaks_total, (long long)scratch_bytes, gt);
 }
 
 int ral_beat_match(const int32_t* ref, const int32_t* ref_count, int64_t ref_cap, const int32_t* det, const int32_t* det_count,
@@ -1828,17 +1815,11 @@ int ral_rhythm_pool(const float* hist, const float* x, int64_t x_total, const ra
                                     hist_len, ring, (long long*)ring_pos, (const long long*)new_pos, (long long)new_total, scratch,
                                     (long long)scratch_bytes, (long long*)out_pos, label, corr, rr_ratio, (long long)out_total,
                                     (hipStream_t)s, &why, &bad);
-  if (rc == -1) {
-    char row[32] = "", gt[96];
-    if (bad >= 0) snprintf(row, sizeof(row), " in row %d", bad);
-    rhythm_geom_text(geom, gt, sizeof(gt));
-    return fail("rhythm_pool: need %s%s (rows=%d capacity=%lld leads=%d hist_len=%d x_total=%lld new_total=%lld out_total=%lld "
-                "scratch_bytes=%lld %s)", why, row, rows, (long long)capacity, leads, hist_len, (long long)x_total,
-                (long long)new_total, (long long)out_total, (long long)scratch_bytes, gt);
-  }
-  if (rc) return fail("rhythm_pool: copying the table to the device failed");
-  HIP_OK(hipGetLastError());
-  return 0;
+  char gt[96] = "";
+  if (rc) rhythm_geom_text(geom, gt, sizeof(gt));
+  return table_done("rhythm_pool", rc, why, bad, "rows=%d capacity=%lld leads=%d hist_len=%d x_total=%lld new_total=%lld "
+                    "out_total=%lld scratch_bytes=%lld %s", rows, (long long)capacity, leads, hist_len, (long long)x_total,
+                    (long long)new_total, (long long)out_total, (long long)scratch_bytes, gt);
 }
 
 int ral_hrv_windows(const int32_t* pos, const int32_t* label_or_null, const int32_t* count, int64_t R, int64_t cap,
@@ -1850,16 +1831,9 @@ int ral_hrv_windows(const int32_t* pos, const int32_t* label_or_null, const int3
   long long bad = -1;
   const int rc = launch_hrv_windows(pos, label_or_null, count, (long long)R, (long long)cap, table, (long long)rows, table_dev,
                                     upload, geom, band, counts, stats, psd_or_null, (hipStream_t)s, &why, &bad);
-  if (rc == -1) {
-    char row[40] = "";
-    if (bad >= 0) snprintf(row, sizeof(row), " in row %lld", bad);
-    return fail("hrv_windows: need %s%s (R=%lld cap=%lld rows=%lld W=%d lo_n=%d hi_n=%d t50=%d F=%d min_nn=%d fs=%g)", why, row,
-                (long long)R, (long long)cap, (long long)rows, geom->W, geom->lo_n, geom->hi_n, geom->t50, geom->F, geom->min_nn,
-                geom->fs);
-  }
-  if (rc) return fail("hrv_windows: copying the table to the device failed");
-  HIP_OK(hipGetLastError());
-  return 0;
+  return table_done("hrv_windows", rc, why, bad, "R=%lld cap=%lld rows=%lld W=%d lo_n=%d hi_n=%d t50=%d F=%d min_nn=%d fs=%g",
+                    (long long)R, (long long)cap, (long long)rows, geom->W, geom->lo_n, geom->hi_n, geom->t50, geom->F,
+                    geom->min_nn, geom->fs);
 }
 
 int ral_wavelet_denoise(const float* x, float* y, int64_t rows, int L, float threshold, ral_stream s) {

@@ -20,9 +20,9 @@
 //            applies the rules, refines in f, and writes its peaks in order (a scan over the threads' counts) and their number.
 //   gather   one workgroup per row scans the tile counts and copies the tiles' peaks in order; no atomic anywhere.
 #include "ral_kernels.hpp"
+#include "ral_slots.hpp"
 #include <math.h>
 #include <stdint.h>
-#include <vector>
 
 namespace {
 
@@ -55,14 +55,6 @@ RAL_DEV void beat_spans(BeatRow& rw, const BeatGeom& g) {
   rw.fhi = d > rw.N ? rw.N : d;
 }
 
-// sample `pos` of the row's lead, clamped to [0, N - 1]
-RAL_DEV float beat_sample(const BeatRow& rw, int lead, long long pos) {
-  pos = pos < 0 ? 0 : (pos > rw.N - 1 ? rw.N - 1 : pos);
-  if (pos >= rw.n0) return rw.chunk[lead * rw.chunk_stride + (pos - rw.n0)];
-  const long long hi = rw.hist_len - (rw.n0 - pos);     // (below 0 only for values that are discarded: halo and padded taps)
-  return rw.hist[(size_t)lead * rw.hist_len + (hi < 0 ? 0 : hi)];
-}
-
 // f and m on [a, a + cnt), cnt <= g.tile.  hl: nt4 floats, xs: leads * g.xs, fl: g.fn; each 16-byte aligned
 RAL_DEV void beat_feature_tile(const BeatRow& rw, long long a, int cnt, const BeatGeom& g, const float* __restrict__ bank, float* hl,
                                float* xs, float* fl) {
@@ -70,8 +62,9 @@ RAL_DEV void beat_feature_tile(const BeatRow& rw, long long a, int cnt, const Be
   for (int e = tid; e < g.nt4; e += BEAT_THREADS) hl[e] = e < g.ntaps ? bank[e] : 0.f;
   const long long fa = a - g.wi;
   const long long xb = fa + g.half - g.nt4;
-  for (int lead = 0; lead < g.leads; ++lead)
-    for (int w = tid; w < g.xs; w += BEAT_THREADS) xs[lead * g.xs + w] = beat_sample(rw, lead, xb + w);
+  for (int lead = 0; lead < g.leads; ++lead)      // (older than the history only for values that are discarded: halo and padded taps)
+    for (int w = tid; w < g.xs; w += BEAT_THREADS)
+      xs[lead * g.xs + w] = slot_sample(rw.chunk, rw.chunk_stride, rw.hist, rw.hist_len, rw.n0, rw.N, lead, xb + w);
   __syncthreads();
 
   const int q4 = g.nt4 >> 2;
@@ -242,7 +235,7 @@ RAL_DEV BeatRow beat_pool_row(const float* hist, const float* x, const BeatPoolR
                               const BeatGeom& g, const BeatScratch& sc) {
   BeatRow rw;
   rw.chunk = x + t.x_off * g.leads;
-  rw.hist = hist + ((size_t)t.turn * cap + t.slot) * g.leads * hist_len;
+  rw.hist = hist + slot_plane(t.turn, t.slot, cap, g.leads, hist_len);
   rw.chunk_stride = t.c, rw.n0 = t.n0, rw.N = t.n0 + t.c, rw.d0 = t.d0, rw.d1 = t.d0 + t.d, rw.hist_len = hist_len;
   rw.f = sc.f + row * sc.S, rw.m = sc.m + row * sc.S;
   beat_spans(rw, g);
@@ -289,11 +282,9 @@ __global__ __launch_bounds__(BEAT_THREADS) void k_beat_feature_pool(float* hist,
   const BeatRow rw = beat_pool_row(hist, x, t, blockIdx.y, cap, hist_len, g, sc);
   if (blockIdx.x == gridDim.x - 1) {
     if (!(t.flags & RAL_POOL_KEEP)) return;
-    float* dst = hist + ((size_t)(1 - t.turn) * cap + t.slot) * g.leads * hist_len;
-    const long long first = rw.N - hist_len;          // the stream position of dst[0]
     for (int lead = 0; lead < g.leads; ++lead)
-      for (int l = threadIdx.x; l < hist_len; l += BEAT_THREADS)
-        dst[(size_t)lead * hist_len + l] = first + l < 0 ? 0.f : beat_sample(rw, lead, first + l);
+      slot_write_history(rw.hist + (size_t)lead * hist_len, rw.chunk + lead * rw.chunk_stride,
+                         hist + slot_plane(1 - t.turn, t.slot, cap, g.leads, hist_len, lead), t.n0, t.c, hist_len);
     return;
   }
   const long long a = rw.flo + (long long)blockIdx.x * g.tile;
@@ -398,22 +389,14 @@ const char* beat_pool_fault(const BeatPoolRow* tab, int rows, long long cap, con
   if (x_total < 0 || peaks_total < 0) return "x_total, peaks_total >= 0";
   if (!walk) return nullptr;
   const long long big = 1LL << 40;
-  std::vector<bool> seen((size_t)cap, false);
-  for (int r = 0; r < rows; ++r) {
-    const BeatPoolRow& t = tab[r];
-    *bad = r;
-    if (t.slot < 0 || t.slot >= cap) return "0 <= slot < capacity";
-    if (seen[(size_t)t.slot]) return "every slot at most once";
-    seen[(size_t)t.slot] = true;
-    if (t.n0 < 0 || t.n0 > big || t.d0 < 0 || t.d0 > big || t.c < 0 || t.c > 0x3fffffff || t.d < 0 || t.cap < 0)
-      return "0 <= n0, d0 <= 2^40, 0 <= c < 2^30, d >= 0 and cap >= 0";
-    if (t.turn != 0 && t.turn != 1) return "turn 0 or 1";
-    if (t.flags & ~(RAL_POOL_KEEP)) return "flags RAL_POOL_KEEP or 0";
-    if (t.T >= 0 ? (t.T < 1 || t.T != t.n0 + t.c || (t.flags & RAL_POOL_KEEP)) : (t.T != -1 || !(t.flags & RAL_POOL_KEEP)))
-      return "T = n0 + c >= 1 without RAL_POOL_KEEP, or T = -1 with RAL_POOL_KEEP";
-    if (t.x_off < 0 || t.x_off + t.c > x_total) return "the chunk inside the packed chunks";
+  const SlotRules rules{1, false, "0 <= n0, d0 <= 2^40, 0 <= c < 2^30, d >= 0 and cap >= 0",
+                        "T = n0 + c >= 1 without RAL_POOL_KEEP, or T = -1 with RAL_POOL_KEEP"};
+  auto in_range = [&](const BeatPoolRow& t) {
+    return !(t.n0 < 0 || t.n0 > big || t.d0 < 0 || t.d0 > big || t.c < 0 || t.c > 0x3fffffff || t.d < 0 || t.cap < 0);
+  };
+  auto own = [&](const BeatPoolRow& t) -> const char* {
     if (t.out_off < 0 || t.out_off + t.cap > peaks_total) return "the row's peaks inside the packed peaks";
-    if (t.d == 0) continue;
+    if (t.d == 0) return nullptr;
     const long long n1 = t.n0 + t.c;
     if (t.T < 0 ? t.d0 + t.d + lat > n1 : t.d0 + t.d > n1)
       return "decisions that are final: d0 + d + Wt + Wi + half <= n0 + c, or d0 + d <= T at the end";
@@ -421,9 +404,9 @@ const char* beat_pool_fault(const BeatPoolRow* tab, int rows, long long cap, con
     long long oldest = t.d0 - lat;
     if (oldest < 0) oldest = 0;
     if (oldest < t.n0 - hist_len) return "the oldest sample of decision d0 inside the history";
-  }
-  *bad = -1;
-  return nullptr;
+    return nullptr;
+  };
+  return slots_walk(tab, rows, cap, x_total, rules, in_range, SlotNoRule{}, own, bad);
 }
 
 // S of a pool call: the longest span of f over its rows (at least 1)
@@ -488,7 +471,7 @@ int launch_beat_pool(float* hist, const float* x, long long x_total, const ral_b
   long long d_max = 0;
   for (int r = 0; r < rows; ++r) d_max = tab[r].d > d_max ? tab[r].d : d_max;
   const long long ft = (S + g.tile - 1) / g.tile, pt = (d_max + BEAT_PICK - 1) / BEAT_PICK;
-  if (upload && hipMemcpyAsync(tab_dev, tab, (size_t)rows * sizeof(ral_beat_row), hipMemcpyHostToDevice, s) != hipSuccess) return -2;
+  if (upload && slots_upload(tab, rows, tab_dev, s)) return -2;
   k_beat_feature_pool<<<dim3((unsigned)ft + 1, (unsigned)rows), BEAT_THREADS, beat_feature_lds_bytes(g), s>>>(hist, x, tab_dev, cap,
                                                                                                             hist_len, g, bank, sc);
   if (pt > 0)

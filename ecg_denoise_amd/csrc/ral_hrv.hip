@@ -17,6 +17,7 @@
 //   bands      lanes 0 .. 3 of wave 0 add the bins of VLF, LF, HF and of all bands, each sequentially in ascending k
 // No floating-point atomics, no scratch memory: the order of every floating-point sum depends on the geometry and on m alone.
 #include "ral_kernels.hpp"
+#include "ral_slots.hpp"
 #include <math.h>
 #include <stdint.h>
 
@@ -241,7 +242,7 @@ int launch_hrv_windows(const int* pos, const int* label, const int* count, long 
       if (t.w0 < 0 || t.w1 <= t.w0 || t.w1 > t.w0 + g.W) { *why = "0 <= w0 < w1 <= w0 + W"; return -1; }
     }
     *bad = -1;
-    if (hipMemcpyAsync(tab_dev, tab, (size_t)rows * sizeof(ral_hrv_row), hipMemcpyHostToDevice, s) != hipSuccess) return -2;
+    if (slots_upload(tab, rows, tab_dev, s)) return -2;
   }
   const size_t lds = ((size_t)2 * g.max_m + g.nd) * 4;
   k_hrv_windows<<<dim3((unsigned)rows), HV_THREADS, lds, s>>>(pos, label, count, cap, tab_dev, g, band, counts, stats, psd);

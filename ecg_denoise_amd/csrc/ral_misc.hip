@@ -7,6 +7,7 @@
 
 #include "ral_device.hpp"
 #include "ral_kernels.hpp"
+#include "ral_slots.hpp"
 
 // block-wide sum of NV per-thread values -> double atomics into out[0..NV)
 template <int NV>
@@ -1154,13 +1155,11 @@ int launch_newrale_live_back(const float* iy, const float* stats, const float* p
 
 // =================================================================================
 // Stream pool (LivePool / NewRALELivePool, infer.py): the live kernels with every per-call scalar replaced by a row of a table,
-// ral_pool_row (include/ralenet.h), one row per stream the call names.  A slot of the pool keeps its last L samples in one of
-// two history planes, hist (2, capacity, leads, L): a row reads plane `turn` of its slot, and the history workgroups of the
-// call's first gather launch write the other plane for the rows that stay open (RAL_POOL_KEEP) - no workgroup reads what
-// another one writes, and the slots of a call are distinct.  V of a row is its history ++ its chunk, samples
-// [n0 - L, n0 + c) of the stream; positions below sample 0 are never read and are written as zeros.  Window gw of the call is
-// window k0 + (gw - w_off) of the row found by pool_find_row (the rows' w_off are the prefix sums of their nw).  The window
-// arithmetic is that of the live kernels: zscore_wave, stream_keep / stream_keep_open, stream_start, stream_kept.
+// ral_pool_row (include/ralenet.h), one row per stream the call names.  The slots, their two history planes of L samples and
+// the rows' shared fields follow the slot protocol (ral_slots.hpp); the history workgroups of the call's first gather launch
+// write the next history.  V of a row is its history ++ its chunk, samples [n0 - L, n0 + c) of the stream.  Window gw of the
+// call is window k0 + (gw - w_off) of the row found by pool_find_row (the rows' w_off are the prefix sums of their nw).  The
+// window arithmetic is that of the live kernels: zscore_wave, stream_keep / stream_keep_open, stream_start, stream_kept.
 // =================================================================================
 typedef ral_pool_row PoolRow;
 
@@ -1198,26 +1197,20 @@ RAL_DEV void pool_kept(const StreamKeep& sk, const PoolRow& t, int k, long long 
 }
 
 // the next history of (row, lead): V[c, c + L), the last L samples the stream has received after this call
-RAL_DEV void pool_write_history(const PoolRow& t, int c, int leads, int L, size_t plane, float* hist, const float* __restrict__ x) {
-  const float* hr = hist + (size_t)t.turn * plane + ((size_t)t.slot * leads + c) * L;
-  const float* xr = x + t.x_off * leads + (long long)c * t.c - L;
-  float* dst = hist + (size_t)(1 - t.turn) * plane + ((size_t)t.slot * leads + c) * L;
-  const long long first = t.n0 + t.c - L;       // the stream position of dst[0]
-  for (int l = threadIdx.x; l < L; l += blockDim.x) {
-    const int v = t.c + l;
-    dst[l] = first + l < 0 ? 0.f : (v < L ? hr[v] : xr[v]);
-  }
+RAL_DEV void pool_write_history(const PoolRow& t, int c, int leads, int L, long long cap, float* hist,
+                                const float* __restrict__ x) {
+  slot_write_history(hist + slot_plane(t.turn, t.slot, cap, leads, L, c), x + t.x_off * leads + (long long)c * t.c,
+                     hist + slot_plane(1 - t.turn, t.slot, cap, leads, L, c), t.n0, t.c, L);
 }
 
 __global__ __launch_bounds__(64) void k_pool_windows(float* hist, const float* __restrict__ x, const PoolRow* __restrict__ tab,
                                                      int rows, long long cap, int leads, int L, int hop, long long w0, int nb,
                                                      float* __restrict__ win, float* __restrict__ stats) {
   const int nwl = nb * leads;
-  const size_t plane = (size_t)cap * leads * L;
   if ((int)blockIdx.x >= nwl) {   // the history of one (row, lead)
     const int rc = blockIdx.x - nwl, r = rc / leads;
     const PoolRow t = tab[r];
-    if (t.flags & RAL_POOL_KEEP) pool_write_history(t, rc - r * leads, leads, L, plane, hist, x);
+    if (t.flags & RAL_POOL_KEEP) pool_write_history(t, rc - r * leads, leads, L, cap, hist, x);
     return;
   }
   const int i = blockIdx.x / leads, c = blockIdx.x - i * leads;   // window of this launch, lead
@@ -1226,7 +1219,7 @@ __global__ __launch_bounds__(64) void k_pool_windows(float* hist, const float* _
   const StreamKeep sk = pool_keep(t, L, hop);
   const int j = (int)(gw - t.w_off);
   const int o = (int)(stream_start(sk, (int)t.k0 + j, t.T, L, hop) - (t.n0 - L));   // the window is V[o, o + L)
-  const float* hr = hist + (size_t)t.turn * plane + ((size_t)t.slot * leads + c) * L;
+  const float* hr = hist + slot_plane(t.turn, t.slot, cap, leads, L, c);
   const float* xr = x + t.x_off * leads + (long long)c * t.c - L;
   float mean, sd;
   zscore_wave([=](int l) { const int v = o + l; return v < L ? hr[v] : xr[v]; }, win + ((size_t)i * leads + c) * L, L, mean, sd);
@@ -1259,8 +1252,8 @@ __global__ __launch_bounds__(64) void k_pool_emit(const float* __restrict__ y, c
   }
 }
 
-// The table is checked here, on the host, before anything reaches the device: a wrong row would send a kernel out of bounds.
-// -> null if the table is sound, else the rule that is broken, with *bad the row that breaks it (-1: the geometry).
+// The table is checked here, on the host, before anything reaches the device (slots_walk, ral_slots.hpp, with the window pools'
+// own rules).  -> null if the table is sound, else the rule that is broken, with *bad the row that breaks it (-1: the geometry).
 // x_total / out_total: samples per lead in the packed chunk / output buffer (ignored when negative: the emit / gather does not
 // touch that buffer).  from_last: the table of an emit of kept windows (one window per row, the last regular one before n0).
 // walk = false (a launch that reuses the device copy of a table checked at its upload): the geometry only.
@@ -1273,23 +1266,18 @@ static const char* pool_table_fault(const PoolRow* tab, int rows, long long cap,
   if (L < lmul || L % lmul != 0 || L > lmax) return lmul == 64 ? "L a multiple of 64 and <= 2048" : "L a multiple of 16 in [16, 1024]";
   if (hop < 1 || hop > L || ((L - hop) & 1)) return "1 <= hop <= L with L - hop even";
   if (!walk) return nullptr;
-  std::vector<bool> seen((size_t)cap, false);
+  const SlotRules rules{L, true, "n0, c, nw, m, k0, lo >= 0 and c < 2^30",
+                        "T = n0 + c >= L without RAL_POOL_KEEP, or T = -1 with RAL_POOL_KEEP and c >= 1"};
   long long w_sum = 0;
-  for (int r = 0; r < rows; ++r) {
-    const PoolRow& t = tab[r];
-    *bad = r;
-    if (t.slot < 0 || t.slot >= cap) return "0 <= slot < capacity";
-    if (seen[(size_t)t.slot]) return "every slot at most once";
-    seen[(size_t)t.slot] = true;
-    if (t.n0 < 0 || t.c < 0 || t.c > 0x3fffffff || t.nw < 0 || t.m < 0 || t.k0 < 0 || t.lo < 0)
-      return "n0, c, nw, m, k0, lo >= 0 and c < 2^30";
-    if (t.turn != 0 && t.turn != 1) return "turn 0 or 1";
-    if (t.flags & ~(RAL_POOL_KEEP)) return "flags RAL_POOL_KEEP or 0";
-    if (t.T >= 0 ? (t.T < L || t.T != t.n0 + t.c || (t.flags & RAL_POOL_KEEP)) : (t.T != -1 || !(t.flags & RAL_POOL_KEEP) || t.c < 1))
-      return "T = n0 + c >= L without RAL_POOL_KEEP, or T = -1 with RAL_POOL_KEEP and c >= 1";
+  auto in_range = [](const PoolRow& t) {
+    return !(t.n0 < 0 || t.c < 0 || t.c > 0x3fffffff || t.nw < 0 || t.m < 0 || t.k0 < 0 || t.lo < 0);
+  };
+  auto early = [&](const PoolRow& t) -> const char* {
     if (t.w_off != w_sum) return "w_off the prefix sum of nw";
     w_sum += t.nw;
-    if (x_total >= 0 && (t.x_off < 0 || t.x_off + t.c > x_total)) return "the chunk inside the packed chunks";
+    return nullptr;
+  };
+  auto own = [&](const PoolRow& t) -> const char* {
     if (out_total >= 0 && (t.out_off < 0 || t.out_off + t.m > out_total)) return "the emitted samples inside the packed output";
     if (t.lo + t.m > t.n0 + t.c) return "lo + m <= n0 + c (nothing emitted that was not received)";
     if (from_last) {   // the last regular window complete at n0: it ends at or before n0, the next one would not
@@ -1305,8 +1293,9 @@ static const char* pool_table_fault(const PoolRow* tab, int rows, long long cap,
       if (last + L > t.n0 + t.c) return "the last window inside the received samples, n0 + c";
       if (t.lo < first || t.lo + t.m > last + L) return "[lo, lo + m) inside the windows";
     }
-  }
-  *bad = -1;
+    return nullptr;
+  };
+  if (const char* why = slots_walk(tab, rows, cap, x_total, rules, in_range, early, own, bad)) return why;
   return w_sum <= 0x7fffffffLL ? nullptr : "at most 2^31 - 1 windows";
 }
 
@@ -1338,16 +1327,12 @@ static const char* pool_emit_fault(const PoolRow* tab, int rows, long long cap, 
   return nullptr;
 }
 
-static int pool_upload(const PoolRow* tab, int rows, PoolRow* tab_dev, hipStream_t s) {
-  return hipMemcpyAsync(tab_dev, tab, (size_t)rows * sizeof(PoolRow), hipMemcpyHostToDevice, s) == hipSuccess ? 0 : -2;
-}
-
 int launch_pool_windows(float* hist, const float* x, long long x_total, const ral_pool_row* tab, int rows, ral_pool_row* tab_dev,
                         int upload, long long cap, int leads, int L, int hop, int write_hist, long long w0, int nb, float* win,
                         float* stats, hipStream_t s, const char** why, int* bad) {
   if ((*why = pool_gather_fault(tab, rows, cap, leads, L, hop, 64, 2048, x_total, upload, write_hist, w0, nb, bad))) return -1;
   const long long grid = (long long)nb * leads + (write_hist ? (long long)rows * leads : 0);
-  if (upload && pool_upload(tab, rows, tab_dev, s)) return -2;
+  if (upload && slots_upload(tab, rows, tab_dev, s)) return -2;
   k_pool_windows<<<(int)grid, 64, 0, s>>>(hist, x, tab_dev, rows, cap, leads, L, hop, w0, nb, win, stats);
   return 0;
 }
@@ -1357,7 +1342,7 @@ int launch_pool_emit(const float* y, const float* stats, const ral_pool_row* tab
                      long long out_total, float* last_y, float* last_stats, hipStream_t s, const char** why, int* bad) {
   if ((*why = pool_emit_fault(tab, rows, cap, leads, L, hop, 64, 2048, out_total, upload, w0, nb, from_last, last_y, last_stats, bad)))
     return -1;
-  if (upload && pool_upload(tab, rows, tab_dev, s)) return -2;
+  if (upload && slots_upload(tab, rows, tab_dev, s)) return -2;
   k_pool_emit<<<nb * leads, 64, 0, s>>>(y, stats, tab_dev, rows, leads, L, hop, w0, from_last, out, last_y, last_stats);
   return 0;
 }
@@ -1378,7 +1363,7 @@ struct NrPoolWindows {
     const StreamKeep sk = pool_keep(t, L, hop);
     const int j = (int)(gw - t.w_off);
     src.o = pool_uniform((int)(stream_start(sk, (int)t.k0 + j, t.T, L, hop) - (t.n0 - L)));
-    src.hr = hist + pool_uniform((long long)(((size_t)t.turn * cap + t.slot) * NR_LEADS * L));
+    src.hr = hist + pool_uniform((long long)slot_plane(t.turn, t.slot, cap, NR_LEADS, L));
     src.xr = x + pool_uniform((long long)(t.x_off * NR_LEADS - L));
     src.L = L;
     src.C = pool_uniform(t.c);
@@ -1389,7 +1374,7 @@ struct NrPoolWindows {
     for (int rc = g; rc < rows * NR_LEADS; rc += ng) {
       const int r = rc / NR_LEADS;
       const PoolRow t = tab[r];
-      if (t.flags & RAL_POOL_KEEP) pool_write_history(t, rc - r * NR_LEADS, NR_LEADS, L, (size_t)cap * NR_LEADS * L, hist, x);
+      if (t.flags & RAL_POOL_KEEP) pool_write_history(t, rc - r * NR_LEADS, NR_LEADS, L, cap, hist, x);
     }
   }
 };
@@ -1431,7 +1416,7 @@ int launch_newrale_pool_front(float* hist, const float* x, long long x_total, co
                               ral_pool_row* tab_dev, int upload, long long cap, int L, int hop, int write_hist, long long w0,
                               int nb, const float* prm, float* inner, float* stats, hipStream_t s, const char** why, int* bad) {
   if ((*why = pool_gather_fault(tab, rows, cap, NR_LEADS, L, hop, 16, 1024, x_total, upload, write_hist, w0, nb, bad))) return -1;
-  if (upload && pool_upload(tab, rows, tab_dev, s)) return -2;
+  if (upload && slots_upload(tab, rows, tab_dev, s)) return -2;
   const long long hrows = (long long)rows * NR_LEADS;
   const int nwg = nb < NR_GRID ? nb : NR_GRID;
   const int nhg = write_hist ? (int)(hrows < NR_GRID ? hrows : NR_GRID) : 0;
@@ -1448,7 +1433,7 @@ int launch_newrale_pool_back(const float* iy, const float* stats, const float* p
   if ((*why = pool_emit_fault(tab, rows, cap, NR_LEADS, L, hop, 16, 1024, out_total, upload, w0, nb, from_last, last_y, last_stats,
                               bad)))
     return -1;
-  if (upload && pool_upload(tab, rows, tab_dev, s)) return -2;
+  if (upload && slots_upload(tab, rows, tab_dev, s)) return -2;
   const size_t lds = newrale_back_lds(L);
   RAL_SET_LDS(k_newrale_back<NrPoolKeep>, lds);
   k_newrale_back<<<nb < NR_GRID ? nb : NR_GRID, 256, lds, s>>>(NrPoolKeep{out, last_y, last_stats, tab_dev, w0, rows, L, hop, from_last},

@@ -18,8 +18,8 @@
 // rate_tile is the only place that forms an output, for whole records and for pool chunks alike: a record is a stream that
 // has received nothing before (n0 = 0) and gets all T samples now, so both read the same staged values through the same code.
 #include "ral_kernels.hpp"
+#include "ral_slots.hpp"
 #include <stdint.h>
-#include <vector>
 
 namespace {
 
@@ -45,15 +45,6 @@ struct RateRow {
 
 RAL_DEV int rate_word(const void* p) { return (int)(((uintptr_t)p >> 2) & 3); }
 
-// sample `pos` of the stream, clamped to what it holds
-RAL_DEV float rate_sample(const RateRow& rw, long long pos) {
-  const long long last = rw.n0 + rw.c - 1;
-  pos = pos < 0 ? 0 : (pos > last ? last : pos);
-  if (pos >= rw.n0) return rw.chunk[pos - rw.n0];
-  long long hi = rw.hist_len - (rw.n0 - pos);     // (the host has checked that the call needs nothing older than the history)
-  return rw.hist[hi < 0 ? 0 : hi];
-}
-
 // outputs [m0 + j0, m0 + j0 + cnt) of one row.  bl, xs, os: the three LDS regions, each 16-byte aligned
 RAL_DEV void rate_tile(const RateRow& rw, long long j0, int cnt, const RateGeom& g, const float* __restrict__ bank, float* bl,
                        float* xs, float* os) {
@@ -72,7 +63,8 @@ RAL_DEV void rate_tile(const RateRow& rw, long long j0, int cnt, const RateGeom&
     bl[e] = j < g.ntaps ? bank[j] : 0.f;
   }
 
-  // the span.  Word w of xs holds sample n_first - ax + w; the chunk is the part of the stream that float4 loads may touch
+  // the span.  Word w of xs holds sample n_first - ax + w, clamped to what the stream holds (the host has checked that the call
+  // needs nothing older than the history); the chunk is the part of the stream that float4 loads may touch
   const long long c_lo = rw.n0, c_hi = rw.n0 + rw.c;
   const int ax = (int)(((long long)rate_word(rw.chunk) + ((n_first - c_lo) & 3)) & 3);
   for (int gi = tid; gi < (ax + count + 3) >> 2; gi += RATE_THREADS) {
@@ -82,7 +74,7 @@ RAL_DEV void rate_tile(const RateRow& rw, long long j0, int cnt, const RateGeom&
     } else {
       for (int e = 0; e < 4; ++e) {
         const int w = 4 * gi + e;
-        if (w >= ax && w < ax + count) xs[w] = rate_sample(rw, pos + e);
+        if (w >= ax && w < ax + count) xs[w] = slot_sample(rw.chunk, 0, rw.hist, rw.hist_len, rw.n0, c_hi, 0, pos + e);
       }
     }
   }
@@ -142,17 +134,11 @@ __global__ __launch_bounds__(RATE_THREADS) void k_rate_pool(float* hist, const f
   extern __shared__ __attribute__((aligned(16))) float rate_smem[];
   const int r = blockIdx.y / leads, lead = blockIdx.y - r * leads;
   const RatePoolRow t = tab[r];
-  const size_t plane = (size_t)cap * leads * hist_len;
-  const float* hr = hist + (size_t)t.turn * plane + ((size_t)t.slot * leads + lead) * hist_len;
+  const float* hr = hist + slot_plane(t.turn, t.slot, cap, leads, hist_len, lead);
   const float* chunk = x + (t.x_off * leads + (long long)lead * t.c);
-  if (blockIdx.x == gridDim.x - 1) {      // V[c, c + hist_len): the last hist_len samples the stream has received now
-    if (!(t.flags & RAL_POOL_KEEP)) return;
-    float* dst = hist + (size_t)(1 - t.turn) * plane + ((size_t)t.slot * leads + lead) * hist_len;
-    const long long first = t.n0 + t.c - hist_len;       // the stream position of dst[0]
-    for (int l = threadIdx.x; l < hist_len; l += RATE_THREADS) {
-      const long long v = (long long)t.c + l;
-      dst[l] = first + l < 0 ? 0.f : (v < hist_len ? hr[v] : chunk[v - hist_len]);
-    }
+  if (blockIdx.x == gridDim.x - 1) {
+    if (t.flags & RAL_POOL_KEEP)
+      slot_write_history(hr, chunk, hist + slot_plane(1 - t.turn, t.slot, cap, leads, hist_len, lead), t.n0, t.c, hist_len);
     return;
   }
   const long long j0 = (long long)blockIdx.x * g.tile;
@@ -203,22 +189,14 @@ const char* rate_pool_fault(const RatePoolRow* tab, int rows, long long cap, int
   if (x_total < 0 || out_total < 0) return "x_total, out_total >= 0";
   if (!walk) return nullptr;
   const long long big = 1LL << 40;
-  std::vector<bool> seen((size_t)cap, false);
-  for (int r = 0; r < rows; ++r) {
-    const RatePoolRow& t = tab[r];
-    *bad = r;
-    if (t.slot < 0 || t.slot >= cap) return "0 <= slot < capacity";
-    if (seen[(size_t)t.slot]) return "every slot at most once";
-    seen[(size_t)t.slot] = true;
-    if (t.n0 < 0 || t.n0 > big || t.m0 < 0 || t.m0 > big || t.c < 0 || t.c > 0x3fffffff || t.m < 0)
-      return "0 <= n0, m0 <= 2^40, 0 <= c < 2^30 and m >= 0";
-    if (t.turn != 0 && t.turn != 1) return "turn 0 or 1";
-    if (t.flags & ~(RAL_POOL_KEEP)) return "flags RAL_POOL_KEEP or 0";
-    if (t.T >= 0 ? (t.T < 1 || t.T != t.n0 + t.c || (t.flags & RAL_POOL_KEEP)) : (t.T != -1 || !(t.flags & RAL_POOL_KEEP)))
-      return "T = n0 + c >= 1 without RAL_POOL_KEEP, or T = -1 with RAL_POOL_KEEP";
-    if (t.x_off < 0 || t.x_off + t.c > x_total) return "the chunk inside the packed chunks";
+  const SlotRules rules{1, false, "0 <= n0, m0 <= 2^40, 0 <= c < 2^30 and m >= 0",
+                        "T = n0 + c >= 1 without RAL_POOL_KEEP, or T = -1 with RAL_POOL_KEEP"};
+  auto in_range = [&](const RatePoolRow& t) {
+    return !(t.n0 < 0 || t.n0 > big || t.m0 < 0 || t.m0 > big || t.c < 0 || t.c > 0x3fffffff || t.m < 0);
+  };
+  auto own = [&](const RatePoolRow& t) -> const char* {
     if (t.out_off < 0 || t.out_off + t.m > out_total) return "the emitted samples inside the packed output";
-    if (t.m == 0) continue;
+    if (t.m == 0) return nullptr;
     const long long n1 = t.n0 + t.c, last = t.m0 + t.m - 1;
     if (n1 < 1) return "a sample received before anything is emitted";
     if (t.T < 0 ? last * g.down + g.half >= n1 * g.up : last * g.down >= n1 * g.up)
@@ -226,9 +204,9 @@ const char* rate_pool_fault(const RatePoolRow* tab, int rows, long long cap, int
     long long oldest = (t.m0 * g.down + g.half) / g.up - (g.K - 1);
     if (oldest < 0) oldest = 0;
     if (oldest < t.n0 - hist_len) return "the oldest sample of output m0 inside the history";
-  }
-  *bad = -1;
-  return nullptr;
+    return nullptr;
+  };
+  return slots_walk(tab, rows, cap, x_total, rules, in_range, SlotNoRule{}, own, bad);
 }
 
 }  // namespace
@@ -257,7 +235,7 @@ int launch_rate_pool(float* hist, const float* x, long long x_total, const ral_r
   for (int r = 0; r < rows; ++r) m_max = tab[r].m > m_max ? tab[r].m : m_max;
   const long long tiles = (m_max + g.tile - 1) / g.tile;
   if (tiles > 0xffffffLL) { *why = "fewer than 2^24 tiles of outputs per row"; return -1; }
-  if (upload && hipMemcpyAsync(tab_dev, tab, (size_t)rows * sizeof(ral_rate_row), hipMemcpyHostToDevice, s) != hipSuccess) return -2;
+  if (upload && slots_upload(tab, rows, tab_dev, s)) return -2;
   const size_t lds = rate_lds_bytes(g);
   k_rate_pool<<<dim3((unsigned)tiles + 1, (unsigned)(rows * leads)), RATE_THREADS, lds, s>>>(hist, x, tab_dev, cap, leads, hist_len, g,
                                                                                             bank, out);

@@ -17,9 +17,9 @@
 //            pool     gather (the extended windows of the call's new beats, from the history plane and the chunk, into scratch),
 //                     classify (a wave per beat that became final), keep (the last K beats' windows and positions into the ring).
 #include "ral_kernels.hpp"
+#include "ral_slots.hpp"
 #include <math.h>
 #include <stdint.h>
-#include <vector>
 
 namespace {
 
@@ -224,20 +224,11 @@ __global__ __launch_bounds__(RH_WAVE) void k_rhythm_gather_pool(const float* __r
   const long long b = t.new_off + blockIdx.x, N = t.n0 + t.c;
   const long long first = new_pos[b] - g.wb - g.sa;
   const float* chunk = x + (size_t)t.x_off * g.leads;
-  const float* h = hist + ((size_t)t.turn * cap + t.slot) * g.leads * hist_len;
+  const float* h = hist + slot_plane(t.turn, t.slot, cap, g.leads, hist_len);
   float* dst = win + (size_t)b * g.leads * g.We;
-  for (int lead = 0; lead < g.leads; ++lead)
-    for (int e = threadIdx.x; e < g.We; e += RH_WAVE) {
-      long long at = first + e;
-      at = at < 0 ? 0 : (at > N - 1 ? N - 1 : at);
-      float v;
-      if (at >= t.n0) v = chunk[(size_t)lead * t.c + (at - t.n0)];
-      else {
-        const long long hi = hist_len - (t.n0 - at);      // (never below 0 for a beat the detector has just given)
-        v = h[(size_t)lead * hist_len + (hi < 0 ? 0 : hi)];
-      }
-      dst[(size_t)lead * g.We + e] = v;
-    }
+  for (int lead = 0; lead < g.leads; ++lead)      // (a beat the detector has just given lies inside the history)
+    for (int e = threadIdx.x; e < g.We; e += RH_WAVE)
+      dst[(size_t)lead * g.We + e] = slot_sample(chunk, t.c, h, hist_len, t.n0, N, lead, first + e);
 }
 
 // grid (beats that become final of the row with the most, rows)
@@ -310,31 +301,23 @@ const char* rhythm_pool_fault(const RhythmRow* tab, int rows, long long cap, con
   if (x_total < 0 || new_total < 0 || out_total < 0) return "x_total, new_total, out_total >= 0";
   if (!walk) return nullptr;
   const long long big = 1LL << 40;
-  std::vector<bool> seen((size_t)cap, false);
-  for (int r = 0; r < rows; ++r) {
-    const RhythmRow& t = tab[r];
-    *bad = r;
-    if (t.slot < 0 || t.slot >= cap) return "0 <= slot < capacity";
-    if (seen[(size_t)t.slot]) return "every slot at most once";
-    seen[(size_t)t.slot] = true;
-    if (t.n0 < 0 || t.n0 > big || t.c < 0 || t.c > 0x3fffffff || t.nb < 0 || t.nb > big || t.m < 0 || t.ne < 0)
-      return "0 <= n0, nb <= 2^40, 0 <= c < 2^30, m >= 0 and ne >= 0";
-    if (t.turn != 0 && t.turn != 1) return "turn 0 or 1";
-    if (t.flags & ~(RAL_POOL_KEEP)) return "flags RAL_POOL_KEEP or 0";
-    if (t.T >= 0 ? (t.T < 1 || t.T != t.n0 + t.c || (t.flags & RAL_POOL_KEEP)) : (t.T != -1 || !(t.flags & RAL_POOL_KEEP)))
-      return "T = n0 + c >= 1 without RAL_POOL_KEEP, or T = -1 with RAL_POOL_KEEP";
-    if (t.x_off < 0 || t.x_off + t.c > x_total) return "the chunk inside the packed chunks";
+  const SlotRules rules{1, false, "0 <= n0, nb <= 2^40, 0 <= c < 2^30, m >= 0 and ne >= 0",
+                        "T = n0 + c >= 1 without RAL_POOL_KEEP, or T = -1 with RAL_POOL_KEEP"};
+  auto in_range = [&](const RhythmRow& t) {
+    return !(t.n0 < 0 || t.n0 > big || t.c < 0 || t.c > 0x3fffffff || t.nb < 0 || t.nb > big || t.m < 0 || t.ne < 0);
+  };
+  auto own = [&](const RhythmRow& t) -> const char* {
     if (t.new_off < 0 || t.new_off + t.m > new_total) return "the row's new beats inside the packed new beats";
     if (t.out_off < 0 || t.out_off + t.ne > out_total) return "the row's results inside the packed results";
     if (t.m > 0 && t.n0 + t.c < 1) return "no new beat in a stream without a sample";
     const long long n = t.nb + t.m;
-    if (t.ne == 0) continue;
+    if (t.ne == 0) return nullptr;
     if (t.e0 + t.ne != n) return "results up to the stream's last beat: e0 + ne = nb + m";
     if (t.e0 != t.nb && !(t.e0 == 0 && t.nb <= RH_K)) return "e0 = nb, or e0 = 0 while the first K beats wait (nb <= K)";
     if (t.T < 0 && n < RH_K + 1) return "beats that are final: nb + m >= K + 1, or the stream ends";
-  }
-  *bad = -1;
-  return nullptr;
+    return nullptr;
+  };
+  return slots_walk(tab, rows, cap, x_total, rules, in_range, SlotNoRule{}, own, bad);
 }
 
 }  // namespace
@@ -374,7 +357,7 @@ int launch_rhythm_pool(const float* hist, const float* x, long long x_total, con
     m_max = tab[r].m > m_max ? tab[r].m : m_max;
     ne_max = tab[r].ne > ne_max ? tab[r].ne : ne_max;
   }
-  if (upload && hipMemcpyAsync(tab_dev, tab, (size_t)rows * sizeof(ral_rhythm_row), hipMemcpyHostToDevice, s) != hipSuccess) return -2;
+  if (upload && slots_upload(tab, rows, tab_dev, s)) return -2;
   float* win = (float*)scratch;
   if (m_max > 0)
     k_rhythm_gather_pool<<<dim3((unsigned)m_max, (unsigned)rows), RH_WAVE, 0, s>>>(hist, x, tab_dev, cap, hist_len, g, new_pos, win);

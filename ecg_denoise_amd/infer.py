@@ -473,7 +473,8 @@ class PoolState(SlotState):
         """shapes {sid: shape of its chunk}, close: the sids that end with this call -> (sids in row order, table, table of the
         kept last windows to emit); raises RalError for a bad argument"""
         name = self.name
-        sids, slot, lens, ends, n0 = self.named(shapes, close)
+        named = self.named(shapes, close)
+        sids, _, lens, ends, n0 = named
         if np.any((lens == 0) & ~ends):
             sid = sids[int(np.argmax((lens == 0) & ~ends))]
             raise _lib.RalError(f"{name}.push: stream {sid}: an empty chunk (only a closing stream may come without samples)")
@@ -483,10 +484,9 @@ class PoolState(SlotState):
             raise _lib.RalError(f"{name}.push: stream {sids[r]} would end shorter than one window ({int(n0[r] + lens[r])} < "
                                 f"{self.L} samples)")
         k0, nw, lo, m, T = pool_plan(n0, lens, ends, self.L, self.hop)
-        tab = np.zeros(len(sids), dtype=_lib.POOL_ROW)
-        tab["n0"], tab["T"], tab["k0"], tab["lo"], tab["slot"], tab["c"], tab["nw"], tab["m"] = n0, T, k0, lo, slot, lens, nw, m
-        tab["x_off"], tab["out_off"], tab["w_off"] = np.cumsum(lens) - lens, np.cumsum(m) - m, np.cumsum(nw) - nw
-        tab["turn"], tab["flags"] = self.turn[slot], np.where(ends, 0, _lib.POOL_KEEP)
+        tab = self.rows(_lib.POOL_ROW, named)            # (T as pool_plan gives it)
+        tab["k0"], tab["lo"], tab["nw"], tab["m"] = k0, lo, nw, m
+        tab["out_off"], tab["w_off"] = np.cumsum(m) - m, np.cumsum(nw) - nw
         # a closing stream without a further window: its last regular window so far turns out to be its last one and keeps
         # [lo, T) (with further windows that one stays regular and has given everything it keeps)
         last = tab[ends & (n0 >= self.L) & (nw == 0) & (T > lo)].copy()

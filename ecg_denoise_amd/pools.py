@@ -2,7 +2,8 @@
 planned and checked before any device work.
 
     SlotState      which slots hold an open stream, how many samples each has received, which of its two history planes is
-                   current; the argument checks every pool makes (`named`) and the common commit (`commit_rows`)
+                   current; the argument checks every pool makes (`named`), the columns every table shares (`rows`) and the
+                   common commit (`commit_rows`)
     as_chunks      a call's chunks as tensors
     pack_chunks    a call's chunks in one device buffer, row r's (leads, c) at x_off * leads
     StreamSurface  `open_streams`, `open`, `samples_in`, `close` for a class with a `.state` and a `push`
@@ -70,6 +71,20 @@ class SlotState:
         slot = np.asarray(sids, dtype=np.int64)
         ends = np.isin(slot, np.asarray(list(close), dtype=np.int64))
         return sids, slot, lens, ends, self.n[slot]
+
+    def rows(self, dtype, named, need_sample=False):
+        """named: what `named` returned -> the call's table of `dtype`, zeroed but for the columns every pool shares: n0, c, x_off
+        (the chunks packed in row order), slot, its current turn, and T = n0 + c without POOL_KEEP for a row that ends, T = -1
+        with POOL_KEEP for one that stays open.  need_sample: RalError for a stream that would end without a sample."""
+        sids, slot, lens, ends, n0 = named
+        n1 = n0 + lens
+        if need_sample and np.any(ends & (n1 < 1)):
+            r = int(np.argmax(ends & (n1 < 1)))
+            raise _lib.RalError(f"{self.name}.push: stream {sids[r]} would end without a single sample")
+        tab = np.zeros(len(sids), dtype=dtype)
+        tab["n0"], tab["T"], tab["slot"], tab["c"], tab["x_off"] = n0, np.where(ends, n1, -1), slot, lens, np.cumsum(lens) - lens
+        tab["turn"], tab["flags"] = self.turn[slot], np.where(ends, 0, _lib.POOL_KEEP)
+        return tab
 
     def commit_rows(self, tab, flip=True):
         """apply a planned call: the rows' new sample counts, the other history plane for the rows that stay open (`flip`), the

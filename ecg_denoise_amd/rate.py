@@ -180,17 +180,12 @@ class RatePoolState(SlotState):
     def plan(self, shapes, close=()):
         """shapes {sid: shape of its chunk, (leads, c) with c >= 0}, close: the sids that end with this call -> (sids in row
         order, table); raises RalError for a bad argument"""
-        sids, slot, lens, ends, n0 = self.named(shapes, close, 65535 // self.leads, "65535 (stream, lead) pairs")
-        n1 = n0 + lens
-        if np.any(ends & (n1 < 1)):
-            r = int(np.argmax(ends & (n1 < 1)))
-            raise _lib.RalError(f"{self.name}.push: stream {sids[r]} would end without a single sample")
+        named = self.named(shapes, close, 65535 // self.leads, "65535 (stream, lead) pairs")
+        sids, _, lens, ends, n0 = named
+        tab = self.rows(_lib.RATE_ROW, named, need_sample=True)
         m0 = np.asarray([self.frontier(v) for v in n0], dtype=np.int64)
-        m1 = np.asarray([self.length(v) if e else self.frontier(v) for v, e in zip(n1, ends)], dtype=np.int64)
-        tab = np.zeros(len(sids), dtype=_lib.RATE_ROW)
-        tab["n0"], tab["T"], tab["m0"], tab["slot"], tab["c"], tab["m"] = n0, np.where(ends, n1, -1), m0, slot, lens, m1 - m0
-        tab["x_off"], tab["out_off"] = np.cumsum(lens) - lens, np.cumsum(m1 - m0) - (m1 - m0)
-        tab["turn"], tab["flags"] = self.turn[slot], np.where(ends, 0, _lib.POOL_KEEP)
+        m1 = np.asarray([self.length(v) if e else self.frontier(v) for v, e in zip(n0 + lens, ends)], dtype=np.int64)
+        tab["m0"], tab["m"], tab["out_off"] = m0, m1 - m0, np.cumsum(m1 - m0) - (m1 - m0)
         return sids, tab
 
     def commit(self, tab):

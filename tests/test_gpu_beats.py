@@ -212,6 +212,23 @@ def test_pool_one_sample_chunks_a_stream_alone_and_a_short_stream():
     assert ga == want
 
 
+def test_pool_history_planes_hold_the_last_samples_received():
+    """the history itself (tests/slot_util.py): chunks around hist_len = 1314, a slot reused after both its planes were set to
+    NaN; and the peaks of all four streams still equal the record path's"""
+    from slot_util import run_with_history_checks
+    from ecg_denoise_amd import BeatPool
+    pool = BeatPool(2, 3, 360, device=DEV)
+    assert pool.hist_len == 1314
+    x = dict(U.inputs())["seed7_3x2x3000_emb6dB"]
+    long = np.concatenate([x[0], x[1]], axis=1)                      # (2, 6000)
+    recs = [torch.from_numpy(np.ascontiguousarray(r)).to(DEV) for r in (long[:, :4100], long[:, 1000:1000 + 3943], long[:, 1500:5500],
+                                                                        x[2][:, :1400])]
+    want = [_detect(r)[0] for r in recs]
+    assert sum(len(w) for w in want) >= 10
+    got = [torch.cat(outs).tolist() for outs in run_with_history_checks(pool, recs)]
+    assert got == want
+
+
 def test_pool_raising_calls_change_nothing():
     from ecg_denoise_amd import BeatPool, RalError, _lib
     from ecg_denoise_amd.model import _ptr, _stream

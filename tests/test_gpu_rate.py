@@ -170,6 +170,19 @@ def test_pool_one_sample_chunks_and_a_stream_alone():
     assert torch.equal(torch.cat(outs[a], dim=1), want[0]) and torch.equal(torch.cat(outs[b], dim=1), want[1])
 
 
+def test_pool_history_planes_hold_the_last_samples_received():
+    """the history itself (tests/slot_util.py): chunks around hist_len = 28, a slot reused after both its planes were set to
+    NaN; and the results of all four streams still equal the record path's bit for bit"""
+    from slot_util import run_with_history_checks
+    from ecg_denoise_amd import Resampler, ResamplerPool
+    pool = ResamplerPool(500, 360, leads=2, capacity=3, device=DEV)
+    assert pool.hist_len == 28
+    recs = [_signal(1, 2, T, seed=T)[0].to(DEV) for T in (140, 85, 133, 70)]
+    rs = Resampler(500, 360, DEV)
+    for rec, outs in zip(recs, run_with_history_checks(pool, recs)):
+        assert torch.equal(torch.cat(outs, dim=1), rs.convert(rec))
+
+
 # ------------------------------------------------------------------------------------------------ 3. calls that raise
 def test_pool_raising_calls_change_nothing():
     from ecg_denoise_amd import RalError, ResamplerPool, _lib
