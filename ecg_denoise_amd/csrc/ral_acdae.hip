@@ -23,7 +23,7 @@
 #include <string>
 #include <vector>
 
-#include "ral_acdae.hpp"
+#include "ral_model.hpp"
 #include "ral_device.hpp"
 
 namespace {
@@ -545,69 +545,45 @@ __global__ __launch_bounds__(256) void k_acd_dw_m(const float* __restrict__ Y, c
 // =================================================================================
 // host model
 // =================================================================================
-struct AEntry { std::string name; int64_t offset; int ndim; int64_t shape[4]; };
-struct ALayout {
-  std::vector<AEntry> e;
-  int64_t nparam = 0;
-  int64_t ew[4], eb[4], dw[4], db[4], de[4];
-};
-static int64_t aalloc(int64_t& cur, int64_t n) { const int64_t o = cur; cur += (n + 3) & ~int64_t(3); return o; }
-static void abuild(ALayout& L) {
-  int64_t cur = 0;
-  auto push = [&](const std::string& n, int64_t off, std::initializer_list<int64_t> shp) {
-    AEntry e; e.name = n; e.offset = off; e.ndim = (int)shp.size();
-    int i = 0;
-    for (auto s : shp) e.shape[i++] = s;
-    for (; i < 4; ++i) e.shape[i] = 1;
-    L.e.push_back(e);
-  };
+struct AOff { int64_t ew[4], eb[4], dw[4], db[4], de[4]; };
+static void abuild(ParamLayout& L, AOff& O) {
+  auto alloc = [&](int64_t n) { return L.alloc(n, 4); };
   for (int i = 0; i < 4; ++i) {
     const std::string p = "EncList." + std::to_string(i) + ".conv.";
-    L.ew[i] = aalloc(cur, (int64_t)ACH[i + 1] * ACH[i] * AKS[i]); L.eb[i] = aalloc(cur, ACH[i + 1]);
-    push(p + "weight", L.ew[i], {ACH[i + 1], ACH[i], AKS[i]});
-    push(p + "bias", L.eb[i], {ACH[i + 1]});
+    O.ew[i] = alloc((int64_t)ACH[i + 1] * ACH[i] * AKS[i]); O.eb[i] = alloc(ACH[i + 1]);
+    L.add(p + "weight", RAL_PARAM, O.ew[i], {ACH[i + 1], ACH[i], AKS[i]});
+    L.add(p + "bias", RAL_PARAM, O.eb[i], {ACH[i + 1]});
   }
   for (int i = 0; i < 4; ++i) {
     const std::string p = "DecList." + std::to_string(i) + ".";
     const int cin = ACH[4 - i], cout = ACH[3 - i], k = AKS[3 - i];
-    L.dw[i] = aalloc(cur, (int64_t)cin * cout * k); L.db[i] = aalloc(cur, cout); L.de[i] = aalloc(cur, 3);
-    push(p + "conv.weight", L.dw[i], {cin, cout, k});
-    push(p + "conv.bias", L.db[i], {cout});
-    push(p + "ECA.conv.weight", L.de[i], {1, 1, 3});
+    O.dw[i] = alloc((int64_t)cin * cout * k); O.db[i] = alloc(cout); O.de[i] = alloc(3);
+    L.add(p + "conv.weight", RAL_PARAM, O.dw[i], {cin, cout, k});
+    L.add(p + "conv.bias", RAL_PARAM, O.db[i], {cout});
+    L.add(p + "ECA.conv.weight", RAL_PARAM, O.de[i], {1, 1, 3});
   }
-  L.nparam = cur;
 }
 
-struct AcdaeModel {
-  AcdaePublic pub;
-  ALayout lay;
-  char* slab = nullptr;
+struct AcdaeModel : ral_handle {
+  AOff off;
   // per window: encoder outputs e[i] (C_{i+1} x L / 2^{i+1}) + argmax bytes, decoder ECA inputs a[i], scales s[i], block
   // outputs d[i] (d[3] = y is the caller's), gradients: dc[i] (conv-output gradients, C_{i+1} x L / 2^i), dt[i], G tensors
   float *e[4], *a[4], *s[4], *d[3];
-  unsigned char* am[4];
+  unsigned char* amax[4];   // argmax of each pooled encoder output
   float *dc[4], *dt[4], *gd[3], *ge[4];   // gd[i]: gradient at d[i]; ge[i]: input gradient of encoder i + 1 (at e[i])
   const float* last_x = nullptr;
   int last_B = 0;
+  int init() override;
+  int forward(const float* x, float* y, int B, int training, hipStream_t st) override;
+  int backward(const float* dy, float* dx, int B, hipStream_t st) override;
 };
 
-int acdae_check_cfg(const ral_config* c, char* err, size_t cap) {
-  if (c->leads != 2) { snprintf(err, cap, "ACDAE has 2 input channels (got leads=%d)", c->leads); return -1; }
-  if (c->L <= 0 || c->L % 64 != 0 || c->L > 1024) { snprintf(err, cap, "ACDAE: L must be a multiple of 64 and <= 1024 (got %d)", c->L); return -1; }
-  if (c->max_batch <= 0) { snprintf(err, cap, "max_batch must be positive"); return -1; }
+static int acdae_check_cfg(const ral_config* c) {
+  if (c->leads != 2) return ral_fail("ACDAE has 2 input channels (got leads=%d)", c->leads);
+  if (c->L <= 0 || c->L % 64 != 0 || c->L > 1024) return ral_fail("ACDAE: L must be a multiple of 64 and <= 1024 (got %d)", c->L);
+  if (c->max_batch <= 0) return ral_fail("max_batch must be positive");
   return 0;
 }
-int acdae_layout_count(const ral_config*) { ALayout L; abuild(L); return (int)L.e.size(); }
-int acdae_layout_entry(const ral_config*, int idx, char* name, int name_cap, int32_t* kind, int64_t* offset, int32_t* ndim,
-                       int64_t shape[4]) {
-  ALayout L; abuild(L);
-  if (idx < 0 || idx >= (int)L.e.size() || (int)L.e[idx].name.size() + 1 > name_cap) return -1;
-  strcpy(name, L.e[idx].name.c_str());
-  *kind = RAL_PARAM; *offset = L.e[idx].offset; *ndim = L.e[idx].ndim;
-  for (int i = 0; i < 4; ++i) shape[i] = L.e[idx].shape[i];
-  return 0;
-}
-int64_t acdae_param_floats(const ral_config*) { ALayout L; abuild(L); return L.nparam; }
 
 static size_t acdae_plan(const ral_config& c, AcdaeModel* m, char* base) {
   size_t cur = 0;
@@ -617,7 +593,7 @@ static size_t acdae_plan(const ral_config& c, AcdaeModel* m, char* base) {
     const size_t n = B * ACH[i + 1] * (c.L >> (i + 1));
     float* pe = reinterpret_cast<float*>(take(n * 4));
     unsigned char* pa = reinterpret_cast<unsigned char*>(take(n));
-    if (m) { m->e[i] = pe; m->am[i] = pa; }
+    if (m) { m->e[i] = pe; m->amax[i] = pa; }
   }
   for (int i = 0; i < 4; ++i) {        // decoder i: COUT = ACH[3 - i], output length L >> (3 - i)
     const size_t n = B * ACH[3 - i] * (c.L >> (3 - i));
@@ -637,51 +613,47 @@ static size_t acdae_plan(const ral_config& c, AcdaeModel* m, char* base) {
   }
   return cur;
 }
-int64_t acdae_workspace_bytes(const ral_config* c) { return (int64_t)acdae_plan(*c, nullptr, nullptr); }
 
-AcdaeModel* acdae_create(const ral_config* c, char* err, size_t cap) {
-  AcdaeModel* m = new AcdaeModel();
-  memset(&m->pub, 0, sizeof(m->pub));
-  m->pub.cfg = *c;
-  abuild(m->lay);
-  m->pub.nparam = m->lay.nparam;
-  const size_t bytes = acdae_plan(*c, nullptr, nullptr);
-  if (hipMalloc(reinterpret_cast<void**>(&m->slab), bytes) != hipSuccess) {
-    snprintf(err, cap, "hipMalloc(%zu) failed", bytes);
-    delete m;
-    return nullptr;
-  }
-  acdae_plan(*c, m, m->slab);
-  return m;
-}
-void acdae_destroy(AcdaeModel* m) { if (m) { if (m->slab) (void)hipFree(m->slab); delete m; } }
-AcdaePublic* acdae_public(AcdaeModel* m) { return &m->pub; }
-int acdae_bind(AcdaeModel* m, float* params, float* grads, float* am, float* av) {
-  m->pub.params = params; m->pub.grads = grads; m->pub.am = am; m->pub.av = av;
+int AcdaeModel::init() {
+  abuild(lay, off);
+  const size_t bytes = acdae_plan(cfg, nullptr, nullptr);
+  if (alloc_slab(bytes) != hipSuccess) return ral_fail("hipMalloc(%zu) failed", bytes);
+  acdae_plan(cfg, this, slab);
   return 0;
+}
+
+const RalKind* acdae_kind() {
+  static const RalKind k = {
+      acdae_check_cfg,
+      [](const ral_config&, ParamLayout& L) { AOff o; abuild(L, o); },
+      [](const ral_config& c) { return acdae_plan(c, nullptr, nullptr); },
+      0,
+      []() -> ral_handle* { return new AcdaeModel(); },
+      "ACDAE has no BatchNorm: use ral_forward"};
+  return &k;
 }
 
 #define ACD_LDS(kernel, bytes) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes))
 
-int acdae_forward(AcdaeModel* m, const float* x, float* y, int B, hipStream_t st, char* err, size_t cap) {
-  AcdaePublic& P = m->pub;
-  if (!P.params) { snprintf(err, cap, "ral_bind was not called"); return -1; }
-  if (B <= 0 || B > P.cfg.max_batch) { snprintf(err, cap, "batch %d outside (0, %d]", B, P.cfg.max_batch); return -1; }
-  const int L = P.cfg.L, grid = B < 1024 ? B : 1024;
-  const ALayout& Y = m->lay;
+int AcdaeModel::forward(const float* x, float* y, int B, int, hipStream_t st) {
+  AcdaeModel* const m = this;
+  if (!m->params) return ral_fail("ral_bind was not called");
+  if (B <= 0 || B > m->cfg.max_batch) return ral_fail("batch %d outside (0, %d]", B, m->cfg.max_batch);
+  const int L = m->cfg.L, grid = B < 1024 ? B : 1024;
+  const AOff& Y = m->off;
   m->last_x = x; m->last_B = B;
   const float* in = x;
   for (int i = 0; i < 4; ++i) {
     const int cin = ACH[i], cout = ACH[i + 1], lin = L >> i;
     const size_t lds = (size_t)cin * (lin + 16) * sizeof(float);
-    if (AKS[i] == 13) { ACD_LDS(k_acd_enc_fwd<13>, lds); k_acd_enc_fwd<13><<<grid, 256, lds, st>>>(in, P.params + Y.ew[i], P.params + Y.eb[i], m->e[i], m->am[i], cin, cout, lin, B); }
+    if (AKS[i] == 13) { ACD_LDS(k_acd_enc_fwd<13>, lds); k_acd_enc_fwd<13><<<grid, 256, lds, st>>>(in, m->params + Y.ew[i], m->params + Y.eb[i], m->e[i], m->amax[i], cin, cout, lin, B); }
     else if (cin >= 16 && cout % 32 == 0 && lin % 16 == 0) {
       const size_t l2 = lds + (size_t)32 * cin * 7 * sizeof(float);
       const int gx = B < 512 ? B : 512;
       ACD_LDS(k_acd_enc_fwd_m<7>, l2);
-      k_acd_enc_fwd_m<7><<<dim3(gx, cout / 32), 256, l2, st>>>(in, P.params + Y.ew[i], P.params + Y.eb[i], m->e[i], m->am[i], cin, cout, lin, B);
+      k_acd_enc_fwd_m<7><<<dim3(gx, cout / 32), 256, l2, st>>>(in, m->params + Y.ew[i], m->params + Y.eb[i], m->e[i], m->amax[i], cin, cout, lin, B);
     }
-    else { ACD_LDS(k_acd_enc_fwd<7>, lds); k_acd_enc_fwd<7><<<grid, 256, lds, st>>>(in, P.params + Y.ew[i], P.params + Y.eb[i], m->e[i], m->am[i], cin, cout, lin, B); }
+    else { ACD_LDS(k_acd_enc_fwd<7>, lds); k_acd_enc_fwd<7><<<grid, 256, lds, st>>>(in, m->params + Y.ew[i], m->params + Y.eb[i], m->e[i], m->amax[i], cin, cout, lin, B); }
     in = m->e[i];
   }
   for (int i = 0; i < 4; ++i) {
@@ -689,11 +661,11 @@ int acdae_forward(AcdaeModel* m, const float* x, float* y, int B, hipStream_t st
     const size_t lds = ((size_t)cin * (lin + 16) + (size_t)cout * lin * 3 + 2 * cout + 8) * sizeof(float);
     const float* skip = i < 3 ? m->e[2 - i] : nullptr;
     float* out = i < 3 ? m->d[i] : y;
-    if (ks == 13) { ACD_LDS(k_acd_dec_fwd<13>, lds); k_acd_dec_fwd<13><<<grid, 256, lds, st>>>(in, P.params + Y.dw[i], P.params + Y.db[i], P.params + Y.de[i], skip, m->a[i], m->s[i], out, cin, cout, lin, B); }
-    else { ACD_LDS(k_acd_dec_fwd<7>, lds); k_acd_dec_fwd<7><<<grid, 256, lds, st>>>(in, P.params + Y.dw[i], P.params + Y.db[i], P.params + Y.de[i], skip, m->a[i], m->s[i], out, cin, cout, lin, B); }
+    if (ks == 13) { ACD_LDS(k_acd_dec_fwd<13>, lds); k_acd_dec_fwd<13><<<grid, 256, lds, st>>>(in, m->params + Y.dw[i], m->params + Y.db[i], m->params + Y.de[i], skip, m->a[i], m->s[i], out, cin, cout, lin, B); }
+    else { ACD_LDS(k_acd_dec_fwd<7>, lds); k_acd_dec_fwd<7><<<grid, 256, lds, st>>>(in, m->params + Y.dw[i], m->params + Y.db[i], m->params + Y.de[i], skip, m->a[i], m->s[i], out, cin, cout, lin, B); }
     in = out;
   }
-  if (hipGetLastError() != hipSuccess) { snprintf(err, cap, "ACDAE forward launch failed"); return -1; }
+  if (hipGetLastError() != hipSuccess) return ral_fail("ACDAE forward launch failed");
   return 0;
 }
 
@@ -719,13 +691,14 @@ static void launch_acd_dw(const float* Yg, const float* Xg, float* gw, float* gb
   k_acd_dw<KS, CONVT><<<dim3(nblk, splits), 256, lds, st>>>(Yg, Xg, gw, gb, CY, CX, L, B);
 }
 
-int acdae_backward(AcdaeModel* m, const float* dy, float* dx, int B, hipStream_t st, char* err, size_t cap) {
-  AcdaePublic& P = m->pub;
-  if (!P.cfg.train || !P.grads) { snprintf(err, cap, "ACDAE backward needs train=1 and a bound gradient buffer"); return -1; }
-  if (B != m->last_B) { snprintf(err, cap, "backward batch %d != forward batch %d", B, m->last_B); return -1; }
-  const int L = P.cfg.L, grid = B < 1024 ? B : 1024;
-  const ALayout& Y = m->lay;
-  (void)hipMemsetAsync(P.grads, 0, (size_t)Y.nparam * sizeof(float), st);
+int AcdaeModel::backward(const float* dy, float* dx, int B, hipStream_t st) {
+  AcdaeModel* const m = this;
+  if (!dy) return ral_fail("ral_backward: dy is NULL");
+  if (!m->cfg.train || !m->grads) return ral_fail("ACDAE backward needs train=1 and a bound gradient buffer");
+  if (B != m->last_B) return ral_fail("backward batch %d != forward batch %d", B, m->last_B);
+  const int L = m->cfg.L, grid = B < 1024 ? B : 1024;
+  const AOff& Y = m->off;
+  (void)hipMemsetAsync(m->grads, 0, (size_t)lay.nparam * sizeof(float), st);
   // decoder blocks, last to first: g = gradient at the block output
   const float* g = dy;
   for (int i = 3; i >= 0; --i) {
@@ -735,12 +708,12 @@ int acdae_backward(AcdaeModel* m, const float* dy, float* dx, int B, hipStream_t
     const size_t lds = ((size_t)cout * lin * 2 + (size_t)cout * (lin + 16) + 3 * cout + 16) * sizeof(float);
     if (ks == 13) {
       ACD_LDS(k_acd_dec_bwd<13>, lds);
-      k_acd_dec_bwd<13><<<grid, 256, lds, st>>>(g, m->a[i], m->s[i], P.params + Y.dw[i], P.params + Y.de[i], m->dt[i], gin, P.grads + Y.de[i], cin, cout, lin, B);
-      launch_acd_dw<13, true>(m->dt[i], in, P.grads + Y.dw[i], P.grads + Y.db[i], cout, cin, lin, B, st);
+      k_acd_dec_bwd<13><<<grid, 256, lds, st>>>(g, m->a[i], m->s[i], m->params + Y.dw[i], m->params + Y.de[i], m->dt[i], gin, m->grads + Y.de[i], cin, cout, lin, B);
+      launch_acd_dw<13, true>(m->dt[i], in, m->grads + Y.dw[i], m->grads + Y.db[i], cout, cin, lin, B, st);
     } else {
       ACD_LDS(k_acd_dec_bwd<7>, lds);
-      k_acd_dec_bwd<7><<<grid, 256, lds, st>>>(g, m->a[i], m->s[i], P.params + Y.dw[i], P.params + Y.de[i], m->dt[i], gin, P.grads + Y.de[i], cin, cout, lin, B);
-      launch_acd_dw<7, true>(m->dt[i], in, P.grads + Y.dw[i], P.grads + Y.db[i], cout, cin, lin, B, st);
+      k_acd_dec_bwd<7><<<grid, 256, lds, st>>>(g, m->a[i], m->s[i], m->params + Y.dw[i], m->params + Y.de[i], m->dt[i], gin, m->grads + Y.de[i], cin, cout, lin, B);
+      launch_acd_dw<7, true>(m->dt[i], in, m->grads + Y.dw[i], m->grads + Y.db[i], cout, cin, lin, B, st);
     }
     g = gin;
   }
@@ -753,14 +726,14 @@ int acdae_backward(AcdaeModel* m, const float* dy, float* dx, int B, hipStream_t
     const size_t lds = (size_t)cout * (lin + 16) * sizeof(float);
     if (AKS[i] == 13) {
       ACD_LDS(k_acd_enc_bwd<13>, lds);
-      k_acd_enc_bwd<13><<<grid, 256, lds, st>>>(m->ge[i], g2, m->e[i], m->am[i], P.params + Y.ew[i], m->dc[i], gin, cin, cout, lin, B);
-      launch_acd_dw<13, false>(m->dc[i], in, P.grads + Y.ew[i], P.grads + Y.eb[i], cout, cin, lin, B, st);
+      k_acd_enc_bwd<13><<<grid, 256, lds, st>>>(m->ge[i], g2, m->e[i], m->amax[i], m->params + Y.ew[i], m->dc[i], gin, cin, cout, lin, B);
+      launch_acd_dw<13, false>(m->dc[i], in, m->grads + Y.ew[i], m->grads + Y.eb[i], cout, cin, lin, B, st);
     } else {
       ACD_LDS(k_acd_enc_bwd<7>, lds);
-      k_acd_enc_bwd<7><<<grid, 256, lds, st>>>(m->ge[i], g2, m->e[i], m->am[i], P.params + Y.ew[i], m->dc[i], gin, cin, cout, lin, B);
-      launch_acd_dw<7, false>(m->dc[i], in, P.grads + Y.ew[i], P.grads + Y.eb[i], cout, cin, lin, B, st);
+      k_acd_enc_bwd<7><<<grid, 256, lds, st>>>(m->ge[i], g2, m->e[i], m->amax[i], m->params + Y.ew[i], m->dc[i], gin, cin, cout, lin, B);
+      launch_acd_dw<7, false>(m->dc[i], in, m->grads + Y.ew[i], m->grads + Y.eb[i], cout, cin, lin, B, st);
     }
   }
-  if (hipGetLastError() != hipSuccess) { snprintf(err, cap, "ACDAE backward launch failed"); return -1; }
+  if (hipGetLastError() != hipSuccess) return ral_fail("ACDAE backward launch failed");
   return 0;
 }

@@ -33,7 +33,7 @@
 #include <string>
 #include <vector>
 
-#include "ral_danet.hpp"
+#include "ral_model.hpp"
 #include "ral_device.hpp"
 
 namespace {
@@ -920,20 +920,14 @@ __global__ __launch_bounds__(NT) void k_dn_conv_b(const float* __restrict__ da, 
 // =================================================================================
 // layout (state_dict contract) and host side
 // =================================================================================
-struct DEntry { std::string name; int kind; int64_t offset; int ndim; int64_t shape[4]; };
 struct BnOff { int64_t w, b, rm, rv; };
 struct FcnOff { int64_t w0, b0, w3, b3; BnOff bn1, bn2; int din, dh, dout; };
 struct CellOff { Geo g; int64_t cw, cb; FcnOff act; BnOff bn; FcnOff dam; int64_t saw, sab; };
-struct DLayout { std::vector<DEntry> e; int64_t nparam = 0, nstate = 0; CellOff cell[8]; };
 
-void dbuild(const ral_config& c, DLayout& Y) {
-  auto add = [&](const std::string& name, int kind, int64_t off, std::vector<int64_t> shp) {
-    DEntry en; en.name = name; en.kind = kind; en.offset = off; en.ndim = (int)shp.size();
-    for (int i = 0; i < 4; ++i) en.shape[i] = i < (int)shp.size() ? shp[i] : 1;
-    Y.e.push_back(en);
-  };
+void dbuild(const ral_config& c, ParamLayout& Y, CellOff cell[8]) {
+  auto add = [&](const std::string& name, int kind, int64_t off, const std::vector<int64_t>& shp) { Y.add(name, kind, off, shp); };
   auto numel = [](const std::vector<int64_t>& s) { int64_t n = 1; for (auto v : s) n *= v; return n; };
-  auto param = [&](const std::string& name, std::vector<int64_t> shp) { const int64_t o = Y.nparam; add(name, RAL_PARAM, o, shp); Y.nparam += (numel(shp) + 3) / 4 * 4; return o; };
+  auto param = [&](const std::string& name, std::vector<int64_t> shp) { const int64_t o = Y.alloc(numel(shp), 4); add(name, RAL_PARAM, o, shp); return o; };
   auto state = [&](const std::string& name, int64_t n) { const int64_t o = Y.nstate; add(name, RAL_STATE_F32, o, {n}); Y.nstate += (n + 3) / 4 * 4; return o; };
   auto bn = [&](const std::string& pre, int64_t n) {
     BnOff b; b.w = param(pre + ".weight", {n}); b.b = param(pre + ".bias", {n});
@@ -951,7 +945,7 @@ void dbuild(const ral_config& c, DLayout& Y) {
   };
   int cin = c.leads;
   for (int i = 0; i < 8; ++i) {
-    CellOff& K = Y.cell[i];
+    CellOff& K = cell[i];
     const bool enc = i < 4;
     const int j = enc ? i : i - 4;
     const int C = enc ? ENC_CH[j] : DEC_CH[j];
@@ -966,11 +960,11 @@ void dbuild(const ral_config& c, DLayout& Y) {
     if (K.g.dam) {
       K.dam = fcn(pre + ".dam.fcn1", C, C, C);
       // fcn2 is the same module list as fcn1 (DAM.py:122-131): alias entries at the same offsets
-      const size_t first = Y.e.size() - 14;
+      const size_t first = Y.entries.size() - 14;
       for (size_t q = first; q < first + 14; ++q) {
-        DEntry en = Y.e[q];
+        ParamEntry en = Y.entries[q];
         en.name.replace(en.name.find(".dam.fcn1."), 10, ".dam.fcn2.");
-        Y.e.push_back(en);
+        Y.entries.push_back(en);
       }
       K.saw = param(pre + ".dam.convsa.weight", {1, 2, 1}); K.sab = param(pre + ".dam.convsa.bias", {1});
     }
@@ -979,43 +973,34 @@ void dbuild(const ral_config& c, DLayout& Y) {
 }
 }  // namespace
 
-struct DanetModel {
-  DanetPublic pub;
-  DLayout lay;
-  char* slab = nullptr;
+struct DanetModel : ral_handle {
+  CellOff cell[8];
   float *z[8], *a[8], *out[8], *desc[8], *h1[8], *h2[8], *pool[8], *dh1[8], *dh2[8];   // forward tensors per cell
   float *g[8], *gs[4], *dy2[8], *dy1[8], *ddy2[8], *ddy1[8];                           // backward tensors
   double* sums = nullptr;            // 8 x S_CELL
   const float* last_x = nullptr; int last_B = 0; bool last_training = false;
+  int init() override;
+  int forward(const float* x, float* y, int B, int training, hipStream_t st) override;
+  int backward(const float* dy, float* dx, int B, hipStream_t st) override;
 };
 
-int danet_check_cfg(const ral_config* c, char* err, size_t cap) {
-  if (c->leads != 2) { snprintf(err, cap, "DANet: the last decoder cell has 2 output channels, so leads must be 2 (got %d)", c->leads); return -1; }
-  if (c->L < 32 || c->L % 16 != 0 || c->L > 2048) { snprintf(err, cap, "DANet: L must be a multiple of 16 in [32, 2048], got %d", c->L); return -1; }
-  if (c->max_batch < 1) { snprintf(err, cap, "DANet: max_batch must be positive"); return -1; }
+static int danet_check_cfg(const ral_config* c) {
+  if (c->leads != 2) return ral_fail("DANet: the last decoder cell has 2 output channels, so leads must be 2 (got %d)", c->leads);
+  if (c->L < 32 || c->L % 16 != 0 || c->L > 2048) return ral_fail("DANet: L must be a multiple of 16 in [32, 2048], got %d", c->L);
+  if (c->max_batch < 1) return ral_fail("DANet: max_batch must be positive");
   return 0;
 }
-int danet_layout_count(const ral_config* c) { DLayout Y; dbuild(*c, Y); return (int)Y.e.size(); }
-int danet_layout_entry(const ral_config* c, int idx, char* name, int name_cap, int32_t* kind, int64_t* offset, int32_t* ndim,
-                       int64_t shape[4]) {
-  DLayout Y; dbuild(*c, Y);
-  if (idx < 0 || idx >= (int)Y.e.size() || (int)Y.e[idx].name.size() + 1 > name_cap) return -1;
-  strcpy(name, Y.e[idx].name.c_str());
-  *kind = Y.e[idx].kind; *offset = Y.e[idx].offset; *ndim = Y.e[idx].ndim;
-  for (int i = 0; i < 4; ++i) shape[i] = Y.e[idx].shape[i];
-  return 0;
-}
-int64_t danet_param_floats(const ral_config* c) { DLayout Y; dbuild(*c, Y); return Y.nparam; }
-int64_t danet_state_floats(const ral_config* c) { DLayout Y; dbuild(*c, Y); return Y.nstate; }
+static void danet_layout(const ral_config& c, ParamLayout& L) { CellOff cell[8]; dbuild(c, L, cell); }
 
 static size_t danet_plan(const ral_config& c, DanetModel* m, char* base) {
-  DLayout Yl; const DLayout* Y = m ? &m->lay : &Yl;
-  if (!m) dbuild(c, Yl);
+  CellOff own[8];
+  const CellOff* cell = m ? m->cell : own;
+  if (!m) { ParamLayout Y; dbuild(c, Y, own); }
   size_t cur = 0;
   const size_t B = c.max_batch;
   auto take = [&](size_t floats) -> float* { float* p = base ? reinterpret_cast<float*>(base + cur) : nullptr; cur += (floats * 4 + 255) & ~size_t(255); return p; };
   for (int i = 0; i < 8; ++i) {
-    const Geo& G = Y->cell[i].g;
+    const Geo& G = cell[i].g;
     const size_t n = B * G.c * G.lout;
     float *pz = take(n), *pa = take(n), *po = take(n), *pd = take(B * 2 * G.c), *p1 = take(B * 2 * G.c), *p2 = take(B * G.c);
     float *pp = G.dam ? take(2 * B * G.c) : nullptr, *q1 = G.dam ? take(2 * B * G.c) : nullptr, *q2 = G.dam ? take(2 * B * G.c) : nullptr;
@@ -1030,37 +1015,33 @@ static size_t danet_plan(const ral_config& c, DanetModel* m, char* base) {
   if (m) m->sums = ps;
   return cur;
 }
-int64_t danet_workspace_bytes(const ral_config* c) { return (int64_t)danet_plan(*c, nullptr, nullptr); }
 
-DanetModel* danet_create(const ral_config* c, char* err, size_t cap) {
-  DanetModel* m = new DanetModel();
-  memset(&m->pub, 0, sizeof(m->pub));
-  m->pub.cfg = *c;
-  dbuild(*c, m->lay);
-  m->pub.nparam = m->lay.nparam; m->pub.nstate = m->lay.nstate;
-  const size_t bytes = danet_plan(*c, m, nullptr);
-  if (hipMalloc(reinterpret_cast<void**>(&m->slab), bytes) != hipSuccess) {
-    snprintf(err, cap, "hipMalloc(%zu) failed", bytes);
-    delete m;
-    return nullptr;
-  }
-  danet_plan(*c, m, m->slab);
-  return m;
-}
-void danet_destroy(DanetModel* m) { if (m) { if (m->slab) (void)hipFree(m->slab); delete m; } }
-DanetPublic* danet_public(DanetModel* m) { return &m->pub; }
-int danet_bind(DanetModel* m, float* params, float* grads, float* am, float* av, float* state) {
-  m->pub.params = params; m->pub.grads = grads; m->pub.am = am; m->pub.av = av; m->pub.state = state;
+int DanetModel::init() {
+  dbuild(cfg, lay, cell);
+  const size_t bytes = danet_plan(cfg, this, nullptr);
+  if (alloc_slab(bytes) != hipSuccess) return ral_fail("hipMalloc(%zu) failed", bytes);
+  danet_plan(cfg, this, slab);
   return 0;
 }
 
+const RalKind* danet_kind() {
+  static const RalKind k = {
+      danet_check_cfg,
+      danet_layout,
+      [](const ral_config& c) { return danet_plan(c, nullptr, nullptr); },
+      0,     // (its batch sums live in its own workspace)
+      []() -> ral_handle* { return new DanetModel(); },
+      "U-Net / DANet have a BatchNorm per layer: use ral_forward (per-rank statistics)"};
+  return &k;
+}
+
 namespace {
-Bn mk_bn(const DanetPublic& P, const BnOff& o) {
+Bn mk_bn(const ral_handle& P, const BnOff& o) {
   Bn b; b.g = P.params + o.w; b.b = P.params + o.b; b.rm = P.state + o.rm; b.rv = P.state + o.rv;
   b.dg = P.grads ? P.grads + o.w : nullptr; b.db = P.grads ? P.grads + o.b : nullptr;
   return b;
 }
-Fcn mk_fcn(const DanetPublic& P, const FcnOff& o) {
+Fcn mk_fcn(const ral_handle& P, const FcnOff& o) {
   Fcn f; f.w0 = P.params + o.w0; f.b0 = P.params + o.b0; f.w3 = P.params + o.w3; f.b3 = P.params + o.b3;
   f.dw0 = P.grads ? P.grads + o.w0 : nullptr; f.db0 = P.grads ? P.grads + o.b0 : nullptr;
   f.dw3 = P.grads ? P.grads + o.w3 : nullptr; f.db3 = P.grads ? P.grads + o.b3 : nullptr;
@@ -1072,11 +1053,11 @@ template <class K> void set_lds(K kernel, size_t bytes) {
 }
 }  // namespace
 
-int danet_forward(DanetModel* m, const float* x, float* y, int B, int training, hipStream_t st, char* err, size_t cap) {
-  DanetPublic& P = m->pub;
-  if (!P.params || !P.state) { snprintf(err, cap, "ral_bind was not called"); return -1; }
-  if (B <= 0 || B > P.cfg.max_batch) { snprintf(err, cap, "batch %d outside (0, %d]", B, P.cfg.max_batch); return -1; }
-  if (training && B < 2) { snprintf(err, cap, "DANet: a training forward needs at least 2 windows (BatchNorm over the batch of descriptors)"); return -1; }
+int DanetModel::forward(const float* x, float* y, int B, int training, hipStream_t st) {
+  DanetModel* const m = this;
+  if (!m->params || !m->state) return ral_fail("ral_bind was not called");
+  if (B <= 0 || B > m->cfg.max_batch) return ral_fail("batch %d outside (0, %d]", B, m->cfg.max_batch);
+  if (training && B < 2) return ral_fail("DANet: a training forward needs at least 2 windows (BatchNorm over the batch of descriptors)");
   constexpr int gf = 1024;
   const int grid = B < gf ? B : gf;
   constexpr int gdesc = 256;   // descriptor-level kernels: a wave per window,
@@ -1086,11 +1067,11 @@ int danet_forward(DanetModel* m, const float* x, float* y, int B, int training, 
   if (training) (void)hipMemsetAsync(m->sums, 0, sizeof(double) * 8 * S_CELL, st);
   m->last_x = x; m->last_B = B; m->last_training = training != 0;
   for (int i = 0; i < 8; ++i) {
-    const CellOff& K = m->lay.cell[i];
+    const CellOff& K = m->cell[i];
     const Geo& G = K.g;
     double* S = m->sums + (size_t)i * S_CELL;
-    const Fcn Fa = mk_fcn(P, K.act);
-    const Bn bn = mk_bn(P, K.bn);
+    const Fcn Fa = mk_fcn(*m, K.act);
+    const Bn bn = mk_bn(*m, K.bn);
     const float* in0 = i == 0 ? x : m->out[i - 1];
     const float* in1 = i >= 5 ? m->out[7 - i] : nullptr;     // decoder cells 1..3 add encoder features 2, 1, 0
     float* out = i == 7 ? y : m->out[i];
@@ -1098,7 +1079,7 @@ int danet_forward(DanetModel* m, const float* x, float* y, int B, int training, 
     const size_t l1 = ((size_t)G.cin * (G.lin + 2 * CH) + nz + 2 * G.c) * sizeof(float);
     auto conv = [&](auto kern) {
       set_lds(kern, l1);
-      kern<<<grid, NT, l1, st>>>(in0, in1, P.params + K.cw, P.params + K.cb, G, Fa, m->z[i], m->desc[i], m->h1[i],
+      kern<<<grid, NT, l1, st>>>(in0, in1, m->params + K.cw, m->params + K.cb, G, Fa, m->z[i], m->desc[i], m->h1[i],
                                  training ? S + S_AH1 : nullptr, B);
     };
     if (G.k == 17) conv(k_dn_conv<17, false>); else if (G.k == 3) conv(k_dn_conv<3, false>);
@@ -1108,7 +1089,7 @@ int danet_forward(DanetModel* m, const float* x, float* y, int B, int training, 
     else k_dn_act<1><<<grida, NT, 0, st>>>(m->z[i], m->h2[i], S + S_AH2, Fa, G, m->a[i], training ? S + S_BN : nullptr, B, training);
     Fcn Fd = Fa;
     if (G.dam) {
-      Fd = mk_fcn(P, K.dam);
+      Fd = mk_fcn(*m, K.dam);
       const size_t l2 = nz * sizeof(float);
       set_lds(k_dn_dam1, l2);
       k_dn_dam1<<<grid, NT, l2, st>>>(m->a[i], S + S_BN, bn, Fd, G, m->pool[i], m->dh1[i], training ? S + S_DH1 : nullptr, B, training);
@@ -1116,17 +1097,18 @@ int danet_forward(DanetModel* m, const float* x, float* y, int B, int training, 
     }
     const size_t l3 = (nz + G.lout) * sizeof(float);
     set_lds(k_dn_out, l3);
-    k_dn_out<<<grid, NT, l3, st>>>(m->a[i], S + S_BN, bn, G, m->dh2[i], S + S_DH2, Fd, G.dam ? P.params + K.saw : nullptr,
-                                    G.dam ? P.params + K.sab : nullptr, out, B, training, G.dam ? 0 : 1);
+    k_dn_out<<<grid, NT, l3, st>>>(m->a[i], S + S_BN, bn, G, m->dh2[i], S + S_DH2, Fd, G.dam ? m->params + K.saw : nullptr,
+                                    G.dam ? m->params + K.sab : nullptr, out, B, training, G.dam ? 0 : 1);
   }
-  if (hipGetLastError() != hipSuccess) { snprintf(err, cap, "DANet forward launch failed"); return -1; }
+  if (hipGetLastError() != hipSuccess) return ral_fail("DANet forward launch failed");
   return 0;
 }
 
-int danet_backward(DanetModel* m, const float* dy, float* dx, int B, hipStream_t st, char* err, size_t cap) {
-  DanetPublic& P = m->pub;
-  if (!P.cfg.train || !P.grads) { snprintf(err, cap, "DANet backward needs train=1 and a bound gradient buffer"); return -1; }
-  if (B != m->last_B || !m->last_training) { snprintf(err, cap, "DANet backward needs a training forward of the same batch first"); return -1; }
+int DanetModel::backward(const float* dy, float* dx, int B, hipStream_t st) {
+  DanetModel* const m = this;
+  if (!dy) return ral_fail("ral_backward: dy is NULL");
+  if (!m->cfg.train || !m->grads) return ral_fail("DANet backward needs train=1 and a bound gradient buffer");
+  if (B != m->last_B || !m->last_training) return ral_fail("DANet backward needs a training forward of the same batch first");
   constexpr int gb = 1024;   // (train step at batch 2048: 3.84 / 3.58 / 4.43 ms with 512 / 1024 / 2048)
   const int grid = B < gb ? B : gb;
   constexpr int gdesc = 256;   // descriptor-level kernels (see danet_forward)
@@ -1135,15 +1117,15 @@ int danet_backward(DanetModel* m, const float* dy, float* dx, int B, hipStream_t
   const int grida = (B + 3) / 4 < gact ? (B + 3) / 4 : gact;
   constexpr int gwin = 512;   // window-at-a-time kernels with column-sum flushes (train step at batch 2048: 2.33 / 2.23 / 2.26 / 2.44 ms with 1024 / 512 / 256 / 128)
   const int gridw = B < gwin ? B : gwin;
-  (void)hipMemsetAsync(P.grads, 0, (size_t)m->lay.nparam * sizeof(float), st);
+  (void)hipMemsetAsync(m->grads, 0, (size_t)m->lay.nparam * sizeof(float), st);
   // the backward halves [T_D2, S_CELL) of the eight cells' sum records: one strided fill
   (void)hipMemset2DAsync(m->sums + T_D2, sizeof(double) * S_CELL, 0, sizeof(double) * (S_CELL - T_D2), 8, st);
   for (int i = 7; i >= 0; --i) {
-    const CellOff& K = m->lay.cell[i];
+    const CellOff& K = m->cell[i];
     const Geo& G = K.g;
     double* S = m->sums + (size_t)i * S_CELL;
-    const Fcn Fa = mk_fcn(P, K.act);
-    const Bn bn = mk_bn(P, K.bn);
+    const Fcn Fa = mk_fcn(*m, K.act);
+    const Bn bn = mk_bn(*m, K.bn);
     const size_t nz = (size_t)G.c * G.lout;
     // gradient(s) at the cell output: the last cell gets dy, decoder cells the next cell's input gradient, encoder cell
     // 3 the first decoder cell's, encoder cells 0..2 the next encoder cell's plus the decoder's skip
@@ -1152,11 +1134,11 @@ int danet_backward(DanetModel* m, const float* dy, float* dx, int B, hipStream_t
     float* work = m->g[i];                         // dxo / da live here (for i == 7: copy of dy's role)
     Fcn Fd = Fa;
     if (G.dam) {
-      Fd = mk_fcn(P, K.dam);
+      Fd = mk_fcn(*m, K.dam);
       const size_t l1 = (2 * nz + 3 * G.lout) * sizeof(float);
       set_lds(k_dn_dam_b, l1);
-      k_dn_dam_b<<<gridw, NT, l1, st>>>(g0, m->a[i], S + S_BN, bn, G, m->dh2[i], S + S_DH2, Fd, P.params + K.saw, P.params + K.sab,
-                                        P.grads + K.saw, P.grads + K.sab, work, m->ddy2[i], S + T_D2, B);
+      k_dn_dam_b<<<gridw, NT, l1, st>>>(g0, m->a[i], S + S_BN, bn, G, m->dh2[i], S + S_DH2, Fd, m->params + K.saw, m->params + K.sab,
+                                        m->grads + K.saw, m->grads + K.sab, work, m->ddy2[i], S + T_D2, B);
       const size_t l2 = ((size_t)Fd.dout * Fd.dh + Fd.dout) * sizeof(float);
       k_dn_fcn_bmid<<<gridd, NT, l2, st>>>(m->ddy2[i], S + T_D2, m->dh2[i], S + S_DH2, m->dh1[i], S + S_DH1, Fd, m->ddy1[i], S + T_D1, 2, B);
       g0 = work; g1 = nullptr;
@@ -1178,12 +1160,12 @@ int danet_backward(DanetModel* m, const float* dy, float* dx, int B, hipStream_t
                        (size_t)Fa.dh * Fa.din + Fa.dh) * sizeof(float);
     auto convb = [&](auto kern) {
       set_lds(kern, l5);
-      kern<<<grid, NT, l5, st>>>(work, m->z[i], in0, in1, P.params + K.cw, P.grads + K.cw, P.grads + K.cb, G, m->dy1[i], S + T_A1,
+      kern<<<grid, NT, l5, st>>>(work, m->z[i], in0, in1, m->params + K.cw, m->grads + K.cw, m->grads + K.cb, G, m->dy1[i], S + T_A1,
                                  m->h1[i], S + S_AH1, m->h2[i], S + S_AH2, m->desc[i], Fa, gi0, gi1, B);
     };
     if (G.k == 17) convb(k_dn_conv_b<17, false>); else if (G.k == 3) convb(k_dn_conv_b<3, false>);
     else if (G.k == 4) convb(k_dn_conv_b<4, true>); else convb(k_dn_conv_b<18, true>);
   }
-  if (hipGetLastError() != hipSuccess) { snprintf(err, cap, "DANet backward launch failed"); return -1; }
+  if (hipGetLastError() != hipSuccess) return ral_fail("DANet backward launch failed");
   return 0;
 }

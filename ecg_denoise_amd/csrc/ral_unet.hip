@@ -11,6 +11,7 @@
 #ifdef RAL_STAMP_TU_UNET
 #define RAL_STAMP_HERE
 #endif
+#include "ral_model.hpp"
 #include "ral_unet.hpp"
 
 #include <stdio.h>
@@ -1693,71 +1694,55 @@ static size_t uinf_lds_floats(int L) {
 // =================================================================================
 // host model
 // =================================================================================
-struct UEntry { std::string name; int kind; int64_t offset; int ndim; int64_t shape[4]; };
-
-struct ULayout {
-  std::vector<UEntry> e;
-  int64_t nparam = 0, nstate = 0;
+struct UOff {
   int64_t w[11], b[11];         // conv weights/biases: 0-3 enc, 4-6 bottleneck convs, 7-10 dec
   int64_t bnw[10], bnb[10], run[10];  // BN: 0-3 enc, 4-5 bottleneck, 6-9 dec
   int bnC[10];
   int ch[5];
 };
 
-static int64_t ualloc(int64_t& cur, int64_t n) { const int64_t o = cur; cur += (n + 3) & ~int64_t(3); return o; }
-static void upush(ULayout& L, const std::string& n, int kind, int64_t off, std::initializer_list<int64_t> shp) {
-  UEntry e; e.name = n; e.kind = kind; e.offset = off; e.ndim = (int)shp.size();
-  int i = 0;
-  for (auto s : shp) e.shape[i++] = s;
-  for (; i < 4; ++i) e.shape[i] = 1;
-  L.e.push_back(e);
-}
-
-static void ubuild(const ral_config& c, ULayout& L) {
-  int64_t cur = 0, st = 0;
+static void ubuild(const ral_config& c, ParamLayout& L, UOff& O) {
+  auto alloc = [&](int64_t n) { return L.alloc(n, 4); };
   const int ch[5] = {c.leads, 4, 8, 16, 32};
-  memcpy(L.ch, ch, sizeof(ch));
+  memcpy(O.ch, ch, sizeof(ch));
   auto bn = [&](int idx, const std::string& pre, int C) {
-    L.bnC[idx] = C;
-    L.bnw[idx] = ualloc(cur, C); L.bnb[idx] = ualloc(cur, C);
-    L.run[idx] = st; st += 2 * C;
-    upush(L, pre + ".weight", RAL_PARAM, L.bnw[idx], {C});
-    upush(L, pre + ".bias", RAL_PARAM, L.bnb[idx], {C});
-    upush(L, pre + ".running_mean", RAL_STATE_F32, L.run[idx], {C});
-    upush(L, pre + ".running_var", RAL_STATE_F32, L.run[idx] + C, {C});
-    upush(L, pre + ".num_batches_tracked", RAL_COUNTER_I64, 0, {});
+    O.bnC[idx] = C;
+    O.bnw[idx] = alloc(C); O.bnb[idx] = alloc(C);
+    O.run[idx] = L.nstate; L.nstate += 2 * C;
+    L.add(pre + ".weight", RAL_PARAM, O.bnw[idx], {C});
+    L.add(pre + ".bias", RAL_PARAM, O.bnb[idx], {C});
+    L.add(pre + ".running_mean", RAL_STATE_F32, O.run[idx], {C});
+    L.add(pre + ".running_var", RAL_STATE_F32, O.run[idx] + C, {C});
+    L.add(pre + ".num_batches_tracked", RAL_COUNTER_I64, 0, {});
   };
   for (int i = 0; i < 4; ++i) {
     const std::string p = "EncList." + std::to_string(i);
-    L.w[i] = ualloc(cur, ch[i + 1] * ch[i] * 3); L.b[i] = ualloc(cur, ch[i + 1]);
-    upush(L, p + ".conv.weight", RAL_PARAM, L.w[i], {ch[i + 1], ch[i], 3});
-    upush(L, p + ".conv.bias", RAL_PARAM, L.b[i], {ch[i + 1]});
+    O.w[i] = alloc(ch[i + 1] * ch[i] * 3); O.b[i] = alloc(ch[i + 1]);
+    L.add(p + ".conv.weight", RAL_PARAM, O.w[i], {ch[i + 1], ch[i], 3});
+    L.add(p + ".conv.bias", RAL_PARAM, O.b[i], {ch[i + 1]});
     bn(i, p + ".bn", ch[i + 1]);
   }
   for (int i = 0; i < 4; ++i) {
     const std::string p = "DecList." + std::to_string(i);
     const int cin = ch[4 - i], cout = ch[3 - i];
-    L.w[7 + i] = ualloc(cur, cin * cout * 4); L.b[7 + i] = ualloc(cur, cout);
-    upush(L, p + ".conv.weight", RAL_PARAM, L.w[7 + i], {cin, cout, 4});
-    upush(L, p + ".conv.bias", RAL_PARAM, L.b[7 + i], {cout});
+    O.w[7 + i] = alloc(cin * cout * 4); O.b[7 + i] = alloc(cout);
+    L.add(p + ".conv.weight", RAL_PARAM, O.w[7 + i], {cin, cout, 4});
+    L.add(p + ".conv.bias", RAL_PARAM, O.b[7 + i], {cout});
     bn(6 + i, p + ".bn", cout);
   }
   const int ks[3] = {1, 3, 1};
   const char* cn[3] = {"bottleneck.0", "bottleneck.3", "bottleneck.6"};
   const char* bnn[2] = {"bottleneck.2", "bottleneck.5"};
   for (int i = 0; i < 3; ++i) {
-    L.w[4 + i] = ualloc(cur, 32 * 32 * ks[i]); L.b[4 + i] = ualloc(cur, 32);
-    upush(L, std::string(cn[i]) + ".weight", RAL_PARAM, L.w[4 + i], {32, 32, ks[i]});
-    upush(L, std::string(cn[i]) + ".bias", RAL_PARAM, L.b[4 + i], {32});
+    O.w[4 + i] = alloc(32 * 32 * ks[i]); O.b[4 + i] = alloc(32);
+    L.add(std::string(cn[i]) + ".weight", RAL_PARAM, O.w[4 + i], {32, 32, ks[i]});
+    L.add(std::string(cn[i]) + ".bias", RAL_PARAM, O.b[4 + i], {32});
     if (i < 2) bn(4 + i, bnn[i], 32);
   }
-  L.nparam = cur; L.nstate = st;
 }
 
-struct UNetModel {
-  UNetPublic pub;
-  ULayout lay;
-  char* slab = nullptr;
+struct UNetModel : ral_handle {
+  UOff off;
   float* z[11];       // conv outputs: 0-3 enc, 4 a4, 5 a5, 6 r, 7-10 dec (z6..z9 in the text above)
   float* pack = nullptr;   // fused inference: re-packed weights + folded BatchNorm coefficients (uinf::PTOT floats)
   int infer_grid = 0;      // resident workgroups of the fused inference kernel (occupancy query, first call)
@@ -1779,26 +1764,23 @@ struct UNetModel {
   int nrep_f = 1, nrep_b = 1;     // replicas the current forward / backward pass adds to (1: straight into bn_sums)
   bool rep_bwd_clean = false;     // the backward half of `rep` was zeroed by the forward pass's fill and not used since
   bool rep_all_clean = false;     // both halves were zeroed by the last backward pass's fold kernel and not used since
+  int init() override;
+  int forward(const float* x, float* y, int B, int training, hipStream_t s) override;
+  int backward(const float* dy, float* dx, int B, hipStream_t s) override;
+  int set_option(const char* key, int value) override {
+    if (!strcmp(key, "unet_fused")) { fused = value != 0; return 0; }   // eval forward as one kernel (default 1)
+    return ral_fail("unknown U-Net option %s", key);
+  }
 };
+UNetModel* unet_model(ral_handle* h) { return dynamic_cast<UNetModel*>(h); }
 
-int unet_check_cfg(const ral_config* c, char* err, size_t cap) {
-  if (c->leads != 1 && c->leads != 2) { snprintf(err, cap, "leads must be 1 or 2 (got %d)", c->leads); return -1; }
-  if (c->L <= 0 || c->L % 16 != 0 || c->L > 2048) { snprintf(err, cap, "U-Net: L must be a multiple of 16 and <= 2048 (got %d)", c->L); return -1; }
-  if (c->max_batch <= 0) { snprintf(err, cap, "max_batch must be positive"); return -1; }
+static int unet_check_cfg(const ral_config* c) {
+  if (c->leads != 1 && c->leads != 2) return ral_fail("leads must be 1 or 2 (got %d)", c->leads);
+  if (c->L <= 0 || c->L % 16 != 0 || c->L > 2048) return ral_fail("U-Net: L must be a multiple of 16 and <= 2048 (got %d)", c->L);
+  if (c->max_batch <= 0) return ral_fail("max_batch must be positive");
   return 0;
 }
-int unet_layout_count(const ral_config* c) { ULayout L; ubuild(*c, L); return (int)L.e.size(); }
-int unet_layout_entry(const ral_config* c, int idx, char* name, int name_cap, int32_t* kind, int64_t* offset,
-                      int32_t* ndim, int64_t shape[4]) {
-  ULayout L; ubuild(*c, L);
-  if (idx < 0 || idx >= (int)L.e.size() || (int)L.e[idx].name.size() + 1 > name_cap) return -1;
-  strcpy(name, L.e[idx].name.c_str());
-  *kind = L.e[idx].kind; *offset = L.e[idx].offset; *ndim = L.e[idx].ndim;
-  for (int i = 0; i < 4; ++i) shape[i] = L.e[idx].shape[i];
-  return 0;
-}
-int64_t unet_param_floats(const ral_config* c) { ULayout L; ubuild(*c, L); return L.nparam; }
-int64_t unet_state_floats(const ral_config* c) { ULayout L; ubuild(*c, L); return L.nstate; }
+static void unet_layout(const ral_config& c, ParamLayout& L) { UOff o; ubuild(c, L, o); }
 #define UNET_PART_ROWS 1024   // most workgroups a backward stage is ever launched with
 static size_t unet_plan(const ral_config& c, UNetModel* m, char* base) {
   const int ch[5] = {c.leads, 4, 8, 16, 32};
@@ -1814,7 +1796,7 @@ static size_t unet_plan(const ral_config& c, UNetModel* m, char* base) {
   if (m) m->pack = base ? reinterpret_cast<float*>(base + cur) : nullptr;
   cur += ((size_t)uinf::PTOT * sizeof(float) + 255) & ~size_t(255);
   if (c.train) {
-    ULayout Y; ubuild(c, Y);
+    ParamLayout Y; unet_layout(c, Y);
     const int64_t stride = (Y.nparam + 63) & ~int64_t(63);
     const int rows = c.max_batch < UNET_PART_ROWS ? c.max_batch : UNET_PART_ROWS;
     if (m) { m->part = base ? reinterpret_cast<float*>(base + cur) : nullptr; m->part_stride = stride; m->part_rows_max = rows; }
@@ -1826,49 +1808,42 @@ static size_t unet_plan(const ral_config& c, UNetModel* m, char* base) {
   }
   return cur;
 }
-int64_t unet_workspace_bytes(const ral_config* c) { return (int64_t)unet_plan(*c, nullptr, nullptr); }
 
-UNetModel* unet_create(const ral_config* c, char* err, size_t cap) {
-  UNetModel* m = new UNetModel();
-  memset(&m->pub, 0, sizeof(m->pub));
-  m->pub.cfg = *c;
-  ubuild(*c, m->lay);
-  m->pub.nparam = m->lay.nparam;
-  const size_t bytes = unet_plan(*c, nullptr, nullptr);
-  if (hipMalloc(reinterpret_cast<void**>(&m->slab), bytes) != hipSuccess) {
-    snprintf(err, cap, "hipMalloc(%zu) failed", bytes);
-    delete m;
-    return nullptr;
-  }
-  unet_plan(*c, m, m->slab);
+int UNetModel::init() {
+  UNetModel* const m = this;
+  ubuild(cfg, lay, off);
+  const size_t bytes = unet_plan(cfg, nullptr, nullptr);
+  if (alloc_slab(bytes) != hipSuccess) return ral_fail("hipMalloc(%zu) failed", bytes);
+  unet_plan(cfg, m, slab);
   m->fused = (ral_knob("UNET_FUSED", 1) != 0);
-  if (c->train) {
+  if (cfg.train) {
     // the specialised backward kernels (all of them apply when every level's length is a multiple of 4) leave their
     // weight-gradient partials in scratch rows; otherwise some stage runs the generic kernel and everything stays atomic
-    m->fold = c->L % 64 == 0;
+    m->fold = cfg.L % 64 == 0;
     std::vector<int> cols;
-    const int ch[5] = {c->leads, 4, 8, 16, 32};
+    const int ch[5] = {cfg.leads, 4, 8, 16, 32};
     const int Cs[11] = {4, 8, 16, 32, 32, 32, 32, 16, 8, 4, ch[0]};
     const int Ci[11] = {ch[0], 4, 8, 16, 32, 32, 32, 32, 16, 8, 4};
     const int Ks[11] = {3, 3, 3, 3, 1, 3, 1, 4, 4, 4, 4};
     for (int si = 0; si < 11; ++si) {
-      for (int i = 0; i < Cs[si] * Ci[si] * Ks[si]; ++i) cols.push_back((int)m->lay.w[si] + i);
-      for (int i = 0; i < Cs[si]; ++i) cols.push_back((int)m->lay.b[si] + i);
+      for (int i = 0; i < Cs[si] * Ci[si] * Ks[si]; ++i) cols.push_back((int)m->off.w[si] + i);
+      for (int i = 0; i < Cs[si]; ++i) cols.push_back((int)m->off.b[si] + i);
     }
     m->ncols = (int)cols.size();
-    if (hipMemcpy(m->cols, cols.data(), cols.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-      snprintf(err, cap, "hipMemcpy(cols) failed");
-      (void)hipFree(m->slab); delete m;
-      return nullptr;
-    }
+    if (hipMemcpy(m->cols, cols.data(), cols.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return ral_fail("hipMemcpy(cols) failed");
   }
-  return m;
-}
-void unet_destroy(UNetModel* u) { if (u) { if (u->slab) (void)hipFree(u->slab); delete u; } }
-UNetPublic* unet_public(UNetModel* u) { return &u->pub; }
-int unet_bind(UNetModel* u, float* params, float* grads, float* am, float* av, float* state, double* bn_sums) {
-  u->pub.params = params; u->pub.grads = grads; u->pub.am = am; u->pub.av = av; u->pub.state = state; u->pub.bn_sums = bn_sums;
   return 0;
+}
+
+const RalKind* unet_kind() {
+  static const RalKind k = {
+      unet_check_cfg,
+      unet_layout,
+      [](const ral_config& c) { return unet_plan(c, nullptr, nullptr); },
+      1280,
+      []() -> ral_handle* { return new UNetModel(); },
+      "U-Net / DANet have a BatchNorm per layer: use ral_forward (per-rank statistics)"};
+  return &k;
 }
 
 // BatchNorm index feeding each z tensor (z index -> bn index), -1: none (z[6] = r)
@@ -1878,7 +1853,6 @@ static double* unet_rep(UNetModel* m, int dir, int bi) { return m->rep + ((size_
 
 static Src make_src(UNetModel* m, int zi, int act, bool training, bool with_grad, int accumulate) {
   Src s; memset(&s, 0, sizeof(s));
-  const UNetPublic& P = m->pub;
   s.z = m->z[zi];
   const int bi = BN_OF_Z[zi];
   if (bi >= 0) {
@@ -1886,11 +1860,11 @@ static Src make_src(UNetModel* m, int zi, int act, bool training, bool with_grad
     // forward statistics: the stages of a running one-call forward read the replicas their producers add to; everything
     // after it (and every stage-by-stage caller) reads the folded record in bn_sums
     const bool frep = !with_grad && m->nrep_f > 1;
-    s.sums = frep ? unet_rep(m, 0, bi) : (P.bn_sums ? P.bn_sums + 128 * bi : nullptr);
+    s.sums = frep ? unet_rep(m, 0, bi) : (m->bn_sums ? m->bn_sums + 128 * bi : nullptr);
     s.nrep = frep ? m->nrep_f : 1;
-    s.gamma = P.params + m->lay.bnw[bi]; s.beta = P.params + m->lay.bnb[bi];
-    s.running = P.state + m->lay.run[bi];
-    if (with_grad) s.bsums = m->nrep_b > 1 ? unet_rep(m, 1, bi) : P.bn_sums + 128 * bi + 64;
+    s.gamma = m->params + m->off.bnw[bi]; s.beta = m->params + m->off.bnb[bi];
+    s.running = m->state + m->off.run[bi];
+    if (with_grad) s.bsums = m->nrep_b > 1 ? unet_rep(m, 1, bi) : m->bn_sums + 128 * bi + 64;
   } else {
     s.norm = NORM_NONE;
   }
@@ -1908,18 +1882,17 @@ static size_t bwd_lds(const Stage& s) {
 
 // stage table: index 0-3 enc, 4-6 bottleneck, 7-10 dec
 static Stage make_stage(UNetModel* m, int si, const float* x, bool training, bool bwd, int B, double gwin) {
-  const ral_config& c = m->pub.cfg;
-  const UNetPublic& P = m->pub;
-  const ULayout& Y = m->lay;
+  const ral_config& c = m->cfg;
+  const UOff& Y = m->off;
   Stage s; memset(&s, 0, sizeof(s));
   const double cnt = gwin;   // windows behind every BatchNorm statistic: B, or the global batch under data parallelism
   auto cnt_of = [&](int zi) { return cnt * m->Ln[zi]; };
-  s.w = P.params + Y.w[si]; s.bias = P.params + Y.b[si];
+  s.w = m->params + Y.w[si]; s.bias = m->params + Y.b[si];
   s.out = m->z[si]; s.cout = m->C[si]; s.lout = m->Ln[si];
   const int bo = BN_OF_Z[si];
   // (forward: the record this stage adds to, in nrep replicas; backward: the folded forward record of its output)
   s.nrep = bwd ? m->nrep_b : m->nrep_f;
-  s.sums_out = (bo >= 0 && P.bn_sums) ? ((!bwd && m->nrep_f > 1) ? unet_rep(m, 0, bo) : P.bn_sums + 128 * bo) : nullptr;
+  s.sums_out = (bo >= 0 && m->bn_sums) ? ((!bwd && m->nrep_f > 1) ? unet_rep(m, 0, bo) : m->bn_sums + 128 * bo) : nullptr;
   s.count = cnt_of(si);
   s.stride = 1; s.pad = 0; s.mode = CONV;
   if (si <= 3) {                      // encoder: Conv1d(k3, s2, p1) -> BN -> LeakyReLU
@@ -1949,9 +1922,9 @@ static Stage make_stage(UNetModel* m, int si, const float* x, bool training, boo
   }
   if (bwd) {
     s.Gout = m->G[si];
-    s.bsums_out = bo >= 0 ? (m->nrep_b > 1 ? unet_rep(m, 1, bo) : P.bn_sums + 128 * bo + 64) : nullptr;
-    s.gamma_out = bo >= 0 ? P.params + Y.bnw[bo] : nullptr;
-    s.gw = P.grads + Y.w[si]; s.gb = P.grads + Y.b[si];
+    s.bsums_out = bo >= 0 ? (m->nrep_b > 1 ? unet_rep(m, 1, bo) : m->bn_sums + 128 * bo + 64) : nullptr;
+    s.gamma_out = bo >= 0 ? m->params + Y.bnw[bo] : nullptr;
+    s.gw = m->grads + Y.w[si]; s.gb = m->grads + Y.b[si];
     if (si == 10) s.Gout = m->last_dy;        // the gradient at the output BatchNorm is the caller's dy itself
     if (m->fold) { s.part = m->part; s.part_stride = m->part_stride; s.part_w = (int)Y.w[si]; s.part_b = (int)Y.b[si]; }
   }
@@ -2000,12 +1973,11 @@ static bool launch_unet_fwd_fast(const Stage& st, int si, int leads, int B, int 
 }
 
 // ---- forward, one stage at a time (a data-parallel caller all-reduces the stage's BatchNorm sums in between) ----
-int unet_forward_stage(UNetModel* m, const float* x, int B, int training, int si, int64_t gwin, hipStream_t s, char* err, size_t cap) {
-  UNetPublic& P = m->pub;
-  if (!P.params || !P.state) { snprintf(err, cap, "ral_bind was not called"); return -1; }
-  if (B <= 0 || B > P.cfg.max_batch) { snprintf(err, cap, "batch %d outside (0, %d]", B, P.cfg.max_batch); return -1; }
-  if (si < 0 || si > 10) { snprintf(err, cap, "U-Net stage %d outside [0, 10]", si); return -1; }
-  if (training && (!P.cfg.train || !P.bn_sums)) { snprintf(err, cap, "training forward needs train=1 and bn_sums"); return -1; }
+int unet_forward_stage(UNetModel* m, const float* x, int B, int training, int si, int64_t gwin, hipStream_t s) {
+  if (!m->params || !m->state) return ral_fail("ral_bind was not called");
+  if (B <= 0 || B > m->cfg.max_batch) return ral_fail("batch %d outside (0, %d]", B, m->cfg.max_batch);
+  if (si < 0 || si > 10) return ral_fail("U-Net stage %d outside [0, 10]", si);
+  if (training && (!m->cfg.train || !m->bn_sums)) return ral_fail("training forward needs train=1 and bn_sums");
   if (si == 0) {
     m->last_x = x; m->last_B = B; m->gsums_dy = nullptr;
     if (training) {
@@ -2014,23 +1986,22 @@ int unet_forward_stage(UNetModel* m, const float* x, int B, int training, int si
         if (!m->rep_all_clean) (void)hipMemsetAsync(unet_rep(m, 0, 0), 0, (size_t)2 * 10 * UNET_MAXREP * 64 * sizeof(double), s);
         m->rep_all_clean = false; m->rep_bwd_clean = true;
       }
-      else (void)hipMemsetAsync(P.bn_sums, 0, 1280 * sizeof(double), s);
+      else (void)hipMemsetAsync(m->bn_sums, 0, 1280 * sizeof(double), s);
     }
-  } else if (x != m->last_x || B != m->last_B) { snprintf(err, cap, "U-Net stages must follow stage 0 of the same batch"); return -1; }
+  } else if (x != m->last_x || B != m->last_B) return ral_fail("U-Net stages must follow stage 0 of the same batch");
   constexpr int fgmax = 512;   // (train forward at batch 2048: 0.31 / 0.27 / 0.29 / 0.41 ms with 256 / 512 / 1024 / 2048 workgroups)
   static const int egmax = (int)ral_knob("UNET_EVAL_GRID", 512);   // (stage-by-stage eval forward at batch 2048: 173 / 158 / 177 us with 256 / 512 / 1024 workgroups)
   const int gcap = training ? fgmax : egmax;
   const int grid = B < gcap ? B : gcap;
   Stage st = make_stage(m, si, x, training != 0, false, B, (double)gwin);
   if (!training) st.sums_out = nullptr;
-  if (!launch_unet_fwd_fast(st, si, P.cfg.leads, B, grid, s)) k_unet_fwd<<<grid, 256, fwd_lds(st), s>>>(st, B);
-  if (hipGetLastError() != hipSuccess) { snprintf(err, cap, "U-Net forward launch failed"); return -1; }
+  if (!launch_unet_fwd_fast(st, si, m->cfg.leads, B, grid, s)) k_unet_fwd<<<grid, 256, fwd_lds(st), s>>>(st, B);
+  if (hipGetLastError() != hipSuccess) return ral_fail("U-Net forward launch failed");
   return 0;
 }
 
-int unet_forward_finish(UNetModel* m, float* y, int B, int training, int64_t gwin, hipStream_t s, char* err, size_t cap) {
-  UNetPublic& P = m->pub;
-  if (B != m->last_B) { snprintf(err, cap, "finish batch %d != stage batch %d", B, m->last_B); return -1; }
+int unet_forward_finish(UNetModel* m, float* y, int B, int training, int64_t gwin, hipStream_t s) {
+  if (B != m->last_B) return ral_fail("finish batch %d != stage batch %d", B, m->last_B);
   Src o = make_src(m, 10, ACT_NONE, training != 0, false, 0);
   const size_t total = (size_t)B * m->C[10] * m->Ln[10];
   BnUpdAll u;
@@ -2039,7 +2010,7 @@ int unet_forward_finish(UNetModel* m, float* y, int B, int training, int64_t gwi
     for (int zi = 0, k = 0; zi < 11; ++zi) {
       const int bi = BN_OF_Z[zi];
       if (bi < 0) continue;
-      u.l[k++] = BnUpd{m->nrep_f > 1 ? unet_rep(m, 0, bi) : P.bn_sums + 128 * bi, P.bn_sums + 128 * bi, P.state + m->lay.run[bi],
+      u.l[k++] = BnUpd{m->nrep_f > 1 ? unet_rep(m, 0, bi) : m->bn_sums + 128 * bi, m->bn_sums + 128 * bi, m->state + m->off.run[bi],
                        m->C[zi], (double)gwin * m->Ln[zi], m->nrep_f};
     }
   }
@@ -2048,7 +2019,7 @@ int unet_forward_finish(UNetModel* m, float* y, int B, int training, int64_t gwi
   k_unet_out<<<(int)((total / 4 + 255) / 256 < 1024 ? (total / 4 + 255) / 256 : 1024), 256, 0, s>>>(o, y, m->C[10], m->Ln[10],
                                                                                                (double)gwin * m->Ln[10], total, u, training ? 1 : 0);
   m->nrep_f = 1;
-  if (hipGetLastError() != hipSuccess) { snprintf(err, cap, "U-Net forward launch failed"); return -1; }
+  if (hipGetLastError() != hipSuccess) return ral_fail("U-Net forward launch failed");
   return 0;
 }
 
@@ -2056,50 +2027,46 @@ int unet_forward_finish(UNetModel* m, float* y, int B, int training, int64_t gwi
 // need whole 16-row tiles at the deepest level and the window's tensors must fit LDS).  RAL_UNET_FUSED=0 keeps the
 // stage-by-stage path (which serves every other length, and training).
 static bool unet_infer_fused_applies(const UNetModel* m) {
-  const ral_config& c = m->pub.cfg;
+  const ral_config& c = m->cfg;
   return m->fused && c.L % 256 == 0 && c.L <= 1024;
 }
-int unet_set_option(UNetModel* m, const char* key, int value) {
-  if (!strcmp(key, "unet_fused")) { m->fused = value != 0; return 0; }
-  return -1;
-}
 
-static int unet_forward_fused(UNetModel* m, const float* x, float* y, int B, hipStream_t s, char* err, size_t cap) {
-  UNetPublic& P = m->pub;
-  if (!P.params || !P.state) { snprintf(err, cap, "ral_bind was not called"); return -1; }
-  if (B <= 0 || B > P.cfg.max_batch) { snprintf(err, cap, "batch %d outside (0, %d]", B, P.cfg.max_batch); return -1; }
+static int unet_forward_fused(UNetModel* m, const float* x, float* y, int B, hipStream_t s) {
+  if (!m->params || !m->state) return ral_fail("ral_bind was not called");
+  if (B <= 0 || B > m->cfg.max_batch) return ral_fail("batch %d outside (0, %d]", B, m->cfg.max_batch);
   UPackArgs a;
-  a.params = P.params; a.state = P.state; a.pk = m->pack; a.leads = P.cfg.leads;
-  for (int i = 0; i < 11; ++i) { a.w[i] = m->lay.w[i]; a.b[i] = m->lay.b[i]; }
-  for (int i = 0; i < 10; ++i) { a.bnw[i] = m->lay.bnw[i]; a.bnb[i] = m->lay.bnb[i]; a.run[i] = m->lay.run[i]; }
+  a.params = m->params; a.state = m->state; a.pk = m->pack; a.leads = m->cfg.leads;
+  for (int i = 0; i < 11; ++i) { a.w[i] = m->off.w[i]; a.b[i] = m->off.b[i]; }
+  for (int i = 0; i < 10; ++i) { a.bnw[i] = m->off.bnw[i]; a.bnb[i] = m->off.bnb[i]; a.run[i] = m->off.run[i]; }
   k_unet_pack<<<(uinf::PTOT + 255) / 256, 256, 0, s>>>(a);
-  const size_t lds = uinf_lds_floats(P.cfg.L) * sizeof(float);
+  const size_t lds = uinf_lds_floats(m->cfg.L) * sizeof(float);
   // persistent grid = exactly the workgroups that are resident at once (a grid one LDS granule too optimistic runs its
   // surplus workgroups as a second round: measured 76 us instead of 45 us at batch 2048)
-  const void* kfn = P.cfg.leads == 1 ? reinterpret_cast<const void*>(k_unet_infer<1>) : reinterpret_cast<const void*>(k_unet_infer<2>);
+  const void* kfn = m->cfg.leads == 1 ? reinterpret_cast<const void*>(k_unet_infer<1>) : reinterpret_cast<const void*>(k_unet_infer<2>);
   (void)hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (m->infer_grid == 0) {
     int per_cu = 0, dev = 0, ncu = 256;
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-    const hipError_t e = P.cfg.leads == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_unet_infer<1>, 256, lds)
+    const hipError_t e = m->cfg.leads == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_unet_infer<1>, 256, lds)
                                            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_unet_infer<2>, 256, lds);
     if (e != hipSuccess || per_cu < 1) per_cu = 1;
     m->infer_grid = per_cu * ncu;
   }
   const int grid = B < m->infer_grid ? B : m->infer_grid;
-  if (P.cfg.leads == 1) k_unet_infer<1><<<grid, 256, lds, s>>>(m->pack, x, y, P.cfg.L, B);
-  else k_unet_infer<2><<<grid, 256, lds, s>>>(m->pack, x, y, P.cfg.L, B);
-  if (hipGetLastError() != hipSuccess) { snprintf(err, cap, "U-Net fused forward launch failed"); return -1; }
+  if (m->cfg.leads == 1) k_unet_infer<1><<<grid, 256, lds, s>>>(m->pack, x, y, m->cfg.L, B);
+  else k_unet_infer<2><<<grid, 256, lds, s>>>(m->pack, x, y, m->cfg.L, B);
+  if (hipGetLastError() != hipSuccess) return ral_fail("U-Net fused forward launch failed");
   return 0;
 }
 
-int unet_forward(UNetModel* m, const float* x, float* y, int B, int training, hipStream_t s, char* err, size_t cap) {
-  if (!training && unet_infer_fused_applies(m)) return unet_forward_fused(m, x, y, B, s, err, cap);
-  m->nrep_f = (training && m->pub.cfg.train) ? UNET_MAXREP : 1;
+int UNetModel::forward(const float* x, float* y, int B, int training, hipStream_t s) {
+  UNetModel* const m = this;
+  if (!training && unet_infer_fused_applies(m)) return unet_forward_fused(m, x, y, B, s);
+  m->nrep_f = (training && m->cfg.train) ? UNET_MAXREP : 1;
   for (int si = 0; si < 11; ++si)
-    if (unet_forward_stage(m, x, B, training, si, B, s, err, cap)) { m->nrep_f = 1; return -1; }
-  const int rc = unet_forward_finish(m, y, B, training, B, s, err, cap);
+    if (unet_forward_stage(m, x, B, training, si, B, s)) { m->nrep_f = 1; return -1; }
+  const int rc = unet_forward_finish(m, y, B, training, B, s);
   m->nrep_f = 1;
   return rc;
 }
@@ -2148,27 +2115,26 @@ static void unet_zero_bwd_records(UNetModel* m, hipStream_t s) {
   if (m->nrep_b > 1) {
     if (!m->rep_bwd_clean) (void)hipMemsetAsync(unet_rep(m, 1, 0), 0, (size_t)10 * UNET_MAXREP * 64 * sizeof(double), s);
     m->rep_bwd_clean = false; m->rep_all_clean = false;
-  } else (void)hipMemset2DAsync(m->pub.bn_sums + 64, 128 * sizeof(double), 0, 64 * sizeof(double), 10, s);
+  } else (void)hipMemset2DAsync(m->bn_sums + 64, 128 * sizeof(double), 0, 64 * sizeof(double), 10, s);
 }
 
 // Training forward + loss + metrics in one call (ral_forward_loss_means): the stage kernels, then ONE kernel for the output
 // BatchNorm, the loss sums, dy and the backward pass's first two sums (k_unet_out_loss).  Whole-batch statistics only (the
 // data-parallel path drives the stages itself); the sums are left where unet_backward(dy) looks for them.
 int unet_forward_loss(UNetModel* m, const float* x, const float* target, float* y, int B, float* dy, float* snr, float* rmse,
-                      double* loss_sum, double* fin, double fin_scale, int fin3, hipStream_t s, char* err, size_t cap) {
-  UNetPublic& P = m->pub;
-  if (!P.cfg.train || !P.grads || !P.bn_sums) { snprintf(err, cap, "forward + loss needs train=1, grads and bn_sums bound"); return -1; }
-  if (!target || !y || !dy) { snprintf(err, cap, "forward + loss: null pointer"); return -1; }
+                      double* loss_sum, double* fin, double fin_scale, int fin3, hipStream_t s) {
+  if (!m->cfg.train || !m->grads || !m->bn_sums) return ral_fail("forward + loss needs train=1, grads and bn_sums bound");
+  if (!target || !y || !dy) return ral_fail("forward + loss: null pointer");
   m->nrep_f = UNET_MAXREP;
   for (int si = 0; si < 11; ++si)
-    if (unet_forward_stage(m, x, B, 1, si, B, s, err, cap)) { m->nrep_f = 1; return -1; }
+    if (unet_forward_stage(m, x, B, 1, si, B, s)) { m->nrep_f = 1; return -1; }
   Src o = make_src(m, 10, ACT_NONE, true, false, 0);
   BnUpdAll u;
   memset(&u, 0, sizeof(u));
   for (int zi = 0, k = 0; zi < 11; ++zi) {
     const int bi = BN_OF_Z[zi];
     if (bi < 0) continue;
-    u.l[k++] = BnUpd{m->nrep_f > 1 ? unet_rep(m, 0, bi) : P.bn_sums + 128 * bi, P.bn_sums + 128 * bi, P.state + m->lay.run[bi],
+    u.l[k++] = BnUpd{m->nrep_f > 1 ? unet_rep(m, 0, bi) : m->bn_sums + 128 * bi, m->bn_sums + 128 * bi, m->state + m->off.run[bi],
                      m->C[zi], (double)B * m->Ln[zi], m->nrep_f};
   }
   m->nrep_b = UNET_MAXREP;
@@ -2178,25 +2144,24 @@ int unet_forward_loss(UNetModel* m, const float* x, const float* target, float* 
   const int g = (B + UOL_WAVES - 1) / UOL_WAVES;
   k_unet_out_loss<<<g < gmax ? g : gmax, 64 * UOL_WAVES, 0, s>>>(o, y, target, dy, snr, rmse, loss_sum, C, L, B, (double)B * L,
                                                                (float)(2.0 / ((double)B * n)), fin, fin_scale, fin3, u,
-                                                               m->nrep_b > 1 ? unet_rep(m, 1, 9) : P.bn_sums + 128 * 9 + 64, m->nrep_b);
+                                                               m->nrep_b > 1 ? unet_rep(m, 1, 9) : m->bn_sums + 128 * 9 + 64, m->nrep_b);
   m->gsums_dy = dy; m->gsums_nrep = m->nrep_b;
   m->nrep_f = 1; m->nrep_b = 1;
-  if (hipGetLastError() != hipSuccess) { snprintf(err, cap, "U-Net forward launch failed"); return -1; }
+  if (hipGetLastError() != hipSuccess) return ral_fail("U-Net forward launch failed");
   return 0;
 }
 
-int unet_backward_start(UNetModel* m, const float* dy, int B, int64_t gwin, hipStream_t s, char* err, size_t cap) {
-  UNetPublic& P = m->pub;
-  if (!P.cfg.train || !P.grads || !P.bn_sums) { snprintf(err, cap, "backward needs train=1, grads and bn_sums bound"); return -1; }
-  if (B != m->last_B) { snprintf(err, cap, "backward batch %d != forward batch %d", B, m->last_B); return -1; }
+int unet_backward_start(UNetModel* m, const float* dy, int B, int64_t gwin, hipStream_t s) {
+  if (!m->cfg.train || !m->grads || !m->bn_sums) return ral_fail("backward needs train=1, grads and bn_sums bound");
+  if (B != m->last_B) return ral_fail("backward batch %d != forward batch %d", B, m->last_B);
   // with the fold every gradient entry is WRITTEN by k_unet_fold; the atomic path accumulates into a zeroed buffer
-  if (!m->fold) (void)hipMemsetAsync(P.grads, 0, (size_t)m->lay.nparam * sizeof(float), s);
+  if (!m->fold) (void)hipMemsetAsync(m->grads, 0, (size_t)m->lay.nparam * sizeof(float), s);
   // dy == NULL: "the gradient unet_forward_loss wrote, untouched" - its sums are already in the output layer's backward record.
   // A dy the caller passes explicitly is summed again, whatever its address: its CONTENTS may have changed since (loss
   // scaling, gradient accumulation), and the stage kernels read the new values.
   bool have_sums = false;
   if (!dy) {
-    if (!m->gsums_dy) { snprintf(err, cap, "U-Net backward with dy = NULL must follow ral_forward_loss_means"); return -1; }
+    if (!m->gsums_dy) return ral_fail("U-Net backward with dy = NULL must follow ral_forward_loss_means");
     dy = m->gsums_dy;
     have_sums = m->gsums_nrep == m->nrep_b;
   }
@@ -2209,22 +2174,21 @@ int unet_backward_start(UNetModel* m, const float* dy, int B, int64_t gwin, hipS
   Src o = make_src(m, 10, ACT_NONE, true, false, 0);
   const size_t grows = (total / m->Ln[10] + 3) / 4;      // one wave per (window, channel) row
   k_unet_gsums<<<(int)(grows < 512 ? grows : 512), 256, 0, s>>>(
-      dy, o, m->C[10], m->Ln[10], (double)gwin * m->Ln[10], m->nrep_b > 1 ? unet_rep(m, 1, 9) : P.bn_sums + 128 * 9 + 64, m->nrep_b, total);
-  if (hipGetLastError() != hipSuccess) { snprintf(err, cap, "U-Net backward launch failed"); return -1; }
+      dy, o, m->C[10], m->Ln[10], (double)gwin * m->Ln[10], m->nrep_b > 1 ? unet_rep(m, 1, 9) : m->bn_sums + 128 * 9 + 64, m->nrep_b, total);
+  if (hipGetLastError() != hipSuccess) return ral_fail("U-Net backward launch failed");
   return 0;
 }
 
-int unet_backward_stage(UNetModel* m, int B, int si, int64_t gwin, hipStream_t s, char* err, size_t cap) {
-  UNetPublic& P = m->pub;
-  if (B != m->last_B) { snprintf(err, cap, "backward batch %d != forward batch %d", B, m->last_B); return -1; }
-  if (si < 0 || si > 10) { snprintf(err, cap, "U-Net stage %d outside [0, 10]", si); return -1; }
+int unet_backward_stage(UNetModel* m, int B, int si, int64_t gwin, hipStream_t s) {
+  if (B != m->last_B) return ral_fail("backward batch %d != forward batch %d", B, m->last_B);
+  if (si < 0 || si > 10) return ral_fail("U-Net stage %d outside [0, 10]", si);
   // every workgroup ends with ~2 000 global atomics (its share of dW, db and the BatchNorm-backward sums): the chip retires
   // ~75 of them per ns, so 1024 workgroups spend 30 us per launch on them alone.  Measured train step at batch 2048 with
   // 1024 / 512 / 384 workgroups: 1.23 / 1.08 / 1.12 ms
   constexpr int gmax0 = 512, wp = 2;   // (wp: at most two windows per pass of the specialised kernels, launch_bwd_t)
   const int gmax = (m->fold && gmax0 > m->part_rows_max) ? m->part_rows_max : gmax0;
   const int grid = B < gmax ? B : gmax;
-  if (m->last_dy == nullptr) { snprintf(err, cap, "U-Net backward stages must follow ral_unet_backward_start"); return -1; }
+  if (m->last_dy == nullptr) return ral_fail("U-Net backward stages must follow ral_unet_backward_start");
   m->bwd_rows = grid;                             // (the same for every stage of a backward pass: it depends on B only)
   // consumers run in reverse order; an encoder tensor's gradient is first WRITTEN by its decoder-side consumer
   // (skip / residual, accumulate = 0) and later ACCUMULATED by the next encoder / bottleneck stage (accumulate = 1)
@@ -2233,21 +2197,20 @@ int unet_backward_stage(UNetModel* m, int B, int si, int64_t gwin, hipStream_t s
   const size_t lds = bwd_lds(st);
   static size_t cur = 0;
   if (lds > cur) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_unet_bwd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); cur = lds; }
-  if (!launch_unet_bwd_fast(st, si, P.cfg.leads, B, grid, wp, s)) k_unet_bwd<<<grid, 256, lds, s>>>(st, B);
-  if (hipGetLastError() != hipSuccess) { snprintf(err, cap, "U-Net backward launch failed"); return -1; }
+  if (!launch_unet_bwd_fast(st, si, m->cfg.leads, B, grid, wp, s)) k_unet_bwd<<<grid, 256, lds, s>>>(st, B);
+  if (hipGetLastError() != hipSuccess) return ral_fail("U-Net backward launch failed");
   return 0;
 }
 
-int unet_backward_finish(UNetModel* m, int B, int64_t gwin, hipStream_t s, char* err, size_t cap) {
-  UNetPublic& P = m->pub;
+int unet_backward_finish(UNetModel* m, int B, int64_t gwin, hipStream_t s) {
   BnGradAll u;
   for (int bi = 0; bi < 10; ++bi)
-    u.l[bi] = BnGrad{m->nrep_b > 1 ? unet_rep(m, 1, bi) : P.bn_sums + 128 * bi + 64, P.bn_sums + 128 * bi + 64,
-                     P.grads + m->lay.bnw[bi], P.grads + m->lay.bnb[bi], m->lay.bnC[bi], m->nrep_b};
+    u.l[bi] = BnGrad{m->nrep_b > 1 ? unet_rep(m, 1, bi) : m->bn_sums + 128 * bi + 64, m->bn_sums + 128 * bi + 64,
+                     m->grads + m->off.bnw[bi], m->grads + m->off.bnb[bi], m->off.bnC[bi], m->nrep_b};
   if (m->fold) {
-    if (m->bwd_rows <= 0) { snprintf(err, cap, "U-Net backward finish without its stages"); return -1; }
+    if (m->bwd_rows <= 0) return ral_fail("U-Net backward finish without its stages");
     const bool reps = m->nrep_b > 1;
-    k_unet_fold<<<(m->ncols + 63) / 64 + 1, 64 * UNET_FOLD_WAVES, 0, s>>>(m->part, m->part_stride, m->bwd_rows, m->cols, m->ncols, P.grads, u,
+    k_unet_fold<<<(m->ncols + 63) / 64 + 1, 64 * UNET_FOLD_WAVES, 0, s>>>(m->part, m->part_stride, m->bwd_rows, m->cols, m->ncols, m->grads, u,
                                                         (double)B / (double)gwin, reps ? unet_rep(m, 0, 0) : nullptr,
                                                         reps ? 2 * 10 * UNET_MAXREP * 64 : 0);
     if (reps) m->rep_all_clean = true;
@@ -2256,17 +2219,18 @@ int unet_backward_finish(UNetModel* m, int B, int64_t gwin, hipStream_t s, char*
   }
   m->last_dy = nullptr;
   m->nrep_b = 1;
-  if (hipGetLastError() != hipSuccess) { snprintf(err, cap, "U-Net backward launch failed"); return -1; }
+  if (hipGetLastError() != hipSuccess) return ral_fail("U-Net backward launch failed");
   return 0;
 }
 
-int unet_backward(UNetModel* m, const float* dy, float* dx, int B, hipStream_t s, char* err, size_t cap) {
-  if (dx) { snprintf(err, cap, "U-Net input gradient is not provided"); return -1; }
+int UNetModel::backward(const float* dy, float* dx, int B, hipStream_t s) {   // (dy = NULL: the gradient ral_forward_loss_means wrote)
+  UNetModel* const m = this;
+  if (dx) return ral_fail("U-Net input gradient is not provided");
   m->nrep_b = UNET_MAXREP;
-  if (unet_backward_start(m, dy, B, B, s, err, cap)) { m->nrep_b = 1; return -1; }
+  if (unet_backward_start(m, dy, B, B, s)) { m->nrep_b = 1; return -1; }
   for (int si = 10; si >= 0; --si)
-    if (unet_backward_stage(m, B, si, B, s, err, cap)) { m->nrep_b = 1; return -1; }
-  const int rc = unet_backward_finish(m, B, B, s, err, cap);
+    if (unet_backward_stage(m, B, si, B, s)) { m->nrep_b = 1; return -1; }
+  const int rc = unet_backward_finish(m, B, B, s);
   m->nrep_b = 1;
   return rc;
 }

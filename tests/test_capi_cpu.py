@@ -184,5 +184,87 @@ def test_library_reads_only_the_two_documented_environment_variables():
                 n_outside += 1
                 assert f.endswith("ral_api.hip"), (f, line)
     assert n_outside == 1                      # the one inside ral_env_int
-    src = open(os.path.join(ROOT, "ecg_denoise_amd", "csrc", "ral_api.hip")).read()
+    src = "".join(open(f).read() for f in sorted(glob.glob(os.path.join(ROOT, "ecg_denoise_amd", "csrc", "*.h*"))))   # (the two callers are RA-LENet's: ral_ralenet.hip)
     assert sorted(set(re.findall(r'ral_env_int\("(RAL_[A-Z_]+)"', src))) == ["RAL_LANES", "RAL_NO_SIDE_STREAM"]
+
+
+@pytest.mark.parametrize("variant,leads", [("unet", 2), ("unet", 1), ("acdae", 2)])
+def test_baseline_layout_matches_reference_state_dict(variant, leads, golden_dir):
+    """U-Net and ACDAE: parameter names in the reference's named_parameters() order (the fixtures' key lists), the oracle's
+    shapes, tensors that do not overlap, start on 16 bytes and end inside ral_param_floats; U-Net's BatchNorm buffers follow
+    their layer and tile the state buffer"""
+    cfg = _lib.make_config(variant, leads, 512, 4, 1)
+    ent = _lib.layout(cfg)
+    shapes = O.unet_param_shapes(leads) if variant == "unet" else O.acdae_param_shapes()
+    mine = [(e["name"], tuple(e["shape"])) for e in ent if e["kind"] == _lib.KIND_PARAM]
+    assert mine == [(k, tuple(s)) for k, s in shapes.items()]
+    if leads == 2:
+        g = np.load(os.path.join(golden_dir, f"g3_{variant}_l2_L512.npz"))
+        assert [str(k) for k in g["keys"]] == [n for n, _ in mine]
+    segs = sorted((e["offset"], e["offset"] + int(np.prod(e["shape"]))) for e in ent if e["kind"] == _lib.KIND_PARAM)
+    assert segs[0][0] == 0 and all(a[1] <= b[0] for a, b in zip(segs, segs[1:]))
+    assert all(s[0] % 4 == 0 for s in segs)
+    nparam = _lib.lib().ral_param_floats(C.byref(cfg))
+    assert segs[-1][1] <= nparam < segs[-1][1] + 4          # (nothing after the last tensor but its padding)
+    state = sorted((e["offset"], e["offset"] + int(np.prod(e["shape"]))) for e in ent if e["kind"] == _lib.KIND_STATE)
+    nstate = _lib.lib().ral_state_floats(C.byref(cfg))
+    if variant == "acdae":
+        assert len(ent) == len(mine) == 20 and nstate == 0
+    else:
+        names = [e["name"] for e in ent]
+        for i, n in enumerate(names):
+            if n.endswith(".running_mean"):
+                pre = n[:-len("running_mean")]
+                assert names[i - 2:i + 3] == [pre + s for s in ("weight", "bias", "running_mean", "running_var", "num_batches_tracked")]
+        assert len(ent) == 42 + 3 * 10 and len(state) == 20
+        assert state[0][0] == 0 and all(a[1] == b[0] for a, b in zip(state, state[1:])) and state[-1][1] == nstate
+
+
+def _entry(cfg, idx, cap):
+    name = C.create_string_buffer(256)
+    kind, ndim, off, shape = C.c_int32(), C.c_int32(), C.c_int64(), (C.c_int64 * 4)()
+    rc = _lib.lib().ral_layout_entry(C.byref(cfg), idx, name, cap, C.byref(kind), C.byref(off), C.byref(ndim), shape)
+    return rc, _lib.lib().ral_last_error().decode()
+
+
+ALL_NETWORKS = [("nra", 1, 64), ("full", 2, 512), ("mlp", 2, 512), ("unet", 1, 16), ("acdae", 2, 64), ("danet", 2, 32)]
+
+
+@pytest.mark.parametrize("variant,leads,L", ALL_NETWORKS)
+def test_layout_entry_failures_say_which_argument(variant, leads, L):
+    """a bad index and a short name buffer are told apart, in the same words, for every network (return code -1 as ever)"""
+    cfg = _lib.make_config(variant, leads, L, 2, 1)
+    n = _lib.lib().ral_layout_count(C.byref(cfg))
+    assert n > 0
+    _lib.lib().ral_param_floats(C.byref(_lib.make_config(variant, leads, L, 0, 1)))     # leaves another message behind
+    assert _entry(cfg, -1, 256) == (-1, "entry -1 out of range")
+    assert _entry(cfg, n, 256) == (-1, f"entry {n} out of range")
+    assert _entry(cfg, 0, 1) == (-1, "name buffer too small")
+    assert _entry(cfg, n - 1, 256)[0] == 0
+
+
+@pytest.mark.parametrize("variant,leads,L", ALL_NETWORKS)
+def test_pe_table_only_for_ralenet_variants(variant, leads, L):
+    """the positional-encoding table is RA-LENet's: every other network is refused, at every level"""
+    cfg = _lib.make_config(variant, leads, L, 2, 1)
+    buf = np.full(L * 128, np.nan, np.float32)
+    for level in range(-1, 6):
+        rc = _lib.lib().ral_pe_table(C.byref(cfg), level, buf.ctypes.data_as(C.c_void_p), C.c_int64(buf.size))
+        if variant in ("nra", "full", "mlp") and 0 <= level <= 4:
+            assert rc == 0
+        else:
+            assert rc == -1 and _lib.lib().ral_last_error().decode() == "no PE table for this variant/level"
+    if variant not in ("nra", "full", "mlp"):
+        assert np.isnan(buf).all()                # (nothing was written)
+
+
+def test_backward_halves_refusal_names_no_network():
+    """ral_backward_begin / _end are RA-LENet's; their refusal on another handle says so without naming a network the handle
+    is not (the text the GPU test of the handles asserts on real handles: no handle can be created here)"""
+    src = open(os.path.join(ROOT, "ecg_denoise_amd", "csrc", "ral_api.hip")).read()
+    for fn in ("ral_backward_begin", "ral_backward_end"):
+        body = src[src.index(f"int {fn}(ral_handle* h"):]
+        body = body[:body.index("\n}\n")]
+        msgs = re.findall(r'"([^"]+)"', body)
+        assert msgs == ["null handle", f"{fn}: RA-LENet handles only (the other networks: ral_backward)"], msgs
+        assert not re.search(r"U-Net|ACDAE|DANet", body)

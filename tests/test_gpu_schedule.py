@@ -1,4 +1,4 @@
-"""The host code that strings the RA-LENet kernels into a step (csrc/ral_api.hip): micro-batch lanes 1 .. 4, weight-gradient
+"""The host code that strings the RA-LENet kernels into a step (csrc/ral_ralenet.hip): micro-batch lanes 1 .. 4, weight-gradient
 side streams on and off, 2 / 6 / 8 sets of backward temporaries, one handle driven with changing batches, the weight planes
 an eval-mode model keeps between forwards, and the profile hooks (`pytest -m gpu`).
 
