@@ -163,6 +163,8 @@ _SIGS = {
     "ral_attention_backward_scratch_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "ral_attention_plan": (C.c_int, [C.c_int] * 8 + [C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                      C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "ral_block_plan": (C.c_int, [C.c_int] * 9 + [C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+                       + [C.POINTER(C.c_int32)] * 5),
     "ral_attention_backward": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, C.c_int, C.c_int, C.c_int,
                                          C.c_int, _VP]),
     "ral_set_option": (C.c_int, [_VP, C.c_char_p, C.c_int]),

@@ -869,6 +869,31 @@ int ral_attention_plan(int backward, int N, int H, int Len, int has_table, int f
   return 0;
 }
 
+int ral_block_plan(int launch, int C, int N, int NE, int training, int second_out, int want_dw, int f16_split, int narrow_f16,
+                   char* kernel_name, int name_cap, int32_t* threads, int64_t* lds_bytes, int32_t* chunks, int32_t* split,
+                   int32_t* stores_upre, int32_t* mlp_dw_fused, int32_t* dw_split) {
+  if (launch < 0 || launch > 7) return ral_fail("block plan: launch must be 0 .. 7 (qkv_fwd, mlp_fwd, mlp_bwd, qkv_bwd, dw fc2, fc1, proj, qkv; got %d)", launch);
+  if (C != 8 && C != 16 && C != 32 && C != 64 && C != 128) return ral_fail("block plan: C must be 8, 16, 32, 64 or 128 (got %d)", C);
+  if (N < 16 || N % 16 != 0 || N > 1024) return ral_fail("block plan: N must be a multiple of 16 in [16, 1024] (got %d)", N);
+  if (C * N > 8 * 1024) return ral_fail("block plan: C N = %d: a level of a model holds C N = 8 Lp <= 8192 floats per window", C * N);
+  if (NE < 0 || NE > N) return ral_fail("block plan: NE=%d existing tokens of N=%d slots", NE, N);
+  if (f16_split < 0) return ral_fail("block plan: f16_split must not be negative (got %d)", f16_split);
+  if (f16_split > 0 && NE > 0 && NE < N) return ral_fail("block plan: f16_split > 0 needs whole windows (NE=%d of N=%d: padded windows run on fp32 MFMA)", NE, N);
+  const BlockPlan p = block_plan(BlockShape{C, N, NE, training != 0, second_out != 0, want_dw != 0, f16_split > 0 && C >= f16_split,
+                                            f16_split > 0 && narrow_f16 != 0});
+  const BlockLaunch* const all[8] = {&p.qkv_fwd, &p.mlp_fwd, &p.mlp_bwd, &p.qkv_bwd, &p.dw[0], &p.dw[1], &p.dw[2], &p.dw[3]};
+  const BlockLaunch& l = *all[launch];
+  if (kernel_name && name_cap > 0) snprintf(kernel_name, (size_t)name_cap, "%s", l.name);
+  if (threads) *threads = l.threads;
+  if (lds_bytes) *lds_bytes = (int64_t)l.lds;
+  if (chunks) *chunks = l.chunks;
+  if (split) *split = l.split ? 1 : 0;
+  if (stores_upre) *stores_upre = p.stores_upre ? 1 : 0;
+  if (mlp_dw_fused) *mlp_dw_fused = p.mlp_dw_fused ? 1 : 0;
+  if (dw_split) *dw_split = p.dw_split ? 1 : 0;
+  return 0;
+}
+
 int64_t ral_attention_backward_scratch_floats(int N, int H, int Len, int has_table, int B) {
   if (!has_table) Len = 0;
   if (check_attn_args(N, H, Len, B)) return -1;

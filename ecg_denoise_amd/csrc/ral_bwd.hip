@@ -1803,130 +1803,50 @@ size_t mlp_bwd_lds(int C, int N, int nch) {
   return ((size_t)2 * N * ld_of(C) + (size_t)N * ld_of(4 * C / nch) + 2 * (N + 2) + 2 * N + 8 * C + 16) * sizeof(float);
 }
 
-// narrow levels: fused weight-gradient variant (k_mlp_bwd_s) when the window length gives each wave a whole
-// number (1, 2, 4 or 8) of dg token tiles; RAL_FUSE_DW=0 keeps the separate dW kernels
-// does the fused narrow-level kernel take (C, N)?  The forward asks too: it does not store u_pre for such blocks
-template <int C>
-static bool mlp_bwd_s_applies(int N, int* tw_out, size_t* lds_out) {
-  static const int maxc = (int)ral_knob("FUSE_DW", 32);
-  constexpr int MT = C >= 16 ? C / 16 : 1;
-  if (C > maxc || (N * MT) % 128 != 0) return false;
-  const int tw = N * MT / 128;
-  if (tw != 1 && tw != 2 && tw != 4 && tw != 8) return false;
+// narrow levels, fused weight-gradient variant (k_mlp_bwd_s): the bytes of its tiles, and of the region its weight-gradient
+// flush needs at least (fold region + the two staged weight-gradient matrices)
+size_t mlp_bwd_s_lds(int C, int N) {
   const int ldb = C == 16 ? C : ld_of(C);
-  size_t lds = ((size_t)2 * N * ld_of(C) + (size_t)2 * N * ldb + 2 * (N + 2) + 2 * N + 2 * C + 8) * sizeof(float);
-  if (lds > 80 * 1024) return false;
-  const size_t flush = ((size_t)6656 + 8 * C * C) * sizeof(float);   // fold region + the two staged weight-gradient matrices
-  if (lds < flush) lds = flush;
-  if (tw_out) *tw_out = tw;
-  if (lds_out) *lds_out = lds;
-  return true;
+  return ((size_t)2 * N * ld_of(C) + (size_t)2 * N * ldb + 2 * (N + 2) + 2 * N + 2 * C + 8) * sizeof(float);
 }
-bool mlp_bwd_is_fused(int C, int N) {
-  switch (C) {
-    case 8: return mlp_bwd_s_applies<8>(N, nullptr, nullptr);
-    case 16: return mlp_bwd_s_applies<16>(N, nullptr, nullptr);
-    case 32: return mlp_bwd_s_applies<32>(N, nullptr, nullptr);
-  }
-  return false;
-}
+size_t mlp_bwd_s_flush_lds(int C) { return ((size_t)6656 + 8 * C * C) * sizeof(float); }
 
-template <int C>
-static bool launch_mlp_bwd_s(const float* dx2, const float* x1, const BlockP& w, const BlockP& wt,
-                             const BlockP& gr, float* dx1, float* do_hm, int N, int B, bool want_dw, hipStream_t s, int NE) {
-  // widest level that takes the fused kernel: RAL_FUSE_DW (0 disables it, 8 / 16 narrow it).  Measured at batch 2048:
-  // none 102.8k, C <= 8 103.8k, C <= 16 105.5k, C <= 32 105.8k windows/s (at C = 32 the weight-gradient MFMAs are
-  // no longer negligible on the critical stream, so the gain flattens)
-  int tw; size_t lds;
-  if (!mlp_bwd_s_applies<C>(N, &tw, &lds)) return false;
-  const int grid = cap(B, GRID_MLPS);
-#define GO(t) { RAL_SET_LDS((k_mlp_bwd_s<C, t>), lds); k_mlp_bwd_s<C, t><<<grid, 512, lds, s>>>(dx2, x1, w, wt, gr, dx1, do_hm, N, B, want_dw ? 1 : 0, NE); return true; }
-  switch (tw) { case 1: GO(1) case 2: GO(2) case 4: GO(4) case 8: GO(8) default: return false; }
-#undef GO
-}
-
-// wide levels on split fp16 operands: the hidden-chunk count that gives the fc2^T phase exactly one 32 x 32 unit per wave and
-// fits the LDS budget, or 0
-size_t mlp_bwd_h_lds(int C, int N, int nch, bool small = false) {   // small: the four-wave form (no separate dg tile)
+// wide levels on split fp16 operands
+size_t mlp_bwd_h_lds(int C, int N, int nch, bool small) {   // small: the four-wave form (no separate dg tile)
   const int HC = 4 * C / nch;
   return (size_t)2 * N * ldb_of(C) * 2 + (small ? 0 : (size_t)N * ld_of(C) * 4) + (size_t)N * (HC + 8) * 4 + ((size_t)2 * (N + 2) + 5 * N + 2 * C + 4) * 4;
 }
-// Threads of a k_mlp_bwd_h workgroup: 256 (nch > 0): four waves, 37-39 KB of LDS, 150 registers per lane, three workgroups per
-// CU; 512 (nch < 0): eight waves, 75-78 KB, 128 registers (28-68 bytes of scratch), two per CU - the shapes the four-wave form does
-// not cover.  Measured at batch 2048 on the shapes both take: the four-wave form is the SLOWER kernel on an empty GPU (`mlp_bwd`
-// 2.66 -> 2.76 ms per step serialised) and the faster training step (12.98 -> 12.88 ms, 13.57 -> 13.42 on a slower box;
-// interleaved A/B, three rounds each).  What it changes beside the other lane's kernels and the 76 KB weight-gradient
-// workgroups: half the LDS and half the waves per workgroup, no spills, and no dg read-modify-write through LDS per hidden chunk
-// (k_qkv_bwd_h with half the LDS and waves alone - half-window work items - did not move the step).
-int mlp_bwd_h_nch(int C, int N) {
-  if ((C != 32 && C != 64 && C != 128) || N % 32 != 0) return 0;
-  // four waves: N C = 4096, one 32 x 32 unit of dg per wave; HC + 8 >= C + 4: the dg tile fits the chunk's bytes
-  for (int nch = 1; nch <= 4; nch *= 2)
-    if (N * C == 4096 && 4 * C / nch >= C && (4 * C / nch / 32) * (N / 32) == 4 && mlp_bwd_h_lds(C, N, nch, true) <= 54400) return nch;
-  for (int nch = 1; nch <= 4; nch *= 2)   // eight waves
-    if ((4 * C / nch / 32) * (N / 32) == 8 && mlp_bwd_h_lds(C, N, nch) <= 79872) return -nch;
-  return 0;
-}
-template <int C>
-static void launch_mlp_bwd_hc(int nch, const float* dx2, const float* x1, const float* upre, const BlockP& w, const BlockP& wt,
-                              const float* ptbase, const void* wtt, const BlockP& gr, float* dupre, float* dx1, float* do_hm,
-                              float* a2c0, unsigned* gmax, int N, int B, hipStream_t s) {
-  const bool small = nch > 0;
-  if (nch < 0) nch = -nch;
-  const size_t lds = mlp_bwd_h_lds(C, N, nch, small);
-  const int grid = cap(B, small ? GRID_MLPB * 3 / 2 : GRID_MLPB);
-  const _Float16* wp = reinterpret_cast<const _Float16*>(wtt);
-  if (small) {
-    if (nch == 2) { RAL_SET_LDS((k_mlp_bwd_h<C, 2, 256>), lds); k_mlp_bwd_h<C, 2, 256><<<grid, 256, lds, s>>>(dx2, x1, upre, w, wt, ptbase, wp, gr, dupre, dx1, do_hm, a2c0, gmax, N, B); }
-    else { RAL_SET_LDS((k_mlp_bwd_h<C, 4, 256>), lds); k_mlp_bwd_h<C, 4, 256><<<grid, 256, lds, s>>>(dx2, x1, upre, w, wt, ptbase, wp, gr, dupre, dx1, do_hm, a2c0, gmax, N, B); }
-    return;
-  }
-  if (nch == 1) { RAL_SET_LDS((k_mlp_bwd_h<C, 1>), lds); k_mlp_bwd_h<C, 1><<<grid, 512, lds, s>>>(dx2, x1, upre, w, wt, ptbase, wp, gr, dupre, dx1, do_hm, a2c0, gmax, N, B); }
-  else if (nch == 2) { RAL_SET_LDS((k_mlp_bwd_h<C, 2>), lds); k_mlp_bwd_h<C, 2><<<grid, 512, lds, s>>>(dx2, x1, upre, w, wt, ptbase, wp, gr, dupre, dx1, do_hm, a2c0, gmax, N, B); }
-  else { RAL_SET_LDS((k_mlp_bwd_h<C, 4>), lds); k_mlp_bwd_h<C, 4><<<grid, 512, lds, s>>>(dx2, x1, upre, w, wt, ptbase, wp, gr, dupre, dx1, do_hm, a2c0, gmax, N, B); }
-}
 
-template <int C>
-static bool launch_mlp_bwd_c(int nch, const float* dx2, const float* x1, const float* upre, const BlockP& w,
-                             const BlockP& wt, const BlockP& gr, float* dupre, float* dx1, float* do_hm, float* a2c0, int N, int B,
-                             bool want_dw, hipStream_t s, int NE) {
-  if constexpr (C <= 32) {
-    if (launch_mlp_bwd_s<C>(dx2, x1, w, wt, gr, dx1, do_hm, N, B, want_dw, s, NE)) return true;
-  }
-  const size_t lds = mlp_bwd_lds(C, N, nch);
-  const int grid = cap(B, GRID_MLPB);
-  if (nch == 1) { RAL_SET_LDS((k_mlp_bwd<C, 1>), lds); k_mlp_bwd<C, 1><<<grid, 512, lds, s>>>(dx2, x1, upre, w, wt, gr, dupre, dx1, do_hm, a2c0, N, B, NE); }
-  else if (nch == 2) { RAL_SET_LDS((k_mlp_bwd<C, 2>), lds); k_mlp_bwd<C, 2><<<grid, 512, lds, s>>>(dx2, x1, upre, w, wt, gr, dupre, dx1, do_hm, a2c0, N, B, NE); }
-  else { RAL_SET_LDS((k_mlp_bwd<C, 4>), lds); k_mlp_bwd<C, 4><<<grid, 512, lds, s>>>(dx2, x1, upre, w, wt, gr, dupre, dx1, do_hm, a2c0, N, B, NE); }
-  return false;
-}
-
-// returns true when the fc1 / fc2 weight (and bias) gradients were produced here (narrow levels): the caller then
-// skips those two products in launch_block_dw
-bool launch_mlp_bwd(int C, int nch, const float* dx2, const float* x1, const float* upre, const BlockP& w,
+// dupre, a2c0: consumed by the weight-gradient kernels only (want_dw).  gmax: see ral_kernels.hpp
+void launch_mlp_bwd(const BlockLaunch& p, const float* dx2, const float* x1, const float* upre, const BlockP& w,
                     const BlockP& wt, const float* ptbase, const void* wtt, unsigned* gmax, const BlockP& gr, float* dupre, float* dx1, float* do_hm,
-                    float* a2c0, int N, int B, bool want_dw, hipStream_t s, int f16_narrow, int NE) {
-  if (!want_dw) { dupre = nullptr; a2c0 = nullptr; }   // consumed by the weight-gradient kernels only
+                    float* a2c0, int N, int B, bool want_dw, hipStream_t s, int NE) {
+  using K = BlockKernel;
+  if (!want_dw) { dupre = nullptr; a2c0 = nullptr; }
   if (NE <= 0 || NE > N) NE = N;
-  const bool padded = NE < N;   // padded windows: the generic kernels (their local-enhancement conv knows where the window ends)
-  if (!padded && wtt && upre) {   // (upre == nullptr: a level whose forward does not store u_pre - the fused narrow-level kernel re-computes it)
-    const int nh = mlp_bwd_h_nch(C, N);
-    if (nh && C == 32) { launch_mlp_bwd_hc<32>(nh, dx2, x1, upre, w, wt, ptbase, wtt, gr, dupre, dx1, do_hm, a2c0, want_dw ? gmax : nullptr, N, B, s); return false; }
-    if (nh && C == 64) { launch_mlp_bwd_hc<64>(nh, dx2, x1, upre, w, wt, ptbase, wtt, gr, dupre, dx1, do_hm, a2c0, want_dw ? gmax : nullptr, N, B, s); return false; }
-    if (nh && C == 128) { launch_mlp_bwd_hc<128>(nh, dx2, x1, upre, w, wt, ptbase, wtt, gr, dupre, dx1, do_hm, a2c0, want_dw ? gmax : nullptr, N, B, s); return false; }
+  const _Float16* wp = reinterpret_cast<const _Float16*>(wtt);
+  const int grid = cap(B, GRID_MLPB);
+#define H(tag, c, n, t, g) case K::MLP_BWD_##tag##_##c##_##n: RAL_SET_LDS((k_mlp_bwd_h<c, n, t>), p.lds); \
+    k_mlp_bwd_h<c, n, t><<<cap(B, g), t, p.lds, s>>>(dx2, x1, upre, w, wt, ptbase, wp, gr, dupre, dx1, do_hm, a2c0, gmax, N, B); break;
+#define H4(c, n) H(H4, c, n, 256, GRID_MLPB * 3 / 2)
+#define H8(c, n) H(H8, c, n, 512, GRID_MLPB)
+#define S(c, t) case K::MLP_BWD_S_##c##_##t: RAL_SET_LDS((k_mlp_bwd_s<c, t>), p.lds); \
+    k_mlp_bwd_s<c, t><<<cap(B, GRID_MLPS), 512, p.lds, s>>>(dx2, x1, w, wt, gr, dx1, do_hm, N, B, want_dw ? 1 : 0, NE); break;
+#define F(c, n) case K::MLP_BWD_##c##_##n: RAL_SET_LDS((k_mlp_bwd<c, n>), p.lds); \
+    k_mlp_bwd<c, n><<<grid, 512, p.lds, s>>>(dx2, x1, upre, w, wt, gr, dupre, dx1, do_hm, a2c0, N, B, NE); break;
+#define F3(c) F(c, 1) F(c, 2) F(c, 4)
+  switch (p.kernel) {
+    H4(32, 4) H4(64, 4) H4(128, 4) H8(32, 1) H8(64, 1)
+    S(8, 1) S(8, 2) S(8, 4) S(16, 1) S(16, 2) S(32, 1) S(32, 2)
+    F3(8) F3(16) F3(32) F3(64) F3(128)
+    default: launch_mlp_bwd_w(p, dx2, x1, w, gr, dx1, do_hm, N, B, want_dw, s);   // narrow levels: the strips of ral_mlpw.hip
   }
-  if (!padded && !upre && mlp_bwd_is_fused(C, N)) {   // strip kernels (ral_mlpw.hip), fc1 / fc2 weight gradients fused
-    if (const int kind = mlp_bwd_w_kind(C, N, f16_narrow != 0)) {
-      launch_mlp_bwd_w(C, kind, dx2, x1, w, gr, dx1, do_hm, N, B, want_dw, s);
-      return true;
-    }
-  }
-  switch (C) {
-#define CASE(c) case c: return launch_mlp_bwd_c<c>(nch, dx2, x1, upre, w, wt, gr, dupre, dx1, do_hm, a2c0, N, B, want_dw, s, NE);
-    CASE(8) CASE(16) CASE(32) CASE(64) CASE(128)
-#undef CASE
-  }
-  return false;
+#undef H
+#undef H4
+#undef H8
+#undef S
+#undef F
+#undef F3
 }
 
 int launch_attn_bwd(const AttnPlan& p, const float* qkv, const float* o_hm, const float* do_hm, const float* lse, const float* table,
@@ -1972,30 +1892,25 @@ int launch_attn_bwd(const AttnPlan& p, const float* qkv, const float* o_hm, cons
 }
 
 size_t qkv_bwd_lds(int C, int N) { return ((size_t)N * 3 * C + (size_t)N * ld_of(C) + 5 * C + 8) * sizeof(float); }
-bool qkv_bwd_uses_f16(int C, int N) {
-  return (C == 32 || C == 64 || C == 128) && N % 32 == 0 && N * 3 * C / 4 <= 6 * 512;
-}
-void launch_qkv_bwd(int C, const float* dqkv, const float* x, const float* pe, const float* dx1, const float* extra,
+// (split operands: a work item is a whole window, NS = 1.  Half-window items (NS = 2: four-wave workgroups, half the LDS)
+// measured `qkv_bwd` 1.105 -> 1.075 ms per step serialised and the step unchanged.)
+size_t qkv_bwd_h_lds(int C, int N) { return (size_t)2 * N * ldb_of(3 * C) * 2 + ((size_t)N * ld_of(C) + 2 * C + 2 * N) * 4; }
+void launch_qkv_bwd(const BlockLaunch& p, const float* dqkv, const float* x, const float* pe, const float* dx1, const float* extra,
                     const BlockP& w, const BlockP& wt, const float* ptbase, const void* wtt, unsigned* gmax, const BlockP& gr, float* dx, int N, int B,
                     hipStream_t s) {
+  using K = BlockKernel;
   const int grid = cap(B, GRID_QKVB);
-  if (wtt && qkv_bwd_uses_f16(C, N)) {
-    // a work item is a whole window (NS = 1).  Half-window items (NS = 2: four-wave workgroups, half the LDS) measured `qkv_bwd`
-    // 1.105 -> 1.075 ms per step serialised and the step unchanged.
-    const size_t ldsh = (size_t)2 * N * ldb_of(3 * C) * 2 + ((size_t)N * ld_of(C) + 2 * C + 2 * N) * 4;
-    const _Float16* wp = reinterpret_cast<const _Float16*>(wtt);
-    if (C == 32) { RAL_SET_LDS((k_qkv_bwd_h<32>), ldsh); k_qkv_bwd_h<32><<<grid, 512, ldsh, s>>>(dqkv, x, pe, dx1, extra, w, wt, ptbase, wp, gr, dx, gmax, N, B, 1); }
-    else if (C == 64) { RAL_SET_LDS((k_qkv_bwd_h<64>), ldsh); k_qkv_bwd_h<64><<<grid, 512, ldsh, s>>>(dqkv, x, pe, dx1, extra, w, wt, ptbase, wp, gr, dx, gmax, N, B, 1); }
-    else { RAL_SET_LDS((k_qkv_bwd_h<128>), ldsh); k_qkv_bwd_h<128><<<grid, 512, ldsh, s>>>(dqkv, x, pe, dx1, extra, w, wt, ptbase, wp, gr, dx, gmax, N, B, 1); }
-    return;
+  const _Float16* wp = reinterpret_cast<const _Float16*>(wtt);
+#define H(c) case K::QKV_BWD_H_##c: RAL_SET_LDS((k_qkv_bwd_h<c>), p.lds); \
+    k_qkv_bwd_h<c><<<grid, 512, p.lds, s>>>(dqkv, x, pe, dx1, extra, w, wt, ptbase, wp, gr, dx, gmax, N, B, 1); break;
+#define F(c) case K::QKV_BWD_##c: RAL_SET_LDS((k_qkv_bwd<c>), p.lds); \
+    k_qkv_bwd<c><<<grid, 512, p.lds, s>>>(dqkv, x, pe, dx1, extra, w, wt, gr, dx, N, B); break;
+  switch (p.kernel) {
+    H(32) H(64) H(128) F(8) F(16) F(32) F(64) F(128)
+    default: block_launch_missing("launch_qkv_bwd", p);
   }
-  const size_t lds = qkv_bwd_lds(C, N);
-  switch (C) {
-#define CASE(c) case c: RAL_SET_LDS((k_qkv_bwd<c>), lds); \
-    k_qkv_bwd<c><<<grid, 512, lds, s>>>(dqkv, x, pe, dx1, extra, w, wt, gr, dx, N, B); break;
-    CASE(8) CASE(16) CASE(32) CASE(64) CASE(128)
-#undef CASE
-  }
+#undef H
+#undef F
 }
 
 void launch_resample_bwd(int D, bool sep, const float* dy, const float* x, const float* wred, const float* lnw,

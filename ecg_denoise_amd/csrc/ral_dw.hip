@@ -506,75 +506,97 @@ __global__ __launch_bounds__(512, RAL_DW_WPE) void k_dw(const float* Y, const fl
 }
 
 // ---------------------------------------------------------------------------------
-template <int M, int NC, int MS, int NS, int LAYY, int XF>
-static void launch_dw_t(const float* Y, const float* X, const float* pe, const float* lnw, const float* lnb,
-                        const float* a2c0, float* dW, float* dB, int N, int B, int ksplit, hipStream_t s,
-                        const unsigned* ymax = nullptr, const float* xscale = nullptr, int NV = 0) {
-  static_assert(M % MS == 0 && NC % NS == 0, "slices must tile dW");
+// Token chunk and LDS bytes of a product with (MS x NS) slices over windows of N tokens.  split: operands as fp16 pairs (token
+// chunks of at least one 32-token MFMA step); false when no such chunk divides N within the LDS budget (*tc, *lds untouched).
+// fp32 operands: the largest power-of-two chunk dividing N within the compile-time staging bound and the LDS budget.
+template <int MS, int NS, int LAYY, int XF>
+static bool dw_chunk_t(int N, bool split, int* tc, size_t* lds) {
   constexpr bool yhm = LAYY == LAY_HM, xhm = XF == XF_HM;
   constexpr int TM = (MS + 15) / 16, TN = (NS + 15) / 16;
   constexpr int KW = 4 / (WaveGrid4<TM, TN>::WM * WaveGrid4<TM, TN>::WN);
+  const size_t fold = (size_t)(KW - 1) * (TM * TN * 256 + TM * 16) * sizeof(float);   // K-split partials of the spare waves
+  int TC = dw_tcmax(MS, NS, yhm, xhm, XF == XF_LNPE);
+  if (split) {
+    if (MS % 16 != 0 || NS % 16 != 0 || MS < 32 || NS < 32) return false;
+    auto bytesh = [&](int t) { return (size_t)2 * t * (MS + 8 + NS + 8) * sizeof(float); };
+    while (TC > 32 && (N % TC != 0 || bytesh(TC) > RAL_DW_LDS_BYTES)) TC /= 2;
+    if (TC < 32 || N % TC != 0 || bytesh(TC) > RAL_DW_LDS_BYTES + 4096) return false;
+    *tc = TC; *lds = bytesh(TC) > fold ? bytesh(TC) : fold;
+    return true;
+  }
+  auto bytes = [&](int t) { return (size_t)2 * (dw_tile_floats(MS, yhm, t) + dw_tile_floats(NS, xhm, t)) * sizeof(float); };
+  while (TC > 16 && (N % TC != 0 || bytes(TC) > RAL_DW_LDS_BYTES)) TC /= 2;
+  *tc = TC; *lds = bytes(TC) > fold ? bytes(TC) : fold;
+  return true;
+}
+
+// H: split operands (ymax: the bits of the largest |Y| of the launch's windows, xscale: the activation scale of X)
+template <int M, int NC, int MS, int NS, int LAYY, int XF, bool H>
+static void launch_dw_t(const float* Y, const float* X, const float* pe, const float* lnw, const float* lnb,
+                        const float* a2c0, float* dW, float* dB, int N, int B, int ksplit, int TC, size_t lds, hipStream_t s,
+                        const unsigned* ymax = nullptr, const float* xscale = nullptr, int NV = 0) {
+  static_assert(M % MS == 0 && NC % NS == 0, "slices must tile dW");
   // ksplit is the split-K count of a fully sliced product; products with fewer slices get proportionally more
   // split-K workgroups so that every launch still fills the chip (at least ~256 workgroups)
   constexpr int nsl = (M / MS) * (NC / NS);
   int ks = ksplit;
   if (ks * nsl < RAL_DW_MINWG) ks = (RAL_DW_MINWG + nsl - 1) / nsl;
   dim3 grid(B < ks ? B : ks, nsl);
-  const size_t fold = (size_t)(KW - 1) * (TM * TN * 256 + TM * 16) * sizeof(float);   // K-split partials of the spare waves
-  if constexpr (MS % 16 == 0 && NS % 16 == 0 && MS >= 32 && NS >= 32) {
-    if (ymax) {   // split operands (token chunks of at least one 32-token MFMA step)
-      int TC = dw_tcmax(MS, NS, yhm, xhm, XF == XF_LNPE);
-      auto bytesh = [&](int tc) { return (size_t)2 * tc * (MS + 8 + NS + 8) * sizeof(float); };
-      while (TC > 32 && (N % TC != 0 || bytesh(TC) > RAL_DW_LDS_BYTES)) TC /= 2;
-      if (TC >= 32 && N % TC == 0 && bytesh(TC) <= RAL_DW_LDS_BYTES + 4096) {
-        const size_t lds = bytesh(TC) > fold ? bytesh(TC) : fold;
-        RAL_SET_LDS((k_dw<M, NC, MS, NS, LAYY, XF, true>), lds);
-        k_dw<M, NC, MS, NS, LAYY, XF, true><<<grid, 512, lds, s>>>(Y, X, pe, lnw, lnb, a2c0, dW, dB, ymax, xscale, N, TC, B, NV);
-        return;
-      }
-    }
-  }
-  // largest power-of-two token chunk dividing N within the compile-time staging bound and the LDS budget
-  int TC = dw_tcmax(MS, NS, yhm, xhm, XF == XF_LNPE);
-  auto bytes = [&](int tc) { return (size_t)2 * (dw_tile_floats(MS, yhm, tc) + dw_tile_floats(NS, xhm, tc)) * sizeof(float); };
-  while (TC > 16 && (N % TC != 0 || bytes(TC) > RAL_DW_LDS_BYTES)) TC /= 2;
-  const size_t lds = bytes(TC) > fold ? bytes(TC) : fold;
-  RAL_SET_LDS((k_dw<M, NC, MS, NS, LAYY, XF>), lds);
-  k_dw<M, NC, MS, NS, LAYY, XF><<<grid, 512, lds, s>>>(Y, X, pe, lnw, lnb, a2c0, dW, dB, nullptr, nullptr, N, TC, B, NV);
+  RAL_SET_LDS((k_dw<M, NC, MS, NS, LAYY, XF, H>), lds);
+  k_dw<M, NC, MS, NS, LAYY, XF, H><<<grid, 512, lds, s>>>(Y, X, pe, lnw, lnb, a2c0, dW, dB, H ? ymax : nullptr, H ? xscale : nullptr, N, TC, B, NV);
 }
 
 // slice widths: at most RAL_DW_SLICE rows/columns of the wide operand per workgroup
 template <int W> struct SliceOf { static constexpr int v = W > RAL_DW_SLICE ? ((W % RAL_DW_SLICE == 0) ? RAL_DW_SLICE : W / 2) : W; };
 
-// gmax (or nullptr): bits of the largest |dx2|, |du|, |dx1|, |dqkv| of this launch's windows (published by the split
-// data-gradient kernels): the four products then run on split operands (k_dw<..., true>)
-template <int C>
-static void launch_block_dw_c(const float* dx2, const float* upre, const float* a2c0, const float* dupre, const float* x1,
-                              const float* dx1, const float* o_hm, const float* dqkv, const float* x, const float* pe,
-                              const BlockP& w, const BlockP& gr, int N, int B, int ks, bool skip_mlp, const unsigned* gmax, hipStream_t s) {
-  const unsigned* gm = C >= 32 ? gmax : nullptr;
-  if (!skip_mlp) {
-  launch_dw_t<C, 4 * C, C, SliceOf<4 * C>::v, LAY_TOK, XF_A2>(dx2, upre, nullptr, nullptr, nullptr, a2c0, gr.w2, gr.b2, N, B, ks, s, gm ? gm + 0 : nullptr, w.asc ? w.asc + ASC_HID : nullptr);
-  launch_dw_t<4 * C, C, SliceOf<4 * C>::v, C, LAY_TOK, XF_LN>(dupre, x1, nullptr, w.ln2w, w.ln2b, nullptr, gr.w1, gr.b1, N, B, ks, s, gm ? gm + 1 : nullptr, w.asc ? w.asc + ASC_LN2 : nullptr);
-  }
-  launch_dw_t<C, C, SliceOf<C>::v, C, LAY_TOK, XF_HM>(dx1, o_hm, nullptr, nullptr, nullptr, nullptr, gr.wp, gr.bp, N, B, ks, s, gm ? gm + 2 : nullptr, w.asc ? w.asc + ASC_O : nullptr);
-  launch_dw_t<3 * C, C, SliceOf<3 * C>::v, C, LAY_HM, XF_LNPE>(dqkv, x, pe, w.ln1w, w.ln1b, nullptr, gr.wqkv, gr.bqkv, N, B, ks, s, gm ? gm + 3 : nullptr, w.asc ? w.asc + ASC_LN1 : nullptr);
+// The four products of a block at width C: fc2, fc1, proj, qkv (DW_FC2 .. DW_QKV) as <M, NC, MS, NS, LAYY, XF>
+#define DW_FC2_T(C) C, 4 * C, C, SliceOf<4 * C>::v, LAY_TOK, XF_A2
+#define DW_FC1_T(C) 4 * C, C, SliceOf<4 * C>::v, C, LAY_TOK, XF_LN
+#define DW_PROJ_T(C) C, C, SliceOf<C>::v, C, LAY_TOK, XF_HM
+#define DW_QKV_T(C) 3 * C, C, SliceOf<3 * C>::v, C, LAY_HM, XF_LNPE
+bool dw_chunk(int C, int prod, int N, bool split, int* tc, size_t* lds) {
+#define P(c) case c * 4 + DW_FC2: return dw_chunk_t<c, SliceOf<4 * c>::v, LAY_TOK, XF_A2>(N, split, tc, lds); \
+             case c * 4 + DW_FC1: return dw_chunk_t<SliceOf<4 * c>::v, c, LAY_TOK, XF_LN>(N, split, tc, lds); \
+             case c * 4 + DW_PROJ: return dw_chunk_t<SliceOf<c>::v, c, LAY_TOK, XF_HM>(N, split, tc, lds); \
+             case c * 4 + DW_QKV: return dw_chunk_t<SliceOf<3 * c>::v, c, LAY_HM, XF_LNPE>(N, split, tc, lds);
+  switch (C * 4 + prod) { P(8) P(16) P(32) P(64) P(128) }
+#undef P
+  return false;
 }
 
-void launch_block_dw(int C, const float* dx2, const float* upre, const float* a2c0, const float* dupre, const float* x1,
+// gmax: bits of the largest |dx2|, |du|, |dx1|, |dqkv| of this launch's windows (published by the split data-gradient
+// kernels, read by the split products only)
+void launch_block_dw(const BlockPlan& p, const float* dx2, const float* upre, const float* a2c0, const float* dupre, const float* x1,
                      const float* dx1, const float* o_hm, const float* dqkv, const float* x, const float* pe,
-                     const BlockP& w, const BlockP& gr, int N, int B, int ksplit, bool skip_mlp, const unsigned* gmax, hipStream_t s) {
-  switch (C) {
-#define CASE(c) case c: launch_block_dw_c<c>(dx2, upre, a2c0, dupre, x1, dx1, o_hm, dqkv, x, pe, w, gr, N, B, ksplit, skip_mlp, gmax, s); break;
-    CASE(8) CASE(16) CASE(32) CASE(64) CASE(128)
-#undef CASE
-  }
+                     const BlockP& w, const BlockP& gr, int N, int B, int ksplit, const unsigned* gmax, hipStream_t s) {
+  using K = BlockKernel;
+  const float* asc = w.asc;
+#define ARGS(i) N, B, ksplit, p.dw[i].chunks, p.dw[i].lds, s, gmax ? gmax + i : nullptr
+#define FC2(c, h, e) case K::e: launch_dw_t<DW_FC2_T(c), h>(dx2, upre, nullptr, nullptr, nullptr, a2c0, gr.w2, gr.b2, ARGS(DW_FC2), asc ? asc + ASC_HID : nullptr); break;
+#define FC1(c, h, e) case K::e: launch_dw_t<DW_FC1_T(c), h>(dupre, x1, nullptr, w.ln2w, w.ln2b, nullptr, gr.w1, gr.b1, ARGS(DW_FC1), asc ? asc + ASC_LN2 : nullptr); break;
+#define PROJ(c, h, e) case K::e: launch_dw_t<DW_PROJ_T(c), h>(dx1, o_hm, nullptr, nullptr, nullptr, nullptr, gr.wp, gr.bp, ARGS(DW_PROJ), asc ? asc + ASC_O : nullptr); break;
+#define QKV(c, h, e) case K::e: launch_dw_t<DW_QKV_T(c), h>(dqkv, x, pe, w.ln1w, w.ln1b, nullptr, gr.wqkv, gr.bqkv, ARGS(DW_QKV), asc ? asc + ASC_LN1 : nullptr); break;
+#define EVERY(F, tag) F(8, false, tag##_8) F(16, false, tag##_16) F(32, false, tag##_32) F(64, false, tag##_64) F(128, false, tag##_128) \
+                      F(32, true, tag##_32_H) F(64, true, tag##_64_H) F(128, true, tag##_128_H)
+  // (NONE, fc2 and fc1 only: the MLP backward produced them)
+  switch (p.dw[DW_FC2].kernel) { EVERY(FC2, DW_FC2) case K::NONE: break; default: block_launch_missing("launch_block_dw (fc2)", p.dw[DW_FC2]); }
+  switch (p.dw[DW_FC1].kernel) { EVERY(FC1, DW_FC1) case K::NONE: break; default: block_launch_missing("launch_block_dw (fc1)", p.dw[DW_FC1]); }
+  switch (p.dw[DW_PROJ].kernel) { EVERY(PROJ, DW_PROJ) default: block_launch_missing("launch_block_dw (proj)", p.dw[DW_PROJ]); }
+  switch (p.dw[DW_QKV].kernel) { EVERY(QKV, DW_QKV) default: block_launch_missing("launch_block_dw (qkv)", p.dw[DW_QKV]); }
+#undef ARGS
+#undef FC2
+#undef FC1
+#undef PROJ
+#undef QKV
+#undef EVERY
 }
 
 void launch_resample_dw(int D, bool sep, const float* dy, const float* x, const float* lnw, const float* lnb,
                         float* dW, int T, int Tv, int B, int ksplit, hipStream_t s) {
-#define CASE(d) case d: if (sep) launch_dw_t<d, d, d, d, LAY_TOK, XF_LN_SEP>(dy, x, nullptr, lnw, lnb, nullptr, dW, nullptr, T, B, ksplit, s, nullptr, nullptr, Tv); \
-                        else launch_dw_t<d, d, d, d, LAY_TOK, XF_LN>(dy, x, nullptr, lnw, lnb, nullptr, dW, nullptr, T, B, ksplit, s); break;
+  int tc; size_t lds;
+#define CASE(d) case d: dw_chunk_t<d, d, LAY_TOK, XF_LN>(T, false, &tc, &lds); /* (XF_LN_SEP: the same tiles) */ \
+    if (sep) launch_dw_t<d, d, d, d, LAY_TOK, XF_LN_SEP, false>(dy, x, nullptr, lnw, lnb, nullptr, dW, nullptr, T, B, ksplit, tc, lds, s, nullptr, nullptr, Tv); \
+    else launch_dw_t<d, d, d, d, LAY_TOK, XF_LN, false>(dy, x, nullptr, lnw, lnb, nullptr, dW, nullptr, T, B, ksplit, tc, lds, s); break;
   switch (D) { CASE(8) CASE(16) CASE(32) CASE(64) CASE(128) }
 #undef CASE
 }

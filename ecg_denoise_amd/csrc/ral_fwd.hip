@@ -1198,41 +1198,28 @@ __global__ void k_add(const float* __restrict__ a, const float* __restrict__ b, 
 static constexpr int GRID_FWD = 4096;   // workgroup cap of the persistent forward kernels
 static inline int grid_for(int items) { return items < GRID_FWD ? items : GRID_FWD; }
 
-// widths whose projection has a split-operand kernel (the caller passes the tiled weight planes to choose it)
-bool qkv_fwd_uses_f16(int C) { return C == 32 || C == 64 || C == 128; }
+// LDS of the QKV projection: the fp32-MFMA kernel holds a window; the split-operand kernels `bufs` buffers of 64-token groups
+// (1: k_qkv_fwd_h, 2: the weight-stationary k_qkv_fwd_ws)
+size_t qkv_fwd_lds(int C, int N) { return (size_t)N * ld_of(C) * sizeof(float); }
+size_t qkv_fwd_h_lds(int C, int bufs) { return (size_t)bufs * 2 * 64 * ldb_of(C) * 2; }
 
-void launch_qkv_fwd(int C, const float* x, const float* pe, const BlockP& w, const void* wt, float* qkv, int N, int B, hipStream_t s) {
-  if (wt && qkv_fwd_uses_f16(C) && N % 16 == 0) {
-    const _Float16* wtp = reinterpret_cast<const _Float16*>(wt);
-    auto go = [&](auto kern, int GT) {
-      const size_t ldsb = (size_t)2 * GT * ldb_of(C) * 2;
-      RAL_SET_LDS(kern, ldsb);
-      const long ngroups = ((long)B * N + GT - 1) / GT;
-      const int wgs = 512;
-      kern<<<(int)(ngroups < wgs ? ngroups : wgs), 256, ldsb, s>>>(x, pe, w, wtp, qkv, N, B);
-    };
-    // weight-stationary kernel: one workgroup per CU (C = 128) / two (C = 64), token groups of 64 = whole windows
-    auto gows = [&](auto kern, int C_, int per_cu) {
-      const size_t ldsb = (size_t)2 * 2 * 64 * ldb_of(C_) * 2;
-      RAL_SET_LDS(kern, ldsb);
-      const long ngroups = ((long)B * N + 63) / 64;
-      const int wgs = 256 * per_cu;
-      kern<<<(int)(ngroups < wgs ? ngroups : wgs), 6 * C_, ldsb, s>>>(x, pe, w, wtp, qkv, N, B);
-    };
-    if (64 % N == 0) {
-      if (C == 64) { gows(k_qkv_fwd_ws<64, 64>, 64, 2); return; }
-      if (C == 128) { gows(k_qkv_fwd_ws<128, 64>, 128, 1); return; }
-    }
-    if (C == 32 && (N % 64 == 0 || 64 % N == 0)) { go(k_qkv_fwd_h<32, 64>, 64); return; }
-    if (C == 64 && (N % 64 == 0 || 64 % N == 0)) { go(k_qkv_fwd_h<64, 64>, 64); return; }
-    if (C == 128 && (N % 64 == 0 || 64 % N == 0)) { go(k_qkv_fwd_h<128, 64>, 64); return; }
+void launch_qkv_fwd(const BlockLaunch& p, const float* x, const float* pe, const BlockP& w, const void* wt, float* qkv, int N, int B, hipStream_t s) {
+  using K = BlockKernel;
+  const _Float16* wtp = reinterpret_cast<const _Float16*>(wt);
+  const long ngroups = ((long)B * N + 63) / 64;   // of the split-operand kernels: token groups of 64
+  // k_qkv_fwd_h: at most 512 workgroups; the weight-stationary kernel: one workgroup per CU (C = 128) / two (C = 64)
+#define H(c) case K::QKV_FWD_H_##c: RAL_SET_LDS((k_qkv_fwd_h<c, 64>), p.lds); \
+    k_qkv_fwd_h<c, 64><<<(int)(ngroups < 512 ? ngroups : 512), p.threads, p.lds, s>>>(x, pe, w, wtp, qkv, N, B); break;
+#define WS(c, per_cu) case K::QKV_FWD_WS_##c: RAL_SET_LDS((k_qkv_fwd_ws<c, 64>), p.lds); \
+    k_qkv_fwd_ws<c, 64><<<(int)(ngroups < 256 * per_cu ? ngroups : 256 * per_cu), p.threads, p.lds, s>>>(x, pe, w, wtp, qkv, N, B); break;
+#define F(c) case K::QKV_FWD_##c: k_qkv_fwd<c><<<grid_for(B), p.threads, p.lds, s>>>(x, pe, w, qkv, N, B); break;
+  switch (p.kernel) {
+    WS(64, 2) WS(128, 1) H(32) H(64) F(8) F(16) F(32) F(64) F(128)
+    default: block_launch_missing("launch_qkv_fwd", p);
   }
-  const size_t lds = (size_t)N * ld_of(C) * sizeof(float);
-  switch (C) {
-#define CASE(c) case c: k_qkv_fwd<c><<<grid_for(B), 256, lds, s>>>(x, pe, w, qkv, N, B); break;
-    CASE(8) CASE(16) CASE(32) CASE(64) CASE(128)
-#undef CASE
-  }
+#undef H
+#undef WS
+#undef F
 }
 
 void launch_attn_fwd(const AttnPlan& p, const float* qkv, float* o_hm, float* lse, const float* table, int N, int H, int Len,
@@ -1263,65 +1250,33 @@ size_t mlp_fwd_lds(int C, int N, int nch) {
   return ((size_t)2 * N * ld_of(C) + (size_t)N * ld_of(4 * C / nch) + N + 2 + 2) * sizeof(float);
 }
 
-template <int C>
-static void launch_mlp_fwd_c(int nch, const float* x, const float* o, const BlockP& w, float* x1, float* upre,
-                             float* x2, int N, int B, hipStream_t s, int NE, const float* addend, float* sum_out) {
-  const size_t lds = mlp_fwd_lds(C, N, nch);
-  if (nch == 1) { RAL_SET_LDS((k_mlp_fwd<C, 1>), lds); k_mlp_fwd<C, 1><<<grid_for(B), 512, lds, s>>>(x, o, w, x1, upre, x2, N, B, NE, addend, sum_out); }
-  else if (nch == 2) { RAL_SET_LDS((k_mlp_fwd<C, 2>), lds); k_mlp_fwd<C, 2><<<grid_for(B), 512, lds, s>>>(x, o, w, x1, upre, x2, N, B, NE, addend, sum_out); }
-  else { RAL_SET_LDS((k_mlp_fwd<C, 4>), lds); k_mlp_fwd<C, 4><<<grid_for(B), 512, lds, s>>>(x, o, w, x1, upre, x2, N, B, NE, addend, sum_out); }
-}
-
 // wide levels on split fp16 operands
-bool mlp_fwd_uses_f16(int C, int N) { return (C == 32 || C == 64 || C == 128) && N % 32 == 0; }
 size_t mlp_fwd_h_lds(int C, int T, int nch) {   // T = tokens of a work item
   return (size_t)T * ld_of(C) * 4 + (size_t)2 * T * ldb_of(C) * 2 + (size_t)2 * T * ldb_of(4 * C / nch) * 2 + (T / 16 * 2 + T + 4) * 4;
 }
-// hidden chunks of the split-operand kernel: the fewest whose tiles fit the workgroup's LDS budget.  A work item is one window
-// (wpi = 1: items of 64 / 128 tokens measured slower, mlp_fwd 1.87 / 1.93 against 1.76 ms per step - one workgroup per CU).
-// (four-wave workgroups: three per CU.  The hardware admits one workgroup fewer than 160 KB / LDS suggests once the last one
-// would end within a granule of the top: 53 000 bytes run three per CU, 54 576 two - tools/diag/occ_probe.hip, census - while
-// hipOccupancyMaxActiveBlocksPerMultiprocessor still answers three.)
-static int mlp_fwd_h_nch(int C, int N, int nth /* threads of the workgroup that will run it */) {
-  const size_t budget = nth == 256 ? 53000 : 78000;
-  int nch = 1;
-  while (nch < (nth == 256 ? 8 : 4) && mlp_fwd_h_lds(C, N, nch) > budget) nch *= 2;
-  return nch;
-}
-template <int C, int NTH>
-static void launch_mlp_fwd_hc(const float* x, const float* o, const BlockP& w, const float* pbase, const void* wh,
-                              float* x1, float* upre, float* x2, int N, int B, hipStream_t s, const float* addend, float* sum_out) {
-  const int nch = mlp_fwd_h_nch(C, N, NTH), wpi = 1;
-  const size_t lds = mlp_fwd_h_lds(C, N, nch);
+
+void launch_mlp_fwd(const BlockLaunch& p, const float* x, const float* o, const BlockP& w, const float* pbase, const void* wh,
+                    float* x1, float* upre, float* x2, int N, int B, hipStream_t s, int NE, const float* addend, float* sum_out) {
+  using K = BlockKernel;
+  if (NE <= 0 || NE > N) NE = N;
   const _Float16* whp = reinterpret_cast<const _Float16*>(wh);
   const int grid = grid_for(B);
-  if (nch == 1) { RAL_SET_LDS((k_mlp_fwd_h<C, 1, NTH>), lds); k_mlp_fwd_h<C, 1, NTH><<<grid, NTH, lds, s>>>(x, o, w, pbase, whp, x1, upre, x2, N, B, wpi, addend, sum_out); }
-  else if (nch == 2) { RAL_SET_LDS((k_mlp_fwd_h<C, 2, NTH>), lds); k_mlp_fwd_h<C, 2, NTH><<<grid, NTH, lds, s>>>(x, o, w, pbase, whp, x1, upre, x2, N, B, wpi, addend, sum_out); }
-  else if (nch == 4 || NTH != 256) { RAL_SET_LDS((k_mlp_fwd_h<C, 4, NTH>), lds); k_mlp_fwd_h<C, 4, NTH><<<grid, NTH, lds, s>>>(x, o, w, pbase, whp, x1, upre, x2, N, B, wpi, addend, sum_out); }
-  else if constexpr (NTH == 256) { RAL_SET_LDS((k_mlp_fwd_h<C, 8, NTH>), lds); k_mlp_fwd_h<C, 8, NTH><<<grid, NTH, lds, s>>>(x, o, w, pbase, whp, x1, upre, x2, N, B, wpi, addend, sum_out); }
-}
-
-void launch_mlp_fwd(int C, int nch, const float* x, const float* o, const BlockP& w, const float* pbase, const void* wh,
-                    float* x1, float* upre, float* x2, int N, int B, int f16_narrow, hipStream_t s, int NE, const float* addend, float* sum_out) {
-  if (NE <= 0 || NE > N) NE = N;
-  const bool padded = NE < N;   // padded windows: the generic kernel (its local-enhancement conv knows where the window ends)
-  if (!padded && wh && mlp_fwd_uses_f16(C, N)) {
-    // threads of a k_mlp_fwd_h workgroup at C = 64, 128: 256 (four waves, four or eight hidden chunks, <= 53 000 bytes of LDS, three
-    // workgroups per CU, every K-chunk's weight fragments of a proj / fc1 unit requested together: 135-163 registers).  Measured
-    // 256 / 512 threads (512: two per CU at 128 registers): `mlp_fwd` 1.625 / 1.620 ms per step serialised, the step 12.67 / 12.69
-    // ms (three interleaved rounds, each in favour of 256), inference 562.3 k / 557.6 k windows/s.  C = 32 runs 512.
-    if (C == 32) launch_mlp_fwd_hc<32, 512>(x, o, w, pbase, wh, x1, upre, x2, N, B, s, addend, sum_out);
-    else if (C == 64) launch_mlp_fwd_hc<64, 256>(x, o, w, pbase, wh, x1, upre, x2, N, B, s, addend, sum_out);
-    else launch_mlp_fwd_hc<128, 256>(x, o, w, pbase, wh, x1, upre, x2, N, B, s, addend, sum_out);
-    return;
+  // (k_mlp_fwd_h: a work item is one window, wpi = 1: items of 64 / 128 tokens measured slower, mlp_fwd 1.87 / 1.93 against
+  // 1.76 ms per step - one workgroup per CU)
+#define H(c, n, t) case K::MLP_FWD_H_##c##_##n: RAL_SET_LDS((k_mlp_fwd_h<c, n, t>), p.lds); \
+    k_mlp_fwd_h<c, n, t><<<grid, t, p.lds, s>>>(x, o, w, pbase, whp, x1, upre, x2, N, B, 1, addend, sum_out); break;
+#define F(c, n) case K::MLP_FWD_##c##_##n: RAL_SET_LDS((k_mlp_fwd<c, n>), p.lds); \
+    k_mlp_fwd<c, n><<<grid, 512, p.lds, s>>>(x, o, w, x1, upre, x2, N, B, NE, addend, sum_out); break;
+#define F3(c) F(c, 1) F(c, 2) F(c, 4)
+  switch (p.kernel) {
+    H(32, 1, 512) H(32, 2, 512) H(32, 4, 512)
+    H(64, 1, 256) H(64, 8, 256) H(128, 4, 256) H(128, 8, 256)
+    F3(8) F3(16) F3(32) F3(64) F3(128)
+    default: launch_mlp_fwd_w(p, x, o, w, x1, x2, N, B, s);   // narrow levels: the strips of ral_mlpw.hip
   }
-  if (!padded && !sum_out)
-    if (const int kind = mlp_fwd_w_kind(C, N, upre != nullptr, f16_narrow != 0)) { launch_mlp_fwd_w(C, kind, x, o, w, x1, x2, N, B, s); return; }   // narrow levels: ral_mlpw.hip
-  switch (C) {
-#define CASE(c) case c: launch_mlp_fwd_c<c>(nch, x, o, w, x1, upre, x2, N, B, s, NE, addend, sum_out); break;
-    CASE(8) CASE(16) CASE(32) CASE(64) CASE(128)
-#undef CASE
-  }
+#undef H
+#undef F
+#undef F3
 }
 
 void launch_resample_fwd(int D, bool sep, const float* x, const float* wred, const float* lnw, const float* lnb,

@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include "ral_device.hpp"
 #include "ral_attn_plan.hpp"
+#include "ral_block_plan.hpp"
 #include "../../include/ralenet.h"   // ral_pool_row
 
 // gfx950 has 160 KB of LDS per CU; dynamic LDS above 64 KB must be opted into per kernel.
@@ -18,31 +19,29 @@
   } while (0)
 
 // ---- forward (ral_fwd.hip)
+// ---- the Linear layers of a transformer block: ral_block_plan.hpp chooses the kernel, the launchers execute the plan entry they
+// are given (each family's launch code sits with its kernel: ral_fwd.hip, ral_bwd.hip, ral_mlpw.hip (strips), ral_dw.hip).  The
+// LDS formulas below sit beside their kernels too; the plan calls them.
 // Linear layers of the wide levels on the f16 matrix cores (two fp16 pieces per operand, three products per term): the
 // weight matrices are re-written once per forward as tiled split planes (launch_tile_planes: desc = int4 {float offset, rows,
 // columns, first work item} per matrix, nwork = sum of rows * columns / 8; a matrix's planes sit at twice its float offset
-// in `wt`).  wt == nullptr selects the fp32-MFMA kernels.
-bool qkv_fwd_uses_f16(int C);
+// in `wt`).
 void launch_tile_planes(const float* params, void* wt, const void* desc, int ndesc, int nwork, int unscaled_residual, hipStream_t s);
 // the activation scales of the nblk transformer blocks (ASC_N floats each; desc: 12 ints per block - see k_act_scales)
 void launch_act_scales(const float* params, const void* desc, float* asc, int nblk, hipStream_t s);
-void launch_qkv_fwd(int C, const float* x, const float* pe, const BlockP& w, const void* wt /* of Wqkv */, float* qkv, int N, int B, hipStream_t s);
+size_t qkv_fwd_lds(int C, int N);
+size_t qkv_fwd_h_lds(int C, int bufs);
+void launch_qkv_fwd(const BlockLaunch& p, const float* x, const float* pe, const BlockP& w, const void* wt /* planes of Wqkv */, float* qkv, int N, int B, hipStream_t s);
 size_t mlp_fwd_lds(int C, int N, int nch);
-// pbase / wt: the parameter buffer and the tiled-plane buffer; the levels where mlp_fwd_uses_f16(C, N) run their Linear
-// layers on the planes (wt == nullptr: fp32 MFMA everywhere)
-bool mlp_fwd_uses_f16(int C, int N);
-// f16_narrow: the model allows fp16-pair products (f16_split > 0): the narrow levels may take their f16 strip kernel
-void launch_mlp_fwd(int C, int nch, const float* x, const float* o, const BlockP& w, const float* pbase, const void* wt,
-                    float* x1, float* upre, float* x2, int N, int B, int f16_narrow, hipStream_t s, int NE = 0 /* existing tokens; see launch_attn_fwd */,
+size_t mlp_fwd_h_lds(int C, int T, int nch);
+size_t mlp_fwd_w_lds(int C, bool f16);
+// pbase / wt: the parameter buffer and the tiled-plane buffer (read by the split-operand kernels only)
+void launch_mlp_fwd(const BlockLaunch& p, const float* x, const float* o, const BlockP& w, const float* pbase, const void* wt,
+                    float* x1, float* upre, float* x2, int N, int B, hipStream_t s, int NE = 0 /* existing tokens; see launch_attn_fwd */,
                     const float* addend = nullptr, float* sum_out = nullptr /* optional second output: block output + addend */);
-// narrow levels (C <= 32), wave-autonomous (ral_mlpw.hip): kind 0 = not taken, 1 = fp32-MFMA strips, 2 = f16 strips
-int mlp_fwd_w_kind(int C, int N, bool want_upre, bool f16_ok);
-bool mlp_fwd_w_takes(int C, int N, bool want_upre);
-void launch_mlp_fwd_w(int C, int kind, const float* x, const float* o, const BlockP& w, float* x1, float* x2, int N, int B, hipStream_t s);
-// narrow levels, backward as a strip kernel (ral_mlpw.hip; fc1 / fc2 weight gradients fused like k_mlp_bwd_s)
-// kind: 0 = not taken, 1 = fp32-MFMA strips, 2 = f16 strips (f16_ok: the model allows fp16-pair products)
-int mlp_bwd_w_kind(int C, int N, bool f16_ok);
-void launch_mlp_bwd_w(int C, int kind, const float* dx2, const float* x1, const BlockP& w, const BlockP& gr, float* dx1, float* do_hm, int N, int B,
+void launch_mlp_fwd_w(const BlockLaunch& p, const float* x, const float* o, const BlockP& w, float* x1, float* x2, int N, int B, hipStream_t s);
+size_t mlp_bwd_w_lds(int C, bool h16, int* threads);
+void launch_mlp_bwd_w(const BlockLaunch& p, const float* dx2, const float* x1, const BlockP& w, const BlockP& gr, float* dx1, float* do_hm, int N, int B,
                       bool want_dw, hipStream_t s);
 void launch_resample_fwd(int D, bool sep, const float* x, const float* wred, const float* lnw, const float* lnb,
                          const float* skip, float* y, int T, int Tv /* existing output tokens (<= T slots) */, int B, hipStream_t s);
@@ -160,16 +159,15 @@ void launch_transpose_mats(const float* src, float* dst, const void* desc, int n
 
 // ---- backward (ral_bwd.hip)
 size_t mlp_bwd_lds(int C, int N, int nch);
-bool mlp_bwd_is_fused(int C, int N);   // narrow levels: fused weight gradients, u_pre re-computed (not stored by the forward)
-// ptbase / wtt: the transposed-parameter buffer and the tiled split planes of its weight matrices (launch_tile_planes over
-// it); the (C, N) for which mlp_bwd_h_nch is non-zero run their data-gradient products on them (wtt == nullptr: fp32 MFMA)
-int mlp_bwd_h_nch(int C, int N);
-bool qkv_bwd_uses_f16(int C, int N);
-// gmax (4 unsigned, zeroed by the caller): the split kernels raise it to the bits of the largest |dx2|, |du|, |dx1| (mlp) and
-// |dqkv| (qkv) of the launch - the scales of the split weight-gradient products (launch_block_dw)
-bool launch_mlp_bwd(int C, int nch, const float* dx2, const float* x1, const float* upre, const BlockP& w,
+size_t mlp_bwd_s_lds(int C, int N);
+size_t mlp_bwd_s_flush_lds(int C);
+size_t mlp_bwd_h_lds(int C, int N, int nch, bool small);
+// ptbase / wtt: the transposed-parameter buffer and the tiled split planes of its weight matrices (launch_tile_planes over it)
+// gmax (4 unsigned, zeroed by the caller; nullptr unless the plan says dw_split): the split kernels raise it to the bits of the
+// largest |dx2|, |du|, |dx1| (mlp) and |dqkv| (qkv) of the launch - the scales of the split weight-gradient products
+void launch_mlp_bwd(const BlockLaunch& p, const float* dx2, const float* x1, const float* upre, const BlockP& w,
                     const BlockP& wt, const float* ptbase, const void* wtt, unsigned* gmax, const BlockP& gr, float* dupre, float* dx1, float* do_hm,
-                    float* a2c0, int N, int B, bool want_dw, hipStream_t s, int f16_narrow = 0, int NE = 0 /* existing tokens; see launch_attn_fwd */);
+                    float* a2c0, int N, int B, bool want_dw, hipStream_t s, int NE = 0 /* existing tokens; see launch_attn_fwd */);
 // ---- attention: ral_attn_plan.hpp chooses the kernel, these execute the plan (each family's launch code sits with its kernel:
 // ral_fwd.hip, ral_bwd.hip, ral_attn.hip (_w), ral_attnm.hip (_m, _mh))
 void launch_attn_fwd(const AttnPlan& p, const float* qkv, float* o_hm, float* lse, const float* table, int N, int H, int Len,
@@ -193,7 +191,8 @@ int launch_attn_bwd_mh(const AttnPlan& p, const float* qkv, const float* o_hm, c
 // grid of a persistent wave-per-head kernel (256 threads, four tasks per workgroup): whole resident rounds, at most max_rows
 int attn_wave_grid(const void* kernel, size_t lds, int ntask, int occ_cap, int max_rows);
 size_t qkv_bwd_lds(int C, int N);
-void launch_qkv_bwd(int C, const float* dqkv, const float* x, const float* pe, const float* dx1, const float* extra,
+size_t qkv_bwd_h_lds(int C, int N);
+void launch_qkv_bwd(const BlockLaunch& p, const float* dqkv, const float* x, const float* pe, const float* dx1, const float* extra,
                     const BlockP& w, const BlockP& wt, const float* ptbase, const void* wtt /* as launch_mlp_bwd */, unsigned* gmax,
                     const BlockP& gr, float* dx, int N, int B, hipStream_t s);
 void launch_resample_bwd(int D, bool sep, const float* dy, const float* x, const float* wred, const float* lnw,
@@ -207,9 +206,10 @@ void launch_conv1_bwd(int leads, const float* dy, const float* a0, const float* 
 void launch_conv1_bwd_dx(int leads, const float* dz, const float* w, float* dx, int L, int Lp, int B, hipStream_t s);
 
 // ---- weight gradients (ral_dw.hip)
-void launch_block_dw(int C, const float* dx2, const float* upre, const float* a2c0, const float* dupre, const float* x1,
+bool dw_chunk(int C, int prod /* DW_FC2 .. DW_QKV */, int N, bool split, int* tc, size_t* lds);   // token chunk and LDS of a product; false: no split chunk fits
+void launch_block_dw(const BlockPlan& p, const float* dx2, const float* upre, const float* a2c0, const float* dupre, const float* x1,
                      const float* dx1, const float* o_hm, const float* dqkv, const float* x, const float* pe,
-                     const BlockP& w, const BlockP& gr, int N, int B, int ksplit, bool skip_mlp, const unsigned* gmax /* 4 maxima of the split data-gradient kernels, or nullptr */, hipStream_t s);
+                     const BlockP& w, const BlockP& gr, int N, int B, int ksplit, const unsigned* gmax, hipStream_t s);
 void launch_resample_dw(int D, bool sep, const float* dy, const float* x, const float* lnw, const float* lnb,
                         float* dW, int T, int Tv, int B, int ksplit, hipStream_t s);
 

@@ -435,57 +435,54 @@ __global__ __launch_bounds__(256, RAL_MLPW_WPE) void k_mlp_fwd_wh(const float* _
 // at about half their issue bound (C = 16: 36 fp32 MFMAs + 32 GELU evaluations per lane and tile = ~2 400 cycles, measured
 // 4 200 / 4 900): what the narrow levels pay for is the fp32 MFMA itself, not the barriers.  Default: C = 16 only
 // (RAL_MLP_FWD_W=2: all three widths, 0: never).
-// which narrow-level forward: 0 = k_mlp_fwd (ral_fwd.hip), 1 = k_mlp_fwd_w (fp32 MFMA), 2 = k_mlp_fwd_wh (f16 matrix cores;
-// only when the model allows fp16-pair products, f16_split > 0).  RAL_MLP_FWD_W: 0 never a strip kernel, 1 fp32 strips
-// at C = 16 only, 2 fp32 strips at every width, 3 (default) f16 strips at every width where allowed, else fp32 strips at
-// C = 16.
+// Which narrow-level forward - k_mlp_fwd (ral_fwd.hip), k_mlp_fwd_w (fp32 MFMA) or k_mlp_fwd_wh (f16 matrix cores; only when
+// the model allows fp16-pair products, f16_split > 0) - is decided in ral_block_plan.hip (switch MLP_FWD_W).
 // Measured at batch 2048 (rocprofv3, serialised step, us per launch; k_mlp_fwd / fp32 strips / f16 strips), first with the
 // two-transcendental GELU: C = 16: 78.7 / 68.5 / 62.1; C = 8: 66.0 / 73.9 / 71.4; C = 32: 93.4 / 107 / 137 (two tiles of state
 // per strip spilled at 168 registers); then with the one-exponential forward GELU and one-tile strips at C = 32 (104
 // registers): C = 16: - / - / 51.3; C = 8: 64.1 / - / 62.1; C = 32: 86.5 / - / 71.2.  The f16 form removes the matrix share
 // (36 fp32 MFMAs = 1 500 of ~4 200 cycles per tile at C = 16 -> 27 f16 ones that overlap); what is left is the 32 GELU
 // evaluations per lane and tile.
-int mlp_fwd_w_kind(int C, int N, bool want_upre, bool f16_ok) {
-  static const int on = (int)ral_knob("MLP_FWD_W", 3);
-  if (!on || want_upre || N % 64 != 0 || !(C == 8 || C == 16 || C == 32)) return 0;   // (64: a whole number of strips at every width)
-  if (on >= 3 && f16_ok) return 2;
-  if (on == 2) return 1;
-  return C == 16 ? 1 : 0;
-}
-bool mlp_fwd_w_takes(int C, int N, bool want_upre) { return mlp_fwd_w_kind(C, N, want_upre, false) != 0; }
-
 template <int C>
-static void go_mlp_fwd_w(const float* x, const float* o, const BlockP& w, float* x1, float* x2, int N, int B, hipStream_t s) {
-  const size_t lds = (size_t)MlpwShape<C>::TOTAL * sizeof(float);
+static void go_mlp_fwd_w(const BlockLaunch& p, const float* x, const float* o, const BlockP& w, float* x1, float* x2, int N, int B, hipStream_t s) {
+  const size_t lds = p.lds;
   RAL_SET_LDS((k_mlp_fwd_w<C>), lds);
   static int occ = 0;
-  if (!occ && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_mlp_fwd_w<C>, 256, lds) != hipSuccess || occ < 1)) occ = 3;
+  if (!occ && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_mlp_fwd_w<C>, p.threads, lds) != hipSuccess || occ < 1)) occ = 3;
   const int nwg = (B * (N / (16 * MlpwShape<C>::S)) + 3) / 4;
   int grid = ral_num_cus() * (occ > 4 ? 4 : occ);
   if (grid > nwg) grid = nwg;
-  k_mlp_fwd_w<C><<<grid, 256, lds, s>>>(x, o, w, x1, x2, N, B);
+  k_mlp_fwd_w<C><<<grid, p.threads, lds, s>>>(x, o, w, x1, x2, N, B);
 }
 template <int C>
-static void go_mlp_fwd_wh(const float* x, const float* o, const BlockP& w, float* x1, float* x2, int N, int B, hipStream_t s) {
-  const size_t lds = MlpwhShape<C>::BYTES;
+static void go_mlp_fwd_wh(const BlockLaunch& p, const float* x, const float* o, const BlockP& w, float* x1, float* x2, int N, int B, hipStream_t s) {
+  const size_t lds = p.lds;
   RAL_SET_LDS((k_mlp_fwd_wh<C>), lds);
   static int occ = 0;
-  if (!occ && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_mlp_fwd_wh<C>, 256, lds) != hipSuccess || occ < 1)) occ = 3;
+  if (!occ && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_mlp_fwd_wh<C>, p.threads, lds) != hipSuccess || occ < 1)) occ = 3;
   const int nwg = (B * (N / (16 * MlpwhShape<C>::S)) + 3) / 4;
   int grid = ral_num_cus() * (occ > 4 ? 4 : occ);
   if (grid > nwg) grid = nwg;
-  k_mlp_fwd_wh<C><<<grid, 256, lds, s>>>(x, o, w, x1, x2, N, B);
+  k_mlp_fwd_wh<C><<<grid, p.threads, lds, s>>>(x, o, w, x1, x2, N, B);
 }
-void launch_mlp_fwd_w(int C, int kind, const float* x, const float* o, const BlockP& w, float* x1, float* x2, int N, int B, hipStream_t s) {
-  if (kind == 2) {
-    if (C == 8) go_mlp_fwd_wh<8>(x, o, w, x1, x2, N, B, s);
-    else if (C == 16) go_mlp_fwd_wh<16>(x, o, w, x1, x2, N, B, s);
-    else go_mlp_fwd_wh<32>(x, o, w, x1, x2, N, B, s);
-    return;
+size_t mlp_fwd_w_lds(int C, bool f16) {
+  switch (C) {
+    case 8: return f16 ? MlpwhShape<8>::BYTES : (size_t)MlpwShape<8>::TOTAL * sizeof(float);
+    case 16: return f16 ? MlpwhShape<16>::BYTES : (size_t)MlpwShape<16>::TOTAL * sizeof(float);
+    default: return f16 ? MlpwhShape<32>::BYTES : (size_t)MlpwShape<32>::TOTAL * sizeof(float);
   }
-  if (C == 8) go_mlp_fwd_w<8>(x, o, w, x1, x2, N, B, s);
-  else if (C == 16) go_mlp_fwd_w<16>(x, o, w, x1, x2, N, B, s);
-  else go_mlp_fwd_w<32>(x, o, w, x1, x2, N, B, s);
+}
+void launch_mlp_fwd_w(const BlockLaunch& p, const float* x, const float* o, const BlockP& w, float* x1, float* x2, int N, int B, hipStream_t s) {
+  using K = BlockKernel;
+  switch (p.kernel) {
+    case K::MLP_FWD_WH_8: go_mlp_fwd_wh<8>(p, x, o, w, x1, x2, N, B, s); break;
+    case K::MLP_FWD_WH_16: go_mlp_fwd_wh<16>(p, x, o, w, x1, x2, N, B, s); break;
+    case K::MLP_FWD_WH_32: go_mlp_fwd_wh<32>(p, x, o, w, x1, x2, N, B, s); break;
+    case K::MLP_FWD_W_8: go_mlp_fwd_w<8>(p, x, o, w, x1, x2, N, B, s); break;
+    case K::MLP_FWD_W_16: go_mlp_fwd_w<16>(p, x, o, w, x1, x2, N, B, s); break;
+    case K::MLP_FWD_W_32: go_mlp_fwd_w<32>(p, x, o, w, x1, x2, N, B, s); break;
+    default: block_launch_missing("launch_mlp_fwd", p);
+  }
 }
 
 // =================================================================================
@@ -1282,40 +1279,43 @@ __global__ __launch_bounds__(128 * RAL_MLPW2_NP, 2) void k_mlp_bwd_w2(const floa
 // k_mlp_bwd_w2 178 - 182 on the fp32 instruction, 167 with the channel products as fp16 pairs (default where the model allows).  Its tile loop is 1 571 instructions per wave and tile (~1 000 vector, 168 matrix, 75 transcendental)
 // and takes ~27 000 cycles per pair of tiles and SIMD: both pipes are under half busy, the waves wait on each other's chain
 // (fc1 MFMAs -> GELU -> fc1^T MFMAs -> LDS transposes -> weight-gradient MFMAs) with two waves per SIMD to hide it.
-// MLP_BWD_W: 0 never, 1: C = 16 only, 2: C = 8 and 16, 3 (default): C = 32 too (k_mlp_bwd_w2, two waves per tile).
-int mlp_bwd_w_kind(int C, int N, bool f16_ok) {
-  static const int on = (int)ral_knob("MLP_BWD_W", 3);
-  static const int h16 = (int)ral_knob("MLP_BWD_W_F16", 1);   // C = 32: the channel products as fp16 pairs where the model allows them
-  if (!on || N % 16 != 0 || !(C == 16 || (on >= 2 && C == 8) || (on >= 3 && C == 32))) return 0;
-  return (C == 32 && f16_ok && h16) ? 2 : 1;
-}
+// (Which shapes take them: ral_block_plan.hip, switches MLP_BWD_W and MLP_BWD_W_F16.)
 template <int C>
-static void go_mlp_bwd_w(const float* dx2, const float* x1, const BlockP& w, const BlockP& gr, float* dx1, float* do_hm, int N, int B,
+static void go_mlp_bwd_w(const BlockLaunch& p, const float* dx2, const float* x1, const BlockP& w, const BlockP& gr, float* dx1, float* do_hm, int N, int B,
                          bool want_dw, hipStream_t s) {
   const int nwg = (B * (N / 16) + 3) / 4;
-  const size_t lds = (size_t)MlpbwShape<C>::TOTAL * sizeof(float);
+  const size_t lds = p.lds;
   RAL_SET_LDS((k_mlp_bwd_w<C>), lds);
   static int occ = 0;
-  if (!occ && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_mlp_bwd_w<C>, 256, lds) != hipSuccess || occ < 1)) occ = 3;
+  if (!occ && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_mlp_bwd_w<C>, p.threads, lds) != hipSuccess || occ < 1)) occ = 3;
   int grid = ral_num_cus() * (occ > 3 ? 3 : occ);
   if (grid > nwg) grid = nwg;
-  k_mlp_bwd_w<C><<<grid, 256, lds, s>>>(dx2, x1, w, gr, dx1, do_hm, N, B, want_dw ? 1 : 0);
+  k_mlp_bwd_w<C><<<grid, p.threads, lds, s>>>(dx2, x1, w, gr, dx1, do_hm, N, B, want_dw ? 1 : 0);
 }
 template <bool H16>
-static void go_mlp_bwd_w2(const float* dx2, const float* x1, const BlockP& w, const BlockP& gr, float* dx1, float* do_hm, int N, int B,
+static void go_mlp_bwd_w2(const BlockLaunch& p, const float* dx2, const float* x1, const BlockP& w, const BlockP& gr, float* dx1, float* do_hm, int N, int B,
                           bool want_dw, hipStream_t s) {
   using SH = Mlpbw2Shape<32>;
   const int nwg = (B * (N / 16) + SH::NP - 1) / SH::NP;
-  const size_t lds = (size_t)(H16 ? Mlpbw2hShape<32>::TOTAL : SH::TOTAL) * sizeof(float);
+  const size_t lds = p.lds;
   RAL_SET_LDS((k_mlp_bwd_w2<32, H16>), lds);
   int grid = ral_num_cus() * (4 / SH::NP);      // (eight waves per CU: 232 registers)
   if (grid > nwg) grid = nwg;
-  k_mlp_bwd_w2<32, H16><<<grid, 128 * SH::NP, lds, s>>>(dx2, x1, w, gr, dx1, do_hm, N, B, want_dw ? 1 : 0);
+  k_mlp_bwd_w2<32, H16><<<grid, p.threads, lds, s>>>(dx2, x1, w, gr, dx1, do_hm, N, B, want_dw ? 1 : 0);
 }
-void launch_mlp_bwd_w(int C, int kind, const float* dx2, const float* x1, const BlockP& w, const BlockP& gr, float* dx1, float* do_hm, int N, int B,
+size_t mlp_bwd_w_lds(int C, bool h16, int* threads) {
+  *threads = C == 32 ? 128 * Mlpbw2Shape<32>::NP : 256;
+  if (C == 32) return (size_t)(h16 ? Mlpbw2hShape<32>::TOTAL : Mlpbw2Shape<32>::TOTAL) * sizeof(float);
+  return (size_t)(C == 8 ? MlpbwShape<8>::TOTAL : MlpbwShape<16>::TOTAL) * sizeof(float);
+}
+void launch_mlp_bwd_w(const BlockLaunch& p, const float* dx2, const float* x1, const BlockP& w, const BlockP& gr, float* dx1, float* do_hm, int N, int B,
                       bool want_dw, hipStream_t s) {
-  if (C == 32 && kind == 2) go_mlp_bwd_w2<true>(dx2, x1, w, gr, dx1, do_hm, N, B, want_dw, s);
-  else if (C == 32) go_mlp_bwd_w2<false>(dx2, x1, w, gr, dx1, do_hm, N, B, want_dw, s);
-  else if (C == 8) go_mlp_bwd_w<8>(dx2, x1, w, gr, dx1, do_hm, N, B, want_dw, s);
-  else go_mlp_bwd_w<16>(dx2, x1, w, gr, dx1, do_hm, N, B, want_dw, s);
+  using K = BlockKernel;
+  switch (p.kernel) {
+    case K::MLP_BWD_W2_32_H: go_mlp_bwd_w2<true>(p, dx2, x1, w, gr, dx1, do_hm, N, B, want_dw, s); break;
+    case K::MLP_BWD_W2_32: go_mlp_bwd_w2<false>(p, dx2, x1, w, gr, dx1, do_hm, N, B, want_dw, s); break;
+    case K::MLP_BWD_W_8: go_mlp_bwd_w<8>(p, dx2, x1, w, gr, dx1, do_hm, N, B, want_dw, s); break;
+    case K::MLP_BWD_W_16: go_mlp_bwd_w<16>(p, dx2, x1, w, gr, dx1, do_hm, N, B, want_dw, s); break;
+    default: block_launch_missing("launch_mlp_bwd", p);
+  }
 }

@@ -240,7 +240,6 @@ struct RalModel : ral_handle {
   void* tdesc = nullptr; int tn = 0, ttotal = 0;
   const float* last_x = nullptr;
   int last_B = 0;
-  int nch_f[5], nch_b[5];
   int dw_ksplit[5] = {256, 256, 256, 256, 256};
   // optional in-library kernel timing (bench.py roofline leg): hipEvent pairs around the
   // launches of ONE selected kernel kind, on the stream the kernels run on
@@ -308,9 +307,10 @@ static size_t plan_workspace(const ral_config& c, RalModel* m /* may be null: si
     a.o = tr ? take((p + "o").c_str(), E) : sh_o;
     a.lse = tr ? take((p + "lse").c_str(), E / 4) : nullptr;
     a.x1 = tr ? take((p + "x1").c_str(), E) : nullptr;
-    // u_pre is kept only where the backward reads it: the narrow levels re-compute it (k_mlp_bwd_s)
+    // u_pre is kept only where the backward reads it (the plan's stores_upre: a function of width, slots and mode alone)
     const int lvl = STAGES[b / 2].level;
-    a.upre = (tr && !mlp_bwd_is_fused(CH[lvl], Lp >> lvl)) ? take((p + "upre").c_str(), 4 * E) : nullptr;
+    const bool upre = block_plan(BlockShape{CH[lvl], Lp >> lvl, 0, tr, false, true, false, false}).stores_upre;
+    a.upre = upre ? take((p + "upre").c_str(), 4 * E) : nullptr;
     a.out = take((p + "out").c_str(), E);
   }
   { ParamLayout L_; ralenet_layout(c, L_); M.wh = reinterpret_cast<unsigned short*>(take("wh", (size_t)L_.nparam)); }
@@ -342,9 +342,6 @@ static size_t plan_workspace(const ral_config& c, RalModel* m /* may be null: si
   return cur;
 }
 
-// LDS budget of an MLP workgroup (bytes; fewer bytes = more hidden chunks but more co-resident workgroups per CU)
-static constexpr size_t MLP_LDS = 78000;
-
 // The attention backward of every level must find its scratch in the workspace for any lane batch: a plan's need is at most
 // B times its need at B = 1 (linear, or min(ceil(B c), ATTN_ROWS_MAX) rows), so one window's share has to cover B = 1.
 static int check_attn_scratch(const RalModel* m) {
@@ -362,20 +359,19 @@ static int check_attn_scratch(const RalModel* m) {
   return 0;
 }
 
-static void choose_tiling(RalModel* m) {
+static void choose_ksplit(RalModel* m) {
   // split-K workgroups of a fully sliced weight-gradient product per channel width {8,16,32,64,128} (products with
   // fewer slices get more, up to RAL_DW_MINWG workgroups per launch - see ral_dw.hip for why that is 192)
   static const int KS_DEFAULT[5] = {128, 128, 128, 64, 32};
   for (int l = 0; l < 5; ++l) m->dw_ksplit[l] = KS_DEFAULT[l];
-  for (int l = 0; l < 5; ++l) {
-    const int C = CH[l], N = m->Lp >> l;
-    int n = 1;
-    while (n < 4 && mlp_fwd_lds(C, N, n) > MLP_LDS) n *= 2;
-    m->nch_f[l] = n;
-    n = 1;
-    while (n < 4 && mlp_bwd_lds(C, N, n) > MLP_LDS) n *= 2;
-    m->nch_b[l] = n;
-  }
+}
+
+// the Linear-layer dispatch of a block at level l under the handle's options (ral_block_plan.hpp; computed per call: a few
+// dozen integer operations)
+static BlockPlan level_plan(const RalModel* m, int l, bool training, bool second_out) {
+  const int C = CH[l];
+  const bool f16 = m->f16_split > 0;
+  return block_plan(BlockShape{C, m->Lp >> l, m->L >> l, training, second_out, m->want_dw, f16 && C >= m->f16_split, f16 && m->narrow_f16});
 }
 
 static BlockP block_ptrs(const BlockOff& o, float* base) {
@@ -428,19 +424,19 @@ static void run_block_fwd(RalModel* m, int bi, const float* in, bool training, c
   }
   const int w0 = ln.w0, B = ln.B;
   hipStream_t s = ln.s;
-  const bool split = m->f16_split > 0 && C >= m->f16_split;
+  const BlockPlan plan = level_plan(m, l, training, sum_out != nullptr);
   const float* x = woff(in, w0, E1);
   float* qkv = woff(a.qkv, w0, 3 * E1);
   float* o = woff(a.o, w0, E1);
-  { ProfScope p(m, K_QKV_FWD, s); launch_qkv_fwd(C, x, m->pe[l], w, split ? m->wh + 2 * m->off.blk[bi].wqkv : nullptr, qkv, N, B, s); }
+  { ProfScope p(m, K_QKV_FWD, s); launch_qkv_fwd(plan.qkv_fwd, x, m->pe[l], w, m->wh + 2 * m->off.blk[bi].wqkv, qkv, N, B, s); }
   const int NE = m->L >> l;   // existing tokens of the N slots (NE < N: a window length that is not a multiple of 256)
   { ProfScope p(m, K_ATTN_FWD, s);
     launch_attn_fwd(attn_fwd_plan(N, H, Len, (m->f16_split > 0 && m->attn_f16) ? 1 : 0, NE), qkv, o,
                     training ? woff(a.lse, w0, E1 / 4) : nullptr, table, N, H, Len, B, s, NE); }
   { ProfScope p(m, K_MLP_FWD, s);
-    launch_mlp_fwd(C, m->nch_f[l], x, o, w, m->params, split ? m->wh : nullptr, training ? woff(a.x1, w0, E1) : nullptr,
-                   (training && !mlp_bwd_is_fused(C, N)) ? woff(a.upre, w0, 4 * E1) : nullptr,
-                   woff(a.out, w0, E1), N, B, (m->f16_split > 0 && m->narrow_f16) ? 1 : 0, s, NE, woff(addend, w0, E1), woff(sum_out, w0, E1)); }
+    launch_mlp_fwd(plan.mlp_fwd, x, o, w, m->params, m->wh, training ? woff(a.x1, w0, E1) : nullptr,
+                   plan.stores_upre ? woff(a.upre, w0, 4 * E1) : nullptr,
+                   woff(a.out, w0, E1), N, B, s, NE, woff(addend, w0, E1), woff(sum_out, w0, E1)); }
 }
 
 static const float* run_stage_fwd(RalModel* m, int si, const float* in, bool training, const Lane& ln) {
@@ -610,14 +606,12 @@ static int run_block_bwd(RalModel* m, int bi, const float* dy, const float* extr
         *dqkv = woff(m->dqkv[k], w0, 3 * E1), *a2c0 = woff(m->a2c0[k], w0, m->Lp);   // (per-window stride L at every level: the lanes run different levels concurrently)
   const float *x1 = woff(a.x1, w0, E1), *upre = woff(a.upre, w0, 4 * E1), *qkv = woff(a.qkv, w0, 3 * E1),
               *o = woff(a.o, w0, E1), *lse = woff(a.lse, w0, E1 / 4), *xin = woff(a.in, w0, E1);
-  bool fused_mlp_dw;
-  const bool splitb = m->f16_split > 0 && C >= m->f16_split;
-  // maxima of this block's gradient tensors (this lane's windows), for the split weight-gradient products: only when both
-  // split data-gradient kernels take the shape (they publish them)
-  unsigned* gmax = (splitb && m->want_dw && !mlp_bwd_is_fused(C, N) && mlp_bwd_h_nch(C, N) && qkv_bwd_uses_f16(C, N)) ? m->gmax + ((size_t)bi * 4 + (&ln - lanes_of(m)->l)) * 4 : nullptr;
+  const BlockPlan plan = level_plan(m, l, true, false);
+  // maxima of this block's gradient tensors (this lane's windows), for the split weight-gradient products
+  unsigned* gmax = plan.dw_split ? m->gmax + ((size_t)bi * 4 + (&ln - lanes_of(m)->l)) * 4 : nullptr;
   const int NE = m->L >> l;
-  { ProfScope p(m, K_MLP_BWD, s); fused_mlp_dw = launch_mlp_bwd(C, m->nch_b[l], dyw, x1, upre, w, wt, m->paramsT, splitb ? m->whT : nullptr, gmax, g, dupre, dx1, dohm, a2c0, N, B, m->want_dw, s,
-                                                                  (m->f16_split > 0 && m->narrow_f16) ? 1 : 0, NE); }
+  { ProfScope p(m, K_MLP_BWD, s);
+    launch_mlp_bwd(plan.mlp_bwd, dyw, x1, upre, w, wt, m->paramsT, m->whT, gmax, g, dupre, dx1, dohm, a2c0, N, B, m->want_dw, s, NE); }
   // the R-wave table gradient leaves the one-sweep attention kernels as one row of partials per workgroup; the kernel that adds
   // the rows up runs with the block's weight-gradient kernels (side stream), not on the chain: nothing on the chain reads it
   AttnTabReduce tabred{nullptr, nullptr, 0, 0};
@@ -629,7 +623,7 @@ static int run_block_bwd(RalModel* m, int bi, const float* dy, const float* extr
                                     gtable, dqkv, m->astat[k] + (size_t)w0 * per_window, (size_t)B * per_window, N, H, Len, B, s, NE,
                                     side && tab_side ? &tabred : nullptr); }
   { ProfScope p(m, K_QKV_BWD, s);
-    launch_qkv_bwd(C, dqkv, xin, m->pe[l], dx1, woff(extra, w0, E1), w, wt, m->paramsT, splitb ? m->whT : nullptr, gmax, g, woff(dx, w0, E1), N, B, s); }
+    launch_qkv_bwd(plan.qkv_bwd, dqkv, xin, m->pe[l], dx1, woff(extra, w0, E1), w, wt, m->paramsT, m->whT, gmax, g, woff(dx, w0, E1), N, B, s); }
   if (!m->want_dw) return short_scratch;
   if (side) {
     EV(hipEventRecord(ln.ev_ready[k], s));
@@ -637,7 +631,7 @@ static int run_block_bwd(RalModel* m, int bi, const float* dy, const float* extr
   }
   if (tabred.ntab > 0) launch_attn_tpart_reduce(tabred, sd);
   { ProfScope p(m, K_DW, sd);
-    launch_block_dw(C, dyw, upre, w.le ? a2c0 : nullptr, dupre, x1, dx1, o, dqkv, xin, m->pe[l], w, g, N, B, m->dw_ksplit[l], fused_mlp_dw, gmax, sd); }
+    launch_block_dw(plan, dyw, upre, w.le ? a2c0 : nullptr, dupre, x1, dx1, o, dqkv, xin, m->pe[l], w, g, N, B, m->dw_ksplit[l], gmax, sd); }
   if (side) { EV(hipEventRecord(ln.ev_done[k], sd)); ln.dw_pending[k] = true; }
   return short_scratch;
 }
@@ -800,7 +794,7 @@ int RalModel::init() {
   hipError_t e = alloc_slab(m->slab_bytes);
   if (e != hipSuccess) return ral_fail("hipMalloc(%zu bytes) failed: %s", m->slab_bytes, hipGetErrorString(e));
   plan_workspace(cfg, m, m->slab);
-  choose_tiling(m);
+  choose_ksplit(m);
   {
     LaneSet* LS = new LaneSet();
     m->lanes = LS;
@@ -870,7 +864,7 @@ int RalModel::init() {
     auto add = [&](int64_t off, int rows, int cols) { d.push_back((int)off); d.push_back(rows); d.push_back(cols); d.push_back(run); run += rows * cols / 8; };
     for (int b = 0; b < 18; ++b) {
       const int C = CH[STAGES[b / 2].level];
-      if (!qkv_fwd_uses_f16(C)) continue;
+      if (!block_has_planes(C)) continue;
       const BlockOff& o = m->off.blk[b];
       add(o.wqkv, 3 * C, C); add(o.wp, C, C); add(o.w1, 4 * C, C); add(o.w2, C, 4 * C);
     }
@@ -881,7 +875,7 @@ int RalModel::init() {
       auto addT = [&](int64_t off, int rows, int cols) { dt.push_back((int)off); dt.push_back(rows); dt.push_back(cols); dt.push_back(runT); runT += rows * cols / 8; };
       for (int b = 0; b < 18; ++b) {
         const int C = CH[STAGES[b / 2].level];
-        if (!qkv_fwd_uses_f16(C)) continue;
+        if (!block_has_planes(C)) continue;
         const BlockOff& o = m->off.blk[b];
         addT(o.wqkv, C, 3 * C); addT(o.wp, C, C); addT(o.w1, C, 4 * C); addT(o.w2, 4 * C, C);
       }
