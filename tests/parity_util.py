@@ -81,12 +81,19 @@ def compare_grads(ng, p, grads):
     return gerr
 
 
-def run_parity(variant, leads, L, B, device="cuda:0", trace=True, seed=1234):
-    """-> dict of relative errors (HIP fp32 vs fp64 oracle)."""
-    from ecg_denoise_amd import RALENet
+def run_parity(variant, leads, L, B, device="cuda:0", trace=True, seed=1234, options=None, eval_forward=False, before_forward=None):
+    """-> dict of relative errors (HIP fp32 vs fp64 oracle).  `options`: {name: value} for ral_set_option on the model's handle,
+    applied before the first forward.  `eval_forward`: after the train step, the eval-mode forward of the same model against
+    the oracle's eval output (its BatchNorm on the running statistics the step left) as res["y_eval"].  `before_forward(model)`
+    is called once the options are set."""
+    from ecg_denoise_amd import RALENet, _lib
     p32, x, tgt = make_case(variant, leads, L, B, seed)
     model = RALENet(variant, leads=leads, L=L, max_batch=B, train=True, device=device)
     model.load_state_dict(p32, strict=False)
+    for key, value in (options or {}).items():
+        _lib.check(_lib.lib().ral_set_option(model.eng.h, key.encode(), int(value)))
+    if before_forward is not None:
+        before_forward(model)
     xd, td = x.to(device), tgt.to(device)
     model.train()
     y = model(xd)
@@ -111,6 +118,14 @@ def run_parity(variant, leads, L, B, device="cuda:0", trace=True, seed=1234):
         for k, v in tr.items():
             res["act:" + k] = rel(model.debug_tensor(k).cpu().numpy()[:v.numel()], v.detach().numpy())
     res.update(compare_grads(model.named_grads(), p, grads))
+    if eval_forward:
+        model.eval()
+        ye = model(xd)
+        torch.cuda.synchronize()
+        with torch.no_grad():
+            yeo = O.ralenet_forward(OrderedDict((k, v.detach()) for k, v in p.items()), x.double(), variant, training=False, bn=bn)
+        res["y_eval"] = rel(ye.cpu().numpy(), yeo.numpy())
+        model.train()
     return res, model, (p32, x, tgt)
 
 

@@ -3,10 +3,10 @@ kernel runs the QKV projection, the MLP half block, their backwards and the four
 these tests pin it to the first-match tables of DESIGN.md section 3, "Linear-layer dispatch": for the five levels of
 L = 256, 512, 1024 and of the padded lengths L = 128, 320, in training and eval, with and without a second output, under
 f16_split in {0, 32, 64, 128} x narrow_f16 in {0, 1}, under the default switches and under each option string of
-tests/test_gpu_configs.py::test_narrow_level_mlp_forward_kernel_choices (a process per string: the switches latch at their
-first read).  The expected names below are written out from the tables, level by level, not computed.  Names are
-template-ids as a kernel trace prints them, default template arguments included: k_mlp_bwd_h<C, NCH, NTH>,
-k_dw<M, NC, MS, NS, LAYY, XF, H>."""
+tests/test_gpu_configs.py::test_narrow_level_mlp_forward_kernel_choices and of the switch runs of
+tests/test_gpu_block_instances.py (a process per string: the switches latch at their first read).  The expected names below
+are written out from the tables, level by level, not computed.  Names are template-ids as a kernel trace prints them, default
+template arguments included: k_mlp_bwd_h<C, NCH, NTH>, k_dw<M, NC, MS, NS, LAYY, XF, H>."""
 import ctypes as C
 import itertools
 import json
@@ -22,10 +22,25 @@ from ecg_denoise_amd import _lib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def parametrize_args(fn):
+    """the argument list of a test function's parametrize mark"""
+    return list([m for m in fn.pytestmark if m.name == "parametrize"][0].args[1])
+
+
+def switch_part(opts):
+    """an option string without its f16_split item: the plan query takes f16_split as an argument, so "f16_split=32,fuse_dw=0"
+    reads the table of "fuse_dw=0" """
+    return ",".join(kv for kv in opts.split(",") if kv and not kv.startswith("f16_split="))
+
+
 def option_strings():
-    """the option strings of the GPU file's strip-kernel test, read from its parametrize mark"""
-    import test_gpu_configs as gpu_file   # (not at import: the child processes below import this module for its helpers)
-    return list([m for m in gpu_file.test_narrow_level_mlp_forward_kernel_choices.pytestmark if m.name == "parametrize"][0].args[1])
+    """the option strings of the GPU files' child processes, read from their parametrize marks: the strip-kernel test of
+    tests/test_gpu_configs.py and the switch runs of tests/test_gpu_block_instances.py"""
+    import test_gpu_block_instances as inst_file   # (not at import: the child processes below import this module for its helpers)
+    import test_gpu_configs as gpu_file
+    both = parametrize_args(gpu_file.test_narrow_level_mlp_forward_kernel_choices) \
+        + [switch_part(opts) for opts, _ in parametrize_args(inst_file.test_block_instances_under_latched_switches)]
+    return list(dict.fromkeys(both))
 
 
 LAUNCHES = ("qkv_fwd", "mlp_fwd", "mlp_bwd", "qkv_bwd", "dw_fc2", "dw_fc1", "dw_proj", "dw_qkv")
@@ -187,6 +202,21 @@ EXPECTED = {
                                              ("", MF % (32, 2))],
                                  "mlp_bwd": [("not padded and wide", MBH % (32, 4, 256)), ("", MB % (32, 2))], "fused": False, "split": True}),
 }
+# fuse_dw = 0: no level is fused.  C = 32 as under fuse_dw = 16; C = 8 and 16 take k_mlp_bwd<C, NCH> (one hidden chunk at the
+# levels of L = 256, four at those of L = 512; padded windows too), store u_pre in training and keep their strip forward for eval
+# mode, with four fp32 weight-gradient products.  fuse_dw = 8: the same at C = 16 and 32, C = 8 stays fused.
+EXPECTED["fuse_dw=8"] = _with(EXPECTED["fuse_dw=16"],
+                              _16_128={"mlp_fwd": [("not padded and not training and not second and narrow", MFWH % 16),
+                                                   ("not padded and not training and not second", MFW % 16), ("", MF % (16, 1))],
+                                       "mlp_bwd": [("", MB % (16, 1))], "fused": False},
+                              _16_256={"mlp_fwd": [("not padded and not training and not second and narrow", MFWH % 16),
+                                                   ("not padded and not training and not second", MFW % 16), ("", MF % (16, 4))],
+                                       "mlp_bwd": [("", MB % (16, 4))], "fused": False})
+EXPECTED["fuse_dw=0"] = _with(EXPECTED["fuse_dw=8"],
+                              _8_256={"mlp_fwd": [("not padded and not training and not second and narrow", MFWH % 8), ("", MF % (8, 1))],
+                                      "mlp_bwd": [("", MB % (8, 1))], "fused": False},
+                              _8_512={"mlp_fwd": [("not padded and not training and not second and narrow", MFWH % 8), ("", MF % (8, 2))],
+                                      "mlp_bwd": [("", MB % (8, 4))], "fused": False})
 
 
 def expected_point(tables, Cw, N, point):
@@ -217,6 +247,22 @@ def plan(launch, Cw, N, NE=0, training=1, second=0, want_dw=1, f16_split=64, nar
                           C.byref(ch), C.byref(sp), C.byref(su), C.byref(fu), C.byref(ds))
     assert rc == 0, L.ral_last_error()
     return name.value.decode(), th.value, lds.value, ch.value, sp.value, su.value, fu.value, ds.value
+
+
+def model_points(Lw, f16_split):
+    """(level, C, N, NE, second_out, f16_split) of the blocks of a model of window length Lw: levels are Lp >> l with Lp the next
+    multiple of 256; a padded length forces f16_split 0; block 9, at level 4, is the only one with a second output"""
+    Lp = -(-Lw // 256) * 256
+    for l in range(5):
+        for second in ((0, 1) if l == 4 else (0,)):
+            yield l, 8 << l, Lp >> l, (0 if Lw == Lp else Lw >> l), second, (f16_split if Lw == Lp else 0)
+
+
+def model_instances(Lw, training, f16_split, narrow, L=None):
+    """the kernel instances a model of window length Lw launches under this process's switches: the eight launches of a train
+    step, or the two forward launches in eval mode"""
+    return {plan(i, Cw, N, NE, training, second, 1, fs, narrow, L)[0] for _, Cw, N, NE, second, fs in model_points(Lw, f16_split)
+            for i in (range(8) if training else (0, 1))} - {""}
 
 
 _CHILD = r"""
@@ -287,7 +333,10 @@ def test_kernel_names_and_flags_of_the_model_levels(seen, opts):
 
 def test_every_kernel_instance_is_reached(seen):
     """Coverage closure: every enumerator of BlockKernel (csrc/ral_block_plan.hpp) is chosen at some point of the legal space
-    under some option string - an instance nothing reaches is dead code."""
+    under some option string - an instance nothing reaches is dead code.  (Chosen somewhere in the space is not yet launched by
+    a model, nor compared with the oracle: tests/test_block_coverage_cpu.py, the ledger, counts which instances a model can
+    launch and which GPU test compares each with the fp64 oracle; tests/test_gpu_block_instances.py holds the cases for the
+    instances the other parity tests do not reach.)"""
     hpp = open(os.path.join(ROOT, "ecg_denoise_amd", "csrc", "ral_block_plan.hpp")).read()
     every = dict(re.findall(r'^\s*X\((\w+), "([^"]+)"\)', hpp, flags=re.M))
     assert len(every) >= 100 and len(set(every.values())) == len(every)
