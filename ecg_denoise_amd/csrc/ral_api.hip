@@ -19,6 +19,7 @@
 #include "ral_kernels.hpp"
 #include "ral_ralenet.hpp"
 #include "ral_unet.hpp"
+#include "ral_unet_plan.hpp"
 
 static thread_local char g_err[512] = "";
 int ral_fail(const char* fmt, ...) {
@@ -891,6 +892,38 @@ int ral_block_plan(int launch, int C, int N, int NE, int training, int second_ou
   if (stores_upre) *stores_upre = p.stores_upre ? 1 : 0;
   if (mlp_dw_fused) *mlp_dw_fused = p.mlp_dw_fused ? 1 : 0;
   if (dw_split) *dw_split = p.dw_split ? 1 : 0;
+  return 0;
+}
+
+int ral_unet_stage_geom(int leads, int si, int32_t* row, int cap) {
+  if (leads != 1 && leads != 2) return ral_fail("leads must be 1 or 2 (got %d)", leads);
+  if (si < 0 || si > 10) return ral_fail("U-Net stage %d outside [0, 10]", si);
+  const UStageGeom& g = unet_stages(leads)[si];
+  const int v[19] = {g.cin, g.cout, g.ks, g.mode, g.stride, g.pad, g.type, g.post_lrelu, g.bn, g.a.z, g.a.act, g.a.accumulate,
+                     g.b.z, g.b.act, g.b.accumulate, g.r.z, g.r.act, g.r.accumulate, g.len_shift};
+  if (!row || cap < 19) return ral_fail("U-Net stage row: room for 19 values is needed (got %d)", row ? cap : 0);
+  for (int i = 0; i < 19; ++i) row[i] = v[i];
+  return 0;
+}
+
+int ral_unet_stage_plan(int backward, int leads, int L, int B, int training, int si, int unet_fused, char* kernel_name, int name_cap,
+                        int32_t* grid, int32_t* threads, int32_t* windows_per_pass, int64_t* lds_bytes, int32_t* fold, int32_t* fused_eval) {
+  ral_config c;
+  memset(&c, 0, sizeof(c));
+  c.leads = leads; c.L = L; c.max_batch = B; c.train = 1;
+  if (unet_kind()->check_cfg(&c)) return -1;
+  if (si < -1 || si > 10) return ral_fail("U-Net stage %d outside [0, 10]", si);
+  const UPassPlan pp = unet_pass_plan(leads, L, true, unet_fused < 0 ? unet_fused_default() : unet_fused != 0);
+  const bool eval_forward = !backward && !training;
+  const UStageLaunch l = si >= 0 ? unet_stage_plan(leads, L, B, training != 0, backward != 0, si)
+                                 : (eval_forward ? pp.fused : unet_pass_plan(leads, L, true, false).fused);
+  if (kernel_name && name_cap > 0) snprintf(kernel_name, (size_t)name_cap, "%s", l.name);
+  if (grid) *grid = l.grid;
+  if (threads) *threads = l.threads;
+  if (windows_per_pass) *windows_per_pass = l.windows_per_pass;
+  if (lds_bytes) *lds_bytes = (int64_t)l.lds;
+  if (fold) *fold = pp.fold ? 1 : 0;
+  if (fused_eval) *fused_eval = pp.fused_eval ? 1 : 0;
   return 0;
 }
 

@@ -7,17 +7,6 @@
 #include "ral_block_plan.hpp"
 #include "../../include/ralenet.h"   // ral_pool_row
 
-// gfx950 has 160 KB of LDS per CU; dynamic LDS above 64 KB must be opted into per kernel.
-#define RAL_SET_LDS(kernel, bytes)                                                                     \
-  do {                                                                                                 \
-    static size_t ral_cur_ = 0;                                                                        \
-    if ((size_t)(bytes) > ral_cur_) {                                                                  \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),                                 \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes));             \
-      ral_cur_ = (size_t)(bytes);                                                                      \
-    }                                                                                                  \
-  } while (0)
-
 // ---- forward (ral_fwd.hip)
 // ---- the Linear layers of a transformer block: ral_block_plan.hpp chooses the kernel, the launchers execute the plan entry they
 // are given (each family's launch code sits with its kernel: ral_fwd.hip, ral_bwd.hip, ral_mlpw.hip (strips), ral_dw.hip).  The

@@ -22,12 +22,10 @@
 #include <vector>
 
 #include "ral_device.hpp"
+#include "ral_unet_plan.hpp"   // the stage table, ACT_* / CONV / CONVT / TY_*, the workgroup sizes of the specialised kernels
 
-#define MAXC 32
-enum { ACT_NONE = 0, ACT_LRELU = 1 };
+#define MAXC UNET_MAXC
 enum { NORM_NONE = 0, NORM_BATCH = 1, NORM_RUNNING = 2 };
-enum { CONV = 0, CONVT = 1 };
-enum { TY_ZBN = 0 /* z -> BN -> [lrelu] */, TY_ABN = 1 /* lrelu(z) -> BN */, TY_PLAIN = 2 /* no BN */ };
 
 struct Src {            // one input operand of a stage: act(norm(z))
   const float* z;       // (B, C, L) pre-BN tensor
@@ -264,9 +262,6 @@ RAL_DEV void seg_atomic(T* addr, float v, int w) {
 #define UB_STAMP_INIT() do {} while (0)
 #endif
 // ---------------------------------------------------------------------------------
-#ifndef UNET_FWD_THREADS
-#define UNET_FWD_THREADS 512
-#endif
 template <int CIN, int COUT, int KS, int MODE>
 __global__ __launch_bounds__(UNET_FWD_THREADS) void k_unet_fwd_t(Stage st, int B, int WP) {
   // A workgroup takes WP CONSECUTIVE windows per pass (one pass per workgroup at the launch sizes used): their inputs are
@@ -877,7 +872,6 @@ __global__ __launch_bounds__(256) void k_unet_bwd(Stage st, int B) {
 // (st.part: workgroups x parameters), folded by k_unet_fold after the last stage - no global atomics except the 2 x C
 // BatchNorm-backward sums the NEXT stage needs.  (st.part == nullptr: atomics straight into the gradient buffer.)
 // ---------------------------------------------------------------------------------
-#define UNET_BWD_THREADS 512
 template <int CIN, int COUT, int KS, int MODE>
 __global__ __launch_bounds__(UNET_BWD_THREADS, 2) void k_unet_bwd_t(Stage st, int B, int WP) {
   extern __shared__ float4 smem4[];
@@ -1685,59 +1679,43 @@ __global__ __launch_bounds__(256, 2) void k_unet_infer(const float* __restrict__
   }
 }
 
-static size_t uinf_lds_floats(int L) {
-  const int N1 = L / 2, N2 = L / 4, N3 = L / 8, N4 = L / 16;
-  return (size_t)4 * (N1 + 8) + (size_t)N4 * 100 + (size_t)N2 * 8 + (size_t)N3 * 16 + (size_t)(N4 + 1) * 68 + (size_t)N4 * 36 * 2 +
-         (size_t)(N3 + 1) * 36 + 288 + (uinf::PTOT - uinf::PB);
-}
+static_assert(uinf::PTOT - uinf::PB == UINF_COEFF_FLOATS, "the plan's LDS bytes of k_unet_infer");
 
 // =================================================================================
-// host model
+// host model (the network's shape: unet_stages, ral_unet_plan.hip)
 // =================================================================================
 struct UOff {
   int64_t w[11], b[11];         // conv weights/biases: 0-3 enc, 4-6 bottleneck convs, 7-10 dec
   int64_t bnw[10], bnb[10], run[10];  // BN: 0-3 enc, 4-5 bottleneck, 6-9 dec
   int bnC[10];
-  int ch[5];
 };
 
 static void ubuild(const ral_config& c, ParamLayout& L, UOff& O) {
-  auto alloc = [&](int64_t n) { return L.alloc(n, 4); };
-  const int ch[5] = {c.leads, 4, 8, 16, 32};
-  memcpy(O.ch, ch, sizeof(ch));
-  auto bn = [&](int idx, const std::string& pre, int C) {
-    O.bnC[idx] = C;
-    O.bnw[idx] = alloc(C); O.bnb[idx] = alloc(C);
-    O.run[idx] = L.nstate; L.nstate += 2 * C;
-    L.add(pre + ".weight", RAL_PARAM, O.bnw[idx], {C});
-    L.add(pre + ".bias", RAL_PARAM, O.bnb[idx], {C});
-    L.add(pre + ".running_mean", RAL_STATE_F32, O.run[idx], {C});
-    L.add(pre + ".running_var", RAL_STATE_F32, O.run[idx] + C, {C});
+  // the parameter order and names of the reference's state_dict: EncList, DecList, bottleneck
+  static const struct { int si; const char* conv; const char* bn; } order[UNET_STAGES] = {
+      {0, "EncList.0.conv", "EncList.0.bn"}, {1, "EncList.1.conv", "EncList.1.bn"}, {2, "EncList.2.conv", "EncList.2.bn"},
+      {3, "EncList.3.conv", "EncList.3.bn"}, {7, "DecList.0.conv", "DecList.0.bn"}, {8, "DecList.1.conv", "DecList.1.bn"},
+      {9, "DecList.2.conv", "DecList.2.bn"}, {10, "DecList.3.conv", "DecList.3.bn"}, {4, "bottleneck.0", "bottleneck.2"},
+      {5, "bottleneck.3", "bottleneck.5"}, {6, "bottleneck.6", nullptr}};
+  const UStageGeom* const tab = unet_stages(c.leads);
+  for (const auto& e : order) {
+    const UStageGeom& g = tab[e.si];
+    const std::string conv = e.conv;
+    O.w[e.si] = L.alloc(g.cin * g.cout * g.ks, 4); O.b[e.si] = L.alloc(g.cout, 4);
+    if (g.mode == UMODE_CONVT) L.add(conv + ".weight", RAL_PARAM, O.w[e.si], {g.cin, g.cout, g.ks});
+    else L.add(conv + ".weight", RAL_PARAM, O.w[e.si], {g.cout, g.cin, g.ks});
+    L.add(conv + ".bias", RAL_PARAM, O.b[e.si], {g.cout});
+    if (g.bn < 0) continue;
+    const std::string pre = e.bn;
+    const int C = g.cout;
+    O.bnC[g.bn] = C;
+    O.bnw[g.bn] = L.alloc(C, 4); O.bnb[g.bn] = L.alloc(C, 4);
+    O.run[g.bn] = L.nstate; L.nstate += 2 * C;
+    L.add(pre + ".weight", RAL_PARAM, O.bnw[g.bn], {C});
+    L.add(pre + ".bias", RAL_PARAM, O.bnb[g.bn], {C});
+    L.add(pre + ".running_mean", RAL_STATE_F32, O.run[g.bn], {C});
+    L.add(pre + ".running_var", RAL_STATE_F32, O.run[g.bn] + C, {C});
     L.add(pre + ".num_batches_tracked", RAL_COUNTER_I64, 0, {});
-  };
-  for (int i = 0; i < 4; ++i) {
-    const std::string p = "EncList." + std::to_string(i);
-    O.w[i] = alloc(ch[i + 1] * ch[i] * 3); O.b[i] = alloc(ch[i + 1]);
-    L.add(p + ".conv.weight", RAL_PARAM, O.w[i], {ch[i + 1], ch[i], 3});
-    L.add(p + ".conv.bias", RAL_PARAM, O.b[i], {ch[i + 1]});
-    bn(i, p + ".bn", ch[i + 1]);
-  }
-  for (int i = 0; i < 4; ++i) {
-    const std::string p = "DecList." + std::to_string(i);
-    const int cin = ch[4 - i], cout = ch[3 - i];
-    O.w[7 + i] = alloc(cin * cout * 4); O.b[7 + i] = alloc(cout);
-    L.add(p + ".conv.weight", RAL_PARAM, O.w[7 + i], {cin, cout, 4});
-    L.add(p + ".conv.bias", RAL_PARAM, O.b[7 + i], {cout});
-    bn(6 + i, p + ".bn", cout);
-  }
-  const int ks[3] = {1, 3, 1};
-  const char* cn[3] = {"bottleneck.0", "bottleneck.3", "bottleneck.6"};
-  const char* bnn[2] = {"bottleneck.2", "bottleneck.5"};
-  for (int i = 0; i < 3; ++i) {
-    O.w[4 + i] = alloc(32 * 32 * ks[i]); O.b[4 + i] = alloc(32);
-    L.add(std::string(cn[i]) + ".weight", RAL_PARAM, O.w[4 + i], {32, 32, ks[i]});
-    L.add(std::string(cn[i]) + ".bias", RAL_PARAM, O.b[4 + i], {32});
-    if (i < 2) bn(4 + i, bnn[i], 32);
   }
 }
 
@@ -1746,9 +1724,9 @@ struct UNetModel : ral_handle {
   float* z[11];       // conv outputs: 0-3 enc, 4 a4, 5 a5, 6 r, 7-10 dec (z6..z9 in the text above)
   float* pack = nullptr;   // fused inference: re-packed weights + folded BatchNorm coefficients (uinf::PTOT floats)
   int infer_grid = 0;      // resident workgroups of the fused inference kernel (occupancy query, first call)
-  bool fused = true;       // eval forward as one kernel where it applies (ral_set_option "unet_fused"; RAL_UNET_FUSED=0)
+  bool fused = true;       // eval forward as one kernel where it applies (ral_set_option "unet_fused"; switch UNET_FUSED)
   float* G[11];       // gradients at the BatchNorm outputs (same indexing; G[6] = d r)
-  int C[11], Ln[11];  // channels / length of z[i]
+  int C[11], Ln[11];  // channels / length of z[i] (the stage table at this model's L)
   const float* last_x = nullptr;
   const float* last_dy = nullptr;   // gradient at the output BatchNorm = the caller's dy (read by the last stage's backward)
   const float* gsums_dy = nullptr;  // unet_forward_loss left the sums of THIS dy in the output layer's backward record ...
@@ -1758,10 +1736,10 @@ struct UNetModel : ral_handle {
   // layout) per workgroup, folded by k_unet_fold; `cols` = the flat offsets of all conv weights and biases
   float* part = nullptr; int64_t part_stride = 0; int part_rows_max = 0;
   int* cols = nullptr; int ncols = 0;
-  bool fold = false; int bwd_rows = 0;
-  // replicas of the BatchNorm records for the one-call forward / backward (see Stage::nrep): [fwd | bwd][10][UNET_MAXREP][64]
+  bool fold = false; int bwd_rows = 0;   // unet_pass_plan's fold; the grid of this backward pass's stage plans
+  // replicas of the BatchNorm records for the one-call forward / backward (see Stage::nrep): [fwd | bwd][10][UNET_MAXREP][64].
+  // How many of them a pass adds to is an argument of the stage functions (`nrep`; 1: straight into bn_sums)
   double* rep = nullptr;
-  int nrep_f = 1, nrep_b = 1;     // replicas the current forward / backward pass adds to (1: straight into bn_sums)
   bool rep_bwd_clean = false;     // the backward half of `rep` was zeroed by the forward pass's fill and not used since
   bool rep_all_clean = false;     // both halves were zeroed by the last backward pass's fold kernel and not used since
   int init() override;
@@ -1781,16 +1759,14 @@ static int unet_check_cfg(const ral_config* c) {
   return 0;
 }
 static void unet_layout(const ral_config& c, ParamLayout& L) { UOff o; ubuild(c, L, o); }
-#define UNET_PART_ROWS 1024   // most workgroups a backward stage is ever launched with
-static size_t unet_plan(const ral_config& c, UNetModel* m, char* base) {
-  const int ch[5] = {c.leads, 4, 8, 16, 32};
-  const int Cs[11] = {4, 8, 16, 32, 32, 32, 32, 16, 8, 4, ch[0]};
-  const int Ls[11] = {c.L / 2, c.L / 4, c.L / 8, c.L / 16, c.L / 16, c.L / 16, c.L / 16, c.L / 8, c.L / 4, c.L / 2, c.L};
+static size_t unet_workspace(const ral_config& c, UNetModel* m, char* base) {
+  const UStageGeom* const tab = unet_stages(c.leads);
   size_t cur = 0;
   for (int pass = 0; pass < (c.train ? 2 : 1); ++pass)
-    for (int i = 0; i < 11; ++i) {
-      const size_t bytes = ((size_t)c.max_batch * Cs[i] * Ls[i] * sizeof(float) + 255) & ~size_t(255);
-      if (m) { (pass ? m->G : m->z)[i] = base ? reinterpret_cast<float*>(base + cur) : nullptr; m->C[i] = Cs[i]; m->Ln[i] = Ls[i]; }
+    for (int i = 0; i < UNET_STAGES; ++i) {
+      const int Ci = tab[i].cout, Li = unet_len(tab, i, c.L);
+      const size_t bytes = ((size_t)c.max_batch * Ci * Li * sizeof(float) + 255) & ~size_t(255);
+      if (m) { (pass ? m->G : m->z)[i] = base ? reinterpret_cast<float*>(base + cur) : nullptr; m->C[i] = Ci; m->Ln[i] = Li; }
       cur += bytes;
     }
   if (m) m->pack = base ? reinterpret_cast<float*>(base + cur) : nullptr;
@@ -1798,7 +1774,7 @@ static size_t unet_plan(const ral_config& c, UNetModel* m, char* base) {
   if (c.train) {
     ParamLayout Y; unet_layout(c, Y);
     const int64_t stride = (Y.nparam + 63) & ~int64_t(63);
-    const int rows = c.max_batch < UNET_PART_ROWS ? c.max_batch : UNET_PART_ROWS;
+    const int rows = c.max_batch < UNET_PART_ROWS ? c.max_batch : UNET_PART_ROWS;   // (a backward stage's grid never exceeds it)
     if (m) { m->part = base ? reinterpret_cast<float*>(base + cur) : nullptr; m->part_stride = stride; m->part_rows_max = rows; }
     cur += ((size_t)rows * stride * sizeof(float) + 255) & ~size_t(255);
     if (m) m->cols = base ? reinterpret_cast<int*>(base + cur) : nullptr;
@@ -1812,22 +1788,17 @@ static size_t unet_plan(const ral_config& c, UNetModel* m, char* base) {
 int UNetModel::init() {
   UNetModel* const m = this;
   ubuild(cfg, lay, off);
-  const size_t bytes = unet_plan(cfg, nullptr, nullptr);
+  const size_t bytes = unet_workspace(cfg, nullptr, nullptr);
   if (alloc_slab(bytes) != hipSuccess) return ral_fail("hipMalloc(%zu) failed", bytes);
-  unet_plan(cfg, m, slab);
-  m->fused = (ral_knob("UNET_FUSED", 1) != 0);
+  unet_workspace(cfg, m, slab);
+  m->fused = unet_fused_default();
+  m->fold = unet_pass_plan(cfg.leads, cfg.L, cfg.train != 0, m->fused).fold;
   if (cfg.train) {
-    // the specialised backward kernels (all of them apply when every level's length is a multiple of 4) leave their
-    // weight-gradient partials in scratch rows; otherwise some stage runs the generic kernel and everything stays atomic
-    m->fold = cfg.L % 64 == 0;
     std::vector<int> cols;
-    const int ch[5] = {cfg.leads, 4, 8, 16, 32};
-    const int Cs[11] = {4, 8, 16, 32, 32, 32, 32, 16, 8, 4, ch[0]};
-    const int Ci[11] = {ch[0], 4, 8, 16, 32, 32, 32, 32, 16, 8, 4};
-    const int Ks[11] = {3, 3, 3, 3, 1, 3, 1, 4, 4, 4, 4};
-    for (int si = 0; si < 11; ++si) {
-      for (int i = 0; i < Cs[si] * Ci[si] * Ks[si]; ++i) cols.push_back((int)m->off.w[si] + i);
-      for (int i = 0; i < Cs[si]; ++i) cols.push_back((int)m->off.b[si] + i);
+    const UStageGeom* const tab = unet_stages(cfg.leads);
+    for (int si = 0; si < UNET_STAGES; ++si) {
+      for (int i = 0; i < tab[si].cout * tab[si].cin * tab[si].ks; ++i) cols.push_back((int)m->off.w[si] + i);
+      for (int i = 0; i < tab[si].cout; ++i) cols.push_back((int)m->off.b[si] + i);
     }
     m->ncols = (int)cols.size();
     if (hipMemcpy(m->cols, cols.data(), cols.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return ral_fail("hipMemcpy(cols) failed");
@@ -1839,32 +1810,35 @@ const RalKind* unet_kind() {
   static const RalKind k = {
       unet_check_cfg,
       unet_layout,
-      [](const ral_config& c) { return unet_plan(c, nullptr, nullptr); },
+      [](const ral_config& c) { return unet_workspace(c, nullptr, nullptr); },
       1280,
       []() -> ral_handle* { return new UNetModel(); },
       "U-Net / DANet have a BatchNorm per layer: use ral_forward (per-rank statistics)"};
   return &k;
 }
 
-// BatchNorm index feeding each z tensor (z index -> bn index), -1: none (z[6] = r)
-static const int BN_OF_Z[11] = {0, 1, 2, 3, 4, 5, -1, 6, 7, 8, 9};
+int unet_stage_bn(int si) { return (si >= 0 && si < UNET_STAGES) ? unet_stages(1)[si].bn : -1; }
 
-static double* unet_rep(UNetModel* m, int dir, int bi) { return m->rep + ((size_t)(dir * 10 + bi) * UNET_MAXREP) * 64; }
+// BatchNorm record bi of a pass that adds to nrep replicas: dir 0 the forward sums, 1 the backward sums.  nrep > 1: the
+// replicas in the workspace; 1: the record itself, halves [0, 64) / [64, 128) of the caller's 128 doubles
+static double* bn_record(UNetModel* m, int dir, int bi, int nrep) {
+  if (nrep > 1) return m->rep + ((size_t)(dir * 10 + bi) * UNET_MAXREP) * 64;
+  return m->bn_sums ? m->bn_sums + 128 * bi + 64 * dir : nullptr;
+}
 
-static Src make_src(UNetModel* m, int zi, int act, bool training, bool with_grad, int accumulate) {
+static Src make_src(UNetModel* m, int zi, int act, bool training, bool with_grad, int accumulate, int nrep) {
   Src s; memset(&s, 0, sizeof(s));
   s.z = m->z[zi];
-  const int bi = BN_OF_Z[zi];
+  const int bi = unet_stage_bn(zi);
   if (bi >= 0) {
     s.norm = training ? NORM_BATCH : NORM_RUNNING;
-    // forward statistics: the stages of a running one-call forward read the replicas their producers add to; everything
-    // after it (and every stage-by-stage caller) reads the folded record in bn_sums
-    const bool frep = !with_grad && m->nrep_f > 1;
-    s.sums = frep ? unet_rep(m, 0, bi) : (m->bn_sums ? m->bn_sums + 128 * bi : nullptr);
-    s.nrep = frep ? m->nrep_f : 1;
+    // forward statistics: the stages of a one-call forward read the replicas their producers add to; everything after it
+    // (its backward pass, and every stage-by-stage caller) reads the folded record in bn_sums
+    s.nrep = with_grad ? 1 : nrep;
+    s.sums = bn_record(m, 0, bi, s.nrep);
     s.gamma = m->params + m->off.bnw[bi]; s.beta = m->params + m->off.bnb[bi];
     s.running = m->state + m->off.run[bi];
-    if (with_grad) s.bsums = m->nrep_b > 1 ? unet_rep(m, 1, bi) : m->bn_sums + 128 * bi + 64;
+    if (with_grad) s.bsums = bn_record(m, 1, bi, nrep);
   } else {
     s.norm = NORM_NONE;
   }
@@ -1873,107 +1847,78 @@ static Src make_src(UNetModel* m, int zi, int act, bool training, bool with_grad
   return s;
 }
 
-static size_t fwd_lds(const Stage& s) {
-  return ((size_t)s.cin * s.lin + (size_t)s.cin * s.cout * s.ks + MAXC + 12 * MAXC + 2 * MAXC + 8) * sizeof(float);
-}
-static size_t bwd_lds(const Stage& s) {
-  return ((size_t)2 * s.cin * s.lin + (size_t)s.cout * s.lout + (size_t)s.cin * s.cout * s.ks + 16 * MAXC + 6 * MAXC + 7 * MAXC + 8) * sizeof(float);
-}
-
-// stage table: index 0-3 enc, 4-6 bottleneck, 7-10 dec
-static Stage make_stage(UNetModel* m, int si, const float* x, bool training, bool bwd, int B, double gwin) {
-  const ral_config& c = m->cfg;
+// the kernels' argument of stage si: the table row bound to this model's buffers.  gwin: windows behind every BatchNorm
+// statistic (B, or the global batch under data parallelism); nrep: replicas of the records this pass adds to
+static Stage make_stage(UNetModel* m, int si, const float* x, bool training, bool bwd, double gwin, int nrep) {
   const UOff& Y = m->off;
+  const UStageGeom* const tab = unet_stages(m->cfg.leads);
+  const UStageGeom& g = tab[si];
   Stage s; memset(&s, 0, sizeof(s));
-  const double cnt = gwin;   // windows behind every BatchNorm statistic: B, or the global batch under data parallelism
-  auto cnt_of = [&](int zi) { return cnt * m->Ln[zi]; };
   s.w = m->params + Y.w[si]; s.bias = m->params + Y.b[si];
-  s.out = m->z[si]; s.cout = m->C[si]; s.lout = m->Ln[si];
-  const int bo = BN_OF_Z[si];
+  s.out = m->z[si];
+  s.cin = g.cin; s.cout = g.cout; s.ks = g.ks; s.stride = g.stride; s.pad = g.pad;
+  s.mode = g.mode == UMODE_CONVT ? CONVT : CONV; s.type = g.type; s.post_lrelu = g.post_lrelu;
+  s.lin = unet_len(tab, g.a.z, m->cfg.L); s.lout = m->Ln[si];
   // (forward: the record this stage adds to, in nrep replicas; backward: the folded forward record of its output)
-  s.nrep = bwd ? m->nrep_b : m->nrep_f;
-  s.sums_out = (bo >= 0 && m->bn_sums) ? ((!bwd && m->nrep_f > 1) ? unet_rep(m, 0, bo) : m->bn_sums + 128 * bo) : nullptr;
-  s.count = cnt_of(si);
-  s.stride = 1; s.pad = 0; s.mode = CONV;
-  if (si <= 3) {                      // encoder: Conv1d(k3, s2, p1) -> BN -> LeakyReLU
-    s.ks = 3; s.stride = 2; s.pad = 1; s.type = TY_ZBN;
-    if (si == 0) { memset(&s.a, 0, sizeof(Src)); s.a.z = x; s.a.norm = NORM_NONE; s.a.act = ACT_NONE; s.cin = c.leads; s.lin = c.L; }
-    else { s.a = make_src(m, si - 1, ACT_LRELU, training, bwd, 1); s.cin = m->C[si - 1]; s.lin = m->Ln[si - 1]; s.count_a = cnt_of(si - 1); }
-  } else if (si == 4) {               // bottleneck.0: 1x1 conv -> LeakyReLU -> BN(2)
-    s.ks = 1; s.post_lrelu = 1; s.type = TY_ABN;
-    s.a = make_src(m, 3, ACT_LRELU, training, bwd, 1); s.cin = 32; s.lin = m->Ln[3]; s.count_a = cnt_of(3);
-  } else if (si == 5) {               // bottleneck.3: k3 conv -> LeakyReLU -> BN(5)
-    s.ks = 3; s.pad = 1; s.post_lrelu = 1; s.type = TY_ABN;
-    s.a = make_src(m, 4, ACT_NONE, training, bwd, 0); s.cin = 32; s.lin = m->Ln[4]; s.count_a = cnt_of(4);
-  } else if (si == 6) {               // bottleneck.6: 1x1 conv, + x (x = lrelu(BN3(z3)))
-    s.ks = 1; s.type = TY_PLAIN;
-    s.a = make_src(m, 5, ACT_NONE, training, bwd, 0); s.cin = 32; s.lin = m->Ln[5]; s.count_a = cnt_of(5);
-    s.r = make_src(m, 3, ACT_LRELU, training, bwd, 0); s.count_r = cnt_of(3);
-  } else {                            // decoder: ConvTranspose1d(k4, s2, p1) -> BN -> [LeakyReLU] (+ skip in the consumer)
-    s.ks = 4; s.mode = CONVT; s.type = TY_ZBN;
-    const int i = si - 7;
-    if (i == 0) { s.a = make_src(m, 6, ACT_NONE, training, bwd, 0); }
-    else {
-      s.a = make_src(m, si - 1, ACT_LRELU, training, bwd, 0);
-      s.b = make_src(m, 3 - i, ACT_LRELU, training, bwd, 0);   // feats[2 - (i-1)] = enc stage (3 - i)
-      s.count_b = cnt_of(3 - i);
-    }
-    s.cin = m->C[si - 1]; s.lin = m->Ln[si - 1]; s.count_a = cnt_of(si - 1);
-  }
+  s.nrep = nrep;
+  s.sums_out = g.bn >= 0 ? bn_record(m, 0, g.bn, bwd ? 1 : nrep) : nullptr;
+  s.count = gwin * m->Ln[si];
+  auto operand = [&](const UOperand& o, Src& src, double& count) {
+    if (o.z == UZ_NONE) return;                                                  // (src.z stays null)
+    if (o.z == UZ_X) { src.z = x; src.norm = NORM_NONE; src.act = ACT_NONE; return; }   // (no BatchNorm, no gradient)
+    src = make_src(m, o.z, o.act, training, bwd, o.accumulate, nrep);
+    count = gwin * m->Ln[o.z];
+  };
+  operand(g.a, s.a, s.count_a); operand(g.b, s.b, s.count_b); operand(g.r, s.r, s.count_r);
   if (bwd) {
-    s.Gout = m->G[si];
-    s.bsums_out = bo >= 0 ? (m->nrep_b > 1 ? unet_rep(m, 1, bo) : m->bn_sums + 128 * bo + 64) : nullptr;
-    s.gamma_out = bo >= 0 ? m->params + Y.bnw[bo] : nullptr;
+    s.Gout = si == 10 ? m->last_dy : m->G[si];   // the gradient at the output BatchNorm is the caller's dy itself
+    s.bsums_out = g.bn >= 0 ? bn_record(m, 1, g.bn, nrep) : nullptr;
+    s.gamma_out = g.bn >= 0 ? m->params + Y.bnw[g.bn] : nullptr;
     s.gw = m->grads + Y.w[si]; s.gb = m->grads + Y.b[si];
-    if (si == 10) s.Gout = m->last_dy;        // the gradient at the output BatchNorm is the caller's dy itself
     if (m->fold) { s.part = m->part; s.part_stride = m->part_stride; s.part_w = (int)Y.w[si]; s.part_b = (int)Y.b[si]; }
   }
   return s;
 }
 
-
-// residual operand r of the specialised kernel is always lrelu(BN(z)) (bottleneck.6 + x); main operand act is a runtime flag
-template <int CIN, int COUT, int KS, int MODE>
-static void launch_fwd_t(const Stage& st, int B, int grid, hipStream_t s) {
-  // windows per workgroup pass: all of a workgroup's windows at once (up to 4), so the grid is B / WP workgroups - fewer
-  // while the tiles of a pass would not leave room for two workgroups per CU (long windows: at L = 2048 the 32-channel
-  // stages take 64 KB at WP = 2 already); dynamic LDS above 64 KB is opted into per instantiation
-  auto lds_of = [&](int WP) {
-    return ((size_t)WP * CIN * (st.lin + 8) + (st.r.z ? (size_t)WP * COUT * st.lout : 0) + (size_t)COUT * (CIN * KS + 4) + MAXC +
-            12 * MAXC + 4 * MAXC + 8) * sizeof(float);   // (weights: rows padded by up to 4 floats; the column sums are doubles)
-  };
-  int WP = (B + grid - 1) / grid;
-  if (WP > 4) WP = 4;
-  if (WP < 1) WP = 1;
-  while (WP > 1 && lds_of(WP) > 80 * 1024) --WP;
-  const int nwg = (B + WP - 1) / WP;
-  const int g2 = nwg < grid ? nwg : grid;         // (the kernel loops over passes)
-  const size_t lds = lds_of(WP);
-  static size_t cur = 0;                          // (one per instantiation)
-  if (lds > cur) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_unet_fwd_t<CIN, COUT, KS, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); cur = lds; }
-  k_unet_fwd_t<CIN, COUT, KS, MODE><<<g2, UNET_FWD_THREADS, lds, s>>>(st, B, WP);
-}
-
-static bool launch_unet_fwd_fast(const Stage& st, int si, int leads, int B, int grid, hipStream_t s) {
-  if (st.lout % 4 || st.lin % 4) return false;
-  switch (si) {
-    case 0: if (leads == 1) launch_fwd_t<1, 4, 3, 0>(st, B, grid, s); else launch_fwd_t<2, 4, 3, 0>(st, B, grid, s); return true;
-    case 1: launch_fwd_t<4, 8, 3, 0>(st, B, grid, s); return true;
-    case 2: launch_fwd_t<8, 16, 3, 0>(st, B, grid, s); return true;
-    case 3: launch_fwd_t<16, 32, 3, 0>(st, B, grid, s); return true;
-    case 4: launch_fwd_t<32, 32, 1, 1>(st, B, grid, s); return true;
-    case 5: launch_fwd_t<32, 32, 3, 1>(st, B, grid, s); return true;
-    case 6: launch_fwd_t<32, 32, 1, 1>(st, B, grid, s); return true;
-    case 7: launch_fwd_t<32, 16, 4, 2>(st, B, grid, s); return true;
-    case 8: launch_fwd_t<16, 8, 4, 2>(st, B, grid, s); return true;
-    case 9: launch_fwd_t<8, 4, 4, 2>(st, B, grid, s); return true;
-    case 10: if (leads == 1) launch_fwd_t<4, 1, 4, 2>(st, B, grid, s); else launch_fwd_t<4, 2, 4, 2>(st, B, grid, s); return true;
+// ---- the launchers execute a stage plan (unet_stage_plan) and never choose
+using K = UKernel;
+static void launch_unet_fwd(const UStageLaunch& p, const Stage& st, int B, hipStream_t s) {
+  switch (p.kernel) {
+    case K::FWD: RAL_SET_LDS(k_unet_fwd, p.lds); k_unet_fwd<<<p.grid, p.threads, p.lds, s>>>(st, B); break;
+#define T(ci, co, k, md) case K::FWD_T_##ci##_##co##_##k##_##md: RAL_SET_LDS((k_unet_fwd_t<ci, co, k, md>), p.lds); \
+      k_unet_fwd_t<ci, co, k, md><<<p.grid, p.threads, p.lds, s>>>(st, B, p.windows_per_pass); break;
+    UNET_T_INSTANCES(T)
+#undef T
+    default: unet_launch_missing("launch_unet_fwd", p);
   }
-  return false;
+}
+static void launch_unet_bwd(const UStageLaunch& p, const Stage& st, int B, hipStream_t s) {
+  switch (p.kernel) {
+    case K::BWD: RAL_SET_LDS(k_unet_bwd, p.lds); k_unet_bwd<<<p.grid, p.threads, p.lds, s>>>(st, B); break;
+#define T(ci, co, k, md) case K::BWD_T_##ci##_##co##_##k##_##md: RAL_SET_LDS((k_unet_bwd_t<ci, co, k, md>), p.lds); \
+      k_unet_bwd_t<ci, co, k, md><<<p.grid, p.threads, p.lds, s>>>(st, B, p.windows_per_pass); break;
+    UNET_T_INSTANCES(T)
+#undef T
+    default: unet_launch_missing("launch_unet_bwd", p);
+  }
+}
+// the fused eval forward: a persistent grid of exactly the workgroups that are resident at once (a grid one LDS granule too
+// optimistic runs its surplus workgroups as a second round: measured 76 us instead of 45 us at batch 2048)
+template <int LEADS>
+static void launch_infer(UNetModel* m, const UStageLaunch& p, const float* x, float* y, int B, hipStream_t s) {
+  RAL_SET_LDS(k_unet_infer<LEADS>, p.lds);
+  if (m->infer_grid == 0) {
+    int per_cu = 0, dev = 0, ncu = 256;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_unet_infer<LEADS>, p.threads, p.lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    m->infer_grid = per_cu * ncu;
+  }
+  k_unet_infer<LEADS><<<B < m->infer_grid ? B : m->infer_grid, p.threads, p.lds, s>>>(m->pack, x, y, m->cfg.L, B);
 }
 
 // ---- forward, one stage at a time (a data-parallel caller all-reduces the stage's BatchNorm sums in between) ----
-int unet_forward_stage(UNetModel* m, const float* x, int B, int training, int si, int64_t gwin, hipStream_t s) {
+int unet_forward_stage(UNetModel* m, const float* x, int B, int training, int si, int64_t gwin, hipStream_t s, int nrep) {
   if (!m->params || !m->state) return ral_fail("ral_bind was not called");
   if (B <= 0 || B > m->cfg.max_batch) return ral_fail("batch %d outside (0, %d]", B, m->cfg.max_batch);
   if (si < 0 || si > 10) return ral_fail("U-Net stage %d outside [0, 10]", si);
@@ -1982,56 +1927,46 @@ int unet_forward_stage(UNetModel* m, const float* x, int B, int training, int si
     m->last_x = x; m->last_B = B; m->gsums_dy = nullptr;
     if (training) {
       // (one fill for both halves of the replica records: the backward pass of this step finds its half zeroed)
-      if (m->nrep_f > 1) {
-        if (!m->rep_all_clean) (void)hipMemsetAsync(unet_rep(m, 0, 0), 0, (size_t)2 * 10 * UNET_MAXREP * 64 * sizeof(double), s);
+      if (nrep > 1) {
+        if (!m->rep_all_clean) (void)hipMemsetAsync(bn_record(m, 0, 0, nrep), 0, (size_t)2 * 10 * UNET_MAXREP * 64 * sizeof(double), s);
         m->rep_all_clean = false; m->rep_bwd_clean = true;
       }
       else (void)hipMemsetAsync(m->bn_sums, 0, 1280 * sizeof(double), s);
     }
   } else if (x != m->last_x || B != m->last_B) return ral_fail("U-Net stages must follow stage 0 of the same batch");
-  constexpr int fgmax = 512;   // (train forward at batch 2048: 0.31 / 0.27 / 0.29 / 0.41 ms with 256 / 512 / 1024 / 2048 workgroups)
-  static const int egmax = (int)ral_knob("UNET_EVAL_GRID", 512);   // (stage-by-stage eval forward at batch 2048: 173 / 158 / 177 us with 256 / 512 / 1024 workgroups)
-  const int gcap = training ? fgmax : egmax;
-  const int grid = B < gcap ? B : gcap;
-  Stage st = make_stage(m, si, x, training != 0, false, B, (double)gwin);
+  Stage st = make_stage(m, si, x, training != 0, false, (double)gwin, nrep);
   if (!training) st.sums_out = nullptr;
-  if (!launch_unet_fwd_fast(st, si, m->cfg.leads, B, grid, s)) k_unet_fwd<<<grid, 256, fwd_lds(st), s>>>(st, B);
+  launch_unet_fwd(unet_stage_plan(m->cfg.leads, m->cfg.L, B, training != 0, false, si), st, B, s);
   if (hipGetLastError() != hipSuccess) return ral_fail("U-Net forward launch failed");
   return 0;
 }
 
-int unet_forward_finish(UNetModel* m, float* y, int B, int training, int64_t gwin, hipStream_t s) {
-  if (B != m->last_B) return ral_fail("finish batch %d != stage batch %d", B, m->last_B);
-  Src o = make_src(m, 10, ACT_NONE, training != 0, false, 0);
-  const size_t total = (size_t)B * m->C[10] * m->Ln[10];
+// the running-statistics update of the ten BatchNorm layers, done by the kernel that ends a training forward
+static BnUpdAll bn_updates(UNetModel* m, bool training, double gwin, int nrep) {
   BnUpdAll u;
   memset(&u, 0, sizeof(u));
-  if (training) {
-    for (int zi = 0, k = 0; zi < 11; ++zi) {
-      const int bi = BN_OF_Z[zi];
-      if (bi < 0) continue;
-      u.l[k++] = BnUpd{m->nrep_f > 1 ? unet_rep(m, 0, bi) : m->bn_sums + 128 * bi, m->bn_sums + 128 * bi, m->state + m->off.run[bi],
-                       m->C[zi], (double)gwin * m->Ln[zi], m->nrep_f};
-    }
+  for (int zi = 0; training && zi < UNET_STAGES; ++zi) {
+    const int bi = unet_stage_bn(zi);
+    if (bi >= 0) u.l[bi] = BnUpd{bn_record(m, 0, bi, nrep), m->bn_sums + 128 * bi, m->state + m->off.run[bi], m->C[zi], gwin * m->Ln[zi], nrep};
   }
+  return u;
+}
+
+int unet_forward_finish(UNetModel* m, float* y, int B, int training, int64_t gwin, hipStream_t s, int nrep) {
+  if (B != m->last_B) return ral_fail("finish batch %d != stage batch %d", B, m->last_B);
+  Src o = make_src(m, 10, ACT_NONE, training != 0, false, 0, nrep);
+  const size_t total = (size_t)B * m->C[10] * m->Ln[10];
   // (the running update reads the layers' complete records: every stage kernel has finished; the output layer's record is
   // read by this kernel's own coefficient fold, not written)
-  k_unet_out<<<(int)((total / 4 + 255) / 256 < 1024 ? (total / 4 + 255) / 256 : 1024), 256, 0, s>>>(o, y, m->C[10], m->Ln[10],
-                                                                                               (double)gwin * m->Ln[10], total, u, training ? 1 : 0);
-  m->nrep_f = 1;
+  k_unet_out<<<(int)((total / 4 + 255) / 256 < 1024 ? (total / 4 + 255) / 256 : 1024), 256, 0, s>>>(
+      o, y, m->C[10], m->Ln[10], (double)gwin * m->Ln[10], total, bn_updates(m, training != 0, (double)gwin, nrep), training ? 1 : 0);
   if (hipGetLastError() != hipSuccess) return ral_fail("U-Net forward launch failed");
   return 0;
 }
 
-// The eval-mode forward as one kernel (+ the weight re-pack): windows of 256 / 512 / 768 / 1024 samples (the GEMM layers
-// need whole 16-row tiles at the deepest level and the window's tensors must fit LDS).  RAL_UNET_FUSED=0 keeps the
+// The eval-mode forward as one kernel (+ the weight re-pack) where unet_pass_plan says so; "unet_fused" = 0 keeps the
 // stage-by-stage path (which serves every other length, and training).
-static bool unet_infer_fused_applies(const UNetModel* m) {
-  const ral_config& c = m->cfg;
-  return m->fused && c.L % 256 == 0 && c.L <= 1024;
-}
-
-static int unet_forward_fused(UNetModel* m, const float* x, float* y, int B, hipStream_t s) {
+static int unet_forward_fused(UNetModel* m, const UStageLaunch& p, const float* x, float* y, int B, hipStream_t s) {
   if (!m->params || !m->state) return ral_fail("ral_bind was not called");
   if (B <= 0 || B > m->cfg.max_batch) return ral_fail("batch %d outside (0, %d]", B, m->cfg.max_batch);
   UPackArgs a;
@@ -2039,81 +1974,33 @@ static int unet_forward_fused(UNetModel* m, const float* x, float* y, int B, hip
   for (int i = 0; i < 11; ++i) { a.w[i] = m->off.w[i]; a.b[i] = m->off.b[i]; }
   for (int i = 0; i < 10; ++i) { a.bnw[i] = m->off.bnw[i]; a.bnb[i] = m->off.bnb[i]; a.run[i] = m->off.run[i]; }
   k_unet_pack<<<(uinf::PTOT + 255) / 256, 256, 0, s>>>(a);
-  const size_t lds = uinf_lds_floats(m->cfg.L) * sizeof(float);
-  // persistent grid = exactly the workgroups that are resident at once (a grid one LDS granule too optimistic runs its
-  // surplus workgroups as a second round: measured 76 us instead of 45 us at batch 2048)
-  const void* kfn = m->cfg.leads == 1 ? reinterpret_cast<const void*>(k_unet_infer<1>) : reinterpret_cast<const void*>(k_unet_infer<2>);
-  (void)hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (m->infer_grid == 0) {
-    int per_cu = 0, dev = 0, ncu = 256;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-    const hipError_t e = m->cfg.leads == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_unet_infer<1>, 256, lds)
-                                           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_unet_infer<2>, 256, lds);
-    if (e != hipSuccess || per_cu < 1) per_cu = 1;
-    m->infer_grid = per_cu * ncu;
+  switch (p.kernel) {
+    case K::INFER_1: launch_infer<1>(m, p, x, y, B, s); break;
+    case K::INFER_2: launch_infer<2>(m, p, x, y, B, s); break;
+    default: unet_launch_missing("unet_forward_fused", p);
   }
-  const int grid = B < m->infer_grid ? B : m->infer_grid;
-  if (m->cfg.leads == 1) k_unet_infer<1><<<grid, 256, lds, s>>>(m->pack, x, y, m->cfg.L, B);
-  else k_unet_infer<2><<<grid, 256, lds, s>>>(m->pack, x, y, m->cfg.L, B);
   if (hipGetLastError() != hipSuccess) return ral_fail("U-Net fused forward launch failed");
   return 0;
 }
 
 int UNetModel::forward(const float* x, float* y, int B, int training, hipStream_t s) {
   UNetModel* const m = this;
-  if (!training && unet_infer_fused_applies(m)) return unet_forward_fused(m, x, y, B, s);
-  m->nrep_f = (training && m->cfg.train) ? UNET_MAXREP : 1;
-  for (int si = 0; si < 11; ++si)
-    if (unet_forward_stage(m, x, B, training, si, B, s)) { m->nrep_f = 1; return -1; }
-  const int rc = unet_forward_finish(m, y, B, training, B, s);
-  m->nrep_f = 1;
-  return rc;
-}
-
-int unet_stage_bn(int si) { return (si >= 0 && si <= 10) ? BN_OF_Z[si] : -1; }
-
-
-template <int CIN, int COUT, int KS, int MODE>
-static void launch_bwd_t(const Stage& st, int B, int grid, int wp_req, hipStream_t s) {
-  const bool want_din = st.a.G != nullptr, third = st.b.z != nullptr || (want_din && st.a.accumulate);
-  auto lds_of = [&](int WP) {
-    return ((size_t)WP * CIN * (st.lin + 8) * (1 + (want_din ? 1 : 0) + (third ? 1 : 0)) + (size_t)WP * COUT * (st.lout + 10) +
-            (size_t)2 * CIN * COUT * KS + 4 * CIN + 31 * MAXC + 12) * sizeof(float);   // (weights: rows padded by up to 4 floats; 7 MAXC doubles of sums)
-  };
-  int WP = (B + grid - 1) / grid;                 // windows per workgroup
-  if (WP > wp_req) WP = wp_req;
-  while (WP > 1 && lds_of(WP) > 80 * 1024) WP = WP > 2 ? 2 : 1;  // two workgroups per CU; passes of equal size (4, 2 or 1 windows)
-  const size_t lds = lds_of(WP);
-  static size_t cur = 0;                          // (one per instantiation)
-  if (lds > cur) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_unet_bwd_t<CIN, COUT, KS, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); cur = lds; }
-  k_unet_bwd_t<CIN, COUT, KS, MODE><<<grid, UNET_BWD_THREADS, lds, s>>>(st, B, WP);
-}
-
-static bool launch_unet_bwd_fast(const Stage& st, int si, int leads, int B, int grid, int wp, hipStream_t s) {
-  if (st.lout % 4 || st.lin % 4) return false;
-  switch (si) {
-    case 0: if (leads == 1) launch_bwd_t<1, 4, 3, 0>(st, B, grid, wp, s); else launch_bwd_t<2, 4, 3, 0>(st, B, grid, wp, s); return true;
-    case 1: launch_bwd_t<4, 8, 3, 0>(st, B, grid, wp, s); return true;
-    case 2: launch_bwd_t<8, 16, 3, 0>(st, B, grid, wp, s); return true;
-    case 3: launch_bwd_t<16, 32, 3, 0>(st, B, grid, wp, s); return true;
-    case 4: launch_bwd_t<32, 32, 1, 1>(st, B, grid, wp, s); return true;
-    case 5: launch_bwd_t<32, 32, 3, 1>(st, B, grid, wp, s); return true;
-    case 6: launch_bwd_t<32, 32, 1, 1>(st, B, grid, wp, s); return true;
-    case 7: launch_bwd_t<32, 16, 4, 2>(st, B, grid, wp, s); return true;
-    case 8: launch_bwd_t<16, 8, 4, 2>(st, B, grid, wp, s); return true;
-    case 9: launch_bwd_t<8, 4, 4, 2>(st, B, grid, wp, s); return true;
-    case 10: if (leads == 1) launch_bwd_t<4, 1, 4, 2>(st, B, grid, wp, s); else launch_bwd_t<4, 2, 4, 2>(st, B, grid, wp, s); return true;
+  if (!training) {
+    const UPassPlan pp = unet_pass_plan(cfg.leads, cfg.L, cfg.train != 0, m->fused);
+    if (pp.fused_eval) return unet_forward_fused(m, pp.fused, x, y, B, s);
   }
-  return false;
+  const int nrep = training ? UNET_MAXREP : 1;
+  for (int si = 0; si < UNET_STAGES; ++si)
+    if (unet_forward_stage(m, x, B, training, si, B, s, nrep)) return -1;
+  return unet_forward_finish(m, y, B, training, B, s, nrep);
 }
 
 // ---- backward, one stage at a time: stage si needs the BatchNorm-backward sums of ITS OUTPUT's BatchNorm, which
 // the backward of its consumers (stages > si, and unet_backward_start for the last layer) has accumulated ----
 // the ten backward halves [64, 128) of the 128-double BatchNorm records, one strided fill
-static void unet_zero_bwd_records(UNetModel* m, hipStream_t s) {
-  if (m->nrep_b > 1) {
-    if (!m->rep_bwd_clean) (void)hipMemsetAsync(unet_rep(m, 1, 0), 0, (size_t)10 * UNET_MAXREP * 64 * sizeof(double), s);
+static void unet_zero_bwd_records(UNetModel* m, int nrep, hipStream_t s) {
+  if (nrep > 1) {
+    if (!m->rep_bwd_clean) (void)hipMemsetAsync(bn_record(m, 1, 0, nrep), 0, (size_t)10 * UNET_MAXREP * 64 * sizeof(double), s);
     m->rep_bwd_clean = false; m->rep_all_clean = false;
   } else (void)hipMemset2DAsync(m->bn_sums + 64, 128 * sizeof(double), 0, 64 * sizeof(double), 10, s);
 }
@@ -2125,33 +2012,23 @@ int unet_forward_loss(UNetModel* m, const float* x, const float* target, float* 
                       double* loss_sum, double* fin, double fin_scale, int fin3, hipStream_t s) {
   if (!m->cfg.train || !m->grads || !m->bn_sums) return ral_fail("forward + loss needs train=1, grads and bn_sums bound");
   if (!target || !y || !dy) return ral_fail("forward + loss: null pointer");
-  m->nrep_f = UNET_MAXREP;
-  for (int si = 0; si < 11; ++si)
-    if (unet_forward_stage(m, x, B, 1, si, B, s)) { m->nrep_f = 1; return -1; }
-  Src o = make_src(m, 10, ACT_NONE, true, false, 0);
-  BnUpdAll u;
-  memset(&u, 0, sizeof(u));
-  for (int zi = 0, k = 0; zi < 11; ++zi) {
-    const int bi = BN_OF_Z[zi];
-    if (bi < 0) continue;
-    u.l[k++] = BnUpd{m->nrep_f > 1 ? unet_rep(m, 0, bi) : m->bn_sums + 128 * bi, m->bn_sums + 128 * bi, m->state + m->off.run[bi],
-                     m->C[zi], (double)B * m->Ln[zi], m->nrep_f};
-  }
-  m->nrep_b = UNET_MAXREP;
-  unet_zero_bwd_records(m, s);
+  constexpr int nrep = UNET_MAXREP;
+  for (int si = 0; si < UNET_STAGES; ++si)
+    if (unet_forward_stage(m, x, B, 1, si, B, s, nrep)) return -1;
+  Src o = make_src(m, 10, ACT_NONE, true, false, 0, nrep);
+  unet_zero_bwd_records(m, nrep, s);
   const int C = m->C[10], L = m->Ln[10], n = C * L;
   constexpr int gmax = 256;   // (as k_loss_w's grid, ral_misc.hip)
   const int g = (B + UOL_WAVES - 1) / UOL_WAVES;
   k_unet_out_loss<<<g < gmax ? g : gmax, 64 * UOL_WAVES, 0, s>>>(o, y, target, dy, snr, rmse, loss_sum, C, L, B, (double)B * L,
-                                                               (float)(2.0 / ((double)B * n)), fin, fin_scale, fin3, u,
-                                                               m->nrep_b > 1 ? unet_rep(m, 1, 9) : m->bn_sums + 128 * 9 + 64, m->nrep_b);
-  m->gsums_dy = dy; m->gsums_nrep = m->nrep_b;
-  m->nrep_f = 1; m->nrep_b = 1;
+                                                               (float)(2.0 / ((double)B * n)), fin, fin_scale, fin3,
+                                                               bn_updates(m, true, (double)B, nrep), bn_record(m, 1, 9, nrep), nrep);
+  m->gsums_dy = dy; m->gsums_nrep = nrep;
   if (hipGetLastError() != hipSuccess) return ral_fail("U-Net forward launch failed");
   return 0;
 }
 
-int unet_backward_start(UNetModel* m, const float* dy, int B, int64_t gwin, hipStream_t s) {
+int unet_backward_start(UNetModel* m, const float* dy, int B, int64_t gwin, hipStream_t s, int nrep) {
   if (!m->cfg.train || !m->grads || !m->bn_sums) return ral_fail("backward needs train=1, grads and bn_sums bound");
   if (B != m->last_B) return ral_fail("backward batch %d != forward batch %d", B, m->last_B);
   // with the fold every gradient entry is WRITTEN by k_unet_fold; the atomic path accumulates into a zeroed buffer
@@ -2163,62 +2040,47 @@ int unet_backward_start(UNetModel* m, const float* dy, int B, int64_t gwin, hipS
   if (!dy) {
     if (!m->gsums_dy) return ral_fail("U-Net backward with dy = NULL must follow ral_forward_loss_means");
     dy = m->gsums_dy;
-    have_sums = m->gsums_nrep == m->nrep_b;
+    have_sums = m->gsums_nrep == nrep;
   }
   m->last_dy = dy;
   m->bwd_rows = 0;
   m->gsums_dy = nullptr;
   if (have_sums) return 0;
-  unet_zero_bwd_records(m, s);
+  unet_zero_bwd_records(m, nrep, s);
   const size_t total = (size_t)B * m->C[10] * m->Ln[10];
-  Src o = make_src(m, 10, ACT_NONE, true, false, 0);
+  Src o = make_src(m, 10, ACT_NONE, true, false, 0, 1);   // (the forward pass has folded its records)
   const size_t grows = (total / m->Ln[10] + 3) / 4;      // one wave per (window, channel) row
-  k_unet_gsums<<<(int)(grows < 512 ? grows : 512), 256, 0, s>>>(
-      dy, o, m->C[10], m->Ln[10], (double)gwin * m->Ln[10], m->nrep_b > 1 ? unet_rep(m, 1, 9) : m->bn_sums + 128 * 9 + 64, m->nrep_b, total);
+  k_unet_gsums<<<(int)(grows < 512 ? grows : 512), 256, 0, s>>>(dy, o, m->C[10], m->Ln[10], (double)gwin * m->Ln[10], bn_record(m, 1, 9, nrep), nrep, total);
   if (hipGetLastError() != hipSuccess) return ral_fail("U-Net backward launch failed");
   return 0;
 }
 
-int unet_backward_stage(UNetModel* m, int B, int si, int64_t gwin, hipStream_t s) {
+int unet_backward_stage(UNetModel* m, int B, int si, int64_t gwin, hipStream_t s, int nrep) {
   if (B != m->last_B) return ral_fail("backward batch %d != forward batch %d", B, m->last_B);
   if (si < 0 || si > 10) return ral_fail("U-Net stage %d outside [0, 10]", si);
-  // every workgroup ends with ~2 000 global atomics (its share of dW, db and the BatchNorm-backward sums): the chip retires
-  // ~75 of them per ns, so 1024 workgroups spend 30 us per launch on them alone.  Measured train step at batch 2048 with
-  // 1024 / 512 / 384 workgroups: 1.23 / 1.08 / 1.12 ms
-  constexpr int gmax0 = 512, wp = 2;   // (wp: at most two windows per pass of the specialised kernels, launch_bwd_t)
-  const int gmax = (m->fold && gmax0 > m->part_rows_max) ? m->part_rows_max : gmax0;
-  const int grid = B < gmax ? B : gmax;
   if (m->last_dy == nullptr) return ral_fail("U-Net backward stages must follow ral_unet_backward_start");
-  m->bwd_rows = grid;                             // (the same for every stage of a backward pass: it depends on B only)
-  // consumers run in reverse order; an encoder tensor's gradient is first WRITTEN by its decoder-side consumer
-  // (skip / residual, accumulate = 0) and later ACCUMULATED by the next encoder / bottleneck stage (accumulate = 1)
-  Stage st = make_stage(m, si, m->last_x, true, true, B, (double)gwin);
-  if (si == 0) { st.a.G = nullptr; }
-  const size_t lds = bwd_lds(st);
-  static size_t cur = 0;
-  if (lds > cur) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_unet_bwd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); cur = lds; }
-  if (!launch_unet_bwd_fast(st, si, m->cfg.leads, B, grid, wp, s)) k_unet_bwd<<<grid, 256, lds, s>>>(st, B);
+  const UStageLaunch p = unet_stage_plan(m->cfg.leads, m->cfg.L, B, true, true, si);
+  m->bwd_rows = p.grid;                           // (the same for every stage of a backward pass: it depends on B only)
+  launch_unet_bwd(p, make_stage(m, si, m->last_x, true, true, (double)gwin, nrep), B, s);
   if (hipGetLastError() != hipSuccess) return ral_fail("U-Net backward launch failed");
   return 0;
 }
 
-int unet_backward_finish(UNetModel* m, int B, int64_t gwin, hipStream_t s) {
+int unet_backward_finish(UNetModel* m, int B, int64_t gwin, hipStream_t s, int nrep) {
   BnGradAll u;
   for (int bi = 0; bi < 10; ++bi)
-    u.l[bi] = BnGrad{m->nrep_b > 1 ? unet_rep(m, 1, bi) : m->bn_sums + 128 * bi + 64, m->bn_sums + 128 * bi + 64,
-                     m->grads + m->off.bnw[bi], m->grads + m->off.bnb[bi], m->off.bnC[bi], m->nrep_b};
+    u.l[bi] = BnGrad{bn_record(m, 1, bi, nrep), m->bn_sums + 128 * bi + 64, m->grads + m->off.bnw[bi], m->grads + m->off.bnb[bi], m->off.bnC[bi], nrep};
   if (m->fold) {
     if (m->bwd_rows <= 0) return ral_fail("U-Net backward finish without its stages");
-    const bool reps = m->nrep_b > 1;
+    const bool reps = nrep > 1;
     k_unet_fold<<<(m->ncols + 63) / 64 + 1, 64 * UNET_FOLD_WAVES, 0, s>>>(m->part, m->part_stride, m->bwd_rows, m->cols, m->ncols, m->grads, u,
-                                                        (double)B / (double)gwin, reps ? unet_rep(m, 0, 0) : nullptr,
+                                                        (double)B / (double)gwin, reps ? bn_record(m, 0, 0, nrep) : nullptr,
                                                         reps ? 2 * 10 * UNET_MAXREP * 64 : 0);
     if (reps) m->rep_all_clean = true;
   } else {
     k_unet_bn_grads<<<10, MAXC, 0, s>>>(u, (double)B / (double)gwin);
   }
   m->last_dy = nullptr;
-  m->nrep_b = 1;
   if (hipGetLastError() != hipSuccess) return ral_fail("U-Net backward launch failed");
   return 0;
 }
@@ -2226,11 +2088,8 @@ int unet_backward_finish(UNetModel* m, int B, int64_t gwin, hipStream_t s) {
 int UNetModel::backward(const float* dy, float* dx, int B, hipStream_t s) {   // (dy = NULL: the gradient ral_forward_loss_means wrote)
   UNetModel* const m = this;
   if (dx) return ral_fail("U-Net input gradient is not provided");
-  m->nrep_b = UNET_MAXREP;
-  if (unet_backward_start(m, dy, B, B, s)) { m->nrep_b = 1; return -1; }
+  if (unet_backward_start(m, dy, B, B, s, UNET_MAXREP)) return -1;
   for (int si = 10; si >= 0; --si)
-    if (unet_backward_stage(m, B, si, B, s)) { m->nrep_b = 1; return -1; }
-  const int rc = unet_backward_finish(m, B, B, s);
-  m->nrep_b = 1;
-  return rc;
+    if (unet_backward_stage(m, B, si, B, s, UNET_MAXREP)) return -1;
+  return unet_backward_finish(m, B, B, s, UNET_MAXREP);
 }
