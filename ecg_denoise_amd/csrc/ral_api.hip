@@ -409,14 +409,18 @@ int ral_profile_timeline(ral_handle* h, double* rows, int64_t cap_rows, int64_t*
 
 int ral_conv13_forward(const float* x, const float* w, const float* b, float* y, int B, int cin, int cout, int L,
                        int lrelu, ral_stream s) {
-  if (launch_conv13_fwd(x, w, b, y, B, cin, cout, L, lrelu, (hipStream_t)s)) return ral_fail("conv13: unsupported channel counts %d -> %d", cin, cout);
+  const char* why = nullptr;
+  if (launch_conv13_fwd(x, w, b, y, B, cin, cout, L, lrelu, (hipStream_t)s, &why))
+    return ral_fail("ral_conv13_forward: %s (B=%d, channels %d -> %d, L=%d)", why, B, cin, cout, L);
   HIP_OK(hipGetLastError());
   return 0;
 }
 
 int ral_conv13_backward(const float* x, const float* y, const float* dy, const float* w, float* gw, float* gb,
                         float* dx, int B, int cin, int cout, int L, int lrelu, ral_stream s) {
-  if (launch_conv13_bwd(x, y, dy, w, gw, gb, dx, B, cin, cout, L, lrelu, (hipStream_t)s)) return ral_fail("conv13: unsupported channel counts %d -> %d", cin, cout);
+  const char* why = nullptr;
+  if (launch_conv13_bwd(x, y, dy, w, gw, gb, dx, B, cin, cout, L, lrelu, (hipStream_t)s, &why))
+    return ral_fail("ral_conv13_backward: %s (B=%d, channels %d -> %d, L=%d)", why, B, cin, cout, L);
   HIP_OK(hipGetLastError());
   return 0;
 }

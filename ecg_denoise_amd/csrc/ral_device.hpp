@@ -25,15 +25,15 @@ int ral_env_int(const char* name, int dflt, int lo, int hi);
 int ral_num_cus();                                                          // compute units of the current device (cached per device)
 int ral_occupancy(const void* kernel, int threads, size_t lds, int dflt);   // workgroups per CU, queried once per (kernel, threads, LDS bytes)
 
-// gfx950 has 160 KB of LDS per CU; dynamic LDS above 64 KB must be opted into per kernel (one high-water mark per call site).
+// gfx950 has 160 KB of LDS per CU; dynamic LDS above 64 KB must be opted into per kernel (one high-water mark per call site,
+// raised only by a size the runtime accepted: after a refused one, a smaller legal size still opts in).
 #define RAL_SET_LDS(kernel, bytes)                                                                     \
   do {                                                                                                 \
     static size_t ral_cur_ = 0;                                                                        \
-    if ((size_t)(bytes) > ral_cur_) {                                                                  \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),                                 \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes));             \
+    if ((size_t)(bytes) > ral_cur_ &&                                                                  \
+        hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),                                     \
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)) == hipSuccess)   \
       ral_cur_ = (size_t)(bytes);                                                                      \
-    }                                                                                                  \
   } while (0)
 
 

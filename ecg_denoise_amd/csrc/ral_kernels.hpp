@@ -140,9 +140,9 @@ int launch_rhythm_pool(const float* hist, const float* x, long long x_total, con
                        long long scratch_bytes, long long* out_pos, int* label, float* corr, float* rr, long long out_total,
                        hipStream_t s, const char** why, int* bad);
 int launch_conv13_fwd(const float* x, const float* w, const float* b, float* y, int B, int cin, int cout, int L,
-                      int lrelu, hipStream_t s);
+                      int lrelu, hipStream_t s, const char** why);   // -1: refused before any HIP call, *why names the argument
 int launch_conv13_bwd(const float* x, const float* y, const float* dy, const float* w, float* gw, float* gb,
-                      float* dx, int B, int cin, int cout, int L, int lrelu, hipStream_t s);
+                      float* dx, int B, int cin, int cout, int L, int lrelu, hipStream_t s, const char** why);
 
 void launch_transpose_mats(const float* src, float* dst, const void* desc, int nmat, int total, hipStream_t s);
 

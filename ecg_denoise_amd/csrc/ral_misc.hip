@@ -473,19 +473,34 @@ __global__ __launch_bounds__(256) void k_conv13_bwd(const float* __restrict__ x,
   if ((int)threadIdx.x < cout) atomicAdd(gb + threadIdx.x, gbacc);
 }
 
+// what both launchers refuse before any HIP call (-> the offending argument, or nullptr): a request that fails here never
+// reaches RAL_SET_LDS or the launch.  rows: LDS rows of L + 12 floats (cin forward, cin + cout backward)
+static constexpr size_t CONV13_LDS_MAX = 160 * 1024;   // LDS of one gfx950 CU
+static const char* conv13_refusal(int B, int cin, int cout, int L, int rows, size_t* lds) {
+  if (cin < 1 || cout < 1 || cin > 12 || cout > 12 || cin * cout * K13 > 1024) return "unsupported channel counts";
+  if (B < 1) return "B must be at least 1";
+  if (L < 1) return "L must be at least 1";
+  *lds = ((size_t)rows * ((size_t)L + 12) + (size_t)cout * cin * K13 + 4) * sizeof(float);
+  if (*lds > CONV13_LDS_MAX) return "L needs more than the 160 KB of LDS";
+  return nullptr;
+}
+
 int launch_conv13_fwd(const float* x, const float* w, const float* b, float* y, int B, int cin, int cout, int L,
-                      int lrelu, hipStream_t s) {
-  if (cin * cout * K13 > 1024 || cin > 12 || cout > 12) return -1;
-  const size_t lds = ((size_t)cin * (L + 12) + (size_t)cout * cin * K13 + 4) * sizeof(float);
+                      int lrelu, hipStream_t s, const char** why) {
+  size_t lds = 0;
+  *why = !x ? "x is NULL" : !w ? "w is NULL" : !b ? "b is NULL" : !y ? "y is NULL" : conv13_refusal(B, cin, cout, L, cin, &lds);
+  if (*why) return -1;
   RAL_SET_LDS(k_conv13_fwd, lds);
   k_conv13_fwd<<<B < 2048 ? B : 2048, 256, lds, s>>>(x, w, b, y, B, cin, cout, L, lrelu);
   return 0;
 }
 
 int launch_conv13_bwd(const float* x, const float* y, const float* dy, const float* w, float* gw, float* gb,
-                      float* dx, int B, int cin, int cout, int L, int lrelu, hipStream_t s) {
-  if (cin * cout * K13 > 1024 || cin > 12 || cout > 12) return -1;
-  const size_t lds = ((size_t)(cin + cout) * (L + 12) + (size_t)cout * cin * K13 + 4) * sizeof(float);
+                      float* dx, int B, int cin, int cout, int L, int lrelu, hipStream_t s, const char** why) {
+  size_t lds = 0;   // (dx is optional: NULL = no input gradient)
+  *why = !x ? "x is NULL" : !y ? "y is NULL" : !dy ? "dy is NULL" : !w ? "w is NULL" : !gw ? "gw is NULL" : !gb ? "gb is NULL" :
+         conv13_refusal(B, cin, cout, L, cin + cout, &lds);
+  if (*why) return -1;
   RAL_SET_LDS(k_conv13_bwd, lds);
   k_conv13_bwd<<<B < 512 ? B : 512, 256, lds, s>>>(x, y, dy, w, gw, gb, dx, B, cin, cout, L, lrelu);
   return 0;

@@ -85,7 +85,9 @@ def run_parity(variant, leads, L, B, device="cuda:0", trace=True, seed=1234, opt
     """-> dict of relative errors (HIP fp32 vs fp64 oracle).  `options`: {name: value} for ral_set_option on the model's handle,
     applied before the first forward.  `eval_forward`: after the train step, the eval-mode forward of the same model against
     the oracle's eval output (its BatchNorm on the running statistics the step left) as res["y_eval"].  `before_forward(model)`
-    is called once the options are set."""
+    is called once the options are set.  Gradients: every parameter gradient of `backward()` (dx = NULL, the training default);
+    then res["grad:input"] and the stem parameter gradients "grad:<name>@dx" of `backward(want_dx=True)`, and
+    res["grad:input_frozen"] of `backward_input` - the model comes back with the gradient buffer that last call left."""
     from ecg_denoise_amd import RALENet, _lib
     p32, x, tgt = make_case(variant, leads, L, B, seed)
     model = RALENet(variant, leads=leads, L=L, max_batch=B, train=True, device=device)
@@ -100,12 +102,13 @@ def run_parity(variant, leads, L, B, device="cuda:0", trace=True, seed=1234, opt
     loss, snr, rmse = model.loss_and_metrics(y, td)
     model.backward()
     torch.cuda.synchronize()
-    # fp64 oracle
+    # fp64 oracle (x is a leaf: the input gradient comes out of the same autograd call)
     p = OrderedDict((k, v.double().requires_grad_(True)) for k, v in p32.items())
     bn = O.new_bn_state(8, torch.float64)
-    yo, tr = oracle_trace(p, x.double(), variant, bn)
+    xo = x.double().requires_grad_(True)
+    yo, tr = oracle_trace(p, xo, variant, bn)
     lo = O.mse(yo, tgt.double())
-    grads = torch.autograd.grad(lo, list(p.values()), allow_unused=True)
+    *grads, dxo = torch.autograd.grad(lo, list(p.values()) + [xo], allow_unused=True)
     res = OrderedDict()
     res["y"] = rel(y.cpu().numpy(), yo.detach().numpy())
     res["loss"] = abs(loss.item() - lo.item()) / abs(lo.item())
@@ -118,6 +121,19 @@ def run_parity(variant, leads, L, B, device="cuda:0", trace=True, seed=1234, opt
         for k, v in tr.items():
             res["act:" + k] = rel(model.debug_tensor(k).cpu().numpy()[:v.numel()], v.detach().numpy())
     res.update(compare_grads(model.named_grads(), p, grads))
+    # the backward pass again on the same saved forward, now with the input gradient (ral_backward zeroes the gradient buffer
+    # itself): the stem kernel that formed only parameter gradients above stores dz as well - its parameter gradients are compared
+    # again, as grad:<name>@dx - and k_conv1_bwd_dx turns dz into dx
+    dx = model.backward(want_dx=True)
+    torch.cuda.synchronize()
+    res["grad:input"] = rel(dx.cpu().numpy(), dxo.numpy())
+    stem = [k for k in p if k.startswith(("conv1.0.", "conv1.2."))]
+    again = compare_grads(model.named_grads(), OrderedDict((k, p[k]) for k in stem), [grads[list(p).index(k)] for k in stem])
+    res.update((k + "@dx", v) for k, v in again.items())
+    # the frozen-weight chain (what NewRALE training runs: no weight-gradient kernels) from the same dy
+    dxf = model.backward_input(model._dy)
+    torch.cuda.synchronize()
+    res["grad:input_frozen"] = rel(dxf.cpu().numpy(), dxo.numpy())
     if eval_forward:
         model.eval()
         ye = model(xd)
@@ -127,6 +143,88 @@ def run_parity(variant, leads, L, B, device="cuda:0", trace=True, seed=1234, opt
         res["y_eval"] = rel(ye.cpu().numpy(), yeo.numpy())
         model.train()
     return res, model, (p32, x, tgt)
+
+
+def make_newrale_case(variant, L, B):
+    """`make_case`'s seeds for the 12-lead adapter: inner 2-lead RA-LENet parameters (1234), adapter parameters (77), x and
+    target (B, 12, L) from generator 2023"""
+    p32 = O.init_params(O.ralenet_param_shapes(variant, 2), 1234)
+    pa32 = O.init_params(O.newrale_param_shapes(), 77)
+    g = torch.Generator().manual_seed(2023)
+    x = torch.randn(B, 12, L, generator=g)
+    tgt = torch.randn(B, 12, L, generator=g)
+    return p32, pa32, x, tgt
+
+
+def _newrale_model(variant, L, B, p32, pa32, device):
+    from ecg_denoise_amd import NewRALE, RALENet
+    inner = RALENet(variant, leads=2, L=L, max_batch=B, train=True, device=device)
+    inner.load_state_dict(p32, strict=False)
+    m = NewRALE(inner)
+    m.load_state_dict(pa32)
+    return m.train()
+
+
+def run_newrale_parity(variant, L, B, device="cuda:0"):
+    """One train step of the 12-lead adapter around a frozen RA-LENet (HIP fp32) against the fp64 oracle -> dict of relative
+    errors: y in train mode, loss / SNR / RMSE over the 12 x L windows, the eight adapter gradients ("grad:<name>"), the inner
+    BatchNorm's running statistics after the step (quirk A16: the frozen model's BatchNorm keeps training) and the eval-mode
+    forward on those statistics."""
+    p32, pa32, x, tgt = make_newrale_case(variant, L, B)
+    m = _newrale_model(variant, L, B, p32, pa32, device)
+    xd, td = x.to(device), tgt.to(device)
+    y = m(xd)
+    loss, snr, rmse = m.loss_and_metrics(y, td)
+    m.backward()
+    torch.cuda.synchronize()
+    p = OrderedDict((k, v.double()) for k, v in p32.items())
+    pa = OrderedDict((k, v.double().requires_grad_(True)) for k, v in pa32.items())
+    bn = O.new_bn_state(8, torch.float64)
+    yo = O.newrale_forward(pa, p, x.double(), variant, True, bn)
+    lo = O.mse(yo, tgt.double())
+    grads = torch.autograd.grad(lo, list(pa.values()))
+    res = OrderedDict()
+    res["y"] = rel(y.cpu().numpy(), yo.detach().numpy())
+    res["loss"] = abs(loss.item() - lo.item()) / abs(lo.item())
+    res["snr"] = rel(snr.cpu().numpy(), O.snr(tgt.double(), yo.detach()).numpy())
+    res["rmse"] = rel(rmse.cpu().numpy(), O.rmse(tgt.double(), yo.detach()).numpy())
+    for (k, g), mine in zip(zip(pa, grads), m.named_grads().values()):
+        res["grad:" + k] = rel(mine.cpu().numpy(), g.numpy())
+    st = m.rale.state_dict()
+    res["bn_mean"] = rel(st["conv1.2.running_mean"].cpu().numpy(), bn["running_mean"].numpy())
+    res["bn_var"] = rel(st["conv1.2.running_var"].cpu().numpy(), bn["running_var"].numpy())
+    m.eval()
+    ye = m(xd)
+    torch.cuda.synchronize()
+    with torch.no_grad():
+        yeo = O.newrale_forward(OrderedDict((k, v.detach()) for k, v in pa.items()), p, x.double(), variant, training=False, bn=bn)
+    res["y_eval"] = rel(ye.cpu().numpy(), yeo.numpy())
+    return res
+
+
+def run_newrale_adam(variant, L, B, steps=3, device="cuda:0"):
+    """`steps` train_steps of a fresh adapter against as many O.train_step / O.adam_step iterations on the adapter parameters
+    in fp64 -> (dict of relative errors: "loss<i>", "pred<i>" per step, "param:<name>" after the last one; the model; the inner
+    model's flat parameters before the first step)."""
+    p32, pa32, x, tgt = make_newrale_case(variant, L, B)
+    m = _newrale_model(variant, L, B, p32, pa32, device)
+    xd, td = x.to(device), tgt.to(device)
+    inner_before = m.rale.eng.params.clone()
+    p = OrderedDict((k, v.double()) for k, v in p32.items())
+    pa = OrderedDict((k, v.double()) for k, v in pa32.items())
+    am = OrderedDict((k, torch.zeros_like(v)) for k, v in pa.items())
+    av = OrderedDict((k, torch.zeros_like(v)) for k, v in pa.items())
+    bn = O.new_bn_state(8, torch.float64)
+    res = OrderedDict()
+    for i in range(1, steps + 1):
+        out = m.train_step(xd, td)
+        ref = O.train_step(pa, x.double(), tgt.double(), lambda leaves, xx: O.newrale_forward(leaves, p, xx, variant, True, bn), am, av, i)
+        res[f"loss{i}"] = abs(out["loss"].item() - ref["loss"].item()) / abs(ref["loss"].item())
+        res[f"pred{i}"] = rel(out["pred"].cpu().numpy(), ref["pred"].numpy())
+    torch.cuda.synchronize()
+    for k, v in m.named_parameters():
+        res["param:" + k] = rel(v.cpu().numpy(), pa[k].numpy())
+    return res, m, inner_before
 
 
 def oracle_windows(p32, x, tgt, idx, variant="full"):

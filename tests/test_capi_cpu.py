@@ -258,6 +258,44 @@ def test_pe_table_only_for_ralenet_variants(variant, leads, L):
         assert np.isnan(buf).all()                # (nothing was written)
 
 
+_CONV13_FWD = ("x", "w", "b", "y")
+_CONV13_BWD = ("x", "y", "dy", "w", "gw", "gb", "dx")
+# (entry point, {argument: value} over the legal call B=2, 12 -> 6 channels, L=256, what the message must name)
+_CONV13_REFUSALS = (
+    [(fn, {p: None}, f"{p} is NULL") for fn, ps in (("forward", _CONV13_FWD), ("backward", _CONV13_BWD[:-1])) for p in ps]
+    + [(fn, kw, msg) for fn in ("forward", "backward") for kw, msg in [
+        (dict(B=0), "B must be at least 1"), (dict(B=-3), "B must be at least 1"),
+        (dict(L=0), "L must be at least 1"), (dict(L=-1), "L must be at least 1"),
+        (dict(cin=12, cout=12), "unsupported channel counts"), (dict(cin=13, cout=1), "unsupported channel counts"),
+        (dict(cin=1, cout=13), "unsupported channel counts"), (dict(cin=0, cout=6), "unsupported channel counts"),
+        (dict(L=2 ** 31 - 1), "L needs more than the 160 KB of LDS")]]
+    # 12 -> 6 channels: forward rows of 12, backward rows of 18 floats per sample; the first L past 160 KB of LDS each
+    + [("forward", dict(L=3324), "L needs more than the 160 KB of LDS"), ("backward", dict(L=2212), "L needs more than the 160 KB of LDS")])
+
+
+@pytest.mark.parametrize("fn,kw,msg", _CONV13_REFUSALS, ids=[f"{fn}-{'-'.join(f'{k}={v}' for k, v in kw.items())}" for fn, kw, _ in _CONV13_REFUSALS])
+def test_conv13_entry_points_refuse_bad_arguments_before_any_launch(fn, kw, msg):
+    """ral_conv13_forward / _backward refuse a null operand (dx alone is optional), B < 1, L < 1, channel counts the kernels
+    do not take and a row length whose LDS need passes the 160 KB of a CU - each with a message that names the argument, and
+    before any HIP call: this runs without a device (the operand pointers are host memory that a launch would fault on)."""
+    host = np.zeros(16, np.float32)
+    a = dict(B=2, cin=12, cout=6, L=256)
+    ptr = {p: host.ctypes.data_as(C.c_void_p) for p in _CONV13_FWD + _CONV13_BWD}
+    for k, v in kw.items():
+        if k in ptr:
+            ptr[k] = C.c_void_p(0)
+        else:
+            a[k] = v
+    L = _lib.lib()
+    L.ral_param_floats(C.byref(_lib.make_config("full", 2, 512, 0, 1)))     # leaves another message behind
+    if fn == "forward":
+        rc = L.ral_conv13_forward(*(ptr[p] for p in _CONV13_FWD), a["B"], a["cin"], a["cout"], a["L"], 1, C.c_void_p(0))
+    else:
+        rc = L.ral_conv13_backward(*(ptr[p] for p in _CONV13_BWD), a["B"], a["cin"], a["cout"], a["L"], 1, C.c_void_p(0))
+    err = L.ral_last_error().decode()
+    assert rc != 0 and err.startswith(f"ral_conv13_{fn}: {msg}"), (rc, err)
+
+
 def test_backward_halves_refusal_names_no_network():
     """ral_backward_begin / _end are RA-LENet's; their refusal on another handle says so without naming a network the handle
     is not (the text the GPU test of the handles asserts on real handles: no handle can be created here)"""

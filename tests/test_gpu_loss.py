@@ -12,11 +12,18 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
+# k_loss_w has 256 workgroups of 8 waves and a wave takes its windows two at a time, w and w + 2048: the second window of a pair
+# exists only beyond 2048 windows.  (2049, 8): window 0 alone has a partner; (4097, 4): every window of the first pass has one
+# and the last window is alone in a second pass; (6000, 8): a ragged second half; (5, 1028): n / 4 = 257, one live lane (the
+# others on the clamped index) in the second pass over the window
+PAIRED = [(2049, 8, 2049), (4097, 4, 4097), (6000, 8, 6000), (5, 1028, 5)]
+
+
 def _vp(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
-@pytest.mark.parametrize("B,n,gw", [(37, 1024, 37), (2048, 512, 8192), (5, 1022, 5), (1, 4, 3)])
+@pytest.mark.parametrize("B,n,gw", [(37, 1024, 37), (2048, 512, 8192), (5, 1022, 5), (1, 4, 3)] + PAIRED)
 def test_loss_mean_equals_the_host_formula_and_resets_its_scratch(B, n, gw):
     g = torch.Generator().manual_seed(B + n)
     pred = torch.randn(B, n, generator=g).to(DEV); tgt = torch.randn(B, n, generator=g).to(DEV)
@@ -37,7 +44,7 @@ def test_loss_mean_equals_the_host_formula_and_resets_its_scratch(B, n, gw):
         assert torch.allclose(snr.double(), ref_snr, rtol=1e-5, atol=1e-5)
 
 
-@pytest.mark.parametrize("B,n,gw", [(37, 1024, 37), (2048, 512, 8192), (5, 1022, 5)])
+@pytest.mark.parametrize("B,n,gw", [(37, 1024, 37), (2048, 512, 8192), (5, 1022, 5)] + PAIRED)
 def test_loss_means_carry_the_metric_means(B, n, gw):
     """ral_loss_means: the batch means of SNR and RMSE (what denoise_train.py:58-64 logs per step) leave the loss kernel
     with the loss - sums of the per-window fp32 values in double, divided by the global window count."""

@@ -2,7 +2,8 @@
 vectors generated from the reference.  Needs an MI355X: `pytest -m gpu`.
 
 Tolerances (fp32 kernels vs the oracle evaluated in fp64): forward 1e-5 relative L2
-(north-star bar: 1e-3), gradients 1e-4, both far above the observed 2e-7 / 2e-6."""
+(north-star bar: 1e-3), gradients 1e-4, both far above the observed 2e-7 / 2e-6.  The gradient bar covers the input
+gradient as well (parity_util.run_parity: `grad:input`, `grad:input_frozen`, the stem gradients `@dx`; observed 2e-7 .. 4e-7)."""
 import os
 from collections import OrderedDict
 

@@ -147,6 +147,19 @@ def test_unet_backward_twice_gives_the_same_gradients():
             assert rel(g2[k].cpu().numpy(), g1[k].cpu().numpy()) < 1e-5, k
 
 
+def test_unet_refuses_an_input_gradient():
+    """the U-Net forms no input gradient: `backward(want_dx=True)` is refused, not answered with an unwritten tensor"""
+    from ecg_denoise_amd import RalError, UNet
+    m = UNet(leads=2, L=64, max_batch=2, device=DEV, seed=5)
+    x = torch.randn(2, 2, 64, device=DEV)
+    m.train()
+    m.loss_and_metrics(m(x), torch.zeros_like(x))
+    with pytest.raises(RalError, match="U-Net input gradient is not provided"):
+        m.backward(want_dx=True)
+    m.backward()                                      # (the refusal leaves the saved forward usable)
+    torch.cuda.synchronize()
+
+
 @pytest.mark.parametrize("leads,L,B", [(2, 512, 2048), (1, 256, 37), (2, 48, 5), (2, 2048, 9), (2, 64, 1025)])
 def test_unet_forward_loss_in_one_call_equals_forward_then_loss(leads, L, B):
     """`forward_loss` (ral_forward_loss_means: the output BatchNorm, the loss sums, dy and the first two sums of the backward pass
