@@ -33,6 +33,7 @@ def hw_queues_set_too_late():
 from .model import ACDAE, DANet, NewRALE, RALENet, UNet, ralenet  # noqa: F401
 from .infer import LiveDenoiser, LivePool, NewRALELiveDenoiser, NewRALELivePool  # noqa: F401
 from .evaluate import RecordScores, mix_records, score_records  # noqa: F401
+from .augment import MixedBatch, NoiseMixSampler, kind_thresholds  # noqa: F401
 from .rate import (RateLivePool, RateStreamingDenoiser, Resampler, ResamplerPool, rate_bank, rate_frontier,  # noqa: F401
                    rate_latency, rate_length, rate_ratio)
 from .beats import (BeatDetector, BeatPool, Beats, BeatScores, beat_bank, beat_frontier, beat_geometry, beat_latency,  # noqa: F401

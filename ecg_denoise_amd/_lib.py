@@ -143,6 +143,10 @@ _SIGS = {
     "ral_mix_records": (C.c_int, [_VP, _VP, C.c_int64, C.c_int, C.c_int64, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP]),
     "ral_score_records_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int, C.c_int64, C.c_int64]),
     "ral_score_records": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int, C.c_int64, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "ral_mix_batch": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, _VP, C.c_double,
+                                C.c_double, C.c_uint64, C.c_uint64, C.c_int64, _VP, _VP, _VP, _VP, _VP]),
+    "ral_mix_draw": (C.c_int, [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int64, _VP, C.c_double, C.c_double, C.c_uint64,
+                               C.c_uint64, _VP, _VP]),
     "ral_rate_records": (C.c_int, [_VP, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, _VP, C.c_int, _VP, C.c_int64, _VP]),
     "ral_rate_pool": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int, _VP, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _VP,
                                 C.c_int, C.c_int, _VP, C.c_int64, _VP]),

@@ -653,6 +653,43 @@ int ral_score_records(const float* clean, const float* out, const float* noisy, 
   return 0;
 }
 
+static MixBatchGeom mix_geom(int64_t N, int leads, int64_t Lsrc, int L, int K, int64_t Tn, const uint32_t* cum, double snr_lo,
+                             double snr_hi, uint64_t seed, uint64_t first) {
+  MixBatchGeom G;
+  G.N = (long long)N; G.Lsrc = (long long)Lsrc; G.Tn = (long long)Tn;
+  G.leads = leads; G.L = L; G.K = K;
+  for (int k = 0; k < RAL_MIX_MAX_KINDS; ++k) G.cum[k] = (cum && k < K) ? cum[k] : 0xffffffffu;
+  G.snr_lo = snr_lo; G.snr_hi = snr_hi;
+  G.seed = seed; G.first = first;
+  return G;
+}
+#define MIX_ARGS "(N=%lld leads=%d Lsrc=%lld L=%d K=%d Tn=%lld B=%lld snr_db=[%g, %g])"
+
+int ral_mix_batch(const float* bank, const float* noise, const int64_t* rows, int64_t N, int leads, int64_t Lsrc, int L, int K,
+                  int64_t Tn, const uint32_t* cum, double snr_lo, double snr_hi, uint64_t seed, uint64_t first, int64_t B,
+                  float* noisy, float* clean, int32_t* draws, double* snr_db, ral_stream s) {
+  const char* why = nullptr;
+  int rc = -1;
+  if (!bank || !noise || !cum || !noisy || !clean || !draws || !snr_db) why = "no null pointer (only rows may be null)";
+  else rc = launch_mix_batch(bank, noise, rows, mix_geom(N, leads, Lsrc, L, K, Tn, cum, snr_lo, snr_hi, seed, first), (long long)B,
+                             noisy, clean, draws, snr_db, (hipStream_t)s, &why);
+  if (rc)
+    return ral_fail("mix_batch: need %s " MIX_ARGS, why, (long long)N, leads, (long long)Lsrc, L, K, (long long)Tn, (long long)B,
+                    snr_lo, snr_hi);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int ral_mix_draw(int64_t N, int64_t Lsrc, int L, int K, int64_t Tn, const uint32_t* cum, double snr_lo, double snr_hi,
+                 uint64_t seed, uint64_t g, int32_t* draw, double* snr_db) {
+  const MixBatchGeom G = mix_geom(N, 1, Lsrc, L, K, Tn, cum, snr_lo, snr_hi, seed, 0);
+  const char* why = (!cum || !draw || !snr_db) ? "no null pointer" : mix_batch_check(G);
+  if (why)
+    return ral_fail("mix_draw: need %s " MIX_ARGS, why, (long long)N, 1, (long long)Lsrc, L, K, (long long)Tn, 1LL, snr_lo, snr_hi);
+  mix_batch_draw(G, g, draw, snr_db);
+  return 0;
+}
+
 int ral_rate_records(const float* x, int64_t R, int leads, int64_t T, int up, int down, const float* bank, int ntaps, float* y,
                      int64_t T_out, ral_stream s) {
   if (!x || !bank || !y) return ral_fail("rate_records: null pointer");

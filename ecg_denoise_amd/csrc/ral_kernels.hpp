@@ -104,6 +104,21 @@ long long score_records_scratch_bytes(long long R, int leads, long long T, long 
 int launch_score_records(const float* clean, const float* out, const float* noisy, long long R, int leads, long long T, long long W,
                          void* scratch, double* per_lead, double* per_record, double* per_window, double* window_mean,
                          hipStream_t s, const char** why);
+// on-the-fly noise mixing of training batches (ral_augment.hip; ral_mix_batch / ral_mix_draw).  The geometry travels by value, as
+// a kernel argument (thresholds included: no copy).  mix_batch_check: the broken rule, or nullptr; launch_mix_batch checks, then
+// launches one kernel; -1: bad arguments (*why: the rule that is broken).  mix_batch_draw: the draw of ordinal g on the host, by
+// the code the kernel runs (the geometry must have passed the check)
+struct MixBatchGeom {
+  long long N, Lsrc, Tn;
+  int leads, L, K;
+  uint32_t cum[RAL_MIX_MAX_KINDS];
+  double snr_lo, snr_hi;
+  uint64_t seed, first;
+};
+const char* mix_batch_check(const MixBatchGeom& G);
+void mix_batch_draw(const MixBatchGeom& G, uint64_t g, int32_t* draw, double* snr_db);
+int launch_mix_batch(const float* bank, const float* noise, const int64_t* rows, const MixBatchGeom& G, long long B, float* noisy,
+                     float* clean, int32_t* draws, double* snr_db, hipStream_t s, const char** why);
 // sample-rate conversion (ral_rate.hip; ral_rate_records / ral_rate_pool): the arguments (and, with upload != 0, the host table)
 // are checked, the table copied to tab_dev on s, the kernel launched; -1: bad arguments (*why: the rule that is broken, *bad:
 // the row that breaks it or -1), -2: the copy failed
