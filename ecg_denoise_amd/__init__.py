@@ -39,5 +39,7 @@ from .rate import (RateLivePool, RateStreamingDenoiser, Resampler, ResamplerPool
 from .beats import (BeatDetector, BeatPool, Beats, BeatScores, beat_bank, beat_frontier, beat_geometry, beat_latency,  # noqa: F401
                     evaluate_beats, match_beats)
 from .rhythm import (BeatClasses, BeatClassifier, BeatClassPool, evaluate_rhythm, rhythm_check, rhythm_geometry)  # noqa: F401
+from .delineate import (BeatDelineator, Fiducials, IntervalEvaluation, delineate_check, delineate_geometry,  # noqa: F401
+                        evaluate_intervals, interval_scores)
 from .hrv import (HrvAnalyzer, HrvEvaluation, HrvPool, HrvPoolState, HrvWindows, evaluate_hrv, hrv_check, hrv_geometry,  # noqa: F401
                   hrv_windows)

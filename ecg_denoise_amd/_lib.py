@@ -37,6 +37,12 @@ class RhythmGeom(C.Structure):
     _fields_ = [("wb", C.c_int32), ("sa", C.c_int32), ("c0", C.c_float), ("r0", C.c_float)]
 
 
+class DelinGeom(C.Structure):
+    """ral_delin_geom: the delineator's seven lengths in samples and its threshold"""
+    _fields_ = [("h", C.c_int32), ("m", C.c_int32), ("wq", C.c_int32), ("g", C.c_int32), ("m2", C.c_int32), ("gt", C.c_int32),
+                ("wt", C.c_int32), ("q0", C.c_float)]
+
+
 class HrvGeom(C.Structure):
     """ral_hrv_geom: the HRV window's lengths in samples, its bin count, min_nn and the rate"""
     _fields_ = [("W", C.c_int32), ("lo_n", C.c_int32), ("hi_n", C.c_int32), ("t50", C.c_int32), ("F", C.c_int32),
@@ -161,6 +167,8 @@ _SIGS = {
                                      _VP]),
     "ral_rhythm_pool": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int, _VP, C.c_int, C.c_int64, C.c_int, C.POINTER(RhythmGeom),
                                   C.c_int, _VP, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
+    "ral_delineate_records": (C.c_int, [_VP, C.c_int64, C.c_int, C.c_int64, C.POINTER(DelinGeom), _VP, _VP, C.c_int64, _VP, _VP, _VP,
+                                        _VP, _VP]),
     "ral_hrv_windows": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int64, _VP, C.c_int, C.POINTER(HrvGeom), _VP, _VP,
                                   _VP, _VP, _VP]),
     "ral_attention_forward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),

@@ -825,6 +825,19 @@ int ral_rhythm_pool(const float* hist, const float* x, int64_t x_total, const ra
                     (long long)new_total, (long long)out_total, (long long)scratch_bytes, gt);
 }
 
+int ral_delineate_records(const float* x, int64_t R, int leads, int64_t T, const ral_delin_geom* geom, const int32_t* peaks,
+                          const int32_t* count, int64_t cap, int32_t* on, int32_t* off, int32_t* tpeak, int32_t* tend, ral_stream s) {
+  if (!x || !geom || !peaks || !count || !on || !off || !tpeak || !tend) return ral_fail("delineate_records: null pointer");
+  const char* why = nullptr;
+  if (launch_delineate_records(x, (long long)R, leads, (long long)T, geom, peaks, count, (long long)cap, on, off, tpeak, tend,
+                               (hipStream_t)s, &why))
+    return ral_fail("delineate_records: need %s (R=%lld leads=%d T=%lld cap=%lld h=%d m=%d Wq=%d g=%d m2=%d gt=%d Wt=%d q0=%g)", why,
+                    (long long)R, leads, (long long)T, (long long)cap, geom->h, geom->m, geom->wq, geom->g, geom->m2, geom->gt,
+                    geom->wt, geom->q0);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 int ral_hrv_windows(const int32_t* pos, const int32_t* label_or_null, const int32_t* count, int64_t R, int64_t cap,
                     const ral_hrv_row* table, int64_t rows, ral_hrv_row* table_dev, int upload, const ral_hrv_geom* geom,
                     const int32_t* band, int32_t* counts, float* stats, float* psd_or_null, ral_stream s) {

@@ -154,6 +154,10 @@ int launch_rhythm_pool(const float* hist, const float* x, long long x_total, con
                        float* ring, long long* ring_pos, const long long* new_pos, long long new_total, void* scratch,
                        long long scratch_bytes, long long* out_pos, int* label, float* corr, float* rr, long long out_total,
                        hipStream_t s, const char** why, int* bad);
+// beat delineation (ral_delineate.hip; ral_delineate_records): -1 with *why for a refusal, before any launch
+int launch_delineate_records(const float* x, long long R, int leads, long long T, const ral_delin_geom* geom, const int* peaks,
+                             const int* count, long long cap, int* on, int* off, int* tpeak, int* tend, hipStream_t s,
+                             const char** why);
 int launch_conv13_fwd(const float* x, const float* w, const float* b, float* y, int B, int cin, int cout, int L,
                       int lrelu, hipStream_t s, const char** why);   // -1: refused before any HIP call, *why names the argument
 int launch_conv13_bwd(const float* x, const float* y, const float* dy, const float* w, float* gw, float* gb,

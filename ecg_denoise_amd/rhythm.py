@@ -122,19 +122,20 @@ def _geom(g, c0, r0, what):
     return _lib.RhythmGeom(g["Wb"], g["Sa"], c0, r0)
 
 
-def _positions(beats, R, T, device):
-    """`Beats`, or one strictly ascending list of positions in [0, T) per record -> ((R, cap) int32, (R,) int32) on the device"""
+def _positions(beats, R, T, device, what="BeatClassifier.classify"):
+    """`Beats`, or one strictly ascending list of positions in [0, T) per record -> ((R, cap) int32, (R,) int32) on the device;
+    `what` names the caller in the error messages"""
     if isinstance(beats, Beats):
         if beats.peaks.shape[0] != R or beats.peaks.device != device:
-            raise _lib.RalError(f"BeatClassifier.classify: {beats.peaks.shape[0]} beat lists on {beats.peaks.device} for {R} "
+            raise _lib.RalError(f"{what}: {beats.peaks.shape[0]} beat lists on {beats.peaks.device} for {R} "
                                 f"records on {device}")
         return beats.peaks.contiguous(), beats.count.contiguous()
     rows = [np.asarray(r.cpu() if torch.is_tensor(r) else r, dtype=np.int64).reshape(-1) for r in beats]
     if len(rows) != R:
-        raise _lib.RalError(f"BeatClassifier.classify: {len(rows)} beat lists for {R} records")
+        raise _lib.RalError(f"{what}: {len(rows)} beat lists for {R} records")
     for r in rows:
         if len(r) and (r[0] < 0 or r[-1] >= T or np.any(np.diff(r) <= 0)):
-            raise _lib.RalError(f"BeatClassifier.classify: the beats of a record must be strictly ascending positions in [0, {T})")
+            raise _lib.RalError(f"{what}: the beats of a record must be strictly ascending positions in [0, {T})")
     pad = np.full((R, max(1, max(len(r) for r in rows))), -1, dtype=np.int32)
     for i, r in enumerate(rows):
         pad[i, :len(r)] = r

@@ -36,9 +36,15 @@ mean absolute error of heart rate, SDNN, RMSSD and log(LF/HF) of the noisy and o
 each record detected, classified and analysed on its own (`evaluate_hrv`; windows of `--hrv-win` seconds every `--hrv-hop`
 seconds; NaN where no window has all three values).  Without the flag the output is what it was.
 
+`--intervals` asks the fourth question, are the intervals back: per cell one more line and an "intervals" entry in the JSON
+with, for the noisy and for the denoised records, the share of the beats whose QRS duration (and whose QT) can be measured in the
+clean record and can be measured here too, and the mean absolute error of QRS duration and of QT in ms over the beats measurable
+in both - `BeatDelineator` at the clean records' detections (`evaluate_intervals`; NaN where there is no such beat).  Without
+the flag the output is what it was.
+
     python tools/stress_eval.py [--model full|nra|mlp|unet|acdae|danet|newrale] [--ckpt state_dict.pth] [--L 512]
                                 [--records 4] [--T 65000] [--overlap 0] [--batch 4096] [--time-shapes ...] [--reps 5] [--beats]
-                                [--classes] [--fft] [--fft-L 1000] [--hrv] [--hrv-win 60] [--hrv-hop 30]
+                                [--classes] [--fft] [--fft-L 1000] [--hrv] [--hrv-win 60] [--hrv-hop 30] [--intervals]
 """
 import argparse
 import json
@@ -51,8 +57,9 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from ecg_denoise_amd import (ACDAE, ClassicalDenoiser, DANet, NewRALE, RALENet, UNet, evaluate_beats, evaluate_hrv, evaluate_rhythm,  # noqa: E402
-                             mix_records, score_records, synth, wavelet_denoise)
+from ecg_denoise_amd import (ACDAE, ClassicalDenoiser, DANet, NewRALE, RALENet, UNet, evaluate_beats, evaluate_hrv,  # noqa: E402
+                             evaluate_intervals, evaluate_rhythm, interval_scores, mix_records, score_records, synth,
+                             wavelet_denoise)
 from ecg_denoise_amd.data import NOISE_TYPES, TRUE_NOISE  # noqa: E402
 from ecg_denoise_amd.infer import StreamingDenoiser  # noqa: E402
 
@@ -130,6 +137,11 @@ def _hrv_cell(ev, idx):
     return out
 
 
+def _intervals_cell(ev, idx):
+    """the records idx of an `evaluate_intervals` result -> the pooled shares and errors, noisy and denoised"""
+    return {key: interval_scores(ev.clean, f, rows=idx)[2] for key, f in (("noisy", ev.noisy), ("denoised", ev.denoised))}
+
+
 def grid(args, model, name):
     sd = StreamingDenoiser(model, batch=args.batch, overlap=args.overlap, use_graph=True)
     leads, n_int = sd.leads, len(TRUE_NOISE)
@@ -156,6 +168,7 @@ def grid(args, model, name):
             from ecg_denoise_amd import HrvAnalyzer
             evh = evaluate_hrv(sd, rec, noise, snrs, offsets=offsets,
                                analyzer=HrvAnalyzer(win_s=args.hrv_win, hop_s=args.hrv_hop, device=DEV))
+        evi = evaluate_intervals(sd, rec, noise, snrs, offsets=offsets) if args.intervals else None
         for i, snr in enumerate(TRUE_NOISE):
             idx = torch.arange(i * args.records, (i + 1) * args.records, device=DEV)
             a, b = _subset(sc, idx, sd.L), _subset(sw, idx, sd.L)
@@ -185,6 +198,12 @@ def grid(args, model, name):
                                  f"log(lf/hf) {d['log_lf_hf']:.3f}")
                 lines.append(f"{name}_0_{kind}_intensity{snr}:hrv: mean absolute error over {hc['windows']['hr']} windows, "
                              f"noisy {col(hc['noisy'])}, denoised {col(hc['denoised'])}\n")
+            if evi is not None:
+                ic = _intervals_cell(evi, idx)
+                cells[-1]["intervals"] = ic
+                col = lambda d: (f"qrs {d['qrs_share']:.4f} of the clean beats, error {d['qrs_mae_ms']:.2f} ms over {d['qrs_beats']}; "
+                                 f"qt {d['qt_share']:.4f}, error {d['qt_mae_ms']:.2f} ms over {d['qt_beats']}")
+                lines.append(f"{name}_0_{kind}_intensity{snr}:intervals: noisy {col(ic['noisy'])}, denoised {col(ic['denoised'])}\n")
     return cells, lines
 
 
@@ -246,6 +265,7 @@ def main():
     ap.add_argument("--fft", action="store_true", help="add the FFT-threshold baseline (the model 'fft') beside the wavelet one")
     ap.add_argument("--fft-L", type=int, default=1000)
     ap.add_argument("--hrv", action="store_true", help="add the errors of heart rate, SDNN, RMSSD and log(LF/HF), noisy and denoised")
+    ap.add_argument("--intervals", action="store_true", help="add the shares and errors of QRS duration and QT, noisy and denoised")
     ap.add_argument("--hrv-win", type=int, default=60)
     ap.add_argument("--hrv-hop", type=int, default=30)
     args = ap.parse_args()
