@@ -33,15 +33,16 @@ rounding residue is its "signal"); a floor, in units of m (squared filtered ampl
 on synthetic data (`synth`) only; none has been tuned on MIT-BIH.
 
 Device tensors only: there is no CPU fallback."""
-import numbers
 from fractions import Fraction
 
 import numpy as np
 import torch
 
 from . import _lib
+from .evaluate import stress_front
+from .intake import Beats, beat_lists, check_leads, device_records, record_shape
 from .model import _ptr, _stream
-from .pools import SlotState, StreamSurface, as_chunks, pack_chunks
+from .pools import SlotState, StreamSurface, as_chunks, pack_chunks, scratch_bytes, table_buffer
 from .rate import _rate
 
 MODEL_RATE = 360
@@ -94,8 +95,7 @@ def beat_latency(fs=MODEL_RATE):
 def beat_check(fs, leads):
     """raise RalError unless the detector's spans for `leads` leads at rate `fs` fit the kernels' LDS budget -> the geometry"""
     g = beat_geometry(fs)
-    if isinstance(leads, bool) or not isinstance(leads, numbers.Integral) or leads < 1:
-        raise _lib.RalError(f"beat detection: leads must be >= 1 (got {leads!r})")
+    check_leads(leads, "beat detection")
     nt4 = (2 * g["half"] + 1 + 3) // 4 * 4
     ok = 1 <= g["half"] <= 8192 and 1 <= g["Rf"] <= g["Wt"] and 2 * g["Rw"] <= g["Rf"] and g["Rw"] <= g["Wt"] + g["Wi"]
     ok = ok and 3 * (_PICK + 2 * g["Wt"]) + _THREADS <= _LDS_FLOATS
@@ -107,26 +107,6 @@ def beat_check(fs, leads):
                             f"span of all leads of one tile and the threshold window ({2 * g['Wt'] + 1} samples) do not fit the "
                             f"kernels' {_LDS_FLOATS * 4 // 1024} KB of LDS")
     return g
-
-
-class Beats:
-    """What `BeatDetector.detect` returns: `peaks` (R, cap) int32, each row the record's R-peak sample indices in ascending
-    order padded with -1, and `count` (R,) int32, both on the device; `fs` is the rate the indices refer to."""
-
-    def __init__(self, peaks, count, fs=MODEL_RATE):
-        self.peaks, self.count, self.fs = peaks, count, fs
-
-    def __len__(self):
-        return self.peaks.shape[0]
-
-    def tolist(self):
-        """-> [[peak indices of record r] for r] as plain ints (synchronises)"""
-        return [row[:n] for row, n in zip(self.peaks.tolist(), self.count.tolist())]
-
-    def rr_seconds(self):
-        """-> per record the RR intervals in seconds, a float64 numpy array of count - 1 values (synchronises)"""
-        fs = float(Fraction(self.fs))
-        return [np.diff(np.asarray(p, dtype=np.float64)) / fs for p in self.tolist()]
 
 
 class _Detector:
@@ -164,20 +144,14 @@ class BeatDetector:
 
     @torch.no_grad()
     def detect(self, records):
-        if not (torch.is_tensor(records) and records.is_cuda):
-            raise _lib.RalError("BeatDetector.detect runs on the GPU: pass a device tensor (there is no CPU fallback)")
-        if records.dim() not in (2, 3) or records.shape[-1] < 1 or records.shape[-2] < 1 or records.shape[0] < 1:
-            raise _lib.RalError(f"BeatDetector.detect: expected (leads, T) or (R, leads, T) with T >= 1, got {tuple(records.shape)}")
-        x = records.to(torch.float32).contiguous()
-        R, leads, T = (1,) + tuple(x.shape) if x.dim() == 2 else tuple(x.shape)
+        R, leads, T = record_shape(records, "BeatDetector.detect")
         beat_check(self.fs, leads)
+        x = device_records(records, "BeatDetector.detect")
         d, lib, cap = self.det, _lib.lib(), self.cap(T)
         d.device = x.device if d.bank is None else d.device
         if x.device != d.device:
             raise _lib.RalError(f"BeatDetector.detect: the records are on {x.device}, the detector's bank on {d.device}")
-        nbytes = lib.ral_beat_records_scratch_bytes(R, leads, T, d.geom)
-        if nbytes < 0:
-            raise _lib.RalError(lib.ral_last_error().decode())
+        nbytes = scratch_bytes(lib.ral_beat_records_scratch_bytes(R, leads, T, d.geom))
         with torch.cuda.device(x.device):
             scratch = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=x.device)
             peaks = torch.empty(R, cap, dtype=torch.int32, device=x.device)
@@ -260,14 +234,12 @@ class BeatPool(StreamSurface):
         {sid: peaks}; commits the plan"""
         dev, leads, d, lib = self.device, self.leads, self.det, _lib.lib()
         peaks_total = int(tab["cap"].sum())
-        nbytes = lib.ral_beat_records_scratch_bytes(len(tab), leads, self.state.span(tab), d.geom)
-        if nbytes < 0:
-            raise _lib.RalError(lib.ral_last_error().decode())
+        nbytes = scratch_bytes(lib.ral_beat_records_scratch_bytes(len(tab), leads, self.state.span(tab), d.geom))
         with torch.cuda.device(dev):
             scratch = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=dev)
             peaks = torch.empty(max(peaks_total, 1), dtype=torch.int64, device=dev)
             count = torch.empty(len(tab), dtype=torch.int32, device=dev)
-            tab_dev = torch.empty(len(tab) * tab.itemsize, dtype=torch.uint8, device=dev)
+            tab_dev = table_buffer(tab, dev)
             _lib.check(lib.ral_beat_pool(_ptr(self.hist), _ptr(xp), x_total, tab.ctypes.data, len(tab), _ptr(tab_dev), 1,
                                          self.capacity, leads, d.geom, _ptr(d.bank), d.bank_host.size, self.hist_len,
                                          _ptr(scratch), scratch.numel() * 8, _ptr(peaks), peaks_total, _ptr(count), _stream()))
@@ -300,21 +272,6 @@ class BeatScores:
         return {"tp": tp, "fp": fp, "fn": fn, "sensitivity": se, "ppv": pp, "f1": f1}
 
 
-def _beat_lists(b, device, what):
-    """`Beats`, or one ascending list of sample indices per record -> ((R, cap) int32, (R,) int32) on the device"""
-    if isinstance(b, Beats):
-        return b.peaks.contiguous(), b.count.contiguous()
-    rows = [np.asarray(r.cpu() if torch.is_tensor(r) else r, dtype=np.int64).reshape(-1) for r in b]
-    if not rows:
-        raise _lib.RalError(f"match_beats: {what} holds no record")
-    if any(len(r) and (r.min() < 0 or r.max() > 0x7fffffff or np.any(np.diff(r) < 0)) for r in rows):
-        raise _lib.RalError(f"match_beats: {what} must hold ascending sample indices in [0, 2^31)")
-    pad = np.full((len(rows), max(1, max(len(r) for r in rows))), -1, dtype=np.int32)
-    for i, r in enumerate(rows):
-        pad[i, :len(r)] = r
-    return torch.from_numpy(pad).to(device), torch.tensor([len(r) for r in rows], dtype=torch.int32, device=device)
-
-
 def match_beats(ref, det, tol_s=AAMI_TOL_S, fs=MODEL_RATE, device=None):
     """`ref` and `det`: `Beats`, or per record one ascending list (or tensor) of sample indices -> `BeatScores` (`ral_beat_match`).
     Per record the two lists are walked together: ref[i] and det[j] match iff |det - ref| <= tol = floor(tol_s fs) samples,
@@ -326,7 +283,7 @@ def match_beats(ref, det, tol_s=AAMI_TOL_S, fs=MODEL_RATE, device=None):
     tol = int((Fraction(str(tol_s)) * _rate(fs, "fs")).__floor__())
     if tol < 0:
         raise _lib.RalError(f"match_beats: tol_s must be >= 0 (got {tol_s!r})")
-    (rp, rc), (dp, dc) = _beat_lists(ref, dev, "ref"), _beat_lists(det, dev, "det")
+    (rp, rc), (dp, dc) = (beat_lists(b, dev, "match_beats", strict=False, name=n) for b, n in ((ref, "ref"), (det, "det")))
     if rp.shape[0] != dp.shape[0] or rp.device != dp.device:
         raise _lib.RalError(f"match_beats: ref has {rp.shape[0]} records on {rp.device}, det {dp.shape[0]} on {dp.device}")
     with torch.cuda.device(dev):
@@ -350,11 +307,8 @@ def evaluate_beats(denoiser, records, noise, snr_db, ref=None, offsets=None, rng
     lists; default: the detections on the clean records) -> `BeatEvaluation`.  `denoiser` is a `StreamingDenoiser` or a
     `RateStreamingDenoiser`; the detector (default `BeatDetector(fs)`) runs at that object's outer rate `fs`, 360 Hz for a
     `StreamingDenoiser`."""
-    from .evaluate import mix_records
-    fs = getattr(denoiser, "fs", MODEL_RATE)
-    det = detector or BeatDetector(fs, device=records.device if torch.is_tensor(records) else "cuda")
-    noisy, clean = mix_records(records, noise, snr_db, offsets, rng)
-    out = denoiser.denoise(noisy)
+    fs, dev, clean, noisy, out = stress_front(denoiser, records, noise, snr_db, offsets, rng)
+    det = detector or BeatDetector(fs, device=dev)
     ref = det.detect(clean) if ref is None else ref
     b_noisy, b_out = det.detect(noisy), det.detect(out)
     return BeatEvaluation(match_beats(ref, b_noisy, tol_s, fs), match_beats(ref, b_out, tol_s, fs), ref, b_noisy, b_out)

@@ -39,16 +39,15 @@ Non-finite samples are out of scope, as for the detector.  The defaults were cho
 been tuned on a database.
 
 Device tensors only: there is no CPU fallback."""
-import numbers
-
 import numpy as np
 import torch
 
 from . import _lib
 from .beats import MODEL_RATE, BeatDetector, Beats, _round
+from .evaluate import stress_front
+from .intake import beat_lists, check_leads, device_records, record_shape
 from .model import _ptr, _stream
 from .rate import _rate
-from .rhythm import _positions
 
 # the LDS budget of ral_delineate.hip (delin_geom there): a wave keeps d over [lo - g - m, hi + g + m], a over [lo - g, hi + g]
 # and s over [t0, lim]
@@ -69,8 +68,7 @@ def _lds_bytes(g):
 def delineate_check(fs, leads):
     """raise RalError unless the delineator's windows at rate `fs` fit the kernel's LDS budget -> the geometry"""
     g = delineate_geometry(fs)
-    if isinstance(leads, bool) or not isinstance(leads, numbers.Integral) or not 1 <= leads <= 65535:
-        raise _lib.RalError(f"beat delineation: leads must be in [1, 65535] (got {leads!r})")
+    check_leads(leads, "beat delineation", 65535)
     if g["Wq"] < 1 or g["g"] < 1 or g["Wt"] < 1 or _lds_bytes(g) > _LDS_BYTES:
         raise _lib.RalError(f"beat delineation at fs={fs} is not supported: the windows of one beat "
                             f"({2 * (g['Wq'] + g['g'] + g['m']) + 1}, {2 * (g['Wq'] + g['g']) + 1} and {g['Wt'] + 1} samples) "
@@ -146,16 +144,10 @@ class BeatDelineator:
     @torch.no_grad()
     def delineate(self, records, beats):
         what = "BeatDelineator.delineate"
-        if not torch.is_tensor(records):
-            raise _lib.RalError(f"{what} runs on the GPU: pass a device tensor (there is no CPU fallback)")
-        if records.dim() not in (2, 3) or records.shape[-1] < 1 or records.shape[-2] < 1 or records.shape[0] < 1:
-            raise _lib.RalError(f"{what}: expected (leads, T) or (R, leads, T) with T >= 1, got {tuple(records.shape)}")
-        R, leads, T = (1,) + tuple(records.shape) if records.dim() == 2 else tuple(records.shape)
+        R, leads, T = record_shape(records, what)
         delineate_check(self.fs, leads)
-        peaks, count = _positions(beats, R, T, records.device, what)       # (the lists are checked on the host)
-        if not records.is_cuda:
-            raise _lib.RalError(f"{what} runs on the GPU: pass a device tensor (there is no CPU fallback)")
-        x = records.to(torch.float32).contiguous()
+        peaks, count = beat_lists(beats, records.device, what, T=T, R=R)       # (the lists are checked on the host)
+        x = device_records(records, what)
         cap = peaks.shape[1]
         with torch.cuda.device(x.device):
             on, off, tpeak, tend = (torch.empty(R, cap, dtype=torch.int32, device=x.device) for _ in range(4))
@@ -206,12 +198,8 @@ def evaluate_intervals(denoiser, records, noise, snr_db, ref=None, offsets=None,
     beats measurable in both, are taken -> `IntervalEvaluation`.  `denoiser` is a `StreamingDenoiser`, a `RateStreamingDenoiser`
     or a `ClassicalDenoiser`; delineator and detector (defaults `BeatDelineator(fs)`, `BeatDetector(fs)`) run at that object's
     outer rate `fs`, 360 Hz where it names none."""
-    from .evaluate import mix_records
-    fs = getattr(denoiser, "fs", MODEL_RATE)
-    dev = records.device if torch.is_tensor(records) else "cuda"
+    fs, dev, clean, noisy, out = stress_front(denoiser, records, noise, snr_db, offsets, rng)
     dl = delineator or BeatDelineator(fs, device=dev)
-    noisy, clean = mix_records(records, noise, snr_db, offsets, rng)
-    out = denoiser.denoise(noisy)
     if ref is None:
         ref = (detector or BeatDetector(fs, device=dev)).detect(clean)
     f_clean = dl.delineate(clean, ref)

@@ -18,6 +18,7 @@ import torch
 
 from . import _lib
 from .model import _ptr, _stream
+from .pools import scratch_bytes
 
 COLUMNS = ("snr_in_db", "snr_out_db", "rmse_in", "rmse_out")
 
@@ -51,15 +52,22 @@ def mix_records(records, noise, snr_db, offsets=None, rng=None):
     if snr.shape != (R,) or off.shape != (R,):
         raise _lib.RalError(f"snr_db must be a scalar or {R} values and offsets {R} values (one per record)")
     lib = _lib.lib()
-    nbytes = lib.ral_mix_records_scratch_bytes(R, leads, T)
-    if nbytes < 0:
-        raise _lib.RalError(lib.ral_last_error().decode())
+    nbytes = scratch_bytes(lib.ral_mix_records_scratch_bytes(R, leads, T))
     with torch.cuda.device(rec.device):
         scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=rec.device)
         noisy, clean = torch.empty_like(rec), torch.empty_like(rec)
         _lib.check(lib.ral_mix_records(_ptr(rec), _ptr(noi), R, leads, T, Tn, off.ctypes.data, snr.ctypes.data, _ptr(scratch),
                                        _ptr(noisy), _ptr(clean), _stream()))
     return noisy, clean
+
+
+def stress_front(denoiser, records, noise, snr_db, offsets=None, rng=None):
+    """the front of every noise-stress evaluation of a downstream statistic (`evaluate_beats`, `evaluate_rhythm`,
+    `evaluate_intervals`, `evaluate_hrv`): `mix_records(records, noise, snr_db, offsets, rng)`, then `denoiser.denoise(noisy)` ->
+    (fs, device, clean, noisy, denoised); `fs` is the denoiser's outer rate, 360 Hz where it names none, `device` that of the
+    records, where the caller's default detector, classifier and so on belong"""
+    noisy, clean = mix_records(records, noise, snr_db, offsets, rng)            # (refuses anything but device tensors)
+    return getattr(denoiser, "fs", 360), records.device, clean, noisy, denoiser.denoise(noisy)
 
 
 class RecordScores:
@@ -106,9 +114,7 @@ def score_records(clean, out, noisy=None, window=256):
     R, leads, T = c.shape
     W = int(window)
     lib = _lib.lib()
-    nbytes = lib.ral_score_records_scratch_bytes(R, leads, T, W)
-    if nbytes < 0:
-        raise _lib.RalError(lib.ral_last_error().decode())
+    nbytes = scratch_bytes(lib.ral_score_records_scratch_bytes(R, leads, T, W))
     with torch.cuda.device(c.device):
         e = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=c.device)
         scratch = e(nbytes // 8)

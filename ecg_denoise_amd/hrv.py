@@ -46,9 +46,11 @@ import numpy as np
 import torch
 
 from . import _lib
-from .beats import MODEL_RATE, BeatDetector, Beats, _round
+from .beats import MODEL_RATE, BeatDetector, _round
+from .evaluate import stress_front
+from .intake import beat_lists, pad_rows
 from .model import _ptr, _stream
-from .pools import StreamSurface, as_chunks
+from .pools import StreamSurface, as_chunks, pack_chunks, table_buffer
 from .rate import _rate
 from .rhythm import BeatClasses, BeatClassifier, BeatClassPool
 
@@ -156,33 +158,12 @@ class _Engine:
             stats = torch.empty(N, 10, dtype=torch.float32, device=dev)
             out = torch.empty(N, g["F"], dtype=torch.float32, device=dev) if psd else None
             if N:
-                tab_dev = torch.empty(N * tab.itemsize, dtype=torch.uint8, device=dev)
+                tab_dev = table_buffer(tab, dev)
                 _lib.check(_lib.lib().ral_hrv_windows(_ptr(pos), None if label is None else _ptr(label), _ptr(count), pos.shape[0],
                                                       pos.shape[1], tab.ctypes.data, N, _ptr(tab_dev), 1, self.geom,
                                                       _ptr(self.band), _ptr(counts), _ptr(stats), None if out is None else _ptr(out),
                                                       _stream()))
         return HrvWindows(counts, stats, out, np.asarray(index, dtype=np.int64).reshape(N, 2), g)
-
-
-def _pad(rows, fill):
-    pad = np.full((len(rows), max(1, max(len(r) for r in rows))), fill, dtype=np.int32)
-    for i, r in enumerate(rows):
-        pad[i, :len(r)] = r
-    return pad
-
-
-def _positions(beats, T, device):
-    """`Beats` (trusted), or one strictly ascending list of positions in [0, T) per record (checked) -> ((R, cap) int32, (R,)
-    int32) on the device"""
-    if isinstance(beats, Beats):
-        return beats.peaks.contiguous(), beats.count.contiguous()
-    rows = [np.asarray(r.cpu() if torch.is_tensor(r) else r, dtype=np.int64).reshape(-1) for r in beats]
-    if not rows:
-        raise _lib.RalError("HrvAnalyzer.analyse: no record")
-    for r in rows:
-        if len(r) and (r[0] < 0 or r[-1] >= T or np.any(np.diff(r) <= 0)):
-            raise _lib.RalError(f"HrvAnalyzer.analyse: the beats of a record must be strictly ascending positions in [0, {T})")
-    return torch.from_numpy(_pad(rows, -1)).to(device), torch.tensor([len(r) for r in rows], dtype=torch.int32, device=device)
 
 
 def _labels(classes, pos, count):
@@ -198,10 +179,7 @@ def _labels(classes, pos, count):
     rows = [np.asarray(r.cpu() if torch.is_tensor(r) else r, dtype=np.int64).reshape(-1) for r in classes]
     if len(rows) != pos.shape[0] or [len(r) for r in rows] != count.tolist():
         raise _lib.RalError("HrvAnalyzer.analyse: one label per beat of every record")
-    lab = np.full(tuple(pos.shape), -1, dtype=np.int32)
-    for i, r in enumerate(rows):
-        lab[i, :len(r)] = r
-    return torch.from_numpy(lab).to(pos.device)
+    return torch.from_numpy(pad_rows(rows, -1, shape=tuple(pos.shape))).to(pos.device)
 
 
 class HrvAnalyzer:
@@ -219,7 +197,7 @@ class HrvAnalyzer:
     def analyse(self, beats, T, classes=None, psd=False):
         if isinstance(T, bool) or not isinstance(T, numbers.Integral) or not 1 <= T < 2 ** 31:
             raise _lib.RalError(f"HrvAnalyzer.analyse: T must be in [1, 2^31) (got {T!r})")
-        pos, count = _positions(beats, int(T), self.device)
+        pos, count = beat_lists(beats, self.device, "HrvAnalyzer.analyse", T=int(T))
         label = _labels(classes, pos, count)
         win = hrv_windows(T, self.geometry)
         R, nw = pos.shape[0], len(win)
@@ -301,8 +279,8 @@ class HrvPool(StreamSurface):
     `push(chunks, close=())` takes {sid: (leads, c)} (c >= 0, host or device) for any subset of the open streams, ends the streams
     listed in `close`, and returns {sid: HrvWindows} for every sid named: the windows that became final with this call, possibly
     none (`index` holds the sid and the window's number).  A window is final once a beat at or beyond its end has been released
-    (the classifier holds the first eight beats of a stream until the ninth), or when the stream closes.  A push runs the
-    `BeatClassPool` (which synchronises), copies the new (position, label) pairs to the host, plans the final windows
+    (the classifier holds the first eight beats of a stream until the ninth), or when the stream closes.  A push plans once, runs
+    the `BeatClassPool` (its `run`, which synchronises), copies the new (position, label) pairs to the host, plans the final windows
     (`HrvPoolState`), uploads each affected stream's kept beats as one row - int32 positions relative to the origin of the first
     window the call emits for it - and calls `ral_hrv_windows` once.  Concatenated per stream from `open` to `close`, the windows
     equal those of `HrvAnalyzer.analyse(BeatDetector.detect(record), T, BeatClassifier.classify(record, beats))` bit for bit,
@@ -331,7 +309,8 @@ class HrvPool(StreamSurface):
         xs = as_chunks(chunks)
         sids, btab = self.classes.state.plan({sid: tuple(x.shape) for sid, x in xs.items()}, close)      # (raises before anything changes)
         ends = {sid: int(n0 + c) for sid, n0, c, T in zip(sids, btab["n0"], btab["c"], btab["T"]) if T >= 0}
-        res = self.classes.push(xs, close)
+        xp, x_total, _ = pack_chunks(xs, self.leads, self.device)
+        res = self.classes.run(xp, x_total, sids, btab)                # (its `run`, never its `push`: the call is planned once)
         n = [res[sid][0].numel() for sid in sids]
         if sum(n):
             p = torch.cat([res[sid][0] for sid in sids]).cpu().numpy()
@@ -357,8 +336,8 @@ class HrvPool(StreamSurface):
             index += [(sid, w_first + i) for i in range(len(w))]
         if rows:
             dev = self.device
-            pos_d = torch.from_numpy(_pad(rows, -1)).to(dev)
-            lab_d = torch.from_numpy(_pad(labs, -1)).to(dev)
+            pos_d = torch.from_numpy(pad_rows(rows, -1)).to(dev)
+            lab_d = torch.from_numpy(pad_rows(labs, -1)).to(dev)
             cnt_d = torch.tensor([len(r) for r in rows], dtype=torch.int32, device=dev)
             allw = self.engine.run(pos_d, lab_d, cnt_d, np.asarray(rec, dtype=np.int64), np.concatenate(win), index, False)
         else:
@@ -396,13 +375,9 @@ def evaluate_hrv(denoiser, records, noise, snr_db, offsets=None, rng=None, detec
     windows where all three values are finite -> `HrvEvaluation`.  `denoiser` is a `StreamingDenoiser` or a
     `RateStreamingDenoiser`; detector, classifier and analyzer (defaults `BeatDetector(fs)`, `BeatClassifier(fs)`,
     `HrvAnalyzer(fs)`) run at that object's outer rate `fs`."""
-    from .evaluate import mix_records
-    fs = getattr(denoiser, "fs", MODEL_RATE)
-    dev = records.device if torch.is_tensor(records) else "cuda"
+    fs, dev, clean, noisy, out = stress_front(denoiser, records, noise, snr_db, offsets, rng)
     det, cls = detector or BeatDetector(fs, device=dev), classifier or BeatClassifier(fs, device=dev)
     ana = analyzer or HrvAnalyzer(fs, device=dev)
-    noisy, clean = mix_records(records, noise, snr_db, offsets, rng)
-    out = denoiser.denoise(noisy)
     hs = []
     for x in (clean, noisy, out):
         beats = det.detect(x)

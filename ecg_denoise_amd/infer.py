@@ -20,7 +20,7 @@ import torch
 
 from . import _lib
 from .model import NewRALE, _ptr, _stream
-from .pools import SlotState, StreamSurface, as_chunks, pack_chunks
+from .pools import SlotState, StreamSurface, as_chunks, pack_chunks, table_buffer
 
 
 class GraphedForward:
@@ -537,7 +537,7 @@ class _PoolBase(StreamSurface):
             self.y = torch.zeros_like(self.win)
         if self.stats is None or self.stats.numel() < total * leads * 2:
             self.stats = torch.zeros(max(total, 1) * leads * 2, dtype=torch.float32, device=dev)
-        tab_dev = torch.empty(R * tab.itemsize, dtype=torch.uint8, device=dev)
+        tab_dev = table_buffer(tab, dev)
         geom = (self.capacity, leads, self.L, self.hop)
         keep_any, first = bool((tab["flags"] & _lib.POOL_KEEP).any()), True
         for w0 in range(0, max(total, 1), self.win.shape[0]):
@@ -552,7 +552,7 @@ class _PoolBase(StreamSurface):
             _lib.check(lib.ral_forward(self.eng.h, _ptr(self.win), _ptr(self.y), nb, 0, _stream()))
             self._emit(lib, self.y, self.stats, tab, tab_dev, False, geom, w0, nb, False, out, out_total, True)
         if len(last):
-            last_dev = torch.empty(len(last) * last.itemsize, dtype=torch.uint8, device=dev)
+            last_dev = table_buffer(last, dev)
             self._emit(lib, self.last_y, self.last_stats, last, last_dev, True, geom, 0, len(last), True, out, out_total, False)
         self.state.commit(tab)
         self.windows_run += total

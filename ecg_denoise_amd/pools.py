@@ -6,6 +6,8 @@ planned and checked before any device work.
                    common commit (`commit_rows`)
     as_chunks      a call's chunks as tensors
     pack_chunks    a call's chunks in one device buffer, row r's (leads, c) at x_off * leads
+    table_buffer   the device buffer for a call's table
+    scratch_bytes  the size a `ral_*_scratch_bytes` call returned, or the library's last error
     StreamSurface  `open_streams`, `open`, `samples_in`, `close` for a class with a `.state` and a `push`
 
 A pool's own state class derives from `SlotState` and adds its geometry checks, its refusals, its table and what is special in
@@ -123,6 +125,18 @@ def pack_chunks(xs, leads, device):
         views[sid] = xp[o:o + x.numel()].view(leads, x.numel() // leads)
         o += x.numel()
     return xp, x_total, views
+
+
+def table_buffer(tab, device):
+    """the device buffer a library call uploads the table `tab` into"""
+    return torch.empty(len(tab) * tab.itemsize, dtype=torch.uint8, device=device)
+
+
+def scratch_bytes(nbytes):
+    """what a `ral_*_scratch_bytes` call returned -> that size; RalError with the library's own message if it refused (< 0)"""
+    if nbytes < 0:
+        raise _lib.RalError(_lib.lib().ral_last_error().decode())
+    return nbytes
 
 
 class StreamSurface:

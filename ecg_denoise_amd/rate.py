@@ -33,7 +33,7 @@ import torch
 from . import _lib
 from .infer import LivePool, NewRALELivePool, StreamingDenoiser
 from .model import NewRALE, _ptr, _stream
-from .pools import SlotState, StreamSurface, as_chunks, pack_chunks
+from .pools import SlotState, StreamSurface, as_chunks, pack_chunks, table_buffer
 
 MODEL_RATE = 360
 
@@ -237,7 +237,7 @@ class ResamplerPool(StreamSurface):
         with torch.cuda.device(dev):
             xp, x_total, _ = pack_chunks(xs, leads, dev)
             out = torch.empty(max(out_total, 1) * leads, dtype=torch.float32, device=dev)
-            tab_dev = torch.empty(len(tab) * tab.itemsize, dtype=torch.uint8, device=dev)
+            tab_dev = table_buffer(tab, dev)
             _lib.check(_lib.lib().ral_rate_pool(_ptr(self.hist), _ptr(xp), x_total, tab.ctypes.data, len(tab), _ptr(tab_dev), 1,
                                                 self.capacity, leads, self.up, self.down, _ptr(self.bank), self.bank.numel(),
                                                 self.hist_len, _ptr(out), out_total, _stream()))

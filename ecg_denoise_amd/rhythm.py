@@ -35,15 +35,15 @@ Non-finite samples are out of scope, as for the detector.  The defaults were cho
 been tuned on MIT-BIH.
 
 Device tensors only: there is no CPU fallback."""
-import numbers
-
 import numpy as np
 import torch
 
 from . import _lib, scoring
 from .beats import MODEL_RATE, BeatDetector, BeatPool, BeatPoolState, Beats, _lag, _round
+from .evaluate import stress_front
+from .intake import beat_lists, check_leads, device_records, pad_rows, record_shape
 from .model import _ptr, _stream
-from .pools import StreamSurface, as_chunks, pack_chunks
+from .pools import StreamSurface, as_chunks, pack_chunks, scratch_bytes, table_buffer
 from .rate import _rate
 
 K, MIN_REF = _lib.RHYTHM_K, _lib.RHYTHM_MIN_REF
@@ -66,8 +66,7 @@ def _lds_bytes(g):
 def rhythm_check(fs, leads):
     """raise RalError unless the classifier's windows at rate `fs` fit the kernel's LDS budget -> the geometry"""
     g = rhythm_geometry(fs)
-    if isinstance(leads, bool) or not isinstance(leads, numbers.Integral) or not 1 <= leads <= 65535:
-        raise _lib.RalError(f"beat classes: leads must be in [1, 65535] (got {leads!r})")
+    check_leads(leads, "beat classes", 65535)
     if g["Wb"] < 1 or 2 * g["Sa"] + 1 > _NS_MAX or _lds_bytes(g) > _LDS_BYTES:
         raise _lib.RalError(f"beat classes at fs={fs} are not supported: the windows of {K} neighbours of one lead "
                             f"({2 * g['Wb'] + 1} samples each) and {2 * g['Sa'] + 1} shifts do not fit the kernel's "
@@ -122,26 +121,6 @@ def _geom(g, c0, r0, what):
     return _lib.RhythmGeom(g["Wb"], g["Sa"], c0, r0)
 
 
-def _positions(beats, R, T, device, what="BeatClassifier.classify"):
-    """`Beats`, or one strictly ascending list of positions in [0, T) per record -> ((R, cap) int32, (R,) int32) on the device;
-    `what` names the caller in the error messages"""
-    if isinstance(beats, Beats):
-        if beats.peaks.shape[0] != R or beats.peaks.device != device:
-            raise _lib.RalError(f"{what}: {beats.peaks.shape[0]} beat lists on {beats.peaks.device} for {R} "
-                                f"records on {device}")
-        return beats.peaks.contiguous(), beats.count.contiguous()
-    rows = [np.asarray(r.cpu() if torch.is_tensor(r) else r, dtype=np.int64).reshape(-1) for r in beats]
-    if len(rows) != R:
-        raise _lib.RalError(f"{what}: {len(rows)} beat lists for {R} records")
-    for r in rows:
-        if len(r) and (r[0] < 0 or r[-1] >= T or np.any(np.diff(r) <= 0)):
-            raise _lib.RalError(f"{what}: the beats of a record must be strictly ascending positions in [0, {T})")
-    pad = np.full((R, max(1, max(len(r) for r in rows))), -1, dtype=np.int32)
-    for i, r in enumerate(rows):
-        pad[i, :len(r)] = r
-    return torch.from_numpy(pad).to(device), torch.tensor([len(r) for r in rows], dtype=torch.int32, device=device)
-
-
 class BeatClassifier:
     """Beat classes of whole records at rate `fs` (`ral_rhythm_records`).  `classify(records, beats)` takes a device tensor
     (leads, T) or (R, leads, T) and the beats of every record - a `Beats`, or per-record lists of strictly ascending positions in
@@ -154,14 +133,11 @@ class BeatClassifier:
 
     @torch.no_grad()
     def classify(self, records, beats):
-        if not (torch.is_tensor(records) and records.is_cuda):
-            raise _lib.RalError("BeatClassifier.classify runs on the GPU: pass a device tensor (there is no CPU fallback)")
-        if records.dim() not in (2, 3) or records.shape[-1] < 1 or records.shape[-2] < 1 or records.shape[0] < 1:
-            raise _lib.RalError(f"BeatClassifier.classify: expected (leads, T) or (R, leads, T) with T >= 1, got {tuple(records.shape)}")
-        x = records.to(torch.float32).contiguous()
-        R, leads, T = (1,) + tuple(x.shape) if x.dim() == 2 else tuple(x.shape)
+        what = "BeatClassifier.classify"
+        R, leads, T = record_shape(records, what)
         rhythm_check(self.fs, leads)
-        peaks, count = _positions(beats, R, T, x.device)
+        peaks, count = beat_lists(beats, records.device, what, T=T, R=R)       # (the lists are checked on the host)
+        x = device_records(records, what)
         cap = peaks.shape[1]
         with torch.cuda.device(x.device):
             label = torch.empty(R, cap, dtype=torch.int32, device=x.device)
@@ -256,25 +232,27 @@ class BeatClassPool(StreamSurface):
 
     @torch.no_grad()
     def push(self, chunks, close=()):
-        close = tuple(close)
         xs = as_chunks(chunks)
-        sids, btab = self.state.plan({sid: tuple(x.shape) for sid, x in xs.items()}, close)      # (raises before anything changes)
+        sids, btab = self.state.plan({sid: tuple(x.shape) for sid, x in xs.items()}, tuple(close))      # (raises before anything changes)
+        xp, x_total, _ = pack_chunks(xs, self.leads, self.device)
+        return self.run(xp, x_total, sids, btab)
+
+    def run(self, xp, x_total, sids, btab):
+        """carry out a planned call: xp, x_total the chunks as `pack_chunks` packs them, sids and btab as planned ->
+        {sid: (peaks, label, corr, rr_ratio)}; commits the plan"""
         dev, leads, lib = self.device, self.leads, _lib.lib()
         with torch.cuda.device(dev):
-            xp, x_total, _ = pack_chunks(xs, leads, dev)
             new = self.beats.run(xp, x_total, sids, btab)      # the detector and the classifier read the same buffer
             tab = self.state.table(btab, [new[sid].numel() for sid in sids])
             new_total, out_total = int(tab["m"].sum()), int(tab["ne"].sum())
             new_pos = torch.cat([new[sid] for sid in sids]) if new_total else torch.zeros(1, dtype=torch.int64, device=dev)
-            nbytes = lib.ral_rhythm_pool_scratch_bytes(new_total, leads, self.geom)
-            if nbytes < 0:
-                raise _lib.RalError(lib.ral_last_error().decode())
+            nbytes = scratch_bytes(lib.ral_rhythm_pool_scratch_bytes(new_total, leads, self.geom))
             scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
             out_pos = torch.empty(max(out_total, 1), dtype=torch.int64, device=dev)
             label = torch.empty(max(out_total, 1), dtype=torch.int32, device=dev)
             corr = torch.empty(max(out_total, 1), dtype=torch.float32, device=dev)
             rr = torch.empty(max(out_total, 1), dtype=torch.float32, device=dev)
-            tab_dev = torch.empty(len(tab) * tab.itemsize, dtype=torch.uint8, device=dev)
+            tab_dev = table_buffer(tab, dev)
             _lib.check(lib.ral_rhythm_pool(_ptr(self.beats.hist), _ptr(xp), x_total, tab.ctypes.data, len(tab), _ptr(tab_dev), 1,
                                            self.capacity, leads, self.geom, self.beats.hist_len, _ptr(self.ring),
                                            _ptr(self.ring_pos), _ptr(new_pos), new_total, _ptr(scratch), scratch.numel() * 4,
@@ -315,12 +293,8 @@ def evaluate_rhythm(denoiser, records, noise, snr_db, ref=None, ref_labels=None,
     labels), over the beats classified in all three -> `RhythmEvaluation`.  `denoiser` is a `StreamingDenoiser` or a
     `RateStreamingDenoiser`; detector and classifier (defaults `BeatDetector(fs)`, `BeatClassifier(fs)`) run at that object's
     outer rate `fs`."""
-    from .evaluate import mix_records
-    fs = getattr(denoiser, "fs", MODEL_RATE)
-    dev = records.device if torch.is_tensor(records) else "cuda"
+    fs, dev, clean, noisy, out = stress_front(denoiser, records, noise, snr_db, offsets, rng)
     cls = classifier or BeatClassifier(fs, device=dev)
-    noisy, clean = mix_records(records, noise, snr_db, offsets, rng)
-    out = denoiser.denoise(noisy)
     if ref is None:
         ref = (detector or BeatDetector(fs, device=dev)).detect(clean)
     c_clean = cls.classify(clean, ref)
@@ -332,10 +306,7 @@ def evaluate_rhythm(denoiser, records, noise, snr_db, ref=None, ref_labels=None,
     elif torch.is_tensor(ref_labels):
         lab = ref_labels.to(mask.device)
     else:
-        lab = torch.zeros(mask.shape, dtype=torch.int64)
-        for r, row in enumerate(ref_labels):
-            lab[r, :len(row)] = torch.as_tensor(row, dtype=torch.int64)
-        lab = lab.to(mask.device)
+        lab = torch.from_numpy(pad_rows(ref_labels, 0, np.int64, tuple(mask.shape))).to(mask.device)
     if lab.shape != mask.shape:
         raise _lib.RalError(f"evaluate_rhythm: ref_labels of shape {tuple(lab.shape)} for beats of shape {tuple(mask.shape)}")
     truth = (lab[mask] == 1).long()

@@ -127,12 +127,38 @@ def test_host_refusals_need_no_device():
     for beats in ([[5]], [[5], [6], [7]]):
         with pytest.raises(RalError, match=rf"BeatDelineator.delineate: {len(beats)} beat lists for 2 records"):
             dl.delineate(x, beats)
+    # the classifier and the detector check in the same order: shape, geometry, beat lists, and only then the device
+    from ecg_denoise_amd import BeatClassifier, BeatDetector
+    cl, det = BeatClassifier(), BeatDetector()
+    with pytest.raises(RalError, match="device tensor"):
+        cl.classify(x, [[5], [7]])
+    with pytest.raises(RalError, match="device tensor"):
+        cl.classify(np.zeros((2, 2, 1000), np.float32), [[5], [7]])
+    for bad in (torch.zeros(1000), torch.zeros(2, 2, 2, 1000), torch.zeros(2, 2, 0)):
+        with pytest.raises(RalError, match=r"BeatClassifier.classify: expected \(leads, T\) or \(R, leads, T\)"):
+            cl.classify(bad, [[5], [7]])
+    for beats in ([[9, 3], [1]], [[5, 5], [1]], [[-1], [1]], [[1], [1000]]):
+        with pytest.raises(RalError, match=r"BeatClassifier.classify: the beats of a record must be strictly ascending positions in \[0, 1000\)"):
+            cl.classify(x, beats)
+    for beats in ([[5]], [[5], [6], [7]]):
+        with pytest.raises(RalError, match=rf"BeatClassifier.classify: {len(beats)} beat lists for 2 records"):
+            cl.classify(x, beats)
+    with pytest.raises(RalError, match="device tensor"):
+        det.detect(x)
+    with pytest.raises(RalError, match="device tensor"):
+        det.detect(np.zeros((2, 2, 1000), np.float32))
+    for bad in (torch.zeros(1000), torch.zeros(2, 2, 2, 1000), torch.zeros(2, 2, 0)):
+        with pytest.raises(RalError, match=r"BeatDetector.detect: expected \(leads, T\) or \(R, leads, T\)"):
+            det.detect(bad)
+    with pytest.raises(RalError, match="beat detection at fs=360 with 64 leads is not supported"):
+        det.detect(torch.zeros(64, 1000))                    # a geometry that is refused, on a host tensor
 
 
 def test_the_classifier_keeps_its_own_name_in_the_shared_messages():
     from ecg_denoise_amd import RalError
-    from ecg_denoise_amd.rhythm import _positions
+    from ecg_denoise_amd.intake import beat_lists
+    what = "BeatClassifier.classify"
     with pytest.raises(RalError, match=r"^BeatClassifier.classify: 1 beat lists for 2 records$"):
-        _positions([[5]], 2, 1000, torch.device("cpu"))
+        beat_lists([[5]], torch.device("cpu"), what, T=1000, R=2)
     with pytest.raises(RalError, match=r"^BeatClassifier.classify: the beats of a record must be strictly ascending positions in \[0, 1000\)$"):
-        _positions([[9, 3], [1]], 2, 1000, torch.device("cpu"))
+        beat_lists([[9, 3], [1]], torch.device("cpu"), what, T=1000, R=2)

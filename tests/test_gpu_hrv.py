@@ -171,6 +171,22 @@ def test_a_record_alone_gives_the_bits_of_its_rows_in_the_batch():
         assert torch.equal(_bits(one.psd), _bits(h.psd[r * nw:(r + 1) * nw]))
 
 
+def test_beats_and_classes_of_the_device_and_the_same_values_as_lists_give_identical_tensors():
+    """2 x 2 x 3 600 at 360 Hz, 4 s windows every 2 s: `Beats` and `BeatClasses` (the detector's wider cap) against their lists"""
+    from ecg_denoise_amd import BeatClassifier, BeatDetector, synth
+    x, _, _ = synth.make_records_with_rhythm(2, 2, 3600, seed=24, p_v=0.15)
+    xd = torch.from_numpy(x).to(DEV)
+    beats = BeatDetector(device=DEV).detect(xd)
+    classes = BeatClassifier(device=DEV).classify(xd, beats)
+    lists, labels = beats.tolist(), [c[0] for c in classes.tolist()]
+    assert min(len(p) for p in lists) >= 8 and beats.peaks.shape[1] > max(len(p) for p in lists)
+    geo = dict(win_s=4, hop_s=2, min_nn=3)
+    a = _analyse(360, beats, 3600, classes, psd=True, **geo)
+    b = _analyse(360, lists, 3600, labels, psd=True, **geo)
+    assert len(a) == 2 * ((3600 - 1440) // 720 + 1) and int(a.n_nn.max()) >= 3 and _same_bits(a, b)
+    assert _same_bits(_analyse(360, beats, 3600, **geo), _analyse(360, lists, 3600, **geo))              # and without labels
+
+
 # ------------------------------------------------------------------------------------------------ 5. end to end on records
 CHAIN = dict(win_s=20, hop_s=5, min_nn=8)
 
@@ -253,6 +269,42 @@ def test_pool_equals_the_three_call_chain_bit_for_bit(seed, disturb):
         assert torch.equal(counts, want.counts[i * nw:(i + 1) * nw])
         assert torch.equal(_bits(stats), _bits(want.stats[i * nw:(i + 1) * nw]))
         assert empty[i] >= 1 and all(h.psd is None and tuple(h.stats.shape) == (len(h), 10) for h in got[i])
+
+
+def test_pool_raising_calls_change_nothing():
+    """both records of `_chain` (60 s) through an HrvPool in uneven chunks, with 10 s windows every 5 s; halfway through, a
+    chunk with the wrong lead count and a call that names a closed stream raise, and neither changes what the pool has
+    counted nor what it goes on to give: the windows of the three-call chain on the complete record, bit for bit"""
+    from ecg_denoise_amd import HrvAnalyzer, HrvPool, RalError
+    geo = dict(win_s=10, hop_s=5, min_nn=8)
+    xd, beats, classes, _ = _chain()
+    want = HrvAnalyzer(device=DEV, **geo).analyse(beats, 21600, classes)
+    nw = len(want) // 2
+    assert nw == (21600 - 3600) // 1800 + 1
+    pool = HrvPool(2, capacity=3, device=DEV, **geo)
+    a, b, gone = pool.open(), pool.open(), pool.open()
+    pool.close(gone, xd[0][:, :100])
+    cuts = [0, 1, 700, 5000, 5003, 10800, 14001, 19999, 21600]
+    got = {a: [], b: []}
+    for lo, hi in zip(cuts[:-1], cuts[1:]):
+        if lo == 10800:
+            for chunks, close in (({a: xd[0][:, lo:hi], b: xd[1][:1, lo:hi]}, ()),           # one lead instead of two
+                                  ({a: xd[0][:, lo:hi], gone: xd[1][:, lo:hi]}, ()),          # a stream that has been closed
+                                  ({a: xd[0][:, lo:hi]}, (gone,))):
+                before = (pool.open_streams, pool.samples_in(a), pool.samples_in(b), pool.classes.beats_in(a), pool.classes.beats_in(b))
+                with pytest.raises(RalError):
+                    pool.push(chunks, close=close)
+                assert before == (pool.open_streams, pool.samples_in(a), pool.samples_in(b), pool.classes.beats_in(a),
+                                  pool.classes.beats_in(b)) == ((a, b), lo, lo) + before[3:]
+        res = pool.push({a: xd[0][:, lo:hi], b: xd[1][:, lo:hi]}, close=(a, b) if hi == 21600 else ())
+        for sid in (a, b):
+            got[sid].append(res[sid])
+    assert pool.open_streams == ()
+    for i, sid in enumerate((a, b)):
+        assert [ix for h in got[sid] for ix in h.index.tolist()] == [[sid, w] for w in range(nw)]
+        assert torch.equal(torch.cat([h.counts for h in got[sid]]), want.counts[i * nw:(i + 1) * nw])
+        assert torch.equal(_bits(torch.cat([h.stats for h in got[sid]])), _bits(want.stats[i * nw:(i + 1) * nw]))
+    assert int(want.n_nn.max()) >= geo["min_nn"]               # (some windows have a spectrum)
 
 
 # ------------------------------------------------------------------------------------------------ 7. evaluate_hrv

@@ -159,6 +159,23 @@ def test_refusals():
         cls.classify(torch.zeros(65536, 1, 8, device=DEV), [[1]] * 65536)
 
 
+def test_beats_of_the_detector_and_the_same_positions_as_lists_give_identical_tensors():
+    """2 x 2 x 3 600 at 360 Hz: a `Beats` (the detector's wider cap) against its own lists"""
+    from ecg_denoise_amd import BeatDetector
+    x, _, _ = _records(2, 2, 3600, 24)
+    xd = torch.from_numpy(x).to(DEV)
+    det = BeatDetector(device=DEV).detect(xd)
+    assert min(len(p) for p in det.tolist()) >= 8
+    a, _ = _classify(xd, det)
+    b, _ = _classify(xd, det.tolist())
+    n = b.label.shape[1]
+    assert n == max(det.count.tolist()) < a.label.shape[1]
+    for k in ("label", "corr", "rr_ratio", "peaks"):
+        assert torch.equal(_bits(getattr(a, k)[:, :n]), _bits(getattr(b, k))), k
+    assert (a.label[:, n:] == -1).all() and (a.peaks[:, n:] == -1).all() and torch.equal(a.count, b.count)
+    assert torch.isnan(a.corr[:, n:]).all() and torch.isnan(a.rr_ratio[:, n:]).all()
+
+
 # ------------------------------------------------------------------------------------------------ 3. pool equals record
 def _whole(rec, fs=360):
     """the complete record through detect and classify -> (peaks, label, corr bits, rr bits) as lists"""

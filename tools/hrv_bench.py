@@ -30,7 +30,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch  # noqa: E402
 
 from ecg_denoise_amd import BeatClassPool, Beats, HrvAnalyzer, HrvPool, synth  # noqa: E402
-from ecg_denoise_amd.hrv import _pad  # noqa: E402
+from ecg_denoise_amd.intake import pad_rows  # noqa: E402
 
 DEV = "cuda:0"
 
@@ -62,8 +62,8 @@ def _lists(args):
 def records_leg(args):
     T, (beats, labels) = _lists(args)
     ana = HrvAnalyzer(args.fs, device=DEV)
-    b = Beats(torch.from_numpy(_pad(beats, -1)).to(DEV), torch.tensor([len(p) for p in beats], dtype=torch.int32, device=DEV), args.fs)
-    lab = torch.from_numpy(_pad(labels, -1)).to(DEV)
+    b = Beats(torch.from_numpy(pad_rows(beats, -1)).to(DEV), torch.tensor([len(p) for p in beats], dtype=torch.int32, device=DEV), args.fs)
+    lab = torch.from_numpy(pad_rows(labels, -1)).to(DEV)
     from ecg_denoise_amd.rhythm import BeatClasses
     classes = BeatClasses(lab, None, None, b.count, b.peaks, 0.7, 0.8, args.fs)
     out = {"lists": args.lists, "T": T, "fs": args.fs, "beats": int(b.count.sum()),
