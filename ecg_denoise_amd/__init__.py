@@ -43,3 +43,5 @@ from .delineate import (BeatDelineator, Fiducials, IntervalEvaluation, delineate
                         evaluate_intervals, interval_scores)
 from .hrv import (HrvAnalyzer, HrvEvaluation, HrvPool, HrvPoolState, HrvWindows, evaluate_hrv, hrv_check, hrv_geometry,  # noqa: F401
                   hrv_windows)
+from .template import (BeatTemplates, MedianBeat, TemplateEvaluation, evaluate_templates, template_check,  # noqa: F401
+                       template_geometry, template_rmse)

@@ -43,6 +43,11 @@ class DelinGeom(C.Structure):
                 ("wt", C.c_int32), ("q0", C.c_float)]
 
 
+class TemplateGeom(C.Structure):
+    """ral_template_geom: the median beat's two half-lengths, its window and hop in samples, and the most beats of a template"""
+    _fields_ = [("wpre", C.c_int32), ("wpost", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("kmax", C.c_int32)]
+
+
 class HrvGeom(C.Structure):
     """ral_hrv_geom: the HRV window's lengths in samples, its bin count, min_nn and the rate"""
     _fields_ = [("W", C.c_int32), ("lo_n", C.c_int32), ("hi_n", C.c_int32), ("t50", C.c_int32), ("F", C.c_int32),
@@ -169,6 +174,8 @@ _SIGS = {
                                   C.c_int, _VP, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
     "ral_delineate_records": (C.c_int, [_VP, C.c_int64, C.c_int, C.c_int64, C.POINTER(DelinGeom), _VP, _VP, C.c_int64, _VP, _VP, _VP,
                                         _VP, _VP]),
+    "ral_template_records": (C.c_int, [_VP, C.c_int64, C.c_int, C.c_int64, C.POINTER(TemplateGeom), _VP, _VP, _VP, C.c_int64,
+                                       C.c_int64, _VP, _VP, _VP, _VP, _VP]),
     "ral_hrv_windows": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int64, _VP, C.c_int, C.POINTER(HrvGeom), _VP, _VP,
                                   _VP, _VP, _VP]),
     "ral_attention_forward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),

@@ -838,6 +838,20 @@ int ral_delineate_records(const float* x, int64_t R, int leads, int64_t T, const
   return 0;
 }
 
+int ral_template_records(const float* x, int64_t R, int leads, int64_t T, const ral_template_geom* geom, const int32_t* peaks,
+                         const int32_t* label_or_null, const int32_t* count, int64_t cap, int64_t nw, float* tpl, int32_t* used,
+                         int32_t* total, int32_t* rr, ral_stream s) {
+  const char* why = nullptr;
+  if (launch_template_records(x, (long long)R, leads, (long long)T, geom, peaks, label_or_null, count, (long long)cap,
+                              (long long)nw, tpl, used, total, rr, (hipStream_t)s, &why)) {
+    const ral_template_geom none = {0, 0, 0, 0, 0}, *g = geom ? geom : &none;
+    return ral_fail("ral_template_records: %s (R=%lld leads=%d T=%lld cap=%lld nw=%lld wpre=%d wpost=%d w=%d h=%d kmax=%d)", why,
+                    (long long)R, leads, (long long)T, (long long)cap, (long long)nw, g->wpre, g->wpost, g->w, g->h, g->kmax);
+  }
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 int ral_hrv_windows(const int32_t* pos, const int32_t* label_or_null, const int32_t* count, int64_t R, int64_t cap,
                     const ral_hrv_row* table, int64_t rows, ral_hrv_row* table_dev, int upload, const ral_hrv_geom* geom,
                     const int32_t* band, int32_t* counts, float* stats, float* psd_or_null, ral_stream s) {

@@ -158,6 +158,10 @@ int launch_rhythm_pool(const float* hist, const float* x, long long x_total, con
 int launch_delineate_records(const float* x, long long R, int leads, long long T, const ral_delin_geom* geom, const int* peaks,
                              const int* count, long long cap, int* on, int* off, int* tpeak, int* tend, hipStream_t s,
                              const char** why);
+// median beats (ral_template.hip; ral_template_records): -1 with *why, which names the argument, before any HIP call
+int launch_template_records(const float* x, long long R, int leads, long long T, const ral_template_geom* geom, const int* peaks,
+                            const int* label, const int* count, long long cap, long long nw, float* tpl, int* used, int* total,
+                            int* rr, hipStream_t s, const char** why);
 int launch_conv13_fwd(const float* x, const float* w, const float* b, float* y, int B, int cin, int cout, int L,
                       int lrelu, hipStream_t s, const char** why);   // -1: refused before any HIP call, *why names the argument
 int launch_conv13_bwd(const float* x, const float* y, const float* dy, const float* w, float* gw, float* gb,

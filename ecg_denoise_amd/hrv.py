@@ -166,19 +166,20 @@ class _Engine:
         return HrvWindows(counts, stats, out, np.asarray(index, dtype=np.int64).reshape(N, 2), g)
 
 
-def _labels(classes, pos, count):
-    """`BeatClasses`, per-record label lists or None -> (R, cap) int32 on the device of `pos`, or None"""
+def _labels(classes, pos, count, what="HrvAnalyzer.analyse"):
+    """`BeatClasses`, per-record label lists or None -> (R, cap) int32 on the device of `pos`, or None; `what` is the caller's
+    name in the messages"""
     if classes is None:
         return None
     if isinstance(classes, BeatClasses):
         lab = classes.label
         if lab.shape != pos.shape or lab.device != pos.device or lab.dtype != torch.int32:
-            raise _lib.RalError(f"HrvAnalyzer.analyse: labels of shape {tuple(lab.shape)} on {lab.device} for beats of shape "
+            raise _lib.RalError(f"{what}: labels of shape {tuple(lab.shape)} on {lab.device} for beats of shape "
                                 f"{tuple(pos.shape)} on {pos.device}")
         return lab.contiguous()
     rows = [np.asarray(r.cpu() if torch.is_tensor(r) else r, dtype=np.int64).reshape(-1) for r in classes]
     if len(rows) != pos.shape[0] or [len(r) for r in rows] != count.tolist():
-        raise _lib.RalError("HrvAnalyzer.analyse: one label per beat of every record")
+        raise _lib.RalError(f"{what}: one label per beat of every record")
     return torch.from_numpy(pad_rows(rows, -1, shape=tuple(pos.shape))).to(pos.device)
 
 

@@ -42,9 +42,16 @@ clean record and can be measured here too, and the mean absolute error of QRS du
 in both - `BeatDelineator` at the clean records' detections (`evaluate_intervals`; NaN where there is no such beat).  Without
 the flag the output is what it was.
 
+`--templates` asks the fifth question, is the shape of the beat back: per cell one more line and a "templates" entry in the JSON
+with, for the noisy and for the denoised records, the RMSE of the median beat of every `--template-win` seconds against the clean
+records' median beat at the same beats and classes, pooled over the windows with at least three used beats, and the pooled
+shares and errors of QRS duration and QT measured on the median beats (`evaluate_templates`; NaN where there is no such
+window).  Without the flag the output is what it was.
+
     python tools/stress_eval.py [--model full|nra|mlp|unet|acdae|danet|newrale] [--ckpt state_dict.pth] [--L 512]
                                 [--records 4] [--T 65000] [--overlap 0] [--batch 4096] [--time-shapes ...] [--reps 5] [--beats]
                                 [--classes] [--fft] [--fft-L 1000] [--hrv] [--hrv-win 60] [--hrv-hop 30] [--intervals]
+                                [--templates] [--template-win 10]
 """
 import argparse
 import json
@@ -58,7 +65,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from ecg_denoise_amd import (ACDAE, ClassicalDenoiser, DANet, NewRALE, RALENet, UNet, evaluate_beats, evaluate_hrv,  # noqa: E402
-                             evaluate_intervals, evaluate_rhythm, interval_scores, mix_records, score_records, synth,
+                             evaluate_intervals, evaluate_rhythm, evaluate_templates, interval_scores, mix_records, score_records, synth,
                              wavelet_denoise)
 from ecg_denoise_amd.data import NOISE_TYPES, TRUE_NOISE  # noqa: E402
 from ecg_denoise_amd.infer import StreamingDenoiser  # noqa: E402
@@ -142,6 +149,20 @@ def _intervals_cell(ev, idx):
     return {key: interval_scores(ev.clean, f, rows=idx)[2] for key, f in (("noisy", ev.noisy), ("denoised", ev.denoised))}
 
 
+def _templates_cell(ev, idx):
+    """the records idx of an `evaluate_templates` result -> per condition the pooled RMSE against the clean median beats, how
+    many windows it is taken over, and the pooled interval shares and errors"""
+    nw = ev.clean.used.shape[1]
+    rows = (idx[:, None] * nw + torch.arange(nw, device=idx.device)).reshape(-1)
+    out = {}
+    for key in ("noisy", "denoised"):
+        r = ev.rmse[key][idx]
+        ok = torch.isfinite(r)
+        out[key] = dict(interval_scores(ev.fiducials["clean"], ev.fiducials[key], rows=rows)[2], windows=int(ok.sum()),
+                        rmse=float(torch.sqrt((r[ok] ** 2).mean())) if bool(ok.any()) else float("nan"))
+    return out
+
+
 def grid(args, model, name):
     sd = StreamingDenoiser(model, batch=args.batch, overlap=args.overlap, use_graph=True)
     leads, n_int = sd.leads, len(TRUE_NOISE)
@@ -169,6 +190,11 @@ def grid(args, model, name):
             evh = evaluate_hrv(sd, rec, noise, snrs, offsets=offsets,
                                analyzer=HrvAnalyzer(win_s=args.hrv_win, hop_s=args.hrv_hop, device=DEV))
         evi = evaluate_intervals(sd, rec, noise, snrs, offsets=offsets) if args.intervals else None
+        evt = None
+        if args.templates:
+            from ecg_denoise_amd import MedianBeat
+            evt = evaluate_templates(sd, rec, noise, snrs, offsets=offsets,
+                                     averager=MedianBeat(win_s=args.template_win, hop_s=args.template_win, device=DEV))
         for i, snr in enumerate(TRUE_NOISE):
             idx = torch.arange(i * args.records, (i + 1) * args.records, device=DEV)
             a, b = _subset(sc, idx, sd.L), _subset(sw, idx, sd.L)
@@ -204,6 +230,12 @@ def grid(args, model, name):
                 col = lambda d: (f"qrs {d['qrs_share']:.4f} of the clean beats, error {d['qrs_mae_ms']:.2f} ms over {d['qrs_beats']}; "
                                  f"qt {d['qt_share']:.4f}, error {d['qt_mae_ms']:.2f} ms over {d['qt_beats']}")
                 lines.append(f"{name}_0_{kind}_intensity{snr}:intervals: noisy {col(ic['noisy'])}, denoised {col(ic['denoised'])}\n")
+            if evt is not None:
+                tc = _templates_cell(evt, idx)
+                cells[-1]["templates"] = tc
+                col = lambda d: (f"rmse {d['rmse']:.4f} over {d['windows']} median beats; qrs {d['qrs_share']:.4f} of the clean ones, "
+                                 f"error {d['qrs_mae_ms']:.2f} ms; qt {d['qt_share']:.4f}, error {d['qt_mae_ms']:.2f} ms")
+                lines.append(f"{name}_0_{kind}_intensity{snr}:templates: noisy {col(tc['noisy'])}, denoised {col(tc['denoised'])}\n")
     return cells, lines
 
 
@@ -266,6 +298,8 @@ def main():
     ap.add_argument("--fft-L", type=int, default=1000)
     ap.add_argument("--hrv", action="store_true", help="add the errors of heart rate, SDNN, RMSSD and log(LF/HF), noisy and denoised")
     ap.add_argument("--intervals", action="store_true", help="add the shares and errors of QRS duration and QT, noisy and denoised")
+    ap.add_argument("--templates", action="store_true", help="add the RMSE and the intervals of the median beats, noisy and denoised")
+    ap.add_argument("--template-win", type=int, default=10)
     ap.add_argument("--hrv-win", type=int, default=60)
     ap.add_argument("--hrv-hop", type=int, default=30)
     args = ap.parse_args()
