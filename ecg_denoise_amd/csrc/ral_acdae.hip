@@ -14,7 +14,10 @@
 //   k_acd_dec_bwd   ECA backward, LeakyReLU', upsample adjoint -> dT (stored), input gradient (correlation with W)
 //   k_acd_enc_bwd   (main + skip) gradient -> LeakyReLU', un-pool -> dC (stored), input gradient
 //   k_acd_dw_m      weight / bias gradients of one conv: dW[co][ci][k] = sum over windows and positions of Y X as an
-//                   fp32-MFMA GEMM with index-gathered operands (k_acd_dw: the scalar form, kept for 2 output channels)
+//                   fp32-MFMA GEMM with index-gathered operands (k_acd_dw: the scalar form)
+// Which instance runs a row, with what grid and LDS, is the plan's answer (acdae_pass, ral_baseline_plan.hip: the MFMA encoder
+// forward k_acd_enc_fwd_m where its tiles fit, the scalar k_acd_dw for the 2-channel output layer); the host model at the end of
+// this file executes the plan's entries.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -25,11 +28,9 @@
 
 #include "ral_model.hpp"
 #include "ral_device.hpp"
+#include "ral_baseline_plan.hpp"
 
 namespace {
-const int ACH[5] = {2, 16, 32, 64, 128};
-const int AKS[4] = {13, 7, 7, 7};
-
 RAL_DEV float lrelu01(float v) { return v > 0.f ? v : 0.01f * v; }
 
 // ---------------------------------------------------------------------------------
@@ -543,34 +544,31 @@ __global__ __launch_bounds__(256) void k_acd_dw_m(const float* __restrict__ Y, c
 }  // namespace
 
 // =================================================================================
-// host model
+// host model (the network's shape: acdae_layers, ral_baseline_plan.hip)
 // =================================================================================
-struct AOff { int64_t ew[4], eb[4], dw[4], db[4], de[4]; };
+struct AOff { int64_t w[BASELINE_LAYERS], b[BASELINE_LAYERS], eca[BASELINE_LAYERS]; };   // (eca: decoder rows)
 static void abuild(ParamLayout& L, AOff& O) {
   auto alloc = [&](int64_t n) { return L.alloc(n, 4); };
-  for (int i = 0; i < 4; ++i) {
-    const std::string p = "EncList." + std::to_string(i) + ".conv.";
-    O.ew[i] = alloc((int64_t)ACH[i + 1] * ACH[i] * AKS[i]); O.eb[i] = alloc(ACH[i + 1]);
-    L.add(p + "weight", RAL_PARAM, O.ew[i], {ACH[i + 1], ACH[i], AKS[i]});
-    L.add(p + "bias", RAL_PARAM, O.eb[i], {ACH[i + 1]});
-  }
-  for (int i = 0; i < 4; ++i) {
-    const std::string p = "DecList." + std::to_string(i) + ".";
-    const int cin = ACH[4 - i], cout = ACH[3 - i], k = AKS[3 - i];
-    O.dw[i] = alloc((int64_t)cin * cout * k); O.db[i] = alloc(cout); O.de[i] = alloc(3);
-    L.add(p + "conv.weight", RAL_PARAM, O.dw[i], {cin, cout, k});
-    L.add(p + "conv.bias", RAL_PARAM, O.db[i], {cout});
-    L.add(p + "ECA.conv.weight", RAL_PARAM, O.de[i], {1, 1, 3});
+  const AcdaeLayer* const tab = acdae_layers();
+  int nenc = 0, ndec = 0;
+  for (int li = 0; li < BASELINE_LAYERS; ++li) {
+    const AcdaeLayer& r = tab[li];
+    const std::string p = r.convt ? "DecList." + std::to_string(ndec++) + "." : "EncList." + std::to_string(nenc++) + ".";
+    O.w[li] = alloc((int64_t)r.cin * r.cout * r.ks); O.b[li] = alloc(r.cout); O.eca[li] = r.convt ? alloc(3) : 0;
+    L.add(p + "conv.weight", RAL_PARAM, O.w[li], {r.convt ? r.cin : r.cout, r.convt ? r.cout : r.cin, r.ks});
+    L.add(p + "conv.bias", RAL_PARAM, O.b[li], {r.cout});
+    if (r.convt) L.add(p + "ECA.conv.weight", RAL_PARAM, O.eca[li], {1, 1, 3});
   }
 }
 
 struct AcdaeModel : ral_handle {
   AOff off;
-  // per window: encoder outputs e[i] (C_{i+1} x L / 2^{i+1}) + argmax bytes, decoder ECA inputs a[i], scales s[i], block
-  // outputs d[i] (d[3] = y is the caller's), gradients: dc[i] (conv-output gradients, C_{i+1} x L / 2^i), dt[i], G tensors
-  float *e[4], *a[4], *s[4], *d[3];
-  unsigned char* amax[4];   // argmax of each pooled encoder output
-  float *dc[4], *dt[4], *gd[3], *ge[4];   // gd[i]: gradient at d[i]; ge[i]: input gradient of encoder i + 1 (at e[i])
+  // per window and row: the row's output (the last row's is the caller's y); an encoder row's argmax bytes of its pooled pairs;
+  // a decoder row's ECA input a and scale s; gradients: dz at the conv output (cout x lin, kept for the weight gradient) and
+  // gout at the row's output (the last row's is the caller's dy)
+  float *out[BASELINE_LAYERS], *a[BASELINE_LAYERS], *s[BASELINE_LAYERS], *dz[BASELINE_LAYERS], *gout[BASELINE_LAYERS];
+  unsigned char* amax[BASELINE_LAYERS];
+  int skip_user[BASELINE_LAYERS];   // the decoder row that adds this row's output to its own, or BL_NONE
   const float* last_x = nullptr;
   int last_B = 0;
   int init() override;
@@ -579,36 +577,34 @@ struct AcdaeModel : ral_handle {
 };
 
 static int acdae_check_cfg(const ral_config* c) {
-  if (c->leads != 2) return ral_fail("ACDAE has 2 input channels (got leads=%d)", c->leads);
-  if (c->L <= 0 || c->L % 64 != 0 || c->L > 1024) return ral_fail("ACDAE: L must be a multiple of 64 and <= 1024 (got %d)", c->L);
+  const std::string why = acdae_legal(*c);
+  if (!why.empty()) return ral_fail("%s", why.c_str());
   if (c->max_batch <= 0) return ral_fail("max_batch must be positive");
   return 0;
 }
 
-static size_t acdae_plan(const ral_config& c, AcdaeModel* m, char* base) {
+static size_t acdae_workspace(const ral_config& c, AcdaeModel* m, char* base) {
   size_t cur = 0;
   const size_t B = c.max_batch;
   auto take = [&](size_t bytes) -> char* { char* p = base ? base + cur : nullptr; cur += (bytes + 255) & ~size_t(255); return p; };
-  for (int i = 0; i < 4; ++i) {
-    const size_t n = B * ACH[i + 1] * (c.L >> (i + 1));
-    float* pe = reinterpret_cast<float*>(take(n * 4));
-    unsigned char* pa = reinterpret_cast<unsigned char*>(take(n));
-    if (m) { m->e[i] = pe; m->amax[i] = pa; }
-  }
-  for (int i = 0; i < 4; ++i) {        // decoder i: COUT = ACH[3 - i], output length L >> (3 - i)
-    const size_t n = B * ACH[3 - i] * (c.L >> (3 - i));
-    float* pa = reinterpret_cast<float*>(take(n * 4));
-    float* ps = reinterpret_cast<float*>(take(B * ACH[3 - i] * 4));
-    float* pd = i < 3 ? reinterpret_cast<float*>(take(n * 4)) : nullptr;
-    if (m) { m->a[i] = pa; m->s[i] = ps; if (i < 3) m->d[i] = pd; }
+  auto floats = [&](size_t n) { return reinterpret_cast<float*>(take(n * 4)); };
+  const AcdaeLayer* const tab = acdae_layers();
+  const int last = BASELINE_LAYERS - 1;
+  for (int li = 0; li < BASELINE_LAYERS; ++li) {
+    const AcdaeLayer& r = tab[li];
+    const size_t n = B * r.cout * (c.L >> r.out_shift);
+    float *po = nullptr, *pa = nullptr, *ps = nullptr;
+    unsigned char* pm = nullptr;
+    if (r.convt) { pa = floats(n); ps = floats(B * r.cout); if (li < last) po = floats(n); }
+    else { po = floats(n); pm = reinterpret_cast<unsigned char*>(take(n)); }
+    if (m) { m->out[li] = po; m->amax[li] = pm; m->a[li] = pa; m->s[li] = ps; }
   }
   if (c.train) {
-    for (int i = 0; i < 4; ++i) {
-      float* p1 = reinterpret_cast<float*>(take(B * ACH[i + 1] * (c.L >> i) * 4));            // dc[i]
-      float* p2 = reinterpret_cast<float*>(take(B * ACH[3 - i] * (c.L >> (4 - i)) * 4));      // dt[i]: COUT x Lin of decoder i
-      float* p3 = i < 3 ? reinterpret_cast<float*>(take(B * ACH[3 - i] * (c.L >> (3 - i)) * 4)) : nullptr;   // gd[i]
-      float* p4 = reinterpret_cast<float*>(take(B * ACH[i + 1] * (c.L >> (i + 1)) * 4));      // ge[i]: gradient at e[i]
-      if (m) { m->dc[i] = p1; m->dt[i] = p2; if (i < 3) m->gd[i] = p3; m->ge[i] = p4; }
+    for (int li = 0; li < BASELINE_LAYERS; ++li) {
+      const AcdaeLayer& r = tab[li];
+      float* p1 = floats(B * r.cout * (c.L >> r.in_shift));
+      float* p2 = li < last ? floats(B * r.cout * (c.L >> r.out_shift)) : nullptr;
+      if (m) { m->dz[li] = p1; m->gout[li] = p2; }
     }
   }
   return cur;
@@ -616,9 +612,13 @@ static size_t acdae_plan(const ral_config& c, AcdaeModel* m, char* base) {
 
 int AcdaeModel::init() {
   abuild(lay, off);
-  const size_t bytes = acdae_plan(cfg, nullptr, nullptr);
+  const AcdaeLayer* const tab = acdae_layers();
+  for (int li = 0; li < BASELINE_LAYERS; ++li) skip_user[li] = BL_NONE;
+  for (int li = 0; li < BASELINE_LAYERS; ++li)
+    if (tab[li].skip != BL_NONE) skip_user[tab[li].skip] = li;
+  const size_t bytes = acdae_workspace(cfg, nullptr, nullptr);
   if (alloc_slab(bytes) != hipSuccess) return ral_fail("hipMalloc(%zu) failed", bytes);
-  acdae_plan(cfg, this, slab);
+  acdae_workspace(cfg, this, slab);
   return 0;
 }
 
@@ -626,114 +626,78 @@ const RalKind* acdae_kind() {
   static const RalKind k = {
       acdae_check_cfg,
       [](const ral_config&, ParamLayout& L) { AOff o; abuild(L, o); },
-      [](const ral_config& c) { return acdae_plan(c, nullptr, nullptr); },
+      [](const ral_config& c) { return acdae_workspace(c, nullptr, nullptr); },
       0,
       []() -> ral_handle* { return new AcdaeModel(); },
       "ACDAE has no BatchNorm: use ral_forward"};
   return &k;
 }
 
-#define ACD_LDS(kernel, bytes) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes))
+
+// ---- forward and backward execute the entries of a pass (acdae_pass) in order and never choose: each entry's pointers come from
+// its table row, and one switch over the enumerators starts the kernel - a case per instance, one argument list per family
+#define GO(e, kernel, ...) \
+  case BKernel::e: RAL_SET_LDS((kernel), p.lds); kernel<<<dim3(p.gx, p.gy), p.threads, p.lds, st>>>(__VA_ARGS__); break;
 
 int AcdaeModel::forward(const float* x, float* y, int B, int, hipStream_t st) {
-  AcdaeModel* const m = this;
-  if (!m->params) return ral_fail("ral_bind was not called");
-  if (B <= 0 || B > m->cfg.max_batch) return ral_fail("batch %d outside (0, %d]", B, m->cfg.max_batch);
-  const int L = m->cfg.L, grid = B < 1024 ? B : 1024;
-  const AOff& Y = m->off;
-  m->last_x = x; m->last_B = B;
-  const float* in = x;
-  for (int i = 0; i < 4; ++i) {
-    const int cin = ACH[i], cout = ACH[i + 1], lin = L >> i;
-    const size_t lds = (size_t)cin * (lin + 16) * sizeof(float);
-    if (AKS[i] == 13) { ACD_LDS(k_acd_enc_fwd<13>, lds); k_acd_enc_fwd<13><<<grid, 256, lds, st>>>(in, m->params + Y.ew[i], m->params + Y.eb[i], m->e[i], m->amax[i], cin, cout, lin, B); }
-    else if (cin >= 16 && cout % 32 == 0 && lin % 16 == 0) {
-      const size_t l2 = lds + (size_t)32 * cin * 7 * sizeof(float);
-      const int gx = B < 512 ? B : 512;
-      ACD_LDS(k_acd_enc_fwd_m<7>, l2);
-      k_acd_enc_fwd_m<7><<<dim3(gx, cout / 32), 256, l2, st>>>(in, m->params + Y.ew[i], m->params + Y.eb[i], m->e[i], m->amax[i], cin, cout, lin, B);
+  if (!params) return ral_fail("ral_bind was not called");
+  if (B <= 0 || B > cfg.max_batch) return ral_fail("batch %d outside (0, %d]", B, cfg.max_batch);
+  last_x = x; last_B = B;
+  const BPass pass = acdae_pass(cfg.L, B, false);
+  for (int k = 0; k < pass.n; ++k) {
+    const BLaunch& p = pass.e[k];
+    const int li = p.layer;
+    const AcdaeLayer& r = acdae_layers()[li];
+    const float *in = li == 0 ? x : out[li - 1], *skip = r.skip != BL_NONE ? out[r.skip] : nullptr;
+    const float *w = params + off.w[li], *bias = params + off.b[li], *ecaw = params + off.eca[li];
+    float* o = li == BASELINE_LAYERS - 1 ? y : out[li];
+    const int lin = cfg.L >> r.in_shift;
+#define ENC in, w, bias, o, amax[li], r.cin, r.cout, lin, B
+#define DEC in, w, bias, ecaw, skip, a[li], s[li], o, r.cin, r.cout, lin, B
+    switch (p.kernel) {
+      GO(ACD_ENC_FWD_13, k_acd_enc_fwd<13>, ENC) GO(ACD_ENC_FWD_7, k_acd_enc_fwd<7>, ENC) GO(ACD_ENC_FWD_M_7, k_acd_enc_fwd_m<7>, ENC)
+      GO(ACD_DEC_FWD_7, k_acd_dec_fwd<7>, DEC) GO(ACD_DEC_FWD_13, k_acd_dec_fwd<13>, DEC)
+      default: baseline_launch_missing("ACDAE forward", p);
     }
-    else { ACD_LDS(k_acd_enc_fwd<7>, lds); k_acd_enc_fwd<7><<<grid, 256, lds, st>>>(in, m->params + Y.ew[i], m->params + Y.eb[i], m->e[i], m->amax[i], cin, cout, lin, B); }
-    in = m->e[i];
-  }
-  for (int i = 0; i < 4; ++i) {
-    const int cin = ACH[4 - i], cout = ACH[3 - i], lin = L >> (4 - i), ks = AKS[3 - i];
-    const size_t lds = ((size_t)cin * (lin + 16) + (size_t)cout * lin * 3 + 2 * cout + 8) * sizeof(float);
-    const float* skip = i < 3 ? m->e[2 - i] : nullptr;
-    float* out = i < 3 ? m->d[i] : y;
-    if (ks == 13) { ACD_LDS(k_acd_dec_fwd<13>, lds); k_acd_dec_fwd<13><<<grid, 256, lds, st>>>(in, m->params + Y.dw[i], m->params + Y.db[i], m->params + Y.de[i], skip, m->a[i], m->s[i], out, cin, cout, lin, B); }
-    else { ACD_LDS(k_acd_dec_fwd<7>, lds); k_acd_dec_fwd<7><<<grid, 256, lds, st>>>(in, m->params + Y.dw[i], m->params + Y.db[i], m->params + Y.de[i], skip, m->a[i], m->s[i], out, cin, cout, lin, B); }
-    in = out;
+#undef ENC
+#undef DEC
   }
   if (hipGetLastError() != hipSuccess) return ral_fail("ACDAE forward launch failed");
   return 0;
 }
 
-template <int KS, bool CONVT>
-static void launch_acd_dw(const float* Yg, const float* Xg, float* gw, float* gb, int CY, int CX, int L, int B, hipStream_t st) {
-  const size_t lds = ((size_t)8 * L + (size_t)8 * (L + 16)) * sizeof(float);
-  const int nblk = ((CY + 7) / 8) * ((CX + 7) / 8);
-  int splits = 2048 / nblk;                      // ~2048 workgroups per launch
-  if (splits < 1) splits = 1;
-  if (splits > B) splits = B;
-  if (CY >= 16) {
-    const int NT = (CX * KS + 15) / 16, NG = (NT + 15) / 16, MT = (CY + 15) / 16;
-    const int cxr = (16 * 16) / KS + 2 < CX ? (16 * 16) / KS + 2 : CX;          // input-channel rows a column group touches
-    const size_t l2 = ((size_t)16 * L + (size_t)cxr * (L + 16)) * sizeof(float);
-    int sp = 512 / (MT * NG);
-    if (sp < 1) sp = 1;
-    if (sp > B) sp = B;
-    ACD_LDS((k_acd_dw_m<KS, CONVT>), l2);
-    k_acd_dw_m<KS, CONVT><<<dim3(MT * NG, sp), 256, l2, st>>>(Yg, Xg, gw, gb, CY, CX, L, B, NG);
-    return;
-  }
-  ACD_LDS((k_acd_dw<KS, CONVT>), lds);
-  k_acd_dw<KS, CONVT><<<dim3(nblk, splits), 256, lds, st>>>(Yg, Xg, gw, gb, CY, CX, L, B);
-}
-
 int AcdaeModel::backward(const float* dy, float* dx, int B, hipStream_t st) {
-  AcdaeModel* const m = this;
   if (!dy) return ral_fail("ral_backward: dy is NULL");
-  if (!m->cfg.train || !m->grads) return ral_fail("ACDAE backward needs train=1 and a bound gradient buffer");
-  if (B != m->last_B) return ral_fail("backward batch %d != forward batch %d", B, m->last_B);
-  const int L = m->cfg.L, grid = B < 1024 ? B : 1024;
-  const AOff& Y = m->off;
-  (void)hipMemsetAsync(m->grads, 0, (size_t)lay.nparam * sizeof(float), st);
-  // decoder blocks, last to first: g = gradient at the block output
-  const float* g = dy;
-  for (int i = 3; i >= 0; --i) {
-    const int cin = ACH[4 - i], cout = ACH[3 - i], lin = L >> (4 - i), ks = AKS[3 - i];
-    const float* in = i == 0 ? m->e[3] : m->d[i - 1];
-    float* gin = i == 0 ? m->ge[3] : m->gd[i - 1];
-    const size_t lds = ((size_t)cout * lin * 2 + (size_t)cout * (lin + 16) + 3 * cout + 16) * sizeof(float);
-    if (ks == 13) {
-      ACD_LDS(k_acd_dec_bwd<13>, lds);
-      k_acd_dec_bwd<13><<<grid, 256, lds, st>>>(g, m->a[i], m->s[i], m->params + Y.dw[i], m->params + Y.de[i], m->dt[i], gin, m->grads + Y.de[i], cin, cout, lin, B);
-      launch_acd_dw<13, true>(m->dt[i], in, m->grads + Y.dw[i], m->grads + Y.db[i], cout, cin, lin, B, st);
-    } else {
-      ACD_LDS(k_acd_dec_bwd<7>, lds);
-      k_acd_dec_bwd<7><<<grid, 256, lds, st>>>(g, m->a[i], m->s[i], m->params + Y.dw[i], m->params + Y.de[i], m->dt[i], gin, m->grads + Y.de[i], cin, cout, lin, B);
-      launch_acd_dw<7, true>(m->dt[i], in, m->grads + Y.dw[i], m->grads + Y.db[i], cout, cin, lin, B, st);
+  if (!cfg.train || !grads) return ral_fail("ACDAE backward needs train=1 and a bound gradient buffer");
+  if (B != last_B) return ral_fail("backward batch %d != forward batch %d", B, last_B);
+  (void)hipMemsetAsync(grads, 0, (size_t)lay.nparam * sizeof(float), st);
+  const BPass pass = acdae_pass(cfg.L, B, true);
+  for (int k = 0; k < pass.n; ++k) {
+    const BLaunch& p = pass.e[k];
+    const int li = p.layer;
+    const AcdaeLayer& r = acdae_layers()[li];
+    // g: the gradient at the row's output; an encoder output also feeds a decoder row as its skip (g2: that row's output
+    // gradient).  The data kernel leaves dz at the conv output and gin at the row's input; the weight gradient is dz x input.
+    const float *in = li == 0 ? last_x : out[li - 1], *g = li == BASELINE_LAYERS - 1 ? dy : gout[li];
+    const float* g2 = skip_user[li] != BL_NONE ? gout[skip_user[li]] : nullptr;
+    const float *w = params + off.w[li], *ecaw = params + off.eca[li];
+    float* gin = li == 0 ? dx : gout[li - 1];
+    const int lin = cfg.L >> r.in_shift;
+#define DEC g, a[li], s[li], w, ecaw, dz[li], gin, grads + off.eca[li], r.cin, r.cout, lin, B
+#define ENC g, g2, out[li], amax[li], w, dz[li], gin, r.cin, r.cout, lin, B
+#define DW dz[li], in, grads + off.w[li], grads + off.b[li], r.cout, r.cin, lin, B
+    switch (p.kernel) {
+      GO(ACD_DEC_BWD_7, k_acd_dec_bwd<7>, DEC) GO(ACD_DEC_BWD_13, k_acd_dec_bwd<13>, DEC)
+      GO(ACD_ENC_BWD_13, k_acd_enc_bwd<13>, ENC) GO(ACD_ENC_BWD_7, k_acd_enc_bwd<7>, ENC)
+      GO(ACD_DW_M_13_C, (k_acd_dw_m<13, false>), DW, p.extra) GO(ACD_DW_M_7_C, (k_acd_dw_m<7, false>), DW, p.extra)
+      GO(ACD_DW_M_7_T, (k_acd_dw_m<7, true>), DW, p.extra) GO(ACD_DW_13_T, (k_acd_dw<13, true>), DW)
+      default: baseline_launch_missing("ACDAE backward", p);
     }
-    g = gin;
-  }
-  // encoder blocks: gradient at e[i] = input gradient of block i + 1 (ge[i]) + the decoder's skip gradient (gd[2 - i])
-  for (int i = 3; i >= 0; --i) {
-    const int cin = ACH[i], cout = ACH[i + 1], lin = L >> i;
-    const float* in = i == 0 ? m->last_x : m->e[i - 1];
-    const float* g2 = i < 3 ? m->gd[2 - i] : nullptr;
-    float* gin = i == 0 ? dx : m->ge[i - 1];
-    const size_t lds = (size_t)cout * (lin + 16) * sizeof(float);
-    if (AKS[i] == 13) {
-      ACD_LDS(k_acd_enc_bwd<13>, lds);
-      k_acd_enc_bwd<13><<<grid, 256, lds, st>>>(m->ge[i], g2, m->e[i], m->amax[i], m->params + Y.ew[i], m->dc[i], gin, cin, cout, lin, B);
-      launch_acd_dw<13, false>(m->dc[i], in, m->grads + Y.ew[i], m->grads + Y.eb[i], cout, cin, lin, B, st);
-    } else {
-      ACD_LDS(k_acd_enc_bwd<7>, lds);
-      k_acd_enc_bwd<7><<<grid, 256, lds, st>>>(m->ge[i], g2, m->e[i], m->amax[i], m->params + Y.ew[i], m->dc[i], gin, cin, cout, lin, B);
-      launch_acd_dw<7, false>(m->dc[i], in, m->grads + Y.ew[i], m->grads + Y.eb[i], cout, cin, lin, B, st);
-    }
+#undef DEC
+#undef ENC
+#undef DW
   }
   if (hipGetLastError() != hipSuccess) return ral_fail("ACDAE backward launch failed");
   return 0;
 }
+#undef GO

@@ -20,6 +20,7 @@
 #include "ral_ralenet.hpp"
 #include "ral_unet.hpp"
 #include "ral_unet_plan.hpp"
+#include "ral_baseline_plan.hpp"
 
 static thread_local char g_err[512] = "";
 int ral_fail(const char* fmt, ...) {
@@ -992,6 +993,53 @@ int ral_unet_stage_plan(int backward, int leads, int L, int B, int training, int
   if (lds_bytes) *lds_bytes = (int64_t)l.lds;
   if (fold) *fold = pp.fold ? 1 : 0;
   if (fused_eval) *fused_eval = pp.fused_eval ? 1 : 0;
+  return 0;
+}
+
+// the baseline queries refuse a (variant, leads, L) a model of that network refuses, in its words
+static int baseline_refused(int variant, int leads, int L) {
+  if (variant != RAL_ACDAE && variant != RAL_DANET) return ral_fail("baseline plan: variant must be ACDAE (%d) or DANet (%d), got %d", RAL_ACDAE, RAL_DANET, variant);
+  ral_config c;
+  memset(&c, 0, sizeof(c));
+  c.variant = variant; c.leads = leads; c.L = L;
+  const std::string why = variant == RAL_ACDAE ? acdae_legal(c) : danet_legal(c);
+  return why.empty() ? 0 : ral_fail("%s", why.c_str());
+}
+
+int ral_baseline_layer_geom(int variant, int leads, int i, int32_t* row, int cap) {
+  if (baseline_refused(variant, leads, 64)) return -1;      // (the rows do not depend on L: any length both networks take)
+  if (i < 0 || i >= BASELINE_LAYERS) return ral_fail("baseline row %d outside [0, %d]", i, BASELINE_LAYERS - 1);
+  int v[9], n;
+  if (variant == RAL_ACDAE) {
+    const AcdaeLayer& r = acdae_layers()[i];
+    const int a[7] = {r.cin, r.cout, r.ks, r.convt, r.in_shift, r.out_shift, r.skip};
+    n = 7; memcpy(v, a, sizeof(a));
+  } else {
+    const DanetCell& r = danet_cells(leads)[i];
+    const int a[9] = {r.cin, r.c, r.k, r.p, r.tr, r.in_shift, r.out_shift, r.in1, r.dam};
+    n = 9; memcpy(v, a, sizeof(a));
+  }
+  if (!row || cap < n) return ral_fail("baseline row: room for %d values is needed (got %d)", n, row ? cap : 0);
+  for (int j = 0; j < n; ++j) row[j] = v[j];
+  return 0;
+}
+
+int ral_baseline_pass_plan(int variant, int leads, int L, int B, int training, int backward, int k, char* kernel_name, int name_cap,
+                           int32_t* layer, int32_t* grid_x, int32_t* grid_y, int32_t* threads, int64_t* lds_bytes, int32_t* extra) {
+  if (baseline_refused(variant, leads, L)) return -1;
+  if (B < 1) return ral_fail("baseline plan: B must be positive (got %d)", B);
+  (void)training;      // a training and an eval forward launch the same: the kernels take the mode as an argument
+  const BPass pass = variant == RAL_ACDAE ? acdae_pass(L, B, backward != 0) : danet_pass(leads, L, B, backward != 0);
+  if (k < 0) return pass.n;
+  if (k >= pass.n) return ral_fail("baseline plan: launch %d outside [0, %d)", k, pass.n);
+  const BLaunch& l = pass.e[k];
+  if (kernel_name && name_cap > 0) snprintf(kernel_name, (size_t)name_cap, "%s", l.name);
+  if (layer) *layer = l.layer;
+  if (grid_x) *grid_x = l.gx;
+  if (grid_y) *grid_y = l.gy;
+  if (threads) *threads = l.threads;
+  if (lds_bytes) *lds_bytes = (int64_t)l.lds;
+  if (extra) *extra = l.extra;
   return 0;
 }
 

@@ -24,6 +24,8 @@
 // and skip the sums.)  The backward pass mirrors it: every BatchNorm backward needs sum(dy) and sum(dy * xhat) over the
 // batch, so it is cut at the same places - k_dn_dam_b, k_dn_fcn_bmid, k_dn_bn_b, k_dn_act_b, k_dn_fcn_bmid, k_dn_conv_b -
 // with weight gradients accumulated per workgroup in LDS and added to the gradient buffer once at the end.
+// The cells' shapes, the order of these launches and each one's instance, grid and LDS are the plan's (danet_cells, danet_pass:
+// ral_baseline_plan.hip); the host model at the end of this file executes the plan's entries.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -35,14 +37,13 @@
 
 #include "ral_model.hpp"
 #include "ral_device.hpp"
+#include "ral_baseline_plan.hpp"
 
 namespace {
-const int ENC_CH[4] = {4, 8, 16, 32}, ENC_K[4] = {17, 17, 3, 3}, ENC_P[4] = {8, 8, 1, 1};
-const int DEC_CH[4] = {16, 8, 4, 2}, DEC_K[4] = {4, 4, 18, 18}, DEC_P[4] = {1, 1, 8, 8};
 constexpr float BN_EPS = 1e-5f, BN_MOM = 0.1f;
-constexpr int NT = 256;           // threads per workgroup
+constexpr int NT = BASELINE_THREADS;   // threads per workgroup
 constexpr int MAXC = 64;          // widest descriptor (2 x 32)
-constexpr int CH = 12;            // zero halo of the conv tiles in LDS (>= 9 = the widest tap reach, multiple of 4)
+constexpr int CH = DANET_HALO;    // zero halo of the conv tiles in LDS (>= 9 = the widest tap reach, multiple of 4)
 // sum-buffer slots of a cell (doubles): forward column sums, then the sums of the BatchNorm backwards
 enum { S_AH1 = 0, S_AH2 = 128, S_BN = 192, S_DH1 = 256, S_DH2 = 384, T_D2 = 512, T_D1 = 640, T_BN = 768, T_A2 = 832, T_A1 = 896, S_CELL = 1024 };
 
@@ -943,15 +944,15 @@ void dbuild(const ral_config& c, ParamLayout& Y, CellOff cell[8]) {
     f.bn2 = bn(pre + ".4", dout);
     return f;
   };
-  int cin = c.leads;
-  for (int i = 0; i < 8; ++i) {
+  const DanetCell* const tab = danet_cells(c.leads);
+  int nenc = 0, ndec = 0;
+  for (int i = 0; i < BASELINE_LAYERS; ++i) {
     CellOff& K = cell[i];
-    const bool enc = i < 4;
-    const int j = enc ? i : i - 4;
-    const int C = enc ? ENC_CH[j] : DEC_CH[j];
-    K.g.cin = cin; K.g.c = C; K.g.k = enc ? ENC_K[j] : DEC_K[j]; K.g.p = enc ? ENC_P[j] : DEC_P[j]; K.g.tr = enc ? 0 : 1;
-    K.g.lin = enc ? c.L >> j : c.L >> (4 - j); K.g.lout = enc ? c.L >> (j + 1) : c.L >> (3 - j); K.g.dam = (!enc && j < 3) ? 1 : 0;
-    const std::string pre = enc ? "enc.EncoderList.cell" + std::to_string(j) : "dec.DecoderList." + std::to_string(j);
+    const DanetCell& r = tab[i];
+    const bool enc = !r.tr;
+    const int C = r.c, cin = r.cin;
+    K.g = Geo{r.cin, r.c, r.k, r.p, r.tr, c.L >> r.in_shift, c.L >> r.out_shift, r.dam};
+    const std::string pre = enc ? "enc.EncoderList.cell" + std::to_string(nenc++) : "dec.DecoderList." + std::to_string(ndec++);
     const std::string cv = enc ? ".conv" : ".deconv";
     K.cw = enc ? param(pre + cv + ".weight", {C, cin, K.g.k}) : param(pre + cv + ".weight", {cin, C, K.g.k});
     K.cb = param(pre + cv + ".bias", {C});
@@ -968,7 +969,6 @@ void dbuild(const ral_config& c, ParamLayout& Y, CellOff cell[8]) {
       }
       K.saw = param(pre + ".dam.convsa.weight", {1, 2, 1}); K.sab = param(pre + ".dam.convsa.bias", {1});
     }
-    cin = C;
   }
 }
 }  // namespace
@@ -976,39 +976,50 @@ void dbuild(const ral_config& c, ParamLayout& Y, CellOff cell[8]) {
 struct DanetModel : ral_handle {
   CellOff cell[8];
   float *z[8], *a[8], *out[8], *desc[8], *h1[8], *h2[8], *pool[8], *dh1[8], *dh2[8];   // forward tensors per cell
-  float *g[8], *gs[4], *dy2[8], *dy1[8], *ddy2[8], *ddy1[8];                           // backward tensors
+  float *g[8], *gs[8], *dy2[8], *dy1[8], *ddy2[8], *ddy1[8];                           // backward tensors per cell
+  int in1_user[8];                   // the decoder cell that adds cell i's output to its input (it writes gs[i]), or BL_NONE
   double* sums = nullptr;            // 8 x S_CELL
   const float* last_x = nullptr; int last_B = 0; bool last_training = false;
+  // the last forward [0] and backward [1] pass planned and its batch: planning on every call showed as host time in the
+  // 38-launch eval forward at small batches
+  BPass pass[2]; int pass_B[2] = {0, 0};
+  const BPass& pass_for(int B, bool backward) {
+    if (pass_B[backward] != B) { pass[backward] = danet_pass(cfg.leads, cfg.L, B, backward); pass_B[backward] = B; }
+    return pass[backward];
+  }
   int init() override;
   int forward(const float* x, float* y, int B, int training, hipStream_t st) override;
   int backward(const float* dy, float* dx, int B, hipStream_t st) override;
 };
 
 static int danet_check_cfg(const ral_config* c) {
-  if (c->leads != 2) return ral_fail("DANet: the last decoder cell has 2 output channels, so leads must be 2 (got %d)", c->leads);
-  if (c->L < 32 || c->L % 16 != 0 || c->L > 2048) return ral_fail("DANet: L must be a multiple of 16 in [32, 2048], got %d", c->L);
+  const std::string why = danet_legal(*c);
+  if (!why.empty()) return ral_fail("%s", why.c_str());
   if (c->max_batch < 1) return ral_fail("DANet: max_batch must be positive");
   return 0;
 }
 static void danet_layout(const ral_config& c, ParamLayout& L) { CellOff cell[8]; dbuild(c, L, cell); }
 
-static size_t danet_plan(const ral_config& c, DanetModel* m, char* base) {
-  CellOff own[8];
-  const CellOff* cell = m ? m->cell : own;
-  if (!m) { ParamLayout Y; dbuild(c, Y, own); }
+static size_t danet_workspace(const ral_config& c, DanetModel* m, char* base) {
+  const DanetCell* const tab = danet_cells(c.leads);
+  int user[BASELINE_LAYERS];
+  for (int i = 0; i < BASELINE_LAYERS; ++i) user[i] = BL_NONE;
+  for (int i = 0; i < BASELINE_LAYERS; ++i)
+    if (tab[i].in1 != BL_NONE) user[tab[i].in1] = i;
   size_t cur = 0;
   const size_t B = c.max_batch;
   auto take = [&](size_t floats) -> float* { float* p = base ? reinterpret_cast<float*>(base + cur) : nullptr; cur += (floats * 4 + 255) & ~size_t(255); return p; };
-  for (int i = 0; i < 8; ++i) {
-    const Geo& G = cell[i].g;
-    const size_t n = B * G.c * G.lout;
+  for (int i = 0; i < BASELINE_LAYERS; ++i) {
+    const DanetCell& G = tab[i];
+    const size_t n = B * G.c * (c.L >> G.out_shift);
+    if (m) m->in1_user[i] = user[i];
     float *pz = take(n), *pa = take(n), *po = take(n), *pd = take(B * 2 * G.c), *p1 = take(B * 2 * G.c), *p2 = take(B * G.c);
     float *pp = G.dam ? take(2 * B * G.c) : nullptr, *q1 = G.dam ? take(2 * B * G.c) : nullptr, *q2 = G.dam ? take(2 * B * G.c) : nullptr;
     if (m) { m->z[i] = pz; m->a[i] = pa; m->out[i] = po; m->desc[i] = pd; m->h1[i] = p1; m->h2[i] = p2; m->pool[i] = pp; m->dh1[i] = q1; m->dh2[i] = q2; }
     if (c.train) {
-      float *pg = take(n), *pgs = i < 3 ? take(n) : nullptr, *r2 = take(B * G.c), *r1 = take(B * 2 * G.c);
+      float *pg = take(n), *pgs = user[i] != BL_NONE ? take(n) : nullptr, *r2 = take(B * G.c), *r1 = take(B * 2 * G.c);
       float *s2 = G.dam ? take(2 * B * G.c) : nullptr, *s1 = G.dam ? take(2 * B * G.c) : nullptr;
-      if (m) { m->g[i] = pg; if (i < 4) m->gs[i] = pgs; m->dy2[i] = r2; m->dy1[i] = r1; m->ddy2[i] = s2; m->ddy1[i] = s1; }
+      if (m) { m->g[i] = pg; m->gs[i] = pgs; m->dy2[i] = r2; m->dy1[i] = r1; m->ddy2[i] = s2; m->ddy1[i] = s1; }
     }
   }
   double* ps = reinterpret_cast<double*>(take(8 * S_CELL * 2));
@@ -1018,9 +1029,9 @@ static size_t danet_plan(const ral_config& c, DanetModel* m, char* base) {
 
 int DanetModel::init() {
   dbuild(cfg, lay, cell);
-  const size_t bytes = danet_plan(cfg, this, nullptr);
+  const size_t bytes = danet_workspace(cfg, this, nullptr);
   if (alloc_slab(bytes) != hipSuccess) return ral_fail("hipMalloc(%zu) failed", bytes);
-  danet_plan(cfg, this, slab);
+  danet_workspace(cfg, this, slab);
   return 0;
 }
 
@@ -1028,7 +1039,7 @@ const RalKind* danet_kind() {
   static const RalKind k = {
       danet_check_cfg,
       danet_layout,
-      [](const ral_config& c) { return danet_plan(c, nullptr, nullptr); },
+      [](const ral_config& c) { return danet_workspace(c, nullptr, nullptr); },
       0,     // (its batch sums live in its own workspace)
       []() -> ral_handle* { return new DanetModel(); },
       "U-Net / DANet have a BatchNorm per layer: use ral_forward (per-rank statistics)"};
@@ -1048,124 +1059,100 @@ Fcn mk_fcn(const ral_handle& P, const FcnOff& o) {
   f.bn1 = mk_bn(P, o.bn1); f.bn2 = mk_bn(P, o.bn2); f.din = o.din; f.dh = o.dh; f.dout = o.dout;
   return f;
 }
-template <class K> void set_lds(K kernel, size_t bytes) {
-  if (bytes > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
+// the tensors and sum slots of one fcn of a cell: the APReLU's (np = 1) or the DAM's (np = 2 paths)
+struct FcnPath { const Fcn& F; float *h1, *h2, *d2, *d1; int s1, s2, t2, t1; };
 }  // namespace
 
+// ---- forward and backward execute the entries of a pass (danet_pass) in order and never choose: each entry's pointers come from
+// its cell, and one switch over the enumerators starts the kernel - a case per instance, one argument list per family
+#define GO(e, kernel, ...) \
+  case BKernel::e: RAL_SET_LDS((kernel), p.lds); kernel<<<dim3(p.gx, p.gy), p.threads, p.lds, st>>>(__VA_ARGS__); break;
+
 int DanetModel::forward(const float* x, float* y, int B, int training, hipStream_t st) {
-  DanetModel* const m = this;
-  if (!m->params || !m->state) return ral_fail("ral_bind was not called");
-  if (B <= 0 || B > m->cfg.max_batch) return ral_fail("batch %d outside (0, %d]", B, m->cfg.max_batch);
+  if (!params || !state) return ral_fail("ral_bind was not called");
+  if (B <= 0 || B > cfg.max_batch) return ral_fail("batch %d outside (0, %d]", B, cfg.max_batch);
   if (training && B < 2) return ral_fail("DANet: a training forward needs at least 2 windows (BatchNorm over the batch of descriptors)");
-  constexpr int gf = 1024;
-  const int grid = B < gf ? B : gf;
-  constexpr int gdesc = 256;   // descriptor-level kernels: a wave per window,
-  const int gridd = (B + 15) / 16 < gdesc ? (B + 15) / 16 : gdesc;                                   // 16 windows per workgroup and pass
-  constexpr int gact = 256;    // elementwise kernels: EW = 4 windows per pass
-  const int grida = (B + 3) / 4 < gact ? (B + 3) / 4 : gact;
-  if (training) (void)hipMemsetAsync(m->sums, 0, sizeof(double) * 8 * S_CELL, st);
-  m->last_x = x; m->last_B = B; m->last_training = training != 0;
-  for (int i = 0; i < 8; ++i) {
-    const CellOff& K = m->cell[i];
+  if (training) (void)hipMemsetAsync(sums, 0, sizeof(double) * 8 * S_CELL, st);
+  last_x = x; last_B = B; last_training = training != 0;
+  const BPass& pass = pass_for(B, false);
+  for (int k = 0; k < pass.n;) {          // cell by cell: the cell's pointers once, then its entries
+    const int i = pass.e[k].layer, in1c = danet_cells(cfg.leads)[i].in1;
+    const CellOff& K = cell[i];
     const Geo& G = K.g;
-    double* S = m->sums + (size_t)i * S_CELL;
-    const Fcn Fa = mk_fcn(*m, K.act);
-    const Bn bn = mk_bn(*m, K.bn);
-    const float* in0 = i == 0 ? x : m->out[i - 1];
-    const float* in1 = i >= 5 ? m->out[7 - i] : nullptr;     // decoder cells 1..3 add encoder features 2, 1, 0
-    float* out = i == 7 ? y : m->out[i];
-    const size_t nz = (size_t)G.c * G.lout;
-    const size_t l1 = ((size_t)G.cin * (G.lin + 2 * CH) + nz + 2 * G.c) * sizeof(float);
-    auto conv = [&](auto kern) {
-      set_lds(kern, l1);
-      kern<<<grid, NT, l1, st>>>(in0, in1, m->params + K.cw, m->params + K.cb, G, Fa, m->z[i], m->desc[i], m->h1[i],
-                                 training ? S + S_AH1 : nullptr, B);
-    };
-    if (G.k == 17) conv(k_dn_conv<17, false>); else if (G.k == 3) conv(k_dn_conv<3, false>);
-    else if (G.k == 4) conv(k_dn_conv<4, true>); else conv(k_dn_conv<18, true>);
-    k_dn_fcn_mid<<<gridd, NT, 0, st>>>(m->h1[i], S + S_AH1, Fa, m->h2[i], training ? S + S_AH2 : nullptr, 1, B, training);
-    if (G.lout % 4 == 0) k_dn_act<4><<<grida, NT, 0, st>>>(m->z[i], m->h2[i], S + S_AH2, Fa, G, m->a[i], training ? S + S_BN : nullptr, B, training);
-    else k_dn_act<1><<<grida, NT, 0, st>>>(m->z[i], m->h2[i], S + S_AH2, Fa, G, m->a[i], training ? S + S_BN : nullptr, B, training);
-    Fcn Fd = Fa;
-    if (G.dam) {
-      Fd = mk_fcn(*m, K.dam);
-      const size_t l2 = nz * sizeof(float);
-      set_lds(k_dn_dam1, l2);
-      k_dn_dam1<<<grid, NT, l2, st>>>(m->a[i], S + S_BN, bn, Fd, G, m->pool[i], m->dh1[i], training ? S + S_DH1 : nullptr, B, training);
-      k_dn_fcn_mid<<<gridd, NT, 0, st>>>(m->dh1[i], S + S_DH1, Fd, m->dh2[i], training ? S + S_DH2 : nullptr, 2, B, training);
+    double* S = sums + (size_t)i * S_CELL;
+    auto sum = [&](int slot) { return training ? S + slot : nullptr; };          // batch sums are collected in training only
+    const Fcn Fa = mk_fcn(*this, K.act), Fd = G.dam ? mk_fcn(*this, K.dam) : Fa;
+    const Bn bn = mk_bn(*this, K.bn);
+    const float *in0 = i == 0 ? x : out[i - 1], *in1 = in1c != BL_NONE ? out[in1c] : nullptr;
+    const float *saw = G.dam ? params + K.saw : nullptr, *sab = G.dam ? params + K.sab : nullptr;
+    float* o = i == BASELINE_LAYERS - 1 ? y : out[i];
+#define CONV in0, in1, params + K.cw, params + K.cb, G, Fa, z[i], desc[i], h1[i], sum(S_AH1), B
+#define ACT z[i], h2[i], S + S_AH2, Fa, G, a[i], sum(S_BN), B, training
+    const FcnPath fa{Fa, h1[i], h2[i], dy2[i], dy1[i], S_AH1, S_AH2, T_A2, T_A1}, fd{Fd, dh1[i], dh2[i], ddy2[i], ddy1[i], S_DH1, S_DH2, T_D2, T_D1};
+    for (; k < pass.n && pass.e[k].layer == i; ++k) {
+      const BLaunch& p = pass.e[k];
+      const FcnPath& f = p.extra == 2 ? fd : fa;      // (read by the fcn entries: the plan says which fcn of the cell they run)
+      switch (p.kernel) {
+        GO(DN_CONV_17_C, (k_dn_conv<17, false>), CONV) GO(DN_CONV_3_C, (k_dn_conv<3, false>), CONV)
+        GO(DN_CONV_4_T, (k_dn_conv<4, true>), CONV) GO(DN_CONV_18_T, (k_dn_conv<18, true>), CONV)
+        GO(DN_FCN_MID, k_dn_fcn_mid, f.h1, S + f.s1, f.F, f.h2, sum(f.s2), p.extra, B, training)
+        GO(DN_ACT_4, k_dn_act<4>, ACT) GO(DN_ACT_1, k_dn_act<1>, ACT)
+        GO(DN_DAM1, k_dn_dam1, a[i], S + S_BN, bn, Fd, G, pool[i], dh1[i], sum(S_DH1), B, training)
+        GO(DN_OUT, k_dn_out, a[i], S + S_BN, bn, G, dh2[i], S + S_DH2, Fd, saw, sab, o, B, training, G.dam ? 0 : 1)
+        default: baseline_launch_missing("DANet forward", p);
+      }
     }
-    const size_t l3 = (nz + G.lout) * sizeof(float);
-    set_lds(k_dn_out, l3);
-    k_dn_out<<<grid, NT, l3, st>>>(m->a[i], S + S_BN, bn, G, m->dh2[i], S + S_DH2, Fd, G.dam ? m->params + K.saw : nullptr,
-                                    G.dam ? m->params + K.sab : nullptr, out, B, training, G.dam ? 0 : 1);
+#undef CONV
+#undef ACT
   }
   if (hipGetLastError() != hipSuccess) return ral_fail("DANet forward launch failed");
   return 0;
 }
 
 int DanetModel::backward(const float* dy, float* dx, int B, hipStream_t st) {
-  DanetModel* const m = this;
   if (!dy) return ral_fail("ral_backward: dy is NULL");
-  if (!m->cfg.train || !m->grads) return ral_fail("DANet backward needs train=1 and a bound gradient buffer");
-  if (B != m->last_B || !m->last_training) return ral_fail("DANet backward needs a training forward of the same batch first");
-  constexpr int gb = 1024;   // (train step at batch 2048: 3.84 / 3.58 / 4.43 ms with 512 / 1024 / 2048)
-  const int grid = B < gb ? B : gb;
-  constexpr int gdesc = 256;   // descriptor-level kernels (see danet_forward)
-  const int gridd = (B + 15) / 16 < gdesc ? (B + 15) / 16 : gdesc;
-  constexpr int gact = 256;    // elementwise kernels (see danet_forward)
-  const int grida = (B + 3) / 4 < gact ? (B + 3) / 4 : gact;
-  constexpr int gwin = 512;   // window-at-a-time kernels with column-sum flushes (train step at batch 2048: 2.33 / 2.23 / 2.26 / 2.44 ms with 1024 / 512 / 256 / 128)
-  const int gridw = B < gwin ? B : gwin;
-  (void)hipMemsetAsync(m->grads, 0, (size_t)m->lay.nparam * sizeof(float), st);
+  if (!cfg.train || !grads) return ral_fail("DANet backward needs train=1 and a bound gradient buffer");
+  if (B != last_B || !last_training) return ral_fail("DANet backward needs a training forward of the same batch first");
+  (void)hipMemsetAsync(grads, 0, (size_t)lay.nparam * sizeof(float), st);
   // the backward halves [T_D2, S_CELL) of the eight cells' sum records: one strided fill
-  (void)hipMemset2DAsync(m->sums + T_D2, sizeof(double) * S_CELL, 0, sizeof(double) * (S_CELL - T_D2), 8, st);
-  for (int i = 7; i >= 0; --i) {
-    const CellOff& K = m->cell[i];
+  (void)hipMemset2DAsync(sums + T_D2, sizeof(double) * S_CELL, 0, sizeof(double) * (S_CELL - T_D2), 8, st);
+  const BPass& pass = pass_for(B, true);
+  for (int k = 0; k < pass.n;) {          // cell by cell: the cell's pointers once, then its entries
+    const int i = pass.e[k].layer, in1c = danet_cells(cfg.leads)[i].in1;
+    const CellOff& K = cell[i];
     const Geo& G = K.g;
-    double* S = m->sums + (size_t)i * S_CELL;
-    const Fcn Fa = mk_fcn(*m, K.act);
-    const Bn bn = mk_bn(*m, K.bn);
-    const size_t nz = (size_t)G.c * G.lout;
-    // gradient(s) at the cell output: the last cell gets dy, decoder cells the next cell's input gradient, encoder cell
-    // 3 the first decoder cell's, encoder cells 0..2 the next encoder cell's plus the decoder's skip
-    const float* g0 = i == 7 ? dy : m->g[i];
-    const float* g1 = i < 3 ? m->gs[i] : nullptr;
-    float* work = m->g[i];                         // dxo / da live here (for i == 7: copy of dy's role)
-    Fcn Fd = Fa;
-    if (G.dam) {
-      Fd = mk_fcn(*m, K.dam);
-      const size_t l1 = (2 * nz + 3 * G.lout) * sizeof(float);
-      set_lds(k_dn_dam_b, l1);
-      k_dn_dam_b<<<gridw, NT, l1, st>>>(g0, m->a[i], S + S_BN, bn, G, m->dh2[i], S + S_DH2, Fd, m->params + K.saw, m->params + K.sab,
-                                        m->grads + K.saw, m->grads + K.sab, work, m->ddy2[i], S + T_D2, B);
-      const size_t l2 = ((size_t)Fd.dout * Fd.dh + Fd.dout) * sizeof(float);
-      k_dn_fcn_bmid<<<gridd, NT, l2, st>>>(m->ddy2[i], S + T_D2, m->dh2[i], S + S_DH2, m->dh1[i], S + S_DH1, Fd, m->ddy1[i], S + T_D1, 2, B);
-      g0 = work; g1 = nullptr;
+    double* S = sums + (size_t)i * S_CELL;
+    const Fcn Fa = mk_fcn(*this, K.act), Fd = G.dam ? mk_fcn(*this, K.dam) : Fa;
+    const Bn bn = mk_bn(*this, K.bn);
+    // gradient(s) at the cell output: the last cell gets dy, every other cell the next cell's input gradient (g[i]), an encoder
+    // cell whose output a decoder cell added to its input that cell's as well (gs[i]); dxo / da live in g[i] (work).  A DAM
+    // cell's k_dn_dam_b has consumed them into work before k_dn_bn_b runs.
+    float* work = g[i];
+    const float* gout = i == BASELINE_LAYERS - 1 ? dy : g[i];
+    const float *g0 = G.dam ? work : gout, *g1 = !G.dam && in1_user[i] != BL_NONE ? gs[i] : nullptr;
+    const float *in0 = i == 0 ? last_x : out[i - 1], *in1 = in1c != BL_NONE ? out[in1c] : nullptr;
+    float *gi0 = i == 0 ? dx : g[i - 1], *gi1 = in1c != BL_NONE ? gs[in1c] : nullptr;
+#define ACTB work, a[i], z[i], S + S_BN, S + T_BN, bn, G, h2[i], S + S_AH2, Fa, dy2[i], S + T_A2, B
+#define CONVB work, z[i], in0, in1, params + K.cw, grads + K.cw, grads + K.cb, G, dy1[i], S + T_A1, h1[i], S + S_AH1, h2[i], S + S_AH2, desc[i], Fa, gi0, gi1, B
+    const FcnPath fa{Fa, h1[i], h2[i], dy2[i], dy1[i], S_AH1, S_AH2, T_A2, T_A1}, fd{Fd, dh1[i], dh2[i], ddy2[i], ddy1[i], S_DH1, S_DH2, T_D2, T_D1};
+    for (; k < pass.n && pass.e[k].layer == i; ++k) {
+      const BLaunch& p = pass.e[k];
+      const FcnPath& f = p.extra == 2 ? fd : fa;      // (read by the fcn entries: the plan says which fcn of the cell they run)
+      switch (p.kernel) {
+        GO(DN_DAM_B, k_dn_dam_b, gout, a[i], S + S_BN, bn, G, dh2[i], S + S_DH2, Fd, params + K.saw, params + K.sab,
+           grads + K.saw, grads + K.sab, work, ddy2[i], S + T_D2, B)
+        GO(DN_FCN_BMID, k_dn_fcn_bmid, f.d2, S + f.t2, f.h2, S + f.s2, f.h1, S + f.s1, f.F, f.d1, S + f.t1, p.extra, B)
+        GO(DN_BN_B, k_dn_bn_b, g0, g1, a[i], S + S_BN, bn, G, ddy1[i], S + T_D1, dh1[i], S + S_DH1, pool[i], Fd, work, S + T_BN, B)
+        GO(DN_ACT_B_4, k_dn_act_b<4>, ACTB) GO(DN_ACT_B_1, k_dn_act_b<1>, ACTB)
+        GO(DN_CONV_B_17_C, (k_dn_conv_b<17, false>), CONVB) GO(DN_CONV_B_3_C, (k_dn_conv_b<3, false>), CONVB)
+        GO(DN_CONV_B_4_T, (k_dn_conv_b<4, true>), CONVB) GO(DN_CONV_B_18_T, (k_dn_conv_b<18, true>), CONVB)
+        default: baseline_launch_missing("DANet backward", p);
+      }
     }
-    const size_t l3 = (nz + (G.dam ? (size_t)Fd.dh * Fd.din + Fd.dh : 0)) * sizeof(float);
-    set_lds(k_dn_bn_b, l3);
-    k_dn_bn_b<<<gridw, NT, l3, st>>>(g0, g1, m->a[i], S + S_BN, bn, G, m->ddy1[i], S + T_D1, m->dh1[i], S + S_DH1, m->pool[i], Fd,
-                                     work, S + T_BN, B);
-    if (G.lout % 4 == 0) k_dn_act_b<4><<<grida, NT, 0, st>>>(work, m->a[i], m->z[i], S + S_BN, S + T_BN, bn, G, m->h2[i], S + S_AH2, Fa, m->dy2[i], S + T_A2, B);
-    else k_dn_act_b<1><<<grida, NT, 0, st>>>(work, m->a[i], m->z[i], S + S_BN, S + T_BN, bn, G, m->h2[i], S + S_AH2, Fa, m->dy2[i], S + T_A2, B);
-    const size_t l4 = ((size_t)Fa.dout * Fa.dh + Fa.dout) * sizeof(float);
-    set_lds(k_dn_fcn_bmid, l4);
-    k_dn_fcn_bmid<<<gridd, NT, l4, st>>>(m->dy2[i], S + T_A2, m->h2[i], S + S_AH2, m->h1[i], S + S_AH1, Fa, m->dy1[i], S + T_A1, 1, B);
-    const float* in0 = i == 0 ? m->last_x : m->out[i - 1];
-    const float* in1 = i >= 5 ? m->out[7 - i] : nullptr;
-    float* gi0 = i == 0 ? dx : m->g[i - 1];
-    float* gi1 = i >= 5 ? m->gs[7 - i] : nullptr;
-    const size_t l5 = ((size_t)G.cin * (G.lin + 2 * CH) + (size_t)G.c * (G.lout + 2 * CH) + (size_t)G.c * G.cin * G.k + G.c +
-                       (size_t)Fa.dh * Fa.din + Fa.dh) * sizeof(float);
-    auto convb = [&](auto kern) {
-      set_lds(kern, l5);
-      kern<<<grid, NT, l5, st>>>(work, m->z[i], in0, in1, m->params + K.cw, m->grads + K.cw, m->grads + K.cb, G, m->dy1[i], S + T_A1,
-                                 m->h1[i], S + S_AH1, m->h2[i], S + S_AH2, m->desc[i], Fa, gi0, gi1, B);
-    };
-    if (G.k == 17) convb(k_dn_conv_b<17, false>); else if (G.k == 3) convb(k_dn_conv_b<3, false>);
-    else if (G.k == 4) convb(k_dn_conv_b<4, true>); else convb(k_dn_conv_b<18, true>);
+#undef ACTB
+#undef CONVB
   }
   if (hipGetLastError() != hipSuccess) return ral_fail("DANet backward launch failed");
   return 0;
 }
+#undef GO

@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
-@pytest.mark.parametrize("L,B", [(512, 4), (256, 3), (1024, 2)])
+@pytest.mark.parametrize("L,B", [(512, 4), (256, 3), (1024, 2), (64, 3), (192, 2)])
 def test_acdae_train_step_matches_oracle(L, B):
     from ecg_denoise_amd import ACDAE
     p32 = O.init_params(O.acdae_param_shapes(), 1234)
