@@ -41,6 +41,7 @@ from .beats import (BeatDetector, BeatPool, Beats, BeatScores, beat_bank, beat_f
 from .rhythm import (BeatClasses, BeatClassifier, BeatClassPool, evaluate_rhythm, rhythm_check, rhythm_geometry)  # noqa: F401
 from .delineate import (BeatDelineator, Fiducials, IntervalEvaluation, delineate_check, delineate_geometry,  # noqa: F401
                         evaluate_intervals, interval_scores)
+from .pst import (PStEvaluation, PStMeasurer, PStPoints, evaluate_pst, pst_check, pst_geometry, pst_scores)  # noqa: F401
 from .hrv import (HrvAnalyzer, HrvEvaluation, HrvPool, HrvPoolState, HrvWindows, evaluate_hrv, hrv_check, hrv_geometry,  # noqa: F401
                   hrv_windows)
 from .template import (BeatTemplates, MedianBeat, TemplateEvaluation, evaluate_templates, template_check,  # noqa: F401

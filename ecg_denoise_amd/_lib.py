@@ -43,6 +43,11 @@ class DelinGeom(C.Structure):
                 ("wt", C.c_int32), ("q0", C.c_float)]
 
 
+class PstGeom(C.Structure):
+    """ral_pst_geom: the P / ST measurement's four lengths in samples, the scale of the ST level and the P threshold"""
+    _fields_ = [("m2", C.c_int32), ("g", C.c_int32), ("wp", C.c_int32), ("j", C.c_int32), ("w", C.c_float), ("p0", C.c_float)]
+
+
 class TemplateGeom(C.Structure):
     """ral_template_geom: the median beat's two half-lengths, its window and hop in samples, and the most beats of a template"""
     _fields_ = [("wpre", C.c_int32), ("wpost", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("kmax", C.c_int32)]
@@ -174,6 +179,8 @@ _SIGS = {
                                   C.c_int, _VP, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
     "ral_delineate_records": (C.c_int, [_VP, C.c_int64, C.c_int, C.c_int64, C.POINTER(DelinGeom), _VP, _VP, C.c_int64, _VP, _VP, _VP,
                                         _VP, _VP]),
+    "ral_pst_records": (C.c_int, [_VP, C.c_int64, C.c_int, C.c_int64, C.POINTER(PstGeom), _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP,
+                                  _VP, _VP]),
     "ral_template_records": (C.c_int, [_VP, C.c_int64, C.c_int, C.c_int64, C.POINTER(TemplateGeom), _VP, _VP, _VP, C.c_int64,
                                        C.c_int64, _VP, _VP, _VP, _VP, _VP]),
     "ral_hrv_windows": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int64, _VP, C.c_int, C.POINTER(HrvGeom), _VP, _VP,

@@ -839,6 +839,19 @@ int ral_delineate_records(const float* x, int64_t R, int leads, int64_t T, const
   return 0;
 }
 
+int ral_pst_records(const float* x, int64_t R, int leads, int64_t T, const ral_pst_geom* geom, const int32_t* peaks,
+                    const int32_t* count, int64_t cap, const int32_t* on, const int32_t* off, int32_t* pon, int32_t* ppeak,
+                    int32_t* poff, float* st, ral_stream s) {
+  if (!x || !geom || !peaks || !count || !on || !off || !pon || !ppeak || !poff || !st) return ral_fail("pst_records: null pointer");
+  const char* why = nullptr;
+  if (launch_pst_records(x, (long long)R, leads, (long long)T, geom, peaks, count, (long long)cap, on, off, pon, ppeak, poff, st,
+                         (hipStream_t)s, &why))
+    return ral_fail("pst_records: need %s (R=%lld leads=%d T=%lld cap=%lld m2=%d g=%d Wp=%d j=%d w=%g p0=%g)", why, (long long)R,
+                    leads, (long long)T, (long long)cap, geom->m2, geom->g, geom->wp, geom->j, geom->w, geom->p0);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 int ral_template_records(const float* x, int64_t R, int leads, int64_t T, const ral_template_geom* geom, const int32_t* peaks,
                          const int32_t* label_or_null, const int32_t* count, int64_t cap, int64_t nw, float* tpl, int32_t* used,
                          int32_t* total, int32_t* rr, ral_stream s) {

@@ -14,12 +14,12 @@
 //
 // Launch: one, grid (cap, R), a wave per beat (a beat at or beyond count writes the padding).
 #include "ral_kernels.hpp"
+#include "ral_wave_pick.hpp"
 #include <math.h>
 #include <stdint.h>
 
 namespace {
 
-constexpr int DL_WAVE = 64;
 constexpr int DL_LDS_BYTES = 65536;            // the budget: what a kernel gets without opting into more
 
 struct DelinGeom {
@@ -29,47 +29,6 @@ struct DelinGeom {
 };
 
 size_t delin_lds_bytes(const DelinGeom& g) { return ((size_t)g.nd + g.na + g.ns) * sizeof(float); }
-
-RAL_DEV float delin_max(float v) {
-#pragma unroll
-  for (int o = DL_WAVE / 2; o; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, DL_WAVE));
-  return v;
-}
-
-RAL_DEV long long delin_shfl(long long v, int o) {
-  const int lo = __shfl_xor((int)(v & 0xffffffffLL), o, DL_WAVE), hi = __shfl_xor((int)(v >> 32), o, DL_WAVE);
-  return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-}
-
-RAL_DEV long long delin_imax(long long v) {
-#pragma unroll
-  for (int o = DL_WAVE / 2; o; o >>= 1) {
-    const long long w = delin_shfl(v, o);
-    v = w > v ? w : v;
-  }
-  return v;
-}
-
-RAL_DEV long long delin_imin(long long v) {
-#pragma unroll
-  for (int o = DL_WAVE / 2; o; o >>= 1) {
-    const long long w = delin_shfl(v, o);
-    v = w < v ? w : v;
-  }
-  return v;
-}
-
-// the largest value and the smallest index that has it, the same in every lane
-RAL_DEV void delin_argmax(float& v, long long& at) {
-#pragma unroll
-  for (int o = DL_WAVE / 2; o; o >>= 1) {
-    const float w = __shfl_xor(v, o, DL_WAVE);
-    const long long wa = delin_shfl(at, o);
-    if (w > v || (w == v && wa < at)) v = w, at = wa;
-  }
-}
-
-RAL_DEV long long delin_clamp(long long t, long long top) { return t < 0 ? 0 : (t > top ? top : t); }
 
 // grid (cap, R): beat blockIdx.x of record blockIdx.y
 __global__ __launch_bounds__(DL_WAVE) void k_delineate_records(const float* __restrict__ x, long long T, DelinGeom g,

@@ -158,6 +158,10 @@ int launch_rhythm_pool(const float* hist, const float* x, long long x_total, con
 int launch_delineate_records(const float* x, long long R, int leads, long long T, const ral_delin_geom* geom, const int* peaks,
                              const int* count, long long cap, int* on, int* off, int* tpeak, int* tend, hipStream_t s,
                              const char** why);
+// P wave and ST level (ral_pst.hip; ral_pst_records): -1 with *why for a refusal, before any launch
+int launch_pst_records(const float* x, long long R, int leads, long long T, const ral_pst_geom* geom, const int* peaks,
+                       const int* count, long long cap, const int* on, const int* off, int* pon, int* ppeak, int* poff, float* st,
+                       hipStream_t s, const char** why);
 // median beats (ral_template.hip; ral_template_records): -1 with *why, which names the argument, before any HIP call
 int launch_template_records(const float* x, long long R, int leads, long long T, const ral_template_geom* geom, const int* peaks,
                             const int* label, const int* count, long long cap, long long nw, float* tpl, int* used, int* total,

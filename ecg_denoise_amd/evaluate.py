@@ -63,7 +63,7 @@ def mix_records(records, noise, snr_db, offsets=None, rng=None):
 
 def stress_front(denoiser, records, noise, snr_db, offsets=None, rng=None):
     """the front of every noise-stress evaluation of a downstream statistic (`evaluate_beats`, `evaluate_rhythm`,
-    `evaluate_intervals`, `evaluate_hrv`): `mix_records(records, noise, snr_db, offsets, rng)`, then `denoiser.denoise(noisy)` ->
+    `evaluate_intervals`, `evaluate_hrv`, `evaluate_templates`, `evaluate_pst`): `mix_records(records, noise, snr_db, offsets, rng)`, then `denoiser.denoise(noisy)` ->
     (fs, device, clean, noisy, denoised); `fs` is the denoiser's outer rate, 360 Hz where it names none, `device` that of the
     records, where the caller's default detector, classifier and so on belong"""
     noisy, clean = mix_records(records, noise, snr_db, offsets, rng)            # (refuses anything but device tensors)

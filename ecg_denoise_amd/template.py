@@ -2,6 +2,7 @@
 
     tpl = MedianBeat(fs=360).average(records, beats, classes)      # whole records, ral_template_records -> BeatTemplates
     tpl.delineate(), tpl.intervals()                               # the template's fiducial points, QRS / QT / QTc per window
+    tpl.pst()                                                      # its P wave and ST level (`PStMeasurer`)
     ev = evaluate_templates(denoiser, records, noise, snr_db)      # the noise-stress protocol: is the shape of the beat back?
 
 The definition (include/ralenet.h has the same one).  Input (R, leads, T) fp32 at rate fs and, per record, strictly ascending
@@ -36,6 +37,7 @@ from .evaluate import stress_front
 from .hrv import _labels, _sec, hrv_windows
 from .intake import beat_lists, check_leads, device_records, record_shape
 from .model import _ptr, _stream
+from .pst import PStMeasurer, PStPoints
 from .rate import _rate
 from .rhythm import BeatClassifier
 
@@ -109,6 +111,23 @@ class BeatTemplates:
         if len(parts) == 1:
             return parts[0]
         return Fiducials(*(torch.cat([getattr(f, k) for f in parts]) for k in ("on", "off", "tpeak", "tend")), peaks, count, self.fs)
+
+    @torch.no_grad()
+    def pst(self, measurer=None, delineator=None, min_beats=3):
+        """-> the `PStPoints` of the templates, measured by `PStMeasurer` (default `PStMeasurer(fs)`) on the records and the
+        `Fiducials` of `delineate(delineator, min_beats)`: pon, ppeak, poff (R * nw, 1) and st (R * nw, 1, leads), indices
+        relative to the template.  A template's beat has no neighbour, so its P search is [on - Wp, on - g]."""
+        R, nw, leads, Wn = self.template.shape
+        ms = measurer or PStMeasurer(self.fs, device=self.template.device)
+        f = self.delineate(delineator, min_beats)
+        x = self.template.view(R * nw, leads, Wn)
+        keys = ("on", "off", "tpeak", "tend", "peaks", "count")
+        parts = [ms.measure(x[a:a + _MAX_RECORDS], Fiducials(*(getattr(f, k)[a:a + _MAX_RECORDS] for k in keys), f.fs))
+                 for a in range(0, R * nw, _MAX_RECORDS)]
+        if len(parts) == 1:
+            return parts[0]
+        return PStPoints(*(torch.cat([getattr(p, k) for p in parts]) for k in ("pon", "ppeak", "poff", "st")), f.on, f.peaks,
+                         f.count, self.fs)
 
     @torch.no_grad()
     def intervals(self, delineator=None, min_beats=3):

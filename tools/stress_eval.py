@@ -48,10 +48,16 @@ records' median beat at the same beats and classes, pooled over the windows with
 shares and errors of QRS duration and QT measured on the median beats (`evaluate_templates`; NaN where there is no such
 window).  Without the flag the output is what it was.
 
+`--pst` asks the sixth question, are the P wave and the ST level back: per cell one more line and a "pst" entry in the JSON
+with, for the noisy and for the denoised records, the share of the clean records' P waves that are still found, the mean absolute
+error of the PR interval in ms over the beats that have a P wave in both, and that of the ST level per lead over the beats that
+have one in both - `PStMeasurer` on `BeatDelineator` at the clean records' detections (`evaluate_pst`; NaN where there is no such
+beat; the ST error is in the unit of the mixed records, which `mix_records` z-scores).  Without the flag the output is what it was.
+
     python tools/stress_eval.py [--model full|nra|mlp|unet|acdae|danet|newrale] [--ckpt state_dict.pth] [--L 512]
                                 [--records 4] [--T 65000] [--overlap 0] [--batch 4096] [--time-shapes ...] [--reps 5] [--beats]
                                 [--classes] [--fft] [--fft-L 1000] [--hrv] [--hrv-win 60] [--hrv-hop 30] [--intervals]
-                                [--templates] [--template-win 10]
+                                [--templates] [--template-win 10] [--pst]
 """
 import argparse
 import json
@@ -65,8 +71,8 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from ecg_denoise_amd import (ACDAE, ClassicalDenoiser, DANet, NewRALE, RALENet, UNet, evaluate_beats, evaluate_hrv,  # noqa: E402
-                             evaluate_intervals, evaluate_rhythm, evaluate_templates, interval_scores, mix_records, score_records, synth,
-                             wavelet_denoise)
+                             evaluate_intervals, evaluate_pst, evaluate_rhythm, evaluate_templates, interval_scores, mix_records,
+                             pst_scores, score_records, synth, wavelet_denoise)
 from ecg_denoise_amd.data import NOISE_TYPES, TRUE_NOISE  # noqa: E402
 from ecg_denoise_amd.infer import StreamingDenoiser  # noqa: E402
 
@@ -149,6 +155,11 @@ def _intervals_cell(ev, idx):
     return {key: interval_scores(ev.clean, f, rows=idx)[2] for key, f in (("noisy", ev.noisy), ("denoised", ev.denoised))}
 
 
+def _pst_cell(ev, idx):
+    """the records idx of an `evaluate_pst` result -> the pooled share and errors, noisy and denoised"""
+    return {key: pst_scores(ev.clean, p, rows=idx)[2] for key, p in (("noisy", ev.noisy), ("denoised", ev.denoised))}
+
+
 def _templates_cell(ev, idx):
     """the records idx of an `evaluate_templates` result -> per condition the pooled RMSE against the clean median beats, how
     many windows it is taken over, and the pooled interval shares and errors"""
@@ -195,6 +206,7 @@ def grid(args, model, name):
             from ecg_denoise_amd import MedianBeat
             evt = evaluate_templates(sd, rec, noise, snrs, offsets=offsets,
                                      averager=MedianBeat(win_s=args.template_win, hop_s=args.template_win, device=DEV))
+        evp = evaluate_pst(sd, rec, noise, snrs, offsets=offsets) if args.pst else None
         for i, snr in enumerate(TRUE_NOISE):
             idx = torch.arange(i * args.records, (i + 1) * args.records, device=DEV)
             a, b = _subset(sc, idx, sd.L), _subset(sw, idx, sd.L)
@@ -236,6 +248,12 @@ def grid(args, model, name):
                 col = lambda d: (f"rmse {d['rmse']:.4f} over {d['windows']} median beats; qrs {d['qrs_share']:.4f} of the clean ones, "
                                  f"error {d['qrs_mae_ms']:.2f} ms; qt {d['qt_share']:.4f}, error {d['qt_mae_ms']:.2f} ms")
                 lines.append(f"{name}_0_{kind}_intensity{snr}:templates: noisy {col(tc['noisy'])}, denoised {col(tc['denoised'])}\n")
+            if evp is not None:
+                pc = _pst_cell(evp, idx)
+                cells[-1]["pst"] = pc
+                col = lambda d: (f"p {d['p_share']:.4f} of the clean P waves, pr error {d['pr_mae_ms']:.2f} ms over {d['p_beats']}; "
+                                 f"st error {' '.join(f'{v:.4f}' for v in d['st_mae'])} over {d['st_beats']}")
+                lines.append(f"{name}_0_{kind}_intensity{snr}:pst: noisy {col(pc['noisy'])}, denoised {col(pc['denoised'])}\n")
     return cells, lines
 
 
@@ -300,6 +318,7 @@ def main():
     ap.add_argument("--intervals", action="store_true", help="add the shares and errors of QRS duration and QT, noisy and denoised")
     ap.add_argument("--templates", action="store_true", help="add the RMSE and the intervals of the median beats, noisy and denoised")
     ap.add_argument("--template-win", type=int, default=10)
+    ap.add_argument("--pst", action="store_true", help="add the share of P waves and the errors of PR and of the ST level, noisy and denoised")
     ap.add_argument("--hrv-win", type=int, default=60)
     ap.add_argument("--hrv-hop", type=int, default=30)
     args = ap.parse_args()
