@@ -197,6 +197,8 @@ _SIGS = {
     "ral_baseline_layer_geom": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]),
     "ral_baseline_pass_plan": (C.c_int, [C.c_int] * 7 + [C.c_char_p, C.c_int] + [C.POINTER(C.c_int32)] * 4 + [C.POINTER(C.c_int64)]
                                + [C.POINTER(C.c_int32)]),
+    "ral_ralenet_node_geom": (C.c_int, [C.c_int, C.POINTER(C.c_int32), C.c_int]),
+    "ral_ralenet_pass_plan": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_int32), C.c_int]),
     "ral_attention_backward": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, C.c_int, C.c_int, C.c_int,
                                          C.c_int, _VP]),
     "ral_set_option": (C.c_int, [_VP, C.c_char_p, C.c_int]),

@@ -18,6 +18,7 @@
 #include "ral_model.hpp"
 #include "ral_kernels.hpp"
 #include "ral_ralenet.hpp"
+#include "ral_ralenet_plan.hpp"
 #include "ral_unet.hpp"
 #include "ral_unet_plan.hpp"
 #include "ral_baseline_plan.hpp"
@@ -1054,6 +1055,30 @@ int ral_baseline_pass_plan(int variant, int leads, int L, int B, int training, i
   if (lds_bytes) *lds_bytes = (int64_t)l.lds;
   if (extra) *extra = l.extra;
   return 0;
+}
+
+int ral_ralenet_node_geom(int i, int32_t* row, int cap) {
+  if (i < 0 || i >= RAL_NODES) return ral_fail("RA-LENet node %d outside [0, %d]", i, RAL_NODES - 1);
+  if (!row || cap < 9) return ral_fail("RA-LENet node row: room for 9 values is needed (got %d)", row ? cap : 0);
+  const RalNode& n = RAL_NET[i];
+  const int v[9] = {n.kind, n.idx, n.level, n.rw, n.D, n.up, n.in, n.add, n.out};
+  for (int j = 0; j < 9; ++j) row[j] = v[j];
+  return RAL_NODES;
+}
+
+int ral_ralenet_pass_plan(int backward, int B, int lanes, int k, int32_t* row, int cap) {
+  if (B < 1) return ral_fail("RA-LENet pass: B must be positive (got %d)", B);
+  if (lanes < 1 || lanes > MAX_LANES) return ral_fail("RA-LENet pass: lanes must be in [1, %d] (got %d)", MAX_LANES, lanes);
+  const RalLaneSplit sp = ralenet_lane_split(B, lanes);
+  const int n = RAL_NODES * sp.n;
+  if (k < 0 || k >= n) return ral_fail("RA-LENet pass: entry %d outside [0, %d)", k, n);
+  if (!row || cap < 9) return ral_fail("RA-LENet pass row: room for 9 values is needed (got %d)", row ? cap : 0);
+  const RalPassEntry e = ralenet_pass(backward != 0, k / sp.n);
+  const int lane = k % sp.n;
+  const RalBinding b = ralenet_bind(RAL_NET[e.node], backward != 0);
+  const int v[9] = {e.node, lane, sp.w0[lane], sp.B[lane], b.in, b.extra, b.out, b.fwd_in, e.mark && lane == sp.n - 1 ? 1 : 0};
+  for (int j = 0; j < 9; ++j) row[j] = v[j];
+  return n;
 }
 
 int64_t ral_attention_backward_scratch_floats(int N, int H, int Len, int has_table, int B) {

@@ -11,6 +11,7 @@
 #include "ral_model.hpp"
 #include "ral_kernels.hpp"
 #include "ral_ralenet.hpp"
+#include "ral_ralenet_plan.hpp"
 
 // Event records / stream waits of the fork-join scheduler: a failed one would silently drop an ordering edge (a race,
 // not an error), so the first failure is remembered and the entry point that issued it returns it (sched_check).
@@ -35,26 +36,6 @@ static int sched_check() {
 // ---------------------------------------------------------------------------------
 // layout
 // ---------------------------------------------------------------------------------
-static const int CH[5] = {8, 16, 32, 64, 128};
-static const int RWLEN[4] = {32, 16, 8, 4};
-struct StageDef { const char* name; int level; int rw; };
-static const StageDef STAGES[9] = {
-    {"dtransformer1", 0, 1}, {"dtransformer2", 1, 2}, {"dtransformer3", 2, 3}, {"dtransformer34", 3, 4},
-    {"transformer", 4, 0},   {"utransformer4", 4, 0}, {"utranformer3", 3, 4},  {"utransformer2", 2, 3},
-    {"utransformer1", 1, 2}};
-
-struct BlockOff { int64_t wqkv, bqkv, wp, bp, ln1w, ln1b, ln2w, ln2b, w1, b1, w2, b2, le; };
-struct ResOff { int64_t w, lnw, lnb; int D; };
-
-struct RalOff {
-  int64_t dec_off = 0;   // first float of the decoder's parameters (utransformer4 .. transconv are contiguous up to nparam)
-  int64_t conv1_w, conv1_b, bn_w, bn_b, tc_w, tc_b;
-  int64_t rw[4] = {-1, -1, -1, -1};
-  BlockOff blk[18];
-  ResOff res[8];  // pm1..pm4, ps4..ps1
-  bool le = true, rwave = false;
-};
-
 static void build_layout(const ral_config& c, ParamLayout& L, RalOff& O) {
   // 32-byte granules: the fp16 planes of a weight matrix are read 16 bytes (8 elements) at a time
   auto alloc_f = [&](int64_t n) { return L.alloc(n, 8); };
@@ -105,10 +86,10 @@ static void build_layout(const ral_config& c, ParamLayout& L, RalOff& O) {
     L.add(pre + "mlp.fc2.bias", RAL_PARAM, b.b2, {C});
     if (O.le) L.add(pre + "mlp.leconv.partial_conv3.weight", RAL_PARAM, b.le, {1, 1, 3});
   };
-  auto add_stage = [&](int si) {
+  auto add_stage = [&](const RalNode& st) {
     for (int i = 0; i < 2; ++i) {
-      const std::string pre = std::string(STAGES[si].name) + (basic ? ".blocks." : ".") + std::to_string(i) + ".";
-      add_block(si * 2 + i, pre, CH[STAGES[si].level]);
+      const std::string pre = std::string(st.name) + (basic ? ".blocks." : ".") + std::to_string(i) + ".";
+      add_block(st.idx * 2 + i, pre, CH[st.level]);
     }
   };
   auto add_res = [&](int ri, const std::string& name, int D) {
@@ -119,21 +100,14 @@ static void build_layout(const ral_config& c, ParamLayout& L, RalOff& O) {
     L.add(name + ".norm.weight", RAL_PARAM, r.lnw, {D});
     L.add(name + ".norm.bias", RAL_PARAM, r.lnb, {D});
   };
-  add_stage(0); add_res(0, "pm1", 16);
-  add_stage(1); add_res(1, "pm2", 32);
-  add_stage(2); add_res(2, "pm3", 64);
-  add_stage(3); add_res(3, "pm4", 128);
-  add_stage(4);
-  add_stage(5); add_res(4, "ps4", 64);
-  add_stage(6); add_res(5, "ps3", 32);
-  add_stage(7); add_res(6, "ps2", 16);
-  add_stage(8); add_res(7, "ps1", 8);
+  for (int i = 0; i < RAL_NODES; ++i) {
+    const RalNode& nd = RAL_NET[i];
+    if (i == RAL_DEC_NODE) O.dec_off = L.nparam;
+    if (nd.kind == RN_STAGE) add_stage(nd); else add_res(nd.idx, nd.name, nd.D);
+  }
   O.tc_w = alloc_f(ld * 8 * 3); O.tc_b = alloc_f(ld);
   L.add("transconv.0.weight", RAL_PARAM, O.tc_w, {ld, 8, 3});
   L.add("transconv.0.bias", RAL_PARAM, O.tc_b, {ld});
-  O.dec_off = L.nparam;
-  for (const ParamEntry& e : L.entries)
-    if (e.kind == RAL_PARAM && e.name.rfind("utransformer4.", 0) == 0 && e.offset < O.dec_off) O.dec_off = e.offset;
 }
 static void ralenet_layout(const ral_config& c, ParamLayout& L) { RalOff o; build_layout(c, L, o); }
 
@@ -179,6 +153,22 @@ static int dw_sets() {
   return n;
 }
 
+// ---------------------------------------------------------------------------------
+// lanes: the windows of a batch are independent through the whole transformer stack, so a batch is cut
+// into NL contiguous micro-batches ("lanes") that run the same kernel chain on separate HIP streams.
+// Kernels of different kinds (VALU-bound attention, MFMA/latency-bound projections) then share the CUs.
+// Every tensor is batch-major, so a lane is just a pointer offset of w0 windows.
+// ---------------------------------------------------------------------------------
+struct Lane {
+  int w0 = 0, B = 0;
+  hipStream_t s = nullptr, s2 = nullptr;     // chain stream, weight-gradient side stream
+  hipEvent_t ev_ready[MAX_SETS] = {}, ev_done[MAX_SETS] = {}, ev_fork = nullptr, ev_join = nullptr;
+  hipEvent_t ev_dec_main = nullptr, ev_dec_side = nullptr;   // decoder half of the gradients complete (this lane)
+  bool dw_pending[MAX_SETS] = {};
+  int bwd_count = 0;
+};
+struct LaneSet { Lane l[MAX_LANES]; int n = 1; hipStream_t own[MAX_LANES] = {}; };
+
 struct RalModel : ral_handle {
   ~RalModel() override;
   int init() override;
@@ -195,16 +185,15 @@ struct RalModel : ral_handle {
   std::map<std::string, std::pair<float*, int64_t>> dbg;
   // workspace
   float* pe[5];
-  float *xin, *a0, *x0, *ss;
-  BlockAct act[18];
-  float* res_out[8];  // p1..p4 (pm), u3,u2,u1,u0 (ps)
-  float* xmid;
+  float *xin, *a0, *ss;
+  BlockAct act[RAL_NBLOCKS];
+  float* ten[RT_COUNT];   // the named tensors of the node table (a stage output: the `out` of its second block)
   // backward temporaries
   // every gradient tensor has its own buffer (no ping-pong): the weight-gradient kernels run on a side
   // stream and read them long after the data-gradient chain has moved on
-  float *gy[18], *gin[9], *du0, *dz0;
+  float *gbuf[RG_COUNT], *dz0;   // (gbuf[gy9] stays null: ralenet_gy)
   float *dx1[MAX_SETS], *dohm[MAX_SETS], *dqkv[MAX_SETS], *dupre[MAX_SETS], *a2c0[MAX_SETS], *astat[MAX_SETS];   // per-block temporaries, dw_sets() sets (side-stream overlap)
-  void* lanes = nullptr;   // LaneSet
+  LaneSet* lanes = nullptr;
   int n_lanes = 2;
   bool side_stream = true;
   bool attn_f16 = true;      // attention score tiles (S, dP) as fp16-pair products - only while f16_split > 0 (option "attn_f16"; RAL_ATTN_F16=0)
@@ -296,7 +285,7 @@ static size_t plan_workspace(const ral_config& c, RalModel* m /* may be null: si
   RalModel tmp_;
   RalModel& M = m ? *m : tmp_;
   for (int l = 0; l < 5; ++l) M.pe[l] = take(("pe" + std::to_string(l)).c_str(), (size_t)(Lp >> l) * CH[l]);
-  M.a0 = take("a0", E); M.x0 = take("x0", E); M.ss = take("bn_ss", 64);
+  M.a0 = take("a0", E); M.ten[RT_X0] = take(ralenet_tensor_name(RT_X0), E); M.ss = take("bn_ss", 64);
   const bool tr = c.train != 0;
   float *sh_qkv = nullptr, *sh_o = nullptr;
   if (!tr) { sh_qkv = take("qkv", 3 * E); sh_o = take("o", E); }
@@ -308,23 +297,26 @@ static size_t plan_workspace(const ral_config& c, RalModel* m /* may be null: si
     a.lse = tr ? take((p + "lse").c_str(), E / 4) : nullptr;
     a.x1 = tr ? take((p + "x1").c_str(), E) : nullptr;
     // u_pre is kept only where the backward reads it (the plan's stores_upre: a function of width, slots and mode alone)
-    const int lvl = STAGES[b / 2].level;
+    const int lvl = ralenet_stage(b / 2).level;
     const bool upre = block_plan(BlockShape{CH[lvl], Lp >> lvl, 0, tr, false, true, false, false}).stores_upre;
     a.upre = upre ? take((p + "upre").c_str(), 4 * E) : nullptr;
     a.out = take((p + "out").c_str(), E);
+    if (b % 2) M.ten[RT_S0 + b / 2] = a.out;
   }
   { ParamLayout L_; ralenet_layout(c, L_); M.wh = reinterpret_cast<unsigned short*>(take("wh", (size_t)L_.nparam)); }
   M.wdesc = reinterpret_cast<int*>(take("wdesc", 4 * 64));
   M.ascale = take("ascale", 18 * ASC_N);
   M.adesc = reinterpret_cast<int*>(take("adesc", 18 * 12));
-  static const char* RN[8] = {"p1", "p2", "p3", "p4", "u3", "u2", "u1", "u0"};
-  for (int r = 0; r < 8; ++r) M.res_out[r] = take(RN[r], E);
-  M.xmid = take("xmid", E);
+  for (const RalNode& nd : RAL_NET)
+    if (nd.kind == RN_RES) M.ten[nd.out] = take(ralenet_tensor_name(nd.out), E);
+  M.ten[RT_XMID] = take(ralenet_tensor_name(RT_XMID), E);
   if (tr) {
-    for (int i = 0; i < 18; ++i) M.gy[i] = (i == 9) ? nullptr : take(("gy" + std::to_string(i)).c_str(), E);
-    for (int i = 0; i < 9; ++i) M.gin[i] = take(("gin" + std::to_string(i)).c_str(), E);
-    M.gy[9] = M.gin[5];   // x_mid = transformer(x4) + x4: the stage-4 output gradient IS g x_mid
-    M.du0 = take("du0", E);
+    for (int g = 0; g < RG_COUNT; ++g) {
+      // x_mid = transformer(x4) + x4: the gradient of the bottleneck's output IS g x_mid (gin5) - gy9 names no buffer
+      char name[8];
+      ralenet_grad_name(g, name);
+      M.gbuf[g] = ralenet_grad_is_buffer(g) ? take(name, E) : nullptr;
+    }
     for (int k = 0; k < dw_sets(); ++k) {
       M.dx1[k] = take(("dx1_" + std::to_string(k)).c_str(), E); M.dohm[k] = take(("do_" + std::to_string(k)).c_str(), E);
       M.dqkv[k] = take(("dqkv_" + std::to_string(k)).c_str(), 3 * E); M.dupre[k] = take(("dupre_" + std::to_string(k)).c_str(), 4 * E);
@@ -384,33 +376,14 @@ static BlockP block_ptrs(const BlockOff& o, float* base) {
   return p;
 }
 
-// ---------------------------------------------------------------------------------
-// lanes: the windows of a batch are independent through the whole transformer stack, so a batch is cut
-// into NL contiguous micro-batches ("lanes") that run the same kernel chain on separate HIP streams.
-// Kernels of different kinds (VALU-bound attention, MFMA/latency-bound projections) then share the CUs.
-// Every tensor is batch-major, so a lane is just a pointer offset of w0 windows.
-// ---------------------------------------------------------------------------------
-struct Lane {
-  int w0 = 0, B = 0;
-  hipStream_t s = nullptr, s2 = nullptr;     // chain stream, weight-gradient side stream
-  hipEvent_t ev_ready[MAX_SETS] = {}, ev_done[MAX_SETS] = {}, ev_fork = nullptr, ev_join = nullptr;
-  hipEvent_t ev_dec_main = nullptr, ev_dec_side = nullptr;   // decoder half of the gradients complete (this lane)
-  bool dw_pending[MAX_SETS] = {};
-  int bwd_count = 0;
-};
-#ifndef MAX_LANES
-#define MAX_LANES 4
-#endif
-struct LaneSet { Lane l[MAX_LANES]; int n = 1; hipStream_t own[MAX_LANES] = {}; };
-static LaneSet* lanes_of(RalModel* m);
-
 template <class T> static inline T* woff(T* p, int w0, size_t per_window) { return p ? p + (size_t)w0 * per_window : p; }
 
 // ---------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------
 static void run_block_fwd(RalModel* m, int bi, const float* in, bool training, const Lane& ln, const float* addend = nullptr, float* sum_out = nullptr) {
-  const int si = bi / 2, l = STAGES[si].level, C = CH[l], N = m->Lp >> l, H = C / 4;
+  const RalNode& st = ralenet_stage(bi / 2);
+  const int l = st.level, C = CH[l], N = m->Lp >> l, H = C / 4;
   const size_t E1 = m->E1;
   BlockP w = block_ptrs(m->off.blk[bi], m->params);
   w.asc = m->f16_split > 0 ? m->ascale + ASC_N * bi : nullptr;
@@ -418,9 +391,9 @@ static void run_block_fwd(RalModel* m, int bi, const float* in, bool training, c
   a.in = const_cast<float*>(in);   // base pointer (window 0); lanes offset it
   const float* table = nullptr;
   int Len = 0;
-  if (m->off.rwave && STAGES[si].rw) {
-    table = m->params + m->off.rw[STAGES[si].rw - 1];
-    Len = RWLEN[STAGES[si].rw - 1];
+  if (m->off.rwave && st.rw) {
+    table = m->params + m->off.rw[st.rw - 1];
+    Len = RWLEN[st.rw - 1];
   }
   const int w0 = ln.w0, B = ln.B;
   hipStream_t s = ln.s;
@@ -439,28 +412,29 @@ static void run_block_fwd(RalModel* m, int bi, const float* in, bool training, c
                    woff(a.out, w0, E1), N, B, s, NE, woff(addend, w0, E1), woff(sum_out, w0, E1)); }
 }
 
-static const float* run_stage_fwd(RalModel* m, int si, const float* in, bool training, const Lane& ln) {
+// a stage with an addend (the bottleneck: x_mid = transformer(x4) + x4, raletransformer.py:659) leaves the sum as the second
+// output of its last MLP kernel
+static void run_stage_fwd(RalModel* m, int si, const float* in, const float* addend, float* sum_out, bool training, const Lane& ln) {
   run_block_fwd(m, si * 2, in, training, ln);
-  run_block_fwd(m, si * 2 + 1, m->act[si * 2].out, training, ln);
-  return m->act[si * 2 + 1].out;
+  run_block_fwd(m, si * 2 + 1, m->act[si * 2].out, training, ln, addend, addend ? sum_out : nullptr);
 }
 
-static void run_res_fwd(RalModel* m, int ri, const float* in, const float* skip, const Lane& ln) {
-  const ResOff& r = m->off.res[ri];
+static void run_res_fwd(RalModel* m, const RalNode& nd, const float* in, const float* skip, float* out, const Lane& ln) {
+  const ResOff& r = m->off.res[nd.idx];
   const int T = m->E1 / r.D, Tv = 8 * m->L / r.D;  // output token slots per window, and how many of them exist
   ProfScope p(m, K_RES_FWD, ln.s);
-  launch_resample_fwd(r.D, ri >= 4, woff(in, ln.w0, m->E1), m->params + r.w, m->params + r.lnw, m->params + r.lnb,
-                      woff(skip, ln.w0, m->E1), woff(m->res_out[ri], ln.w0, m->E1), T, Tv, ln.B, ln.s);
+  launch_resample_fwd(r.D, nd.up, woff(in, ln.w0, m->E1), m->params + r.w, m->params + r.lnw, m->params + r.lnb,
+                      woff(skip, ln.w0, m->E1), woff(out, ln.w0, m->E1), T, Tv, ln.B, ln.s);
 }
 
 // split [0, B) over the lanes; lane 0 runs on the caller's stream
 static int plan_lanes(RalModel* m, int B, hipStream_t s) {
-  LaneSet* L = lanes_of(m);
-  int n = m->n_lanes;
-  if (B < 64 * n || B % n != 0) n = 1;
+  LaneSet* L = m->lanes;
+  const RalLaneSplit sp = ralenet_lane_split(B, m->n_lanes);
+  const int n = sp.n;
   for (int i = 0; i < n; ++i) {
     Lane& ln = L->l[i];
-    ln.w0 = i * (B / n); ln.B = B / n;
+    ln.w0 = sp.w0[i]; ln.B = sp.B[i];
     ln.s = i == 0 ? s : L->own[i];
     ln.bwd_count = 0;
     for (int k = 0; k < MAX_SETS; ++k) ln.dw_pending[k] = false;
@@ -470,13 +444,13 @@ static int plan_lanes(RalModel* m, int B, hipStream_t s) {
 }
 
 static void fork_lanes(RalModel* m, hipStream_t s) {     // lanes 1.. start after everything queued on s so far
-  LaneSet* L = lanes_of(m);
+  LaneSet* L = m->lanes;
   if (L->n < 2) return;
   EV(hipEventRecord(L->l[0].ev_fork, s));
   for (int i = 1; i < L->n; ++i) EV(hipStreamWaitEvent(L->l[i].s, L->l[0].ev_fork, 0));
 }
 static void join_lanes(RalModel* m, hipStream_t s) {     // s continues after every lane has finished
-  LaneSet* L = lanes_of(m);
+  LaneSet* L = m->lanes;
   for (int i = 1; i < L->n; ++i) {
     EV(hipEventRecord(L->l[i].ev_join, L->l[i].s));
     EV(hipStreamWaitEvent(s, L->l[i].ev_join, 0));
@@ -497,7 +471,7 @@ static int fwd_begin(RalModel* m, const float* x, int B, int training, hipStream
   if (training) m->planes_valid = false;                         // (an optimiser step will follow)
   else if (m->static_params) m->planes_valid = true;             // (what this forward prepares stays)
   if (!m->skip_prep && m->side_stream && m->ev_prep_go) {
-    hipStream_t ps = lanes_of(m)->l[0].s2;
+    hipStream_t ps = m->lanes->l[0].s2;
     HIP_OK(hipEventRecord(m->ev_prep_go, s));            // (the parameters are final: everything queued on s so far has run)
     HIP_OK(hipStreamWaitEvent(ps, m->ev_prep_go, 0));
     if (m->f16_split > 0) {
@@ -519,7 +493,7 @@ static int fwd_begin(RalModel* m, const float* x, int B, int training, hipStream
     launch_conv1_fwd(m->cfg.leads, 0, x, m->params + Y.conv1_w, m->params + Y.conv1_b, m->a0, m->bn_sums, nullptr,
                      nullptr, nullptr, nullptr, m->L, m->Lp, B, s);
   } else {
-    launch_conv1_fwd(m->cfg.leads, 1, x, m->params + Y.conv1_w, m->params + Y.conv1_b, m->x0, nullptr,
+    launch_conv1_fwd(m->cfg.leads, 1, x, m->params + Y.conv1_w, m->params + Y.conv1_b, m->ten[RT_X0], nullptr,
                      m->params + Y.bn_w, m->params + Y.bn_b, m->state, m->state + 8, m->L, m->Lp, B, s);
   }
   return 0;
@@ -530,7 +504,7 @@ static int fwd_end(RalModel* m, float* y, int B, int64_t global_windows, int tra
   const RalOff& Y = m->off;
   if (training) {
     launch_bn_train8(m->bn_sums, (double)global_windows * m->L, m->params + Y.bn_w, m->params + Y.bn_b, m->ss,
-                     m->state, m->state + 8, m->a0, m->x0, (size_t)B * m->Lp, s);
+                     m->state, m->state + 8, m->a0, m->ten[RT_X0], (size_t)B * m->Lp, s);
   }
   const bool tr = training != 0;
   // (the activation scales and the split planes of the wide levels' weights: formed under the stem on an idle stream.  ONE join, here,
@@ -544,29 +518,20 @@ static int fwd_end(RalModel* m, float* y, int B, int64_t global_windows, int tra
   }
   const int nl = plan_lanes(m, B, s);
   fork_lanes(m, s);
-  LaneSet* LS = lanes_of(m);
-  // issue stage by stage, alternating lanes, so that the lanes progress together
-  const float* cur = m->x0;
-  for (int i = 0; i < 4; ++i) {
-    for (int k = 0; k < nl; ++k) run_stage_fwd(m, i, cur, tr, LS->l[k]);
-    for (int k = 0; k < nl; ++k) run_res_fwd(m, i, m->act[2 * i + 1].out, nullptr, LS->l[k]);
-    cur = m->res_out[i];
+  LaneSet* LS = m->lanes;
+  // issue node by node, alternating lanes, so that the lanes progress together
+  for (int e = 0; e < RAL_NODES; ++e) {
+    const RalNode& nd = RAL_NET[ralenet_pass(false, e).node];
+    const RalBinding b = ralenet_bind(nd, false);
+    const float *in = m->ten[b.in], *add = b.extra == RT_NONE ? nullptr : m->ten[b.extra];
+    for (int k = 0; k < nl; ++k) {
+      if (nd.kind == RN_STAGE) run_stage_fwd(m, nd.idx, in, add, m->ten[b.out], tr, LS->l[k]);
+      else run_res_fwd(m, nd, in, add, m->ten[b.out], LS->l[k]);
+    }
   }
   for (int k = 0; k < nl; ++k) {
     const Lane& ln = LS->l[k];
-    // x_mid = transformer(x4) + x4 (raletransformer.py:659): the second output of the bottleneck's last MLP kernel
-    run_block_fwd(m, 8, cur, tr, ln);
-    run_block_fwd(m, 9, m->act[8].out, tr, ln, m->res_out[3], m->xmid);
-  }
-  cur = m->xmid;
-  for (int i = 0; i < 4; ++i) {
-    for (int k = 0; k < nl; ++k) run_stage_fwd(m, 5 + i, cur, tr, LS->l[k]);
-    for (int k = 0; k < nl; ++k) run_res_fwd(m, 4 + i, m->act[2 * (5 + i) + 1].out, i < 3 ? m->res_out[2 - i] : nullptr, LS->l[k]);
-    cur = m->res_out[4 + i];
-  }
-  for (int k = 0; k < nl; ++k) {
-    const Lane& ln = LS->l[k];
-    launch_final_fwd(m->cfg.leads, woff(cur, ln.w0, m->E1), woff(m->x0, ln.w0, m->E1), m->params + Y.tc_w, m->params + Y.tc_b,
+    launch_final_fwd(m->cfg.leads, woff(m->ten[RAL_HEAD_IN], ln.w0, m->E1), woff(m->ten[RAL_HEAD_ADD], ln.w0, m->E1), m->params + Y.tc_w, m->params + Y.tc_b,
                      woff(y, ln.w0, (size_t)m->cfg.leads * m->L), m->L, m->Lp, ln.B, ln.s);
   }
   join_lanes(m, s);
@@ -579,8 +544,9 @@ static int fwd_end(RalModel* m, float* y, int B, int64_t global_windows, int tra
 // ---------------------------------------------------------------------------------
 // one block: dy (grad of block output) -> dx (grad of block input) [+ extra]; all pointers are window-0 bases
 // (non-zero: the attention backward found the workspace scratch smaller than its plan needs - its gradients were not computed)
-static int run_block_bwd(RalModel* m, int bi, const float* dy, const float* extra, float* dx, Lane& ln) {
-  const int si = bi / 2, l = STAGES[si].level, C = CH[l], N = m->Lp >> l, H = C / 4;
+static int run_block_bwd(RalModel* m, int bi, const float* dy, const float* extra, float* dx, Lane& ln, int lane) {
+  const RalNode& st = ralenet_stage(bi / 2);
+  const int l = st.level, C = CH[l], N = m->Lp >> l, H = C / 4;
   const size_t E1 = m->E1;
   BlockP w = block_ptrs(m->off.blk[bi], m->params);
   w.asc = m->f16_split > 0 ? m->ascale + ASC_N * bi : nullptr;
@@ -590,10 +556,10 @@ static int run_block_bwd(RalModel* m, int bi, const float* dy, const float* extr
   const float* table = nullptr;
   float* gtable = nullptr;
   int Len = 0;
-  if (m->off.rwave && STAGES[si].rw) {
-    table = m->params + m->off.rw[STAGES[si].rw - 1];
-    gtable = m->grads + m->off.rw[STAGES[si].rw - 1];
-    Len = RWLEN[STAGES[si].rw - 1];
+  if (m->off.rwave && st.rw) {
+    table = m->params + m->off.rw[st.rw - 1];
+    gtable = m->grads + m->off.rw[st.rw - 1];
+    Len = RWLEN[st.rw - 1];
   }
   const int w0 = ln.w0, B = ln.B;
   hipStream_t s = ln.s;
@@ -608,7 +574,7 @@ static int run_block_bwd(RalModel* m, int bi, const float* dy, const float* extr
               *o = woff(a.o, w0, E1), *lse = woff(a.lse, w0, E1 / 4), *xin = woff(a.in, w0, E1);
   const BlockPlan plan = level_plan(m, l, true, false);
   // maxima of this block's gradient tensors (this lane's windows), for the split weight-gradient products
-  unsigned* gmax = plan.dw_split ? m->gmax + ((size_t)bi * 4 + (&ln - lanes_of(m)->l)) * 4 : nullptr;
+  unsigned* gmax = plan.dw_split ? m->gmax + ((size_t)bi * 4 + lane) * 4 : nullptr;
   const int NE = m->L >> l;
   { ProfScope p(m, K_MLP_BWD, s);
     launch_mlp_bwd(plan.mlp_bwd, dyw, x1, upre, w, wt, m->paramsT, m->whT, gmax, g, dupre, dx1, dohm, a2c0, N, B, m->want_dw, s, NE); }
@@ -637,18 +603,18 @@ static int run_block_bwd(RalModel* m, int bi, const float* dy, const float* extr
 }
 
 // stage: grad of stage output `dy` -> grad of stage input written to `dx` (+extra). Uses `tmp` between blocks.
-static int run_stage_bwd(RalModel* m, int si, const float* dy, const float* extra, float* tmp, float* dx, Lane& ln) {
-  const int rc = run_block_bwd(m, si * 2 + 1, dy, nullptr, tmp, ln);
-  return run_block_bwd(m, si * 2, tmp, extra, dx, ln) | rc;
+static int run_stage_bwd(RalModel* m, int si, const float* dy, const float* extra, float* tmp, float* dx, Lane& ln, int lane) {
+  const int rc = run_block_bwd(m, si * 2 + 1, dy, nullptr, tmp, ln, lane);
+  return run_block_bwd(m, si * 2, tmp, extra, dx, ln, lane) | rc;
 }
 
-static void run_res_bwd(RalModel* m, int ri, const float* dy, const float* in, float* dx, Lane& ln) {
-  const ResOff& r = m->off.res[ri];
+static void run_res_bwd(RalModel* m, const RalNode& nd, const float* dy, const float* in, float* dx, Lane& ln) {
+  const ResOff& r = m->off.res[nd.idx];
   const int T = m->E1 / r.D, Tv = 8 * m->L / r.D;
   const size_t E1 = m->E1;
   hipStream_t s = ln.s;
   { ProfScope p(m, K_RES_BWD, s);
-    launch_resample_bwd(r.D, ri >= 4, woff(dy, ln.w0, E1), woff(in, ln.w0, E1), m->paramsT + r.w, m->params + r.lnw,
+    launch_resample_bwd(r.D, nd.up, woff(dy, ln.w0, E1), woff(in, ln.w0, E1), m->paramsT + r.w, m->params + r.lnw,
                         m->grads + r.lnw, m->grads + r.lnb, woff(dx, ln.w0, E1), T, Tv, ln.B, s); }
   if (!m->want_dw) return;
   int lvl = 0;
@@ -659,7 +625,7 @@ static void run_res_bwd(RalModel* m, int ri, const float* dy, const float* in, f
     EV(hipStreamWaitEvent(ln.s2, ln.ev_fork, 0));
     sd = ln.s2;
   }
-  launch_resample_dw(r.D, ri >= 4, woff(dy, ln.w0, E1), woff(in, ln.w0, E1), m->params + r.lnw, m->params + r.lnb,
+  launch_resample_dw(r.D, nd.up, woff(dy, ln.w0, E1), woff(in, ln.w0, E1), m->params + r.lnw, m->params + r.lnb,
                      m->grads + r.w, T, Tv, ln.B, m->dw_ksplit[lvl], sd);
 }
 
@@ -679,15 +645,14 @@ static int bwd_begin(RalModel* m, const float* dy, int B, hipStream_t s) {
       if (m->prep_stale) launch_act_scales(m->params, m->adesc, m->ascale, 18, s);   // (the weight-gradient products scale their activation operands)
     }
   }
-  float** gy = m->gy; float** gin = m->gin;
   const int nl = plan_lanes(m, B, s);
-  LaneSet* LS = lanes_of(m);
+  LaneSet* LS = m->lanes;
   fork_lanes(m, s);
   // output conv: dy -> d(u0 + x0), each lane its windows
   for (int k = 0; k < nl; ++k) {
     const Lane& ln = LS->l[k];
-    launch_final_bwd(m->cfg.leads, woff(dy, ln.w0, (size_t)m->cfg.leads * m->L), woff(m->res_out[7], ln.w0, m->E1), woff(m->x0, ln.w0, m->E1),
-                     m->params + Y.tc_w, m->grads + Y.tc_w, m->grads + Y.tc_b, woff(m->du0, ln.w0, m->E1), m->L, m->Lp, ln.B, ln.s);
+    launch_final_bwd(m->cfg.leads, woff(dy, ln.w0, (size_t)m->cfg.leads * m->L), woff(m->ten[RAL_HEAD_IN], ln.w0, m->E1), woff(m->ten[RAL_HEAD_ADD], ln.w0, m->E1),
+                     m->params + Y.tc_w, m->grads + Y.tc_w, m->grads + Y.tc_b, woff(m->gbuf[ralenet_grad_of(RAL_HEAD_IN)], ln.w0, m->E1), m->L, m->Lp, ln.B, ln.s);
   }
   const bool side = m->side_stream && m->want_dw;
   if (side)   // side streams start after the gradient buffer has been zeroed
@@ -695,39 +660,37 @@ static int bwd_begin(RalModel* m, const float* dy, int B, hipStream_t s) {
       EV(hipEventRecord(LS->l[k].ev_fork, LS->l[k].s));
       EV(hipStreamWaitEvent(LS->l[k].s2, LS->l[k].ev_fork, 0));
     }
-#define EACH_LANE(stmt) for (int k_ = 0; k_ < nl; ++k_) { Lane& ln = LS->l[k_]; stmt; }
   int short_scratch = 0;
-  // decoder: ps_k <- stage <- (u = ps(.) + p)
-  EACH_LANE(run_res_bwd(m, 7, m->du0, m->act[17].out, gy[17], ln))
-  EACH_LANE(short_scratch |= run_stage_bwd(m, 8, gy[17], nullptr, gy[16], gin[8], ln))          // g u1
-  EACH_LANE(run_res_bwd(m, 6, gin[8], m->act[15].out, gy[15], ln))
-  EACH_LANE(short_scratch |= run_stage_bwd(m, 7, gy[15], nullptr, gy[14], gin[7], ln))          // g u2
-  EACH_LANE(run_res_bwd(m, 5, gin[7], m->act[13].out, gy[13], ln))
-  EACH_LANE(short_scratch |= run_stage_bwd(m, 6, gy[13], nullptr, gy[12], gin[6], ln))          // g u3
-  EACH_LANE(run_res_bwd(m, 4, gin[6], m->act[11].out, gy[11], ln))
-  EACH_LANE(short_scratch |= run_stage_bwd(m, 5, gy[11], nullptr, gy[10], gin[5], ln))          // g x_mid
-  // the decoder's parameters (utransformer4 .. transconv: the upper half of the flat gradient buffer) have their
-  // final gradients once every lane's chain and weight-gradient stream pass this point: gradient bucket 1
-  EACH_LANE(EV(hipEventRecord(ln.ev_dec_main, ln.s)); if (side) EV(hipEventRecord(ln.ev_dec_side, ln.s2));)
-  m->dec_lanes = nl; m->dec_side = side;
-  EACH_LANE(short_scratch |= run_stage_bwd(m, 4, gin[5], gin[5], gy[8], gin[4], ln))            // g p4 = transformer^T(g x_mid) + g x_mid
-  // encoder: pm_k <- stage, skip gradients added by the first block of each stage
-  EACH_LANE(run_res_bwd(m, 3, gin[4], m->act[7].out, gy[7], ln))
-  EACH_LANE(short_scratch |= run_stage_bwd(m, 3, gy[7], gin[6], gy[6], gin[3], ln))             // g p3 (+ g u3)
-  EACH_LANE(run_res_bwd(m, 2, gin[3], m->act[5].out, gy[5], ln))
-  EACH_LANE(short_scratch |= run_stage_bwd(m, 2, gy[5], gin[7], gy[4], gin[2], ln))             // g p2 (+ g u2)
-  EACH_LANE(run_res_bwd(m, 1, gin[2], m->act[3].out, gy[3], ln))
-  EACH_LANE(short_scratch |= run_stage_bwd(m, 1, gy[3], gin[8], gy[2], gin[1], ln))             // g p1 (+ g u1)
-  EACH_LANE(run_res_bwd(m, 0, gin[1], m->act[1].out, gy[1], ln))
-  EACH_LANE(short_scratch |= run_stage_bwd(m, 0, gy[1], m->du0, gy[0], gin[0], ln))             // g x0 (+ d u0)
-#undef EACH_LANE
+  // node by node in reverse, every lane of a node before the next; a stage adds `extra`, the gradient its input tensor receives
+  // as some node's addend (ralenet_extra_of), in its first block
+  for (int e = 0; e < RAL_NODES; ++e) {
+    const RalPassEntry pe = ralenet_pass(true, e);
+    const RalNode& nd = RAL_NET[pe.node];
+    const RalBinding b = ralenet_bind(nd, true);
+    const float *gout = m->gbuf[b.in], *extra = b.extra == RG_NONE ? nullptr : m->gbuf[b.extra];
+    float* tmp = nd.kind == RN_STAGE ? m->gbuf[ralenet_gy(nd.idx, 0)] : nullptr;
+    for (int k = 0; k < nl; ++k) {
+      Lane& ln = LS->l[k];
+      if (nd.kind == RN_STAGE) short_scratch |= run_stage_bwd(m, nd.idx, gout, extra, tmp, m->gbuf[b.out], ln, k);
+      else run_res_bwd(m, nd, gout, m->ten[b.fwd_in], m->gbuf[b.out], ln);
+    }
+    if (!pe.mark) continue;
+    // the decoder's parameters (utransformer4 .. transconv: the upper half of the flat gradient buffer) have their
+    // final gradients once every lane's chain and weight-gradient stream pass this point: gradient bucket 1
+    for (int k = 0; k < nl; ++k) {
+      Lane& ln = LS->l[k];
+      EV(hipEventRecord(ln.ev_dec_main, ln.s));
+      if (side) EV(hipEventRecord(ln.ev_dec_side, ln.s2));
+    }
+    m->dec_lanes = nl; m->dec_side = side;
+  }
   if (side)   // join the side streams into their lanes, then the lanes into s
     for (int k = 0; k < nl; ++k) {
       EV(hipEventRecord(LS->l[k].ev_join, LS->l[k].s2));
       EV(hipStreamWaitEvent(LS->l[k].s, LS->l[k].ev_join, 0));
     }
   join_lanes(m, s);
-  launch_bn8_bwd_stats(gin[0], m->a0, m->ss, m->bn_sums + 32, (size_t)B * m->Lp, s);
+  launch_bn8_bwd_stats(m->gbuf[ralenet_grad_of(RT_X0)], m->a0, m->ss, m->bn_sums + 32, (size_t)B * m->Lp, s);
   HIP_OK(hipGetLastError());
   if (short_scratch) return ral_fail("attention backward: the workspace scratch is smaller than a plan needs (ral_create checks it: the ATTN_* switches changed since?)");
   return sched_check();
@@ -736,7 +699,7 @@ static int bwd_begin(RalModel* m, const float* dy, int B, hipStream_t s) {
 static int bwd_end(RalModel* m, float* dx, int B, int64_t global_windows, hipStream_t s) {
   sched_reset();
   const RalOff& Y = m->off;
-  launch_conv1_bwd(m->cfg.leads, m->gin[0], m->a0, m->last_x, m->ss, m->params + Y.bn_w, m->bn_sums + 32,
+  launch_conv1_bwd(m->cfg.leads, m->gbuf[ralenet_grad_of(RT_X0)], m->a0, m->last_x, m->ss, m->params + Y.bn_w, m->bn_sums + 32,
                    (double)global_windows * m->L, m->grads + Y.conv1_w, m->grads + Y.conv1_b, dx ? m->dz0 : nullptr,
                    m->L, m->Lp, B, s, m->grads + Y.bn_w, m->grads + Y.bn_b, (double)B / (double)global_windows);
   if (dx) launch_conv1_bwd_dx(m->cfg.leads, m->dz0, m->params + Y.conv1_w, dx, m->L, m->Lp, B, s);
@@ -746,8 +709,6 @@ static int bwd_end(RalModel* m, float* dx, int B, int64_t global_windows, hipStr
   return sched_check();
 }
 
-
-static LaneSet* lanes_of(RalModel* m) { return reinterpret_cast<LaneSet*>(m->lanes); }
 
 RalModel* ralenet_model(ral_handle* h) { return dynamic_cast<RalModel*>(h); }
 
@@ -764,7 +725,7 @@ int ralenet_pe_table(const ral_config* cfg, int level, float* out_host, int64_t 
 RalModel::~RalModel() {
   RalModel* const m = this;
   if (m->lanes) {
-    LaneSet* LS = reinterpret_cast<LaneSet*>(m->lanes);
+    LaneSet* LS = m->lanes;
     for (int i = 0; i < MAX_LANES; ++i) {
       Lane& ln = LS->l[i];
       if (LS->own[i]) (void)hipStreamDestroy(LS->own[i]);
@@ -833,7 +794,7 @@ int RalModel::init() {
     std::vector<int> d;
     for (int b = 0; b < 18; ++b) {
       const BlockOff& o = m->off.blk[b];
-      const int v[12] = {CH[STAGES[b / 2].level], (int)o.ln1w, (int)o.ln1b, (int)o.wqkv, (int)o.bqkv, (int)o.ln2w, (int)o.ln2b, (int)o.w1, (int)o.b1,
+      const int v[12] = {CH[ralenet_stage(b / 2).level], (int)o.ln1w, (int)o.ln1b, (int)o.wqkv, (int)o.bqkv, (int)o.ln2w, (int)o.ln2b, (int)o.w1, (int)o.b1,
                          (int)o.le, 0, 0};
       d.insert(d.end(), v, v + 12);
     }
@@ -846,39 +807,18 @@ int RalModel::init() {
   if (cfg.train) {
     m->side_stream = ral_env_int("RAL_NO_SIDE_STREAM", 0, 0, 1) == 0;   // ... and the other
     std::vector<int> d;
-    int run = 0;
-    auto add = [&](int64_t off, int rows, int cols) { d.push_back((int)off); d.push_back(rows); d.push_back(cols); d.push_back(run); run += rows * cols; };
-    for (int b = 0; b < 18; ++b) {
-      const int C = CH[STAGES[b / 2].level];
-      const BlockOff& o = m->off.blk[b];
-      add(o.wqkv, 3 * C, C); add(o.wp, C, C); add(o.w1, 4 * C, C); add(o.w2, C, 4 * C);
-    }
-    for (int r = 0; r < 8; ++r) add(m->off.res[r].w, m->off.res[r].D, m->off.res[r].D);
+    const int run = ralenet_mat_descs(m->off, false, false, 1, true, d);
     m->tn = (int)d.size() / 4; m->ttotal = run;
     e = hipMemcpy(m->tdesc, d.data(), d.size() * sizeof(int), hipMemcpyHostToDevice);
     if (e != hipSuccess) return ral_fail("hipMemcpy(tdesc) failed: %s", hipGetErrorString(e));
   }
   {   // weight matrices that are re-written as tiled split planes every forward (widths with a split-operand kernel)
     std::vector<int> d;
-    int run = 0;
-    auto add = [&](int64_t off, int rows, int cols) { d.push_back((int)off); d.push_back(rows); d.push_back(cols); d.push_back(run); run += rows * cols / 8; };
-    for (int b = 0; b < 18; ++b) {
-      const int C = CH[STAGES[b / 2].level];
-      if (!block_has_planes(C)) continue;
-      const BlockOff& o = m->off.blk[b];
-      add(o.wqkv, 3 * C, C); add(o.wp, C, C); add(o.w1, 4 * C, C); add(o.w2, C, 4 * C);
-    }
+    const int run = ralenet_mat_descs(m->off, true, false, 8, false, d);
     m->ndesc = (int)d.size() / 4; m->nwork = run;
     if (cfg.train) {   // transposed matrices of the backward's data-gradient products (rows x columns as they sit in paramsT)
       std::vector<int> dt;
-      int runT = 0;
-      auto addT = [&](int64_t off, int rows, int cols) { dt.push_back((int)off); dt.push_back(rows); dt.push_back(cols); dt.push_back(runT); runT += rows * cols / 8; };
-      for (int b = 0; b < 18; ++b) {
-        const int C = CH[STAGES[b / 2].level];
-        if (!block_has_planes(C)) continue;
-        const BlockOff& o = m->off.blk[b];
-        addT(o.wqkv, C, 3 * C); addT(o.wp, C, C); addT(o.w1, C, 4 * C); addT(o.w2, 4 * C, C);
-      }
+      const int runT = ralenet_mat_descs(m->off, true, true, 8, false, dt);
       m->ndescT = (int)dt.size() / 4; m->nworkT = runT;
       if (m->ndescT) {
         e = hipMemcpy(m->wdescT, dt.data(), dt.size() * sizeof(int), hipMemcpyHostToDevice);
@@ -955,7 +895,7 @@ int ralenet_grad_bucket(RalModel* m, int k, int64_t* offset, int64_t* count) {
 int ralenet_grad_bucket_wait(RalModel* m, int k, hipStream_t s) {
   if (k == 1) {
     if (m->dec_lanes <= 0) return ral_fail("bucket 1 is available after ral_backward_begin");
-    LaneSet* LS = lanes_of(m);
+    LaneSet* LS = m->lanes;
     for (int i = 0; i < m->dec_lanes; ++i) {
       HIP_OK(hipStreamWaitEvent(s, LS->l[i].ev_dec_main, 0));
       if (m->dec_side) HIP_OK(hipStreamWaitEvent(s, LS->l[i].ev_dec_side, 0));

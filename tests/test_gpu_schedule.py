@@ -202,6 +202,44 @@ def test_fallback_rule_of_the_lane_split(shared, lanes, B, expect):
     assert not bad, bad
 
 
+def _plan_entries(backward, B, lanes):
+    """the pass as `ral_ralenet_pass_plan` gives it -> [(node kind, lane)] in issue order"""
+    lib = _lib().lib()
+    row, geom = (C.c_int32 * 9)(), (C.c_int32 * 9)()
+    n = lib.ral_ralenet_pass_plan(backward, B, lanes, 0, row, 9)
+    assert n > 0, lib.ral_last_error()
+    out = []
+    for k in range(n):
+        assert lib.ral_ralenet_pass_plan(backward, B, lanes, k, row, 9) == n, lib.ral_last_error()
+        assert lib.ral_ralenet_node_geom(row[0], geom, 9) > 0, lib.ral_last_error()
+        out.append((geom[0], row[1]))
+    return out
+
+
+@pytest.mark.parametrize("lanes,side", [(1, 0), (2, 1), (3, 1)])
+def test_timeline_is_the_expansion_of_the_pass_plan(shared, lanes, side):
+    """One recorded step of 192 windows: the (kind, stream) sequence of its timeline, in issue order, is the plan's entries
+    expanded - a forward stage entry on lane k is 2 x (qkv_fwd, attn_fwd, mlp_fwd) on chain stream k, a resampler entry one
+    resample_fwd / resample_bwd, a backward stage entry 2 x (mlp_bwd, attn_bwd, qkv_bwd) on the chain, each followed by its
+    dw on the lane's side stream (on the chain without side streams).  The timeline numbers streams by first appearance:
+    the chains 0 .. lanes - 1 in the forward, then lane k's side stream as lanes + k (the first stage of the backward issues
+    lane 0's blocks, and with them its dw, before lane 1's)."""
+    B = 192
+    m, x, t = shared.m, shared.x[:B].contiguous(), shared.t[:B].contiguous()
+    S.set_schedule(m, lanes, side)
+    rows = S.profiled_step(m, x, t)
+    want = []
+    for kind, k in _plan_entries(0, B, lanes):
+        want += [("qkv_fwd", k), ("attn_fwd", k), ("mlp_fwd", k)] * 2 if kind == 0 else [("resample_fwd", k)]
+    for kind, k in _plan_entries(1, B, lanes):
+        dw = lanes + k if side else k
+        want += [("mlp_bwd", k), ("attn_bwd", k), ("qkv_bwd", k), ("dw", dw)] * 2 if kind == 0 else [("resample_bwd", k)]
+    got = [(r[0], r[1]) for r in rows]
+    assert len(want) == lanes * (9 * 6 + 8 + 9 * 8 + 8)
+    first = next((i for i, (a, b) in enumerate(zip(got, want)) if a != b), None)
+    assert got == want, (first, got[first:first + 4] if first is not None else None, want[first:first + 4] if first is not None else len(got))
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # d, e: fresh processes
 # ---------------------------------------------------------------------------------------------------------------------
