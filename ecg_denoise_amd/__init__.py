@@ -46,3 +46,5 @@ from .hrv import (HrvAnalyzer, HrvEvaluation, HrvPool, HrvPoolState, HrvWindows,
                   hrv_windows)
 from .template import (BeatTemplates, MedianBeat, TemplateEvaluation, evaluate_templates, template_check,  # noqa: F401
                        template_geometry, template_rmse)
+from .arrhythmia import (AfEvaluation, ArrhythmiaAnalyzer, ArrhythmiaWindows, af_scores, af_truth, arrhythmia_check,  # noqa: F401
+                         arrhythmia_geometry, evaluate_af)

@@ -53,6 +53,14 @@ class TemplateGeom(C.Structure):
     _fields_ = [("wpre", C.c_int32), ("wpost", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("kmax", C.c_int32)]
 
 
+class ArrhythmiaGeom(C.Structure):
+    """ral_arrhythmia_geom: the rhythm analysis' lengths in samples, its counts, the five fp32 limits and the rate"""
+    _fields_ = [("W", C.c_int32), ("lo_n", C.c_int32), ("hi_n", C.c_int32), ("bin", C.c_int32), ("G", C.c_int32),
+                ("lock_n", C.c_int32), ("prmax", C.c_int32), ("pause_n", C.c_int32), ("min_m", C.c_int32), ("vrun_min", C.c_int32),
+                ("n0", C.c_float), ("c0", C.c_float), ("pl0", C.c_float), ("tachy", C.c_float), ("brady", C.c_float),
+                ("pad_", C.c_int32), ("fs", C.c_double)]
+
+
 class HrvGeom(C.Structure):
     """ral_hrv_geom: the HRV window's lengths in samples, its bin count, min_nn and the rate"""
     _fields_ = [("W", C.c_int32), ("lo_n", C.c_int32), ("hi_n", C.c_int32), ("t50", C.c_int32), ("F", C.c_int32),
@@ -185,6 +193,8 @@ _SIGS = {
                                        C.c_int64, _VP, _VP, _VP, _VP, _VP]),
     "ral_hrv_windows": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int64, _VP, C.c_int, C.POINTER(HrvGeom), _VP, _VP,
                                   _VP, _VP, _VP]),
+    "ral_arrhythmia_windows": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int64, _VP, C.c_int,
+                                         C.POINTER(ArrhythmiaGeom), _VP, _VP, _VP, _VP]),
     "ral_attention_forward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
     "ral_attention_backward_scratch_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "ral_attention_plan": (C.c_int, [C.c_int] * 8 + [C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),

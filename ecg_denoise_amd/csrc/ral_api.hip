@@ -881,6 +881,28 @@ int ral_hrv_windows(const int32_t* pos, const int32_t* label_or_null, const int3
                     geom->min_nn, geom->fs);
 }
 
+int ral_arrhythmia_windows(const int32_t* peaks, const int32_t* label_or_null, const int32_t* count, const int32_t* on_or_null,
+                           const int32_t* ppeak_or_null, int64_t R, int64_t cap, const ral_hrv_row* table, int64_t rows,
+                           ral_hrv_row* table_dev, int upload, const ral_arrhythmia_geom* geom, int32_t* counts, float* stats,
+                           int32_t* flags, ral_stream s) {
+  static const char NAME[] = "ral_arrhythmia_windows";
+  // (the host table is read only when it is uploaded: without upload NAME stands in for it as something non-null)
+  const struct { const void* p; const char* name; } need[] = {{peaks, "peaks"}, {count, "count"}, {table_dev, "table_dev"},
+      {upload ? (const void*)table : (const void*)NAME, "table"}, {geom, "geom"}, {counts, "counts"}, {stats, "stats"}, {flags, "flags"}};
+  for (const auto& a : need)
+    if (!a.p) return ral_fail("%s: need a non-null %s", NAME, a.name);
+  if (!on_or_null != !ppeak_or_null)
+    return ral_fail("%s: need on and ppeak together or neither (%s is null)", NAME, on_or_null ? "ppeak" : "on");
+  const char* why = nullptr;
+  long long bad = -1;
+  const int rc = launch_arrhythmia_windows(peaks, label_or_null, count, on_or_null, ppeak_or_null, (long long)R, (long long)cap, table,
+                                           (long long)rows, table_dev, upload, geom, counts, stats, flags, (hipStream_t)s, &why, &bad);
+  return table_done(NAME, rc, why, bad, "R=%lld cap=%lld rows=%lld W=%d lo_n=%d hi_n=%d bin=%d G=%d lock_n=%d prmax=%d pause_n=%d "
+                    "min_m=%d vrun_min=%d n0=%g c0=%g pl0=%g tachy=%g brady=%g fs=%g", (long long)R, (long long)cap, (long long)rows,
+                    geom->W, geom->lo_n, geom->hi_n, geom->bin, geom->G, geom->lock_n, geom->prmax, geom->pause_n, geom->min_m,
+                    geom->vrun_min, geom->n0, geom->c0, geom->pl0, geom->tachy, geom->brady, geom->fs);
+}
+
 int ral_wavelet_denoise(const float* x, float* y, int64_t rows, int L, float threshold, ral_stream s) {
   if (!x || !y) return ral_fail("wavelet_denoise: null pointer");
   if (!(threshold >= 0.f)) return ral_fail("wavelet_denoise: the threshold factor must be non-negative (got %g)", (double)threshold);

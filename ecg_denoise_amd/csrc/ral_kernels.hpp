@@ -145,6 +145,11 @@ int launch_beat_match(const int* ref, const int* nref, long long ref_cap, const 
 int launch_hrv_windows(const int* pos, const int* label, const int* count, long long R, long long cap, const ral_hrv_row* tab,
                        long long rows, ral_hrv_row* tab_dev, int upload, const ral_hrv_geom* geom, const int* band, int* counts,
                        float* stats, float* psd, hipStream_t s, const char** why, long long* bad);
+// rhythm findings (ral_arrhythmia.hip; ral_arrhythmia_windows): the conventions of launch_hrv_windows
+int launch_arrhythmia_windows(const int* peaks, const int* label, const int* count, const int* on, const int* ppeak, long long R,
+                              long long cap, const ral_hrv_row* tab, long long rows, ral_hrv_row* tab_dev, int upload,
+                              const ral_arrhythmia_geom* geom, int* counts, float* stats, int* flags, hipStream_t s,
+                              const char** why, long long* bad);
 // beat classes (ral_rhythm.hip;ral_rhythm_records / ral_rhythm_pool): the same conventions as beat detection above
 long long rhythm_pool_scratch_bytes(long long beats, int leads, const ral_rhythm_geom* geom, const char** why);
 int launch_rhythm_records(const float* x, long long R, int leads, long long T, const ral_rhythm_geom* geom, const int* peaks,

@@ -213,6 +213,76 @@ def make_beats_with_hrv(R, T, fs=360, seed=2023, lf=0.04, hf=0.02, p_v=0.0, p_s=
     return beats, labels
 
 
+def make_records_with_af(R, leads, T, seed=2023, cv=(0.15, 0.25), f_amp=(0.03, 0.06), f_hz=(4.0, 9.0), share=(0.3, 0.6)):
+    """-> (records, beats, labels, episodes): R synthetic clean records, float32 (R, leads, T), at 360 Hz, each sinus rhythm, then
+    one episode of atrial fibrillation (AF), then sinus rhythm again; per record the ascending sample indices of its R peaks, per
+    beat its label (all 0: AF beats have the normal QRS) and `episodes`, per record the list [(position of the first AF beat,
+    position of the first sinus beat after it, or T if that one lies beyond the record)].  Draws of its own (the other generators
+    keep theirs).  A record is one strip: heart rate 50 - 110 bpm, amplitude 0.8 - 1.2 and the waves of `_beats` (`_WAVES`, P and
+    T offsets scaled with the square root of the sinus interval), every sinus interval rr (1 + a 3 % jitter).  The episode takes
+    `share` (uniform) of the record and starts at 0.1 .. 0.9 - share of it.  Inside it the intervals are
+    max(0.3 s, rr_af (1 + cv N(0, 1))) with rr_af drawn from 70 - 140 bpm and `cv` uniform; the beats have no P wave; and each
+    lead carries a fibrillatory wave a sin(2 pi f t + phi + 0.8 sin(2 pi 0.23 t + psi)) - amplitude `f_amp` in mV, frequency
+    `f_hz`, a slow phase wobble - from half an interval behind the last sinus beat to half an interval in front of the next,
+    faded in and out over 0.1 s.  A wave is added within 8 of its widths, as in `make_records_with_rhythm`."""
+    rng = np.random.default_rng(seed)
+    T = int(T)
+    x = np.zeros((R, leads, T))
+    t = np.arange(T) / FS
+    dur = T / FS
+    beats, labels, episodes = [], [], []
+    for i in range(R):
+        rr = 60.0 / rng.uniform(50, 110)
+        amp = rng.uniform(0.8, 1.2)
+        stretch = np.sqrt(rr / 0.8)
+        sh = rng.uniform(*share)
+        ta = rng.uniform(0.1, max(0.1, 0.9 - sh)) * dur
+        tb = min(ta + sh * dur, dur)
+        rr_af, c = 60.0 / rng.uniform(70, 140), rng.uniform(*cv)
+        prev = -rng.uniform(1.0, 2.0) * rr                       # (a sinus beat before the record: its T wave may reach in)
+        events = [(prev, 0)]
+        while True:                                              # sinus rhythm up to the episode
+            gap = rr * (1 + rng.normal(0, 0.03))
+            if prev + gap > ta:
+                break
+            prev += gap
+            events.append((prev, 0))
+        f_on = prev
+        first = None
+        while first is None or prev < tb:                        # the episode: at least one beat
+            prev += max(0.3, rr_af * (1 + c * rng.normal(0, 1)))
+            events.append((prev, 3))
+            if first is None:
+                first, f_on = prev, 0.5 * (f_on + prev)
+        last = prev
+        prev += rr * (1 + rng.normal(0, 0.03))
+        back, f_off = prev, 0.5 * (last + prev)
+        events.append((prev, 0))
+        while prev < dur + rr:
+            prev += rr * (1 + rng.normal(0, 0.03))
+            events.append((prev, 0))
+        for rk, kind in events:
+            for ld in range(leads):
+                for (off, wid, a) in _WAVES[ld % 2][1 if kind == 3 else 0:]:
+                    cen = rk + off * stretch
+                    lo, hi = max(0, int((cen - 8 * wid) * FS)), min(T, int((cen + 8 * wid) * FS) + 2)
+                    if lo < hi:
+                        x[i, ld, lo:hi] += amp * a * np.exp(-0.5 * ((t[lo:hi] - cen) / wid) ** 2)
+        lo, hi = max(0, int(f_on * FS)), min(T, int(f_off * FS) + 1)
+        for ld in range(leads):
+            a, f = rng.uniform(*f_amp), rng.uniform(*f_hz)
+            phi, psi = rng.uniform(0, 2 * np.pi, 2)
+            if lo < hi:
+                ts = t[lo:hi]
+                fade = np.clip(np.minimum(ts - f_on, f_off - ts) / 0.1, 0.0, 1.0)
+                x[i, ld, lo:hi] += a * fade * np.sin(2 * np.pi * f * ts + phi + 0.8 * np.sin(2 * np.pi * 0.23 * ts + psi))
+        at = [int(np.floor(rk * FS + 0.5)) for rk, _ in events]
+        beats.append([p for p in at if 0 <= p < T])
+        labels.append([0] * len(beats[-1]))
+        episodes.append([(min(max(int(np.floor(first * FS + 0.5)), 0), T), min(int(np.floor(back * FS + 0.5)), T))])
+    return x.astype(np.float32), beats, labels, episodes
+
+
 def make_noise_record(kind, leads, Tn, seed=2023):
     """-> one synthetic noise record, float32 (leads, Tn), of kind bw / ma / em / emb (`noise`): the stand-in for an NSTDB
     record that `mix_records` cuts its segments from."""

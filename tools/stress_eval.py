@@ -54,10 +54,17 @@ error of the PR interval in ms over the beats that have a P wave in both, and th
 have one in both - `PStMeasurer` on `BeatDelineator` at the clean records' detections (`evaluate_pst`; NaN where there is no such
 beat; the ST error is in the unit of the mixed records, which `mix_records` z-scores).  Without the flag the output is what it was.
 
+`--af` asks the seventh question, is the rhythm diagnosis back: a pass of its own over records with one episode of atrial
+fibrillation each (`synth.make_records_with_af`, the same count, length, noise, SNRs and offsets as the grid's), every condition
+detected, classified, delineated, measured and analysed on its own (`evaluate_af` against the generator's episodes; windows of
+`--af-win` seconds every `--af-hop` seconds).  Per cell one more line and an "af" entry in the JSON with tp, fp, fn, tn,
+sensitivity and specificity of the AF bit per window for the clean, the noisy and the denoised records (NaN where a ratio has
+no denominator).  The analysis' defaults were chosen on synthetic data only.  Without the flag the output is what it was.
+
     python tools/stress_eval.py [--model full|nra|mlp|unet|acdae|danet|newrale] [--ckpt state_dict.pth] [--L 512]
                                 [--records 4] [--T 65000] [--overlap 0] [--batch 4096] [--time-shapes ...] [--reps 5] [--beats]
                                 [--classes] [--fft] [--fft-L 1000] [--hrv] [--hrv-win 60] [--hrv-hop 30] [--intervals]
-                                [--templates] [--template-win 10] [--pst]
+                                [--templates] [--template-win 10] [--pst] [--af] [--af-win 30] [--af-hop 10]
 """
 import argparse
 import json
@@ -70,9 +77,9 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from ecg_denoise_amd import (ACDAE, ClassicalDenoiser, DANet, NewRALE, RALENet, UNet, evaluate_beats, evaluate_hrv,  # noqa: E402
-                             evaluate_intervals, evaluate_pst, evaluate_rhythm, evaluate_templates, interval_scores, mix_records,
-                             pst_scores, score_records, synth, wavelet_denoise)
+from ecg_denoise_amd import (ACDAE, ClassicalDenoiser, DANet, NewRALE, RALENet, UNet, af_scores, evaluate_af,  # noqa: E402
+                             evaluate_beats, evaluate_hrv, evaluate_intervals, evaluate_pst, evaluate_rhythm, evaluate_templates,
+                             interval_scores, mix_records, pst_scores, score_records, synth, wavelet_denoise)
 from ecg_denoise_amd.data import NOISE_TYPES, TRUE_NOISE  # noqa: E402
 from ecg_denoise_amd.infer import StreamingDenoiser  # noqa: E402
 
@@ -160,6 +167,13 @@ def _pst_cell(ev, idx):
     return {key: pst_scores(ev.clean, p, rows=idx)[2] for key, p in (("noisy", ev.noisy), ("denoised", ev.denoised))}
 
 
+def _af_cell(ev, idx):
+    """the records idx of an `evaluate_af` result -> per condition the AF bit's tp, fp, fn, tn, sensitivity and specificity"""
+    rows = np.isin(ev.clean.index[:, 0], idx.cpu().numpy())
+    return {key: af_scores(r.af.cpu().numpy(), ev.positive, ev.scored & rows)
+            for key, r in (("clean", ev.clean), ("noisy", ev.noisy), ("denoised", ev.denoised))}
+
+
 def _templates_cell(ev, idx):
     """the records idx of an `evaluate_templates` result -> per condition the pooled RMSE against the clean median beats, how
     many windows it is taken over, and the pooled interval shares and errors"""
@@ -207,6 +221,12 @@ def grid(args, model, name):
             evt = evaluate_templates(sd, rec, noise, snrs, offsets=offsets,
                                      averager=MedianBeat(win_s=args.template_win, hop_s=args.template_win, device=DEV))
         evp = evaluate_pst(sd, rec, noise, snrs, offsets=offsets) if args.pst else None
+        eva = None
+        if args.af:
+            from ecg_denoise_amd import ArrhythmiaAnalyzer
+            xa, _, _, episodes = synth.make_records_with_af(R, leads, args.T, seed=2023)
+            eva = evaluate_af(sd, torch.tensor(xa, device=DEV), noise, snrs, truth=episodes, offsets=offsets,
+                              analyzer=ArrhythmiaAnalyzer(win_s=args.af_win, hop_s=args.af_hop, device=DEV))
         for i, snr in enumerate(TRUE_NOISE):
             idx = torch.arange(i * args.records, (i + 1) * args.records, device=DEV)
             a, b = _subset(sc, idx, sd.L), _subset(sw, idx, sd.L)
@@ -254,6 +274,13 @@ def grid(args, model, name):
                 col = lambda d: (f"p {d['p_share']:.4f} of the clean P waves, pr error {d['pr_mae_ms']:.2f} ms over {d['p_beats']}; "
                                  f"st error {' '.join(f'{v:.4f}' for v in d['st_mae'])} over {d['st_beats']}")
                 lines.append(f"{name}_0_{kind}_intensity{snr}:pst: noisy {col(pc['noisy'])}, denoised {col(pc['denoised'])}\n")
+            if eva is not None:
+                ac = _af_cell(eva, idx)
+                cells[-1]["af"] = ac
+                col = lambda d: (f"Se {d['sensitivity']:.4f} Sp {d['specificity']:.4f} "
+                                 f"(tp {d['tp']} fp {d['fp']} fn {d['fn']} tn {d['tn']})")
+                lines.append(f"{name}_0_{kind}_intensity{snr}:af: clean {col(ac['clean'])}, noisy {col(ac['noisy'])}, "
+                             f"denoised {col(ac['denoised'])}\n")
     return cells, lines
 
 
@@ -319,6 +346,9 @@ def main():
     ap.add_argument("--templates", action="store_true", help="add the RMSE and the intervals of the median beats, noisy and denoised")
     ap.add_argument("--template-win", type=int, default=10)
     ap.add_argument("--pst", action="store_true", help="add the share of P waves and the errors of PR and of the ST level, noisy and denoised")
+    ap.add_argument("--af", action="store_true", help="add sensitivity and specificity of the AF flag per window on records with AF episodes")
+    ap.add_argument("--af-win", type=int, default=30)
+    ap.add_argument("--af-hop", type=int, default=10)
     ap.add_argument("--hrv-win", type=int, default=60)
     ap.add_argument("--hrv-hop", type=int, default=30)
     args = ap.parse_args()
