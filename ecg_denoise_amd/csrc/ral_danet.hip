@@ -250,12 +250,14 @@ template <int V>
 __global__ __launch_bounds__(NT) void k_dn_act(const float* __restrict__ z, const float* __restrict__ h2, const double* sums2,
                                                Fcn F, Geo G, float* __restrict__ a, double* sumsa, int B, int training) {
   __shared__ float mean2[MAXC], rstd2[MAXC], g2s[MAXC], b2s[MAXC], al[EW][MAXC];
-  __shared__ float acc1[MAXC], acc2[MAXC];
+  // (double: the order in which the row pieces arrive varies from run to run, and in float that left ~1e-7 of noise on mean and
+  // rstd - every element of the step then moved with it, which a gradient that cancels over the batch shows 1000-fold)
+  __shared__ double acc1[MAXC], acc2[MAXC];
   const int tid = threadIdx.x;
   if (tid < G.c) {
     bn_stat(sums2, G.c, tid, B, training, F.bn2.rm, F.bn2.rv, mean2[tid], rstd2[tid]);
     g2s[tid] = F.bn2.g[tid]; b2s[tid] = F.bn2.b[tid];
-    acc1[tid] = 0.f; acc2[tid] = 0.f;
+    acc1[tid] = 0.0; acc2[tid] = 0.0;
     if (training && blockIdx.x == 0) bn_running(sums2, G.c, tid, B, F.bn2.rm, F.bn2.rv);
   }
   const int nz = G.c * G.lout, n4w = nz / V, q4 = G.lout / V;          // items per window / per channel row
@@ -291,13 +293,13 @@ __global__ __launch_bounds__(NT) void k_dn_act(const float* __restrict__ z, cons
           s1 = hsum4(r); s2 = (r.x * r.x + r.y * r.y) + (r.z * r.z + r.w * r.w);
         }
         if (sumsa) {
-          if (segw > 1) { s1 = seg_sum(s1, segw); s2 = seg_sum(s2, segw); if ((tid & (segw - 1)) == 0 && i < n4) { atomicAdd(acc1 + c, s1); atomicAdd(acc2 + c, s2); } }
-          else if (i < n4) { atomicAdd(acc1 + c, s1); atomicAdd(acc2 + c, s2); }
+          if (segw > 1) { s1 = seg_sum(s1, segw); s2 = seg_sum(s2, segw); if ((tid & (segw - 1)) == 0 && i < n4) { atomicAdd(acc1 + c, (double)s1); atomicAdd(acc2 + c, (double)s2); } }
+          else if (i < n4) { atomicAdd(acc1 + c, (double)s1); atomicAdd(acc2 + c, (double)s2); }
         }
       }
     }
     __syncthreads();
-    if (tid < G.c) { t1 += acc1[tid]; t2 += acc2[tid]; acc1[tid] = 0.f; acc2[tid] = 0.f; }
+    if (tid < G.c) { t1 += acc1[tid]; t2 += acc2[tid]; acc1[tid] = 0.0; acc2[tid] = 0.0; }
   }
   if (sumsa && tid < G.c) { atomicAdd(sumsa + tid, t1); atomicAdd(sumsa + G.c + tid, t2); }
 }

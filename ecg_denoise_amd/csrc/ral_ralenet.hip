@@ -229,6 +229,7 @@ struct RalModel : ral_handle {
   void* tdesc = nullptr; int tn = 0, ttotal = 0;
   const float* last_x = nullptr;
   int last_B = 0;
+  bool last_training = false;   // the last forward kept what a backward pass reads (lse, x1, u_pre, batch statistics)
   int dw_ksplit[5] = {256, 256, 256, 256, 256};
   // optional in-library kernel timing (bench.py roofline leg): hipEvent pairs around the
   // launches of ONE selected kernel kind, on the stream the kernels run on
@@ -464,7 +465,7 @@ static int fwd_begin(RalModel* m, const float* x, int B, int training, hipStream
   if (training && !m->cfg.train) return ral_fail("handle was created with train=0");
   if (training && !m->bn_sums) return ral_fail("training forward needs bn_sums bound");
   const RalOff& Y = m->off;
-  m->last_x = x; m->last_B = B;
+  m->last_x = x; m->last_B = B; m->last_training = training != 0;
   m->prep_fwd = m->prep_bwd = false;
   m->prep_stale = false;
   m->skip_prep = !training && m->static_params && m->planes_valid;
@@ -634,6 +635,7 @@ static int bwd_begin(RalModel* m, const float* dy, int B, hipStream_t s) {
   if (!m->cfg.train) return ral_fail("handle was created with train=0");
   if (!m->grads || !m->bn_sums) return ral_fail("ral_bind: grads / bn_sums not bound");
   if (B != m->last_B) return ral_fail("backward batch %d != forward batch %d", B, m->last_B);
+  if (!m->last_training) return ral_fail("RA-LENet backward must follow a training forward: the last forward was an eval one");
   const RalOff& Y = m->off;
   launch_zero_bwd(m->grads, (size_t)m->lay.nparam, m->bn_sums + 32, 32, m->gmax, 18 * 4 * 4, s);   // gradient buffer, backward BatchNorm sums, gradient maxima
   const bool prep_ok = m->prep_bwd && !m->prep_stale;

@@ -1732,6 +1732,7 @@ struct UNetModel : ral_handle {
   const float* gsums_dy = nullptr;  // unet_forward_loss left the sums of THIS dy in the output layer's backward record ...
   int gsums_nrep = 0;               // ... spread over this many replicas (unet_backward_start then skips k_unet_gsums)
   int last_B = 0;
+  bool last_training = false;       // the last forward (either eval path included) left z[] and the batch records of a training pass
   // weight / bias gradient partials of the backward stage kernels: one row of `part_stride` floats (the flat parameter
   // layout) per workgroup, folded by k_unet_fold; `cols` = the flat offsets of all conv weights and biases
   float* part = nullptr; int64_t part_stride = 0; int part_rows_max = 0;
@@ -1924,7 +1925,7 @@ int unet_forward_stage(UNetModel* m, const float* x, int B, int training, int si
   if (si < 0 || si > 10) return ral_fail("U-Net stage %d outside [0, 10]", si);
   if (training && (!m->cfg.train || !m->bn_sums)) return ral_fail("training forward needs train=1 and bn_sums");
   if (si == 0) {
-    m->last_x = x; m->last_B = B; m->gsums_dy = nullptr;
+    m->last_x = x; m->last_B = B; m->gsums_dy = nullptr; m->last_training = training != 0;
     if (training) {
       // (one fill for both halves of the replica records: the backward pass of this step finds its half zeroed)
       if (nrep > 1) {
@@ -1969,6 +1970,8 @@ int unet_forward_finish(UNetModel* m, float* y, int B, int training, int64_t gwi
 static int unet_forward_fused(UNetModel* m, const UStageLaunch& p, const float* x, float* y, int B, hipStream_t s) {
   if (!m->params || !m->state) return ral_fail("ral_bind was not called");
   if (B <= 0 || B > m->cfg.max_batch) return ral_fail("batch %d outside (0, %d]", B, m->cfg.max_batch);
+  // (this kernel leaves z[] and the records alone, the stage-by-stage eval path does not: one rule for both, whatever L)
+  m->last_x = x; m->last_B = B; m->gsums_dy = nullptr; m->last_training = false;
   UPackArgs a;
   a.params = m->params; a.state = m->state; a.pk = m->pack; a.leads = m->cfg.leads;
   for (int i = 0; i < 11; ++i) { a.w[i] = m->off.w[i]; a.b[i] = m->off.b[i]; }
@@ -2031,6 +2034,7 @@ int unet_forward_loss(UNetModel* m, const float* x, const float* target, float* 
 int unet_backward_start(UNetModel* m, const float* dy, int B, int64_t gwin, hipStream_t s, int nrep) {
   if (!m->cfg.train || !m->grads || !m->bn_sums) return ral_fail("backward needs train=1, grads and bn_sums bound");
   if (B != m->last_B) return ral_fail("backward batch %d != forward batch %d", B, m->last_B);
+  if (!m->last_training) return ral_fail("U-Net backward must follow a training forward: the last forward was an eval one");
   // with the fold every gradient entry is WRITTEN by k_unet_fold; the atomic path accumulates into a zeroed buffer
   if (!m->fold) (void)hipMemsetAsync(m->grads, 0, (size_t)m->lay.nparam * sizeof(float), s);
   // dy == NULL: "the gradient unet_forward_loss wrote, untouched" - its sums are already in the output layer's backward record.
