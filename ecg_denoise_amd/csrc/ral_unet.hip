@@ -1270,8 +1270,11 @@ RAL_DEV void bn_affine_grads(const BnGrad& b, int c, double share) {
   b.gb[c] = (float)(s1 * share); b.gw[c] = (float)(s2 * share);
 }
 #define UNET_FOLD_WAVES 16
+// cols[0, nsum): the flat offsets of the conv weights and biases, summed over the rows; cols[nsum, ncols): the padding floats
+// between the tensors of the flat layout, which belong to no parameter and are zeroed - `grads` is the caller's, "zeroed first"
+// holds for all of it, and ral_adam_step runs over the padding too
 __global__ __launch_bounds__(64 * UNET_FOLD_WAVES) void k_unet_fold(const float* __restrict__ part, int64_t stride, int rows, const int* __restrict__ cols,
-                                                   int ncols, float* __restrict__ grads, BnGradAll u, double share,
+                                                   int nsum, int ncols, float* __restrict__ grads, BnGradAll u, double share,
                                                    double* __restrict__ zero, int nzero) {
   if (blockIdx.x == gridDim.x - 1) {
     for (int t = threadIdx.x; t < 10 * MAXC; t += blockDim.x) bn_affine_grads(u.l[t / MAXC], t % MAXC, share);
@@ -1288,7 +1291,7 @@ __global__ __launch_bounds__(64 * UNET_FOLD_WAVES) void k_unet_fold(const float*
   const int j = blockIdx.x * 64 + lane;
   const int col = j < ncols ? cols[j] : -1;
   float acc = 0.f;
-  if (col >= 0) {
+  if (col >= 0 && j < nsum) {
     const int r0 = (int)((int64_t)rows * wave / UNET_FOLD_WAVES), r1 = (int)((int64_t)rows * (wave + 1) / UNET_FOLD_WAVES);
     int rr = r0;
     for (; rr + 8 <= r1; rr += 8) {
@@ -1736,7 +1739,8 @@ struct UNetModel : ral_handle {
   // weight / bias gradient partials of the backward stage kernels: one row of `part_stride` floats (the flat parameter
   // layout) per workgroup, folded by k_unet_fold; `cols` = the flat offsets of all conv weights and biases
   float* part = nullptr; int64_t part_stride = 0; int part_rows_max = 0;
-  int* cols = nullptr; int ncols = 0;
+  int* cols = nullptr; int ncols = 0;     // (behind the ncols offsets: the npad padding floats of the layout, which the fold zeroes)
+  int npad = 0;
   bool fold = false; int bwd_rows = 0;   // unet_pass_plan's fold; the grid of this backward pass's stage plans
   // replicas of the BatchNorm records for the one-call forward / backward (see Stage::nrep): [fwd | bwd][10][UNET_MAXREP][64].
   // How many of them a pass adds to is an argument of the stage functions (`nrep`; 1: straight into bn_sums)
@@ -1802,6 +1806,15 @@ int UNetModel::init() {
       for (int i = 0; i < tab[si].cout; ++i) cols.push_back((int)m->off.b[si] + i);
     }
     m->ncols = (int)cols.size();
+    std::vector<char> owned((size_t)lay.nparam, 0);
+    for (const ParamEntry& e : lay.entries)
+      if (e.kind == RAL_PARAM) {
+        const int64_t n = e.shape[0] * e.shape[1] * e.shape[2] * e.shape[3];
+        for (int64_t i = 0; i < n; ++i) owned[(size_t)(e.offset + i)] = 1;
+      }
+    for (int64_t i = 0; i < lay.nparam; ++i)
+      if (!owned[(size_t)i]) cols.push_back((int)i);
+    m->npad = (int)cols.size() - m->ncols;
     if (hipMemcpy(m->cols, cols.data(), cols.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return ral_fail("hipMemcpy(cols) failed");
   }
   return 0;
@@ -2077,7 +2090,8 @@ int unet_backward_finish(UNetModel* m, int B, int64_t gwin, hipStream_t s, int n
   if (m->fold) {
     if (m->bwd_rows <= 0) return ral_fail("U-Net backward finish without its stages");
     const bool reps = nrep > 1;
-    k_unet_fold<<<(m->ncols + 63) / 64 + 1, 64 * UNET_FOLD_WAVES, 0, s>>>(m->part, m->part_stride, m->bwd_rows, m->cols, m->ncols, m->grads, u,
+    k_unet_fold<<<(m->ncols + m->npad + 63) / 64 + 1, 64 * UNET_FOLD_WAVES, 0, s>>>(m->part, m->part_stride, m->bwd_rows, m->cols, m->ncols,
+                                                                                  m->ncols + m->npad, m->grads, u,
                                                         (double)B / (double)gwin, reps ? bn_record(m, 0, 0, nrep) : nullptr,
                                                         reps ? 2 * 10 * UNET_MAXREP * 64 : 0);
     if (reps) m->rep_all_clean = true;
