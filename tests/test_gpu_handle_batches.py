@@ -9,7 +9,9 @@ pass cache, the adapter's saved tensors) and every kernel loops over windows und
      state), and the fresh handle is compared with the fp64 oracle.
   b  every pass of every window loop, free of activation kinks: eval y of the largest batch at windows of the first, a middle
      and the ragged last pass of each cap equals, bit for bit, eval y of those windows alone on a small handle; for ACDAE (no
-     BatchNorm) y, dx and the parameter gradients of the batch against those of its parts as well.
+     BatchNorm) y, dx and the parameter gradients of the batch against those of its parts as well.  One loop is not here: the
+     fused U-Net inference kernel's (k_unet_infer, L = 256 .. 1024).  Its grid is a device question, so a batch that wraps it
+     follows from the CU count: tests/test_gpu_unet_infer.py, at every shape of the kernel.
   c  call orders: each one either gives the numbers of the canonical order on a fresh handle, or is refused with a pinned
      text and leaves the handle usable.  Never other numbers without an error.
 
@@ -79,7 +81,7 @@ PASS_WINDOWS = {
     "unet_staged": (0, 2, 3),
     "newrale": (0, 3, 7),
     "unet_wrap": (0, 1, 2047, 2048, 2049),
-    "unet_fused": (0, 1, 3),
+    "unet_fused": (0, 1, 3),      # one window per workgroup; the wrapped loop of k_unet_infer: tests/test_gpu_unet_infer.py
 }
 # beyond the lists of (a): the U-Net's forward stage kernels take up to 4 windows per pass on 512 workgroups, so their loop wraps
 # beyond 2048 windows only, and k_unet_out_loss gives a wave a second window per pass only there (tests/test_handle_batches_cpu.py)
