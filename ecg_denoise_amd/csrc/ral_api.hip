@@ -1,5 +1,6 @@
-// C ABI (include/ralenet.h): the error state, the library switches, the dispatch of the model interface (ral_model.hpp)
-// and the stateless entry points.
+// C ABI (include/ralenet.h): the error state, the library switches, the dispatch of the model interface (ral_model.hpp),
+// the loss and Adam entry points, the plan and geometry queries and the attention entry points (their launchers are the
+// model's).  Every other stateless entry point is defined in the file that holds its kernels.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdarg.h>
@@ -32,6 +33,21 @@ int ral_fail(const char* fmt, ...) {
   return -1;
 }
 extern "C" const char* ral_last_error(void) { return g_err; }
+// how the table entry points of the feature files end (ral_model.hpp)
+int table_done(const char* name, int rc, const char* why, long long bad, const char* args_fmt, ...) {
+  if (rc == 0) {
+    HIP_OK(hipGetLastError());
+    return 0;
+  }
+  if (rc != -1) return ral_fail("%s: copying the table to the device failed", name);
+  char row[40] = "", args[sizeof(g_err)];
+  if (bad >= 0) snprintf(row, sizeof(row), " in row %lld", bad);
+  va_list ap;
+  va_start(ap, args_fmt);
+  vsnprintf(args, sizeof(args), args_fmt, ap);
+  va_end(ap);
+  return ral_fail("%s: need %s%s (%s)", name, why, row, args);
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Switches.  A switch stays only while a test, a bench.py leg or a committed tool sets it to pick a kernel or a schedule;
@@ -409,535 +425,10 @@ int ral_profile_timeline(ral_handle* h, double* rows, int64_t cap_rows, int64_t*
   return m ? ralenet_profile_timeline(m, rows, cap_rows, nrows) : -1;
 }
 
-int ral_conv13_forward(const float* x, const float* w, const float* b, float* y, int B, int cin, int cout, int L,
-                       int lrelu, ral_stream s) {
-  const char* why = nullptr;
-  if (launch_conv13_fwd(x, w, b, y, B, cin, cout, L, lrelu, (hipStream_t)s, &why))
-    return ral_fail("ral_conv13_forward: %s (B=%d, channels %d -> %d, L=%d)", why, B, cin, cout, L);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-int ral_conv13_backward(const float* x, const float* y, const float* dy, const float* w, float* gw, float* gb,
-                        float* dx, int B, int cin, int cout, int L, int lrelu, ral_stream s) {
-  const char* why = nullptr;
-  if (launch_conv13_bwd(x, y, dy, w, gw, gb, dx, B, cin, cout, L, lrelu, (hipStream_t)s, &why))
-    return ral_fail("ral_conv13_backward: %s (B=%d, channels %d -> %d, L=%d)", why, B, cin, cout, L);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
 int ral_adam_flat(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
                   double eps, int step, float grad_scale, ral_stream s) {
   if (n % 4) return ral_fail("flat Adam needs a multiple of 4 floats");
   launch_adam(p, g, m, v, (size_t)n, lr, beta1, beta2, eps, step, grad_scale, (hipStream_t)s);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-int ral_prep_windows(const float* sig, const float* noise, int64_t T, int leads, int L, double snr_db, double* sums,
-                     float* noisy, float* clean, ral_stream s) {
-  if (!sig || !noise || !sums || !noisy || !clean) return ral_fail("prep_windows: null pointer");
-  if (launch_prep_windows(sig, noise, (long long)T, leads, L, snr_db, sums, noisy, clean, (hipStream_t)s))
-    return ral_fail("prep_windows: need 1 <= leads <= 16 and T a positive multiple of L (T=%lld leads=%d L=%d)", (long long)T, leads, L);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-int ral_stream_windows(const float* rec, int64_t R, int64_t T, int leads, int L, int hop, int64_t w0, int nw, float* win,
-                       float* stats, ral_stream s) {
-  if (!rec || !win || !stats) return ral_fail("stream_windows: null pointer");
-  if (launch_stream_windows(rec, (long long)R, (long long)T, leads, L, hop, (long long)w0, nw, win, stats, (hipStream_t)s))
-    return ral_fail("stream_windows: need R >= 1, T >= L, 1 <= hop <= L, L a multiple of 64 and <= 2048, a window range inside the records "
-                "(R=%lld T=%lld leads=%d L=%d hop=%d w0=%lld nw=%d)", (long long)R, (long long)T, leads, L, hop, (long long)w0, nw);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-int ral_stream_stitch(const float* y, const float* stats, int64_t R, int64_t T, int leads, int L, int hop, float* out,
-                      ral_stream s) {
-  if (!y || !stats || !out) return ral_fail("stream_stitch: null pointer");
-  if (launch_stream_stitch(y, stats, (long long)R, (long long)T, leads, L, hop, out, (hipStream_t)s))
-    return ral_fail("stream_stitch: need R >= 1, T >= L, 1 <= hop <= L with L - hop even (R=%lld T=%lld leads=%d L=%d hop=%d)",
-                (long long)R, (long long)T, leads, L, hop);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-int ral_live_windows(const float* hist, const float* x, float* hist_out, int64_t S, int leads, int L, int hop, int C, int64_t base,
-                     int64_t k0, int nw, int64_t T, int64_t w0, int nb, float* win, float* stats, ral_stream s) {
-  if (!hist || !x || !win || !stats) return ral_fail("live_windows: null pointer");
-  if (launch_live_windows(hist, x, hist_out, (long long)S, leads, L, hop, C, (long long)base, (long long)k0, nw, (long long)T,
-                          (long long)w0, nb, win, stats, (hipStream_t)s))
-    return ral_fail("live_windows: need S >= 1, leads >= 1, L a multiple of 64 and <= 2048, 1 <= hop <= L with L - hop even, C >= 0, "
-                "T < 0 or T >= L, windows k0 .. k0 + nw - 1 of the stream inside samples [base, base + L + C), a window range "
-                "inside the S * nw windows, and nb >= 1 or a history to write (S=%lld leads=%d L=%d hop=%d C=%d base=%lld k0=%lld "
-                "nw=%d T=%lld w0=%lld nb=%d)", (long long)S, leads, L, hop, C, (long long)base, (long long)k0, nw, (long long)T,
-                (long long)w0, nb);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-int ral_live_emit(const float* y, const float* stats, int64_t S, int leads, int L, int hop, int64_t k0, int nw, int64_t T,
-                  int64_t w0, int nb, int64_t lo, int m, float* out, float* last_y, float* last_stats, ral_stream s) {
-  if (!y || !stats || !out) return ral_fail("live_emit: null pointer");
-  if (launch_live_emit(y, stats, (long long)S, leads, L, hop, (long long)k0, nw, (long long)T, (long long)w0, nb, (long long)lo, m,
-                       out, last_y, last_stats, (hipStream_t)s))
-    return ral_fail("live_emit: need S >= 1, leads >= 1, L a multiple of 64 and <= 2048, 1 <= hop <= L with L - hop even, "
-                "T < 0 or T >= L with windows k0 .. k0 + nw - 1 in the stream, a window range of nb >= 1 windows inside the "
-                "S * nw, lo >= 0, m >= 0, and last_y and last_stats both given or both null (S=%lld leads=%d L=%d hop=%d "
-                "k0=%lld nw=%d T=%lld w0=%lld nb=%d lo=%lld m=%d)", (long long)S, leads, L, hop, (long long)k0, nw, (long long)T,
-                (long long)w0, nb, (long long)lo, m);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-int ral_newrale_stream_front(const float* rec, int64_t R, int64_t T, int L, int hop, int64_t w0, int nw,
-                             const float* adapter_params, float* inner_x, float* stats, ral_stream s) {
-  if (!rec || !adapter_params || !inner_x || !stats) return ral_fail("newrale_stream_front: null pointer");
-  if (launch_newrale_front(rec, (long long)R, (long long)T, L, hop, (long long)w0, nw, adapter_params, inner_x, stats, (hipStream_t)s))
-    return ral_fail("newrale_stream_front: need R >= 1, T >= L, L a multiple of 16 in [16, 1024], 1 <= hop <= L with L - hop even, "
-                "a window range inside the records (R=%lld T=%lld L=%d hop=%d w0=%lld nw=%d)", (long long)R, (long long)T, L, hop,
-                (long long)w0, nw);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-int ral_newrale_stream_back(const float* inner_y, const float* stats, const float* adapter_params, int64_t R, int64_t T, int L,
-                            int hop, int64_t w0, int nw, float* out, ral_stream s) {
-  if (!inner_y || !stats || !adapter_params || !out) return ral_fail("newrale_stream_back: null pointer");
-  if (launch_newrale_back(inner_y, stats, adapter_params, (long long)R, (long long)T, L, hop, (long long)w0, nw, out, (hipStream_t)s))
-    return ral_fail("newrale_stream_back: need R >= 1, T >= L, L a multiple of 16 in [16, 1024], 1 <= hop <= L with L - hop even, "
-                "a window range inside the records (R=%lld T=%lld L=%d hop=%d w0=%lld nw=%d)", (long long)R, (long long)T, L, hop,
-                (long long)w0, nw);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-int ral_newrale_live_front(const float* hist, const float* x, float* hist_out, int64_t S, int L, int hop, int C, int64_t base,
-                           int64_t k0, int nw, int64_t T, int64_t w0, int nb, const float* adapter_params, float* inner_x,
-                           float* stats, ral_stream s) {
-  if (!hist || !x || !adapter_params || !inner_x || !stats) return ral_fail("newrale_live_front: null pointer");
-  if (launch_newrale_live_front(hist, x, hist_out, (long long)S, L, hop, C, (long long)base, (long long)k0, nw, (long long)T,
-                                (long long)w0, nb, adapter_params, inner_x, stats, (hipStream_t)s))
-    return ral_fail("newrale_live_front: need S >= 1, L a multiple of 16 in [16, 1024], 1 <= hop <= L with L - hop even, C >= 0, "
-                "T < 0 or T >= L, windows k0 .. k0 + nw - 1 of the stream inside samples [base, base + L + C), a window range "
-                "inside the S * nw windows, and nb >= 1 or a history to write (another buffer than hist) (S=%lld L=%d hop=%d "
-                "C=%d base=%lld k0=%lld nw=%d T=%lld w0=%lld nb=%d)", (long long)S, L, hop, C, (long long)base, (long long)k0,
-                nw, (long long)T, (long long)w0, nb);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-int ral_newrale_live_back(const float* inner_y, const float* stats, const float* adapter_params, int64_t S, int L, int hop,
-                          int64_t k0, int nw, int64_t T, int64_t w0, int nb, int64_t lo, int m, float* out, float* last_y,
-                          float* last_stats, ral_stream s) {
-  if (!inner_y || !stats || !adapter_params || !out) return ral_fail("newrale_live_back: null pointer");
-  if (launch_newrale_live_back(inner_y, stats, adapter_params, (long long)S, L, hop, (long long)k0, nw, (long long)T,
-                               (long long)w0, nb, (long long)lo, m, out, last_y, last_stats, (hipStream_t)s))
-    return ral_fail("newrale_live_back: need S >= 1, L a multiple of 16 in [16, 1024], 1 <= hop <= L with L - hop even, "
-                "T < 0 or T >= L with windows k0 .. k0 + nw - 1 in the stream, a window range of nb >= 1 windows inside the "
-                "S * nw, lo >= 0, m >= 0, and last_y and last_stats both given or both null (S=%lld L=%d hop=%d k0=%lld nw=%d "
-                "T=%lld w0=%lld nb=%d lo=%lld m=%d)", (long long)S, L, hop, (long long)k0, nw, (long long)T, (long long)w0, nb,
-                (long long)lo, m);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-// How an entry point that takes a table ends.  rc = 0: launched; what the launches left behind is the result.  rc = -1,
-// refused: the one rule that is broken and, if it is a row's, which row, then the call's arguments as args_fmt words them.
-// Any other rc: the table did not reach the device.
-static int table_done(const char* name, int rc, const char* why, long long bad, const char* args_fmt, ...) {
-  if (rc == 0) {
-    HIP_OK(hipGetLastError());
-    return 0;
-  }
-  if (rc != -1) return ral_fail("%s: copying the table to the device failed", name);
-  char row[40] = "", args[sizeof(g_err)];
-  if (bad >= 0) snprintf(row, sizeof(row), " in row %lld", bad);
-  va_list ap;
-  va_start(ap, args_fmt);
-  vsnprintf(args, sizeof(args), args_fmt, ap);
-  va_end(ap);
-  return ral_fail("%s: need %s%s (%s)", name, why, row, args);
-}
-static const char POOL_ARGS[] = "rows=%d capacity=%lld L=%d hop=%d packed=%lld w0=%lld nb=%d";
-
-int ral_pool_windows(float* hist, const float* x, int64_t x_total, const ral_pool_row* table, int rows, ral_pool_row* table_dev,
-                     int upload, int64_t capacity, int leads, int L, int hop, int write_hist, int64_t w0, int nb, float* win,
-                     float* stats, ral_stream s) {
-  if (!hist || !x || !table || !table_dev || !win || !stats) return ral_fail("pool_windows: null pointer");
-  const char* why = nullptr;
-  int bad = -1;
-  const int rc = launch_pool_windows(hist, x, (long long)x_total, table, rows, table_dev, upload, (long long)capacity, leads, L, hop,
-                                     write_hist, (long long)w0, nb, win, stats, (hipStream_t)s, &why, &bad);
-  return table_done("pool_windows", rc, why, bad, POOL_ARGS, rows, (long long)capacity, L, hop, (long long)x_total, (long long)w0,
-                    nb);
-}
-
-int ral_pool_emit(const float* y, const float* stats, const ral_pool_row* table, int rows, ral_pool_row* table_dev, int upload,
-                  int64_t capacity, int leads, int L, int hop, int64_t w0, int nb, int from_last, float* out, int64_t out_total,
-                  float* last_y, float* last_stats, ral_stream s) {
-  if (!y || !stats || !table || !table_dev || !out) return ral_fail("pool_emit: null pointer");
-  const char* why = nullptr;
-  int bad = -1;
-  const int rc = launch_pool_emit(y, stats, table, rows, table_dev, upload, (long long)capacity, leads, L, hop, (long long)w0, nb,
-                                  from_last, out, (long long)out_total, last_y, last_stats, (hipStream_t)s, &why, &bad);
-  return table_done("pool_emit", rc, why, bad, POOL_ARGS, rows, (long long)capacity, L, hop, (long long)out_total, (long long)w0,
-                    nb);
-}
-
-int ral_newrale_pool_front(float* hist, const float* x, int64_t x_total, const ral_pool_row* table, int rows,
-                           ral_pool_row* table_dev, int upload, int64_t capacity, int L, int hop, int write_hist, int64_t w0,
-                           int nb, const float* adapter_params, float* inner_x, float* stats, ral_stream s) {
-  if (!hist || !x || !table || !table_dev || !adapter_params || !inner_x || !stats) return ral_fail("newrale_pool_front: null pointer");
-  const char* why = nullptr;
-  int bad = -1;
-  const int rc = launch_newrale_pool_front(hist, x, (long long)x_total, table, rows, table_dev, upload, (long long)capacity, L, hop,
-                                           write_hist, (long long)w0, nb, adapter_params, inner_x, stats, (hipStream_t)s, &why, &bad);
-  return table_done("newrale_pool_front", rc, why, bad, POOL_ARGS, rows, (long long)capacity, L, hop, (long long)x_total,
-                    (long long)w0, nb);
-}
-
-int ral_newrale_pool_back(const float* inner_y, const float* stats, const float* adapter_params, const ral_pool_row* table,
-                          int rows, ral_pool_row* table_dev, int upload, int64_t capacity, int L, int hop, int64_t w0, int nb,
-                          int from_last, float* out, int64_t out_total, float* last_y, float* last_stats, ral_stream s) {
-  if (!inner_y || !stats || !adapter_params || !table || !table_dev || !out) return ral_fail("newrale_pool_back: null pointer");
-  const char* why = nullptr;
-  int bad = -1;
-  const int rc = launch_newrale_pool_back(inner_y, stats, adapter_params, table, rows, table_dev, upload, (long long)capacity, L,
-                                          hop, (long long)w0, nb, from_last, out, (long long)out_total, last_y, last_stats,
-                                          (hipStream_t)s, &why, &bad);
-  return table_done("newrale_pool_back", rc, why, bad, POOL_ARGS, rows, (long long)capacity, L, hop, (long long)out_total,
-                    (long long)w0, nb);
-}
-
-int64_t ral_mix_records_scratch_bytes(int64_t R, int leads, int64_t T) {
-  const long long n = mix_records_scratch_bytes((long long)R, leads, (long long)T);
-  if (n < 0) return ral_fail("mix_records_scratch_bytes: need R >= 1, 1 <= leads <= 16, T >= 1 (R=%lld leads=%d T=%lld)", (long long)R, leads, (long long)T);
-  return n;
-}
-
-int ral_mix_records(const float* rec, const float* noise, int64_t R, int leads, int64_t T, int64_t Tn, const int64_t* offsets,
-                    const double* snr_db, void* scratch, float* noisy, float* clean, ral_stream s) {
-  if (!rec || !noise || !offsets || !snr_db || !scratch || !noisy || !clean) return ral_fail("mix_records: need no null pointer");
-  const char* why = nullptr;
-  long long bad = -1;
-  const int rc = launch_mix_records(rec, noise, (long long)R, leads, (long long)T, (long long)Tn, offsets, snr_db, scratch, noisy,
-                                    clean, (hipStream_t)s, &why, &bad);
-  if (rc == -1) {
-    char at[96] = "";
-    if (bad >= 0) snprintf(at, sizeof(at), " in record %lld (offset=%lld snr_db=%g)", bad, (long long)offsets[bad], snr_db[bad]);
-    return ral_fail("mix_records: need %s%s (R=%lld leads=%d T=%lld Tn=%lld)", why, at, (long long)R, leads, (long long)T, (long long)Tn);
-  }
-  if (rc) return ral_fail("mix_records: copying offsets / snr_db to the device failed");
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-int64_t ral_score_records_scratch_bytes(int64_t R, int leads, int64_t T, int64_t W) {
-  const long long n = score_records_scratch_bytes((long long)R, leads, (long long)T, (long long)W);
-  if (n < 0)
-    return ral_fail("score_records_scratch_bytes: need R >= 1, 1 <= leads <= 16, T >= 1, 1 <= W <= T (R=%lld leads=%d T=%lld W=%lld)",
-                (long long)R, leads, (long long)T, (long long)W);
-  return n;
-}
-
-int ral_score_records(const float* clean, const float* out, const float* noisy, int64_t R, int leads, int64_t T, int64_t W,
-                      void* scratch, double* per_lead, double* per_record, double* per_window, double* window_mean, ral_stream s) {
-  if (!clean || !out || !scratch || !per_lead || !per_record || !per_window || !window_mean)
-    return ral_fail("score_records: need no null pointer (only noisy may be null)");
-  const char* why = nullptr;
-  if (launch_score_records(clean, out, noisy, (long long)R, leads, (long long)T, (long long)W, scratch, per_lead, per_record,
-                           per_window, window_mean, (hipStream_t)s, &why))
-    return ral_fail("score_records: need %s (R=%lld leads=%d T=%lld W=%lld)", why, (long long)R, leads, (long long)T, (long long)W);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-static MixBatchGeom mix_geom(int64_t N, int leads, int64_t Lsrc, int L, int K, int64_t Tn, const uint32_t* cum, double snr_lo,
-                             double snr_hi, uint64_t seed, uint64_t first) {
-  MixBatchGeom G;
-  G.N = (long long)N; G.Lsrc = (long long)Lsrc; G.Tn = (long long)Tn;
-  G.leads = leads; G.L = L; G.K = K;
-  for (int k = 0; k < RAL_MIX_MAX_KINDS; ++k) G.cum[k] = (cum && k < K) ? cum[k] : 0xffffffffu;
-  G.snr_lo = snr_lo; G.snr_hi = snr_hi;
-  G.seed = seed; G.first = first;
-  return G;
-}
-#define MIX_ARGS "(N=%lld leads=%d Lsrc=%lld L=%d K=%d Tn=%lld B=%lld snr_db=[%g, %g])"
-
-int ral_mix_batch(const float* bank, const float* noise, const int64_t* rows, int64_t N, int leads, int64_t Lsrc, int L, int K,
-                  int64_t Tn, const uint32_t* cum, double snr_lo, double snr_hi, uint64_t seed, uint64_t first, int64_t B,
-                  float* noisy, float* clean, int32_t* draws, double* snr_db, ral_stream s) {
-  const char* why = nullptr;
-  int rc = -1;
-  if (!bank || !noise || !cum || !noisy || !clean || !draws || !snr_db) why = "no null pointer (only rows may be null)";
-  else rc = launch_mix_batch(bank, noise, rows, mix_geom(N, leads, Lsrc, L, K, Tn, cum, snr_lo, snr_hi, seed, first), (long long)B,
-                             noisy, clean, draws, snr_db, (hipStream_t)s, &why);
-  if (rc)
-    return ral_fail("mix_batch: need %s " MIX_ARGS, why, (long long)N, leads, (long long)Lsrc, L, K, (long long)Tn, (long long)B,
-                    snr_lo, snr_hi);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-int ral_mix_draw(int64_t N, int64_t Lsrc, int L, int K, int64_t Tn, const uint32_t* cum, double snr_lo, double snr_hi,
-                 uint64_t seed, uint64_t g, int32_t* draw, double* snr_db) {
-  const MixBatchGeom G = mix_geom(N, 1, Lsrc, L, K, Tn, cum, snr_lo, snr_hi, seed, 0);
-  const char* why = (!cum || !draw || !snr_db) ? "no null pointer" : mix_batch_check(G);
-  if (why)
-    return ral_fail("mix_draw: need %s " MIX_ARGS, why, (long long)N, 1, (long long)Lsrc, L, K, (long long)Tn, 1LL, snr_lo, snr_hi);
-  mix_batch_draw(G, g, draw, snr_db);
-  return 0;
-}
-
-int ral_rate_records(const float* x, int64_t R, int leads, int64_t T, int up, int down, const float* bank, int ntaps, float* y,
-                     int64_t T_out, ral_stream s) {
-  if (!x || !bank || !y) return ral_fail("rate_records: null pointer");
-  const char* why = nullptr;
-  if (launch_rate_records(x, (long long)R, leads, (long long)T, up, down, bank, ntaps, y, (long long)T_out, (hipStream_t)s, &why))
-    return ral_fail("rate_records: need %s (R=%lld leads=%d T=%lld up=%d down=%d ntaps=%d T_out=%lld)", why, (long long)R, leads,
-                (long long)T, up, down, ntaps, (long long)T_out);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-int ral_rate_pool(float* hist, const float* x, int64_t x_total, const ral_rate_row* table, int rows, ral_rate_row* table_dev,
-                  int upload, int64_t capacity, int leads, int up, int down, const float* bank, int ntaps, int hist_len, float* out,
-                  int64_t out_total, ral_stream s) {
-  if (!hist || !x || !table || !table_dev || !bank || !out) return ral_fail("rate_pool: null pointer");
-  const char* why = nullptr;
-  int bad = -1;
-  const int rc = launch_rate_pool(hist, x, (long long)x_total, table, rows, table_dev, upload, (long long)capacity, leads, up, down,
-                                  bank, ntaps, hist_len, out, (long long)out_total, (hipStream_t)s, &why, &bad);
-  return table_done("rate_pool", rc, why, bad, "rows=%d capacity=%lld leads=%d up=%d down=%d ntaps=%d hist_len=%d x_total=%lld "
-                    "out_total=%lld", rows, (long long)capacity, leads, up, down, ntaps, hist_len, (long long)x_total,
-                    (long long)out_total);
-}
-
-static void beat_geom_text(const ral_beat_geom* g, char* buf, size_t n) {
-  if (g) snprintf(buf, n, "half=%d Wi=%d Wt=%d Rf=%d Rw=%d alpha=%g floor=%g", g->half, g->wi, g->wt, g->rf, g->rw, g->alpha, g->floor);
-  else snprintf(buf, n, "no geometry");
-}
-
-int64_t ral_beat_records_scratch_bytes(int64_t R, int leads, int64_t T, const ral_beat_geom* geom) {
-  const char* why = nullptr;
-  const long long n = beat_records_scratch_bytes((long long)R, leads, (long long)T, geom, &why);
-  if (n < 0) {
-    char gt[160];
-    beat_geom_text(geom, gt, sizeof(gt));
-    return ral_fail("beat_records_scratch_bytes: need %s (R=%lld leads=%d T=%lld %s)", why, (long long)R, leads, (long long)T, gt);
-  }
-  return n;
-}
-
-int ral_beat_records(const float* x, int64_t R, int leads, int64_t T, const ral_beat_geom* geom, const float* bank, int ntaps,
-                     void* scratch, int64_t scratch_bytes, int32_t* peaks, int64_t cap, int32_t* count, ral_stream s) {
-  if (!x || !geom || !bank || !scratch || !peaks || !count) return ral_fail("beat_records: null pointer");
-  const char* why = nullptr;
-  if (launch_beat_records(x, (long long)R, leads, (long long)T, geom, bank, ntaps, scratch, (long long)scratch_bytes, peaks,
-                          (long long)cap, count, (hipStream_t)s, &why)) {
-    char gt[160];
-    beat_geom_text(geom, gt, sizeof(gt));
-    return ral_fail("beat_records: need %s (R=%lld leads=%d T=%lld ntaps=%d cap=%lld scratch_bytes=%lld %s)", why, (long long)R, leads,
-                (long long)T, ntaps, (long long)cap, (long long)scratch_bytes, gt);
-  }
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-int ral_beat_pool(float* hist, const float* x, int64_t x_total, const ral_beat_row* table, int rows, ral_beat_row* table_dev,
-                  int upload, int64_t capacity, int leads, const ral_beat_geom* geom, const float* bank, int ntaps, int hist_len,
-                  void* scratch, int64_t scratch_bytes, int64_t* peaks, int64_t peaks_total, int32_t* count, ral_stream s) {
-  if (!hist || !x || !table || !table_dev || !geom || !bank || !scratch || !peaks || !count) return ral_fail("beat_pool: null pointer");
-  const char* why = nullptr;
-  int bad = -1;
-  const int rc = launch_beat_pool(hist, x, (long long)x_total, table, rows, table_dev, upload, (long long)capacity, leads, geom, bank,
-                                  ntaps, hist_len, scratch, (long long)scratch_bytes, (long long*)peaks, (long long)peaks_total, count,
-                                  (hipStream_t)s, &why, &bad);
-  char gt[160] = "";
-  if (rc) beat_geom_text(geom, gt, sizeof(gt));
-  return table_done("beat_pool", rc, why, bad, "rows=%d capacity=%lld leads=%d ntaps=%d hist_len=%d x_total=%lld "
-                    "peaks_total=%lld scratch_bytes=%lld %s", rows, (long long)capacity, leads, ntaps, hist_len, (long long)x_total,
-                    (long long)peaks_total, (long long)scratch_bytes, gt);
-}
-
-int ral_beat_match(const int32_t* ref, const int32_t* ref_count, int64_t ref_cap, const int32_t* det, const int32_t* det_count,
-                   int64_t det_cap, int64_t R, int64_t tol, int64_t* out, ral_stream s) {
-  if (!ref || !ref_count || !det || !det_count || !out) return ral_fail("beat_match: null pointer");
-  const char* why = nullptr;
-  if (launch_beat_match(ref, ref_count, (long long)ref_cap, det, det_count, (long long)det_cap, (long long)R, (long long)tol,
-                        (long long*)out, (hipStream_t)s, &why))
-    return ral_fail("beat_match: need %s (R=%lld ref_cap=%lld det_cap=%lld tol=%lld)", why, (long long)R, (long long)ref_cap,
-                (long long)det_cap, (long long)tol);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-static void rhythm_geom_text(const ral_rhythm_geom* g, char* buf, size_t n) {
-  if (g) snprintf(buf, n, "Wb=%d Sa=%d c0=%g r0=%g", g->wb, g->sa, g->c0, g->r0);
-  else snprintf(buf, n, "no geometry");
-}
-
-int64_t ral_rhythm_pool_scratch_bytes(int64_t beats, int leads, const ral_rhythm_geom* geom) {
-  const char* why = nullptr;
-  const long long n = rhythm_pool_scratch_bytes((long long)beats, leads, geom, &why);
-  if (n < 0) {
-    char gt[96];
-    rhythm_geom_text(geom, gt, sizeof(gt));
-    return ral_fail("rhythm_pool_scratch_bytes: need %s (beats=%lld leads=%d %s)", why, (long long)beats, leads, gt);
-  }
-  return n;
-}
-
-int ral_rhythm_records(const float* x, int64_t R, int leads, int64_t T, const ral_rhythm_geom* geom, const int32_t* peaks,
-                       const int32_t* count, int64_t cap, int32_t* label, float* corr, float* rr_ratio, ral_stream s) {
-  if (!x || !geom || !peaks || !count || !label || !corr || !rr_ratio) return ral_fail("rhythm_records: null pointer");
-  const char* why = nullptr;
-  if (launch_rhythm_records(x, (long long)R, leads, (long long)T, geom, peaks, count, (long long)cap, label, corr, rr_ratio,
-                            (hipStream_t)s, &why)) {
-    char gt[96];
-    rhythm_geom_text(geom, gt, sizeof(gt));
-    return ral_fail("rhythm_records: need %s (R=%lld leads=%d T=%lld cap=%lld %s)", why, (long long)R, leads, (long long)T,
-                (long long)cap, gt);
-  }
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-int ral_rhythm_pool(const float* hist, const float* x, int64_t x_total, const ral_rhythm_row* table, int rows,
-                    ral_rhythm_row* table_dev, int upload, int64_t capacity, int leads, const ral_rhythm_geom* geom, int hist_len,
-                    float* ring, int64_t* ring_pos, const int64_t* new_pos, int64_t new_total, void* scratch,
-                    int64_t scratch_bytes, int64_t* out_pos, int32_t* label, float* corr, float* rr_ratio, int64_t out_total,
-                    ral_stream s) {
-  if (!hist || !x || !table || !table_dev || !geom || !ring || !ring_pos || !new_pos || !scratch || !out_pos || !label || !corr ||
-      !rr_ratio)
-    return ral_fail("rhythm_pool: null pointer");
-  const char* why = nullptr;
-  int bad = -1;
-  const int rc = launch_rhythm_pool(hist, x, (long long)x_total, table, rows, table_dev, upload, (long long)capacity, leads, geom,
-                                    hist_len, ring, (long long*)ring_pos, (const long long*)new_pos, (long long)new_total, scratch,
-                                    (long long)scratch_bytes, (long long*)out_pos, label, corr, rr_ratio, (long long)out_total,
-                                    (hipStream_t)s, &why, &bad);
-  char gt[96] = "";
-  if (rc) rhythm_geom_text(geom, gt, sizeof(gt));
-  return table_done("rhythm_pool", rc, why, bad, "rows=%d capacity=%lld leads=%d hist_len=%d x_total=%lld new_total=%lld "
-                    "out_total=%lld scratch_bytes=%lld %s", rows, (long long)capacity, leads, hist_len, (long long)x_total,
-                    (long long)new_total, (long long)out_total, (long long)scratch_bytes, gt);
-}
-
-int ral_delineate_records(const float* x, int64_t R, int leads, int64_t T, const ral_delin_geom* geom, const int32_t* peaks,
-                          const int32_t* count, int64_t cap, int32_t* on, int32_t* off, int32_t* tpeak, int32_t* tend, ral_stream s) {
-  if (!x || !geom || !peaks || !count || !on || !off || !tpeak || !tend) return ral_fail("delineate_records: null pointer");
-  const char* why = nullptr;
-  if (launch_delineate_records(x, (long long)R, leads, (long long)T, geom, peaks, count, (long long)cap, on, off, tpeak, tend,
-                               (hipStream_t)s, &why))
-    return ral_fail("delineate_records: need %s (R=%lld leads=%d T=%lld cap=%lld h=%d m=%d Wq=%d g=%d m2=%d gt=%d Wt=%d q0=%g)", why,
-                    (long long)R, leads, (long long)T, (long long)cap, geom->h, geom->m, geom->wq, geom->g, geom->m2, geom->gt,
-                    geom->wt, geom->q0);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-int ral_pst_records(const float* x, int64_t R, int leads, int64_t T, const ral_pst_geom* geom, const int32_t* peaks,
-                    const int32_t* count, int64_t cap, const int32_t* on, const int32_t* off, int32_t* pon, int32_t* ppeak,
-                    int32_t* poff, float* st, ral_stream s) {
-  if (!x || !geom || !peaks || !count || !on || !off || !pon || !ppeak || !poff || !st) return ral_fail("pst_records: null pointer");
-  const char* why = nullptr;
-  if (launch_pst_records(x, (long long)R, leads, (long long)T, geom, peaks, count, (long long)cap, on, off, pon, ppeak, poff, st,
-                         (hipStream_t)s, &why))
-    return ral_fail("pst_records: need %s (R=%lld leads=%d T=%lld cap=%lld m2=%d g=%d Wp=%d j=%d w=%g p0=%g)", why, (long long)R,
-                    leads, (long long)T, (long long)cap, geom->m2, geom->g, geom->wp, geom->j, geom->w, geom->p0);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-int ral_template_records(const float* x, int64_t R, int leads, int64_t T, const ral_template_geom* geom, const int32_t* peaks,
-                         const int32_t* label_or_null, const int32_t* count, int64_t cap, int64_t nw, float* tpl, int32_t* used,
-                         int32_t* total, int32_t* rr, ral_stream s) {
-  const char* why = nullptr;
-  if (launch_template_records(x, (long long)R, leads, (long long)T, geom, peaks, label_or_null, count, (long long)cap,
-                              (long long)nw, tpl, used, total, rr, (hipStream_t)s, &why)) {
-    const ral_template_geom none = {0, 0, 0, 0, 0}, *g = geom ? geom : &none;
-    return ral_fail("ral_template_records: %s (R=%lld leads=%d T=%lld cap=%lld nw=%lld wpre=%d wpost=%d w=%d h=%d kmax=%d)", why,
-                    (long long)R, leads, (long long)T, (long long)cap, (long long)nw, g->wpre, g->wpost, g->w, g->h, g->kmax);
-  }
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-int ral_hrv_windows(const int32_t* pos, const int32_t* label_or_null, const int32_t* count, int64_t R, int64_t cap,
-                    const ral_hrv_row* table, int64_t rows, ral_hrv_row* table_dev, int upload, const ral_hrv_geom* geom,
-                    const int32_t* band, int32_t* counts, float* stats, float* psd_or_null, ral_stream s) {
-  if (!pos || !count || !table_dev || (upload && !table) || !geom || !band || !counts || !stats)
-    return ral_fail("hrv_windows: null pointer");
-  const char* why = nullptr;
-  long long bad = -1;
-  const int rc = launch_hrv_windows(pos, label_or_null, count, (long long)R, (long long)cap, table, (long long)rows, table_dev,
-                                    upload, geom, band, counts, stats, psd_or_null, (hipStream_t)s, &why, &bad);
-  return table_done("hrv_windows", rc, why, bad, "R=%lld cap=%lld rows=%lld W=%d lo_n=%d hi_n=%d t50=%d F=%d min_nn=%d fs=%g",
-                    (long long)R, (long long)cap, (long long)rows, geom->W, geom->lo_n, geom->hi_n, geom->t50, geom->F,
-                    geom->min_nn, geom->fs);
-}
-
-int ral_arrhythmia_windows(const int32_t* peaks, const int32_t* label_or_null, const int32_t* count, const int32_t* on_or_null,
-                           const int32_t* ppeak_or_null, int64_t R, int64_t cap, const ral_hrv_row* table, int64_t rows,
-                           ral_hrv_row* table_dev, int upload, const ral_arrhythmia_geom* geom, int32_t* counts, float* stats,
-                           int32_t* flags, ral_stream s) {
-  static const char NAME[] = "ral_arrhythmia_windows";
-  // (the host table is read only when it is uploaded: without upload NAME stands in for it as something non-null)
-  const struct { const void* p; const char* name; } need[] = {{peaks, "peaks"}, {count, "count"}, {table_dev, "table_dev"},
-      {upload ? (const void*)table : (const void*)NAME, "table"}, {geom, "geom"}, {counts, "counts"}, {stats, "stats"}, {flags, "flags"}};
-  for (const auto& a : need)
-    if (!a.p) return ral_fail("%s: need a non-null %s", NAME, a.name);
-  if (!on_or_null != !ppeak_or_null)
-    return ral_fail("%s: need on and ppeak together or neither (%s is null)", NAME, on_or_null ? "ppeak" : "on");
-  const char* why = nullptr;
-  long long bad = -1;
-  const int rc = launch_arrhythmia_windows(peaks, label_or_null, count, on_or_null, ppeak_or_null, (long long)R, (long long)cap, table,
-                                           (long long)rows, table_dev, upload, geom, counts, stats, flags, (hipStream_t)s, &why, &bad);
-  return table_done(NAME, rc, why, bad, "R=%lld cap=%lld rows=%lld W=%d lo_n=%d hi_n=%d bin=%d G=%d lock_n=%d prmax=%d pause_n=%d "
-                    "min_m=%d vrun_min=%d n0=%g c0=%g pl0=%g tachy=%g brady=%g fs=%g", (long long)R, (long long)cap, (long long)rows,
-                    geom->W, geom->lo_n, geom->hi_n, geom->bin, geom->G, geom->lock_n, geom->prmax, geom->pause_n, geom->min_m,
-                    geom->vrun_min, geom->n0, geom->c0, geom->pl0, geom->tachy, geom->brady, geom->fs);
-}
-
-int ral_wavelet_denoise(const float* x, float* y, int64_t rows, int L, float threshold, ral_stream s) {
-  if (!x || !y) return ral_fail("wavelet_denoise: null pointer");
-  if (!(threshold >= 0.f)) return ral_fail("wavelet_denoise: the threshold factor must be non-negative (got %g)", (double)threshold);
-  if (launch_wavelet_denoise(x, y, (long long)rows, L, threshold, (hipStream_t)s))
-    return ral_fail("wavelet_denoise: need rows >= 0 and an even record length <= 8192 (rows=%lld L=%d)", (long long)rows, L);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-static int fft_denoise_counts(const char* who, int64_t groups, int rows_per_group, int L) {
-  if (groups < 0 || rows_per_group < 1)
-    return ral_fail("%s: need groups >= 0 and rows_per_group >= 1 (groups=%lld rows_per_group=%d)", who, (long long)groups, rows_per_group);
-  if (groups > 0x7fffffffLL / rows_per_group)
-    return ral_fail("%s: need groups * rows_per_group < 2^31 (groups=%lld rows_per_group=%d)", who, (long long)groups, rows_per_group);
-  if (fft_denoise_scratch_bytes(0, 1, L) < 0) return ral_fail("%s: L=%d is not supported: need %s", who, L, fft_denoise_rule());
-  return 0;
-}
-
-int64_t ral_fft_denoise_scratch_bytes(int64_t groups, int rows_per_group, int L) {
-  if (fft_denoise_counts("fft_denoise_scratch_bytes", groups, rows_per_group, L)) return -1;
-  return (int64_t)fft_denoise_scratch_bytes((long long)groups, rows_per_group, L);
-}
-
-int ral_fft_denoise(const float* x, float* y, int32_t* kept, int64_t groups, int rows_per_group, int L, float threshold,
-                    void* scratch, ral_stream s) {
-  if (!x || !y) return ral_fail("fft_denoise: null pointer (x=%p y=%p)", (const void*)x, (void*)y);
-  if (fft_denoise_counts("fft_denoise", groups, rows_per_group, L)) return -1;
-  if (!(threshold >= 0.f)) return ral_fail("fft_denoise: the threshold factor must be non-negative (got %g)", (double)threshold);
-  const long long need = fft_denoise_scratch_bytes((long long)groups, rows_per_group, L);
-  if (need > 0 && !scratch)
-    return ral_fail("fft_denoise: null scratch, %lld bytes are needed (groups=%lld rows_per_group=%d L=%d)", need, (long long)groups,
-                rows_per_group, L);
-  const int rc = launch_fft_denoise(x, y, kept, (long long)groups, rows_per_group, L, threshold, scratch, (hipStream_t)s);
-  if (rc == -2) return ral_fail("fft_denoise: %s", hipGetErrorString(hipGetLastError()));
-  if (rc) return ral_fail("fft_denoise: refused (groups=%lld rows_per_group=%d L=%d)", (long long)groups, rows_per_group, L);
   HIP_OK(hipGetLastError());
   return 0;
 }

@@ -19,7 +19,9 @@
 //   cells      the bitmap's words are popcounted
 // Nothing depends on the members being sparse: a window holds up to W of them and the sweep takes them 256 at a time.  No
 // scratch memory, no global atomics, no memset; LDS: 4 (prmax + 1) + 4 ceil((2G + 1)^2 / 32) bytes, at most 34 KB, plus 80 bytes static.
-#include "ral_kernels.hpp"
+#include "../../include/ralenet.h"
+#include "ral_device.hpp"
+#include "ral_model.hpp"
 #include "ral_slots.hpp"
 #include <math.h>
 #include <stdint.h>
@@ -298,29 +300,47 @@ const char* arr_geom(const ral_arrhythmia_geom* p, ArrGeom& g) {
 
 }  // namespace
 
-int launch_arrhythmia_windows(const int* peaks, const int* label, const int* count, const int* on, const int* ppeak, long long R,
-                              long long cap, const ral_hrv_row* tab, long long rows, ral_hrv_row* tab_dev, int upload,
-                              const ral_arrhythmia_geom* geom, int* counts, float* stats, int* flags, hipStream_t s,
-                              const char** why, long long* bad) {
-  ArrGeom g;
+// the rule a call breaks (*bad: the table row that breaks it, or -1), or null; the table is read only when it is uploaded
+static const char* arr_fault(long long R, long long cap, const ral_hrv_row* tab, long long rows, int upload,
+                             const ral_arrhythmia_geom* geom, ArrGeom& g, long long* bad) {
   *bad = -1;
-  if (R < 1 || R > 65535) { *why = "1 <= R <= 65535"; return -1; }
-  if (cap < 1 || cap > 0x7fffffffLL) { *why = "1 <= cap < 2^31"; return -1; }
-  if ((*why = arr_geom(geom, g))) return -1;
-  if (rows < 0 || rows > 0x7fffffffLL) { *why = "0 <= rows < 2^31"; return -1; }
-  if (rows == 0) return 0;
-  if (upload) {
-    for (long long r = 0; r < rows; ++r) {
-      const ral_hrv_row& t = tab[r];
-      *bad = r;
-      if (t.rec < 0 || t.rec >= R) { *why = "0 <= rec < R"; return -1; }
-      if (t.w0 < 0 || t.w1 <= t.w0 || t.w1 > t.w0 + g.W) { *why = "0 <= w0 < w1 <= w0 + W"; return -1; }
-    }
-    *bad = -1;
-    if (slots_upload(tab, rows, tab_dev, s)) return -2;
+  if (R < 1 || R > 65535) return "1 <= R <= 65535";
+  if (cap < 1 || cap > 0x7fffffffLL) return "1 <= cap < 2^31";
+  if (const char* why = arr_geom(geom, g)) return why;
+  if (rows < 0 || rows > 0x7fffffffLL) return "0 <= rows < 2^31";
+  for (long long r = 0; upload && r < rows; ++r) {
+    const ral_hrv_row& t = tab[r];
+    *bad = r;
+    if (t.rec < 0 || t.rec >= R) return "0 <= rec < R";
+    if (t.w0 < 0 || t.w1 <= t.w0 || t.w1 > t.w0 + g.W) return "0 <= w0 < w1 <= w0 + W";
   }
-  const size_t lds = ((size_t)g.prmax + 1 + (size_t)g.words) * 4;
-  k_arrhythmia_windows<<<dim3((unsigned)rows), AR_THREADS, lds, s>>>(peaks, label, count, on, ppeak, cap, tab_dev, g, counts, stats,
-                                                                     flags);
-  return 0;
+  *bad = -1;
+  return nullptr;
+}
+
+extern "C" int ral_arrhythmia_windows(const int32_t* peaks, const int32_t* label_or_null, const int32_t* count,
+                                      const int32_t* on_or_null, const int32_t* ppeak_or_null, int64_t R, int64_t cap,
+                                      const ral_hrv_row* table, int64_t rows, ral_hrv_row* table_dev, int upload,
+                                      const ral_arrhythmia_geom* geom, int32_t* counts, float* stats, int32_t* flags, ral_stream s) {
+  static const char NAME[] = "ral_arrhythmia_windows";
+  // (the host table is read only when it is uploaded: without upload NAME stands in for it as something non-null)
+  const struct { const void* p; const char* name; } need[] = {{peaks, "peaks"}, {count, "count"}, {table_dev, "table_dev"},
+      {upload ? (const void*)table : (const void*)NAME, "table"}, {geom, "geom"}, {counts, "counts"}, {stats, "stats"}, {flags, "flags"}};
+  for (const auto& a : need)
+    if (!a.p) return ral_fail("%s: need a non-null %s", NAME, a.name);
+  if (!on_or_null != !ppeak_or_null)
+    return ral_fail("%s: need on and ppeak together or neither (%s is null)", NAME, on_or_null ? "ppeak" : "on");
+  ArrGeom g;
+  long long bad = -1;
+  const char* why = arr_fault(R, cap, table, rows, upload, geom, g, &bad);
+  const int rc = why ? -1 : (upload && rows > 0) ? slots_upload(table, rows, table_dev, (hipStream_t)s) : 0;
+  if (!rc && rows > 0) {
+    const size_t lds = ((size_t)g.prmax + 1 + (size_t)g.words) * 4;
+    k_arrhythmia_windows<<<dim3((unsigned)rows), AR_THREADS, lds, (hipStream_t)s>>>(peaks, label_or_null, count, on_or_null, ppeak_or_null,
+                                                                                  cap, table_dev, g, counts, stats, flags);
+  }
+  return table_done(NAME, rc, why, bad, "R=%lld cap=%lld rows=%lld W=%d lo_n=%d hi_n=%d bin=%d G=%d lock_n=%d prmax=%d pause_n=%d "
+                    "min_m=%d vrun_min=%d n0=%g c0=%g pl0=%g tachy=%g brady=%g fs=%g", (long long)R, (long long)cap, (long long)rows,
+                    geom->W, geom->lo_n, geom->hi_n, geom->bin, geom->G, geom->lock_n, geom->prmax, geom->pause_n, geom->min_m,
+                    geom->vrun_min, geom->n0, geom->c0, geom->pl0, geom->tachy, geom->brady, geom->fs);
 }

@@ -14,8 +14,18 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "../../include/ralenet.h"
 #include "ral_device.hpp"
-#include "ral_kernels.hpp"
+#include "ral_model.hpp"
+
+// The geometry of a call travels by value, as a kernel argument (thresholds included: no copy).
+struct MixBatchGeom {
+  long long N, Lsrc, Tn;
+  int leads, L, K;
+  uint32_t cum[RAL_MIX_MAX_KINDS];
+  double snr_lo, snr_hi;
+  uint64_t seed, first;
+};
 
 #define AUG_THREADS 256
 #define AUG_WAVES (AUG_THREADS / 64)
@@ -50,12 +60,6 @@ static __host__ __device__ inline void mix_draw(const MixBatchGeom& G, uint64_t 
   d[2] = kind;
   d[3] = mul_hi(b[0], (uint32_t)(G.Tn - G.L + 1));
   *snr_db = G.snr_lo + (G.snr_hi - G.snr_lo) * ((double)a[3] * (1.0 / 4294967296.0));
-}
-
-void mix_batch_draw(const MixBatchGeom& G, uint64_t g, int32_t* draw, double* snr_db) {
-  uint32_t d[4];
-  mix_draw(G, g, d, snr_db);
-  for (int i = 0; i < 4; ++i) draw[i] = (int32_t)d[i];
 }
 
 static __device__ __forceinline__ double aug_wave_sum(double v) {
@@ -166,20 +170,8 @@ __global__ __launch_bounds__(AUG_THREADS) void k_mix_batch(const float* __restri
   }
 }
 
-int launch_mix_batch(const float* bank, const float* noise, const int64_t* rows, const MixBatchGeom& G, long long B, float* noisy,
-                     float* clean, int32_t* draws, double* snr_db, hipStream_t s, const char** why) {
-  if ((*why = mix_batch_check(G)) != nullptr) return -1;
-  if (B < 1) return *why = "B >= 1", -1;
-  if (B > 0x7fffffffLL) return *why = "N < 2^31, B < 2^31, Lsrc - L + 1 < 2^32 and Tn - L + 1 < 2^32", -1;
-  const size_t lds = AUG_PART * sizeof(double) + 2 * (size_t)G.leads * G.L * sizeof(float);
-  RAL_SET_LDS(k_mix_batch, lds);
-  k_mix_batch<<<(unsigned)B, AUG_THREADS, lds, s>>>(bank, noise, reinterpret_cast<const long long*>(rows), G, noisy, clean, draws,
-                                                    snr_db);
-  return 0;
-}
-
 // the rules of the draw and of the window geometry (everything but B and the pointers); nullptr: all hold
-const char* mix_batch_check(const MixBatchGeom& G) {
+static const char* mix_batch_check(const MixBatchGeom& G) {
   if (G.N < 1) return "N >= 1";
   if (G.leads < 1 || G.leads > AUG_MAXLEADS) return "1 <= leads <= 16";
   if (G.L < 1 || G.L > G.Lsrc) return "1 <= L <= Lsrc";
@@ -192,4 +184,48 @@ const char* mix_batch_check(const MixBatchGeom& G) {
     return "N < 2^31, B < 2^31, Lsrc - L + 1 < 2^32 and Tn - L + 1 < 2^32";
   if ((long long)G.leads * G.L > AUG_MAX_FOOT) return "leads * L <= 16384 (the window's two rows are staged in LDS)";
   return nullptr;
+}
+
+static MixBatchGeom mix_geom(int64_t N, int leads, int64_t Lsrc, int L, int K, int64_t Tn, const uint32_t* cum, double snr_lo,
+                             double snr_hi, uint64_t seed, uint64_t first) {
+  MixBatchGeom G;
+  G.N = (long long)N; G.Lsrc = (long long)Lsrc; G.Tn = (long long)Tn;
+  G.leads = leads; G.L = L; G.K = K;
+  for (int k = 0; k < RAL_MIX_MAX_KINDS; ++k) G.cum[k] = (cum && k < K) ? cum[k] : 0xffffffffu;
+  G.snr_lo = snr_lo; G.snr_hi = snr_hi;
+  G.seed = seed; G.first = first;
+  return G;
+}
+#define MIX_ARGS "(N=%lld leads=%d Lsrc=%lld L=%d K=%d Tn=%lld B=%lld snr_db=[%g, %g])"
+
+extern "C" int ral_mix_batch(const float* bank, const float* noise, const int64_t* rows, int64_t N, int leads, int64_t Lsrc, int L,
+                             int K, int64_t Tn, const uint32_t* cum, double snr_lo, double snr_hi, uint64_t seed, uint64_t first,
+                             int64_t B, float* noisy, float* clean, int32_t* draws, double* snr_db, ral_stream s) {
+  const MixBatchGeom G = mix_geom(N, leads, Lsrc, L, K, Tn, cum, snr_lo, snr_hi, seed, first);
+  const char* why = (!bank || !noise || !cum || !noisy || !clean || !draws || !snr_db) ? "no null pointer (only rows may be null)"
+                                                                                       : mix_batch_check(G);
+  if (!why && B < 1) why = "B >= 1";
+  if (!why && B > 0x7fffffffLL) why = "N < 2^31, B < 2^31, Lsrc - L + 1 < 2^32 and Tn - L + 1 < 2^32";
+  if (why)
+    return ral_fail("mix_batch: need %s " MIX_ARGS, why, (long long)N, leads, (long long)Lsrc, L, K, (long long)Tn, (long long)B,
+                    snr_lo, snr_hi);
+  const size_t lds = AUG_PART * sizeof(double) + 2 * (size_t)G.leads * G.L * sizeof(float);
+  RAL_SET_LDS(k_mix_batch, lds);
+  k_mix_batch<<<(unsigned)B, AUG_THREADS, lds, (hipStream_t)s>>>(bank, noise, reinterpret_cast<const long long*>(rows), G, noisy, clean,
+                                                                 draws, snr_db);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// the draw of ordinal g on the host, by the code the kernel runs
+extern "C" int ral_mix_draw(int64_t N, int64_t Lsrc, int L, int K, int64_t Tn, const uint32_t* cum, double snr_lo, double snr_hi,
+                            uint64_t seed, uint64_t g, int32_t* draw, double* snr_db) {
+  const MixBatchGeom G = mix_geom(N, 1, Lsrc, L, K, Tn, cum, snr_lo, snr_hi, seed, 0);
+  const char* why = (!cum || !draw || !snr_db) ? "no null pointer" : mix_batch_check(G);
+  if (why)
+    return ral_fail("mix_draw: need %s " MIX_ARGS, why, (long long)N, 1, (long long)Lsrc, L, K, (long long)Tn, 1LL, snr_lo, snr_hi);
+  uint32_t d[4];
+  mix_draw(G, g, d, snr_db);
+  for (int i = 0; i < 4; ++i) draw[i] = (int32_t)d[i];
+  return 0;
 }

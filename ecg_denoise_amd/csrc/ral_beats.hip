@@ -19,10 +19,13 @@
 //            [w, w + 2^k) in k steps; a window of 2 Wt + 1 is two overlapping spans of the largest power of two below it),
 //            applies the rules, refines in f, and writes its peaks in order (a scan over the threads' counts) and their number.
 //   gather   one workgroup per row scans the tile counts and copies the tiles' peaks in order; no atomic anywhere.
-#include "ral_kernels.hpp"
+#include "../../include/ralenet.h"
+#include "ral_device.hpp"
+#include "ral_model.hpp"
 #include "ral_slots.hpp"
 #include <math.h>
 #include <stdint.h>
+#include <stdio.h>
 
 namespace {
 
@@ -425,65 +428,97 @@ long long beat_pool_span(const BeatPoolRow* tab, int rows, const BeatGeom& g) {
 
 }  // namespace
 
-long long beat_records_scratch_bytes(long long R, int leads, long long T, const ral_beat_geom* geom, const char** why) {
+// the caller's geometry as the refusals print it
+static void beat_geom_text(const ral_beat_geom* g, char* buf, size_t n) {
+  if (g) snprintf(buf, n, "half=%d Wi=%d Wt=%d Rf=%d Rw=%d alpha=%g floor=%g", g->half, g->wi, g->wt, g->rf, g->rw, g->alpha, g->floor);
+  else snprintf(buf, n, "no geometry");
+}
+
+extern "C" int64_t ral_beat_records_scratch_bytes(int64_t R, int leads, int64_t T, const ral_beat_geom* geom) {
   BeatGeom g;
-  if ((*why = beat_geom(leads, geom, geom ? 2 * geom->half + 1 : 0, g))) return -1;
-  if (R < 1 || R > 65535 || T < 1 || T > 0x7fffffffLL) { *why = "1 <= R <= 65535 and 1 <= T < 2^31"; return -1; }
+  const char* why = beat_geom(leads, geom, geom ? 2 * geom->half + 1 : 0, g);
+  if (!why && (R < 1 || R > 65535 || T < 1 || T > 0x7fffffffLL)) why = "1 <= R <= 65535 and 1 <= T < 2^31";
+  if (why) {
+    char gt[160];
+    beat_geom_text(geom, gt, sizeof(gt));
+    return ral_fail("beat_records_scratch_bytes: need %s (R=%lld leads=%d T=%lld %s)", why, (long long)R, leads, (long long)T, gt);
+  }
   return beat_scratch(R, T, g, nullptr, nullptr);
 }
 
-int launch_beat_records(const float* x, long long R, int leads, long long T, const ral_beat_geom* geom, const float* bank, int ntaps,
-                        void* scratch, long long scratch_bytes, int* peaks, long long cap, int* count, hipStream_t s,
-                        const char** why) {
+extern "C" int ral_beat_records(const float* x, int64_t R, int leads, int64_t T, const ral_beat_geom* geom, const float* bank,
+                                int ntaps, void* scratch, int64_t scratch_bytes, int32_t* peaks, int64_t cap, int32_t* count,
+                                ral_stream s) {
+  if (!x || !geom || !bank || !scratch || !peaks || !count) return ral_fail("beat_records: null pointer");
   BeatGeom g;
-  if ((*why = beat_geom(leads, geom, ntaps, g))) return -1;
-  if (R < 1 || R > 65535 || T < 1 || T > 0x7fffffffLL) { *why = "1 <= R <= 65535 and 1 <= T < 2^31"; return -1; }
-  if (cap < T / (g.rf + 1) + 1) { *why = "cap >= T / (Rf + 1) + 1"; return -1; }
-  if (((uintptr_t)scratch & 7) || scratch_bytes < beat_scratch(R, T, g, nullptr, nullptr)) {
-    *why = "an 8-byte aligned scratch of ral_beat_records_scratch_bytes bytes";
-    return -1;
+  const char* why = beat_geom(leads, geom, ntaps, g);
+  if (!why && (R < 1 || R > 65535 || T < 1 || T > 0x7fffffffLL)) why = "1 <= R <= 65535 and 1 <= T < 2^31";
+  if (!why && cap < T / (g.rf + 1) + 1) why = "cap >= T / (Rf + 1) + 1";
+  if (!why && (((uintptr_t)scratch & 7) || scratch_bytes < beat_scratch(R, T, g, nullptr, nullptr)))
+    why = "an 8-byte aligned scratch of ral_beat_records_scratch_bytes bytes";
+  if (!why && (T + g.tile - 1) / g.tile > 0x7fffffffLL) why = "fewer than 2^31 tiles per record";
+  if (why) {
+    char gt[160];
+    beat_geom_text(geom, gt, sizeof(gt));
+    return ral_fail("beat_records: need %s (R=%lld leads=%d T=%lld ntaps=%d cap=%lld scratch_bytes=%lld %s)", why, (long long)R, leads,
+                (long long)T, ntaps, (long long)cap, (long long)scratch_bytes, gt);
   }
+  hipStream_t st = (hipStream_t)s;
   BeatScratch sc;
   beat_scratch(R, T, g, scratch, &sc);
   const long long ft = (T + g.tile - 1) / g.tile;
-  if (ft > 0x7fffffffLL) { *why = "fewer than 2^31 tiles per record"; return -1; }
-  k_beat_feature_records<<<dim3((unsigned)ft, (unsigned)R), BEAT_THREADS, beat_feature_lds_bytes(g), s>>>(x, T, g, bank, sc);
-  k_beat_pick_records<<<dim3((unsigned)sc.NT, (unsigned)R), BEAT_THREADS, beat_pick_lds_bytes(g), s>>>(x, T, g, sc);
-  k_beat_gather_records<<<dim3((unsigned)R), BEAT_THREADS, 0, s>>>(T, g, sc, peaks, cap, count);
+  k_beat_feature_records<<<dim3((unsigned)ft, (unsigned)R), BEAT_THREADS, beat_feature_lds_bytes(g), st>>>(x, T, g, bank, sc);
+  k_beat_pick_records<<<dim3((unsigned)sc.NT, (unsigned)R), BEAT_THREADS, beat_pick_lds_bytes(g), st>>>(x, T, g, sc);
+  k_beat_gather_records<<<dim3((unsigned)R), BEAT_THREADS, 0, st>>>(T, g, sc, peaks, cap, count);
+  HIP_OK(hipGetLastError());
   return 0;
 }
 
-int launch_beat_pool(float* hist, const float* x, long long x_total, const ral_beat_row* tab, int rows, ral_beat_row* tab_dev,
-                     int upload, long long cap, int leads, const ral_beat_geom* geom, const float* bank, int ntaps, int hist_len,
-                     void* scratch, long long scratch_bytes, long long* peaks, long long peaks_total, int* count, hipStream_t s,
-                     const char** why, int* bad) {
+extern "C" int ral_beat_pool(float* hist, const float* x, int64_t x_total, const ral_beat_row* table, int rows,
+                             ral_beat_row* table_dev, int upload, int64_t capacity, int leads, const ral_beat_geom* geom,
+                             const float* bank, int ntaps, int hist_len, void* scratch, int64_t scratch_bytes, int64_t* peaks,
+                             int64_t peaks_total, int32_t* count, ral_stream s) {
+  if (!hist || !x || !table || !table_dev || !geom || !bank || !scratch || !peaks || !count) return ral_fail("beat_pool: null pointer");
+  hipStream_t st = (hipStream_t)s;
   BeatGeom g;
-  *bad = -1;
-  if ((*why = beat_geom(leads, geom, ntaps, g))) return -1;
-  if ((*why = beat_pool_fault(tab, rows, cap, g, hist_len, x_total, peaks_total, upload != 0, bad))) return -1;
-  const long long S = beat_pool_span(tab, rows, g);
-  if (((uintptr_t)scratch & 7) || scratch_bytes < beat_scratch(rows, S, g, nullptr, nullptr)) {
-    *why = "an 8-byte aligned scratch of ral_beat_records_scratch_bytes(rows, leads, the longest span of f, ...) bytes";
-    return -1;
+  int bad = -1;
+  long long S = 1;
+  const char* why = beat_geom(leads, geom, ntaps, g);
+  if (!why) why = beat_pool_fault(table, rows, capacity, g, hist_len, x_total, peaks_total, upload != 0, &bad);
+  if (!why) {
+    S = beat_pool_span(table, rows, g);
+    if (((uintptr_t)scratch & 7) || scratch_bytes < beat_scratch(rows, S, g, nullptr, nullptr))
+      why = "an 8-byte aligned scratch of ral_beat_records_scratch_bytes(rows, leads, the longest span of f, ...) bytes";
   }
-  BeatScratch sc;
-  beat_scratch(rows, S, g, scratch, &sc);
-  long long d_max = 0;
-  for (int r = 0; r < rows; ++r) d_max = tab[r].d > d_max ? tab[r].d : d_max;
-  const long long ft = (S + g.tile - 1) / g.tile, pt = (d_max + BEAT_PICK - 1) / BEAT_PICK;
-  if (upload && slots_upload(tab, rows, tab_dev, s)) return -2;
-  k_beat_feature_pool<<<dim3((unsigned)ft + 1, (unsigned)rows), BEAT_THREADS, beat_feature_lds_bytes(g), s>>>(hist, x, tab_dev, cap,
-                                                                                                            hist_len, g, bank, sc);
-  if (pt > 0)
-    k_beat_pick_pool<<<dim3((unsigned)pt, (unsigned)rows), BEAT_THREADS, beat_pick_lds_bytes(g), s>>>(hist, x, tab_dev, cap, hist_len, g,
-                                                                                                    sc);
-  k_beat_gather_pool<<<dim3((unsigned)rows), BEAT_THREADS, 0, s>>>(tab_dev, g, sc, peaks, count);
-  return 0;
+  const int rc = why ? -1 : upload ? slots_upload(table, rows, table_dev, st) : 0;
+  if (!rc) {
+    BeatScratch sc;
+    beat_scratch(rows, S, g, scratch, &sc);
+    long long d_max = 0;
+    for (int r = 0; r < rows; ++r) d_max = table[r].d > d_max ? table[r].d : d_max;
+    const long long ft = (S + g.tile - 1) / g.tile, pt = (d_max + BEAT_PICK - 1) / BEAT_PICK;
+    k_beat_feature_pool<<<dim3((unsigned)ft + 1, (unsigned)rows), BEAT_THREADS, beat_feature_lds_bytes(g), st>>>(
+        hist, x, table_dev, capacity, hist_len, g, bank, sc);
+    if (pt > 0)
+      k_beat_pick_pool<<<dim3((unsigned)pt, (unsigned)rows), BEAT_THREADS, beat_pick_lds_bytes(g), st>>>(hist, x, table_dev, capacity,
+                                                                                                       hist_len, g, sc);
+    k_beat_gather_pool<<<dim3((unsigned)rows), BEAT_THREADS, 0, st>>>(table_dev, g, sc, (long long*)peaks, count);
+  }
+  char gt[160] = "";
+  if (rc) beat_geom_text(geom, gt, sizeof(gt));
+  return table_done("beat_pool", rc, why, bad, "rows=%d capacity=%lld leads=%d ntaps=%d hist_len=%d x_total=%lld "
+                    "peaks_total=%lld scratch_bytes=%lld %s", rows, (long long)capacity, leads, ntaps, hist_len, (long long)x_total,
+                    (long long)peaks_total, (long long)scratch_bytes, gt);
 }
 
-int launch_beat_match(const int* ref, const int* nref, long long ref_cap, const int* det, const int* ndet, long long det_cap,
-                      long long R, long long tol, long long* out, hipStream_t s, const char** why) {
-  if (R < 1 || R > (1LL << 30) || ref_cap < 1 || det_cap < 1 || tol < 0) { *why = "1 <= R <= 2^30, ref_cap, det_cap >= 1 and tol >= 0"; return -1; }
-  k_beat_match<<<dim3((unsigned)((R + 63) / 64)), 64, 0, s>>>(ref, nref, ref_cap, det, ndet, det_cap, R, tol, out);
+extern "C" int ral_beat_match(const int32_t* ref, const int32_t* ref_count, int64_t ref_cap, const int32_t* det,
+                              const int32_t* det_count, int64_t det_cap, int64_t R, int64_t tol, int64_t* out, ral_stream s) {
+  if (!ref || !ref_count || !det || !det_count || !out) return ral_fail("beat_match: null pointer");
+  if (R < 1 || R > (1LL << 30) || ref_cap < 1 || det_cap < 1 || tol < 0)
+    return ral_fail("beat_match: need 1 <= R <= 2^30, ref_cap, det_cap >= 1 and tol >= 0 (R=%lld ref_cap=%lld det_cap=%lld tol=%lld)",
+                (long long)R, (long long)ref_cap, (long long)det_cap, (long long)tol);
+  k_beat_match<<<dim3((unsigned)((R + 63) / 64)), 64, 0, (hipStream_t)s>>>(ref, ref_count, ref_cap, det, det_count, det_cap, R, tol,
+                                                                         (long long*)out);
+  HIP_OK(hipGetLastError());
   return 0;
 }

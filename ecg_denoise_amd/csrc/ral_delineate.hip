@@ -13,7 +13,9 @@
 // run is a per-lane flag, followed by a butterfly over the indices that passed.
 //
 // Launch: one, grid (cap, R), a wave per beat (a beat at or beyond count writes the padding).
-#include "ral_kernels.hpp"
+#include "../../include/ralenet.h"
+#include "ral_device.hpp"
+#include "ral_model.hpp"
 #include "ral_wave_pick.hpp"
 #include <math.h>
 #include <stdint.h>
@@ -144,14 +146,20 @@ const char* delin_geom(int leads, const ral_delin_geom* p, DelinGeom& g) {
 
 }  // namespace
 
-int launch_delineate_records(const float* x, long long R, int leads, long long T, const ral_delin_geom* geom, const int* peaks,
-                             const int* count, long long cap, int* on, int* off, int* tpeak, int* tend, hipStream_t s,
-                             const char** why) {
+extern "C" int ral_delineate_records(const float* x, int64_t R, int leads, int64_t T, const ral_delin_geom* geom, const int32_t* peaks,
+                                     const int32_t* count, int64_t cap, int32_t* on, int32_t* off, int32_t* tpeak, int32_t* tend,
+                                     ral_stream s) {
+  if (!x || !geom || !peaks || !count || !on || !off || !tpeak || !tend) return ral_fail("delineate_records: null pointer");
   DelinGeom g;
-  if ((*why = delin_geom(leads, geom, g))) return -1;
-  if (R < 1 || R > 65535 || T < 1 || T > 0x7fffffffLL) { *why = "1 <= R <= 65535 and 1 <= T < 2^31"; return -1; }
-  if (cap < 1 || cap > 0x7fffffffLL) { *why = "1 <= cap < 2^31"; return -1; }
-  k_delineate_records<<<dim3((unsigned)cap, (unsigned)R), DL_WAVE, delin_lds_bytes(g), s>>>(x, T, g, peaks, count, cap, on, off,
-                                                                                          tpeak, tend);
+  const char* why = delin_geom(leads, geom, g);
+  if (!why && (R < 1 || R > 65535 || T < 1 || T > 0x7fffffffLL)) why = "1 <= R <= 65535 and 1 <= T < 2^31";
+  if (!why && (cap < 1 || cap > 0x7fffffffLL)) why = "1 <= cap < 2^31";
+  if (why)
+    return ral_fail("delineate_records: need %s (R=%lld leads=%d T=%lld cap=%lld h=%d m=%d Wq=%d g=%d m2=%d gt=%d Wt=%d q0=%g)", why,
+                    (long long)R, leads, (long long)T, (long long)cap, geom->h, geom->m, geom->wq, geom->g, geom->m2, geom->gt,
+                    geom->wt, geom->q0);
+  k_delineate_records<<<dim3((unsigned)cap, (unsigned)R), DL_WAVE, delin_lds_bytes(g), (hipStream_t)s>>>(x, T, g, peaks, count, cap, on,
+                                                                                                       off, tpeak, tend);
+  HIP_OK(hipGetLastError());
   return 0;
 }

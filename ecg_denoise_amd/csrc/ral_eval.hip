@@ -12,8 +12,11 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <stdio.h>
 
-#include "ral_kernels.hpp"
+#include "../../include/ralenet.h"
+#include "ral_device.hpp"
+#include "ral_model.hpp"
 
 #define EVAL_MAXL 16          // leads per record, as RAL_PREP_MAXL
 #define EVAL_THREADS 256
@@ -101,35 +104,51 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_mix_apply(const float* __restr
   }
 }
 
-long long mix_records_scratch_bytes(long long R, int leads, long long T) {
-  if (R < 1 || leads < 1 || leads > EVAL_MAXL || T < 1) return -1;
+extern "C" int64_t ral_mix_records_scratch_bytes(int64_t R, int leads, int64_t T) {
+  if (R < 1 || leads < 1 || leads > EVAL_MAXL || T < 1)
+    return ral_fail("mix_records_scratch_bytes: need R >= 1, 1 <= leads <= 16, T >= 1 (R=%lld leads=%d T=%lld)", (long long)R, leads, (long long)T);
   return 8 * (2 * R + 3 * R * leads * mix_tiles(T));
 }
 
-int launch_mix_records(const float* rec, const float* noise, long long R, int leads, long long T, long long Tn,
-                       const int64_t* offsets, const double* snr_db, void* scratch, float* noisy, float* clean, hipStream_t s,
-                       const char** why, long long* bad) {
+// the rule a mix call breaks (*bad: the record that breaks it, or -1), or null
+static const char* mix_records_fault(long long R, int leads, long long T, long long Tn, const int64_t* offsets, const double* snr_db,
+                                     long long* bad) {
   *bad = -1;
-  if (R < 1) return *why = "R >= 1", -1;
-  if (leads < 1 || leads > EVAL_MAXL) return *why = "1 <= leads <= 16", -1;
-  if (T < 1) return *why = "T >= 1", -1;
-  if (Tn < T) return *why = "Tn >= T", -1;
-  const long long ntile = mix_tiles(T);
-  if (R > 0x7fffffffLL / (leads * ntile)) return *why = "at most 2^31 - 1 workgroups", -1;
+  if (R < 1) return "R >= 1";
+  if (leads < 1 || leads > EVAL_MAXL) return "1 <= leads <= 16";
+  if (T < 1) return "T >= 1";
+  if (Tn < T) return "Tn >= T";
+  if (R > 0x7fffffffLL / (leads * mix_tiles(T))) return "at most 2^31 - 1 workgroups";
   for (long long r = 0; r < R; ++r) {
     *bad = r;
-    if (offsets[r] < 0 || offsets[r] > Tn - T) return *why = "0 <= offset <= Tn - T", -1;
-    if (!isfinite(snr_db[r])) return *why = "a finite snr_db", -1;
+    if (offsets[r] < 0 || offsets[r] > Tn - T) return "0 <= offset <= Tn - T";
+    if (!isfinite(snr_db[r])) return "a finite snr_db";
   }
   *bad = -1;
+  return nullptr;
+}
+
+extern "C" int ral_mix_records(const float* rec, const float* noise, int64_t R, int leads, int64_t T, int64_t Tn,
+                               const int64_t* offsets, const double* snr_db, void* scratch, float* noisy, float* clean, ral_stream s) {
+  if (!rec || !noise || !offsets || !snr_db || !scratch || !noisy || !clean) return ral_fail("mix_records: need no null pointer");
+  long long bad = -1;
+  if (const char* why = mix_records_fault(R, leads, T, Tn, offsets, snr_db, &bad)) {
+    char at[96] = "";
+    if (bad >= 0) snprintf(at, sizeof(at), " in record %lld (offset=%lld snr_db=%g)", bad, (long long)offsets[bad], snr_db[bad]);
+    return ral_fail("mix_records: need %s%s (R=%lld leads=%d T=%lld Tn=%lld)", why, at, (long long)R, leads, (long long)T, (long long)Tn);
+  }
+  hipStream_t st = (hipStream_t)s;
+  const long long ntile = mix_tiles(T);
   long long* offs = reinterpret_cast<long long*>(scratch);
   double* snr = reinterpret_cast<double*>(scratch) + R;
   double* part = snr + R;
-  if (hipMemcpyAsync(offs, offsets, (size_t)R * 8, hipMemcpyHostToDevice, s) != hipSuccess) return -2;
-  if (hipMemcpyAsync(snr, snr_db, (size_t)R * 8, hipMemcpyHostToDevice, s) != hipSuccess) return -2;
+  if (hipMemcpyAsync(offs, offsets, (size_t)R * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(snr, snr_db, (size_t)R * 8, hipMemcpyHostToDevice, st) != hipSuccess)
+    return ral_fail("mix_records: copying offsets / snr_db to the device failed");
   const long long plane = R * leads * ntile;
-  k_mix_stats<<<(int)plane, EVAL_THREADS, 0, s>>>(rec, noise, T, Tn, leads, ntile, offs, part, plane);
-  k_mix_apply<<<(int)plane, EVAL_THREADS, 0, s>>>(rec, noise, T, Tn, leads, ntile, offs, snr, part, plane, noisy, clean);
+  k_mix_stats<<<(int)plane, EVAL_THREADS, 0, st>>>(rec, noise, T, Tn, leads, ntile, offs, part, plane);
+  k_mix_apply<<<(int)plane, EVAL_THREADS, 0, st>>>(rec, noise, T, Tn, leads, ntile, offs, snr, part, plane, noisy, clean);
+  HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -303,27 +322,40 @@ __global__ void k_score_total(long long R, long long nwin, const double* __restr
   window_mean[R * 4 + k] = v / ((double)R * (double)nwin);
 }
 
-long long score_records_scratch_bytes(long long R, int leads, long long T, long long W) {
-  if (R < 1 || leads < 1 || leads > EVAL_MAXL || T < 1 || W < 1 || W > T) return -1;
+extern "C" int64_t ral_score_records_scratch_bytes(int64_t R, int leads, int64_t T, int64_t W) {
+  if (R < 1 || leads < 1 || leads > EVAL_MAXL || T < 1 || W < 1 || W > T)
+    return ral_fail("score_records_scratch_bytes: need R >= 1, 1 <= leads <= 16, T >= 1, 1 <= W <= T (R=%lld leads=%d T=%lld W=%lld)",
+                (long long)R, leads, (long long)T, (long long)W);
   return 8 * (3 * R * leads * score_geom(T, W).nchunk + 4 * R);
 }
 
-int launch_score_records(const float* clean, const float* out, const float* noisy, long long R, int leads, long long T, long long W,
-                         void* scratch, double* per_lead, double* per_record, double* per_window, double* window_mean,
-                         hipStream_t s, const char** why) {
-  if (R < 1) return *why = "R >= 1", -1;
-  if (leads < 1 || leads > EVAL_MAXL) return *why = "1 <= leads <= 16", -1;
-  if (T < 1) return *why = "T >= 1", -1;
-  if (W < 1 || W > T) return *why = "1 <= W <= T", -1;
+// the rule a score call breaks, or null (bpr: workgroups per record)
+static const char* score_records_fault(long long R, int leads, long long T, long long W, long long* bpr) {
+  if (R < 1) return "R >= 1";
+  if (leads < 1 || leads > EVAL_MAXL) return "1 <= leads <= 16";
+  if (T < 1) return "T >= 1";
+  if (W < 1 || W > T) return "1 <= W <= T";
+  *bpr = (score_geom(T, W).nchunk + EVAL_WAVES - 1) / EVAL_WAVES;
+  return R > 0x7fffffffLL / *bpr ? "at most 2^31 - 1 workgroups" : nullptr;
+}
+
+extern "C" int ral_score_records(const float* clean, const float* out, const float* noisy, int64_t R, int leads, int64_t T, int64_t W,
+                                 void* scratch, double* per_lead, double* per_record, double* per_window, double* window_mean,
+                                 ral_stream s) {
+  if (!clean || !out || !scratch || !per_lead || !per_record || !per_window || !window_mean)
+    return ral_fail("score_records: need no null pointer (only noisy may be null)");
+  long long bpr = 0;
+  if (const char* why = score_records_fault(R, leads, T, W, &bpr))
+    return ral_fail("score_records: need %s (R=%lld leads=%d T=%lld W=%lld)", why, (long long)R, leads, (long long)T, (long long)W);
+  hipStream_t st = (hipStream_t)s;
   const ScoreGeom g = score_geom(T, W);
-  const long long bpr = (g.nchunk + EVAL_WAVES - 1) / EVAL_WAVES;
-  if (R > 0x7fffffffLL / bpr) return *why = "at most 2^31 - 1 workgroups", -1;
   double* part = reinterpret_cast<double*>(scratch);
   double* rsum = part + 3 * R * leads * g.nchunk;
-  if (noisy) k_score_chunks<true><<<(int)(R * bpr), EVAL_THREADS, 0, s>>>(clean, out, noisy, T, leads, W, bpr, part, per_window);
-  else k_score_chunks<false><<<(int)(R * bpr), EVAL_THREADS, 0, s>>>(clean, out, noisy, T, leads, W, bpr, part, per_window);
-  k_score_finish<<<(int)R, EVAL_THREADS, 0, s>>>(T, leads, W, noisy != nullptr, part, rsum, per_lead, per_record, per_window,
-                                                 window_mean);
-  k_score_total<<<1, 64, 0, s>>>(R, g.nwin, rsum, window_mean);
+  if (noisy) k_score_chunks<true><<<(int)(R * bpr), EVAL_THREADS, 0, st>>>(clean, out, noisy, T, leads, W, bpr, part, per_window);
+  else k_score_chunks<false><<<(int)(R * bpr), EVAL_THREADS, 0, st>>>(clean, out, noisy, T, leads, W, bpr, part, per_window);
+  k_score_finish<<<(int)R, EVAL_THREADS, 0, st>>>(T, leads, W, noisy != nullptr, part, rsum, per_lead, per_record, per_window,
+                                                  window_mean);
+  k_score_total<<<1, 64, 0, st>>>(R, g.nwin, rsum, window_mean);
+  HIP_OK(hipGetLastError());
   return 0;
 }

@@ -33,7 +33,9 @@
 //   (recomputing the transform is cheaper than a round trip of the spectrum through HBM; the same code on the same input gives
 //   the same bits).  The kept count of a group is summed with an integer atomicAdd there; there is no floating-point atomic.
 // x == y is allowed: a workgroup has read every row it owns before it writes the first.
-#include "ral_kernels.hpp"
+#include "../../include/ralenet.h"
+#include "ral_device.hpp"
+#include "ral_model.hpp"
 #include <stdint.h>
 
 #pragma clang fp contract(off)
@@ -387,13 +389,8 @@ long long fft_lds_bytes(int L, int cls, long long rows) {
 
 }  // namespace
 
-const char* fft_denoise_rule() {
-  return "an even record length with no prime factor above 5 in [16, 8192] (the FFT path), or any other length in [2, 1024] "
-         "(the direct path)";
-}
-
 // bytes of scratch ral_fft_denoise needs (0: one launch, the group is resident), -1: a length or a count that is refused
-long long fft_denoise_scratch_bytes(long long groups, int rows_per_group, int L) {
+static long long fft_denoise_scratch_bytes(long long groups, int rows_per_group, int L) {
   const int cls = fft_classify(L);
   if (cls == FFT_REFUSED || groups < 0 || rows_per_group < 1) return -1;
   if (groups > 0x7fffffffLL / rows_per_group) return -1;
@@ -401,31 +398,60 @@ long long fft_denoise_scratch_bytes(long long groups, int rows_per_group, int L)
   return groups * rows_per_group * (long long)sizeof(float);
 }
 
-// (the C entry point, ral_fft_denoise, is in ral_api.hip with the other argument checks)  -1: refused arguments, -2: a HIP error
-int launch_fft_denoise(const float* x, float* y, int32_t* kept, long long groups, int rows_per_group, int L, float threshold,
-                       void* scratch, hipStream_t stream) {
-  const long long sb = fft_denoise_scratch_bytes(groups, rows_per_group, L);
-  if (sb < 0 || (sb > 0 && !scratch)) return -1;
-  if (groups == 0) return 0;
+// the counts and the length both entry points refuse, in the words of `who`
+static int fft_denoise_counts(const char* who, int64_t groups, int rows_per_group, int L) {
+  if (groups < 0 || rows_per_group < 1)
+    return ral_fail("%s: need groups >= 0 and rows_per_group >= 1 (groups=%lld rows_per_group=%d)", who, (long long)groups, rows_per_group);
+  if (groups > 0x7fffffffLL / rows_per_group)
+    return ral_fail("%s: need groups * rows_per_group < 2^31 (groups=%lld rows_per_group=%d)", who, (long long)groups, rows_per_group);
+  if (fft_denoise_scratch_bytes(0, 1, L) < 0)
+    return ral_fail("%s: L=%d is not supported: need an even record length with no prime factor above 5 in [16, 8192] (the FFT path), "
+                    "or any other length in [2, 1024] (the direct path)", who, L);
+  return 0;
+}
+
+extern "C" int64_t ral_fft_denoise_scratch_bytes(int64_t groups, int rows_per_group, int L) {
+  if (fft_denoise_counts("fft_denoise_scratch_bytes", groups, rows_per_group, L)) return -1;
+  return (int64_t)fft_denoise_scratch_bytes((long long)groups, rows_per_group, L);
+}
+
+extern "C" int ral_fft_denoise(const float* x, float* y, int32_t* kept, int64_t groups, int rows_per_group, int L, float threshold,
+                               void* scratch, ral_stream s) {
+  if (!x || !y) return ral_fail("fft_denoise: null pointer (x=%p y=%p)", (const void*)x, (void*)y);
+  if (fft_denoise_counts("fft_denoise", groups, rows_per_group, L)) return -1;
+  if (!(threshold >= 0.f)) return ral_fail("fft_denoise: the threshold factor must be non-negative (got %g)", (double)threshold);
+  const long long sb = fft_denoise_scratch_bytes((long long)groups, rows_per_group, L);
+  if (sb > 0 && !scratch)
+    return ral_fail("fft_denoise: null scratch, %lld bytes are needed (groups=%lld rows_per_group=%d L=%d)", sb, (long long)groups,
+                rows_per_group, L);
+  if (groups == 0) {
+    HIP_OK(hipGetLastError());
+    return 0;
+  }
+  hipStream_t stream = (hipStream_t)s;
   const int cls = fft_classify(L);
   FftArgs a;
-  if (!fft_plan(L, cls, a.plan)) return -1;
+  if (!fft_plan(L, cls, a.plan))
+    return ral_fail("fft_denoise: refused (groups=%lld rows_per_group=%d L=%d)", (long long)groups, rows_per_group, L);
   a.x = x, a.y = y, a.kept = kept, a.rowmax = static_cast<float*>(scratch), a.rpg = rows_per_group, a.thr = threshold;
   const bool resident = sb == 0;
   const size_t lds = (size_t)fft_lds_bytes(L, cls, resident ? rows_per_group : 1);
   const void* fn = cls == FFT_FAST ? reinterpret_cast<const void*>(k_fft_denoise) : reinterpret_cast<const void*>(k_dft_denoise);
-  if (lds > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -2;
   auto run = [&](int mode, unsigned grid) {
     a.mode = mode;
     if (cls == FFT_FAST) k_fft_denoise<<<grid, FFT_THREADS, lds, stream>>>(a);
     else k_dft_denoise<<<grid, FFT_THREADS, lds, stream>>>(a);
   };
-  if (resident) {
-    run(0, (unsigned)groups);
-    return 0;
+  // (a failed HIP call of the set-up is reported in HIP's words)
+  if (lds > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return ral_fail("fft_denoise: %s", hipGetErrorString(hipGetLastError()));
+  if (resident) run(0, (unsigned)groups);
+  else {
+    if (kept && hipMemsetAsync(kept, 0, (size_t)groups * sizeof(int32_t), stream) != hipSuccess)
+      return ral_fail("fft_denoise: %s", hipGetErrorString(hipGetLastError()));
+    run(1, (unsigned)(groups * rows_per_group));
+    run(2, (unsigned)(groups * rows_per_group));
   }
-  if (kept && hipMemsetAsync(kept, 0, (size_t)groups * sizeof(int32_t), stream) != hipSuccess) return -2;
-  run(1, (unsigned)(groups * rows_per_group));
-  run(2, (unsigned)(groups * rows_per_group));
+  HIP_OK(hipGetLastError());
   return 0;
 }

@@ -16,7 +16,9 @@
 //              multiply with one correction step); psd_k goes to LDS, over d, which is no longer needed
 //   bands      lanes 0 .. 3 of wave 0 add the bins of VLF, LF, HF and of all bands, each sequentially in ascending k
 // No floating-point atomics, no scratch memory: the order of every floating-point sum depends on the geometry and on m alone.
-#include "ral_kernels.hpp"
+#include "../../include/ralenet.h"
+#include "ral_device.hpp"
+#include "ral_model.hpp"
 #include "ral_slots.hpp"
 #include <math.h>
 #include <stdint.h>
@@ -225,26 +227,38 @@ const char* hrv_geom(const ral_hrv_geom* p, HrvGeom& g) {
 
 }  // namespace
 
-int launch_hrv_windows(const int* pos, const int* label, const int* count, long long R, long long cap, const ral_hrv_row* tab,
-                       long long rows, ral_hrv_row* tab_dev, int upload, const ral_hrv_geom* geom, const int* band, int* counts,
-                       float* stats, float* psd, hipStream_t s, const char** why, long long* bad) {
-  HrvGeom g;
+// the rule a call breaks (*bad: the table row that breaks it, or -1), or null; the table is read only when it is uploaded
+static const char* hrv_fault(long long R, long long cap, const ral_hrv_row* tab, long long rows, int upload, const ral_hrv_geom* geom,
+                             HrvGeom& g, long long* bad) {
   *bad = -1;
-  if ((*why = hrv_geom(geom, g))) return -1;
-  if (R < 1 || R > 0x7fffffffLL || cap < 1 || cap > 0x7fffffffLL) { *why = "1 <= R < 2^31 and 1 <= cap < 2^31"; return -1; }
-  if (rows < 0 || rows > 0x7fffffffLL) { *why = "0 <= rows < 2^31"; return -1; }
-  if (rows == 0) return 0;
-  if (upload) {
-    for (long long r = 0; r < rows; ++r) {
-      const ral_hrv_row& t = tab[r];
-      *bad = r;
-      if (t.rec < 0 || t.rec >= R) { *why = "0 <= rec < R"; return -1; }
-      if (t.w0 < 0 || t.w1 <= t.w0 || t.w1 > t.w0 + g.W) { *why = "0 <= w0 < w1 <= w0 + W"; return -1; }
-    }
-    *bad = -1;
-    if (slots_upload(tab, rows, tab_dev, s)) return -2;
+  if (const char* why = hrv_geom(geom, g)) return why;
+  if (R < 1 || R > 0x7fffffffLL || cap < 1 || cap > 0x7fffffffLL) return "1 <= R < 2^31 and 1 <= cap < 2^31";
+  if (rows < 0 || rows > 0x7fffffffLL) return "0 <= rows < 2^31";
+  for (long long r = 0; upload && r < rows; ++r) {
+    const ral_hrv_row& t = tab[r];
+    *bad = r;
+    if (t.rec < 0 || t.rec >= R) return "0 <= rec < R";
+    if (t.w0 < 0 || t.w1 <= t.w0 || t.w1 > t.w0 + g.W) return "0 <= w0 < w1 <= w0 + W";
   }
-  const size_t lds = ((size_t)2 * g.max_m + g.nd) * 4;
-  k_hrv_windows<<<dim3((unsigned)rows), HV_THREADS, lds, s>>>(pos, label, count, cap, tab_dev, g, band, counts, stats, psd);
-  return 0;
+  *bad = -1;
+  return nullptr;
+}
+
+extern "C" int ral_hrv_windows(const int32_t* pos, const int32_t* label_or_null, const int32_t* count, int64_t R, int64_t cap,
+                               const ral_hrv_row* table, int64_t rows, ral_hrv_row* table_dev, int upload, const ral_hrv_geom* geom,
+                               const int32_t* band, int32_t* counts, float* stats, float* psd_or_null, ral_stream s) {
+  if (!pos || !count || !table_dev || (upload && !table) || !geom || !band || !counts || !stats)
+    return ral_fail("hrv_windows: null pointer");
+  HrvGeom g;
+  long long bad = -1;
+  const char* why = hrv_fault(R, cap, table, rows, upload, geom, g, &bad);
+  const int rc = why ? -1 : (upload && rows > 0) ? slots_upload(table, rows, table_dev, (hipStream_t)s) : 0;
+  if (!rc && rows > 0) {
+    const size_t lds = ((size_t)2 * g.max_m + g.nd) * 4;
+    k_hrv_windows<<<dim3((unsigned)rows), HV_THREADS, lds, (hipStream_t)s>>>(pos, label_or_null, count, cap, table_dev, g, band, counts,
+                                                                           stats, psd_or_null);
+  }
+  return table_done("hrv_windows", rc, why, bad, "R=%lld cap=%lld rows=%lld W=%d lo_n=%d hi_n=%d t50=%d F=%d min_nn=%d fs=%g",
+                    (long long)R, (long long)cap, (long long)rows, geom->W, geom->lo_n, geom->hi_n, geom->t50, geom->F,
+                    geom->min_nn, geom->fs);
 }

@@ -1,11 +1,12 @@
-// Host-side launch interface of the RA-LENet / U-Net kernels (internal to libralenet).
+// Host-side launch interface of the model kernels (internal to libralenet): the launchers that another translation unit
+// calls - the networks' passes and the handle entry points of ral_api.hip.  A stateless entry point of the C ABI has no
+// launcher here: it is defined in the file that holds its kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include "ral_device.hpp"
 #include "ral_attn_plan.hpp"
 #include "ral_block_plan.hpp"
-#include "../../include/ralenet.h"   // ral_pool_row
 
 // ---- forward (ral_fwd.hip)
 // ---- the Linear layers of a transformer block: ral_block_plan.hpp chooses the kernel, the launchers execute the plan entry they
@@ -53,128 +54,6 @@ void launch_loss(const float* pred, const float* target, float* dy, float* snr, 
 void launch_zero_bwd(float* grads, size_t nfloat, double* sums, int nsums, unsigned* gmax, int ngmax, hipStream_t s);
 void launch_adam(float* p, const float* g, float* m, float* v, size_t n, double lr, double b1, double b2, double eps,
                  int step, float gscale, hipStream_t s, double* zero64 = nullptr /* optional: 64 doubles cleared by the same launch */);
-
-int launch_prep_windows(const float* sig, const float* noise, long long T, int leads, int L, double snr_db, double* sums,
-                        float* noisy, float* clean, hipStream_t s);
-int launch_stream_windows(const float* rec, long long R, long long T, int leads, int L, int hop, long long w0, int nw,
-                          float* win, float* stats, hipStream_t s);
-int launch_stream_stitch(const float* y, const float* stats, long long R, long long T, int leads, int L, int hop, float* out,
-                         hipStream_t s);
-// live streams (ral_live_windows / ral_live_emit); -1: bad arguments
-int launch_live_windows(const float* hist, const float* x, float* hist_out, long long S, int leads, int L, int hop, int C,
-                        long long base, long long k0, int nw, long long T, long long w0, int nb, float* win, float* stats,
-                        hipStream_t s);
-int launch_live_emit(const float* y, const float* stats, long long S, int leads, int L, int hop, long long k0, int nw, long long T,
-                     long long w0, int nb, long long lo, int m, float* out, float* last_y, float* last_stats, hipStream_t s);
-// the 12-lead adapter around the inner model of a streamed record group (ral_newrale_stream_front / _back); -1: bad arguments
-int launch_newrale_front(const float* rec, long long R, long long T, int L, int hop, long long w0, int nw, const float* prm,
-                         float* inner, float* stats, hipStream_t s);
-int launch_newrale_back(const float* iy, const float* stats, const float* prm, long long R, long long T, int L, int hop,
-                        long long w0, int nw, float* out, hipStream_t s);
-// the same kernels on live 12-lead streams (ral_newrale_live_front / _back; the geometry of launch_live_*); -1: bad arguments
-int launch_newrale_live_front(const float* hist, const float* x, float* hist_out, long long S, int L, int hop, int C,
-                              long long base, long long k0, int nw, long long T, long long w0, int nb, const float* prm,
-                              float* inner, float* stats, hipStream_t s);
-int launch_newrale_live_back(const float* iy, const float* stats, const float* prm, long long S, int L, int hop, long long k0,
-                             int nw, long long T, long long w0, int nb, long long lo, int m, float* out, float* last_y,
-                             float* last_stats, hipStream_t s);
-// the stream pool (ral_pool_windows / ral_pool_emit, ral_newrale_pool_front / _back): the host table is checked, then copied to
-// tab_dev on s (upload != 0), then the kernel is launched; -1: bad arguments (*why: the rule that is broken, *bad: the row that breaks it or -1), -2: the copy failed
-int launch_pool_windows(float* hist, const float* x, long long x_total, const ral_pool_row* tab, int rows, ral_pool_row* tab_dev,
-                        int upload, long long cap, int leads, int L, int hop, int write_hist, long long w0, int nb, float* win,
-                        float* stats, hipStream_t s, const char** why, int* bad);
-int launch_pool_emit(const float* y, const float* stats, const ral_pool_row* tab, int rows, ral_pool_row* tab_dev, int upload,
-                     long long cap, int leads, int L, int hop, long long w0, int nb, int from_last, float* out,
-                     long long out_total, float* last_y, float* last_stats, hipStream_t s, const char** why, int* bad);
-int launch_newrale_pool_front(float* hist, const float* x, long long x_total, const ral_pool_row* tab, int rows,
-                              ral_pool_row* tab_dev, int upload, long long cap, int L, int hop, int write_hist, long long w0,
-                              int nb, const float* prm, float* inner, float* stats, hipStream_t s, const char** why, int* bad);
-int launch_newrale_pool_back(const float* iy, const float* stats, const float* prm, const ral_pool_row* tab, int rows,
-                             ral_pool_row* tab_dev, int upload, long long cap, int L, int hop, long long w0, int nb, int from_last,
-                             float* out, long long out_total, float* last_y, float* last_stats, hipStream_t s, const char** why,
-                             int* bad);
-// noise-stress evaluation of record groups (ral_eval.hip; ral_mix_records / ral_score_records): the arguments are checked, then
-// (mix) the host arrays copied into the scratch on s, then the kernels launched; -1: bad arguments (*why: the rule that is
-// broken, *bad: the record that breaks it or -1), -2: the copy failed.  *_scratch_bytes: -1 for a shape the call would refuse
-long long mix_records_scratch_bytes(long long R, int leads, long long T);
-int launch_mix_records(const float* rec, const float* noise, long long R, int leads, long long T, long long Tn,
-                       const int64_t* offsets, const double* snr_db, void* scratch, float* noisy, float* clean, hipStream_t s,
-                       const char** why, long long* bad);
-long long score_records_scratch_bytes(long long R, int leads, long long T, long long W);
-int launch_score_records(const float* clean, const float* out, const float* noisy, long long R, int leads, long long T, long long W,
-                         void* scratch, double* per_lead, double* per_record, double* per_window, double* window_mean,
-                         hipStream_t s, const char** why);
-// on-the-fly noise mixing of training batches (ral_augment.hip; ral_mix_batch / ral_mix_draw).  The geometry travels by value, as
-// a kernel argument (thresholds included: no copy).  mix_batch_check: the broken rule, or nullptr; launch_mix_batch checks, then
-// launches one kernel; -1: bad arguments (*why: the rule that is broken).  mix_batch_draw: the draw of ordinal g on the host, by
-// the code the kernel runs (the geometry must have passed the check)
-struct MixBatchGeom {
-  long long N, Lsrc, Tn;
-  int leads, L, K;
-  uint32_t cum[RAL_MIX_MAX_KINDS];
-  double snr_lo, snr_hi;
-  uint64_t seed, first;
-};
-const char* mix_batch_check(const MixBatchGeom& G);
-void mix_batch_draw(const MixBatchGeom& G, uint64_t g, int32_t* draw, double* snr_db);
-int launch_mix_batch(const float* bank, const float* noise, const int64_t* rows, const MixBatchGeom& G, long long B, float* noisy,
-                     float* clean, int32_t* draws, double* snr_db, hipStream_t s, const char** why);
-// sample-rate conversion (ral_rate.hip; ral_rate_records / ral_rate_pool): the arguments (and, with upload != 0, the host table)
-// are checked, the table copied to tab_dev on s, the kernel launched; -1: bad arguments (*why: the rule that is broken, *bad:
-// the row that breaks it or -1), -2: the copy failed
-int launch_rate_records(const float* x, long long R, int leads, long long T, int up, int down, const float* bank, int ntaps,
-                        float* y, long long T_out, hipStream_t s, const char** why);
-int launch_rate_pool(float* hist, const float* x, long long x_total, const ral_rate_row* tab, int rows, ral_rate_row* tab_dev,
-                     int upload, long long cap, int leads, int up, int down, const float* bank, int ntaps, int hist_len,
-                     float* out, long long out_total, hipStream_t s, const char** why, int* bad);
-// beat detection (ral_beats.hip; ral_beat_records / ral_beat_pool / ral_beat_match): the arguments (and, with upload != 0, the host
-// table) are checked, the table copied to tab_dev on s, the kernels launched; -1: bad arguments (*why: the rule that is broken,
-// *bad: the row that breaks it or -1), -2: the copy failed.  beat_records_scratch_bytes: -1 for a shape the call would refuse
-long long beat_records_scratch_bytes(long long R, int leads, long long T, const ral_beat_geom* geom, const char** why);
-int launch_beat_records(const float* x, long long R, int leads, long long T, const ral_beat_geom* geom, const float* bank, int ntaps,
-                        void* scratch, long long scratch_bytes, int* peaks, long long cap, int* count, hipStream_t s,
-                        const char** why);
-int launch_beat_pool(float* hist, const float* x, long long x_total, const ral_beat_row* tab, int rows, ral_beat_row* tab_dev,
-                     int upload, long long cap, int leads, const ral_beat_geom* geom, const float* bank, int ntaps, int hist_len,
-                     void* scratch, long long scratch_bytes, long long* peaks, long long peaks_total, int* count, hipStream_t s,
-                     const char** why, int* bad);
-int launch_beat_match(const int* ref, const int* nref, long long ref_cap, const int* det, const int* ndet, long long det_cap,
-                      long long R, long long tol, long long* out, hipStream_t s, const char** why);
-// heart-rate variability (ral_hrv.hip; ral_hrv_windows): -1 with *why (and *bad, the table row, or -1) for a refusal, -2 when the
-// table's copy failed
-int launch_hrv_windows(const int* pos, const int* label, const int* count, long long R, long long cap, const ral_hrv_row* tab,
-                       long long rows, ral_hrv_row* tab_dev, int upload, const ral_hrv_geom* geom, const int* band, int* counts,
-                       float* stats, float* psd, hipStream_t s, const char** why, long long* bad);
-// rhythm findings (ral_arrhythmia.hip; ral_arrhythmia_windows): the conventions of launch_hrv_windows
-int launch_arrhythmia_windows(const int* peaks, const int* label, const int* count, const int* on, const int* ppeak, long long R,
-                              long long cap, const ral_hrv_row* tab, long long rows, ral_hrv_row* tab_dev, int upload,
-                              const ral_arrhythmia_geom* geom, int* counts, float* stats, int* flags, hipStream_t s,
-                              const char** why, long long* bad);
-// beat classes (ral_rhythm.hip;ral_rhythm_records / ral_rhythm_pool): the same conventions as beat detection above
-long long rhythm_pool_scratch_bytes(long long beats, int leads, const ral_rhythm_geom* geom, const char** why);
-int launch_rhythm_records(const float* x, long long R, int leads, long long T, const ral_rhythm_geom* geom, const int* peaks,
-                          const int* count, long long cap, int* label, float* corr, float* rr, hipStream_t s, const char** why);
-int launch_rhythm_pool(const float* hist, const float* x, long long x_total, const ral_rhythm_row* tab, int rows,
-                       ral_rhythm_row* tab_dev, int upload, long long cap, int leads, const ral_rhythm_geom* geom, int hist_len,
-                       float* ring, long long* ring_pos, const long long* new_pos, long long new_total, void* scratch,
-                       long long scratch_bytes, long long* out_pos, int* label, float* corr, float* rr, long long out_total,
-                       hipStream_t s, const char** why, int* bad);
-// beat delineation (ral_delineate.hip; ral_delineate_records): -1 with *why for a refusal, before any launch
-int launch_delineate_records(const float* x, long long R, int leads, long long T, const ral_delin_geom* geom, const int* peaks,
-                             const int* count, long long cap, int* on, int* off, int* tpeak, int* tend, hipStream_t s,
-                             const char** why);
-// P wave and ST level (ral_pst.hip; ral_pst_records): -1 with *why for a refusal, before any launch
-int launch_pst_records(const float* x, long long R, int leads, long long T, const ral_pst_geom* geom, const int* peaks,
-                       const int* count, long long cap, const int* on, const int* off, int* pon, int* ppeak, int* poff, float* st,
-                       hipStream_t s, const char** why);
-// median beats (ral_template.hip; ral_template_records): -1 with *why, which names the argument, before any HIP call
-int launch_template_records(const float* x, long long R, int leads, long long T, const ral_template_geom* geom, const int* peaks,
-                            const int* label, const int* count, long long cap, long long nw, float* tpl, int* used, int* total,
-                            int* rr, hipStream_t s, const char** why);
-int launch_conv13_fwd(const float* x, const float* w, const float* b, float* y, int B, int cin, int cout, int L,
-                      int lrelu, hipStream_t s, const char** why);   // -1: refused before any HIP call, *why names the argument
-int launch_conv13_bwd(const float* x, const float* y, const float* dy, const float* w, float* gw, float* gb,
-                      float* dx, int B, int cin, int cout, int L, int lrelu, hipStream_t s, const char** why);
 
 void launch_transpose_mats(const float* src, float* dst, const void* desc, int nmat, int total, hipStream_t s);
 
@@ -233,12 +112,3 @@ void launch_block_dw(const BlockPlan& p, const float* dx2, const float* upre, co
                      const BlockP& w, const BlockP& gr, int N, int B, int ksplit, const unsigned* gmax, hipStream_t s);
 void launch_resample_dw(int D, bool sep, const float* dy, const float* x, const float* lnw, const float* lnb,
                         float* dW, int T, int Tv, int B, int ksplit, hipStream_t s);
-
-// db8 wavelet-threshold baseline (ral_wavelet.hip); non-zero = rejected arguments
-int launch_wavelet_denoise(const float* x, float* y, long long rows, int L, float threshold, hipStream_t s);
-// FFT-threshold baseline (ral_fft.hip).  scratch bytes: 0 = one launch, -1 = refused length or counts; launch: -1 = refused
-// arguments (fft_denoise_rule names the lengths), -2 = a HIP error
-const char* fft_denoise_rule();
-long long fft_denoise_scratch_bytes(long long groups, int rows_per_group, int L);
-int launch_fft_denoise(const float* x, float* y, int32_t* kept, long long groups, int rows_per_group, int L, float threshold,
-                       void* scratch, hipStream_t s);

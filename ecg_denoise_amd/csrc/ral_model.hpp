@@ -16,6 +16,12 @@ int ral_fail(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
     if (e_ != hipSuccess) return ral_fail("%s failed: %s", #expr, hipGetErrorString(e_));    \
   } while (0)
 
+// How an entry point that takes a table ends (ral_api.hip).  rc = 0: launched; what the launches left behind is the result.
+// rc = -1, refused: `why` is the one rule that is broken and `bad`, if it is a row's, which row (else -1), then the call's
+// arguments as args_fmt words them.  Any other rc: the table did not reach the device.
+int table_done(const char* name, int rc, const char* why, long long bad, const char* args_fmt, ...)
+    __attribute__((format(printf, 5, 6)));
+
 // ---- the flat parameter / state layout (the state_dict contract of ral_layout_entry) ----
 struct ParamEntry {
   std::string name;

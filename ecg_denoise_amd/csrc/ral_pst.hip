@@ -20,7 +20,9 @@
 // positions only move plo and lim: no read leaves the record or the lists whatever the tensors hold.
 //
 // Launch: one, grid (cap, R), a wave per beat (a beat at or beyond count writes the padding).
-#include "ral_kernels.hpp"
+#include "../../include/ralenet.h"
+#include "ral_device.hpp"
+#include "ral_model.hpp"
 #include "ral_wave_pick.hpp"
 #include <math.h>
 #include <stdint.h>
@@ -174,14 +176,19 @@ const char* pst_geom(int leads, const ral_pst_geom* p, PstGeom& g) {
 
 }  // namespace
 
-int launch_pst_records(const float* x, long long R, int leads, long long T, const ral_pst_geom* geom, const int* peaks,
-                       const int* count, long long cap, const int* on, const int* off, int* pon, int* ppeak, int* poff, float* st,
-                       hipStream_t s, const char** why) {
+extern "C" int ral_pst_records(const float* x, int64_t R, int leads, int64_t T, const ral_pst_geom* geom, const int32_t* peaks,
+                               const int32_t* count, int64_t cap, const int32_t* on, const int32_t* off, int32_t* pon, int32_t* ppeak,
+                               int32_t* poff, float* st, ral_stream s) {
+  if (!x || !geom || !peaks || !count || !on || !off || !pon || !ppeak || !poff || !st) return ral_fail("pst_records: null pointer");
   PstGeom g;
-  if ((*why = pst_geom(leads, geom, g))) return -1;
-  if (R < 1 || R > 65535 || T < 1 || T > 0x7fffffffLL) { *why = "1 <= R <= 65535 and 1 <= T < 2^31"; return -1; }
-  if (cap < 1 || cap > 0x7fffffffLL) { *why = "1 <= cap < 2^31"; return -1; }
-  k_pst_records<<<dim3((unsigned)cap, (unsigned)R), DL_WAVE, pst_lds_bytes(g), s>>>(x, T, g, peaks, count, cap, on, off, pon,
-                                                                                  ppeak, poff, st);
+  const char* why = pst_geom(leads, geom, g);
+  if (!why && (R < 1 || R > 65535 || T < 1 || T > 0x7fffffffLL)) why = "1 <= R <= 65535 and 1 <= T < 2^31";
+  if (!why && (cap < 1 || cap > 0x7fffffffLL)) why = "1 <= cap < 2^31";
+  if (why)
+    return ral_fail("pst_records: need %s (R=%lld leads=%d T=%lld cap=%lld m2=%d g=%d Wp=%d j=%d w=%g p0=%g)", why, (long long)R,
+                    leads, (long long)T, (long long)cap, geom->m2, geom->g, geom->wp, geom->j, geom->w, geom->p0);
+  k_pst_records<<<dim3((unsigned)cap, (unsigned)R), DL_WAVE, pst_lds_bytes(g), (hipStream_t)s>>>(x, T, g, peaks, count, cap, on, off, pon,
+                                                                                               ppeak, poff, st);
+  HIP_OK(hipGetLastError());
   return 0;
 }

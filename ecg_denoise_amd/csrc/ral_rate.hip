@@ -17,7 +17,9 @@
 //   the tile's outputs, shifted the same way for float4 stores.
 // rate_tile is the only place that forms an output, for whole records and for pool chunks alike: a record is a stream that
 // has received nothing before (n0 = 0) and gets all T samples now, so both read the same staged values through the same code.
-#include "ral_kernels.hpp"
+#include "../../include/ralenet.h"
+#include "ral_device.hpp"
+#include "ral_model.hpp"
 #include "ral_slots.hpp"
 #include <stdint.h>
 
@@ -211,33 +213,45 @@ const char* rate_pool_fault(const RatePoolRow* tab, int rows, long long cap, int
 
 }  // namespace
 
-int launch_rate_records(const float* x, long long R, int leads, long long T, int up, int down, const float* bank, int ntaps,
-                        float* y, long long T_out, hipStream_t s, const char** why) {
+extern "C" int ral_rate_records(const float* x, int64_t R, int leads, int64_t T, int up, int down, const float* bank, int ntaps,
+                                float* y, int64_t T_out, ral_stream s) {
+  if (!x || !bank || !y) return ral_fail("rate_records: null pointer");
   RateGeom g;
-  if ((*why = rate_geom(up, down, ntaps, g))) return -1;
-  if (R < 1 || leads < 1 || T < 1 || T > (1LL << 40)) { *why = "R >= 1, leads >= 1, 1 <= T <= 2^40"; return -1; }
-  if (T_out != rate_ceil_div(T * up, down)) { *why = "T_out = ceil(T up / down)"; return -1; }
-  const long long tiles = (T_out + g.tile - 1) / g.tile;
-  if (R * leads > 65535 || tiles > 0xffffffLL) { *why = "R * leads <= 65535 and fewer than 2^24 tiles per record"; return -1; }
+  long long tiles = 0;
+  const char* why = rate_geom(up, down, ntaps, g);
+  if (!why && (R < 1 || leads < 1 || T < 1 || T > (1LL << 40))) why = "R >= 1, leads >= 1, 1 <= T <= 2^40";
+  if (!why && T_out != rate_ceil_div(T * up, down)) why = "T_out = ceil(T up / down)";
+  if (!why && ((tiles = (T_out + g.tile - 1) / g.tile) > 0xffffffLL || R * leads > 65535))
+    why = "R * leads <= 65535 and fewer than 2^24 tiles per record";
+  if (why)
+    return ral_fail("rate_records: need %s (R=%lld leads=%d T=%lld up=%d down=%d ntaps=%d T_out=%lld)", why, (long long)R, leads,
+                (long long)T, up, down, ntaps, (long long)T_out);
   const size_t lds = rate_lds_bytes(g);
-  k_rate_records<<<dim3((unsigned)tiles, (unsigned)(R * leads)), RATE_THREADS, lds, s>>>(x, T, T_out, g, bank, y);
+  k_rate_records<<<dim3((unsigned)tiles, (unsigned)(R * leads)), RATE_THREADS, lds, (hipStream_t)s>>>(x, T, T_out, g, bank, y);
+  HIP_OK(hipGetLastError());
   return 0;
 }
 
-int launch_rate_pool(float* hist, const float* x, long long x_total, const ral_rate_row* tab, int rows, ral_rate_row* tab_dev,
-                     int upload, long long cap, int leads, int up, int down, const float* bank, int ntaps, int hist_len,
-                     float* out, long long out_total, hipStream_t s, const char** why, int* bad) {
+extern "C" int ral_rate_pool(float* hist, const float* x, int64_t x_total, const ral_rate_row* table, int rows,
+                             ral_rate_row* table_dev, int upload, int64_t capacity, int leads, int up, int down, const float* bank,
+                             int ntaps, int hist_len, float* out, int64_t out_total, ral_stream s) {
+  if (!hist || !x || !table || !table_dev || !bank || !out) return ral_fail("rate_pool: null pointer");
   RateGeom g;
-  *bad = -1;
-  if ((*why = rate_geom(up, down, ntaps, g))) return -1;
-  if ((*why = rate_pool_fault(tab, rows, cap, leads, g, hist_len, x_total, out_total, upload != 0, bad))) return -1;
-  long long m_max = 0;
-  for (int r = 0; r < rows; ++r) m_max = tab[r].m > m_max ? tab[r].m : m_max;
-  const long long tiles = (m_max + g.tile - 1) / g.tile;
-  if (tiles > 0xffffffLL) { *why = "fewer than 2^24 tiles of outputs per row"; return -1; }
-  if (upload && slots_upload(tab, rows, tab_dev, s)) return -2;
-  const size_t lds = rate_lds_bytes(g);
-  k_rate_pool<<<dim3((unsigned)tiles + 1, (unsigned)(rows * leads)), RATE_THREADS, lds, s>>>(hist, x, tab_dev, cap, leads, hist_len, g,
-                                                                                            bank, out);
-  return 0;
+  int bad = -1;
+  long long tiles = 0;
+  const char* why = rate_geom(up, down, ntaps, g);
+  if (!why) why = rate_pool_fault(table, rows, capacity, leads, g, hist_len, x_total, out_total, upload != 0, &bad);
+  if (!why) {
+    long long m_max = 0;
+    for (int r = 0; r < rows; ++r) m_max = table[r].m > m_max ? table[r].m : m_max;
+    tiles = (m_max + g.tile - 1) / g.tile;
+    if (tiles > 0xffffffLL) why = "fewer than 2^24 tiles of outputs per row";
+  }
+  const int rc = why ? -1 : upload ? slots_upload(table, rows, table_dev, (hipStream_t)s) : 0;
+  if (!rc)
+    k_rate_pool<<<dim3((unsigned)tiles + 1, (unsigned)(rows * leads)), RATE_THREADS, rate_lds_bytes(g), (hipStream_t)s>>>(
+        hist, x, table_dev, capacity, leads, hist_len, g, bank, out);
+  return table_done("rate_pool", rc, why, bad, "rows=%d capacity=%lld leads=%d up=%d down=%d ntaps=%d hist_len=%d x_total=%lld "
+                    "out_total=%lld", rows, (long long)capacity, leads, up, down, ntaps, hist_len, (long long)x_total,
+                    (long long)out_total);
 }

@@ -16,10 +16,13 @@
 // Launches:  records  one: grid (cap, R), a wave per beat (a beat at or beyond count writes the padding).
 //            pool     gather (the extended windows of the call's new beats, from the history plane and the chunk, into scratch),
 //                     classify (a wave per beat that became final), keep (the last K beats' windows and positions into the ring).
-#include "ral_kernels.hpp"
+#include "../../include/ralenet.h"
+#include "ral_device.hpp"
+#include "ral_model.hpp"
 #include "ral_slots.hpp"
 #include <math.h>
 #include <stdint.h>
+#include <stdio.h>
 
 namespace {
 
@@ -322,50 +325,78 @@ const char* rhythm_pool_fault(const RhythmRow* tab, int rows, long long cap, con
 
 }  // namespace
 
-long long rhythm_pool_scratch_bytes(long long beats, int leads, const ral_rhythm_geom* geom, const char** why) {
+// the caller's geometry as the refusals print it
+static void rhythm_geom_text(const ral_rhythm_geom* g, char* buf, size_t n) {
+  if (g) snprintf(buf, n, "Wb=%d Sa=%d c0=%g r0=%g", g->wb, g->sa, g->c0, g->r0);
+  else snprintf(buf, n, "no geometry");
+}
+
+extern "C" int64_t ral_rhythm_pool_scratch_bytes(int64_t beats, int leads, const ral_rhythm_geom* geom) {
   RhythmGeom g;
-  if ((*why = rhythm_geom(leads, geom, g))) return -1;
-  if (beats < 0 || beats > (1LL << 31)) { *why = "0 <= beats <= 2^31"; return -1; }
+  const char* why = rhythm_geom(leads, geom, g);
+  if (!why && (beats < 0 || beats > (1LL << 31))) why = "0 <= beats <= 2^31";
+  if (why) {
+    char gt[96];
+    rhythm_geom_text(geom, gt, sizeof(gt));
+    return ral_fail("rhythm_pool_scratch_bytes: need %s (beats=%lld leads=%d %s)", why, (long long)beats, leads, gt);
+  }
   return (beats > 0 ? beats : 1) * g.leads * g.We * 4;
 }
 
-int launch_rhythm_records(const float* x, long long R, int leads, long long T, const ral_rhythm_geom* geom, const int* peaks,
-                          const int* count, long long cap, int* label, float* corr, float* rr, hipStream_t s, const char** why) {
+extern "C" int ral_rhythm_records(const float* x, int64_t R, int leads, int64_t T, const ral_rhythm_geom* geom, const int32_t* peaks,
+                                  const int32_t* count, int64_t cap, int32_t* label, float* corr, float* rr_ratio, ral_stream s) {
+  if (!x || !geom || !peaks || !count || !label || !corr || !rr_ratio) return ral_fail("rhythm_records: null pointer");
   RhythmGeom g;
-  if ((*why = rhythm_geom(leads, geom, g))) return -1;
-  if (R < 1 || R > 65535 || T < 1 || T > 0x7fffffffLL) { *why = "1 <= R <= 65535 and 1 <= T < 2^31"; return -1; }
-  if (cap < 1 || cap > 0x7fffffffLL) { *why = "1 <= cap < 2^31"; return -1; }
-  k_rhythm_records<<<dim3((unsigned)cap, (unsigned)R), RH_WAVE, rhythm_lds_bytes(g), s>>>(x, T, g, peaks, count, cap, label, corr, rr);
+  const char* why = rhythm_geom(leads, geom, g);
+  if (!why && (R < 1 || R > 65535 || T < 1 || T > 0x7fffffffLL)) why = "1 <= R <= 65535 and 1 <= T < 2^31";
+  if (!why && (cap < 1 || cap > 0x7fffffffLL)) why = "1 <= cap < 2^31";
+  if (why) {
+    char gt[96];
+    rhythm_geom_text(geom, gt, sizeof(gt));
+    return ral_fail("rhythm_records: need %s (R=%lld leads=%d T=%lld cap=%lld %s)", why, (long long)R, leads, (long long)T,
+                (long long)cap, gt);
+  }
+  k_rhythm_records<<<dim3((unsigned)cap, (unsigned)R), RH_WAVE, rhythm_lds_bytes(g), (hipStream_t)s>>>(x, T, g, peaks, count, cap, label,
+                                                                                                     corr, rr_ratio);
+  HIP_OK(hipGetLastError());
   return 0;
 }
 
-int launch_rhythm_pool(const float* hist, const float* x, long long x_total, const ral_rhythm_row* tab, int rows,
-                       ral_rhythm_row* tab_dev, int upload, long long cap, int leads, const ral_rhythm_geom* geom, int hist_len,
-                       float* ring, long long* ring_pos, const long long* new_pos, long long new_total, void* scratch,
-                       long long scratch_bytes, long long* out_pos, int* label, float* corr, float* rr, long long out_total,
-                       hipStream_t s, const char** why, int* bad) {
+extern "C" int ral_rhythm_pool(const float* hist, const float* x, int64_t x_total, const ral_rhythm_row* table, int rows,
+                               ral_rhythm_row* table_dev, int upload, int64_t capacity, int leads, const ral_rhythm_geom* geom,
+                               int hist_len, float* ring, int64_t* ring_pos, const int64_t* new_pos, int64_t new_total, void* scratch,
+                               int64_t scratch_bytes, int64_t* out_pos, int32_t* label, float* corr, float* rr_ratio,
+                               int64_t out_total, ral_stream s) {
+  if (!hist || !x || !table || !table_dev || !geom || !ring || !ring_pos || !new_pos || !scratch || !out_pos || !label || !corr ||
+      !rr_ratio)
+    return ral_fail("rhythm_pool: null pointer");
+  hipStream_t st = (hipStream_t)s;
   RhythmGeom g;
-  *bad = -1;
-  if ((*why = rhythm_geom(leads, geom, g))) return -1;
-  if ((*why = rhythm_pool_fault(tab, rows, cap, g, hist_len, x_total, new_total, out_total, upload != 0, bad))) return -1;
-  if (((uintptr_t)scratch & 3) || scratch_bytes < (new_total > 0 ? new_total : 1) * g.leads * g.We * 4) {
-    *why = "a scratch of ral_rhythm_pool_scratch_bytes(new_total, leads, ...) bytes";
-    return -1;
+  int bad = -1;
+  const char* why = rhythm_geom(leads, geom, g);
+  if (!why) why = rhythm_pool_fault(table, rows, capacity, g, hist_len, x_total, new_total, out_total, upload != 0, &bad);
+  if (!why && (((uintptr_t)scratch & 3) || scratch_bytes < (new_total > 0 ? new_total : 1) * g.leads * g.We * 4))
+    why = "a scratch of ral_rhythm_pool_scratch_bytes(new_total, leads, ...) bytes";
+  const int rc = why ? -1 : upload ? slots_upload(table, rows, table_dev, st) : 0;
+  if (!rc) {
+    long long m_max = 0, ne_max = 0;
+    for (int r = 0; r < rows; ++r) {
+      m_max = table[r].m > m_max ? table[r].m : m_max;
+      ne_max = table[r].ne > ne_max ? table[r].ne : ne_max;
+    }
+    long long* rpos = (long long*)ring_pos;
+    const long long* npos = (const long long*)new_pos;
+    float* win = (float*)scratch;
+    if (m_max > 0)
+      k_rhythm_gather_pool<<<dim3((unsigned)m_max, (unsigned)rows), RH_WAVE, 0, st>>>(hist, x, table_dev, capacity, hist_len, g, npos, win);
+    if (ne_max > 0)
+      k_rhythm_classify_pool<<<dim3((unsigned)ne_max, (unsigned)rows), RH_WAVE, rhythm_lds_bytes(g), st>>>(
+          table_dev, capacity, g, ring, rpos, npos, win, (long long*)out_pos, label, corr, rr_ratio);
+    if (m_max > 0) k_rhythm_keep_pool<<<dim3(RH_K, (unsigned)rows), RH_WAVE, 0, st>>>(table_dev, g, ring, rpos, npos, win);
   }
-  long long m_max = 0, ne_max = 0;
-  for (int r = 0; r < rows; ++r) {
-    m_max = tab[r].m > m_max ? tab[r].m : m_max;
-    ne_max = tab[r].ne > ne_max ? tab[r].ne : ne_max;
-  }
-  if (upload && slots_upload(tab, rows, tab_dev, s)) return -2;
-  float* win = (float*)scratch;
-  if (m_max > 0)
-    k_rhythm_gather_pool<<<dim3((unsigned)m_max, (unsigned)rows), RH_WAVE, 0, s>>>(hist, x, tab_dev, cap, hist_len, g, new_pos, win);
-  if (ne_max > 0)
-    k_rhythm_classify_pool<<<dim3((unsigned)ne_max, (unsigned)rows), RH_WAVE, rhythm_lds_bytes(g), s>>>(tab_dev, cap, g, ring, ring_pos,
-                                                                                                      new_pos, win, out_pos, label,
-                                                                                                      corr, rr);
-  if (m_max > 0)
-    k_rhythm_keep_pool<<<dim3(RH_K, (unsigned)rows), RH_WAVE, 0, s>>>(tab_dev, g, ring, ring_pos, new_pos, win);
-  return 0;
+  char gt[96] = "";
+  if (rc) rhythm_geom_text(geom, gt, sizeof(gt));
+  return table_done("rhythm_pool", rc, why, bad, "rows=%d capacity=%lld leads=%d hist_len=%d x_total=%lld new_total=%lld "
+                    "out_total=%lld scratch_bytes=%lld %s", rows, (long long)capacity, leads, hist_len, (long long)x_total,
+                    (long long)new_total, (long long)out_total, (long long)scratch_bytes, gt);
 }

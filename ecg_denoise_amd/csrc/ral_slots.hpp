@@ -9,7 +9,9 @@
 // nothing is written for it.  No workgroup reads a plane that another one writes; the host flips the turn of the kept rows.
 #pragma once
 #include <vector>
-#include "ral_kernels.hpp"
+#include <hip/hip_runtime.h>
+#include "../../include/ralenet.h"
+#include "ral_device.hpp"
 
 // the rules on the shared fields that differ between the pools: the smallest length a stream may end with, whether an open row
 // must bring samples, and the wording of the two rules that name a pool's own fields

@@ -18,7 +18,9 @@
 // flight together - so their number is not limited by LDS.  Nothing depends on the grid.
 //
 // Launch: one, grid (nw, R, ceil(Wn / (TP_SPAN TP_TILE))), TP_THREADS threads; no scratch buffer, no memset, no atomics.
-#include "ral_kernels.hpp"
+#include "../../include/ralenet.h"
+#include "ral_device.hpp"
+#include "ral_model.hpp"
 #include <stdint.h>
 
 namespace {
@@ -183,29 +185,40 @@ __global__ __launch_bounds__(TP_THREADS) void k_template_records(const float* __
 
 }  // namespace
 
-int launch_template_records(const float* x, long long R, int leads, long long T, const ral_template_geom* geom, const int* peaks,
-                            const int* label, const int* count, long long cap, long long nw, float* tpl, int* used, int* total,
-                            int* rr, hipStream_t s, const char** why) {
-  *why = !x ? "x is NULL" : !geom ? "geom is NULL" : !peaks ? "peaks is NULL" : !count ? "count is NULL" : !tpl ? "tpl is NULL" :
-         !used ? "used is NULL" : !total ? "total is NULL" : !rr ? "rr is NULL" : nullptr;
-  if (*why) return -1;
+// the argument a call is refused for (geom is not null), or null
+static const char* template_fault(long long R, int leads, long long T, const ral_template_geom* geom, long long cap, long long nw) {
   const int big = 1 << 19;      // (Wn <= 2^20 + 1: the spans fit a grid dimension)
-  if (R < 1 || R > 65535) { *why = "R must be in [1, 65535]"; return -1; }
-  if (leads < 1 || leads > 65535) { *why = "leads must be in [1, 65535]"; return -1; }
-  if (T < 1 || T > 0x7fffffffLL) { *why = "T must be in [1, 2^31)"; return -1; }
-  if (cap < 1 || cap > 0x7fffffffLL) { *why = "cap must be in [1, 2^31)"; return -1; }
-  if (geom->wpre < 1 || geom->wpre > big) { *why = "geom.wpre must be in [1, 2^19]"; return -1; }
-  if (geom->wpost < 1 || geom->wpost > big) { *why = "geom.wpost must be in [1, 2^19]"; return -1; }
-  if (geom->w < 1) { *why = "geom.w must be >= 1"; return -1; }
-  if (geom->h < 1) { *why = "geom.h must be >= 1"; return -1; }
-  if (geom->kmax < 1 || geom->kmax > TP_KMAX) { *why = "geom.kmax must be in [1, 256]"; return -1; }
+  if (R < 1 || R > 65535) return "R must be in [1, 65535]";
+  if (leads < 1 || leads > 65535) return "leads must be in [1, 65535]";
+  if (T < 1 || T > 0x7fffffffLL) return "T must be in [1, 2^31)";
+  if (cap < 1 || cap > 0x7fffffffLL) return "cap must be in [1, 2^31)";
+  if (geom->wpre < 1 || geom->wpre > big) return "geom.wpre must be in [1, 2^19]";
+  if (geom->wpost < 1 || geom->wpost > big) return "geom.wpost must be in [1, 2^19]";
+  if (geom->w < 1) return "geom.w must be >= 1";
+  if (geom->h < 1) return "geom.h must be >= 1";
+  if (geom->kmax < 1 || geom->kmax > TP_KMAX) return "geom.kmax must be in [1, 256]";
   const long long rule = T < geom->w ? 1 : (T - geom->w) / geom->h + 1;
-  if (nw != rule) { *why = "nw must be max(1, (T - w) / h + 1), the number of windows of T samples"; return -1; }
+  if (nw != rule) return "nw must be max(1, (T - w) / h + 1), the number of windows of T samples";
+  return nullptr;
+}
+
+extern "C" int ral_template_records(const float* x, int64_t R, int leads, int64_t T, const ral_template_geom* geom,
+                                    const int32_t* peaks, const int32_t* label_or_null, const int32_t* count, int64_t cap, int64_t nw,
+                                    float* tpl, int32_t* used, int32_t* total, int32_t* rr, ral_stream s) {
+  const char* why = !x ? "x is NULL" : !geom ? "geom is NULL" : !peaks ? "peaks is NULL" : !count ? "count is NULL" :
+                    !tpl ? "tpl is NULL" : !used ? "used is NULL" : !total ? "total is NULL" : !rr ? "rr is NULL" :
+                    template_fault(R, leads, T, geom, cap, nw);
+  if (why) {
+    const ral_template_geom none = {0, 0, 0, 0, 0}, *g = geom ? geom : &none;
+    return ral_fail("ral_template_records: %s (R=%lld leads=%d T=%lld cap=%lld nw=%lld wpre=%d wpost=%d w=%d h=%d kmax=%d)", why,
+                    (long long)R, leads, (long long)T, (long long)cap, (long long)nw, g->wpre, g->wpost, g->w, g->h, g->kmax);
+  }
   TplGeom g;
   g.leads = leads, g.wpre = geom->wpre, g.wpost = geom->wpost, g.wn = geom->wpre + geom->wpost + 1, g.kmax = geom->kmax;
   g.w = geom->w, g.h = geom->h;
   const unsigned spans = (unsigned)((g.wn + TP_SPAN * TP_TILE - 1) / (TP_SPAN * TP_TILE));
-  k_template_records<<<dim3((unsigned)nw, (unsigned)R, spans), TP_THREADS, 0, s>>>(x, T, g, peaks, label, count, cap, nw, tpl, used,
-                                                                                 total, rr);
+  k_template_records<<<dim3((unsigned)nw, (unsigned)R, spans), TP_THREADS, 0, (hipStream_t)s>>>(x, T, g, peaks, label_or_null, count, cap,
+                                                                                              nw, tpl, used, total, rr);
+  HIP_OK(hipGetLastError());
   return 0;
 }

@@ -10,6 +10,7 @@
 #include <stdint.h>
 #include "../../include/ralenet.h"
 #include "ral_device.hpp"
+#include "ral_model.hpp"
 
 namespace {
 constexpr int WF = 16;   // db8 filter length
@@ -97,10 +98,17 @@ __global__ __launch_bounds__(128) void k_wavelet_denoise(const float* __restrict
 }
 }  // namespace
 
-// (the C entry point, ral_wavelet_denoise, is in ral_api.hip with the other argument checks)
-int launch_wavelet_denoise(const float* x, float* y, long long rows, int L, float threshold, hipStream_t stream) {
-  if (rows < 0 || L < 2 || (L & 1) || L > 8192) return -1;
-  if (rows == 0) return 0;
+extern "C" int ral_wavelet_denoise(const float* x, float* y, int64_t rows, int L, float threshold, ral_stream s) {
+  if (!x || !y) return ral_fail("wavelet_denoise: null pointer");
+  if (!(threshold >= 0.f)) return ral_fail("wavelet_denoise: the threshold factor must be non-negative (got %g)", (double)threshold);
+  auto refused = [&] {
+    return ral_fail("wavelet_denoise: need rows >= 0 and an even record length <= 8192 (rows=%lld L=%d)", (long long)rows, L);
+  };
+  if (rows < 0 || L < 2 || (L & 1) || L > 8192) return refused();
+  if (rows == 0) {
+    HIP_OK(hipGetLastError());
+    return 0;
+  }
   WavePlan P;
   P.nlev = 0; P.n[0] = L; P.off[0] = 0; P.total = 0;
   if (L >= WF - 1) {
@@ -114,9 +122,10 @@ int launch_wavelet_denoise(const float* x, float* y, long long rows, int L, floa
     P.total += P.n[k];
   }
   const size_t lds = (size_t)(2 * L + P.total + 16) * sizeof(float);
-  if (lds > 150 * 1024) return -1;
+  if (lds > 150 * 1024) return refused();
   if (lds > 48 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_wavelet_denoise), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  k_wavelet_denoise<<<(unsigned)rows, 128, lds, stream>>>(x, y, L, P, threshold);
+  k_wavelet_denoise<<<(unsigned)rows, 128, lds, (hipStream_t)s>>>(x, y, L, P, threshold);
+  HIP_OK(hipGetLastError());
   return 0;
 }

@@ -102,7 +102,7 @@ def test_null_pointers_are_refused(which, null_at):
 # ---- host geometry: brute force against the offline stitch rule ---------------------------------------------------------
 def _offline_owner(T, L, hop):
     """owner window and its start for every sample of a record of T samples: the rule of ral_stream_stitch
-    (stream_keep / stream_owner in ral_misc.hip), restated on the host"""
+    (stream_keep / stream_owner in ral_stream.hip), restated on the host"""
     n_reg = (T - L) // hop + 1
     n = n_reg + (1 if (T - L) % hop else 0)
     h = (L - hop) // 2
