@@ -16,7 +16,8 @@
 
 Functional, dtype-generic (fp64 for the parity tests).  `state` holds running_mean / running_var per BatchNorm, updated in
 place in training mode exactly as torch does (momentum 0.1, unbiased variance).  Pinned against the reference itself by
-tests/golden/g3_danet_L512.npz (oracle/gen_golden_danet.py imports model/DAM.py)."""
+tests/golden/g3_danet_L512.npz and, where the DAM's max-pools meet equal maxima, by g3_danet_ties_L256.npz
+(oracle/gen_golden_danet.py imports model/DAM.py)."""
 from collections import OrderedDict
 import math
 
@@ -117,6 +118,9 @@ def _bn(x, st, pre, training, eps=1e-5, momentum=0.1):
 
 
 def _aprelu(x, st, pre, training):
+    """`clamp` for the reference's torch.max(x, 0) / torch.min(x, 0) (DAM.py:12-48): the two differ only in the gradient
+    at an activation of exactly 0.0 (clamp passes it on, max / min against a zero tensor halve it), which a convolution
+    with a non-zero bias never produces - left as it is"""
     p, n = torch.clamp(x, min=0), torch.clamp(x, max=0)
     d = torch.cat([p.mean(-1), n.mean(-1)], 1)
     h = F.linear(d, st[pre + ".fcn.0.weight"], st[pre + ".fcn.0.bias"])
@@ -134,10 +138,13 @@ def _dam_fcn(v, st, pre, training):
 
 
 def _dam(x, st, pre, training):
+    """both maxima as the reference takes them, with nn.AdaptiveMaxPool1d(1) (DAM.py:121,135,143,150): where several
+    inputs hold the maximum its gradient goes to the FIRST of them (`amax` would split it evenly over all of them)"""
     ga = _dam_fcn(x.mean(-1), st, pre + ".fcn1", training)          # the shared fcn: first the average-pooled batch,
-    gm = _dam_fcn(x.amax(-1), st, pre + ".fcn1", training)          # then the max-pooled one
+    gm = _dam_fcn(F.adaptive_max_pool1d(x, 1).squeeze(-1), st, pre + ".fcn1", training)          # then the max-pooled one
     cattn = torch.sigmoid(ga + gm).unsqueeze(-1)
-    cat = torch.stack([x.mean(1), x.amax(1)], 1)                    # (B, 2, L)
+    cmax = F.adaptive_max_pool1d(x.transpose(1, 2), 1).squeeze(-1)  # (B, L): the maximum over channels, first channel at a tie
+    cat = torch.stack([x.mean(1), cmax], 1)                         # (B, 2, L)
     sattn = torch.sigmoid(F.conv1d(cat, st[pre + ".convsa.weight"], st[pre + ".convsa.bias"]))   # (B, 1, L)
     return sattn * (cattn * x)
 

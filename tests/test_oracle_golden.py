@@ -251,6 +251,35 @@ def test_danet_oracle_matches_reference_golden(golden_dir):
     assert n == 2 * (4 * 3 + 4 * 3 + 3 * 4)
 
 
+def test_danet_oracle_matches_reference_where_the_max_pools_meet_ties(golden_dir):
+    """The reference in float64 on a batch whose even windows repeat one 32-sample beat (g3_danet_ties_L256.npz, made by
+    oracle/gen_golden_danet.py from tests/tie_util.py's builders): on those windows the DAM's nn.AdaptiveMaxPool1d(1) meets its
+    maximum once per period and sends the gradient to the first, and the state has negated BatchNorm gains in the DAM cells.
+    Output, loss and every gradient to 1e-9; the input gradient per window (measured 3e-16 at worst).  An oracle that takes the
+    maxima with `amax`, which splits the gradient evenly over tied maxima, is 5e-3 to 2e-2 off on each periodic window and
+    1e-15 on the others."""
+    import danet_oracle as D
+    import tie_util as T
+    g = load(golden_dir, "g3_danet_ties_L256")
+    x = torch.from_numpy(g["x"]); tgt = torch.from_numpy(g["target"])
+    assert x.dtype == torch.float64 and tuple(x.shape) == (8, 2, 256)
+    xb, tb = T.danet_tie_batch(*T.DANET_CASES[0])           # the fixture is the builders' batch
+    assert torch.equal(x, xb.double()) and torch.equal(tgt, tb.double())
+    r = T.danet_oracle_step(T.danet_negated_state(torch.float64), x, tgt)
+    assert rel(r["y"].numpy(), g["y_train"]) < 1e-9
+    assert abs(r["loss"] - float(g["loss"])) < 1e-9 * float(g["loss"])
+    assert ["grad_" + k for k in r["grads"]] == [k for k in g.files if k.startswith("grad_")]
+    for k, gr in r["grads"].items():
+        if k.endswith((".fcn.0.bias", ".fcn.3.bias", ".fcn1.0.bias", ".fcn1.3.bias")):
+            # a bias in front of a batch-statistics BatchNorm has no gradient: rounding noise on both sides
+            assert np.abs(g["grad_" + k]).max() < 1e-12 and gr.abs().max().item() < 1e-12, k
+        else:
+            assert rel(gr.numpy(), g["grad_" + k]) < 1e-9, k
+    e = T.per_window(r["dx"].numpy(), g["dx"])
+    print("dx per window:", e)
+    assert (e < 1e-9).all(), e
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # wavelet-threshold baseline: the oracle against the reference function run on PyWavelets 1.1.1 (oracle/gen_golden_wavelet.py)
 # ---------------------------------------------------------------------------------------------------------------------
