@@ -1639,6 +1639,9 @@ __global__ __launch_bounds__(256) void k_final_bwd(const float* __restrict__ dy,
 // conv stem backward.  Pass 1: per-channel sums of dy and dy*xhat (BatchNorm backward).
 // Pass 2: d a0 = gamma rstd (dy - mean(dy) - xhat mean(dy xhat)); LeakyReLU'; conv w/b grads.
 // ss = [scale(8), shift(8), mean(8), rstd(8)] from k_bn_train8.
+// Frozen BatchNorm (k_conv1_bwd_frozen; ss from k_conv1_fwd<., 2>): the statistics are constants, so d a0 = gamma rstd dy
+// and pass 1 is not run; the affine gradients g_gamma = sum dy xhat, g_beta = sum dy join the conv gradients in the
+// workgroup reduction (16 more sums).
 // =================================================================================
 __global__ __launch_bounds__(256) void k_bn8_bwd_stats(const float* __restrict__ dy, const float* __restrict__ a0,
                                                        const float* __restrict__ ss, double* __restrict__ out,
@@ -1673,22 +1676,21 @@ __global__ __launch_bounds__(256) void k_bn8_bwd_stats(const float* __restrict__
   }
 }
 
-template <int LEADS>
-__global__ __launch_bounds__(256) void k_conv1_bwd(const float* __restrict__ dy, const float* __restrict__ a0,
-                                                   const float* __restrict__ x, const float* __restrict__ ss,
-                                                   const float* __restrict__ bnw, const double* __restrict__ bst,
-                                                   double count, float* __restrict__ gw, float* __restrict__ gb,
-                                                   float* __restrict__ dzout, int L, int Lp, int B,
-                                                   float* __restrict__ gbnw, float* __restrict__ gbnb, double share) {
+template <int LEADS, bool FROZEN>
+RAL_DEV void conv1_bwd_body(const float* __restrict__ dy, const float* __restrict__ a0, const float* __restrict__ x,
+                            const float* __restrict__ ss, const float* __restrict__ bnw, const double* __restrict__ bst,
+                            double count, float* __restrict__ gw, float* __restrict__ gb, float* __restrict__ dzout, int L,
+                            int Lp, int B, float* __restrict__ gbnw, float* __restrict__ gbnb, double share) {
   // L: samples per window of x; Lp >= L: token slots per window of dy / a0 / dzout (slots past L do not exist: no gradient)
-  constexpr int NG = 8 * LEADS * 3 + 8;
+  constexpr int NC = 8 * LEADS * 3 + 8;         // conv weight + bias gradients
+  constexpr int NG = NC + (FROZEN ? 16 : 0);    // (+ the BatchNorm affine gradients: gamma, beta)
   __shared__ float red[4][NG];
   float k1[8], m1[8], m2[8];
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
     k1[c] = bnw[c] * ss[24 + c];
-    m1[c] = (float)(bst[c] / count);
-    m2[c] = (float)(bst[8 + c] / count);
+    m1[c] = FROZEN ? 0.f : (float)(bst[c] / count);
+    m2[c] = FROZEN ? 0.f : (float)(bst[8 + c] / count);
   }
   float acc[NG];
 #pragma unroll
@@ -1719,7 +1721,8 @@ __global__ __launch_bounds__(256) void k_conv1_bwd(const float* __restrict__ dy,
 #pragma unroll
     for (int o = 0; o < 8; ++o) {
       const float xh = (v[o] - ss[16 + o]) * ss[24 + o];
-      float da = k1[o] * (d[o] - m1[o] - xh * m2[o]);
+      float da = FROZEN ? k1[o] * d[o] : k1[o] * (d[o] - m1[o] - xh * m2[o]);
+      if (FROZEN) { acc[NC + o] += d[o] * xh; acc[NC + 8 + o] += d[o]; }
       da = v[o] > 0.f ? da : 0.2f * da;
       dz[o] = da;
 #pragma unroll
@@ -1744,16 +1747,31 @@ __global__ __launch_bounds__(256) void k_conv1_bwd(const float* __restrict__ dy,
   if ((int)threadIdx.x < NG) {
     const float s = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
     if ((int)threadIdx.x < 8 * LEADS * 3) atomicAdd(gw + threadIdx.x, s);
-    else atomicAdd(gb + threadIdx.x - 8 * LEADS * 3, s);
+    else if ((int)threadIdx.x < NC) atomicAdd(gb + threadIdx.x - 8 * LEADS * 3, s);
+    else if ((int)threadIdx.x < NC + 8) atomicAdd(gbnw + threadIdx.x - NC, s);
+    else atomicAdd(gbnb + threadIdx.x - NC - 8, s);
   }
   // BatchNorm affine grads from the (all-reduced) backward sums: g_w += sum dy*xhat, g_b += sum dy (one workgroup's eight
   // threads; it was a launch of its own).  `share` = this rank's fraction of the global batch: the sums are already all-reduced,
   // and the gradient all-reduce (sum over ranks) that follows must reproduce them exactly once.
-  if (blockIdx.x == 0 && threadIdx.x < 8) {
+  if (!FROZEN && blockIdx.x == 0 && threadIdx.x < 8) {
     const int c = threadIdx.x;
     gbnb[c] += (float)(bst[c] * share); gbnw[c] += (float)(bst[8 + c] * share);
   }
 }
+
+#define CONV1_BWD_ARGS const float* __restrict__ dy, const float* __restrict__ a0, const float* __restrict__ x, const float* __restrict__ ss, \
+    const float* __restrict__ bnw, const double* __restrict__ bst, double count, float* __restrict__ gw, float* __restrict__ gb,                \
+    float* __restrict__ dzout, int L, int Lp, int B, float* __restrict__ gbnw, float* __restrict__ gbnb, double share
+template <int LEADS>
+__global__ __launch_bounds__(256) void k_conv1_bwd(CONV1_BWD_ARGS) {
+  conv1_bwd_body<LEADS, false>(dy, a0, x, ss, bnw, bst, count, gw, gb, dzout, L, Lp, B, gbnw, gbnb, share);
+}
+template <int LEADS>
+__global__ __launch_bounds__(256) void k_conv1_bwd_frozen(CONV1_BWD_ARGS) {
+  conv1_bwd_body<LEADS, true>(dy, a0, x, ss, bnw, bst, count, gw, gb, dzout, L, Lp, B, gbnw, gbnb, share);
+}
+#undef CONV1_BWD_ARGS
 
 // dx[b][c][l] = sum_o sum_k w[o][c][k] dz[b][l-k+1][o]   (input gradient of the stem, 12-lead adapter only)
 template <int LEADS>
@@ -1940,6 +1958,13 @@ void launch_conv1_bwd(int leads, const float* dy, const float* a0, const float* 
   const int grid = ew_grid((size_t)B * Lp, 1024);
   if (leads == 1) k_conv1_bwd<1><<<grid, 256, 0, s>>>(dy, a0, x, ss, bnw, bst, count, gw, gb, dz, L, Lp, B, gbnw, gbnb, share);
   else k_conv1_bwd<2><<<grid, 256, 0, s>>>(dy, a0, x, ss, bnw, bst, count, gw, gb, dz, L, Lp, B, gbnw, gbnb, share);
+}
+
+void launch_conv1_bwd_frozen(int leads, const float* dy, const float* a0, const float* x, const float* ss, const float* bnw,
+                             float* gw, float* gb, float* dz, int L, int Lp, int B, hipStream_t s, float* gbnw, float* gbnb) {
+  const int grid = ew_grid((size_t)B * Lp, 1024);
+  if (leads == 1) k_conv1_bwd_frozen<1><<<grid, 256, 0, s>>>(dy, a0, x, ss, bnw, nullptr, 1.0, gw, gb, dz, L, Lp, B, gbnw, gbnb, 1.0);
+  else k_conv1_bwd_frozen<2><<<grid, 256, 0, s>>>(dy, a0, x, ss, bnw, nullptr, 1.0, gw, gb, dz, L, Lp, B, gbnw, gbnb, 1.0);
 }
 
 void launch_conv1_bwd_dx(int leads, const float* dz, const float* w, float* dx, int L, int Lp, int B, hipStream_t s) {

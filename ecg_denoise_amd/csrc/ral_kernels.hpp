@@ -38,9 +38,11 @@ void launch_resample_fwd(int D, bool sep, const float* x, const float* wred, con
 void launch_add(const float* a, const float* b, float* y, size_t n, hipStream_t s);
 
 // ---- stem / head / loss / optimiser (ral_misc.hip)
+// mode 0: training (a0 + statistics sums), 1: eval (x0 from the running statistics), 2: training with frozen BatchNorm (a0 to
+// out, x0 to out2, [scale, shift, mean, rstd] of the running statistics to ss; no sums)
 void launch_conv1_fwd(int leads, int mode, const float* x, const float* w, const float* b, float* out, double* stats,
                       const float* bnw, const float* bnb, const float* rmean, const float* rvar, int L, int Lp /* token slots per window (>= L) */, int B,
-                      hipStream_t s);
+                      hipStream_t s, float* out2 = nullptr, float* ss = nullptr);
 // the stem BatchNorm of a training forward: scale / shift / mean / rstd into ss, running statistics updated, x0 = a0 * scale + shift
 void launch_bn_train8(const double* stats, double count, const float* bnw, const float* bnb, float* ss, float* rmean, float* rvar,
                       const float* a0, float* x0, size_t ntok, hipStream_t s);
@@ -103,6 +105,10 @@ void launch_bn8_bwd_stats(const float* dy, const float* a0, const float* ss, dou
 void launch_conv1_bwd(int leads, const float* dy, const float* a0, const float* x, const float* ss, const float* bnw,
                       const double* bst, double count, float* gw, float* gb, float* dz, int L, int Lp, int B, hipStream_t s,
                       float* gbnw, float* gbnb /* BatchNorm affine gradients += the backward sums x share */, double share);
+// the same under frozen BatchNorm (ss from launch_conv1_fwd mode 2): d a0 = gamma rstd dy, no sums to read; the affine
+// gradients are reduced with the conv gradients
+void launch_conv1_bwd_frozen(int leads, const float* dy, const float* a0, const float* x, const float* ss, const float* bnw,
+                             float* gw, float* gb, float* dz, int L, int Lp, int B, hipStream_t s, float* gbnw, float* gbnb);
 void launch_conv1_bwd_dx(int leads, const float* dz, const float* w, float* dx, int L, int Lp, int B, hipStream_t s);
 
 // ---- weight gradients (ral_dw.hip)

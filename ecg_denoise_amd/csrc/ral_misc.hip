@@ -31,13 +31,16 @@ RAL_DEV void block_atomic_sums(const float (&v)[NV], double* __restrict__ out, d
 // conv1: Conv1d(leads, 8, k3, p1) + LeakyReLU(0.2) -> a0 (B, L, 8) token-major.
 // MODE 0: training, also accumulates per-channel sum / sum of squares (double).
 // MODE 1: eval, applies BatchNorm with the running statistics and writes x0 directly.
+// MODE 2: training with frozen BatchNorm (option "bn_frozen"): a0 to `out` AND x0 = a0 * scale + shift to `out2`, both from the
+//         running statistics, which are only read; workgroup 0 leaves ss = [scale, shift, mean, rstd] for the backward.  No sums.
 // ---------------------------------------------------------------------------------
 template <int LEADS, int MODE>
 __global__ __launch_bounds__(256) void k_conv1_fwd(const float* __restrict__ x, const float* __restrict__ w,
                                                    const float* __restrict__ bias, float* __restrict__ out,
                                                    double* __restrict__ stats, const float* __restrict__ bnw,
                                                    const float* __restrict__ bnb, const float* __restrict__ rmean,
-                                                   const float* __restrict__ rvar, int L, int Lp, int B) {
+                                                   const float* __restrict__ rvar, int L, int Lp, int B,
+                                                   float* __restrict__ out2, float* __restrict__ ss) {
   // L: samples of a window (row stride of x); Lp >= L: token slots per window in `out` (a window length that is not a multiple
   // of 256 runs on the next multiple, ral_api.hip: the slots past L are written as zeros and are not part of the statistics)
   __shared__ double red[16 * 4];
@@ -58,6 +61,15 @@ __global__ __launch_bounds__(256) void k_conv1_fwd(const float* __restrict__ x, 
       sh[o] = bnb[o] - rmean[o] * sc[o];
     }
   }
+  if (MODE == 2) {
+#pragma unroll
+    for (int o = 0; o < 8; ++o) {
+      const float mean = rmean[o], rstd = 1.0f / sqrtf(rvar[o] + 1e-5f);
+      sc[o] = bnw[o] * rstd;
+      sh[o] = bnb[o] - mean * sc[o];
+      if (blockIdx.x == 0 && threadIdx.x == 0) { ss[o] = sc[o]; ss[8 + o] = sh[o]; ss[16 + o] = mean; ss[24 + o] = rstd; }
+    }
+  }
   float acc[16];
 #pragma unroll
   for (int i = 0; i < 16; ++i) acc[i] = 0.f;
@@ -67,6 +79,10 @@ __global__ __launch_bounds__(256) void k_conv1_fwd(const float* __restrict__ x, 
     if (l >= L) {
       float4* pz = reinterpret_cast<float4*>(out + i * 8);
       pz[0] = make_float4(0.f, 0.f, 0.f, 0.f); pz[1] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (MODE == 2) {
+        float4* pz2 = reinterpret_cast<float4*>(out2 + i * 8);
+        pz2[0] = make_float4(0.f, 0.f, 0.f, 0.f); pz2[1] = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
       continue;
     }
     float xv[LEADS][3];
@@ -77,7 +93,7 @@ __global__ __launch_bounds__(256) void k_conv1_fwd(const float* __restrict__ x, 
       xv[c][1] = xr[l];
       xv[c][2] = l < L - 1 ? xr[l + 1] : 0.f;
     }
-    float y[8];
+    float y[8], y2[8];
 #pragma unroll
     for (int o = 0; o < 8; ++o) {
       float a = br[o];
@@ -87,12 +103,18 @@ __global__ __launch_bounds__(256) void k_conv1_fwd(const float* __restrict__ x, 
         for (int k = 0; k < 3; ++k) a = fmaf(wr[o][c][k], xv[c][k], a);
       a = a > 0.f ? a : 0.2f * a;
       if (MODE == 0) { acc[o] += a; acc[8 + o] += a * a; }
-      else a = a * sc[o] + sh[o];
+      else if (MODE == 1) a = a * sc[o] + sh[o];
+      else y2[o] = a * sc[o] + sh[o];
       y[o] = a;
     }
     float4* po = reinterpret_cast<float4*>(out + i * 8);
     po[0] = make_float4(y[0], y[1], y[2], y[3]);
     po[1] = make_float4(y[4], y[5], y[6], y[7]);
+    if (MODE == 2) {
+      float4* po2 = reinterpret_cast<float4*>(out2 + i * 8);
+      po2[0] = make_float4(y2[0], y2[1], y2[2], y2[3]);
+      po2[1] = make_float4(y2[4], y2[5], y2[6], y2[7]);
+    }
   }
   if (MODE == 0) block_atomic_sums<16>(acc, stats, red);
 }
@@ -306,14 +328,15 @@ static inline int ew_grid(size_t n, int per = 256) {
 
 void launch_conv1_fwd(int leads, int mode, const float* x, const float* w, const float* b, float* out, double* stats,
                       const float* bnw, const float* bnb, const float* rmean, const float* rvar, int L, int Lp, int B,
-                      hipStream_t s) {
+                      hipStream_t s, float* out2, float* ss) {
   // training: every workgroup ends with 16 double atomics on the same 16 addresses (~15 ns per link of a same-address
   // chain): 4096 workgroups were a 56 us kernel for 38 MB of traffic, 512 are an 18 us one
   const int grid = ew_grid((size_t)B * Lp, mode == 0 ? 2048 : 256);
 #define CASE(ld)                                                                                             \
   case ld:                                                                                                   \
-    if (mode == 0) k_conv1_fwd<ld, 0><<<grid, 256, 0, s>>>(x, w, b, out, stats, bnw, bnb, rmean, rvar, L, Lp, B); \
-    else k_conv1_fwd<ld, 1><<<grid, 256, 0, s>>>(x, w, b, out, stats, bnw, bnb, rmean, rvar, L, Lp, B);           \
+    if (mode == 0) k_conv1_fwd<ld, 0><<<grid, 256, 0, s>>>(x, w, b, out, stats, bnw, bnb, rmean, rvar, L, Lp, B, nullptr, nullptr); \
+    else if (mode == 1) k_conv1_fwd<ld, 1><<<grid, 256, 0, s>>>(x, w, b, out, stats, bnw, bnb, rmean, rvar, L, Lp, B, nullptr, nullptr); \
+    else k_conv1_fwd<ld, 2><<<grid, 256, 0, s>>>(x, w, b, out, stats, bnw, bnb, rmean, rvar, L, Lp, B, out2, ss);    \
     break;
   switch (leads) { CASE(1) CASE(2) }
 #undef CASE

@@ -230,6 +230,10 @@ struct RalModel : ral_handle {
   const float* last_x = nullptr;
   int last_B = 0;
   bool last_training = false;   // the last forward kept what a backward pass reads (lse, x1, u_pre, batch statistics)
+  // option "bn_frozen": a training forward normalises with the running statistics and leaves them alone (fine-tuning; the
+  // BatchNorm is a per-channel affine map, its backward has no mean terms).  fwd_frozen: what the last training forward did -
+  // the backward must find the option as that forward left ss
+  bool bn_frozen = false, fwd_frozen = false;
   int dw_ksplit[5] = {256, 256, 256, 256, 256};
   // optional in-library kernel timing (bench.py roofline leg): hipEvent pairs around the
   // launches of ONE selected kernel kind, on the stream the kernels run on
@@ -466,6 +470,7 @@ static int fwd_begin(RalModel* m, const float* x, int B, int training, hipStream
   if (training && !m->bn_sums) return ral_fail("training forward needs bn_sums bound");
   const RalOff& Y = m->off;
   m->last_x = x; m->last_B = B; m->last_training = training != 0;
+  m->fwd_frozen = training && m->bn_frozen;
   m->prep_fwd = m->prep_bwd = false;
   m->prep_stale = false;
   m->skip_prep = !training && m->static_params && m->planes_valid;
@@ -491,8 +496,12 @@ static int fwd_begin(RalModel* m, const float* x, int B, int training, hipStream
   if (training) {
     if (!m->sums_clean) HIP_OK(hipMemsetAsync(m->bn_sums, 0, 64 * sizeof(double), s));
     m->sums_clean = false;
-    launch_conv1_fwd(m->cfg.leads, 0, x, m->params + Y.conv1_w, m->params + Y.conv1_b, m->a0, m->bn_sums, nullptr,
-                     nullptr, nullptr, nullptr, m->L, m->Lp, B, s);
+    if (m->fwd_frozen)   // (nothing adds to the sums: they stay zero for whoever all-reduces them)
+      launch_conv1_fwd(m->cfg.leads, 2, x, m->params + Y.conv1_w, m->params + Y.conv1_b, m->a0, nullptr, m->params + Y.bn_w,
+                       m->params + Y.bn_b, m->state, m->state + 8, m->L, m->Lp, B, s, m->ten[RT_X0], m->ss);
+    else
+      launch_conv1_fwd(m->cfg.leads, 0, x, m->params + Y.conv1_w, m->params + Y.conv1_b, m->a0, m->bn_sums, nullptr,
+                       nullptr, nullptr, nullptr, m->L, m->Lp, B, s);
   } else {
     launch_conv1_fwd(m->cfg.leads, 1, x, m->params + Y.conv1_w, m->params + Y.conv1_b, m->ten[RT_X0], nullptr,
                      m->params + Y.bn_w, m->params + Y.bn_b, m->state, m->state + 8, m->L, m->Lp, B, s);
@@ -503,7 +512,7 @@ static int fwd_begin(RalModel* m, const float* x, int B, int training, hipStream
 static int fwd_end(RalModel* m, float* y, int B, int64_t global_windows, int training, hipStream_t s) {
   sched_reset();
   const RalOff& Y = m->off;
-  if (training) {
+  if (training && !m->fwd_frozen) {
     launch_bn_train8(m->bn_sums, (double)global_windows * m->L, m->params + Y.bn_w, m->params + Y.bn_b, m->ss,
                      m->state, m->state + 8, m->a0, m->ten[RT_X0], (size_t)B * m->Lp, s);
   }
@@ -636,6 +645,7 @@ static int bwd_begin(RalModel* m, const float* dy, int B, hipStream_t s) {
   if (!m->grads || !m->bn_sums) return ral_fail("ral_bind: grads / bn_sums not bound");
   if (B != m->last_B) return ral_fail("backward batch %d != forward batch %d", B, m->last_B);
   if (!m->last_training) return ral_fail("RA-LENet backward must follow a training forward: the last forward was an eval one");
+  if (m->fwd_frozen != m->bn_frozen) return ral_fail("RA-LENet backward: bn_frozen changed since the last forward (run the forward again)");
   const RalOff& Y = m->off;
   launch_zero_bwd(m->grads, (size_t)m->lay.nparam, m->bn_sums + 32, 32, m->gmax, 18 * 4 * 4, s);   // gradient buffer, backward BatchNorm sums, gradient maxima
   const bool prep_ok = m->prep_bwd && !m->prep_stale;
@@ -692,7 +702,7 @@ static int bwd_begin(RalModel* m, const float* dy, int B, hipStream_t s) {
       EV(hipStreamWaitEvent(LS->l[k].s, LS->l[k].ev_join, 0));
     }
   join_lanes(m, s);
-  launch_bn8_bwd_stats(m->gbuf[ralenet_grad_of(RT_X0)], m->a0, m->ss, m->bn_sums + 32, (size_t)B * m->Lp, s);
+  if (!m->fwd_frozen) launch_bn8_bwd_stats(m->gbuf[ralenet_grad_of(RT_X0)], m->a0, m->ss, m->bn_sums + 32, (size_t)B * m->Lp, s);
   HIP_OK(hipGetLastError());
   if (short_scratch) return ral_fail("attention backward: the workspace scratch is smaller than a plan needs (ral_create checks it: the ATTN_* switches changed since?)");
   return sched_check();
@@ -701,9 +711,14 @@ static int bwd_begin(RalModel* m, const float* dy, int B, hipStream_t s) {
 static int bwd_end(RalModel* m, float* dx, int B, int64_t global_windows, hipStream_t s) {
   sched_reset();
   const RalOff& Y = m->off;
-  launch_conv1_bwd(m->cfg.leads, m->gbuf[ralenet_grad_of(RT_X0)], m->a0, m->last_x, m->ss, m->params + Y.bn_w, m->bn_sums + 32,
-                   (double)global_windows * m->L, m->grads + Y.conv1_w, m->grads + Y.conv1_b, dx ? m->dz0 : nullptr,
-                   m->L, m->Lp, B, s, m->grads + Y.bn_w, m->grads + Y.bn_b, (double)B / (double)global_windows);
+  if (m->fwd_frozen)   // (per-window constants: the sums over this rank's windows are this rank's whole share)
+    launch_conv1_bwd_frozen(m->cfg.leads, m->gbuf[ralenet_grad_of(RT_X0)], m->a0, m->last_x, m->ss, m->params + Y.bn_w,
+                            m->grads + Y.conv1_w, m->grads + Y.conv1_b, dx ? m->dz0 : nullptr, m->L, m->Lp, B, s,
+                            m->grads + Y.bn_w, m->grads + Y.bn_b);
+  else
+    launch_conv1_bwd(m->cfg.leads, m->gbuf[ralenet_grad_of(RT_X0)], m->a0, m->last_x, m->ss, m->params + Y.bn_w, m->bn_sums + 32,
+                     (double)global_windows * m->L, m->grads + Y.conv1_w, m->grads + Y.conv1_b, dx ? m->dz0 : nullptr,
+                     m->L, m->Lp, B, s, m->grads + Y.bn_w, m->grads + Y.bn_b, (double)B / (double)global_windows);
   if (dx) launch_conv1_bwd_dx(m->cfg.leads, m->dz0, m->params + Y.conv1_w, dx, m->L, m->Lp, B, s);
   HIP_OK(hipEventRecord(m->ev_bwd_done, s));
   m->bwd_recorded = true;
@@ -873,6 +888,11 @@ double* RalModel::after_adam() {
 
 int RalModel::set_option(const char* key, int value) {
   RalModel* const m = this;
+  if (!strcmp(key, "bn_frozen")) {   // (no arithmetic of the transformer stack depends on it: the weight planes stay valid)
+    if (value != 0 && value != 1) return ral_fail("option bn_frozen must be 0 or 1 (got %d)", value);
+    m->bn_frozen = value != 0;
+    return 0;
+  }
   m->prep_stale = true;   // (weight planes queued by a forward were formed for the options of that moment)
   m->planes_valid = false;
   if (!strcmp(key, "static_params")) { m->static_params = value != 0; return 0; }   // (setting it again = "the parameters have changed")

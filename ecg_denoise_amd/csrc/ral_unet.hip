@@ -46,6 +46,7 @@ struct Stage {
   double count_a, count_b, count_r;
   // backward
   const float* Gout; const double* bsums_out; const float* gamma_out; int type;
+  const float* running_out;   // frozen BatchNorm (the FROZEN kernel forms): running mean[cout], var[cout] of this stage's output
   float* gw; float* gb;
   float* part; int64_t part_stride; int part_w, part_b;   // per-workgroup gradient partial rows (null: atomics into gw / gb)
   int nrep;             // replicas of every record this stage ADDS to (sums_out forward; a / b / r .bsums backward) and of
@@ -684,8 +685,13 @@ __global__ __launch_bounds__(64 * UOL_WAVES) void k_unet_out_loss(Src s, float* 
 // backward stage
 // LDS: in tile | dconv tile (cout x lout) | d_in tile (cin x lin) | weights | coeffs a,b,r,out | sums a,b,r (2*MAXC each) | gb
 // ---------------------------------------------------------------------------------
+// FROZEN (option "bn_frozen"): every BatchNorm is the constant affine map of its running statistics.  The gradient at a conv
+// output is gamma * rstd * G - no mean(G), mean(G zhat) terms, so the output's two records are not read -, and the sums a
+// stage leaves for its producers (S1 = sum G, S2 = sum G zhat, zhat from the running statistics: the operands arrive with
+// NORM_RUNNING) serve the affine gradients alone.
 #define UNET_MAXW 12   // weight-gradient entries per thread (3072 / 256)
-__global__ __launch_bounds__(256) void k_unet_bwd(Stage st, int B) {
+template <bool FROZEN>
+RAL_DEV void unet_bwd_body(const Stage& st, int B) {
   extern __shared__ float4 smem4[];
   const int nin = st.cin * st.lin, nout = st.cout * st.lout, nw = st.cin * st.cout * st.ks;
   float* in = reinterpret_cast<float*>(smem4);
@@ -702,15 +708,16 @@ __global__ __launch_bounds__(256) void k_unet_bwd(Stage st, int B) {
   if (st.r.z) src_coeffs(st.r, st.cout, st.count_r, cr);
   // BN-backward coefficients of THIS stage's output: co_[c] = gamma*rstd, [C+c] = S1/n, [2C+c] = S2/n, mean/rstd after
   if (st.type != TY_PLAIN) {
-    Src o; o.norm = NORM_BATCH; o.sums = st.sums_out; o.nrep = 1; o.gamma = st.gamma_out; o.beta = st.gamma_out; o.act = ACT_NONE;
+    Src o; o.norm = FROZEN ? NORM_RUNNING : NORM_BATCH; o.sums = st.sums_out; o.running = st.running_out; o.nrep = 1;
+    o.gamma = st.gamma_out; o.beta = st.gamma_out; o.act = ACT_NONE;
     float* tmp = gbs + MAXC;  // 4*MAXC scratch
     src_coeffs(o, st.cout, st.count, tmp);
     __shared__ double brec[64];
-    fold_record(st.bsums_out, st.nrep, brec);
+    if (!FROZEN) fold_record(st.bsums_out, st.nrep, brec);
     for (int c = threadIdx.x; c < st.cout; c += blockDim.x) {
       co_[c] = st.gamma_out[c] * tmp[3 * st.cout + c];
-      co_[MAXC + c] = (float)(brec[c] / st.count);
-      co_[2 * MAXC + c] = (float)(brec[MAXC + c] / st.count);
+      co_[MAXC + c] = FROZEN ? 0.f : (float)(brec[c] / st.count);
+      co_[2 * MAXC + c] = FROZEN ? 0.f : (float)(brec[MAXC + c] / st.count);
       co_[3 * MAXC + c] = tmp[2 * st.cout + c];                         // mean
       gbs[5 * MAXC + c] = tmp[3 * st.cout + c];                          // rstd
     }
@@ -735,7 +742,7 @@ __global__ __launch_bounds__(256) void k_unet_bwd(Stage st, int B) {
       if (st.type != TY_PLAIN) {
         const float zo = st.out[(size_t)win * nout + i];
         const float zh = (zo - co_[3 * MAXC + c]) * gbs[5 * MAXC + c];
-        g = co_[c] * (g - co_[MAXC + c] - zh * co_[2 * MAXC + c]);
+        g = FROZEN ? co_[c] * g : co_[c] * (g - co_[MAXC + c] - zh * co_[2 * MAXC + c]);
         if (st.type == TY_ABN) g = zo > 0.f ? g : 0.01f * g;   // stored tensor is lrelu(conv)
       }
       dc[i] = g;
@@ -852,6 +859,9 @@ __global__ __launch_bounds__(256) void k_unet_bwd(Stage st, int B) {
   }
 }
 
+__global__ __launch_bounds__(256) void k_unet_bwd(Stage st, int B) { unet_bwd_body<false>(st, B); }
+__global__ __launch_bounds__(256) void k_unet_bwd_frozen(Stage st, int B) { unet_bwd_body<true>(st, B); }
+
 // ---------------------------------------------------------------------------------
 // backward stage, specialised (same template parameters as k_unet_fwd_t).  A workgroup takes WP consecutive windows
 // per pass (one pass at the launch sizes used) and touches global memory in ONE batched load phase:
@@ -872,8 +882,8 @@ __global__ __launch_bounds__(256) void k_unet_bwd(Stage st, int B) {
 // (st.part: workgroups x parameters), folded by k_unet_fold after the last stage - no global atomics except the 2 x C
 // BatchNorm-backward sums the NEXT stage needs.  (st.part == nullptr: atomics straight into the gradient buffer.)
 // ---------------------------------------------------------------------------------
-template <int CIN, int COUT, int KS, int MODE>
-__global__ __launch_bounds__(UNET_BWD_THREADS, 2) void k_unet_bwd_t(Stage st, int B, int WP) {
+template <int CIN, int COUT, int KS, int MODE, bool FROZEN>
+RAL_DEV void unet_bwd_t_body(const Stage& st, int B, int WP) {
   extern __shared__ float4 smem4[];
   UB_STAMP_INIT();
   constexpr int HALO = 4, nw = CIN * COUT * KS, NT = UNET_BWD_THREADS, NWAVE = NT / 64;
@@ -898,11 +908,13 @@ __global__ __launch_bounds__(UNET_BWD_THREADS, 2) void k_unet_bwd_t(Stage st, in
   double* gbs = sr + 2 * MAXC;                   // MAXC bias grads
   // every global load of the prologue is requested before the first is waited for: the BatchNorm records and affine
   // parameters of the operands and of this stage's output (forward statistics and backward sums) and the weights
-  Src o; o.norm = st.type != TY_PLAIN ? NORM_BATCH : NORM_NONE; o.sums = st.sums_out; o.nrep = 1; o.gamma = st.gamma_out; o.beta = st.gamma_out; o.act = ACT_NONE;
+  Src o; o.norm = st.type != TY_PLAIN ? (FROZEN ? NORM_RUNNING : NORM_BATCH) : NORM_NONE; o.sums = st.sums_out; o.running = st.running_out;
+  o.nrep = 1; o.gamma = st.gamma_out; o.beta = st.gamma_out; o.act = ACT_NONE;
   const SrcReq la = src_request(st.a, CIN, st.w), lb = src_request(has_b ? st.b : st.a, CIN, st.w),
                lr = src_request(st.r.z ? st.r : st.a, st.r.z ? COUT : CIN, st.w), lo = src_request(o, COUT, st.w);
   const FoldPick fp = fold_pick(src_rec(st.a), st.a.nrep, has_b ? src_rec(st.b) : nullptr, st.b.nrep, st.r.z ? src_rec(st.r) : nullptr, st.r.nrep,
-                                st.type != TY_PLAIN ? st.sums_out : nullptr, 1, st.type != TY_PLAIN ? st.bsums_out : nullptr, st.nrep, st.w);
+                                (!FROZEN && st.type != TY_PLAIN) ? st.sums_out : nullptr, 1,
+                                (!FROZEN && st.type != TY_PLAIN) ? st.bsums_out : nullptr, st.nrep, st.w);
   const FoldLd fl = fold_load(fp.rec, fp.nrep);        // (wave w: record w)
   constexpr int NWV = (nw / 4 + NT - 1) / NT;
   float4 wv[NWV];
@@ -934,17 +946,25 @@ __global__ __launch_bounds__(UNET_BWD_THREADS, 2) void k_unet_bwd_t(Stage st, in
   if (st.type != TY_PLAIN) {   // BN-backward coefficients of this stage's output, by thread group 3
     const int c = (int)threadIdx.x - 192;
     if (c >= 0 && c < COUT) {
-      const double* rec = fold_rec(3);
-      const double* brec = fold_rec(4);
-      const double m = rec[c] / st.count;
-      double var = rec[MAXC + c] / st.count - m * m;
-      if (var < 0.0) var = 0.0;
-      const float rstd = (float)(1.0 / sqrt(var + 1e-5));
-      co_[c] = lo.gamma * rstd;                                          // gamma * rstd
-      co_[MAXC + c] = (float)(brec[c] / st.count);                       // mean(G)
-      co_[2 * MAXC + c] = (float)(brec[MAXC + c] / st.count);            // mean(G * zhat)
-      co_[3 * MAXC + c] = (float)m;                                      // mean
-      co_[4 * MAXC + c] = rstd;                                          // rstd
+      if (FROZEN) {   // (the running statistics: constants, no terms of the batch)
+        const float rstd = 1.0f / sqrtf(lo.rvar + 1e-5f);
+        co_[c] = lo.gamma * rstd;
+        co_[MAXC + c] = 0.f; co_[2 * MAXC + c] = 0.f;
+        co_[3 * MAXC + c] = lo.rmean;
+        co_[4 * MAXC + c] = rstd;
+      } else {
+        const double* rec = fold_rec(3);
+        const double* brec = fold_rec(4);
+        const double m = rec[c] / st.count;
+        double var = rec[MAXC + c] / st.count - m * m;
+        if (var < 0.0) var = 0.0;
+        const float rstd = (float)(1.0 / sqrt(var + 1e-5));
+        co_[c] = lo.gamma * rstd;                                          // gamma * rstd
+        co_[MAXC + c] = (float)(brec[c] / st.count);                       // mean(G)
+        co_[2 * MAXC + c] = (float)(brec[MAXC + c] / st.count);            // mean(G * zhat)
+        co_[3 * MAXC + c] = (float)m;                                      // mean
+        co_[4 * MAXC + c] = rstd;                                          // rstd
+      }
     }
   }
   __syncthreads();
@@ -1029,7 +1049,7 @@ __global__ __launch_bounds__(UNET_BWD_THREADS, 2) void k_unet_bwd_t(Stage st, in
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const float zh = (zz[j] - mu) * rs;
-          float v = k * (g[j] - m1 - zh * m2);
+          float v = FROZEN ? k * g[j] : k * (g[j] - m1 - zh * m2);
           if (st.type == TY_ABN && zz[j] <= 0.f) v *= 0.01f;   // stored tensor is lrelu(conv)
           g[j] = v;
         }
@@ -1253,6 +1273,11 @@ __global__ __launch_bounds__(UNET_BWD_THREADS, 2) void k_unet_bwd_t(Stage st, in
   }
   UB_STAMP(21);
 }
+// (the default kernels keep their names in a kernel trace; the frozen-BatchNorm forms are kernels of their own)
+template <int CIN, int COUT, int KS, int MODE>
+__global__ __launch_bounds__(UNET_BWD_THREADS, 2) void k_unet_bwd_t(Stage st, int B, int WP) { unet_bwd_t_body<CIN, COUT, KS, MODE, false>(st, B, WP); }
+template <int CIN, int COUT, int KS, int MODE>
+__global__ __launch_bounds__(UNET_BWD_THREADS, 2) void k_unet_bwd_t_frozen(Stage st, int B, int WP) { unet_bwd_t_body<CIN, COUT, KS, MODE, true>(st, B, WP); }
 
 // Fold of the per-workgroup weight / bias gradient partials (rows x stride scratch matrix written by k_unet_bwd_t) into the
 // gradient buffer: a workgroup owns 64 consecutive columns of the conv-parameter column list `cols`, its four waves take a
@@ -1736,6 +1761,9 @@ struct UNetModel : ral_handle {
   int gsums_nrep = 0;               // ... spread over this many replicas (unet_backward_start then skips k_unet_gsums)
   int last_B = 0;
   bool last_training = false;       // the last forward (either eval path included) left z[] and the batch records of a training pass
+  // option "bn_frozen": a training forward normalises with the running statistics and leaves them alone; the backward pass then
+  // runs the FROZEN stage kernels.  fwd_frozen: what the last training forward did (stage 0 decides for the whole pass)
+  bool bn_frozen = false, fwd_frozen = false;
   // weight / bias gradient partials of the backward stage kernels: one row of `part_stride` floats (the flat parameter
   // layout) per workgroup, folded by k_unet_fold; `cols` = the flat offsets of all conv weights and biases
   float* part = nullptr; int64_t part_stride = 0; int part_rows_max = 0;
@@ -1752,6 +1780,11 @@ struct UNetModel : ral_handle {
   int backward(const float* dy, float* dx, int B, hipStream_t s) override;
   int set_option(const char* key, int value) override {
     if (!strcmp(key, "unet_fused")) { fused = value != 0; return 0; }   // eval forward as one kernel (default 1)
+    if (!strcmp(key, "bn_frozen")) {
+      if (value != 0 && value != 1) return ral_fail("U-Net option bn_frozen must be 0 or 1 (got %d)", value);
+      bn_frozen = value != 0;
+      return 0;
+    }
     return ral_fail("unknown U-Net option %s", key);
   }
 };
@@ -1834,9 +1867,11 @@ const RalKind* unet_kind() {
 int unet_stage_bn(int si) { return (si >= 0 && si < UNET_STAGES) ? unet_stages(1)[si].bn : -1; }
 
 // BatchNorm record bi of a pass that adds to nrep replicas: dir 0 the forward sums, 1 the backward sums.  nrep > 1: the
-// replicas in the workspace; 1: the record itself, halves [0, 64) / [64, 128) of the caller's 128 doubles
+// replicas in the workspace; 1: the record itself, halves [0, 64) / [64, 128) of the caller's 128 doubles.  Frozen BatchNorm:
+// the backward sums feed the affine gradients only and nobody all-reduces them, so they stay in the workspace whatever nrep
+// (replica 0 .. nrep - 1) and bn_sums keeps its zeros
 static double* bn_record(UNetModel* m, int dir, int bi, int nrep) {
-  if (nrep > 1) return m->rep + ((size_t)(dir * 10 + bi) * UNET_MAXREP) * 64;
+  if (nrep > 1 || m->fwd_frozen) return m->rep + ((size_t)(dir * 10 + bi) * UNET_MAXREP) * 64;
   return m->bn_sums ? m->bn_sums + 128 * bi + 64 * dir : nullptr;
 }
 
@@ -1886,6 +1921,7 @@ static Stage make_stage(UNetModel* m, int si, const float* x, bool training, boo
   operand(g.a, s.a, s.count_a); operand(g.b, s.b, s.count_b); operand(g.r, s.r, s.count_r);
   if (bwd) {
     s.Gout = si == 10 ? m->last_dy : m->G[si];   // the gradient at the output BatchNorm is the caller's dy itself
+    s.running_out = g.bn >= 0 ? m->state + Y.run[g.bn] : nullptr;
     s.bsums_out = g.bn >= 0 ? bn_record(m, 1, g.bn, nrep) : nullptr;
     s.gamma_out = g.bn >= 0 ? m->params + Y.bnw[g.bn] : nullptr;
     s.gw = m->grads + Y.w[si]; s.gb = m->grads + Y.b[si];
@@ -1916,6 +1952,17 @@ static void launch_unet_bwd(const UStageLaunch& p, const Stage& st, int B, hipSt
     default: unet_launch_missing("launch_unet_bwd", p);
   }
 }
+// the frozen-BatchNorm form of the planned kernel: same grid, workgroup and LDS
+static void launch_unet_bwd_frozen(const UStageLaunch& p, const Stage& st, int B, hipStream_t s) {
+  switch (p.kernel) {
+    case K::BWD: RAL_SET_LDS(k_unet_bwd_frozen, p.lds); k_unet_bwd_frozen<<<p.grid, p.threads, p.lds, s>>>(st, B); break;
+#define T(ci, co, k, md) case K::BWD_T_##ci##_##co##_##k##_##md: RAL_SET_LDS((k_unet_bwd_t_frozen<ci, co, k, md>), p.lds); \
+      k_unet_bwd_t_frozen<ci, co, k, md><<<p.grid, p.threads, p.lds, s>>>(st, B, p.windows_per_pass); break;
+    UNET_T_INSTANCES(T)
+#undef T
+    default: unet_launch_missing("launch_unet_bwd_frozen", p);
+  }
+}
 // the fused eval forward: a persistent grid of exactly the workgroups that are resident at once (a grid one LDS granule too
 // optimistic runs its surplus workgroups as a second round: measured 76 us instead of 45 us at batch 2048)
 template <int LEADS>
@@ -1939,7 +1986,11 @@ int unet_forward_stage(UNetModel* m, const float* x, int B, int training, int si
   if (training && (!m->cfg.train || !m->bn_sums)) return ral_fail("training forward needs train=1 and bn_sums");
   if (si == 0) {
     m->last_x = x; m->last_B = B; m->gsums_dy = nullptr; m->last_training = training != 0;
-    if (training) {
+    m->fwd_frozen = training && m->bn_frozen;
+    if (m->fwd_frozen) {
+      // (no statistics this step: the records the pass would have filled are left as zeros for whoever all-reduces them)
+      (void)hipMemsetAsync(m->bn_sums, 0, 1280 * sizeof(double), s);
+    } else if (training) {
       // (one fill for both halves of the replica records: the backward pass of this step finds its half zeroed)
       if (nrep > 1) {
         if (!m->rep_all_clean) (void)hipMemsetAsync(bn_record(m, 0, 0, nrep), 0, (size_t)2 * 10 * UNET_MAXREP * 64 * sizeof(double), s);
@@ -1948,8 +1999,11 @@ int unet_forward_stage(UNetModel* m, const float* x, int B, int training, int si
       else (void)hipMemsetAsync(m->bn_sums, 0, 1280 * sizeof(double), s);
     }
   } else if (x != m->last_x || B != m->last_B) return ral_fail("U-Net stages must follow stage 0 of the same batch");
-  Stage st = make_stage(m, si, x, training != 0, false, (double)gwin, nrep);
-  if (!training) st.sums_out = nullptr;
+  // frozen BatchNorm: the operands arrive through the running statistics and no sums leave, as in an eval forward; what a
+  // stage writes - the pre-BatchNorm tensors the backward reads - is the same in every mode
+  const bool batch_stats = training && !m->fwd_frozen;
+  Stage st = make_stage(m, si, x, batch_stats, false, (double)gwin, nrep);
+  if (!batch_stats) st.sums_out = nullptr;
   launch_unet_fwd(unet_stage_plan(m->cfg.leads, m->cfg.L, B, training != 0, false, si), st, B, s);
   if (hipGetLastError() != hipSuccess) return ral_fail("U-Net forward launch failed");
   return 0;
@@ -1968,12 +2022,13 @@ static BnUpdAll bn_updates(UNetModel* m, bool training, double gwin, int nrep) {
 
 int unet_forward_finish(UNetModel* m, float* y, int B, int training, int64_t gwin, hipStream_t s, int nrep) {
   if (B != m->last_B) return ral_fail("finish batch %d != stage batch %d", B, m->last_B);
-  Src o = make_src(m, 10, ACT_NONE, training != 0, false, 0, nrep);
+  const bool batch_stats = training && !m->fwd_frozen;
+  Src o = make_src(m, 10, ACT_NONE, batch_stats, false, 0, nrep);
   const size_t total = (size_t)B * m->C[10] * m->Ln[10];
   // (the running update reads the layers' complete records: every stage kernel has finished; the output layer's record is
   // read by this kernel's own coefficient fold, not written)
   k_unet_out<<<(int)((total / 4 + 255) / 256 < 1024 ? (total / 4 + 255) / 256 : 1024), 256, 0, s>>>(
-      o, y, m->C[10], m->Ln[10], (double)gwin * m->Ln[10], total, bn_updates(m, training != 0, (double)gwin, nrep), training ? 1 : 0);
+      o, y, m->C[10], m->Ln[10], (double)gwin * m->Ln[10], total, bn_updates(m, batch_stats, (double)gwin, nrep), batch_stats ? 1 : 0);
   if (hipGetLastError() != hipSuccess) return ral_fail("U-Net forward launch failed");
   return 0;
 }
@@ -1984,7 +2039,7 @@ static int unet_forward_fused(UNetModel* m, const UStageLaunch& p, const float* 
   if (!m->params || !m->state) return ral_fail("ral_bind was not called");
   if (B <= 0 || B > m->cfg.max_batch) return ral_fail("batch %d outside (0, %d]", B, m->cfg.max_batch);
   // (this kernel leaves z[] and the records alone, the stage-by-stage eval path does not: one rule for both, whatever L)
-  m->last_x = x; m->last_B = B; m->gsums_dy = nullptr; m->last_training = false;
+  m->last_x = x; m->last_B = B; m->gsums_dy = nullptr; m->last_training = false; m->fwd_frozen = false;
   UPackArgs a;
   a.params = m->params; a.state = m->state; a.pk = m->pack; a.leads = m->cfg.leads;
   for (int i = 0; i < 11; ++i) { a.w[i] = m->off.w[i]; a.b[i] = m->off.b[i]; }
@@ -2015,7 +2070,7 @@ int UNetModel::forward(const float* x, float* y, int B, int training, hipStream_
 // the backward of its consumers (stages > si, and unet_backward_start for the last layer) has accumulated ----
 // the ten backward halves [64, 128) of the 128-double BatchNorm records, one strided fill
 static void unet_zero_bwd_records(UNetModel* m, int nrep, hipStream_t s) {
-  if (nrep > 1) {
+  if (nrep > 1 || m->fwd_frozen) {   // (frozen: the sums live in the workspace, see bn_record)
     if (!m->rep_bwd_clean) (void)hipMemsetAsync(bn_record(m, 1, 0, nrep), 0, (size_t)10 * UNET_MAXREP * 64 * sizeof(double), s);
     m->rep_bwd_clean = false; m->rep_all_clean = false;
   } else (void)hipMemset2DAsync(m->bn_sums + 64, 128 * sizeof(double), 0, 64 * sizeof(double), 10, s);
@@ -2031,14 +2086,15 @@ int unet_forward_loss(UNetModel* m, const float* x, const float* target, float* 
   constexpr int nrep = UNET_MAXREP;
   for (int si = 0; si < UNET_STAGES; ++si)
     if (unet_forward_stage(m, x, B, 1, si, B, s, nrep)) return -1;
-  Src o = make_src(m, 10, ACT_NONE, true, false, 0, nrep);
+  const bool batch_stats = !m->fwd_frozen;   // (stage 0 has decided)
+  Src o = make_src(m, 10, ACT_NONE, batch_stats, false, 0, nrep);
   unet_zero_bwd_records(m, nrep, s);
   const int C = m->C[10], L = m->Ln[10], n = C * L;
   constexpr int gmax = 256;   // (as k_loss_w's grid, ral_misc.hip)
   const int g = (B + UOL_WAVES - 1) / UOL_WAVES;
   k_unet_out_loss<<<g < gmax ? g : gmax, 64 * UOL_WAVES, 0, s>>>(o, y, target, dy, snr, rmse, loss_sum, C, L, B, (double)B * L,
                                                                (float)(2.0 / ((double)B * n)), fin, fin_scale, fin3,
-                                                               bn_updates(m, true, (double)B, nrep), bn_record(m, 1, 9, nrep), nrep);
+                                                               bn_updates(m, batch_stats, (double)B, nrep), bn_record(m, 1, 9, nrep), nrep);
   m->gsums_dy = dy; m->gsums_nrep = nrep;
   if (hipGetLastError() != hipSuccess) return ral_fail("U-Net forward launch failed");
   return 0;
@@ -2048,6 +2104,7 @@ int unet_backward_start(UNetModel* m, const float* dy, int B, int64_t gwin, hipS
   if (!m->cfg.train || !m->grads || !m->bn_sums) return ral_fail("backward needs train=1, grads and bn_sums bound");
   if (B != m->last_B) return ral_fail("backward batch %d != forward batch %d", B, m->last_B);
   if (!m->last_training) return ral_fail("U-Net backward must follow a training forward: the last forward was an eval one");
+  if (m->fwd_frozen != m->bn_frozen) return ral_fail("U-Net backward: bn_frozen changed since the last forward (run the forward again)");
   // with the fold every gradient entry is WRITTEN by k_unet_fold; the atomic path accumulates into a zeroed buffer
   if (!m->fold) (void)hipMemsetAsync(m->grads, 0, (size_t)m->lay.nparam * sizeof(float), s);
   // dy == NULL: "the gradient unet_forward_loss wrote, untouched" - its sums are already in the output layer's backward record.
@@ -2065,7 +2122,7 @@ int unet_backward_start(UNetModel* m, const float* dy, int B, int64_t gwin, hipS
   if (have_sums) return 0;
   unet_zero_bwd_records(m, nrep, s);
   const size_t total = (size_t)B * m->C[10] * m->Ln[10];
-  Src o = make_src(m, 10, ACT_NONE, true, false, 0, 1);   // (the forward pass has folded its records)
+  Src o = make_src(m, 10, ACT_NONE, !m->fwd_frozen, false, 0, 1);   // (the forward pass has folded its records)
   const size_t grows = (total / m->Ln[10] + 3) / 4;      // one wave per (window, channel) row
   k_unet_gsums<<<(int)(grows < 512 ? grows : 512), 256, 0, s>>>(dy, o, m->C[10], m->Ln[10], (double)gwin * m->Ln[10], bn_record(m, 1, 9, nrep), nrep, total);
   if (hipGetLastError() != hipSuccess) return ral_fail("U-Net backward launch failed");
@@ -2078,25 +2135,31 @@ int unet_backward_stage(UNetModel* m, int B, int si, int64_t gwin, hipStream_t s
   if (m->last_dy == nullptr) return ral_fail("U-Net backward stages must follow ral_unet_backward_start");
   const UStageLaunch p = unet_stage_plan(m->cfg.leads, m->cfg.L, B, true, true, si);
   m->bwd_rows = p.grid;                           // (the same for every stage of a backward pass: it depends on B only)
-  launch_unet_bwd(p, make_stage(m, si, m->last_x, true, true, (double)gwin, nrep), B, s);
+  if (m->fwd_frozen) launch_unet_bwd_frozen(p, make_stage(m, si, m->last_x, false, true, (double)gwin, nrep), B, s);
+  else launch_unet_bwd(p, make_stage(m, si, m->last_x, true, true, (double)gwin, nrep), B, s);
   if (hipGetLastError() != hipSuccess) return ral_fail("U-Net backward launch failed");
   return 0;
 }
 
 int unet_backward_finish(UNetModel* m, int B, int64_t gwin, hipStream_t s, int nrep) {
+  // (frozen: the sums are this rank's own and stay in the workspace - nothing to leave in bn_sums, the whole of them is the share)
+  const bool frozen = m->fwd_frozen;
+  const double share = frozen ? 1.0 : (double)B / (double)gwin;
   BnGradAll u;
-  for (int bi = 0; bi < 10; ++bi)
-    u.l[bi] = BnGrad{bn_record(m, 1, bi, nrep), m->bn_sums + 128 * bi + 64, m->grads + m->off.bnw[bi], m->grads + m->off.bnb[bi], m->off.bnC[bi], nrep};
+  for (int bi = 0; bi < 10; ++bi) {
+    double* const rec = bn_record(m, 1, bi, nrep);
+    u.l[bi] = BnGrad{rec, frozen ? rec : m->bn_sums + 128 * bi + 64, m->grads + m->off.bnw[bi], m->grads + m->off.bnb[bi], m->off.bnC[bi], nrep};
+  }
   if (m->fold) {
     if (m->bwd_rows <= 0) return ral_fail("U-Net backward finish without its stages");
     const bool reps = nrep > 1;
     k_unet_fold<<<(m->ncols + m->npad + 63) / 64 + 1, 64 * UNET_FOLD_WAVES, 0, s>>>(m->part, m->part_stride, m->bwd_rows, m->cols, m->ncols,
                                                                                   m->ncols + m->npad, m->grads, u,
-                                                        (double)B / (double)gwin, reps ? bn_record(m, 0, 0, nrep) : nullptr,
+                                                        share, reps ? bn_record(m, 0, 0, nrep) : nullptr,
                                                         reps ? 2 * 10 * UNET_MAXREP * 64 : 0);
     if (reps) m->rep_all_clean = true;
   } else {
-    k_unet_bn_grads<<<10, MAXC, 0, s>>>(u, (double)B / (double)gwin);
+    k_unet_bn_grads<<<10, MAXC, 0, s>>>(u, share);
   }
   m->last_dy = nullptr;
   if (hipGetLastError() != hipSuccess) return ral_fail("U-Net backward launch failed");

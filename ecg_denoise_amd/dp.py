@@ -47,8 +47,7 @@ class HipEngineAdapter:
         self.y = torch.empty_like(self.x)
         self._lib.check(self._lib.lib().ral_forward_end(self.m.eng.h, self._ptr(self.y), self.x.shape[0],
                                                         global_windows, self._stream()))
-        for k in self.m.eng.counters:
-            self.m.eng.counters[k] += 1
+        self.m._count_batch()
         return self.y
 
     def loss(self, pred, target, global_windows):
@@ -121,8 +120,7 @@ class UNetEngineAdapter:
                 yield self.bn_sums[128 * bn:128 * bn + 64]
         self.pred = torch.empty_like(self.x)
         self._lib.check(L.ral_unet_forward_finish(h, self._ptr(self.pred), B, 1, global_windows, self._stream()))
-        for k in self.m.eng.counters:
-            self.m.eng.counters[k] += 1
+        self.m._count_batch()
 
     def loss(self, pred, target, global_windows):
         return self.m.loss_and_metrics(pred, target, True, global_windows)
@@ -185,8 +183,7 @@ class NewRALEEngineAdapter:
         r = torch.empty_like(self.a2)
         self._lib.check(self._lib.lib().ral_forward_end(self.inner.eng.h, self._ptr(r), self.a2.shape[0], global_windows,
                                                         self._stream()))
-        for k in self.inner.eng.counters:
-            self.inner.eng.counters[k] += 1
+        self.inner._count_batch()
         return self.m._forward_post(r)
 
     def loss(self, pred, target, global_windows):

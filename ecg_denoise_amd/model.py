@@ -145,11 +145,13 @@ class _AutogradMixin:
 
 class _ModuleBase(_AutogradMixin):
     VARIANT = None
+    _bn_frozen = False      # freeze_bn()
 
     def __init__(self, variant, leads=2, L=512, max_batch=32, train=True, device="cuda:0", seed=None, autograd=False):
         self.param_gen = 0     # host-side parameter generation: bumped whenever the parameters may have changed
         self.eng = _Engine(variant, leads, L, max_batch, train, device)
         self.training = bool(train)
+        self._bn_frozen = False
         self.step_count = 0
         self._dy = None
         self._loss_sum = None
@@ -178,6 +180,30 @@ class _ModuleBase(_AutogradMixin):
 
     def eval(self):
         return self.train(False)
+
+    # ---- fine-tuning with frozen BatchNorm statistics ------------------------------
+    def freeze_bn(self, flag=True):
+        """torch's `bn.eval()` with autograd on (library option "bn_frozen"): while set, a training-mode forward normalises with
+        the stored running statistics and leaves them - and every `num_batches_tracked` - alone; the BatchNorm affines and all
+        other parameters still train.  The training-mode model is then the function `eval()` runs, which is what a model
+        fine-tuned on a handful of windows is used as.  A property of the model, not of its mode or its weights: it survives
+        `train()` / `eval()` and `load_state_dict`.  `freeze_bn(False)` is training from scratch again (batch statistics)."""
+        _lib.check(_lib.lib().ral_set_option(self.eng.h, b"bn_frozen", 1 if flag else 0))
+        self._bn_frozen = bool(flag)
+        return self
+
+    @property
+    def bn_frozen(self):
+        return self._bn_frozen
+
+    def _count_batch(self, match=None):
+        """one training forward has gone through the BatchNorms (those whose counter name contains `match`): their
+        `num_batches_tracked` advance - unless the statistics are frozen, as torch leaves them in eval mode"""
+        if self._bn_frozen:
+            return
+        for k in self.eng.counters:
+            if match is None or match in k:
+                self.eng.counters[k] += 1
 
     def cuda(self, device=None):
         return self
@@ -304,8 +330,7 @@ class _ModuleBase(_AutogradMixin):
         self._dy_fused = False   # (the sums `forward_loss` left for `backward()` belonged to the previous forward)
         _lib.check(_lib.lib().ral_forward(self.eng.h, _ptr(x), _ptr(y), x.shape[0], int(self.training), _stream()))
         if self.training:
-            for k in self.eng.counters:
-                self.eng.counters[k] += 1
+            self._count_batch()
         return y
 
     def _backward_raw(self, dy, want_dx):
@@ -364,8 +389,7 @@ class _ModuleBase(_AutogradMixin):
             self._loss_scratch = torch.zeros(64, dtype=torch.float64, device=x.device)
         _lib.check(_lib.lib().ral_forward_loss_means(self.eng.h, _ptr(x), _ptr(target), _ptr(y), B, _ptr(dy), _ptr(snr), _ptr(rmse),
                                                      _ptr(means), _ptr(self._loss_scratch), _stream()))
-        for k in self.eng.counters:
-            self.eng.counters[k] += 1
+        self._count_batch()
         self._means = means
         self._dy = dy
         self._dy_fused = True
@@ -450,6 +474,9 @@ class ACDAE(_ModuleBase):
     def __init__(self, L=512, max_batch=32, train=True, device="cuda:0", seed=None, autograd=False):
         super().__init__("acdae", 2, L, max_batch, train, device, seed, autograd)
 
+    def freeze_bn(self, flag=True):
+        return self   # no BatchNorm: nothing to freeze
+
 
 class DANet(_ModuleBase):
     """model/DAM.py::Seq2Seq2 (main.py:67-68, test_cls.py:81-83), the "DANet" the reference compares against: four
@@ -461,6 +488,11 @@ class DANet(_ModuleBase):
 
     def __init__(self, L=512, max_batch=32, train=True, device="cuda:0", seed=None, leads=2, autograd=False):
         super().__init__("danet", leads, L, max_batch, train, device, seed, autograd)      # (2 output channels: leads must be 2)
+
+    def freeze_bn(self, flag=True):
+        if flag:
+            raise _lib.RalError("DANet: frozen BatchNorm statistics (freeze_bn) are not provided for its 36 BatchNorms")
+        return self
 
     def named_parameters(self):
         for k, v in super().named_parameters():
@@ -480,27 +512,33 @@ class DANet(_ModuleBase):
     def _forward_raw(self, x):
         y = super()._forward_raw(x)
         if self.training:
-            for k in self.eng.counters:
-                if ".dam.fcn" in k:
-                    self.eng.counters[k] += 1   # the second batch through the shared fcn
+            self._count_batch(match=".dam.fcn")   # the second batch through the shared fcn
         return y
 
 
 class NewRALE(_AutogradMixin):
     """model/ralenet_12leads.py::newrale — 12-lead adapter around a pretrained, frozen RA-LENet
     (Transfer_learning.py:71-75): Conv1d 12->6->2 (k13, LeakyReLU 0.01), RA-LENet, Conv1d 2->6->12.
-    Only the 2 210 adapter parameters train; the inner model keeps running in whatever mode
-    `.train()` sets, so its BatchNorm still uses and updates batch statistics (reference quirk A16)."""
+    Only the 2 210 adapter parameters train.
+
+    freeze_bn=False (default) reproduces the reference's quirk A16: the inner model keeps running in whatever mode
+    `.train()` sets, so during adapter training its BatchNorm normalises with batch statistics and keeps updating its running
+    ones - a model that inference (`eval()`, `StreamingDenoiser`, `NewRALELivePool`) never runs.
+    freeze_bn=True calls `freeze_bn()` on the inner model: it normalises with its stored running statistics and leaves them
+    alone, so the adapter is fitted to exactly the inner function inference runs.  This is the one that matches inference; it
+    deviates from the reference's training."""
 
     SHAPES = OrderedDict([("conv1.weight", (6, 12, 13)), ("conv1.bias", (6,)), ("conv2.weight", (2, 6, 13)),
                           ("conv2.bias", (2,)), ("conv3.weight", (6, 2, 13)), ("conv3.bias", (6,)),
                           ("conv4.weight", (12, 6, 13)), ("conv4.bias", (12,))])
 
-    def __init__(self, pretrained_rale_model, seed=None, autograd=False):
+    def __init__(self, pretrained_rale_model, seed=None, autograd=False, freeze_bn=False):
         self.rale = pretrained_rale_model
         self.enable_autograd(autograd)
         if self.rale.eng.leads != 2:
             raise _lib.RalError("newrale wraps a 2-lead RA-LENet")
+        if freeze_bn:
+            self.rale.freeze_bn(True)
         self.device, self.L = self.rale.eng.device, self.rale.eng.L
         self.off, cur = OrderedDict(), 0
         for k, shp in self.SHAPES.items():
@@ -531,6 +569,14 @@ class NewRALE(_AutogradMixin):
 
     def eval(self):
         return self.train(False)
+
+    def freeze_bn(self, flag=True):
+        self.rale.freeze_bn(flag)
+        return self
+
+    @property
+    def bn_frozen(self):
+        return self.rale.bn_frozen
 
     def cuda(self, device=None):
         return self

@@ -11,6 +11,8 @@
 Differences on purpose: metrics come out of the fused loss kernel ((B,) tensors, no autograd graph
 kept alive — reference quirk A10), the progress-bar loss is not divided by the batch size (A12), and
 `model_path` really resumes (the reference rebinds `model` to load_state_dict's return value, A11).
+`freeze_bn` (not in the reference): True / False calls `model.freeze_bn(...)` before the first epoch - fine-tuning with the
+stored BatchNorm statistics (model.py::freeze_bn); None leaves the model as it is.
 """
 import os
 
@@ -22,7 +24,7 @@ def _to_dev(t, device):
     return t.to(device, non_blocking=True).contiguous()
 
 
-def train(epochs, model, batch_size, train_loader, test_loader, use_gpu=True, model_path=None, *args, **kwargs):
+def train(epochs, model, batch_size, train_loader, test_loader, use_gpu=True, model_path=None, *args, freeze_bn=None, **kwargs):
     model_name = kwargs["model_name"]
     noise_name, noise_intensity = kwargs["noise_name"], kwargs["noise_intensity"]
     out_dir = kwargs.get("out_dir", ".")
@@ -33,6 +35,8 @@ def train(epochs, model, batch_size, train_loader, test_loader, use_gpu=True, mo
     device = model.eng.device if hasattr(model, "eng") else model.device      # NewRALE wraps an engine-backed model
     if model_path:
         model.load_state_dict(torch.load(model_path, map_location="cpu"))
+    if freeze_bn is not None:
+        model.freeze_bn(bool(freeze_bn))
     train_snr_list, test_snr_list, train_rmse_list, test_rmse_list = [], [], [], []
     train_loss_list, eval_loss_list = [], []
     for epoch in range(epochs):
