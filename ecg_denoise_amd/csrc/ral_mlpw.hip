@@ -673,6 +673,9 @@ __global__ __launch_bounds__(256, RAL_MLPW_WPE) void k_mlp_bwd_w(const float* __
       const float u0 = rows_sum(u0p) + b1[0], da0 = rows_sum(d0p);       // u[tok, 0], da2[tok, 0]
       float A0, dA;
       gelu_pair(u0, A0, dA);
+      // the value from gelu_f, like the halo tokens' hA0 and the forward: the pair formula's 1.5e-7 ABSOLUTE error in Phi is a
+      // relative 1e-5 .. 1e-4 of A0 at u0 = -2.5 .. -3.5, and the conv weight gradient (gle*) is built from A0 alone
+      A0 = gelu_f(u0);
       const float sm1 = dpp_shift<0x111>(A0), sp1 = dpp_shift<0x101>(A0);   // row_shr:1 / row_shl:1
       const float Am = r == 0 ? hA0[1] : sm1, Ap = r == 15 ? hA0[2] : sp1;   // A0 of tokens tok - 1, tok + 1
       float c0g, c0d;
@@ -1096,6 +1099,9 @@ __global__ __launch_bounds__(128 * RAL_MLPW2_NP, 2) void k_mlp_bwd_w2(const floa
       const float u0 = rows_sum(u0p) + b1[0], da0 = rows_sum(d0p);       // u[tok, 0], da2[tok, 0]
       float A0, dA;
       gelu_pair(u0, A0, dA);
+      // the value from gelu_f, like the halo tokens' hA0 and the forward: the pair formula's 1.5e-7 ABSOLUTE error in Phi is a
+      // relative 1e-5 .. 1e-4 of A0 at u0 = -2.5 .. -3.5, and the conv weight gradient (gle*) is built from A0 alone
+      A0 = gelu_f(u0);
       const float sm1 = dpp_shift<0x111>(A0), sp1 = dpp_shift<0x101>(A0);   // row_shr:1 / row_shl:1
       const float Am = r == 0 ? hA0[1] : sm1, Ap = r == 15 ? hA0[2] : sp1;   // A0 of tokens tok - 1, tok + 1
       float c0g, c0d;

@@ -1,6 +1,8 @@
 """Shared helpers of the GPU parity tests: run the HIP path and the CPU oracle on the
 same seeded inputs and report relative L2 errors per tensor."""
+import functools
 from collections import OrderedDict
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -55,9 +57,9 @@ def oracle_trace(p, x, variant, bn, dtype=torch.float64):
     return out, tr
 
 
-def make_case(variant, leads, L, B, seed=1234, dtype=torch.float64):
+def make_case(variant, leads, L, B, seed=1234, dtype=torch.float64, input_seed=2023):
     p32 = O.init_params(O.ralenet_param_shapes(variant, leads), seed)
-    g = torch.Generator().manual_seed(2023)
+    g = torch.Generator().manual_seed(input_seed)
     x = torch.randn(B, leads, L, generator=g)
     tgt = torch.randn(B, leads, L, generator=g)
     return p32, x, tgt
@@ -81,15 +83,175 @@ def compare_grads(ng, p, grads):
     return gerr
 
 
-def run_parity(variant, leads, L, B, device="cuda:0", trace=True, seed=1234, options=None, eval_forward=False, before_forward=None):
+STEM_MARGIN = 1e-5          # the smallest |stem pre-activation| a parity case may have (about 100 roundings of an O(1) sum)
+
+
+def stem_margin(variant, leads, L, B, seed=1234, params=None, input_seed=2023):
+    """the smallest |stem pre-activation| of the case in fp64: its distance from the kink of the stem's LeakyReLU(0.2)"""
+    import torch.nn.functional as F
+    p32, x, _ = make_case(variant, leads, L, B, seed, input_seed=input_seed)
+    if params is not None:
+        p32 = params(p32)
+    return F.conv1d(x.double(), p32["conv1.0.weight"].double(), p32["conv1.0.bias"].double(), padding=1).abs().min().item()
+
+
+def oracle_step(variant, leads, L, B, seed=1234, params=None, dtype=torch.float64, gelu=None, input_seed=2023):
+    return _oracle_step(variant, leads, L, B, seed, params, dtype, gelu, input_seed)
+
+
+@functools.lru_cache(maxsize=8)
+def _oracle_step(variant, leads, L, B, seed, params, dtype, gelu, input_seed):
+    """One train step and the eval forward after it in the oracle alone, in `dtype`, on make_case's parameters (through `params`,
+    a callable p32 -> p32, when given) and inputs.  `gelu` stands in for O.gelu during the call (the mutants of
+    tests/test_parity_bars_cpu.py).  Cached and shared between run_parity and parity_yardstick: read-only for every caller.
+    -> namespace: p (leaves), bn (state after the step), y, tr (oracle_trace's tensors), loss, snr, rmse, grads (in the order
+    of p, None where unused), dx, y_eval."""
+    p32, x, tgt = make_case(variant, leads, L, B, seed, input_seed=input_seed)
+    if params is not None:
+        p32 = params(p32)
+    p = OrderedDict((k, v.to(dtype).requires_grad_(True)) for k, v in p32.items())
+    bn = O.new_bn_state(8, dtype)
+    xo = x.to(dtype).requires_grad_(True)
+    t = tgt.to(dtype)
+    keep = O.gelu
+    if gelu is not None:
+        O.gelu = gelu
+    try:
+        yo, tr = oracle_trace(p, xo, variant, bn)
+        lo = O.mse(yo, t)
+        *grads, dxo = torch.autograd.grad(lo, list(p.values()) + [xo], allow_unused=True)
+        p = OrderedDict((k, v.detach()) for k, v in p.items())
+        with torch.no_grad():
+            y_eval = O.ralenet_forward(p, x.to(dtype), variant, training=False, bn=bn)
+    finally:
+        O.gelu = keep
+    yo = yo.detach()
+    return SimpleNamespace(p=p, bn=bn, y=yo, tr=OrderedDict((k, v.detach()) for k, v in tr.items()), loss=lo.detach(),
+                           snr=O.snr(t, yo), rmse=O.rmse(t, yo), grads=grads, dx=dxo, y_eval=y_eval)
+
+
+def oracle_parity(variant, leads, L, B, seed=1234, params=None, eval_forward=False, trace=True, gelu=None, input_seed=2023):
+    """run_parity with the fp32 oracle (torch on the CPU, fp32 leaves and BatchNorm state) in the place of the HIP path: the same
+    keys, each the relative error of the fp32 evaluation against the fp64 one.  `grad:input_frozen` and the `@dx` stem gradients
+    repeat `grad:input` and the stem gradients (the oracle has one backward pass).  `gelu` replaces O.gelu in the fp32
+    evaluation only."""
+    a = oracle_step(variant, leads, L, B, seed, params, torch.float32, gelu, input_seed)
+    o = oracle_step(variant, leads, L, B, seed, params, torch.float64, None, input_seed)
+    res = OrderedDict()
+    res["y"] = rel(a.y.numpy(), o.y.numpy())
+    res["loss"] = abs(a.loss.item() - o.loss.item()) / abs(o.loss.item())
+    res["snr"] = rel(a.snr.numpy(), o.snr.numpy())
+    res["rmse"] = rel(a.rmse.numpy(), o.rmse.numpy())
+    res["bn_mean"] = rel(a.bn["running_mean"].numpy(), o.bn["running_mean"].numpy())
+    res["bn_var"] = rel(a.bn["running_var"].numpy(), o.bn["running_var"].numpy())
+    if trace:
+        for k, v in o.tr.items():
+            res["act:" + k] = rel(a.tr[k].numpy(), v.numpy())
+    ng = OrderedDict((k, torch.zeros_like(a.p[k]) if g is None else g) for k, g in zip(a.p, a.grads))
+    res.update(compare_grads(ng, o.p, o.grads))
+    res["grad:input"] = rel(a.dx.numpy(), o.dx.numpy())
+    stem = [k for k in o.p if k.startswith(("conv1.0.", "conv1.2."))]
+    res.update(("grad:" + k + "@dx", res["grad:" + k]) for k in stem)
+    res["grad:input_frozen"] = res["grad:input"]
+    if eval_forward:
+        res["y_eval"] = rel(a.y_eval.numpy(), o.y_eval.numpy())
+    return res
+
+
+THREE_SEEDS = (2023, 2024, 2025)
+
+
+def parity_yardstick(variant, leads, L, B, seed=1234, params=None, eval_forward=False, trace=True, input_seeds=THREE_SEEDS):
+    """What fp32 arithmetic itself costs, per tensor: a dict with the keys of run_parity(variant, leads, L, B, ...)'s result,
+    each value rel(fp32 oracle, fp64 oracle) of that tensor on the same seeded parameters and inputs (oracle_parity).  It is
+    the oracle's error, never the kernels'.  `gradabs:*` keys and gradients whose fp64 norm is <= 1e-12 get None: a quantity whose
+    true value is zero has no relative yardstick, and keeps its flat absolute bar.
+
+    One fp32 evaluation is a single sample of each tensor's rounding error, and torch's summation order follows the thread
+    count: the three-element `leconv.partial_conv3.weight` gradients came out between 1.1e-7 and 5.5e-7 for the same case at 16
+    threads and at 1, the nearly cancelling attention query gradients of the spread cases vary fivefold from one input to the
+    next - and the strict f16_split = 0 path, whose summation order is its own, sat 8.5 to 8.6 times above such a sample.  So the
+    yardstick is the largest of three fp32 evaluations, each against its own fp64 one, on inputs from the seeds `input_seeds`:
+    2023 (the case's own), 2024 and 2025; the parameters stay.  parity_bars floors it at its group's median besides.
+
+    Precondition: the stem's LeakyReLU(0.2) is the one kink of RA-LENet, and an fp32 pre-activation on the other side of 0
+    from the fp64 one changes gradients by a discrete amount no yardstick describes - the smallest |stem pre-activation| of the
+    case (fp64) must be >= STEM_MARGIN."""
+    assert input_seeds[0] == 2023
+    margin = stem_margin(variant, leads, L, B, seed, params)
+    assert margin >= STEM_MARGIN, (variant, leads, L, B, margin)
+    o = oracle_step(variant, leads, L, B, seed, params, torch.float64)
+    yard = oracle_parity(variant, leads, L, B, seed, params, eval_forward, trace)
+    for s in input_seeds[1:]:
+        # (the other inputs are no parity case and owe no margin: it is enough that no fp32 pre-activation changed sides)
+        a0, a1 = (oracle_step(variant, leads, L, B, seed, params, dt, None, s).tr["a0"] for dt in (torch.float32, torch.float64))
+        assert torch.equal(a0 > 0, a1 > 0), (variant, leads, L, B, s)
+        more = oracle_parity(variant, leads, L, B, seed, params, eval_forward, trace, None, s)
+        yard = OrderedDict((k, max(v, more[k])) for k, v in yard.items())
+    zero = {k for k, g in zip(o.p, o.grads) if g is None or g.norm().item() <= 1e-12}
+    for k in yard:
+        if k.startswith("gradabs:") or (k.startswith("grad:") and k[5:].split("@")[0] in zero):
+            yard[k] = None
+    return yard
+
+
+def _group(key):
+    return 1 if key.startswith("grad:") else 0
+
+
+def yardstick_floors(yard):
+    """-> (median of the non-None yardsticks of the forward group, of the gradient group)"""
+    return tuple(float(np.median([v for k, v in yard.items() if v is not None and _group(k) == g])) for g in (0, 1))
+
+
+def parity_bars(yard, K=8.0, flat=(1e-5, 1e-4), capped=True):
+    """One bar per key of `yard`: min(flat bar of the key's group, K * max(yard[key], median of yard over the group)); the
+    groups are the gradients (`grad:*`, flat[1]) and everything else (flat[0]).  A key without a yardstick (None) has the flat bar.
+
+    K = 8: the design lets an fp16-pair product be 2^-21 relative where fp32 rounds at 2^-24 (csrc/ral_device.hpp, DESIGN.md
+    section 4), so a tensor may carry 2^3 times the error of an fp32 evaluation and no more.  The median floor: the smallest
+    single samples (4.5e-8 .. 1e-7, at small tensors) say little about the tensor's typical rounding error.  The min keeps every
+    bar at or below the flat one; `capped=False` drops it, for cases whose tensors are ill conditioned in fp32 itself (the
+    yardstick of such a tensor is above the flat bar, and so is what any fp32 kernel can reach)."""
+    floors = yardstick_floors(yard)
+    bars = OrderedDict()
+    for k, v in yard.items():
+        g = _group(k)
+        if v is None:
+            bars[k] = flat[g]
+        else:
+            bars[k] = K * max(v, floors[g])
+            if capped:
+                bars[k] = min(flat[g], bars[k])
+    return bars
+
+
+def spread_fc1_bias(p32, lim=9.0, seed=5):
+    """Every `*.mlp.fc1.bias` (H = 32 .. 512 hidden units) becomes torch.linspace(-lim, lim, H) in a seeded random order; the
+    fc1 weights stay, so the GELU arguments are this grid plus each token's own fc1 output: dense over [-lim - 1, lim + 1], where
+    the seeded parameters alone keep them below 3."""
+    g = torch.Generator().manual_seed(seed)
+    out = OrderedDict(p32)
+    for k, v in p32.items():
+        if k.endswith(".mlp.fc1.bias"):
+            H = v.numel()
+            out[k] = torch.linspace(-lim, lim, H, dtype=v.dtype)[torch.randperm(H, generator=g)]
+    return out
+
+
+def run_parity(variant, leads, L, B, device="cuda:0", trace=True, seed=1234, options=None, eval_forward=False, before_forward=None,
+               params=None):
     """-> dict of relative errors (HIP fp32 vs fp64 oracle).  `options`: {name: value} for ral_set_option on the model's handle,
-    applied before the first forward.  `eval_forward`: after the train step, the eval-mode forward of the same model against
+    applied before the first forward.  `params`: a callable p32 -> p32 applied to the seeded parameters before the model and the
+    oracle see them (spread_fc1_bias).  `eval_forward`: after the train step, the eval-mode forward of the same model against
     the oracle's eval output (its BatchNorm on the running statistics the step left) as res["y_eval"].  `before_forward(model)`
     is called once the options are set.  Gradients: every parameter gradient of `backward()` (dx = NULL, the training default);
     then res["grad:input"] and the stem parameter gradients "grad:<name>@dx" of `backward(want_dx=True)`, and
     res["grad:input_frozen"] of `backward_input` - the model comes back with the gradient buffer that last call left."""
     from ecg_denoise_amd import RALENet, _lib
     p32, x, tgt = make_case(variant, leads, L, B, seed)
+    if params is not None:
+        p32 = params(p32)
     model = RALENet(variant, leads=leads, L=L, max_batch=B, train=True, device=device)
     model.load_state_dict(p32, strict=False)
     for key, value in (options or {}).items():
@@ -102,13 +264,9 @@ def run_parity(variant, leads, L, B, device="cuda:0", trace=True, seed=1234, opt
     loss, snr, rmse = model.loss_and_metrics(y, td)
     model.backward()
     torch.cuda.synchronize()
-    # fp64 oracle (x is a leaf: the input gradient comes out of the same autograd call)
-    p = OrderedDict((k, v.double().requires_grad_(True)) for k, v in p32.items())
-    bn = O.new_bn_state(8, torch.float64)
-    xo = x.double().requires_grad_(True)
-    yo, tr = oracle_trace(p, xo, variant, bn)
-    lo = O.mse(yo, tgt.double())
-    *grads, dxo = torch.autograd.grad(lo, list(p.values()) + [xo], allow_unused=True)
+    # fp64 oracle (x is a leaf: the input gradient comes out of the same autograd call); shared with parity_yardstick
+    o = oracle_step(variant, leads, L, B, seed, params, torch.float64)
+    p, bn, yo, tr, lo, grads, dxo = o.p, o.bn, o.y, o.tr, o.loss, o.grads, o.dx
     res = OrderedDict()
     res["y"] = rel(y.cpu().numpy(), yo.detach().numpy())
     res["loss"] = abs(loss.item() - lo.item()) / abs(lo.item())
@@ -138,9 +296,7 @@ def run_parity(variant, leads, L, B, device="cuda:0", trace=True, seed=1234, opt
         model.eval()
         ye = model(xd)
         torch.cuda.synchronize()
-        with torch.no_grad():
-            yeo = O.ralenet_forward(OrderedDict((k, v.detach()) for k, v in p.items()), x.double(), variant, training=False, bn=bn)
-        res["y_eval"] = rel(ye.cpu().numpy(), yeo.numpy())
+        res["y_eval"] = rel(ye.cpu().numpy(), o.y_eval.numpy())
         model.train()
     return res, model, (p32, x, tgt)
 

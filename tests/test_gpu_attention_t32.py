@@ -16,6 +16,7 @@ from ecg_denoise_amd import _lib
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 TOL = 2e-5
+MODEL_CASE = ("full", 1, 512, 4)          # (variant, leads, L, B) of the whole-model train step
 
 
 def _vp(t):
@@ -176,13 +177,12 @@ def test_t32_forward_keeps_non_finite_values_in_their_head():
 
 
 def test_t32_whole_model_train_step_matches_oracle():
-    """forward + backward of RA-LENet "full" at 4 x 1 x 512 against the fp64 oracle, at the parity tolerances of
+    """forward + backward of RA-LENet "full" at 4 x 1 x 512 against the fp64 oracle, at the per-tensor parity bars of
     test_gpu_parity.py (the backward reads the o and lse this forward wrote)"""
-    from parity_util import run_parity
-    res, _, _ = run_parity("full", 1, 512, 4, DEV, trace=False)
-    bad = {k: v for k, v in res.items()
-           if v > (1e-5 if k.startswith("gradabs:") else 1e-4 if k.startswith("grad:") else 1e-5)}
-    assert not bad, bad
+    from parity_util import parity_yardstick, run_parity
+    from test_gpu_parity import _check
+    res, _, _ = run_parity(*MODEL_CASE, DEV, trace=False)
+    _check(res, parity_yardstick(*MODEL_CASE, trace=False), what="t32 %s leads=%d L=%d B=%d" % MODEL_CASE)
 
 
 @pytest.mark.parametrize("opts", ["attn_fwd_t32=0", "attn_fwd_t32=64"])

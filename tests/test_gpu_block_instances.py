@@ -13,8 +13,11 @@ the oracle.  The ones the other files leave are here:
   * k_mlp_fwd_w<8 | 16 | 32>, the fp32 strip forward, in eval mode (MLP_FWD_W = 2; the parity tests run it in training only).
 
 Every case is a whole train step (outputs, loss, metrics, BatchNorm statistics, every block output, every parameter gradient) and
-the eval-mode forward of the same model, through parity_util.run_parity, at the bars of tests/test_gpu_parity.py: forward 1e-5,
-gradients 1e-4, the key-bias half 1e-5 absolute.  Before its forward a case asks ral_block_plan - same process, same switches -
+the eval-mode forward of the same model, through parity_util.run_parity, at the bars of tests/test_gpu_parity.py: per tensor 8 times
+its error in the fp32 oracle (parity_util.parity_yardstick), never above forward 1e-5 and gradients 1e-4; the key-bias half 1e-5
+absolute.  The two `-spread` twins run the same instances with the fc1 biases a grid over [-9, 9] (parity_util.spread_fc1_bias),
+in every process their originals run in: every MLP forward and backward family - k_mlp_fwd_h, k_mlp_fwd_w, the fused strips,
+k_mlp_bwd, k_mlp_bwd_h - evaluates its GELU and the GELU's derivative across [-10, 10], not only below 3.  Before its forward a case asks ral_block_plan - same process, same switches -
 whether the instances it exists for are in the plan of its model, so a case that stops reaching its kernel fails here too.  B is odd
 where a level packs two windows into a 64-token group: the ragged last group is on the path.  FUSE_DW and MLP_FWD_W latch at their first read, so
 the cases that need them run in a pytest process of their own (RAL_TEST_OPTIONS, tests/conftest.py).
@@ -39,14 +42,18 @@ and the eighteen block outputs; gradient: the worst relative L2 over the paramet
   full-L256-B3-split64   mlp_fwd_w=2              6.9e-7    2.2e-6
 
 The worst forward figure is a block output each time (the model output: 1.7e-7 .. 3.1e-7, eval 2.0e-7 .. 3.6e-7); the C = 32 pair
-path sits where the default path does (tests/test_gpu_parity.py: 2e-7 / 2e-6), far below the bars."""
+path sits where the default path does (tests/test_gpu_parity.py: 2e-7 / 2e-6).  Over the per-tensor yardstick (the table of
+tests/test_gpu_parity.py explains the columns) the worst tensor of these cases, in every process, is at 1.0 .. 2.3 in the forward
+group (2.3: blk5.out under mlp_fwd_w=2) and at 1.8 .. 3.6 among the gradients - in the twins at 3.8 .. 7.2, an attention query
+gradient of dtransformer2.1 or dtransformer3.0 each time (7.2: f16_split=32,fuse_dw=0) - the medians at 0.7 .. 1.6 and
+0.9 .. 1.6, where the bar is 8."""
 import os
 import subprocess
 import sys
 
 import pytest
 
-from parity_util import run_parity
+from parity_util import parity_yardstick, run_parity, spread_fc1_bias
 from test_block_plan_cpu import DW, MB, MBH, MFH, MFW, QBH, QH, model_instances
 from test_gpu_parity import DEV, _check
 
@@ -56,31 +63,37 @@ _DW32H = [name % "true" for name in DW[32]]
 _C32_BWD_256 = [MBH % (32, 1, 512)] + _DW32H          # (32, 64) off the fused backward: eight waves, split products
 _C32_BWD_512 = [MBH % (32, 4, 256)] + _DW32H          # (32, 128): four waves
 
-# (variant, L, B, f16_split, {option string of the process: the instances the case exists for under it})
+_SPLIT32_256 = {"": [QH % 32, MFH % (32, 1, 512), QBH % 32], "f16_split=32,fuse_dw=0": _C32_BWD_256, "f16_split=32,fuse_dw=16": _C32_BWD_256}
+_SPLIT64_256 = {"fuse_dw=0": [MB % (8, 1), MB % (16, 1)], "fuse_dw=8": [MB % (16, 1)], "mlp_fwd_w=2": [MFW % 8, MFW % 16, MFW % 32]}
+
+# (variant, L, B, f16_split, {option string of the process: the instances the case exists for under it}, spread: the fc1 biases a
+# grid over [-9, 9] - parity_util.spread_fc1_bias)
 CASES = [
-    pytest.param("full", 256, 3, 32, {"": [QH % 32, MFH % (32, 1, 512), QBH % 32],
-                                      "f16_split=32,fuse_dw=0": _C32_BWD_256, "f16_split=32,fuse_dw=16": _C32_BWD_256}, id="full-L256-B3-split32"),
+    pytest.param("full", 256, 3, 32, _SPLIT32_256, False, id="full-L256-B3-split32"),
     pytest.param("full", 512, 3, 32, {"": [MFH % (32, 2, 512)],
-                                      "f16_split=32,fuse_dw=0": _C32_BWD_512, "f16_split=32,fuse_dw=16": _C32_BWD_512}, id="full-L512-B3-split32"),
-    pytest.param("full", 768, 2, 32, {"": [MFH % (32, 4, 512)]}, id="full-L768-B2-split32"),       # level (32, 192), training too
-    pytest.param("mlp", 256, 3, 32, {"f16_split=32,fuse_dw=0": _C32_BWD_256}, id="mlp-L256-B3-split32"),   # no local-enhancement conv
-    pytest.param("full", 512, 3, 128, {}, id="full-L512-B3-split128"),
-    pytest.param("full", 256, 3, 64, {"fuse_dw=0": [MB % (8, 1), MB % (16, 1)], "fuse_dw=8": [MB % (16, 1)],
-                                      "mlp_fwd_w=2": [MFW % 8, MFW % 16, MFW % 32]}, id="full-L256-B3-split64"),
+                                      "f16_split=32,fuse_dw=0": _C32_BWD_512, "f16_split=32,fuse_dw=16": _C32_BWD_512}, False, id="full-L512-B3-split32"),
+    pytest.param("full", 768, 2, 32, {"": [MFH % (32, 4, 512)]}, False, id="full-L768-B2-split32"),       # level (32, 192), training too
+    pytest.param("mlp", 256, 3, 32, {"f16_split=32,fuse_dw=0": _C32_BWD_256}, False, id="mlp-L256-B3-split32"),   # no local-enhancement conv
+    pytest.param("full", 512, 3, 128, {}, False, id="full-L512-B3-split128"),
+    pytest.param("full", 256, 3, 64, _SPLIT64_256, False, id="full-L256-B3-split64"),
+    # the twins: the same instances with GELU arguments across [-10, 10]
+    pytest.param("full", 256, 3, 32, _SPLIT32_256, True, id="full-L256-B3-split32-spread"),
+    pytest.param("full", 256, 3, 64, _SPLIT64_256, True, id="full-L256-B3-split64-spread"),
 ]
 # the processes with latched switches: (option string, ids of the cases above it runs)
+_S32, _S64 = "full-L256-B3-split32-spread", "full-L256-B3-split64-spread"
 SWITCH_RUNS = [
-    ("f16_split=32,fuse_dw=0", ("full-L256-B3-split32", "full-L512-B3-split32", "mlp-L256-B3-split32")),
-    ("f16_split=32,fuse_dw=16", ("full-L256-B3-split32", "full-L512-B3-split32")),    # ... beside fused C = 8 / 16 strips
-    ("fuse_dw=0", ("full-L256-B3-split64",)),
-    ("fuse_dw=8", ("full-L256-B3-split64",)),
-    ("mlp_fwd_w=2", ("full-L256-B3-split64",)),      # the fp32 strips in eval mode (the parity tests run them in training only)
+    ("f16_split=32,fuse_dw=0", ("full-L256-B3-split32", "full-L512-B3-split32", "mlp-L256-B3-split32", _S32)),
+    ("f16_split=32,fuse_dw=16", ("full-L256-B3-split32", "full-L512-B3-split32", _S32)),    # ... beside fused C = 8 / 16 strips
+    ("fuse_dw=0", ("full-L256-B3-split64", _S64)),
+    ("fuse_dw=8", ("full-L256-B3-split64", _S64)),
+    ("mlp_fwd_w=2", ("full-L256-B3-split64", _S64)),      # the fp32 strips in eval mode (the parity tests run them in training only)
 ]
 NARROW_F16 = 1            # the model's default; no case changes it
 
 
-@pytest.mark.parametrize("variant,L,B,f16_split,names", CASES)
-def test_block_instances_match_oracle(variant, L, B, f16_split, names):
+@pytest.mark.parametrize("variant,L,B,f16_split,names,spread", CASES)
+def test_block_instances_match_oracle(variant, L, B, f16_split, names, spread):
     opts = os.environ.get("RAL_TEST_OPTIONS", "")
     want = set(names.get(opts, ()))
     forward = {n for n in want if n.startswith(("k_qkv_fwd", "k_mlp_fwd"))}
@@ -89,13 +102,17 @@ def test_block_instances_match_oracle(variant, L, B, f16_split, names):
         train, evalm = (model_instances(L, mode, f16_split, NARROW_F16) for mode in (1, 0))
         assert want <= train and forward <= evalm, (opts, sorted(want - train), sorted(forward - evalm))
 
-    res, _, _ = run_parity(variant, 2, L, B, DEV, options={"f16_split": f16_split}, eval_forward=True, before_forward=planned)
+    params = spread_fc1_bias if spread else None
+    res, _, _ = run_parity(variant, 2, L, B, DEV, options={"f16_split": f16_split}, eval_forward=True, before_forward=planned, params=params)
     fwd = {k: v for k, v in res.items() if not k.startswith(("grad:", "gradabs:"))}
     grad = {k: v for k, v in res.items() if k.startswith("grad:")}
     kf, kg = max(fwd, key=fwd.get), max(grad, key=grad.get)
-    print(f"\nobserved [{opts or 'default'}] {variant} L={L} B={B} f16_split={f16_split}: forward {fwd[kf]:.2e} ({kf}), "
+    what = f"[{opts or 'default'}] {variant} L={L} B={B} f16_split={f16_split}{' spread' if spread else ''}"
+    print(f"\nobserved {what}: forward {fwd[kf]:.2e} ({kf}), "
           f"y {res['y']:.2e}, y_eval {res['y_eval']:.2e}, gradient {grad[kg]:.2e} ({kg})")
-    _check(res)
+    # a twin never had flat bars: 8 x each tensor's fp32-oracle error alone (its ill-conditioned query gradients are above 1e-4
+    # in the fp32 oracle itself)
+    _check(res, parity_yardstick(variant, 2, L, B, params=params, eval_forward=True), capped=not spread, what=what)
 
 
 @pytest.mark.parametrize("opts,ids", SWITCH_RUNS, ids=[opts for opts, _ in SWITCH_RUNS])

@@ -1,9 +1,48 @@
 """Parity of the HIP path (through the C ABI) with the CPU oracle and with the golden
 vectors generated from the reference.  Needs an MI355X: `pytest -m gpu`.
 
-Tolerances (fp32 kernels vs the oracle evaluated in fp64): forward 1e-5 relative L2
-(north-star bar: 1e-3), gradients 1e-4, both far above the observed 2e-7 / 2e-6.  The gradient bar covers the input
-gradient as well (parity_util.run_parity: `grad:input`, `grad:input_frozen`, the stem gradients `@dx`; observed 2e-7 .. 4e-7)."""
+Tolerances (fp32 kernels vs the oracle evaluated in fp64, relative L2): one bar per tensor, 8 times the error of that tensor in
+the oracle evaluated in fp32 (parity_util.parity_yardstick: the yardstick, floored at the median over its group - the gradients,
+and everything else), and never above the flat bars forward 1e-5 (north-star bar: 1e-3), gradients 1e-4.  8 = 2^3: a product
+of fp16 pairs may be 2^-21 relative where fp32 rounds at 2^-24 (parity_util.parity_bars).  The typical yardstick is 2e-7 .. 7e-7,
+the worst 2e-6 .. 1.2e-5 (`leconv.partial_conv3.weight`, `conv1.0.bias`), so the typical gradient bar is 2e-6 .. 6e-6 where it
+was 1e-4.  The gradient bars cover the input gradient as well (parity_util.run_parity: `grad:input`, `grad:input_frozen`, the stem
+gradients `@dx`).  A quantity whose true value is zero keeps its flat absolute bar.  tests/test_parity_bars_cpu.py shows what the
+bars are for: a GELU wrong by a relative 2e-6 is rejected at more than 250 tensors and passes the flat bars at every one.
+
+Observed on an MI355X, as error over yardstick (the yardstick with its floor; the bar is at 8), per case the worst tensor and the
+median of the forward group (output, loss, metrics, BatchNorm statistics, block outputs where traced) and of the gradients;
+leconv.w stands for mlp.leconv.partial_conv3.weight, to_q for attn.qkv_proj.to_q:
+
+  case (variant, leads, L, B)    forward: worst     median   gradients: worst                       median
+  full, 2, 512, 4                1.00 blk13.out     0.95     3.75 transformer.0.norm1.weight        1.78
+  nra, 2, 512, 3                 1.03 p4            0.95     3.05 utransformer4.0.leconv.w          0.77
+  mlp, 2, 256, 4                 1.07 blk9.out      0.99     2.18 utranformer3.1.to_q.bias          1.22
+  full, 2, 256, 5                1.03 blk9.out      0.95     2.35 dtransformer1.1.to_q.bias         1.24
+  full, 1, 512, 2                1.02 blk13.out     0.94     1.95 dtransformer3.0.norm2.bias        1.06
+  full, 2, 1024, 2               0.98 blk13.out     0.90     4.11 dtransformer34.1.norm1.weight     1.83
+  nra, 1, 256, 1                 1.02 blk9.out      0.88     2.02 dtransformer1.1.norm1.bias        0.70
+  mlp, 2, 768, 3                 0.98 blk11.out     0.94     2.14 dtransformer34.0.to_kv.bias[v]    1.04
+  nra, 2, 128, 3                 0.97 y             0.45     2.32 dtransformer1.1.leconv.w          1.10
+  nra, 2, 320, 2                 0.96 y             0.34     3.15 utransformer2.1.leconv.w          1.05
+  full, 2, 640, 2                0.94 y             0.46     2.44 dtransformer1.0.norm2.weight      1.31
+  full, 1, 128, 5                0.97 y             0.71     2.38 dtransformer1.1.leconv.w          0.73
+  mlp, 2, 320, 3                 0.97 y             0.46     1.95 dtransformer1.0.norm1.weight      0.98
+  full, 2, 96, 2                 1.20 snr           0.64     2.64 dtransformer3.0.leconv.w          0.85
+  nra, 1, 16, 4                  0.96 y             0.59     2.47 utranformer3.1.leconv.w           0.63
+  full, 2, 1008, 1               0.91 y             0.58     5.70 utransformer4.1.leconv.w          1.50
+  full, 2, 32, 2                 1.06 y             0.59     2.55 utransformer2.1.leconv.w          0.67
+  spread full, 2, 256, 3         1.55 blk11.out     0.73     5.88 dtransformer3.0.to_q.bias         1.05
+  spread nra, 2, 256, 3          1.64 blk9.out      0.76     4.13 dtransformer3.1.to_q.bias         1.42
+  spread mlp, 2, 256, 3          1.54 blk9.out      0.75     3.03 dtransformer3.1.to_q.bias         1.09
+  spread full, 2, 96, 2          0.92 y_eval        0.52     1.71 rwattn1 table                     0.68
+  spread full, 2, 256, 3 strict  1.57 blk11.out     1.04     4.98 dtransformer3.0.to_q.weight       1.00
+
+The forward group sits at the fp32 oracle's own error, the median gradient at 0.6 .. 1.8 times it.  Under the switch strings of
+tests/test_gpu_configs.py::test_narrow_level_mlp_forward_kernel_choices the first eight cases pass as well.  With a yardstick
+from ONE fp32 evaluation the three-element leconv.w gradients did not: 8.0 .. 11.9 under mlp_fwd_w = 0 / 1 / 2 and fuse_dw = 16
+(and 8.5 for a query gradient of the spread case with f16_split = 0) - the sample, not the kernels: the same tensor's sample
+moved from 1.1e-7 to 5.5e-7 with torch's thread count, and the strict path was above it too (parity_util.parity_yardstick)."""
 import os
 from collections import OrderedDict
 
@@ -12,40 +51,87 @@ import pytest
 import torch
 
 import ralenet_oracle as O
-from parity_util import rel, run_parity
+from parity_util import parity_bars, parity_yardstick, rel, run_parity, spread_fc1_bias, yardstick_floors
 
 pytestmark = pytest.mark.gpu
 FWD_TOL, GRAD_TOL = 1e-5, 1e-4
+K_YARD = 8.0               # an fp16-pair product: 2^-21 relative, fp32: 2^-24 (parity_util.parity_bars)
 DEV = "cuda:0"
 
 
-def _check(res):
-    bad = {}
-    for k, v in res.items():
-        if k.startswith("gradabs:"):
-            if v > 1e-5:
-                bad[k] = v
-        elif k.startswith("grad:"):
-            if v > GRAD_TOL:
-                bad[k] = v
-        elif v > FWD_TOL:
-            bad[k] = v
-    assert not bad, bad
+def yardstick_ratios(res, yard):
+    """-> per group (forward, gradients): (worst error over yardstick, its key, median error over yardstick), the yardstick of a
+    key being max(yard[key], median of yard over the group), as in parity_bars; keys without a yardstick are left out"""
+    floors = yardstick_floors(yard)
+    out = []
+    for g in (0, 1):
+        r = {k: res[k] / max(y, floors[g]) for k, y in yard.items() if y is not None and k.startswith("grad:") == bool(g)}
+        worst = max(r, key=r.get)
+        out.append((r[worst], worst, float(np.median(list(r.values())))))
+    return out
 
 
-@pytest.mark.parametrize("variant,leads,L,B", [
+def _check(res, yard=None, capped=True, what=""):
+    """Without a yardstick: the flat bars.  With the parity_yardstick of the case: parity_bars per tensor (capped=False for the
+    cases that never had flat bars and hold tensors ill conditioned in fp32 itself), and a line of what was observed."""
+    if yard is None:
+        bars = {k: 1e-5 if k.startswith("gradabs:") else GRAD_TOL if k.startswith("grad:") else FWD_TOL for k in res}
+    else:
+        assert list(res) == list(yard), sorted(set(res) ^ set(yard))
+        bars = parity_bars(yard, K_YARD, (FWD_TOL, GRAD_TOL), capped)
+        (fw, fk, fm), (gw, gk, gm) = yardstick_ratios(res, yard)
+        print(f"\nobserved {what}: error over yardstick: forward worst {fw:.2f} ({fk}) median {fm:.2f}, "
+              f"gradient worst {gw:.2f} ({gk}) median {gm:.2f}")
+    bad = {k: v for k, v in res.items() if not v <= bars[k]}
+    yd = {k: "none" if yard is None or yard[k] is None else "%.3e" % yard[k] for k in bad}
+    assert not bad, "\n".join(["%d tensors above their bars:" % len(bad)] + [
+        f"  {k}: error {v:.3e}, yardstick {yd[k]}, bar {bars[k]:.3e}" for k, v in bad.items()])
+
+
+PLAIN_CASES = [
     ("full", 2, 512, 4), ("nra", 2, 512, 3), ("mlp", 2, 256, 4), ("full", 2, 256, 5),
     ("full", 1, 512, 2), ("full", 2, 1024, 2), ("nra", 1, 256, 1), ("mlp", 2, 768, 3),
-])
-def test_train_step_matches_oracle(variant, leads, L, B):
-    res, _, _ = run_parity(variant, leads, L, B, DEV)
-    _check(res)
-
-
-@pytest.mark.parametrize("variant,leads,L,B", [
+]
+LENGTH_CASES = [
     ("nra", 2, 128, 3), ("nra", 2, 320, 2), ("full", 2, 640, 2), ("full", 1, 128, 5), ("mlp", 2, 320, 3), ("full", 2, 96, 2),
     ("nra", 1, 16, 4), ("full", 2, 1008, 1), ("full", 2, 32, 2),
-])
+]
+# (variant, leads, L, B, options): GELU arguments across [-10, 10] (parity_util.spread_fc1_bias); L = 96 has masked token slots
+SPREAD_CASES = [
+    pytest.param("full", 2, 256, 3, None, id="full-2-256-3"), pytest.param("nra", 2, 256, 3, None, id="nra-2-256-3"),
+    pytest.param("mlp", 2, 256, 3, None, id="mlp-2-256-3"), pytest.param("full", 2, 96, 2, None, id="full-2-96-2"),
+    pytest.param("full", 2, 256, 3, {"f16_split": 0}, id="full-2-256-3-strict"),
+]
+
+
+@pytest.mark.parametrize("variant,leads,L,B", PLAIN_CASES)
+def test_train_step_matches_oracle(variant, leads, L, B):
+    res, _, _ = run_parity(variant, leads, L, B, DEV)
+    _check(res, parity_yardstick(variant, leads, L, B), what=f"{variant} leads={leads} L={L} B={B}")
+
+
+@pytest.mark.parametrize("variant,leads,L,B,options", SPREAD_CASES)
+def test_gelu_arguments_across_the_fitted_range_match_oracle(variant, leads, L, B, options):
+    """With the seeded parameters no GELU argument of any parity case lies beyond 3 (99.9 % below 1.9), so most of the range of
+    gelu_f (a degree-7 fit on |x| <= 7.78 with an underflow tail) and of gelu_pair (csrc/ral_device.hpp) - the fit, the hand-over
+    to the tail, the negative part of the derivative - never ran on the device against the oracle.  Here the fc1 biases are a
+    grid over [-9, 9] (spread_fc1_bias): arguments from -13 to 10, every 2-wide bin of [-10, 10] populated
+    (tests/test_parity_bars_cpu.py).  A whole train step and the eval forward at per-tensor bars of 8 x the fp32 oracle's own
+    error, uncapped: one or two attention query gradients of utransformer4.*.1 are ill conditioned in fp32 itself (8.6e-4, 6.8e-4
+    in the fp32 oracle) and their bars follow.  The comparison is relative L2: an absolute error far out in the negative tail,
+    where GELU itself is below 1e-6, is rightly not counted.
+
+    What it found: `utransformer1.1.mlp.leconv.partial_conv3.weight` of the nra case (channel-0 bias -2.4, so the whole gradient
+    is made of GELU values at -1.4 .. -3.4) was 6.1e-5 off, 32 x its yardstick, with f16_split = 0 as well: the fused narrow-level
+    backward took those values from gelu_pair, whose error is 1.5e-7 ABSOLUTE in Phi.  With gelu_f's value (ral_mlpw.hip) it is
+    within its bar; the fp32 oracle with the same two formulas in GELU's place gives 6.4e-5 and 4.8e-6."""
+    trace = L % 256 == 0          # (the debug tensors of a padded length are laid out on its token slots)
+    res, _, _ = run_parity(variant, leads, L, B, DEV, trace=trace, options=options, eval_forward=True, params=spread_fc1_bias)
+    yard = parity_yardstick(variant, leads, L, B, params=spread_fc1_bias, eval_forward=True, trace=trace)
+    _check(res, yard, capped=False, what=f"spread {variant} leads={leads} L={L} B={B} {options or ''}")
+
+
+@pytest.mark.parametrize("variant,leads,L,B", LENGTH_CASES)
 def test_window_lengths_that_are_multiples_of_16_match_oracle(variant, leads, L, B):
     """The reference runs at any window length that is a multiple of 16 (raletransformer.py:170,448-450: four PatchMerging
     halvings; its positional table ends at 1000); here such a length runs on the next multiple of 256 token slots with the
@@ -54,7 +140,7 @@ def test_window_lengths_that_are_multiples_of_16_match_oracle(variant, leads, L,
     running statistics and every parameter gradient against the fp64 oracle, as for the other lengths: 128, 320, 640 (the
     review's list), 96 / 32 / 16 (fewer than 16 tokens at the deep levels), 1008 (one tile short of 1024)."""
     res, _, _ = run_parity(variant, leads, L, B, DEV, trace=False)
-    _check(res)
+    _check(res, parity_yardstick(variant, leads, L, B, trace=False), what=f"{variant} leads={leads} L={L} B={B}")
 
 
 @pytest.mark.parametrize("variant,leads,L", [("nra", 2, 512), ("full", 2, 256), ("mlp", 2, 256), ("full", 2, 512),
