@@ -27,6 +27,9 @@ import torch.nn.functional as F
 
 ENC_CH, ENC_K, ENC_P = [4, 8, 16, 32], [17, 17, 3, 3], [8, 8, 1, 1]
 DEC_CH, DEC_K, DEC_P = [16, 8, 4, 2], [4, 4, 18, 18], [1, 1, 8, 8]
+# the two kinks that are no member of F, and the gate function, under module-level names: a test that needs every kink's input
+# stands a recording function in their place, one that needs a slightly wrong gate a wrong one (tests/baseline_parity_util.py)
+relu, clamp, sigmoid = torch.relu, torch.clamp, torch.sigmoid
 
 
 def _bn_keys(d, pre, c):
@@ -121,20 +124,20 @@ def _aprelu(x, st, pre, training):
     """`clamp` for the reference's torch.max(x, 0) / torch.min(x, 0) (DAM.py:12-48): the two differ only in the gradient
     at an activation of exactly 0.0 (clamp passes it on, max / min against a zero tensor halve it), which a convolution
     with a non-zero bias never produces - left as it is"""
-    p, n = torch.clamp(x, min=0), torch.clamp(x, max=0)
+    p, n = clamp(x, min=0), clamp(x, max=0)
     d = torch.cat([p.mean(-1), n.mean(-1)], 1)
     h = F.linear(d, st[pre + ".fcn.0.weight"], st[pre + ".fcn.0.bias"])
-    h = torch.relu(_bn(h, st, pre + ".fcn.1", training))
+    h = relu(_bn(h, st, pre + ".fcn.1", training))
     h = F.linear(h, st[pre + ".fcn.3.weight"], st[pre + ".fcn.3.bias"])
-    alpha = torch.sigmoid(_bn(h, st, pre + ".fcn.4", training))
+    alpha = sigmoid(_bn(h, st, pre + ".fcn.4", training))
     return p + alpha.unsqueeze(2) * n
 
 
 def _dam_fcn(v, st, pre, training):
     h = F.linear(v, st[pre + ".0.weight"], st[pre + ".0.bias"])
-    h = torch.relu(_bn(h, st, pre + ".1", training))
+    h = relu(_bn(h, st, pre + ".1", training))
     h = F.linear(h, st[pre + ".3.weight"], st[pre + ".3.bias"])
-    return torch.sigmoid(_bn(h, st, pre + ".4", training))
+    return sigmoid(_bn(h, st, pre + ".4", training))
 
 
 def _dam(x, st, pre, training):
@@ -142,10 +145,10 @@ def _dam(x, st, pre, training):
     inputs hold the maximum its gradient goes to the FIRST of them (`amax` would split it evenly over all of them)"""
     ga = _dam_fcn(x.mean(-1), st, pre + ".fcn1", training)          # the shared fcn: first the average-pooled batch,
     gm = _dam_fcn(F.adaptive_max_pool1d(x, 1).squeeze(-1), st, pre + ".fcn1", training)          # then the max-pooled one
-    cattn = torch.sigmoid(ga + gm).unsqueeze(-1)
+    cattn = sigmoid(ga + gm).unsqueeze(-1)
     cmax = F.adaptive_max_pool1d(x.transpose(1, 2), 1).squeeze(-1)  # (B, L): the maximum over channels, first channel at a tie
     cat = torch.stack([x.mean(1), cmax], 1)                         # (B, 2, L)
-    sattn = torch.sigmoid(F.conv1d(cat, st[pre + ".convsa.weight"], st[pre + ".convsa.bias"]))   # (B, 1, L)
+    sattn = sigmoid(F.conv1d(cat, st[pre + ".convsa.weight"], st[pre + ".convsa.bias"]))   # (B, 1, L)
     return sattn * (cattn * x)
 
 

@@ -301,12 +301,12 @@ def run_parity(variant, leads, L, B, device="cuda:0", trace=True, seed=1234, opt
     return res, model, (p32, x, tgt)
 
 
-def make_newrale_case(variant, L, B):
+def make_newrale_case(variant, L, B, input_seed=2023):
     """`make_case`'s seeds for the 12-lead adapter: inner 2-lead RA-LENet parameters (1234), adapter parameters (77), x and
-    target (B, 12, L) from generator 2023"""
+    target (B, 12, L) from generator `input_seed`"""
     p32 = O.init_params(O.ralenet_param_shapes(variant, 2), 1234)
     pa32 = O.init_params(O.newrale_param_shapes(), 77)
-    g = torch.Generator().manual_seed(2023)
+    g = torch.Generator().manual_seed(input_seed)
     x = torch.randn(B, 12, L, generator=g)
     tgt = torch.randn(B, 12, L, generator=g)
     return p32, pa32, x, tgt
@@ -321,12 +321,12 @@ def _newrale_model(variant, L, B, p32, pa32, device):
     return m.train()
 
 
-def run_newrale_parity(variant, L, B, device="cuda:0"):
+def run_newrale_parity(variant, L, B, device="cuda:0", input_seed=2023):
     """One train step of the 12-lead adapter around a frozen RA-LENet (HIP fp32) against the fp64 oracle -> dict of relative
     errors: y in train mode, loss / SNR / RMSE over the 12 x L windows, the eight adapter gradients ("grad:<name>"), the inner
     BatchNorm's running statistics after the step (quirk A16: the frozen model's BatchNorm keeps training) and the eval-mode
     forward on those statistics."""
-    p32, pa32, x, tgt = make_newrale_case(variant, L, B)
+    p32, pa32, x, tgt = make_newrale_case(variant, L, B, input_seed)
     m = _newrale_model(variant, L, B, p32, pa32, device)
     xd, td = x.to(device), tgt.to(device)
     y = m(xd)

@@ -331,8 +331,9 @@ def covering_runs():
     launches as a training forward).  The golden tests run one configuration each: L = 512 at their fixture's batch."""
     import test_gpu_acdae as A
     import test_gpu_danet as D
-    runs = [("test_acdae_train_step_matches_oracle", ACDAE, L, B) for L, B in parametrize_args(A.test_acdae_train_step_matches_oracle)]
-    runs += [("test_danet_matches_fp64_oracle", DANET, L, B) for B, L, leads in parametrize_args(D.test_danet_matches_fp64_oracle)]
+    shapes = lambda fn: list(dict.fromkeys(c.values[0] for c in parametrize_args(fn)))      # (shape, input seed, yardstick seeds)
+    runs = [("test_acdae_train_step_matches_oracle", ACDAE, L, B) for L, B in shapes(A.test_acdae_train_step_matches_oracle)]
+    runs += [("test_danet_matches_fp64_oracle", DANET, L, B) for B, L, leads in shapes(D.test_danet_matches_fp64_oracle)]
     for test, variant, fixture in (("test_acdae_against_reference_golden", ACDAE, "g3_acdae_l2_L512.npz"), ("test_danet_matches_reference_golden", DANET, "g3_danet_L512.npz")):
         assert hasattr(A if variant == ACDAE else D, test)
         runs.append((test, variant, 512, np.load(os.path.join(ROOT, "tests", "golden", fixture))["x"].shape[0]))

@@ -1,5 +1,21 @@
 """ACDAE comparison baseline (reference model/ACDAE.py) on the HIP path vs the fp64 oracle and the reference's golden
-vectors: outputs, loss, every parameter gradient, the input gradient, three Adam steps."""
+vectors: outputs, loss, every parameter gradient, the input gradient, three Adam steps.
+
+Tolerances of the train-step test (fp32 kernels against the oracle in fp64, relative L2): one bar per tensor, 4 times the error of
+that tensor in the oracle evaluated in fp32 (tests/baseline_parity_util.py: the yardstick, floored at the median of its group),
+never above the flat 1e-5 (forward) and 1e-4 (gradients) every case had before.  A case gets such bars only if no LeakyReLU input
+and no MaxPool1d(2) pair is within 1e-5 of its tensor's RMS of its kink and fp32 and fp64 agree on every one (the kink
+precondition, tests/test_baseline_bars_cpu.py).  The typical yardstick is 3e-7, so the typical bar 1.2e-6 where it was 1e-4: the
+ECA gate's sigmoid on the fast exponential (k_acd_dec_fwd) stays within it, 1.44 x the yardstick at most on an ECA weight gradient.
+
+Observed on an MI355X, as error over yardstick (with its floor; the bar is at 4): the worst tensor and the median per group
+  case (L, B) seed   forward: worst   median   gradients: worst                median
+  512, 4    2025     1.24 y           0.64     1.44 DecList.1.ECA.conv.weight  0.65
+  256, 3    2023     1.20 y           0.67     1.22 EncList.3.conv.weight      0.83
+  1024, 2   2026     1.21 y           0.61     1.08 input                      0.45
+  64, 3     2023     1.11 y           0.62     0.95 DecList.1.ECA.conv.weight  0.46
+  192, 2    2023     1.22 y           0.62     2.18 DecList.2.conv.bias        1.69
+(512, 4) and (1024, 2) at seed 2023 miss the precondition and keep the flat bars."""
 import os
 from collections import OrderedDict
 
@@ -7,6 +23,7 @@ import numpy as np
 import pytest
 import torch
 
+import baseline_parity_util as U
 import ralenet_oracle as O
 from parity_util import rel
 
@@ -14,31 +31,19 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
-@pytest.mark.parametrize("L,B", [(512, 4), (256, 3), (1024, 2), (64, 3), (192, 2)])
-def test_acdae_train_step_matches_oracle(L, B):
-    from ecg_denoise_amd import ACDAE
-    p32 = O.init_params(O.acdae_param_shapes(), 1234)
-    g = torch.Generator().manual_seed(2023)
-    x = torch.randn(B, 2, L, generator=g); tgt = torch.randn(B, 2, L, generator=g)
-    m = ACDAE(L=L, max_batch=B, device=DEV)
-    m.load_state_dict(p32)
-    m.train()
-    y = m(x.to(DEV))
-    loss, snr, rmse = m.loss_and_metrics(y, tgt.to(DEV))
-    dx = m.backward(want_dx=True)
-    torch.cuda.synchronize()
-    p = OrderedDict((k, v.double().requires_grad_(True)) for k, v in p32.items())
-    xd = x.double().requires_grad_(True)
-    yo = O.acdae_forward(p, xd)
-    lo = O.mse(yo, tgt.double())
-    grads = torch.autograd.grad(lo, list(p.values()) + [xd])
-    assert rel(y.cpu().numpy(), yo.detach().numpy()) < 1e-5
-    assert abs(loss.item() - lo.item()) < 1e-5 * abs(lo.item())
-    np.testing.assert_allclose(snr.cpu().numpy(), O.snr(tgt.double(), yo.detach()).numpy(), rtol=0, atol=1e-4)
-    ng = m.named_grads()
-    bad = {k: e for (k, _), gr in zip(p.items(), grads[:-1]) if (e := rel(ng[k].cpu().numpy(), gr.numpy())) > 1e-4}
-    assert not bad, bad
-    assert rel(dx.cpu().numpy(), grads[-1].numpy()) < 1e-4
+@pytest.mark.parametrize("case,seed,seeds", U.case_params("acdae"))
+def test_acdae_train_step_matches_oracle(case, seed, seeds):
+    """Output, loss, every parameter gradient and the input gradient, each at its own bar: K_BASE x what the fp32 oracle
+    deviates from the fp64 one on that tensor, never above the flat 1e-5 / 1e-4 (baseline_parity_util).  (512, 4) and (1024, 2)
+    have a LeakyReLU input 9.0e-6 / 4.9e-6 of its RMS from 0 at input seed 2023: they run at seeds 2025 / 2026 under
+    per-tensor bars and at 2023 under the flat ones.  The per-window SNR keeps its absolute 1e-4 (it is near 0 dB here: a relative
+    error says little), eval against train mode its bit equality."""
+    bars, yard = U.case_bars("acdae", case, seed, seeds)
+    mine, m, x, y, snr, tgt = U.run_acdae(case, seed, DEV)
+    o = U.oracle_step("acdae", case, torch.float64, seed)
+    U.check(U.errors(mine, o.vals), bars, yard, what="ACDAE L=%d B=%d seed %d" % (case + (seed,)))
+    yo = torch.from_numpy(o.vals["y"])
+    np.testing.assert_allclose(snr.cpu().numpy(), O.snr(tgt.double(), yo).numpy(), rtol=0, atol=1e-4)
     m.eval()
     assert torch.equal(m(x.to(DEV)), y)                    # no BatchNorm, no dropout: eval is the same function
 

@@ -1,6 +1,22 @@
 """DANet baseline (model/DAM.py::Seq2Seq2) on the GPU, through the C ABI, against the reference-generated fixture
 (tests/golden/g3_danet_L512.npz, oracle/gen_golden_danet.py) and against the fp64 oracle at a larger batch.
-Tolerances: forward 1e-5, gradients 1e-4 relative L2 vs fp64 (2e-4 vs the reference's own fp32 numbers)."""
+Tolerances: forward 1e-5, gradients 1e-4 relative L2 vs fp64 (2e-4 vs the reference's own fp32 numbers).
+
+The first step of test_danet_matches_fp64_oracle has one bar per tensor where the case allows it: 4 times the error of that tensor
+in the oracle evaluated in fp32 (tests/baseline_parity_util.py: the yardstick, floored at the median of its group - the gradients,
+and everything else), never above the bars above.  A case gets them only if no clamp or ReLU input and no max-pool winner is
+within 1e-5 of its tensor's RMS of its kink and fp32 and fp64 agree on every one (tests/test_baseline_bars_cpu.py); the cases of
+0.6 million kink inputs and more find no such input.  The yardsticks spread widely here - 7e-8 for a running statistic, 2e-6 for
+the median gradient, 1e-5 .. 2e-4 for `dam.convsa.*` and the gradients behind a BatchNorm over 4 descriptors - and the bars with
+them.  The gates' sigmoid on the fast exponential (sigm, ral_danet.hip) stays within them.
+
+Observed on an MI355X, as error over yardstick (with its floor; the bar is at 4): the worst tensor and the median per group
+  case (B, L, leads) seed   forward: worst                                 median   gradients: worst                        median
+  8, 512, 2     20          1.14 y_eval                                    0.67     2.14 DecoderList.0.dam.convsa.bias       0.38
+  4, 1024, 2    8           1.10 y_eval                                    0.37     0.65 EncoderList.cell0.activate.fcn.0.weight 0.18
+  8, 256, 2     8           1.65 DecoderList.1.dam.fcn1.1.running_mean     0.76     2.38 DecoderList.2.activate.fcn.4.weight 0.87
+  8, 32, 2      10          1.11 DecoderList.1.dam.fcn1.1.running_var      0.74     1.14 DecoderList.2.deconv.bias           0.40
+  4, 64, 2      4           2.78 EncoderList.cell1.activate.fcn.4.running_mean 0.79 1.34 DecoderList.0.dam.convsa.weight     0.76"""
 import os
 from collections import OrderedDict
 
@@ -8,6 +24,7 @@ import numpy as np
 import pytest
 import torch
 
+import baseline_parity_util as U
 import danet_oracle as D
 from parity_util import rel
 
@@ -52,17 +69,24 @@ def test_danet_matches_reference_golden(golden_dir):
             assert int(sd[k]) == int(g["after_" + k]), k
 
 
-@pytest.mark.parametrize("B,L,leads", [(64, 512, 2), (37, 256, 2), (16, 1024, 2), (8, 32, 2), (4, 64, 2)])
-def test_danet_matches_fp64_oracle(B, L, leads):
-    st64 = D.init_state(99, leads=leads, dtype=torch.float64)
-    st32 = OrderedDict((k, v.clone().float() if v.dtype.is_floating_point else v.clone()) for k, v in st64.items())
-    gg = torch.Generator().manual_seed(B)
+@pytest.mark.parametrize("case,seed,seeds", U.case_params("danet"))
+def test_danet_matches_fp64_oracle(case, seed, seeds):
+    """The eval forward, then one train step - output, loss, input gradient, every parameter gradient, every running statistic -
+    each at its own bar: K_BASE x what the fp32 oracle deviates from the fp64 one on that tensor, never above the flat 1e-5 /
+    1e-4 (2e-3 at B < 8) - baseline_parity_util.  Then three Adam steps at the bars they had.
+    Flat bars stay where the kink precondition finds no input: (64, 512), (37, 256) and (16, 1024) have 0.6 to 2.2 million
+    clamp, ReLU and max-pool inputs, and at none of nine seeds all of them keep 1e-5 of their RMS from the kink; (8, 512), (4, 1024)
+    and (8, 256) are the long windows at batches small enough for one.  (8, 32) misses at its old seed 8 (a ReLU input at 3.8e-6): per-tensor bars at seed 10,
+    the flat ones at 8."""
+    B, L, leads = case
+    st64, st32 = U.danet_states(leads)
+    gg = torch.Generator().manual_seed(seed)
     x = torch.randn(B, leads, L, generator=gg); tgt = torch.randn(B, leads, L, generator=gg)
     m = _model(st32, B, L, leads=leads)
     m.eval()
     with torch.no_grad():
         ye = D.danet_forward(st64, x.double(), training=False)
-    assert rel(m(x.to(DEV)).cpu().numpy(), ye.numpy()) < 1e-5
+    mine = OrderedDict(y_eval=m(x.to(DEV)).cpu().numpy())
     m.train()
     xd = x.double().requires_grad_(True)
     params = OrderedDict((k, v.requires_grad_(True)) for k, v in st64.items() if D.is_param(k) and ".dam.fcn2." not in k)
@@ -70,22 +94,19 @@ def test_danet_matches_fp64_oracle(B, L, leads):
     loss64 = torch.nn.functional.mse_loss(y64, tgt.double())
     loss64.backward()
     y = m(x.to(DEV))
-    assert rel(y.cpu().numpy(), y64.detach().numpy()) < 1e-5
+    mine["y"] = y.cpu().numpy()
     loss, _, _ = m.loss_and_metrics(y, tgt.to(DEV))
-    assert abs(loss.item() - loss64.item()) < 1e-5 * loss64.item()
-    dx = m.backward(want_dx=True)
-    # a BatchNorm over a batch of 4 descriptors divides by a variance of four samples: fp32 rounding is amplified there
-    gtol = 1e-4 if B >= 8 else 2e-3
-    assert rel(dx.cpu().numpy(), xd.grad.numpy()) < gtol
-    for k, v in m.named_grads().items():
-        if k.endswith(ZERO_GRAD):
-            assert v.abs().max().item() < 1e-5, k
-        else:
-            assert rel(v.cpu().numpy(), params[k].grad.numpy()) < gtol, k
+    mine["loss"] = loss.cpu().numpy()
+    mine["grad:input"] = m.backward(want_dx=True).cpu().numpy()
+    mine.update(("grad:" + k, v.cpu().numpy()) for k, v in m.named_grads().items())
     sd = m.state_dict()
-    for k in sd:
-        if k.endswith("running_mean") or k.endswith("running_var"):
-            assert rel(sd[k].cpu().numpy(), st64[k].numpy()) < 1e-5, k
+    mine.update((k, sd[k].cpu().numpy()) for k in U.danet_stat_names(sd))
+    ref = U.danet_vals(ye, y64, loss64, xd.grad, OrderedDict((k, v.grad) for k, v in params.items()), st64)
+    bars, yard = U.case_bars("danet", case, seed, seeds)
+    if seeds is None:
+        bars = U.flat_bars(ref, *U.caps("danet", case))
+    assert {k[5:] for k, r in ref.items() if k.startswith("grad:") and U.is_zero(r)} == {k for k in params if k.endswith(ZERO_GRAD)}
+    U.check(U.errors(mine, ref), bars, yard, what="DANet B=%d L=%d leads=%d seed %d" % (case + (seed,)))
     # three Adam steps stay on the oracle's trajectory
     opt = torch.optim.Adam(list(params.values()), lr=1e-3)
     for _ in range(3):

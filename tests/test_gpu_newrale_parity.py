@@ -11,9 +11,23 @@ The cases are the smallest at which each thing can still go wrong:
   ("nra", 16, 513)   k_conv13_bwd beyond its 512 workgroups (workgroup 0 takes two windows, the others one); the inner model
                      at a batch above 512
 
-Bars: those of tests/test_gpu_parity.py (forward 1e-5, gradients 1e-4, relative L2 against fp64); the Adam trajectory at
-the bars of tests/test_gpu_danet.py (2e-5 on the prediction after a step, 1e-5 on the parameters after the last).  The fp64
-oracle evaluated in fp32 differs from itself by up to 4.9e-7 on y and 1.2e-6 on the adapter gradients.
+Bars of the train step: one per quantity, 4 times its error in the oracle evaluated in fp32 (tests/baseline_parity_util.py: the
+yardstick, floored at the median of its group), never above the flat forward 1e-5 and gradients 1e-4 of tests/test_gpu_parity.py;
+4, since the adapter's own kernels multiply no fp16 pairs and the frozen inner model's forward sits at the fp32 oracle's error
+(tests/test_gpu_parity.py).  A case gets them only if no input of the three adapter LeakyReLUs and of the stem's is within 1e-5 of
+its tensor's RMS of 0 (tests/test_baseline_bars_cpu.py): ("nra", 64, 5) moves to input seed 2024 for that and runs at 2023 under
+the flat bars, ("nra", 16, 513) keeps the flat bars.  The Adam trajectory: the bars of tests/test_gpu_danet.py (2e-5 on the
+prediction after a step, 1e-5 on the parameters after the last).  The fp64 oracle evaluated in fp32 differs from itself by up to
+4.9e-7 on y and 1.2e-6 on the adapter gradients.
+
+Observed on an MI355X, as error over yardstick (with its floor; the bar is at 4): the worst quantity and the median per group
+  case               forward: worst   median   gradients: worst    median
+  full, 256, 3       1.16 y_eval      0.54     2.64 conv1.bias     0.74
+  nra, 16, 4         1.12 y           0.63     1.16 conv3.weight   0.85
+  full, 32, 2        1.57 y           0.69     2.21 conv2.bias     1.55
+  mlp, 320, 2        1.06 y           0.41     0.89 conv1.weight   0.57
+  nra, 64, 5 @2024   1.13 y_eval      0.75     1.24 conv1.weight   0.80
+  full, 1008, 1      2.03 snr         0.31     3.12 conv2.bias     1.49
 
 Observed worst errors on an MI355X (train step: forward = max over y, loss, SNR, RMSE, BatchNorm statistics, y_eval):
   case               forward (which)   y        y_eval   gradient (which)       | Adam: loss   prediction  parameters
@@ -29,8 +43,9 @@ and the fp32 rounding of the ratio, 6e-8, is divided by it)."""
 import pytest
 import torch
 
+import baseline_parity_util as U
 from parity_util import run_newrale_adam, run_newrale_parity
-from test_gpu_parity import DEV, FWD_TOL, GRAD_TOL, _check
+from test_gpu_parity import DEV, FWD_TOL, GRAD_TOL
 
 pytestmark = pytest.mark.gpu
 
@@ -38,16 +53,23 @@ CASES = [("full", 256, 3), ("nra", 16, 4), ("full", 32, 2), ("mlp", 320, 2), ("n
 ADAM_PRED_TOL, ADAM_PARAM_TOL = 2e-5, 1e-5     # tests/test_gpu_danet.py
 
 
-@pytest.mark.parametrize("variant,L,B", CASES)
-def test_adapter_train_step_matches_oracle(variant, L, B):
-    res = run_newrale_parity(variant, L, B, DEV)
+@pytest.mark.parametrize("case,seed,seeds", U.case_params("newrale"))
+def test_adapter_train_step_matches_oracle(case, seed, seeds):
+    """Every quantity of run_newrale_parity at its own bar: K_BASE x what the fp32 oracle deviates from the fp64 one on it, never
+    above the flat bars (baseline_parity_util).  ("nra", 64, 5) has an adapter LeakyReLU input 8.2e-6 of its RMS from 0 at input
+    seed 2023: per-tensor bars at seed 2024, the flat ones at 2023.  ("nra", 16, 513) has 361 000 LeakyReLU inputs and no seed
+    among nine keeps them all 1e-5 from 0: flat bars."""
+    variant, L, B = case
+    assert case in CASES
+    res = run_newrale_parity(variant, L, B, DEV, seed)
     fwd = {k: v for k, v in res.items() if not k.startswith("grad:")}
     grad = {k: v for k, v in res.items() if k.startswith("grad:")}
     kf, kg = max(fwd, key=fwd.get), max(grad, key=grad.get)
     print(f"\nobserved {variant} L={L} B={B}: forward {fwd[kf]:.2e} ({kf}), y {res['y']:.2e}, y_eval {res['y_eval']:.2e}, "
           f"gradient {grad[kg]:.2e} ({kg})")
     assert len(grad) == 8
-    _check(res)
+    bars, yard = U.case_bars("newrale", case, seed, seeds)
+    U.check(res, bars, yard, what=f"adapter {variant} L={L} B={B} seed {seed}")
 
 
 @pytest.mark.parametrize("variant,L,B", CASES)

@@ -1,4 +1,20 @@
-"""U-Net baseline (reference model/UNet.py) on the HIP path vs the oracle and the golden vectors."""
+"""U-Net baseline (reference model/UNet.py) on the HIP path vs the oracle and the golden vectors.
+
+Tolerances of the train-step test (fp32 kernels against the oracle in fp64, relative L2): one bar per tensor, 4 times the error of
+that tensor in the oracle evaluated in fp32 (tests/baseline_parity_util.py: the yardstick, floored at the median of its group -
+the gradients, and everything else), never above the flat 1e-5 (forward) and 1e-4 (gradients) every case had before.  4, not the
+8 of tests/test_gpu_parity.py: no U-Net kernel multiplies fp16 pairs.  A case gets such bars only if no LeakyReLU input is within
+1e-5 of its tensor's RMS of 0 and fp32 and fp64 agree on every sign (the kink precondition, checked in
+tests/test_baseline_bars_cpu.py).  The typical yardstick is 5e-8 (running statistics), 3e-7 (output) and 1e-6 (gradients).
+
+Observed on an MI355X, as error over yardstick (with its floor; the bar is at 4): the worst tensor and the median per group
+  case (leads, L, B) seed   forward: worst                       median   gradients: worst              median
+  2, 512, 4     2023        1.83 loss                            0.54     2.72 DecList.3.conv.weight    0.81
+  1, 256, 3     2023        1.00 DecList.2.bn.running_mean       0.65     1.03 EncList.1.bn.bias        0.66
+  2, 1024, 2    2023        1.19 EncList.2.bn.running_mean       0.70     0.89 bottleneck.3.bias        0.62
+  2, 48, 5      2024        1.19 EncList.1.bn.running_mean       0.76     0.92 DecList.2.bn.bias        0.35
+  2, 320, 3     2023        1.00 DecList.3.bn.running_mean       0.75     1.46 DecList.2.bn.weight      0.69
+(2, 48, 5) at seed 2023 and (2, 64, 1025) miss the precondition and keep the flat bars."""
 import os
 from collections import OrderedDict
 
@@ -6,6 +22,7 @@ import numpy as np
 import pytest
 import torch
 
+import baseline_parity_util as U
 import ralenet_oracle as O
 from parity_util import rel
 
@@ -36,31 +53,20 @@ def _run(leads, L, B, seed=1234):
 # (2, 48, 5): a level length that is not a multiple of 4 -> generic stage kernels, gradient atomics instead of the fold;
 # (2, 320, 3): fold path, stage-by-stage eval forward (the fused kernel takes multiples of 256 only);
 # (2, 64, 1025): more windows than workgroup slots with a ragged last pass (1 window of 2), short levels (4 samples)
-@pytest.mark.parametrize("leads,L,B", [(2, 512, 4), (1, 256, 3), (2, 1024, 2), (2, 48, 5), (2, 320, 3), (2, 64, 1025)])
-def test_unet_train_step_matches_oracle(leads, L, B):
-    m, y, loss, p, bn, yo, lo, grads, x, tgt = _run(leads, L, B)
-    assert rel(y.cpu().numpy(), yo.detach().numpy()) < 1e-5
-    assert abs(loss.item() - lo.item()) < 1e-5 * abs(lo.item())
-    ng = m.named_grads()
-    bad = {}
-    for (k, _), g in zip(p.items(), grads):
-        e = rel(ng[k].cpu().numpy(), g.numpy())
-        # conv biases feeding a BatchNorm have an exactly-zero gradient: bounded by rounding noise
-        if g.norm().item() < 1e-9:
-            e = float(np.abs(ng[k].cpu().numpy()).max())
-            if e > 2e-5:
-                bad[k] = e
-        elif e > 1e-4:
-            bad[k] = e
-    assert not bad, bad
-    sd = m.state_dict()
+@pytest.mark.parametrize("case,seed,seeds", U.case_params("unet"))
+def test_unet_train_step_matches_oracle(case, seed, seeds):
+    """Output, loss, the running statistics of the ten BatchNorms, every parameter gradient and the eval forward after the step,
+    each at its own bar: K_BASE x what the fp32 oracle deviates from the fp64 one on that tensor, never above the flat 1e-5
+    (forward) / 1e-4 (gradients) - baseline_parity_util.  (2, 48, 5) has a LeakyReLU input 2.4e-6 of its RMS from 0 at input
+    seed 2023: it runs at seed 2024 under per-tensor bars and at 2023 under the flat ones.  (2, 64, 1025) has 2.4 million
+    LeakyReLU inputs and no seed among nine keeps them all 1e-5 from 0: flat bars."""
+    bars, yard = U.case_bars("unet", case, seed, seeds)
+    mine, m = U.run_unet(case, seed, DEV)
+    ref = U.oracle_step("unet", case, torch.float64, seed).vals
+    U.check(U.errors(mine, ref), bars, yard, what="U-Net leads=%d L=%d B=%d seed %d" % (case + (seed,)))
     for k in O.UNET_BN:
-        np.testing.assert_allclose(sd[k + ".running_mean"].cpu().numpy(), bn[k]["running_mean"].numpy(), rtol=1e-5, atol=1e-6)
-        np.testing.assert_allclose(sd[k + ".running_var"].cpu().numpy(), bn[k]["running_var"].numpy(), rtol=1e-5, atol=1e-6)
-    m.eval()
-    with torch.no_grad():
-        ye = O.unet_forward(OrderedDict((k, v.detach()) for k, v in p.items()), x.double(), False, bn)
-    assert rel(m(x.to(DEV)).cpu().numpy(), ye.numpy()) < 1e-5
+        for s in (".running_mean", ".running_var"):
+            np.testing.assert_allclose(mine[k + s], ref[k + s], rtol=1e-5, atol=1e-6)
 
 
 def test_unet_against_reference_golden(golden_dir):

@@ -214,7 +214,8 @@ def test_query_refuses_what_a_model_refuses():
 # ---- the ledger
 def train_step_cases():
     import test_gpu_unet as G
-    return list([m for m in G.test_unet_train_step_matches_oracle.pytestmark if m.name == "parametrize"][0].args[1])
+    cases = [m for m in G.test_unet_train_step_matches_oracle.pytestmark if m.name == "parametrize"][0].args[1]
+    return list(dict.fromkeys(c.values[0] for c in cases))             # (shape, input seed, yardstick seeds): the shapes
 
 
 def launched_by(leads, L, B):
