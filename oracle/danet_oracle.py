@@ -28,7 +28,7 @@ import torch.nn.functional as F
 ENC_CH, ENC_K, ENC_P = [4, 8, 16, 32], [17, 17, 3, 3], [8, 8, 1, 1]
 DEC_CH, DEC_K, DEC_P = [16, 8, 4, 2], [4, 4, 18, 18], [1, 1, 8, 8]
 # the two kinks that are no member of F, and the gate function, under module-level names: a test that needs every kink's input
-# stands a recording function in their place, one that needs a slightly wrong gate a wrong one (tests/baseline_parity_util.py)
+# stands a recording function in their place, one that needs a slightly wrong gate a wrong one (tests/parity_bars.py, tests/parity_util.py)
 relu, clamp, sigmoid = torch.relu, torch.clamp, torch.sigmoid
 
 

@@ -1,25 +1,35 @@
-"""Shared helpers of the GPU parity tests: run the HIP path and the CPU oracle on the
-same seeded inputs and report relative L2 errors per tensor."""
+"""Shared helpers of the GPU parity tests: for each of the five networks one oracle step and one run of the HIP path on the same
+seeded inputs, both as named float64 values under the keys the network's GPU test compares (the rule that turns them into errors,
+yardsticks and bars: tests/parity_bars.py; the cases of the baselines and the adapter: tests/baseline_parity_util.py).
+
+A case is (network, shape, input seed):
+  "ralenet"  (variant, leads, L, B)   parameters O.init_params(..., 1234), inputs torch.Generator(seed): x, target (make_case)
+  "unet"     (leads, L, B)            the same
+  "acdae"    (L, B)                   the same
+  "danet"    (B, L, leads)            state D.init_state(99), inputs torch.Generator(seed) - the GPU test's seed is B
+  "newrale"  (variant, L, B)          make_newrale_case"""
 import functools
+import inspect
 from collections import OrderedDict
+from contextlib import nullcontext
 from types import SimpleNamespace
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 
+import danet_oracle as D
 import ralenet_oracle as O
+from parity_bars import errors, kink_precondition, recording, rel, standing_in, yardstick  # noqa: F401 (rel: fifteen files import it from here)
 
-
-def rel(a, b):
-    a = np.asarray(a, dtype=np.float64).ravel(); b = np.asarray(b, dtype=np.float64).ravel()
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
+THREE_SEEDS = (2023, 2024, 2025)
+STEM = ("conv1.0.", "conv1.2.")
 
 
 def oracle_trace(p, x, variant, bn, dtype=torch.float64):
     """Oracle forward (training mode) that also returns every block / resample output,
     named like the library's debug tensors."""
-    import math
-    import torch.nn.functional as F
+    F = O.F          # (the oracle's own: a recorded or mutated functional reaches the stem here as well)
     le, rw, _ = O.variant_flags(variant)
     tr = OrderedDict()
     B, _, L = x.shape
@@ -65,165 +75,52 @@ def make_case(variant, leads, L, B, seed=1234, dtype=torch.float64, input_seed=2
     return p32, x, tgt
 
 
-def compare_grads(ng, p, grads):
-    """relative L2 error per parameter gradient: the library's `named_grads()` against the oracle's `grads` (in the order of `p`)"""
-    gerr = OrderedDict()
-    for (k, _), g in zip(p.items(), grads):
-        g = torch.zeros_like(p[k]) if g is None else g
-        gn = g.norm().item()
-        mine = ng[k].cpu().numpy()
+def make_newrale_case(variant, L, B, input_seed=2023):
+    """`make_case`'s seeds for the 12-lead adapter: inner 2-lead RA-LENet parameters (1234), adapter parameters (77), x and
+    target (B, 12, L) from generator `input_seed`"""
+    p32 = O.init_params(O.ralenet_param_shapes(variant, 2), 1234)
+    pa32 = O.init_params(O.newrale_param_shapes(), 77)
+    g = torch.Generator().manual_seed(input_seed)
+    x = torch.randn(B, 12, L, generator=g)
+    tgt = torch.randn(B, 12, L, generator=g)
+    return p32, pa32, x, tgt
+
+
+def _inputs(B, leads, L, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(B, leads, L, generator=g), torch.randn(B, leads, L, generator=g)
+
+
+def _np(t):
+    return t.detach().cpu().double().numpy()
+
+
+def grad_values(p, grads):
+    """RA-LENet's parameter gradients `grads` (in the order of `p`, None where unused: zero) as values "grad:<name>".  The key
+    half of a `to_kv.bias` gradient is identically zero (softmax shift invariance): the value half is "grad:<name>[v]", the key
+    half "gradabs:<name>[k]", which `errors` bounds by rounding noise."""
+    v = OrderedDict()
+    for k, g in zip(p, grads):
+        g = np.zeros(tuple(p[k].shape)) if g is None else _np(g)
         if k.endswith("to_kv.bias"):
-            # key-bias gradient is identically zero (softmax shift invariance): compare the value half,
-            # and bound the key half by rounding noise
-            C = mine.size // 2
-            gerr["grad:" + k + "[v]"] = rel(mine[C:], g.numpy()[C:])
-            gerr["gradabs:" + k + "[k]"] = float(np.abs(mine[:C]).max())
+            C = g.size // 2
+            v["grad:" + k + "[v]"], v["gradabs:" + k + "[k]"] = g[C:], g[:C]
         else:
-            gerr["grad:" + k] = rel(mine, g.numpy()) if gn > 1e-12 else float(np.abs(mine).max())
-    return gerr
+            v["grad:" + k] = g
+    return v
 
 
-STEM_MARGIN = 1e-5          # the smallest |stem pre-activation| a parity case may have (about 100 roundings of an O(1) sum)
+def compare_grads(ng, p, grads):
+    """error per parameter gradient (parity_bars.errors): the library's `named_grads()` against the oracle's `grads` (in the order of `p`)"""
+    return errors(grad_values(p, [ng[k] for k in p]), grad_values(p, grads))
 
 
 def stem_margin(variant, leads, L, B, seed=1234, params=None, input_seed=2023):
     """the smallest |stem pre-activation| of the case in fp64: its distance from the kink of the stem's LeakyReLU(0.2)"""
-    import torch.nn.functional as F
     p32, x, _ = make_case(variant, leads, L, B, seed, input_seed=input_seed)
     if params is not None:
         p32 = params(p32)
     return F.conv1d(x.double(), p32["conv1.0.weight"].double(), p32["conv1.0.bias"].double(), padding=1).abs().min().item()
-
-
-def oracle_step(variant, leads, L, B, seed=1234, params=None, dtype=torch.float64, gelu=None, input_seed=2023):
-    return _oracle_step(variant, leads, L, B, seed, params, dtype, gelu, input_seed)
-
-
-@functools.lru_cache(maxsize=8)
-def _oracle_step(variant, leads, L, B, seed, params, dtype, gelu, input_seed):
-    """One train step and the eval forward after it in the oracle alone, in `dtype`, on make_case's parameters (through `params`,
-    a callable p32 -> p32, when given) and inputs.  `gelu` stands in for O.gelu during the call (the mutants of
-    tests/test_parity_bars_cpu.py).  Cached and shared between run_parity and parity_yardstick: read-only for every caller.
-    -> namespace: p (leaves), bn (state after the step), y, tr (oracle_trace's tensors), loss, snr, rmse, grads (in the order
-    of p, None where unused), dx, y_eval."""
-    p32, x, tgt = make_case(variant, leads, L, B, seed, input_seed=input_seed)
-    if params is not None:
-        p32 = params(p32)
-    p = OrderedDict((k, v.to(dtype).requires_grad_(True)) for k, v in p32.items())
-    bn = O.new_bn_state(8, dtype)
-    xo = x.to(dtype).requires_grad_(True)
-    t = tgt.to(dtype)
-    keep = O.gelu
-    if gelu is not None:
-        O.gelu = gelu
-    try:
-        yo, tr = oracle_trace(p, xo, variant, bn)
-        lo = O.mse(yo, t)
-        *grads, dxo = torch.autograd.grad(lo, list(p.values()) + [xo], allow_unused=True)
-        p = OrderedDict((k, v.detach()) for k, v in p.items())
-        with torch.no_grad():
-            y_eval = O.ralenet_forward(p, x.to(dtype), variant, training=False, bn=bn)
-    finally:
-        O.gelu = keep
-    yo = yo.detach()
-    return SimpleNamespace(p=p, bn=bn, y=yo, tr=OrderedDict((k, v.detach()) for k, v in tr.items()), loss=lo.detach(),
-                           snr=O.snr(t, yo), rmse=O.rmse(t, yo), grads=grads, dx=dxo, y_eval=y_eval)
-
-
-def oracle_parity(variant, leads, L, B, seed=1234, params=None, eval_forward=False, trace=True, gelu=None, input_seed=2023):
-    """run_parity with the fp32 oracle (torch on the CPU, fp32 leaves and BatchNorm state) in the place of the HIP path: the same
-    keys, each the relative error of the fp32 evaluation against the fp64 one.  `grad:input_frozen` and the `@dx` stem gradients
-    repeat `grad:input` and the stem gradients (the oracle has one backward pass).  `gelu` replaces O.gelu in the fp32
-    evaluation only."""
-    a = oracle_step(variant, leads, L, B, seed, params, torch.float32, gelu, input_seed)
-    o = oracle_step(variant, leads, L, B, seed, params, torch.float64, None, input_seed)
-    res = OrderedDict()
-    res["y"] = rel(a.y.numpy(), o.y.numpy())
-    res["loss"] = abs(a.loss.item() - o.loss.item()) / abs(o.loss.item())
-    res["snr"] = rel(a.snr.numpy(), o.snr.numpy())
-    res["rmse"] = rel(a.rmse.numpy(), o.rmse.numpy())
-    res["bn_mean"] = rel(a.bn["running_mean"].numpy(), o.bn["running_mean"].numpy())
-    res["bn_var"] = rel(a.bn["running_var"].numpy(), o.bn["running_var"].numpy())
-    if trace:
-        for k, v in o.tr.items():
-            res["act:" + k] = rel(a.tr[k].numpy(), v.numpy())
-    ng = OrderedDict((k, torch.zeros_like(a.p[k]) if g is None else g) for k, g in zip(a.p, a.grads))
-    res.update(compare_grads(ng, o.p, o.grads))
-    res["grad:input"] = rel(a.dx.numpy(), o.dx.numpy())
-    stem = [k for k in o.p if k.startswith(("conv1.0.", "conv1.2."))]
-    res.update(("grad:" + k + "@dx", res["grad:" + k]) for k in stem)
-    res["grad:input_frozen"] = res["grad:input"]
-    if eval_forward:
-        res["y_eval"] = rel(a.y_eval.numpy(), o.y_eval.numpy())
-    return res
-
-
-THREE_SEEDS = (2023, 2024, 2025)
-
-
-def parity_yardstick(variant, leads, L, B, seed=1234, params=None, eval_forward=False, trace=True, input_seeds=THREE_SEEDS):
-    """What fp32 arithmetic itself costs, per tensor: a dict with the keys of run_parity(variant, leads, L, B, ...)'s result,
-    each value rel(fp32 oracle, fp64 oracle) of that tensor on the same seeded parameters and inputs (oracle_parity).  It is
-    the oracle's error, never the kernels'.  `gradabs:*` keys and gradients whose fp64 norm is <= 1e-12 get None: a quantity whose
-    true value is zero has no relative yardstick, and keeps its flat absolute bar.
-
-    One fp32 evaluation is a single sample of each tensor's rounding error, and torch's summation order follows the thread
-    count: the three-element `leconv.partial_conv3.weight` gradients came out between 1.1e-7 and 5.5e-7 for the same case at 16
-    threads and at 1, the nearly cancelling attention query gradients of the spread cases vary fivefold from one input to the
-    next - and the strict f16_split = 0 path, whose summation order is its own, sat 8.5 to 8.6 times above such a sample.  So the
-    yardstick is the largest of three fp32 evaluations, each against its own fp64 one, on inputs from the seeds `input_seeds`:
-    2023 (the case's own), 2024 and 2025; the parameters stay.  parity_bars floors it at its group's median besides.
-
-    Precondition: the stem's LeakyReLU(0.2) is the one kink of RA-LENet, and an fp32 pre-activation on the other side of 0
-    from the fp64 one changes gradients by a discrete amount no yardstick describes - the smallest |stem pre-activation| of the
-    case (fp64) must be >= STEM_MARGIN."""
-    assert input_seeds[0] == 2023
-    margin = stem_margin(variant, leads, L, B, seed, params)
-    assert margin >= STEM_MARGIN, (variant, leads, L, B, margin)
-    o = oracle_step(variant, leads, L, B, seed, params, torch.float64)
-    yard = oracle_parity(variant, leads, L, B, seed, params, eval_forward, trace)
-    for s in input_seeds[1:]:
-        # (the other inputs are no parity case and owe no margin: it is enough that no fp32 pre-activation changed sides)
-        a0, a1 = (oracle_step(variant, leads, L, B, seed, params, dt, None, s).tr["a0"] for dt in (torch.float32, torch.float64))
-        assert torch.equal(a0 > 0, a1 > 0), (variant, leads, L, B, s)
-        more = oracle_parity(variant, leads, L, B, seed, params, eval_forward, trace, None, s)
-        yard = OrderedDict((k, max(v, more[k])) for k, v in yard.items())
-    zero = {k for k, g in zip(o.p, o.grads) if g is None or g.norm().item() <= 1e-12}
-    for k in yard:
-        if k.startswith("gradabs:") or (k.startswith("grad:") and k[5:].split("@")[0] in zero):
-            yard[k] = None
-    return yard
-
-
-def _group(key):
-    return 1 if key.startswith("grad:") else 0
-
-
-def yardstick_floors(yard):
-    """-> (median of the non-None yardsticks of the forward group, of the gradient group)"""
-    return tuple(float(np.median([v for k, v in yard.items() if v is not None and _group(k) == g])) for g in (0, 1))
-
-
-def parity_bars(yard, K=8.0, flat=(1e-5, 1e-4), capped=True):
-    """One bar per key of `yard`: min(flat bar of the key's group, K * max(yard[key], median of yard over the group)); the
-    groups are the gradients (`grad:*`, flat[1]) and everything else (flat[0]).  A key without a yardstick (None) has the flat bar.
-
-    K = 8: the design lets an fp16-pair product be 2^-21 relative where fp32 rounds at 2^-24 (csrc/ral_device.hpp, DESIGN.md
-    section 4), so a tensor may carry 2^3 times the error of an fp32 evaluation and no more.  The median floor: the smallest
-    single samples (4.5e-8 .. 1e-7, at small tensors) say little about the tensor's typical rounding error.  The min keeps every
-    bar at or below the flat one; `capped=False` drops it, for cases whose tensors are ill conditioned in fp32 itself (the
-    yardstick of such a tensor is above the flat bar, and so is what any fp32 kernel can reach)."""
-    floors = yardstick_floors(yard)
-    bars = OrderedDict()
-    for k, v in yard.items():
-        g = _group(k)
-        if v is None:
-            bars[k] = flat[g]
-        else:
-            bars[k] = K * max(v, floors[g])
-            if capped:
-                bars[k] = min(flat[g], bars[k])
-    return bars
 
 
 def spread_fc1_bias(p32, lim=9.0, seed=5):
@@ -239,17 +136,239 @@ def spread_fc1_bias(p32, lim=9.0, seed=5):
     return out
 
 
-def run_parity(variant, leads, L, B, device="cuda:0", trace=True, seed=1234, options=None, eval_forward=False, before_forward=None,
-               params=None):
-    """-> dict of relative errors (HIP fp32 vs fp64 oracle).  `options`: {name: value} for ral_set_option on the model's handle,
-    applied before the first forward.  `params`: a callable p32 -> p32 applied to the seeded parameters before the model and the
-    oracle see them (spread_fc1_bias).  `eval_forward`: after the train step, the eval-mode forward of the same model against
-    the oracle's eval output (its BatchNorm on the running statistics the step left) as res["y_eval"].  `before_forward(model)`
-    is called once the options are set.  Gradients: every parameter gradient of `backward()` (dx = NULL, the training default);
-    then res["grad:input"] and the stem parameter gradients "grad:<name>@dx" of `backward(want_dx=True)`, and
-    res["grad:input_frozen"] of `backward_input` - the model comes back with the gradient buffer that last call left."""
+# ------------------------------------------------------------------------------------------------------------ oracle steps
+# One train step and the eval forward that goes with it in the oracle alone, in `dtype`: fn(case, dtype, seed, **options) ->
+# dict(vals = one float64 array per quantity the network's GPU test compares, ...)
+def _ralenet_step(case, dtype, seed, param_seed=1234, params=None, gelu=None):
+    """`params`: a callable p32 -> p32 applied to the seeded parameters (spread_fc1_bias); `gelu` stands in for O.gelu (the
+    mutants of tests/test_parity_bars_cpu.py).  `grad:input_frozen` and the `@dx` stem gradients repeat `grad:input` and the
+    stem gradients: the oracle has one backward pass."""
+    variant, leads, L, B = case
+    p32, x, tgt = make_case(variant, leads, L, B, param_seed, input_seed=seed)
+    if params is not None:
+        p32 = params(p32)
+    p = OrderedDict((k, v.to(dtype).requires_grad_(True)) for k, v in p32.items())
+    bn = O.new_bn_state(8, dtype)
+    xo = x.to(dtype).requires_grad_(True)          # (x is a leaf: the input gradient comes out of the same autograd call)
+    t = tgt.to(dtype)
+    with standing_in(O, gelu=gelu) if gelu is not None else nullcontext():
+        yo, tr = oracle_trace(p, xo, variant, bn)
+        lo = O.mse(yo, t)
+        *grads, dxo = torch.autograd.grad(lo, list(p.values()) + [xo], allow_unused=True)
+        with torch.no_grad():
+            ye = O.ralenet_forward(OrderedDict((k, v.detach()) for k, v in p.items()), x.to(dtype), variant, training=False, bn=bn)
+    yo = yo.detach()
+    v = OrderedDict(y=_np(yo), loss=_np(lo), snr=_np(O.snr(t, yo)), rmse=_np(O.rmse(t, yo)),
+                    bn_mean=_np(bn["running_mean"]), bn_var=_np(bn["running_var"]))
+    v.update(("act:" + k, _np(a)) for k, a in tr.items())
+    v.update(grad_values(p, grads))
+    v["grad:input"] = _np(dxo)
+    v.update(("grad:" + k + "@dx", v["grad:" + k]) for k in p if k.startswith(STEM))
+    v["grad:input_frozen"] = v["grad:input"]
+    v["y_eval"] = _np(ye)
+    return dict(vals=v)
+
+
+def _unet_step(case, dtype, seed):
+    leads, L, B = case
+    p32 = O.init_params(O.unet_param_shapes(leads), 1234)
+    x, tgt = _inputs(B, leads, L, seed)
+    p = OrderedDict((k, v.to(dtype).requires_grad_(True)) for k, v in p32.items())
+    bn = O.unet_bn_state(p, dtype)
+    y = O.unet_forward(p, x.to(dtype), True, bn)
+    loss = O.mse(y, tgt.to(dtype))
+    grads = torch.autograd.grad(loss, list(p.values()))
+    with torch.no_grad():
+        ye = O.unet_forward(OrderedDict((k, v.detach()) for k, v in p.items()), x.to(dtype), False, bn)
+    v = OrderedDict(y=_np(y), loss=_np(loss))
+    for k in O.UNET_BN:
+        v[k + ".running_mean"], v[k + ".running_var"] = _np(bn[k]["running_mean"]), _np(bn[k]["running_var"])
+    v.update(("grad:" + k, _np(g)) for k, g in zip(p, grads))
+    v["y_eval"] = _np(ye)
+    return dict(vals=v)
+
+
+def _acdae_step(case, dtype, seed):
+    L, B = case
+    p32 = O.init_params(O.acdae_param_shapes(), 1234)
+    x, tgt = _inputs(B, 2, L, seed)
+    p = OrderedDict((k, v.to(dtype).requires_grad_(True)) for k, v in p32.items())
+    xd = x.to(dtype).requires_grad_(True)
+    t = tgt.to(dtype)
+    y = O.acdae_forward(p, xd)
+    loss = O.mse(y, t)
+    grads = torch.autograd.grad(loss, list(p.values()) + [xd])
+    v = OrderedDict(y=_np(y), loss=_np(loss))
+    v.update(("grad:" + k, _np(g)) for k, g in zip(p, grads))
+    v["grad:input"] = _np(grads[-1])
+    return dict(vals=v)
+
+
+DANET_ZERO = (".fcn.0.bias", ".fcn.3.bias", ".fcn1.0.bias", ".fcn1.3.bias")      # biases in front of a batch-statistics BatchNorm
+
+
+def danet_states(leads):
+    """(fp64 state, its fp32 copy) as the GPU test loads them: D.init_state(99) drawn in fp64"""
+    st64 = D.init_state(99, leads=leads, dtype=torch.float64)
+    for k in st64:
+        if ".dam.fcn2." in k:
+            assert st64[k] is st64[k.replace(".dam.fcn2.", ".dam.fcn1.")]
+    st32 = OrderedDict()
+    for k, v in st64.items():
+        src = k.replace(".dam.fcn2.", ".dam.fcn1.")
+        st32[k] = st32[src] if src != k else (v.clone().float() if v.dtype.is_floating_point else v.clone())
+    return st64, st32
+
+
+def danet_param_names(st):
+    return [k for k in st if D.is_param(k) and ".dam.fcn2." not in k]
+
+
+def danet_stat_names(st):
+    return [k for k in st if k.endswith(("running_mean", "running_var"))]
+
+
+def _danet_step(case, dtype, seed):
+    """the eval forward on the initial running statistics first, then the train step: the order of the GPU test.  Besides
+    vals: `state` after the step, `params` (its leaves, each with its gradient in .grad), `x` and `tgt` in `dtype` - from
+    fresh_step they are live, for the Adam steps of tests/test_gpu_danet.py to go on from"""
+    B, L, leads = case
+    st = danet_states(leads)[0 if dtype == torch.float64 else 1]
+    x, tgt = (t.to(dtype) for t in _inputs(B, leads, L, seed))
+    with torch.no_grad():
+        ye = D.danet_forward(st, x, training=False)
+    params = OrderedDict((k, st[k].requires_grad_(True)) for k in danet_param_names(st))
+    xd = x.clone().requires_grad_(True)
+    y = D.danet_forward(st, xd, training=True)
+    loss = F.mse_loss(y, tgt)
+    *grads, dx = torch.autograd.grad(loss, list(params.values()) + [xd])
+    v = OrderedDict(y_eval=_np(ye), y=_np(y), loss=_np(loss))
+    v["grad:input"] = _np(dx)
+    for (k, p), g in zip(params.items(), grads):
+        v["grad:" + k], p.grad = _np(g), g
+    v.update((k, _np(st[k])) for k in danet_stat_names(st))
+    return dict(vals=v, state=st, params=params, x=x, tgt=tgt)
+
+
+def _newrale_step(case, dtype, seed):
+    variant, L, B = case
+    p32, pa32, x, tgt = make_newrale_case(variant, L, B, seed)
+    p = OrderedDict((k, v.to(dtype)) for k, v in p32.items())
+    pa = OrderedDict((k, v.to(dtype).requires_grad_(True)) for k, v in pa32.items())
+    bn = O.new_bn_state(8, dtype)
+    t = tgt.to(dtype)
+    y = O.newrale_forward(pa, p, x.to(dtype), variant, True, bn)
+    loss = O.mse(y, t)
+    grads = torch.autograd.grad(loss, list(pa.values()))
+    with torch.no_grad():
+        ye = O.newrale_forward(OrderedDict((k, v.detach()) for k, v in pa.items()), p, x.to(dtype), variant, False, bn)
+    v = OrderedDict(y=_np(y), loss=_np(loss), snr=_np(O.snr(t, y.detach())), rmse=_np(O.rmse(t, y.detach())))
+    v.update(("grad:" + k, _np(g)) for k, g in zip(pa, grads))
+    v["bn_mean"], v["bn_var"], v["y_eval"] = _np(bn["running_mean"]), _np(bn["running_var"]), _np(ye)
+    return dict(vals=v)
+
+
+STEPS = {"ralenet": (_ralenet_step, O), "unet": (_unet_step, O), "acdae": (_acdae_step, O), "danet": (_danet_step, D),
+         "newrale": (_newrale_step, O)}
+
+
+# ---------------------------------------------------------------------------------------------- defects for the fp32 oracle
+# Each returns a context (parity_bars.standing_in) that builds on the oracle module as it finds it - recorded, inside step() -
+# and puts back what it changed.  tests/test_baseline_bars_cpu.py holds what each does to the errors.
+def _bn_eps_unet():
+    """BatchNorm eps 1.02e-5 where 1e-5 is specified (2e-5 is above the flat bars as well: channels of small variance)"""
+    return standing_in(O, F=dict(batch_norm=lambda t, rm, rv, w, b, tr, mom, eps: F.batch_norm(t, rm, rv, w, b, tr, mom, 1.02e-5)))
+
+
+def _bn_eps_danet():
+    """BatchNorm eps 1.0015e-5 (the descriptor nets normalise over the batch: a variance of B samples)"""
+    keep = D._bn
+    return standing_in(D, _bn=lambda x, st, pre, training: keep(x, st, pre, training, eps=1.0015e-5))
+
+
+def _sigmoid_danet():
+    """every gate of DANet (APReLU alpha, the DAM's channel and spatial attention) from a sigmoid that is 3e-6 relative too
+    large: what an approximate exponential may cost"""
+    keep = D.sigmoid
+    return standing_in(D, sigmoid=lambda x: keep(x) * (1.0 + 3e-6))
+
+
+def _tap_scaled(taps, by):
+    def mutant():
+        """the middle tap of every `taps`-tap convolution times 1 + `by`"""
+        def conv1d(x, w, *a, **k):
+            if w.shape[-1] == taps:
+                w = w * (1.0 + by * (torch.arange(taps) == taps // 2)).to(w.dtype)
+            return F.conv1d(x, w, *a, **k)
+        return standing_in(O, F=dict(conv1d=conv1d))
+    return mutant
+
+
+def _upsample_weights():
+    """the 0.25 / 0.75 weights of ACDAE's linear upsample 0.249999 / 0.750001: (1 - d) * linear + d * nearest with d = 4e-6
+    (the nearest-neighbour upsample is the nearer of the two samples)"""
+    def interpolate(x, **k):
+        out = F.interpolate(x, **k)
+        return out + 4e-6 * (F.interpolate(x, scale_factor=2, mode="nearest") - out)
+    return standing_in(O, F=dict(interpolate=interpolate))
+
+
+def _stem_slope():
+    """the stem's LeakyReLU(0.2) with slope 0.2 + 1e-5"""
+    keep = O.F.leaky_relu
+    return standing_in(O, F=dict(leaky_relu=lambda x, s=0.01: keep(x, s + 1e-5 if s == 0.2 else s)))
+
+
+MUTANTS = {"unet_bn_eps": _bn_eps_unet, "danet_bn_eps": _bn_eps_danet, "danet_sigmoid": _sigmoid_danet, "acdae_tap13": _tap_scaled(13, 1e-5),
+           "acdae_upsample": _upsample_weights, "newrale_tap13": _tap_scaled(13, 1e-5), "newrale_stem_slope": _stem_slope}
+
+
+def fresh_step(net, case, dtype, seed, mutant=None, **options):
+    """The oracle step of `net` (STEPS) with every kink recorded; `mutant` names one of MUTANTS, `options` are the step's own
+    (RA-LENet: param_seed, params, gelu).  -> namespace: vals; kinks, the Kinks of the run; what else the step hands back."""
+    fn, mod = STEPS[net]
+    with recording(mod) as kinks, (MUTANTS[mutant]() if mutant else nullcontext()):
+        return SimpleNamespace(kinks=kinks, **fn(case, dtype, seed, **options))
+
+
+@functools.lru_cache(maxsize=16)
+def _cached_step(net, case, dtype, seed, mutant, options):
+    return fresh_step(net, case, dtype, seed, mutant, **dict(options))
+
+
+def step(net, case, dtype, seed, mutant=None, trace=True, eval_forward=True, **options):
+    """fresh_step, cached: shared between a test's reference and its yardstick, and read-only for every caller.  Without
+    `trace` the values leave out the `act:` keys, without `eval_forward` `y_eval`."""
+    defaults = inspect.signature(STEPS[net][0]).parameters
+    o = _cached_step(net, case, dtype, seed, mutant, tuple(sorted((k, v) for k, v in options.items() if v != defaults[k].default)))
+    if trace and eval_forward:
+        return o
+    vals = OrderedDict((k, v) for k, v in o.vals.items() if (trace or not k.startswith("act:")) and (eval_forward or k != "y_eval"))
+    return SimpleNamespace(**dict(vars(o), vals=vals))
+
+
+def parity_yardstick(variant, leads, L, B, seed=1234, params=None, eval_forward=False, trace=True, input_seeds=THREE_SEEDS):
+    """parity_bars.yardstick of an RA-LENet case, under the keys of run_parity(variant, leads, L, B, ...)'s result.
+    Precondition: the stem's LeakyReLU(0.2) is the one kink of RA-LENet, and an fp32 pre-activation on the other side of 0
+    from the fp64 one changes gradients by a discrete amount no yardstick describes - the smallest |stem pre-activation| of the
+    case (fp64) must be >= STEM_MARGIN, absolute, and on all three inputs no fp32 pre-activation may change sides."""
+    assert input_seeds[0] == 2023
+    case = (variant, leads, L, B)
+    return yardstick(lambda dtype, s: step("ralenet", case, dtype, s, None, trace, eval_forward, param_seed=seed, params=params), input_seeds,
+                     functools.partial(kink_precondition, margin=lambda: stem_margin(variant, leads, L, B, seed, params)))
+
+
+# ------------------------------------------------------------------------------------------------------- the HIP path
+# run_<net>(case, seed, device) -> (the values of step(net, case, ...), from the library; the model; ...)
+def run_ralenet(case, seed, device, trace=(), eval_forward=False, options=None, before_forward=None, params=None, param_seed=1234):
+    """-> (vals, the model, (p32, x, tgt)).  `trace`: the names of the debug tensors to return as "act:<name>", each whole, laid
+    out on the model's token slots.
+    Gradients: every parameter gradient of `backward()` (dx = NULL, the training default); then "grad:input" and the stem
+    parameter gradients "grad:<name>@dx" of `backward(want_dx=True)`, and "grad:input_frozen" of `backward_input` - the model
+    comes back with the gradient buffer that last call left."""
     from ecg_denoise_amd import RALENet, _lib
-    p32, x, tgt = make_case(variant, leads, L, B, seed)
+    variant, leads, L, B = case
+    p32, x, tgt = make_case(variant, leads, L, B, param_seed, input_seed=seed)
     if params is not None:
         p32 = params(p32)
     model = RALENet(variant, leads=leads, L=L, max_batch=B, train=True, device=device)
@@ -264,52 +383,109 @@ def run_parity(variant, leads, L, B, device="cuda:0", trace=True, seed=1234, opt
     loss, snr, rmse = model.loss_and_metrics(y, td)
     model.backward()
     torch.cuda.synchronize()
-    # fp64 oracle (x is a leaf: the input gradient comes out of the same autograd call); shared with parity_yardstick
-    o = oracle_step(variant, leads, L, B, seed, params, torch.float64)
-    p, bn, yo, tr, lo, grads, dxo = o.p, o.bn, o.y, o.tr, o.loss, o.grads, o.dx
-    res = OrderedDict()
-    res["y"] = rel(y.cpu().numpy(), yo.detach().numpy())
-    res["loss"] = abs(loss.item() - lo.item()) / abs(lo.item())
-    res["snr"] = rel(snr.cpu().numpy(), O.snr(tgt.double(), yo.detach()).numpy())
-    res["rmse"] = rel(rmse.cpu().numpy(), O.rmse(tgt.double(), yo.detach()).numpy())
     st = model.state_dict()
-    res["bn_mean"] = rel(st["conv1.2.running_mean"].cpu().numpy(), bn["running_mean"].numpy())
-    res["bn_var"] = rel(st["conv1.2.running_var"].cpu().numpy(), bn["running_var"].numpy())
-    if trace:
-        for k, v in tr.items():
-            res["act:" + k] = rel(model.debug_tensor(k).cpu().numpy()[:v.numel()], v.detach().numpy())
-    res.update(compare_grads(model.named_grads(), p, grads))
+    v = OrderedDict(y=_np(y), loss=_np(loss), snr=_np(snr), rmse=_np(rmse), bn_mean=_np(st["conv1.2.running_mean"]),
+                    bn_var=_np(st["conv1.2.running_var"]))
+    v.update(("act:" + k, _np(model.debug_tensor(k))) for k in trace)
+    v.update(grad_values(p32, [model.named_grads()[k] for k in p32]))
     # the backward pass again on the same saved forward, now with the input gradient (ral_backward zeroes the gradient buffer
     # itself): the stem kernel that formed only parameter gradients above stores dz as well - its parameter gradients are compared
     # again, as grad:<name>@dx - and k_conv1_bwd_dx turns dz into dx
     dx = model.backward(want_dx=True)
     torch.cuda.synchronize()
-    res["grad:input"] = rel(dx.cpu().numpy(), dxo.numpy())
-    stem = [k for k in p if k.startswith(("conv1.0.", "conv1.2."))]
-    again = compare_grads(model.named_grads(), OrderedDict((k, p[k]) for k in stem), [grads[list(p).index(k)] for k in stem])
-    res.update((k + "@dx", v) for k, v in again.items())
+    v["grad:input"] = _np(dx)
+    v.update(("grad:" + k + "@dx", _np(model.named_grads()[k])) for k in p32 if k.startswith(STEM))
     # the frozen-weight chain (what NewRALE training runs: no weight-gradient kernels) from the same dy
     dxf = model.backward_input(model._dy)
     torch.cuda.synchronize()
-    res["grad:input_frozen"] = rel(dxf.cpu().numpy(), dxo.numpy())
+    v["grad:input_frozen"] = _np(dxf)
     if eval_forward:
         model.eval()
-        ye = model(xd)
-        torch.cuda.synchronize()
-        res["y_eval"] = rel(ye.cpu().numpy(), o.y_eval.numpy())
+        v["y_eval"] = _np(model(xd))
         model.train()
-    return res, model, (p32, x, tgt)
+    return v, model, (p32, x, tgt)
 
 
-def make_newrale_case(variant, L, B, input_seed=2023):
-    """`make_case`'s seeds for the 12-lead adapter: inner 2-lead RA-LENet parameters (1234), adapter parameters (77), x and
-    target (B, 12, L) from generator `input_seed`"""
-    p32 = O.init_params(O.ralenet_param_shapes(variant, 2), 1234)
-    pa32 = O.init_params(O.newrale_param_shapes(), 77)
-    g = torch.Generator().manual_seed(input_seed)
-    x = torch.randn(B, 12, L, generator=g)
-    tgt = torch.randn(B, 12, L, generator=g)
-    return p32, pa32, x, tgt
+def run_parity(variant, leads, L, B, device="cuda:0", trace=True, seed=1234, options=None, eval_forward=False, before_forward=None,
+               params=None):
+    """-> (dict of errors, HIP fp32 against the fp64 oracle - parity_bars.errors of run_ralenet against step("ralenet", ...) at
+    input seed 2023; the model; (p32, x, tgt)).  `options`: {name: value} for ral_set_option on the model's handle, applied
+    before the first forward.  `params`: a callable p32 -> p32 applied to the seeded parameters (of seed `seed`) before the
+    model and the oracle see them (spread_fc1_bias).  `eval_forward`: after the train step, the eval-mode forward of the same
+    model against the oracle's eval output (its BatchNorm on the running statistics the step left) as res["y_eval"].
+    `before_forward(model)` is called once the options are set."""
+    case = (variant, leads, L, B)
+    ref = step("ralenet", case, torch.float64, 2023, None, trace, eval_forward, param_seed=seed, params=params).vals
+    acts = [k[4:] for k in ref if k.startswith("act:")]
+    mine, model, inputs = run_ralenet(case, 2023, device, acts, eval_forward, options, before_forward, params, seed)
+    mine.update((k, mine[k].ravel()[:ref[k].size]) for k in ref if k.startswith("act:"))
+    return errors(mine, ref), model, inputs
+
+
+def run_unet(case, seed, device):
+    """one train step and the eval forward after it -> (vals, the model in eval mode)"""
+    from ecg_denoise_amd import UNet
+    leads, L, B = case
+    p32 = O.init_params(O.unet_param_shapes(leads), 1234)
+    x, tgt = _inputs(B, leads, L, seed)
+    m = UNet(leads=leads, L=L, max_batch=B, device=device)
+    m.load_state_dict(p32, strict=False)
+    m.train()
+    y = m(x.to(device))
+    loss, _, _ = m.loss_and_metrics(y, tgt.to(device))
+    m.backward()
+    torch.cuda.synchronize()
+    v = OrderedDict(y=_np(y), loss=_np(loss))
+    sd = m.state_dict()
+    for k in O.UNET_BN:
+        v[k + ".running_mean"], v[k + ".running_var"] = _np(sd[k + ".running_mean"]), _np(sd[k + ".running_var"])
+    ng = m.named_grads()
+    v.update(("grad:" + k, _np(ng[k])) for k in p32)
+    m.eval()
+    v["y_eval"] = _np(m(x.to(device)))
+    return v, m
+
+
+def run_acdae(case, seed, device):
+    """one train step -> (vals, the model, x, y, snr, target)"""
+    from ecg_denoise_amd import ACDAE
+    L, B = case
+    p32 = O.init_params(O.acdae_param_shapes(), 1234)
+    x, tgt = _inputs(B, 2, L, seed)
+    m = ACDAE(L=L, max_batch=B, device=device)
+    m.load_state_dict(p32)
+    m.train()
+    y = m(x.to(device))
+    loss, snr, _ = m.loss_and_metrics(y, tgt.to(device))
+    dx = m.backward(want_dx=True)
+    torch.cuda.synchronize()
+    v = OrderedDict(y=_np(y), loss=_np(loss))
+    ng = m.named_grads()
+    v.update(("grad:" + k, _np(ng[k])) for k in p32)
+    v["grad:input"] = _np(dx)
+    return v, m, x, y, snr, tgt
+
+
+def run_danet(case, seed, device):
+    """the eval forward on the initial running statistics, then one train step -> (vals, the model in train mode, x and
+    target on the device)"""
+    from ecg_denoise_amd import DANet
+    B, L, leads = case
+    xd, td = (t.to(device) for t in _inputs(B, leads, L, seed))
+    m = DANet(L=L, max_batch=B, train=True, device=device, leads=leads)
+    m.load_state_dict(danet_states(leads)[1])
+    m.eval()
+    v = OrderedDict(y_eval=_np(m(xd)))
+    m.train()
+    y = m(xd)
+    v["y"] = _np(y)
+    loss, _, _ = m.loss_and_metrics(y, td)
+    v["loss"] = _np(loss)
+    v["grad:input"] = _np(m.backward(want_dx=True))
+    v.update(("grad:" + k, _np(g)) for k, g in m.named_grads().items())
+    sd = m.state_dict()
+    v.update((k, _np(sd[k])) for k in danet_stat_names(sd))
+    return v, m, xd, td
 
 
 def _newrale_model(variant, L, B, p32, pa32, device):
@@ -321,41 +497,31 @@ def _newrale_model(variant, L, B, p32, pa32, device):
     return m.train()
 
 
-def run_newrale_parity(variant, L, B, device="cuda:0", input_seed=2023):
-    """One train step of the 12-lead adapter around a frozen RA-LENet (HIP fp32) against the fp64 oracle -> dict of relative
-    errors: y in train mode, loss / SNR / RMSE over the 12 x L windows, the eight adapter gradients ("grad:<name>"), the inner
-    BatchNorm's running statistics after the step (quirk A16: the frozen model's BatchNorm keeps training) and the eval-mode
-    forward on those statistics."""
-    p32, pa32, x, tgt = make_newrale_case(variant, L, B, input_seed)
+def run_newrale(case, seed, device):
+    """One train step of the 12-lead adapter around a frozen RA-LENet -> (vals, the model in eval mode): y in train mode, loss /
+    SNR / RMSE over the 12 x L windows, the eight adapter gradients, the inner BatchNorm's running statistics after the step
+    (quirk A16: the frozen model's BatchNorm keeps training) and the eval-mode forward on those statistics."""
+    variant, L, B = case
+    p32, pa32, x, tgt = make_newrale_case(variant, L, B, seed)
     m = _newrale_model(variant, L, B, p32, pa32, device)
     xd, td = x.to(device), tgt.to(device)
     y = m(xd)
     loss, snr, rmse = m.loss_and_metrics(y, td)
     m.backward()
     torch.cuda.synchronize()
-    p = OrderedDict((k, v.double()) for k, v in p32.items())
-    pa = OrderedDict((k, v.double().requires_grad_(True)) for k, v in pa32.items())
-    bn = O.new_bn_state(8, torch.float64)
-    yo = O.newrale_forward(pa, p, x.double(), variant, True, bn)
-    lo = O.mse(yo, tgt.double())
-    grads = torch.autograd.grad(lo, list(pa.values()))
-    res = OrderedDict()
-    res["y"] = rel(y.cpu().numpy(), yo.detach().numpy())
-    res["loss"] = abs(loss.item() - lo.item()) / abs(lo.item())
-    res["snr"] = rel(snr.cpu().numpy(), O.snr(tgt.double(), yo.detach()).numpy())
-    res["rmse"] = rel(rmse.cpu().numpy(), O.rmse(tgt.double(), yo.detach()).numpy())
-    for (k, g), mine in zip(zip(pa, grads), m.named_grads().values()):
-        res["grad:" + k] = rel(mine.cpu().numpy(), g.numpy())
+    v = OrderedDict(y=_np(y), loss=_np(loss), snr=_np(snr), rmse=_np(rmse))
+    v.update(("grad:" + k, _np(g)) for k, g in zip(pa32, m.named_grads().values()))
     st = m.rale.state_dict()
-    res["bn_mean"] = rel(st["conv1.2.running_mean"].cpu().numpy(), bn["running_mean"].numpy())
-    res["bn_var"] = rel(st["conv1.2.running_var"].cpu().numpy(), bn["running_var"].numpy())
+    v["bn_mean"], v["bn_var"] = _np(st["conv1.2.running_mean"]), _np(st["conv1.2.running_var"])
     m.eval()
-    ye = m(xd)
-    torch.cuda.synchronize()
-    with torch.no_grad():
-        yeo = O.newrale_forward(OrderedDict((k, v.detach()) for k, v in pa.items()), p, x.double(), variant, training=False, bn=bn)
-    res["y_eval"] = rel(ye.cpu().numpy(), yeo.numpy())
-    return res
+    v["y_eval"] = _np(m(xd))
+    return v, m
+
+
+def run_newrale_parity(variant, L, B, device="cuda:0", input_seed=2023):
+    """-> dict of errors (parity_bars.errors) of run_newrale against step("newrale", ...), the fp64 oracle"""
+    case = (variant, L, B)
+    return errors(run_newrale(case, input_seed, device)[0], step("newrale", case, torch.float64, input_seed).vals)
 
 
 def run_newrale_adam(variant, L, B, steps=3, device="cuda:0"):

@@ -1,4 +1,5 @@
-"""The per-tensor bars of the baseline networks and the 12-lead adapter (tests/baseline_parity_util.py) on the CPU: the
+"""The per-tensor bars of the baseline networks and the 12-lead adapter (tests/baseline_parity_util.py: the rule of
+tests/parity_bars.py on the steps of tests/parity_util.py) on the CPU: the
 yardsticks have the keys the GPU tests compare, no bar is above the flat bar its case had, the kink precondition holds for every
 case that takes per-tensor bars (and fails where CASES says it does), and the bars reject what they are for - an fp32 oracle
 with a small defect that the flat bars let through:
@@ -22,12 +23,22 @@ import torch
 import baseline_parity_util as U
 import danet_oracle as D
 import ralenet_oracle as O
-from parity_util import STEM_MARGIN
+from parity_bars import K_FP32, STEM_MARGIN, Kinks, check, errors, flat_bars, is_zero, yardstick
+from parity_util import DANET_ZERO, step
 
 NETS = ("unet", "acdae", "danet", "newrale")
 BARRED = [(net,) + e for net in NETS for e in U.CASES[net] if e[2] is not None]
 FLAT = [(net,) + e for net in NETS for e in U.CASES[net] if e[2] is None]
 _id = lambda e: e[0] + "-" + U.case_id(e[0], e[1:])
+
+
+def kinks(net, case, dtype, seed, mutant=None):
+    return step(net, case, dtype, seed, mutant).kinks
+
+
+def fp32_errors(net, case, seed, mutant=None):
+    """errors with the fp32 oracle in the place of the HIP path; `mutant` changes the fp32 evaluation only"""
+    return errors(step(net, case, torch.float32, seed, mutant).vals, step(net, case, torch.float64, seed).vals)
 
 
 def documented_keys(net, case):
@@ -74,19 +85,19 @@ def test_the_cases_are_those_of_the_gpu_tests():
 
 @pytest.mark.parametrize("net,case,seed,seeds", BARRED, ids=map(_id, BARRED))
 def test_precondition_keys_and_bars_of_every_case_with_per_tensor_bars(net, case, seed, seeds):
-    margin, where = U.kink_margin(net, case, seed)
-    assert margin >= STEM_MARGIN, (margin, where)
-    assert all(U.same_branches(net, case, s) for s in seeds) and U.precondition(net, case, seeds)
+    k = kinks(net, case, torch.float64, seed)
+    assert k.margin >= STEM_MARGIN, (k.margin, k.where)
+    assert all(kinks(net, case, torch.float32, s).same_sides(kinks(net, case, torch.float64, s)) for s in seeds)
     bars, yard = U.case_bars(net, case, seed, seeds)
     assert list(yard) == list(bars) == documented_keys(net, case)
-    ref = U.oracle_step(net, case, torch.float64, seed).vals
+    ref = step(net, case, torch.float64, seed).vals
     (fwd, grad), zero_abs = U.caps(net, case)
     assert (fwd, zero_abs) == (1e-5, 2e-5 if net == "unet" else 1e-5)
     assert grad == (2e-3 if net == "danet" and case[0] < 8 else 1e-4)
     zero = {k for k in yard if yard[k] is None}
-    assert zero == {k for k, r in ref.items() if k.startswith("grad:") and U.is_zero(r)}
+    assert zero == {k for k, r in ref.items() if k.startswith("grad:") and is_zero(r)}
     if net == "danet":
-        assert zero == {k for k in yard if k.endswith(U.DANET_ZERO)}
+        assert zero == {k for k in yard if k.endswith(DANET_ZERO)}
     elif net == "unet":       # the convolution biases in front of a batch-statistics BatchNorm; the old test's threshold was 1e-9
         assert zero == {"grad:%s.%d.conv.bias" % (s, i) for s in ("EncList", "DecList") for i in range(4)}
         assert all(np.linalg.norm(r) >= 1e-9 for k, r in ref.items() if k.startswith("grad:") and k not in zero)
@@ -98,7 +109,7 @@ def test_precondition_keys_and_bars_of_every_case_with_per_tensor_bars(net, case
             continue
         flat = grad if k.startswith("grad:") else fwd
         assert math.isfinite(yard[k]) and yard[k] > 0 and 0 < b <= flat, (k, yard[k], b)
-        assert b >= U.K_BASE * yard[k] or b == flat, (k, yard[k], b)
+        assert b >= K_FP32 * yard[k] or b == flat, (k, yard[k], b)
     # the typical bar is well below the flat one, and few bars are the flat one (DANet's gradients behind a BatchNorm over 4 or 8
     # descriptors are the least: the fp32 oracle's median gradient error is 6e-6 .. 9e-6 at B = 8, 7e-5 at B = 4)
     gb = [b for k, b in bars.items() if k.startswith("grad:") and k not in zero]
@@ -106,15 +117,15 @@ def test_precondition_keys_and_bars_of_every_case_with_per_tensor_bars(net, case
     assert np.median(gb) < grad / (2 if net == "danet" else 10) and np.median(fb) < fwd / 4
     assert sum(b == grad for b in gb) <= max(1, len(gb) / 10) and sum(b == fwd for b in fb) <= max(1, len(fb) / 10)   # (the adapter's SNR)
     # ... and the fp32 oracle itself is within them
-    U.check(U.oracle_errors(net, case, seed), bars, yard)
+    check(fp32_errors(net, case, seed), bars, yard)
 
 
 @pytest.mark.parametrize("net,case,seed,seeds", FLAT, ids=map(_id, FLAT))
 def test_cases_that_keep_their_flat_bars_miss_the_precondition(net, case, seed, seeds):
-    margin, _ = U.kink_margin(net, case, seed)
+    margin = kinks(net, case, torch.float64, seed).margin
     assert margin < STEM_MARGIN, margin
     with pytest.raises(AssertionError):
-        U.yardstick(net, case, (seed, seed + 1, seed + 2))
+        yardstick(lambda dtype, s: step(net, case, dtype, s), (seed, seed + 1, seed + 2))
     if net != "danet":
         bars, yard = U.case_bars(net, case, seed, None)
         assert yard is None and list(bars) == documented_keys(net, case)
@@ -123,38 +134,38 @@ def test_cases_that_keep_their_flat_bars_miss_the_precondition(net, case, seed, 
 
 def test_recording_sees_every_kink_and_leaves_the_oracles_as_they_were():
     before = (D.relu, D.clamp, D.sigmoid, D._bn, D.F, O.F)
-    k = U.oracle_step("danet", (4, 64, 2), torch.float64, 4).kinks
+    k = kinks("danet", (4, 64, 2), torch.float64, 4)
     kinds = [kind for kind, _ in k.sides]
     # per forward: 8 APReLUs (2 clamps and a ReLU each), 3 DAMs (2 ReLUs and 2 max-pools each); the eval and the train forward
     assert kinds.count("clamp") == 2 * 16 and kinds.count("relu") == 2 * (8 + 6) and kinds.count("adaptive_max_pool1d") == 2 * 6
-    k = U.oracle_step("acdae", (64, 3), torch.float64, 2023).kinks
+    k = kinks("acdae", (64, 3), torch.float64, 2023)
     kinds = [kind for kind, _ in k.sides]
     assert kinds.count("max_pool1d") == 4 and kinds.count("leaky_relu") == 8
     assert k.count == 3 * (16 * 32 + 32 * 16 + 64 * 8 + 128 * 4) * 2 + 3 * (64 * 8 + 32 * 16 + 16 * 32 + 2 * 64)
-    k = U.oracle_step("unet", (2, 48, 5), torch.float64, 2024).kinks
+    k = kinks("unet", (2, 48, 5), torch.float64, 2024)
     assert [kind for kind, _ in k.sides] == ["leaky_relu"] * 18                      # 4 + 2 + 3 per forward, train and eval
-    k = U.oracle_step("newrale", ("nra", 16, 4), torch.float64, 2023).kinks
+    k = kinks("newrale", ("nra", 16, 4), torch.float64, 2023)
     assert [kind for kind, _ in k.sides] == ["leaky_relu"] * 8                       # 3 of the adapter and the stem's, twice
     assert (D.relu, D.clamp, D.sigmoid, D._bn, D.F, O.F) == before
     assert D.relu is torch.relu and D.clamp is torch.clamp and D.sigmoid is torch.sigmoid
 
 
 def test_a_kink_on_the_other_side_is_noticed():
-    a, b = U.Kinks(), U.Kinks()
+    a, b = Kinks(), Kinks()
     x = torch.tensor([[[1.0, -2.0, 3e-9, 4.0]]], dtype=torch.float64)
     a.leaky_relu(x); a.max_pool1d(x, 2); a.adaptive_max_pool1d(x, 1)
     b.leaky_relu(x); b.max_pool1d(x, 2); b.adaptive_max_pool1d(x, 1)
     assert a.same_sides(b) and a.count == 4 + 2 + 1
     assert a.margin == pytest.approx(3e-9 / math.sqrt((1 + 4 + 16) / 4)) and a.where == "leaky_relu, call 0"
-    c = U.Kinks()
+    c = Kinks()
     y = x.clone(); y[0, 0, 2] = -3e-9
     c.leaky_relu(y); c.max_pool1d(y, 2); c.adaptive_max_pool1d(y, 1)
     assert not a.same_sides(c)
-    d = U.Kinks()
+    d = Kinks()
     z = torch.tensor([[[1.0, 1.0 + 1e-9, 0.5, 4.0]]], dtype=torch.float64)          # a pool pair 1e-9 apart
     d.max_pool1d(z, 2)
     assert d.margin < 1e-9 and d.where == "max_pool1d, call 0"
-    e = U.Kinks()
+    e = Kinks()
     e.adaptive_max_pool1d(torch.tensor([[[4.0, 1.0, 4.0]]], dtype=torch.float64), 1)  # an exact tie
     assert e.margin == 0.0
 
@@ -175,12 +186,12 @@ MUTANT_CASES = [
 def test_the_bars_reject_a_small_defect_that_the_flat_bars_let_through(net, case, seed, seeds, mutant):
     assert (case, seed, seeds) in U.CASES[net]
     bars, yard = U.case_bars(net, case, seed, seeds)
-    flat = U.flat_bars(U.oracle_step(net, case, torch.float64, seed).vals, *U.caps(net, case))
-    err = U.oracle_errors(net, case, seed, mutant)
+    flat = flat_bars(step(net, case, torch.float64, seed).vals, *U.caps(net, case))
+    err = fp32_errors(net, case, seed, mutant)
     # the defect moved no activation across a kink: what is measured is its arithmetic
-    assert U.oracle_step(net, case, torch.float32, seed, mutant).kinks.same_sides(U.oracle_step(net, case, torch.float64, seed).kinks)
-    U.check(err, flat)                                                 # invisible to the flat bars
+    assert kinks(net, case, torch.float32, seed, mutant).same_sides(kinks(net, case, torch.float64, seed))
+    check(err, flat)                                                   # invisible to the flat bars
     with pytest.raises(AssertionError, match=r"tensors above their bars") as e:
-        U.check(err, bars, yard)
+        check(err, bars, yard)
     print(net, case, mutant, str(e.value).split("\n")[0], "of", len(err))
     assert "yardstick" in str(e.value) and "bar" in str(e.value)

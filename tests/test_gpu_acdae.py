@@ -2,7 +2,7 @@
 vectors: outputs, loss, every parameter gradient, the input gradient, three Adam steps.
 
 Tolerances of the train-step test (fp32 kernels against the oracle in fp64, relative L2): one bar per tensor, 4 times the error of
-that tensor in the oracle evaluated in fp32 (tests/baseline_parity_util.py: the yardstick, floored at the median of its group),
+that tensor in the oracle evaluated in fp32 (tests/parity_bars.py: the yardstick, floored at the median of its group),
 never above the flat 1e-5 (forward) and 1e-4 (gradients) every case had before.  A case gets such bars only if no LeakyReLU input
 and no MaxPool1d(2) pair is within 1e-5 of its tensor's RMS of its kink and fp32 and fp64 agree on every one (the kink
 precondition, tests/test_baseline_bars_cpu.py).  The typical yardstick is 3e-7, so the typical bar 1.2e-6 where it was 1e-4: the
@@ -25,7 +25,8 @@ import torch
 
 import baseline_parity_util as U
 import ralenet_oracle as O
-from parity_util import rel
+from parity_bars import check, errors
+from parity_util import rel, run_acdae, step
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -33,15 +34,15 @@ DEV = "cuda:0"
 
 @pytest.mark.parametrize("case,seed,seeds", U.case_params("acdae"))
 def test_acdae_train_step_matches_oracle(case, seed, seeds):
-    """Output, loss, every parameter gradient and the input gradient, each at its own bar: K_BASE x what the fp32 oracle
+    """Output, loss, every parameter gradient and the input gradient, each at its own bar: K_FP32 x what the fp32 oracle
     deviates from the fp64 one on that tensor, never above the flat 1e-5 / 1e-4 (baseline_parity_util).  (512, 4) and (1024, 2)
     have a LeakyReLU input 9.0e-6 / 4.9e-6 of its RMS from 0 at input seed 2023: they run at seeds 2025 / 2026 under
     per-tensor bars and at 2023 under the flat ones.  The per-window SNR keeps its absolute 1e-4 (it is near 0 dB here: a relative
     error says little), eval against train mode its bit equality."""
     bars, yard = U.case_bars("acdae", case, seed, seeds)
-    mine, m, x, y, snr, tgt = U.run_acdae(case, seed, DEV)
-    o = U.oracle_step("acdae", case, torch.float64, seed)
-    U.check(U.errors(mine, o.vals), bars, yard, what="ACDAE L=%d B=%d seed %d" % (case + (seed,)))
+    mine, m, x, y, snr, tgt = run_acdae(case, seed, DEV)
+    o = step("acdae", case, torch.float64, seed)
+    check(errors(mine, o.vals), bars, yard, what="ACDAE L=%d B=%d seed %d" % (case + (seed,)))
     yo = torch.from_numpy(o.vals["y"])
     np.testing.assert_allclose(snr.cpu().numpy(), O.snr(tgt.double(), yo).numpy(), rtol=0, atol=1e-4)
     m.eval()

@@ -179,10 +179,11 @@ def test_t32_forward_keeps_non_finite_values_in_their_head():
 def test_t32_whole_model_train_step_matches_oracle():
     """forward + backward of RA-LENet "full" at 4 x 1 x 512 against the fp64 oracle, at the per-tensor parity bars of
     test_gpu_parity.py (the backward reads the o and lse this forward wrote)"""
+    from parity_bars import bars, check
     from parity_util import parity_yardstick, run_parity
-    from test_gpu_parity import _check
     res, _, _ = run_parity(*MODEL_CASE, DEV, trace=False)
-    _check(res, parity_yardstick(*MODEL_CASE, trace=False), what="t32 %s leads=%d L=%d B=%d" % MODEL_CASE)
+    yard = parity_yardstick(*MODEL_CASE, trace=False)
+    check(res, bars(yard), yard, what="t32 %s leads=%d L=%d B=%d" % MODEL_CASE)
 
 
 @pytest.mark.parametrize("opts", ["attn_fwd_t32=0", "attn_fwd_t32=64"])

@@ -14,7 +14,7 @@ the oracle.  The ones the other files leave are here:
 
 Every case is a whole train step (outputs, loss, metrics, BatchNorm statistics, every block output, every parameter gradient) and
 the eval-mode forward of the same model, through parity_util.run_parity, at the bars of tests/test_gpu_parity.py: per tensor 8 times
-its error in the fp32 oracle (parity_util.parity_yardstick), never above forward 1e-5 and gradients 1e-4; the key-bias half 1e-5
+its error in the fp32 oracle (parity_bars.yardstick), never above forward 1e-5 and gradients 1e-4; the key-bias half 1e-5
 absolute.  The two `-spread` twins run the same instances with the fc1 biases a grid over [-9, 9] (parity_util.spread_fc1_bias),
 in every process their originals run in: every MLP forward and backward family - k_mlp_fwd_h, k_mlp_fwd_w, the fused strips,
 k_mlp_bwd, k_mlp_bwd_h - evaluates its GELU and the GELU's derivative across [-10, 10], not only below 3.  Before its forward a case asks ral_block_plan - same process, same switches -
@@ -53,11 +53,12 @@ import sys
 
 import pytest
 
+from parity_bars import bars, check
 from parity_util import parity_yardstick, run_parity, spread_fc1_bias
 from test_block_plan_cpu import DW, MB, MBH, MFH, MFW, QBH, QH, model_instances
-from test_gpu_parity import DEV, _check
 
 pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
 
 _DW32H = [name % "true" for name in DW[32]]
 _C32_BWD_256 = [MBH % (32, 1, 512)] + _DW32H          # (32, 64) off the fused backward: eight waves, split products
@@ -112,7 +113,8 @@ def test_block_instances_match_oracle(variant, L, B, f16_split, names, spread):
           f"y {res['y']:.2e}, y_eval {res['y_eval']:.2e}, gradient {grad[kg]:.2e} ({kg})")
     # a twin never had flat bars: 8 x each tensor's fp32-oracle error alone (its ill-conditioned query gradients are above 1e-4
     # in the fp32 oracle itself)
-    _check(res, parity_yardstick(variant, 2, L, B, params=params, eval_forward=True), capped=not spread, what=what)
+    yard = parity_yardstick(variant, 2, L, B, params=params, eval_forward=True)
+    check(res, bars(yard, capped=not spread), yard, what=what)
 
 
 @pytest.mark.parametrize("opts,ids", SWITCH_RUNS, ids=[opts for opts, _ in SWITCH_RUNS])

@@ -30,10 +30,11 @@ import torch
 import torch.nn.functional as F
 
 from ecg_denoise_amd import _lib
+from parity_bars import FWD_TOL, GRAD_TOL
 from parity_util import rel
-from test_gpu_parity import DEV, FWD_TOL, GRAD_TOL
 
 pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
 
 MODEL_PAIRS = [(12, 6, 1), (6, 2, 1), (2, 6, 1), (6, 12, 0)]
 OTHER_PAIRS = [(1, 1, 0), (12, 6, 0), (3, 5, 1)]

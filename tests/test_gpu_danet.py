@@ -3,7 +3,7 @@
 Tolerances: forward 1e-5, gradients 1e-4 relative L2 vs fp64 (2e-4 vs the reference's own fp32 numbers).
 
 The first step of test_danet_matches_fp64_oracle has one bar per tensor where the case allows it: 4 times the error of that tensor
-in the oracle evaluated in fp32 (tests/baseline_parity_util.py: the yardstick, floored at the median of its group - the gradients,
+in the oracle evaluated in fp32 (tests/parity_bars.py: the yardstick, floored at the median of its group - the gradients,
 and everything else), never above the bars above.  A case gets them only if no clamp or ReLU input and no max-pool winner is
 within 1e-5 of its tensor's RMS of its kink and fp32 and fp64 agree on every one (tests/test_baseline_bars_cpu.py); the cases of
 0.6 million kink inputs and more find no such input.  The yardsticks spread widely here - 7e-8 for a running statistic, 2e-6 for
@@ -26,11 +26,11 @@ import torch
 
 import baseline_parity_util as U
 import danet_oracle as D
-from parity_util import rel
+from parity_bars import check, errors, flat_bars, is_zero
+from parity_util import DANET_ZERO, fresh_step, rel, run_danet
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-ZERO_GRAD = (".fcn.0.bias", ".fcn.3.bias", ".fcn1.0.bias", ".fcn1.3.bias")   # biases in front of a batch-statistics BatchNorm
 
 
 def _model(st, B, L=512, train=True, leads=2):
@@ -57,7 +57,7 @@ def test_danet_matches_reference_golden(golden_dir):
     grads = m.named_grads()
     assert [k for k, _ in m.named_parameters()] == [k[5:] for k in g.files if k.startswith("grad_")]
     for k, v in grads.items():
-        if k.endswith(ZERO_GRAD):
+        if k.endswith(DANET_ZERO):
             assert v.abs().max().item() < 1e-5, k
         else:
             assert rel(v.cpu().numpy(), g["grad_" + k]) < 2e-4, k
@@ -72,53 +72,33 @@ def test_danet_matches_reference_golden(golden_dir):
 @pytest.mark.parametrize("case,seed,seeds", U.case_params("danet"))
 def test_danet_matches_fp64_oracle(case, seed, seeds):
     """The eval forward, then one train step - output, loss, input gradient, every parameter gradient, every running statistic -
-    each at its own bar: K_BASE x what the fp32 oracle deviates from the fp64 one on that tensor, never above the flat 1e-5 /
-    1e-4 (2e-3 at B < 8) - baseline_parity_util.  Then three Adam steps at the bars they had.
+    each at its own bar: K_FP32 x what the fp32 oracle deviates from the fp64 one on that tensor, never above the flat 1e-5 /
+    1e-4 (2e-3 at B < 8) - baseline_parity_util.caps.  Then three Adam steps at the bars they had.
     Flat bars stay where the kink precondition finds no input: (64, 512), (37, 256) and (16, 1024) have 0.6 to 2.2 million
     clamp, ReLU and max-pool inputs, and at none of nine seeds all of them keep 1e-5 of their RMS from the kink; (8, 512), (4, 1024)
     and (8, 256) are the long windows at batches small enough for one.  (8, 32) misses at its old seed 8 (a ReLU input at 3.8e-6): per-tensor bars at seed 10,
     the flat ones at 8."""
-    B, L, leads = case
-    st64, st32 = U.danet_states(leads)
-    gg = torch.Generator().manual_seed(seed)
-    x = torch.randn(B, leads, L, generator=gg); tgt = torch.randn(B, leads, L, generator=gg)
-    m = _model(st32, B, L, leads=leads)
-    m.eval()
-    with torch.no_grad():
-        ye = D.danet_forward(st64, x.double(), training=False)
-    mine = OrderedDict(y_eval=m(x.to(DEV)).cpu().numpy())
-    m.train()
-    xd = x.double().requires_grad_(True)
-    params = OrderedDict((k, v.requires_grad_(True)) for k, v in st64.items() if D.is_param(k) and ".dam.fcn2." not in k)
-    y64 = D.danet_forward(st64, xd, training=True)
-    loss64 = torch.nn.functional.mse_loss(y64, tgt.double())
-    loss64.backward()
-    y = m(x.to(DEV))
-    mine["y"] = y.cpu().numpy()
-    loss, _, _ = m.loss_and_metrics(y, tgt.to(DEV))
-    mine["loss"] = loss.cpu().numpy()
-    mine["grad:input"] = m.backward(want_dx=True).cpu().numpy()
-    mine.update(("grad:" + k, v.cpu().numpy()) for k, v in m.named_grads().items())
-    sd = m.state_dict()
-    mine.update((k, sd[k].cpu().numpy()) for k in U.danet_stat_names(sd))
-    ref = U.danet_vals(ye, y64, loss64, xd.grad, OrderedDict((k, v.grad) for k, v in params.items()), st64)
+    B = case[0]
     bars, yard = U.case_bars("danet", case, seed, seeds)
+    mine, m, xd, td = run_danet(case, seed, DEV)
+    o = fresh_step("danet", case, torch.float64, seed)        # (uncached: its state and leaves go on through the Adam steps)
     if seeds is None:
-        bars = U.flat_bars(ref, *U.caps("danet", case))
-    assert {k[5:] for k, r in ref.items() if k.startswith("grad:") and U.is_zero(r)} == {k for k in params if k.endswith(ZERO_GRAD)}
-    U.check(U.errors(mine, ref), bars, yard, what="DANet B=%d L=%d leads=%d seed %d" % (case + (seed,)))
+        bars = flat_bars(o.vals, *U.caps("danet", case))
+    assert {k[5:] for k, r in o.vals.items() if k.startswith("grad:") and is_zero(r)} == {k for k in o.params if k.endswith(DANET_ZERO)}
+    check(errors(mine, o.vals), bars, yard, what="DANet B=%d L=%d leads=%d seed %d" % (case + (seed,)))
     # three Adam steps stay on the oracle's trajectory
+    params = o.params
     opt = torch.optim.Adam(list(params.values()), lr=1e-3)
     for _ in range(3):
         opt.step(); opt.zero_grad(); m.step()
-        y64 = D.danet_forward(st64, x.double(), training=True)
-        torch.nn.functional.mse_loss(y64, tgt.double()).backward()
-        y = m(x.to(DEV)); m.loss_and_metrics(y, tgt.to(DEV)); m.backward()
+        y64 = D.danet_forward(o.state, o.x, training=True)
+        torch.nn.functional.mse_loss(y64, o.tgt).backward()
+        y = m(xd); m.loss_and_metrics(y, td); m.backward()
     if B < 8:
         return
     assert rel(y.cpu().numpy(), y64.detach().numpy()) < 2e-5
     for k, v in m.named_parameters():
-        if not k.endswith(ZERO_GRAD):     # (Adam turns the rounding noise of a zero gradient into +-lr steps, in both)
+        if not k.endswith(DANET_ZERO):     # (Adam turns the rounding noise of a zero gradient into +-lr steps, in both)
             assert rel(v.cpu().numpy(), params[k].detach().numpy()) < 1e-5, k
 
 
@@ -187,7 +167,7 @@ def test_danet_bench_batch_matches_fp64_oracle():
     assert np.median(e) < 2e-4 and (e > 1e-3).sum() <= 6, (np.median(e), np.sort(e)[-8:])
     assert rel(dx.numpy(), xd.grad.numpy()) < 1e-2
     for k, v in m.named_grads().items():
-        if k.endswith(ZERO_GRAD):
+        if k.endswith(DANET_ZERO):
             assert v.abs().max().item() < 1e-5, k
         else:
             assert rel(v.cpu().numpy(), params[k].grad.numpy()) < 1e-2, k

@@ -16,12 +16,12 @@ import pytest
 import torch
 
 import ralenet_oracle as O
+from parity_bars import FWD_TOL, GRAD_TOL
 from parity_util import compare_grads, make_case, make_newrale_case, rel
 from test_unet_plan_cpu import query
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-FWD_TOL, GRAD_TOL = 1e-5, 1e-4          # tests/test_gpu_parity.py
 TRAJ_RTOL = 5e-4                        # the golden Adam trajectories (test_gpu_parity.py, test_gpu_unet.py)
 SPLIT_TOL = 1e-4                        # test_split_ralenet / test_split_unet
 LOOP_LOSS_RTOL, LOOP_PARAM_TOL = 2e-5, 2e-4   # tests/test_gpu_reference_loop.py

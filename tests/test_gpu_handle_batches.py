@@ -51,13 +51,13 @@ import torch
 
 import danet_oracle as D
 import ralenet_oracle as O
-from parity_util import rel
+from parity_bars import FWD_TOL, GRAD_TOL
+from parity_util import DANET_ZERO, rel
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-FWD_TOL, GRAD_TOL, E32_MAX = 1e-5, 1e-4, 2.5e-4
+E32_MAX = 2.5e-4
 ZERO_GRAD_ABS = {"unet": 2e-5, "danet": 1e-5}
-DANET_ZERO = (".fcn.0.bias", ".fcn.3.bias", ".fcn1.0.bias", ".fcn1.3.bias")   # biases in front of a batch-statistics BatchNorm
 REFUSAL = {"ralenet": "RA-LENet backward must follow a training forward: the last forward was an eval one",
            "unet": "U-Net backward must follow a training forward: the last forward was an eval one",
            "danet": "DANet backward needs a training forward of the same batch first"}

@@ -11,8 +11,8 @@ The cases are the smallest at which each thing can still go wrong:
   ("nra", 16, 513)   k_conv13_bwd beyond its 512 workgroups (workgroup 0 takes two windows, the others one); the inner model
                      at a batch above 512
 
-Bars of the train step: one per quantity, 4 times its error in the oracle evaluated in fp32 (tests/baseline_parity_util.py: the
-yardstick, floored at the median of its group), never above the flat forward 1e-5 and gradients 1e-4 of tests/test_gpu_parity.py;
+Bars of the train step: one per quantity, 4 times its error in the oracle evaluated in fp32 (tests/parity_bars.py: the
+yardstick, floored at the median of its group), never above the flat forward 1e-5 and gradients 1e-4 of tests/parity_bars.py;
 4, since the adapter's own kernels multiply no fp16 pairs and the frozen inner model's forward sits at the fp32 oracle's error
 (tests/test_gpu_parity.py).  A case gets them only if no input of the three adapter LeakyReLUs and of the stem's is within 1e-5 of
 its tensor's RMS of 0 (tests/test_baseline_bars_cpu.py): ("nra", 64, 5) moves to input seed 2024 for that and runs at 2023 under
@@ -44,10 +44,11 @@ import pytest
 import torch
 
 import baseline_parity_util as U
+from parity_bars import FWD_TOL, GRAD_TOL, check
 from parity_util import run_newrale_adam, run_newrale_parity
-from test_gpu_parity import DEV, FWD_TOL, GRAD_TOL
 
 pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
 
 CASES = [("full", 256, 3), ("nra", 16, 4), ("full", 32, 2), ("mlp", 320, 2), ("nra", 64, 5), ("full", 1008, 1), ("nra", 16, 513)]
 ADAM_PRED_TOL, ADAM_PARAM_TOL = 2e-5, 1e-5     # tests/test_gpu_danet.py
@@ -55,7 +56,7 @@ ADAM_PRED_TOL, ADAM_PARAM_TOL = 2e-5, 1e-5     # tests/test_gpu_danet.py
 
 @pytest.mark.parametrize("case,seed,seeds", U.case_params("newrale"))
 def test_adapter_train_step_matches_oracle(case, seed, seeds):
-    """Every quantity of run_newrale_parity at its own bar: K_BASE x what the fp32 oracle deviates from the fp64 one on it, never
+    """Every quantity of run_newrale_parity at its own bar: K_FP32 x what the fp32 oracle deviates from the fp64 one on it, never
     above the flat bars (baseline_parity_util).  ("nra", 64, 5) has an adapter LeakyReLU input 8.2e-6 of its RMS from 0 at input
     seed 2023: per-tensor bars at seed 2024, the flat ones at 2023.  ("nra", 16, 513) has 361 000 LeakyReLU inputs and no seed
     among nine keeps them all 1e-5 from 0: flat bars."""
@@ -69,7 +70,7 @@ def test_adapter_train_step_matches_oracle(case, seed, seeds):
           f"gradient {grad[kg]:.2e} ({kg})")
     assert len(grad) == 8
     bars, yard = U.case_bars("newrale", case, seed, seeds)
-    U.check(res, bars, yard, what=f"adapter {variant} L={L} B={B} seed {seed}")
+    check(res, bars, yard, what=f"adapter {variant} L={L} B={B} seed {seed}")
 
 
 @pytest.mark.parametrize("variant,L,B", CASES)

@@ -2,9 +2,9 @@
 vectors generated from the reference.  Needs an MI355X: `pytest -m gpu`.
 
 Tolerances (fp32 kernels vs the oracle evaluated in fp64, relative L2): one bar per tensor, 8 times the error of that tensor in
-the oracle evaluated in fp32 (parity_util.parity_yardstick: the yardstick, floored at the median over its group - the gradients,
+the oracle evaluated in fp32 (parity_bars.yardstick: the yardstick, floored at the median over its group - the gradients,
 and everything else), and never above the flat bars forward 1e-5 (north-star bar: 1e-3), gradients 1e-4.  8 = 2^3: a product
-of fp16 pairs may be 2^-21 relative where fp32 rounds at 2^-24 (parity_util.parity_bars).  The typical yardstick is 2e-7 .. 7e-7,
+of fp16 pairs may be 2^-21 relative where fp32 rounds at 2^-24 (parity_bars.K_PAIR).  The typical yardstick is 2e-7 .. 7e-7,
 the worst 2e-6 .. 1.2e-5 (`leconv.partial_conv3.weight`, `conv1.0.bias`), so the typical gradient bar is 2e-6 .. 6e-6 where it
 was 1e-4.  The gradient bars cover the input gradient as well (parity_util.run_parity: `grad:input`, `grad:input_frozen`, the stem
 gradients `@dx`).  A quantity whose true value is zero keeps its flat absolute bar.  tests/test_parity_bars_cpu.py shows what the
@@ -42,7 +42,7 @@ The forward group sits at the fp32 oracle's own error, the median gradient at 0.
 tests/test_gpu_configs.py::test_narrow_level_mlp_forward_kernel_choices the first eight cases pass as well.  With a yardstick
 from ONE fp32 evaluation the three-element leconv.w gradients did not: 8.0 .. 11.9 under mlp_fwd_w = 0 / 1 / 2 and fuse_dw = 16
 (and 8.5 for a query gradient of the spread case with f16_split = 0) - the sample, not the kernels: the same tensor's sample
-moved from 1.1e-7 to 5.5e-7 with torch's thread count, and the strict path was above it too (parity_util.parity_yardstick)."""
+moved from 1.1e-7 to 5.5e-7 with torch's thread count, and the strict path was above it too (parity_bars.yardstick)."""
 import os
 from collections import OrderedDict
 
@@ -51,41 +51,11 @@ import pytest
 import torch
 
 import ralenet_oracle as O
-from parity_util import parity_bars, parity_yardstick, rel, run_parity, spread_fc1_bias, yardstick_floors
+from parity_bars import bars, check
+from parity_util import parity_yardstick, rel, run_parity, spread_fc1_bias
 
 pytestmark = pytest.mark.gpu
-FWD_TOL, GRAD_TOL = 1e-5, 1e-4
-K_YARD = 8.0               # an fp16-pair product: 2^-21 relative, fp32: 2^-24 (parity_util.parity_bars)
 DEV = "cuda:0"
-
-
-def yardstick_ratios(res, yard):
-    """-> per group (forward, gradients): (worst error over yardstick, its key, median error over yardstick), the yardstick of a
-    key being max(yard[key], median of yard over the group), as in parity_bars; keys without a yardstick are left out"""
-    floors = yardstick_floors(yard)
-    out = []
-    for g in (0, 1):
-        r = {k: res[k] / max(y, floors[g]) for k, y in yard.items() if y is not None and k.startswith("grad:") == bool(g)}
-        worst = max(r, key=r.get)
-        out.append((r[worst], worst, float(np.median(list(r.values())))))
-    return out
-
-
-def _check(res, yard=None, capped=True, what=""):
-    """Without a yardstick: the flat bars.  With the parity_yardstick of the case: parity_bars per tensor (capped=False for the
-    cases that never had flat bars and hold tensors ill conditioned in fp32 itself), and a line of what was observed."""
-    if yard is None:
-        bars = {k: 1e-5 if k.startswith("gradabs:") else GRAD_TOL if k.startswith("grad:") else FWD_TOL for k in res}
-    else:
-        assert list(res) == list(yard), sorted(set(res) ^ set(yard))
-        bars = parity_bars(yard, K_YARD, (FWD_TOL, GRAD_TOL), capped)
-        (fw, fk, fm), (gw, gk, gm) = yardstick_ratios(res, yard)
-        print(f"\nobserved {what}: error over yardstick: forward worst {fw:.2f} ({fk}) median {fm:.2f}, "
-              f"gradient worst {gw:.2f} ({gk}) median {gm:.2f}")
-    bad = {k: v for k, v in res.items() if not v <= bars[k]}
-    yd = {k: "none" if yard is None or yard[k] is None else "%.3e" % yard[k] for k in bad}
-    assert not bad, "\n".join(["%d tensors above their bars:" % len(bad)] + [
-        f"  {k}: error {v:.3e}, yardstick {yd[k]}, bar {bars[k]:.3e}" for k, v in bad.items()])
 
 
 PLAIN_CASES = [
@@ -107,7 +77,8 @@ SPREAD_CASES = [
 @pytest.mark.parametrize("variant,leads,L,B", PLAIN_CASES)
 def test_train_step_matches_oracle(variant, leads, L, B):
     res, _, _ = run_parity(variant, leads, L, B, DEV)
-    _check(res, parity_yardstick(variant, leads, L, B), what=f"{variant} leads={leads} L={L} B={B}")
+    yard = parity_yardstick(variant, leads, L, B)
+    check(res, bars(yard), yard, what=f"{variant} leads={leads} L={L} B={B}")
 
 
 @pytest.mark.parametrize("variant,leads,L,B,options", SPREAD_CASES)
@@ -128,7 +99,7 @@ def test_gelu_arguments_across_the_fitted_range_match_oracle(variant, leads, L, 
     trace = L % 256 == 0          # (the debug tensors of a padded length are laid out on its token slots)
     res, _, _ = run_parity(variant, leads, L, B, DEV, trace=trace, options=options, eval_forward=True, params=spread_fc1_bias)
     yard = parity_yardstick(variant, leads, L, B, params=spread_fc1_bias, eval_forward=True, trace=trace)
-    _check(res, yard, capped=False, what=f"spread {variant} leads={leads} L={L} B={B} {options or ''}")
+    check(res, bars(yard, capped=False), yard, what=f"spread {variant} leads={leads} L={L} B={B} {options or ''}")
 
 
 @pytest.mark.parametrize("variant,leads,L,B", LENGTH_CASES)
@@ -140,7 +111,8 @@ def test_window_lengths_that_are_multiples_of_16_match_oracle(variant, leads, L,
     running statistics and every parameter gradient against the fp64 oracle, as for the other lengths: 128, 320, 640 (the
     review's list), 96 / 32 / 16 (fewer than 16 tokens at the deep levels), 1008 (one tile short of 1024)."""
     res, _, _ = run_parity(variant, leads, L, B, DEV, trace=False)
-    _check(res, parity_yardstick(variant, leads, L, B, trace=False), what=f"{variant} leads={leads} L={L} B={B}")
+    yard = parity_yardstick(variant, leads, L, B, trace=False)
+    check(res, bars(yard), yard, what=f"{variant} leads={leads} L={L} B={B}")
 
 
 @pytest.mark.parametrize("variant,leads,L", [("nra", 2, 512), ("full", 2, 256), ("mlp", 2, 256), ("full", 2, 512),

@@ -22,11 +22,10 @@ import torch
 
 import ralenet_oracle as O
 import tie_util as T
-from parity_util import rel
+from parity_util import DANET_ZERO, rel
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-ZERO_GRAD = (".fcn.0.bias", ".fcn.3.bias", ".fcn1.0.bias", ".fcn1.3.bias")   # biases in front of a batch-statistics BatchNorm
 
 
 @pytest.mark.parametrize("L", T.ACDAE_LS)
@@ -75,7 +74,7 @@ def _danet_step(st64, x, tgt):
                dx=T.per_window(dx.cpu().numpy(), ref["dx"].numpy()), grads={}, zero={})
     e32 = {}
     for k, v in m.named_grads().items():
-        if k.endswith(ZERO_GRAD):
+        if k.endswith(DANET_ZERO):
             err["zero"][k] = v.abs().max().item()
         else:
             err["grads"][k] = rel(v.cpu().numpy(), ref["grads"][k].numpy())

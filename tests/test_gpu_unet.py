@@ -1,7 +1,7 @@
 """U-Net baseline (reference model/UNet.py) on the HIP path vs the oracle and the golden vectors.
 
 Tolerances of the train-step test (fp32 kernels against the oracle in fp64, relative L2): one bar per tensor, 4 times the error of
-that tensor in the oracle evaluated in fp32 (tests/baseline_parity_util.py: the yardstick, floored at the median of its group -
+that tensor in the oracle evaluated in fp32 (tests/parity_bars.py: the yardstick, floored at the median of its group -
 the gradients, and everything else), never above the flat 1e-5 (forward) and 1e-4 (gradients) every case had before.  4, not the
 8 of tests/test_gpu_parity.py: no U-Net kernel multiplies fp16 pairs.  A case gets such bars only if no LeakyReLU input is within
 1e-5 of its tensor's RMS of 0 and fp32 and fp64 agree on every sign (the kink precondition, checked in
@@ -24,7 +24,8 @@ import torch
 
 import baseline_parity_util as U
 import ralenet_oracle as O
-from parity_util import rel
+from parity_bars import check, errors
+from parity_util import rel, run_unet, step
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -56,14 +57,14 @@ def _run(leads, L, B, seed=1234):
 @pytest.mark.parametrize("case,seed,seeds", U.case_params("unet"))
 def test_unet_train_step_matches_oracle(case, seed, seeds):
     """Output, loss, the running statistics of the ten BatchNorms, every parameter gradient and the eval forward after the step,
-    each at its own bar: K_BASE x what the fp32 oracle deviates from the fp64 one on that tensor, never above the flat 1e-5
+    each at its own bar: K_FP32 x what the fp32 oracle deviates from the fp64 one on that tensor, never above the flat 1e-5
     (forward) / 1e-4 (gradients) - baseline_parity_util.  (2, 48, 5) has a LeakyReLU input 2.4e-6 of its RMS from 0 at input
     seed 2023: it runs at seed 2024 under per-tensor bars and at 2023 under the flat ones.  (2, 64, 1025) has 2.4 million
     LeakyReLU inputs and no seed among nine keeps them all 1e-5 from 0: flat bars."""
     bars, yard = U.case_bars("unet", case, seed, seeds)
-    mine, m = U.run_unet(case, seed, DEV)
-    ref = U.oracle_step("unet", case, torch.float64, seed).vals
-    U.check(U.errors(mine, ref), bars, yard, what="U-Net leads=%d L=%d B=%d seed %d" % (case + (seed,)))
+    mine, m = run_unet(case, seed, DEV)
+    ref = step("unet", case, torch.float64, seed).vals
+    check(errors(mine, ref), bars, yard, what="U-Net leads=%d L=%d B=%d seed %d" % (case + (seed,)))
     for k in O.UNET_BN:
         for s in (".running_mean", ".running_var"):
             np.testing.assert_allclose(mine[k + s], ref[k + s], rtol=1e-5, atol=1e-6)

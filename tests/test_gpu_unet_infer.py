@@ -33,10 +33,10 @@ import torch
 
 import ralenet_oracle as O
 import unet_infer_util as U
+from parity_bars import FWD_TOL
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-FWD_TOL = 1e-5
 
 _HANDLES = {}
 

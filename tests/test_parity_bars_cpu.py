@@ -1,4 +1,4 @@
-"""The per-tensor parity bars (parity_util.parity_yardstick / parity_bars, test_gpu_parity._check) on the CPU: the yardstick has
+"""The per-tensor parity bars (tests/parity_bars.py on RA-LENet's step, parity_util.parity_yardstick) on the CPU: the yardstick has
 run_parity's keys, its values are usable, no existing case gets a weaker bar, every case keeps its distance from the stem's
 LeakyReLU kink, the spread cases put GELU arguments into every part of [-10, 10] - and the bars reject what they are for:
 the fp32 oracle with a GELU that is wrong by a relative 2e-6 (3e-6 beyond |x| = 3 only), which the flat bars let through."""
@@ -12,7 +12,8 @@ import ralenet_oracle as O
 import test_gpu_attention_t32 as A
 import test_gpu_block_instances as I
 import test_gpu_parity as P
-from parity_util import (STEM_MARGIN, oracle_parity, oracle_step, parity_bars, parity_yardstick, spread_fc1_bias, stem_margin)
+from parity_bars import FWD_TOL, GRAD_TOL, K_PAIR, STEM_MARGIN, bars as parity_bars, check, errors, flat_bars, is_zero
+from parity_util import parity_yardstick, spread_fc1_bias, stem_margin, step
 
 PLAIN = ("full", 2, 256, 3)
 
@@ -32,8 +33,16 @@ _TRACE = (["a0", "x0", "blk0.out", "blk1.out", "p1", "blk2.out", "blk3.out", "p2
            "blk14.out", "blk15.out", "u1", "blk16.out", "blk17.out", "u0"])
 
 
+def fp32_errors(variant, leads, L, B, params=None, eval_forward=False, gelu=None):
+    """run_parity with the fp32 oracle in the place of the HIP path -> (errors against the fp64 oracle, the fp64 values);
+    `gelu` replaces O.gelu in the fp32 evaluation only"""
+    a, o = (step("ralenet", (variant, leads, L, B), dt, 2023, eval_forward=eval_forward, params=params, gelu=g)
+            for dt, g in ((torch.float32, gelu), (torch.float64, None)))
+    return errors(a.vals, o.vals), o.vals
+
+
 def documented_keys(variant, leads, trace, eval_forward):
-    """the keys of run_parity's result as its docstring and compare_grads state them, from the parameter names alone"""
+    """the keys of run_parity's result as its docstring and grad_values state them, from the parameter names alone"""
     keys = ["y", "loss", "snr", "rmse", "bn_mean", "bn_var"] + (["act:" + k for k in _TRACE] if trace else [])
     for k in O.ralenet_param_shapes(variant, leads):
         keys += ["grad:" + k + "[v]", "gradabs:" + k + "[k]"] if k.endswith("to_kv.bias") else ["grad:" + k]
@@ -46,10 +55,9 @@ def documented_keys(variant, leads, trace, eval_forward):
 def test_yardstick_has_the_keys_of_run_parity_and_usable_values(variant, leads, L, B, trace, eval_forward):
     yard = parity_yardstick(variant, leads, L, B, eval_forward=eval_forward, trace=trace)
     assert list(yard) == documented_keys(variant, leads, trace, eval_forward)
-    o = oracle_step(variant, leads, L, B)
-    zero = {k for k, g in zip(o.p, o.grads) if g is None or g.norm().item() <= 1e-12}
+    ref = step("ralenet", (variant, leads, L, B), torch.float64, 2023).vals
     for k, v in yard.items():
-        if k.startswith("gradabs:") or (k.startswith("grad:") and k[5:].split("@")[0] in zero):
+        if k.startswith("gradabs:") or (k.startswith("grad:") and is_zero(ref[k])):
             assert v is None, k                                  # a true zero has no relative yardstick
         else:
             assert v is not None and math.isfinite(v) and v > 0, (k, v)
@@ -61,14 +69,14 @@ def test_yardstick_has_the_keys_of_run_parity_and_usable_values(variant, leads, 
 @pytest.mark.parametrize("variant,leads,L,B", [PLAIN, ("mlp", 2, 256, 4), ("nra", 1, 16, 4), ("full", 2, 96, 2)])
 def test_no_bar_of_an_existing_case_is_above_its_flat_bar(variant, leads, L, B):
     yard = parity_yardstick(variant, leads, L, B, eval_forward=True)
-    bars = parity_bars(yard, P.K_YARD, (P.FWD_TOL, P.GRAD_TOL))
+    bars = parity_bars(yard, K_PAIR, (FWD_TOL, GRAD_TOL))
     for k, b in bars.items():
-        flat = P.GRAD_TOL if k.startswith("grad:") else P.FWD_TOL if not k.startswith("gradabs:") else 1e-5
+        flat = GRAD_TOL if k.startswith("grad:") else FWD_TOL if not k.startswith("gradabs:") else 1e-5
         assert b <= flat, (k, b)
-        assert b == flat if yard[k] is None else b >= P.K_YARD * yard[k] or b == flat, (k, b, yard[k])
+        assert b == flat if yard[k] is None else b >= K_PAIR * yard[k] or b == flat, (k, b, yard[k])
     # the bars are an order of magnitude or more below the flat ones where fp32 arithmetic is (the typical tensor)
-    assert np.median([b for k, b in bars.items() if k.startswith("grad:") and yard[k] is not None]) < P.GRAD_TOL / 10
-    assert np.median([b for k, b in bars.items() if not k.startswith(("grad:", "gradabs:"))]) <= P.FWD_TOL / 2
+    assert np.median([b for k, b in bars.items() if k.startswith("grad:") and yard[k] is not None]) < GRAD_TOL / 10
+    assert np.median([b for k, b in bars.items() if not k.startswith(("grad:", "gradabs:"))]) <= FWD_TOL / 2
 
 
 def test_bars_follow_the_rule():
@@ -101,16 +109,16 @@ def test_spread_cases_fill_the_gelu_range(variant, leads, L, B, params):
         args.append(x.detach().reshape(-1))
         return gelu(x)
 
-    o = oracle_step(variant, leads, L, B, 1234, params, torch.float64, recording)
+    o = step("ralenet", (variant, leads, L, B), torch.float64, 2023, params=params, gelu=recording).vals
     a = torch.cat(args).numpy()
     share = np.histogram(a, bins=np.arange(-10.0, 10.5, 2.0))[0] / a.size
-    print(variant, leads, L, B, "arguments %.1f .. %.1f, bins" % (a.min(), a.max()), np.round(100 * share, 1), "loss %.3f" % o.loss.item())
+    print(variant, leads, L, B, "arguments %.1f .. %.1f, bins" % (a.min(), a.max()), np.round(100 * share, 1), "loss %.3f" % o["loss"])
     assert share.min() >= 0.02, share
     assert a.min() < -10 and a.max() > 10
-    assert math.isfinite(o.loss.item()) and all(torch.isfinite(g).all() for g in o.grads if g is not None)
+    assert math.isfinite(o["loss"]) and all(np.isfinite(g).all() for k, g in o.items() if k.startswith("grad"))
     # ... where the seeded parameters alone stay below 3
     del args[:]
-    oracle_step(variant, leads, L, B, 1234, None, torch.float64, recording)
+    step("ralenet", (variant, leads, L, B), torch.float64, 2023, gelu=recording)
     assert torch.cat(args).abs().max().item() < 3.0
 
 
@@ -122,23 +130,24 @@ def _gelu_off_by(eps, beyond):
 
 def test_the_bars_reject_a_gelu_that_is_wrong_by_2e_6_and_the_flat_bars_do_not():
     yard = parity_yardstick(*PLAIN, eval_forward=True)
-    exact = oracle_parity(*PLAIN, eval_forward=True)
-    P._check(exact)
-    P._check(exact, yard)
-    mutant = oracle_parity(*PLAIN, eval_forward=True, gelu=_gelu_off_by(2e-6, -1.0))
-    P._check(mutant)                                                   # invisible to the flat bars
+    exact, ref = fp32_errors(*PLAIN, eval_forward=True)
+    check(exact, flat_bars(ref))
+    check(exact, parity_bars(yard), yard)
+    mutant, _ = fp32_errors(*PLAIN, eval_forward=True, gelu=_gelu_off_by(2e-6, -1.0))
+    check(mutant, flat_bars(ref))                                      # invisible to the flat bars
     with pytest.raises(AssertionError, match=r"tensors above their bars") as e:
-        P._check(mutant, yard)
+        check(mutant, parity_bars(yard), yard)
     assert int(str(e.value).split()[0]) > 100, str(e.value)[:200]      # (274 .. 286 of 330, by torch's thread count)
     # beyond |x| = 3 no argument of a plain case exists: nothing changes at all
-    assert oracle_parity(*PLAIN, eval_forward=True, gelu=_gelu_off_by(1e-4, 3.0)) == exact
+    assert fp32_errors(*PLAIN, eval_forward=True, gelu=_gelu_off_by(1e-4, 3.0))[0] == exact
 
 
 def test_the_bars_reject_a_gelu_that_is_wrong_by_3e_6_beyond_3_on_the_spread_case():
     yard = parity_yardstick(*PLAIN, params=spread_fc1_bias, eval_forward=True)
-    P._check(oracle_parity(*PLAIN, params=spread_fc1_bias, eval_forward=True), yard, capped=False)
-    mutant = oracle_parity(*PLAIN, params=spread_fc1_bias, eval_forward=True, gelu=_gelu_off_by(3e-6, 3.0))
+    bars = parity_bars(yard, capped=False)
+    check(fp32_errors(*PLAIN, params=spread_fc1_bias, eval_forward=True)[0], bars, yard)
+    mutant, _ = fp32_errors(*PLAIN, params=spread_fc1_bias, eval_forward=True, gelu=_gelu_off_by(3e-6, 3.0))
     with pytest.raises(AssertionError, match=r"tensors above their bars") as e:
-        P._check(mutant, yard, capped=False)
+        check(mutant, bars, yard)
     assert int(str(e.value).split()[0]) > 100, str(e.value)[:200]
     assert "yardstick" in str(e.value) and "bar" in str(e.value) and "grad:" in str(e.value)

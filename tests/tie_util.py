@@ -8,7 +8,6 @@ ECG gives such windows: a lead-off or rail-clipped stretch is exactly flat, a pa
   DANet  the DAM's AdaptiveMaxPool1d(1) over L: a window that repeats one beat attains its maximum once per period, and the
          reference sends the gradient to the first of them."""
 from collections import OrderedDict
-from contextlib import contextmanager
 
 import numpy as np
 import torch
@@ -16,6 +15,7 @@ import torch.nn.functional as F
 
 import danet_oracle as D
 import ralenet_oracle as O
+from parity_bars import standing_in
 
 ACDAE_LS = (64, 192, 256)            # the ACDAE lengths of the GPU test (test_ties_cpu.py: the kernels they launch between them)
 ACDAE_B = 6
@@ -81,25 +81,10 @@ def conv_transpose1d_by_taps(x, w, b=None, stride=1, padding=0):
     return conv1d_by_taps(z, w.flip(2).transpose(0, 1), b, 1, w.shape[2] - 1 - padding)
 
 
-class _Functional:
-    """torch.nn.functional with the convolutions by taps, and `over` on top"""
-    def __init__(self, **over):
-        self.conv1d, self.conv_transpose1d = conv1d_by_taps, conv_transpose1d_by_taps
-        self.__dict__.update(over)
-
-    def __getattr__(self, name):
-        return getattr(F, name)
-
-
-@contextmanager
-def oracle_functional(mod, **over):
-    """oracle module `mod` (ralenet_oracle, danet_oracle) on _Functional(**over) in place of torch.nn.functional"""
-    keep = mod.F
-    mod.F = _Functional(**over)
-    try:
-        yield
-    finally:
-        mod.F = keep
+def oracle_functional(mod, **attrs):
+    """oracle module `mod` (ralenet_oracle, danet_oracle) on the convolutions by taps, with `attrs` as parity_bars.standing_in's"""
+    taps = dict(conv1d=conv1d_by_taps, conv_transpose1d=conv_transpose1d_by_taps)
+    return standing_in(mod, F=dict(taps, **attrs.pop("F", {})), **attrs)
 
 
 def acdae_oracle_step(p32, x, tgt, dtype, pool=None):
@@ -113,7 +98,7 @@ def acdae_oracle_step(p32, x, tgt, dtype, pool=None):
         seen.append(t.detach())
         return (pool or F.max_pool1d)(t, k)
 
-    with oracle_functional(O, max_pool1d=rec):
+    with oracle_functional(O, F=dict(max_pool1d=rec)):
         y = O.acdae_forward(p, xd)
     loss = O.mse(y, tgt.to(dtype))
     gr = torch.autograd.grad(loss, list(p.values()) + [xd])
@@ -172,12 +157,8 @@ def danet_oracle_step(st, x, tgt):
         seen.append(t.detach())
         return keep(t, *a)
 
-    D._dam = rec
-    try:
-        with oracle_functional(D):
-            y = D.danet_forward(st, xd, training=True)
-    finally:
-        D._dam = keep
+    with oracle_functional(D, _dam=rec):
+        y = D.danet_forward(st, xd, training=True)
     loss = F.mse_loss(y, tgt.to(dtype))
     loss.backward()
     return dict(y=y.detach(), loss=loss.item(), grads=OrderedDict((k, v.grad) for k, v in params.items()), dx=xd.grad, dam=seen, state=st)
