@@ -9,10 +9,14 @@ lines (run with -s) give the lanes found, the stamp quantum, the atomics' run-to
 
 Seen on the MI355X: stamp quantum 40 ns; the (1, 0) step run twice differs by 1.0e-7 .. 1.6e-7 in the flat gradient (worst
 tensor 0.03 of its bar, dx the same bits).  Edge (i), `ev_ready`, is exercised by every block: the side stream idles until the
-event and resumes 17 .. 20 us after it.  Edge (ii), `ev_done`, is NOT covered: at dw_sets = 2 none of the 416 edges of the 12
-side-stream steps had its chain launch start within 4 quanta of the end of the dw it waits for (closest 17 us; 0.4 ms at 6 sets,
-0.6 ms at 8) - steps this small are bound by the host's launch rate.  What these tests cover of the set rotation is its index
-arithmetic and its results.
+event and resumes 17 .. 20 us after it.  Edge (ii), `ev_done`: in the steps of THIS file, enqueued eagerly, the host's launch rate
+orders the kernels - at dw_sets = 2 none of the 416 edges of the 12 side-stream steps had its chain launch start within 4 quanta of the
+end of the dw it waits for (closest 17 us; 0.4 ms at 6 sets, 0.6 ms at 8) - so what these tests cover of the set rotation is its
+index arithmetic and its results.  tests/test_gpu_stalled_schedule.py runs the same matrix with every launch enqueued behind a
+stall, where only the events order the kernels: no edge of its 456 (2, 6 and 8 sets) was violated, and the closest stood 17.4 us
+(2 sets), 18.1 us (6) and 54.8 us (8) behind the dw's end.  That is the distance of a launch behind any cross-stream event here
+(edge (i) shows 16 .. 19 us in the same timelines), so the 4-quanta count of waits stays 0 there too and is asserted nowhere; the
+table is in that file's head.
 """
 import ctypes as C
 import json

@@ -1,8 +1,10 @@
 """The timeline checker of tests/schedule_util.py on synthetic timelines: consistent ones pass, and each defect the GPU tests
-rely on it to see is reported under its own name (no GPU)."""
+rely on it to see is reported under its own name; the pure-Python helpers of tests/stall_util.py on synthetic inputs (no GPU)."""
 import pytest
+import torch
 
 import schedule_util as S
+import stall_util as ST
 
 U = 1.0 / 1024      # ms; every stamp is a multiple of it (exact in binary floating point)
 
@@ -148,3 +150,49 @@ def test_expected_sets_follows_the_test_options(monkeypatch):
     assert S.expected_sets() == 2
     monkeypatch.setenv("RAL_TEST_OPTIONS", "dw_sets=11")
     assert S.expected_sets() == 8
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# tests/stall_util.py
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("enqueue_ms,want", [(0.0, 20.0), (1.0, 20.0), (5.0, 20.0), (5.25, 21.0), (30.0, 120.0), (62.5, 250.0), (400.0, 250.0)])
+def test_stall_is_four_times_the_enqueue_time_between_floor_and_cap(enqueue_ms, want):
+    assert ST.stall_ms_for(enqueue_ms) == want
+
+
+def test_broken_premise_fails_with_its_message():
+    ST.check_premise(True, 20.0)
+    for pending in (False, None, 1):
+        with pytest.raises(AssertionError, match=r"premise failed \(case x\): the stall of 20.0 ms had ended"):
+            ST.check_premise(pending, 20.0, "case x")
+
+
+def test_stream_gaps_of_a_device_led_and_a_host_led_timeline():
+    # device-led: launches back to back on stream 0; host-led: 1 U of work every 4 U on stream 1
+    rows = [("qkv_fwd", 0, 2 * i * U, 2 * (i + 1) * U) for i in range(8)] + [("dw", 1, 4 * i * U, (4 * i + 1) * U) for i in range(5)]
+    g = ST.stream_gaps(rows)
+    assert g[0] == {"rows": 8, "busy": 1.0, "median_gap_ms": 0.0, "max_gap_ms": 0.0}
+    assert g[1]["rows"] == 5 and g[1]["busy"] == 5.0 / 17.0 and g[1]["median_gap_ms"] == 3 * U and g[1]["max_gap_ms"] == 3 * U
+    assert ST.least_busy(rows, [0]) == 1.0 and ST.least_busy(rows, [0, 1]) == 5.0 / 17.0
+    assert ST.least_busy(rows, [7]) == 1.0                          # a stream without rows
+    # issue order, not time order, pairs the rows; an overlap counts as no gap; an even number of gaps takes the middle pair
+    rows = [("dw", 3, 0.0, 4 * U), ("dw", 3, 3 * U, 5 * U), ("dw", 3, 7 * U, 8 * U)]
+    g = ST.stream_gaps(rows)[3]
+    assert g["median_gap_ms"] == U and g["max_gap_ms"] == 2 * U and g["busy"] == 7.0 / 8.0
+    assert ST.stream_gaps([("dw", 0, 1.0, 1.0)])[0]["busy"] == 1.0   # a single stamp
+    assert ST.stream_gaps([]) == {}
+
+
+def test_stream_gaps_of_the_synthetic_step():
+    rows = synth(2, 1, 2)
+    g = ST.stream_gaps(rows)
+    assert sorted(g) == [0, 1, 2, 3] and [g[s]["rows"] for s in (2, 3)] == [18, 18]
+    assert g[2]["busy"] == 1.0 and g[2]["max_gap_ms"] == 0.0         # the long dw keeps the side stream busy: the chain waits
+    assert ST.least_busy(rows, [0, 1]) < 1.0
+
+
+def test_poison_and_late_on_host_tensors():
+    f, i, u = torch.ones(3), torch.ones(3, dtype=torch.int32), torch.ones(3, dtype=torch.uint8)
+    assert torch.isnan(ST.poison(f)).all()
+    assert (ST.poison(i) == -12345).all() and (ST.poison(u) == 123).all()
+    assert torch.equal(ST.late(f, torch.arange(3.0)), torch.arange(3.0))
